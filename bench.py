@@ -11,13 +11,18 @@ rank processes its block in chunks and the voxelised clouds are all-gathered wit
 xGMI through the library's own C entry points (rplgpu_comm_*), the gather of chunk k
 overlapping the compute of chunk k + 1 on a second stream.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
-``roofline`` (dominant kernel vs the HBM roofline), ``cpu_baseline`` (the CPU oracle timed on
-this box's host cores on a bounded sample of the same buffers), ``variants`` (the same
-4096 x 32 000 shape on the other data regimes of SURVEY.md §8(d): 1 cm range noise, uniformly
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up,
+times the K steps and reports them (``roofline`` from the events around those steps and the
+committed traffic profile).  With --full the line also carries the measurements that take runs
+of their own: ``roofline`` per-launch minimum and live HBM traffic, ``cpu_baseline`` (the CPU
+oracle timed on this box's host cores on a bounded sample of the same buffers), ``variants`` (the
+same 4096 x 32 000 shape on the other data regimes of SURVEY.md §8(d): 1 cm range noise, uniformly
 random ranges, quality filter on), ``c5`` (8 sensors x 512 frames, E5 + E4, fused arena),
-``single_scan_us`` (the node's per-scan entry points at the scan sizes the reference produces)
-and ``decode`` (the step before the path, per answer type).
+``single_scan_us`` (the node's per-scan entry points at the scan sizes the reference produces),
+``decode`` (the step before the path, per answer type), the PCIe-inclusive rate and, for N > 1,
+the compute-only and exchange-only loops.
+
+--dump-outputs DIR writes what the last timed step computed as .npy files (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -151,6 +156,13 @@ def parse_args():
                     help="N > 1: every rank ends up with the whole voxelised cloud (all-gather, BASELINE "
                          "config 4) or only rank 0 does (gather to root, config 5's fused message: "
                          "rplgpu_gather_clouds_dev, one slot per link instead of one per link and direction)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (CPU baseline, reference-path kernels, data "
+                         "regimes and config 5, decode stage, per-scan table, per-launch and live-traffic "
+                         "roofline figures, PCIe-inclusive rate, N > 1 compute / exchange loops); the "
+                         "--no-* and --cpu-seconds options below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="target wall time of the CPU baseline sample (0 disables)")
     ap.add_argument("--no-laserscan", action="store_true",
@@ -169,7 +181,12 @@ def parse_args():
                     help="no GPU: N ranks over gloo move synthetic clouds through the exchange layout "
                          "of the C ABI (host entry points) and check the result; exercises the spawn "
                          "path and the rendezvous of --gpus N on a CPU-only machine")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -566,6 +583,41 @@ def single_scan_table(gpu, params_voxel, seed, cpu_seconds):
     return table
 
 
+DUMP_BYTES_MAX = 64_000_000  # --dump-outputs: all files together
+DUMP_SCANS = 512             # scans whose voxelised clouds are written in full (~22 MB on config 3)
+
+
+def dump_outputs(out_dir, seed, d_arena, d_cursor, d_start, d_np, d_st):
+    """--dump-outputs: what a caller of rplgpu_cloud_arena_dev receives from the last timed step.
+
+    n_points.npy / status.npy   per scan (float64, exact), cells_total.npy the arena cursor;
+    cloud_sample.npy            the clouds (x, y, z, intensity; float32) of a fixed, seeded sample of
+                                scans, concatenated in the order of cloud_sample_scans.npy (their scan
+                                indices), each scan's cells in the library's order.
+    The arena offsets (d_scan_start) are not written: scans lie in the arena in completion order, which
+    differs from run to run; the per-scan slices do not."""
+    import torch
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    start = d_start.cpu().numpy().astype(np.int64)
+    npts = d_np.cpu().numpy().astype(np.int64)
+    B = len(npts)
+    head = {"n_points": npts.astype(np.float64),
+            "status": d_st.cpu().numpy().astype(np.uint32).astype(np.float64),
+            "cells_total": np.array([float(d_cursor.item())], np.float64)}
+    pick = np.sort(np.random.default_rng(seed).permutation(B)[:min(B, DUMP_SCANS)])
+    # (a fixed prefix of the sample, cut where the byte budget would be exceeded)
+    budget = DUMP_BYTES_MAX - sum(a.nbytes for a in head.values()) - 8 * len(pick) - 4096
+    keep = np.cumsum(16 * npts[pick]) <= budget
+    pick = pick[: int(np.argmin(keep)) if not keep.all() else len(pick)]
+    parts = [d_arena[int(start[b]): int(start[b]) + int(npts[b])] for b in pick]
+    cloud = torch.cat(parts).cpu().numpy() if parts else np.zeros((0, 4), np.float32)
+    head["cloud_sample_scans"] = pick.astype(np.float64)
+    head["cloud_sample"] = np.ascontiguousarray(cloud, dtype=np.float32)
+    for name, arr in head.items():
+        np.save(out / f"{name}.npy", arr)
+
+
 def main():
     args = parse_args()
     if args.gpus < 1:
@@ -606,6 +658,9 @@ def main():
     # RPL_BENCH_FORCE_DIST=1: run the N > 1 code path (process group, exchange, max over ranks)
     # with a single rank — the only way to exercise it on a 1-GPU box
     use_dist = world > 1 or os.environ.get("RPL_BENCH_FORCE_DIST") == "1"
+    if use_dist and args.dump_outputs:
+        raise SystemExit("--dump-outputs writes the single-rank path's outputs; it is not available with "
+                         "--gpus N > 1 or RPL_BENCH_FORCE_DIST=1")
     if use_dist:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29511")
@@ -698,10 +753,12 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:  # (before any later leg reuses the arena and the per-scan words)
+        dump_outputs(args.dump_outputs, args.seed, d_arena, d_cursor, d_start, d_np, d_st)
 
-    # N > 1: the same K steps without the exchange, and the exchange alone
+    # N > 1 (--full): the same K steps without the exchange, and the exchange alone
     compute_only = None
-    if use_dist:
+    if use_dist and args.full:
         def timed_loop(fn):
             fence()
             t0 = time.perf_counter()
@@ -735,15 +792,16 @@ def main():
                         "note": "compute = the rank's whole block in one launch, no exchange; "
                                 "exchange_only = RCCL all-gather of the last step's clouds; "
                                 "overlapped = the timed step (chunked, two streams)"}
+    if use_dist:
         compute_only_step()  # (status / cells below refer to the plain launch)
         torch.cuda.synchronize(dev)
 
     status = int(d_st.max().item())
     cells_local = int(d_cursor.item())
 
-    # PCIe-inclusive rate (NOT `value`): the same batch handed over as a pinned host buffer
+    # PCIe-inclusive rate (NOT `value`, --full): the same batch handed over as a pinned host buffer
     h2d_ms = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             h_pin = h_nodes.pin_memory()
             d_tmp = torch.empty_like(d_nodes)
@@ -761,26 +819,29 @@ def main():
 
     # ---- dominant kernel alone: HIP events on the launch stream ---------------------------
     # back to back (the figure the roofline uses: one event pair around `reps` launches, so the
-    # gaps between an event and a launch are not counted reps times) and per launch (min)
+    # gaps between an event and a launch are not counted reps times) and per launch (min, --full)
     reps = max(args.steps, 5)
     # N = 1: the step IS the launch, so the kernel's average duration is the device time of the
-    # timed loop itself; N > 1: the step also holds the exchange, the launch is timed on its own
-    k_ms_b2b = loop_dev_ms if exch is None else \
-        timed(compute_only_step, stream, reps, lambda: torch.cuda.synchronize(dev))
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-          for _ in range(reps)]
-    for a, b in ev:
-        a.record(stream)  # the same launch as in the step (k_cloud_voxel + two tiny memsets)
-        compute_only_step()
-        b.record(stream)
-    torch.cuda.synchronize(dev)
-    k_ms = sorted(a.elapsed_time(b) for a, b in ev)
+    # timed loop itself; N > 1: the step also holds the exchange, the launch is timed on its own (--full)
+    k_ms_b2b = loop_dev_ms if exch is None else None
+    k_ms_min = None
+    if args.full:
+        if exch is not None:
+            k_ms_b2b = timed(compute_only_step, stream, reps, lambda: torch.cuda.synchronize(dev))
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+              for _ in range(reps)]
+        for a, b in ev:
+            a.record(stream)  # the same launch as in the step (k_cloud_voxel + two tiny memsets)
+            compute_only_step()
+            b.record(stream)
+        torch.cuda.synchronize(dev)
+        k_ms_min = min(a.elapsed_time(b) for a, b in ev)
     algo_bytes = 8 * B * n + 16 * cells_local  # 8 B read/sample + 16 B/cell out
-    achieved = algo_bytes / (k_ms_b2b * 1e-3) / 1e9
+    achieved = None if k_ms_b2b is None else algo_bytes / (k_ms_b2b * 1e-3) / 1e9
 
     extra = {}
     sync = lambda: torch.cuda.synchronize(dev)
-    if not args.no_laserscan:
+    if args.full and not args.no_laserscan:
         # secondary: the reference's own path (ascend + publish_scan Mode A) on a copy
         d_nodes2 = d_nodes.clone()
         d_r = torch.empty(B, n, dtype=torch.float32, device=dev)
@@ -916,7 +977,7 @@ def main():
 
     variants = None
     c5 = None
-    if not no_variants and rank == 0 and world == 1:
+    if args.full and not no_variants and rank == 0 and world == 1:
         # the other data regimes of SURVEY.md §8(d) at the SAME shape (4096 x 32 000), same kernel
         vreps = max(3, min(args.steps, 10))
         variants = {"ring_clean": {"ms": round(k_ms_b2b, 4), "gpts_s": round(B * n / k_ms_b2b / 1e6, 1),
@@ -1001,19 +1062,19 @@ def main():
         del c5b, big_arena, d_c5
 
     # (the side legs below are single-GPU properties: at N > 1 the ranks leave together)
-    if not args.no_decode and rank == 0 and world == 1:
+    if args.full and not args.no_decode and rank == 0 and world == 1:
         extra["decode"] = decode_stage(gpu, dev, stream, args.cpu_seconds)
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(batch_np, lens_np, params, args.cpu_seconds)
 
-    if rank == 0 and world == 1 and not args.no_single:
+    if args.full and rank == 0 and world == 1 and not args.no_single:
         extra["single_scan_us"] = single_scan_table(gpu, params, args.seed, args.cpu_seconds)
 
     if rank == 0:
-        traffic, traffic_src = (None, "not measured")
-        if world == 1 and not args.no_live_traffic and not args.dry_run:
+        traffic, traffic_src = (None, "not measured" if args.full else "taken with --full only")
+        if args.full and world == 1 and not args.no_live_traffic and not args.dry_run:
             traffic, traffic_src = live_traffic(args, B, n)
         if traffic is None:
             why = traffic_src
@@ -1023,6 +1084,7 @@ def main():
             else:
                 traffic_src = f"none (live measurement: {why})"
         ms_per_step = elapsed / args.steps * 1e3
+        rnd = lambda x, d: None if x is None else round(x, d)  # (figures a plain N > 1 run does not take)
         value = B_total * n / (elapsed / args.steps) / 1e6
         line = {
             "metric": "Mpoints/s raw-scan->filtered PointCloud2",
@@ -1050,20 +1112,20 @@ def main():
             "roofline": {
                 "kernel": "k_cloud_voxel",
                 "bound": "hbm",
-                "achieved": round(achieved, 1),
+                "achieved": rnd(achieved, 1),
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "frac_read": round(8 * B * n / (k_ms_b2b * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                "frac_of_copy_rate": round(achieved / HBM_COPY_GBS, 4),
+                "frac": rnd(achieved and achieved / HBM_PEAK_GBS, 4),
+                "frac_read": rnd(k_ms_b2b and 8 * B * n / (k_ms_b2b * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                "frac_of_copy_rate": rnd(achieved and achieved / HBM_COPY_GBS, 4),
                 "traffic": traffic,
                 "traffic_source": traffic_src,
-                "kernel_ms_avg": round(k_ms_b2b, 4),
-                "kernel_ms_min": round(k_ms[0], 4),
+                "kernel_ms_avg": rnd(k_ms_b2b, 4),
+                "kernel_ms_min": rnd(k_ms_min, 4),
                 "kernel_ms_note": "avg = HIP events on the launch stream around the K timed steps "
                                   "themselves (N = 1: a step is the launch + two 8-byte memsets; N > 1: "
                                   "the launch alone, back to back); min = best single launch bracketed "
-                                  "by its own events",
+                                  "by its own events (launches of their own, as N > 1's avg: --full only)",
                 "algorithmic_bytes": algo_bytes,
                 "note": "priced against HBM as SURVEY 8(d) asks; the kernel is not HBM bound (traffic = 1.02 x the "
                         "algorithmic bytes).  Per scan and CU 62.6 k cycles: the streaming phase 41.6 k — a wave needs "

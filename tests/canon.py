@@ -4,6 +4,7 @@ oracle tests and the GPU parity tests, so that all three compare the same thing.
 from __future__ import annotations
 
 import hashlib
+from pathlib import Path
 
 import numpy as np
 
@@ -84,3 +85,50 @@ def check_large_golden(g, name, nodes, ascend_fn, laserscan_fn):
                     assert digest(ci).tobytes() == g[tag + "__intens_sha"].tobytes(), tag
                 checked += 1
     return checked
+
+
+# ---- live cross-checks against the genuine reference, with or without it -------------------
+LIVE_GOLDEN = Path(__file__).resolve().parent / "golden" / "live_golden.npz"
+
+
+def out_digest(*parts) -> np.ndarray:
+    """SHA-256 over several outputs of one call (arrays, bytes, ints, lists of ints), uint8[32]."""
+    h = hashlib.sha256()
+    for p in parts:
+        if isinstance(p, (bytes, bytearray)):
+            b = bytes(p)
+        elif isinstance(p, (int, np.integer, list, tuple)):
+            b = np.asarray(p, np.int64).tobytes()
+        else:
+            b = np.ascontiguousarray(p).tobytes()
+        h.update(len(b).to_bytes(8, "little"))
+        h.update(b)
+    return np.frombuffer(h.digest(), np.uint8).copy()
+
+
+class Genuine:
+    """The genuine reference's side of a live cross-check.  Where oracle/_ref is built, every call
+    goes to the reference libraries themselves (``live``); elsewhere the oracle's outputs are
+    compared with the digests recorded from those libraries on the same seeded inputs
+    (tests/golden/live_golden.npz, written by tests/golden/make_live_golden.py)."""
+
+    def __init__(self, key: str, live):
+        self.key, self.live, self.seen = key, live, []
+        self.want = None if live is not None else np.load(LIVE_GOLDEN)[key]
+
+    def check(self, ours, theirs, ctx=None):
+        """``ours``: the oracle's outputs of one call (a tuple); ``theirs(live)``: the same call
+        to the reference libraries, outputs in the same form."""
+        d = out_digest(*ours)
+        if self.live is not None:
+            t = out_digest(*theirs(self.live))
+        else:
+            i = len(self.seen)
+            assert i < len(self.want), (self.key, "more calls than recorded", ctx)
+            t = self.want[i]
+        assert d.tobytes() == t.tobytes(), (self.key, ctx)
+        self.seen.append(t)
+
+    def done(self):
+        if self.live is None:
+            assert len(self.seen) == len(self.want), (self.key, len(self.seen), len(self.want))

@@ -30,7 +30,7 @@ def _run_worker(world, port):
 
 def _run_bench(world, port):
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
-           "--scans", "512", "--cpu-seconds", "0", "--no-laserscan", "--no-variants", "--no-decode",
+           "--full", "--scans", "512", "--cpu-seconds", "0", "--no-laserscan", "--no-variants", "--no-decode",
            "--no-single"]
     env = _env(port)
     if world == 1:

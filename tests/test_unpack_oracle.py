@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from rplidar_ros2_driver_amd import capsules as cp
-from tests import oracle_lib
+from tests import canon, oracle_lib
 
 GOLD = Path(__file__).resolve().parent / "golden" / "unpack_golden.npz"
 ALL_ANS = (0x81, 0x82, 0x83, 0x84, 0x85, 0x86)
@@ -92,11 +92,24 @@ def test_segment_rules(oracle):
     assert list(so["dist_mm_q2"]) == [3, 5, 6, 7, 8, 11]
 
 
-@pytest.mark.parametrize("ans", ALL_ANS)
-def test_unpack_matches_genuine_live(oracle, ans):
+def _listed(nodes, marks, *rest):
+    """(nodes, [reset / offset marks as ints], rest...): the same form from the oracle and the reference"""
+    return (nodes, [int(v) for v in marks], *rest)
+
+
+def _genuine_unpack(key):
+    """canon.Genuine over the reference unpackers.  The genuine dense decoder keeps a process-wide
+    static (`dense_last` follows it); the recorded digests were taken with each test in a fresh
+    process, so without the live libraries the test starts from that state."""
     ref = oracle_lib.load_ref_unpack()
     if ref is None:
-        pytest.skip("oracle/_ref/libunpackref.so not built (no /root/reference here)")
+        test_unpack_matches_genuine_live.dense_last = 0
+    return canon.Genuine(key, ref)
+
+
+@pytest.mark.parametrize("ans", ALL_ANS)
+def test_unpack_matches_genuine_live(oracle, ans):
+    g = _genuine_unpack(f"unpack_{ans:#04x}")
     total = 0
     for seed in range(8):
         for corrupt in (False, True):
@@ -104,19 +117,18 @@ def test_unpack_matches_genuine_live(oracle, ans):
             dur = [125, 125, 32, 20, 2, 500, 1000000, 1][seed]
             data = cp.make_stream(ans, 50 if ans != 0x81 else 600, 100 + seed, corrupt=corrupt,
                                   payload="random" if seed % 2 else "ring", frames_per_rev=fpr)
-            # (the genuine dense decoder keeps a process-wide static: `dense_last` follows it)
-            r_nodes, r_rst, r_err = ref.unpack(ans, data, dur, chunk=[0, 1, 7, 84, 1000, 33, 5, 2][seed])
+            chunk = [0, 1, 7, 84, 1000, 33, 5, 2][seed]
             last = test_unpack_matches_genuine_live.dense_last if ans == 0x85 else 0
             o_nodes, o_rst, o_err, st = oracle.unpack(ans, data, dur, state=(last, 0))
             if ans == 0x85:
                 test_unpack_matches_genuine_live.dense_last = st[0]
-            assert o_nodes.tobytes() == r_nodes.tobytes(), (seed, corrupt)
-            assert list(o_rst) == list(r_rst) and o_err == r_err
+            g.check(_listed(o_nodes, o_rst, o_err), lambda ref: _listed(*ref.unpack(ans, data, dur, chunk=chunk)),
+                    (seed, corrupt))
             so, offs = oracle.segment(o_nodes, o_rst, 64)
-            rso, roffs = ref.segment(o_nodes, o_rst, 64)
-            assert so.tobytes() == rso.tobytes() and list(offs) == list(roffs)
-            total += len(r_nodes)
+            g.check(_listed(so, offs), lambda ref: _listed(*ref.segment(o_nodes, o_rst, 64)), (seed, corrupt))
+            total += len(o_nodes)
     assert total > 1000
+    g.done()
 
 
 test_unpack_matches_genuine_live.dense_last = 0
@@ -125,9 +137,7 @@ test_unpack_matches_genuine_live.dense_last = 0
 def test_unpack_fuzz_vs_genuine_live(oracle):
     """Random lengths, heavy fault rates and pure byte soup through the oracle's restatement and
     through the GENUINE SDK unpackers + ScanDataHolder (fed in random chunk sizes)."""
-    ref = oracle_lib.load_ref_unpack()
-    if ref is None:
-        pytest.skip("oracle/_ref/libunpackref.so not built (no /root/reference here)")
+    g = _genuine_unpack("unpack_fuzz")
     rng = np.random.default_rng(4242)
     for t in range(240):
         ans = ALL_ANS[t % len(ALL_ANS)]
@@ -148,15 +158,13 @@ def test_unpack_fuzz_vs_genuine_live(oracle):
         else:
             data = rng.integers(0, 256, int(rng.integers(0, 3000)), dtype=np.uint8)
         chunk = int(rng.choice([0, 1, 7, 84, 1000, 33]))
-        r_nodes, r_rst, r_err = ref.unpack(ans, data, dur, chunk=chunk)
         last = test_unpack_matches_genuine_live.dense_last if ans == 0x85 else 0
         o_nodes, o_rst, o_err, st = oracle.unpack(ans, data, dur, state=(last, 0))
         if ans == 0x85:
             test_unpack_matches_genuine_live.dense_last = st[0]
         ctx = (t, hex(ans), nf, mode, chunk)
-        assert o_nodes.tobytes() == r_nodes.tobytes(), ctx
-        assert list(o_rst) == list(r_rst) and o_err == r_err, ctx
+        g.check(_listed(o_nodes, o_rst, o_err), lambda ref: _listed(*ref.unpack(ans, data, dur, chunk=chunk)), ctx)
         mc = int(rng.choice([64, 8192, 5]))
         so, offs = oracle.segment(o_nodes, o_rst, mc)
-        rso, roffs = ref.segment(o_nodes, o_rst, mc)
-        assert so.tobytes() == rso.tobytes() and list(offs) == list(roffs), ctx
+        g.check(_listed(so, offs), lambda ref: _listed(*ref.segment(o_nodes, o_rst, mc)), ctx)
+    g.done()

@@ -3,7 +3,7 @@
 # both exchange modes; the gathered cloud must be the rank's own cloud whatever the chunking
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; O=$R/gpurun_out/${1:-exchange_chunks}; mkdir -p $O; export RPL_SYNTH_CACHE=/tmp/rplc
 for x in allgather gather; do for c in 1 2 4 8; do
-  RPL_BENCH_FORCE_DIST=1 timeout 300 python bench.py --steps 20 --no-variants --no-decode --no-single --no-laserscan --cpu-seconds 0 --exchange $x --chunks $c > $O/bench_${x}_$c.json 2> $O/bench_${x}_$c.err; rc=$?
+  RPL_BENCH_FORCE_DIST=1 timeout 300 python bench.py --full --steps 20 --no-variants --no-decode --no-single --no-laserscan --cpu-seconds 0 --exchange $x --chunks $c > $O/bench_${x}_$c.json 2> $O/bench_${x}_$c.err; rc=$?
   python - <<P
 import json
 try:

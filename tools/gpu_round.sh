@@ -14,7 +14,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.log
   tail -3 $OUT/pytest_gpu.log
 fi
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 echo "bench rc=$?"; cat $OUT/bench.json; tail -3 $OUT/bench.err
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   bash tools/prof.sh $TAG > /dev/null 2>&1
