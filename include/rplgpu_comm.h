@@ -137,6 +137,70 @@ int32_t rplgpu_unpack_gathered_xyi_dev(rplgpu_handle_t h, const float *d_slots_a
                                        uint64_t *d_scan_start_all, uint32_t *d_n_points_all,
                                        uint32_t *d_status);
 
+/* ---- the cell exchange: one fused voxel grid across GPUs ------------------------------------
+ * A finished centroid carries no count, so two ranks' centroids of the same cell cannot be merged
+ * back into the single-grid result.  A CELL RECORD carries what the voxel kernel holds in front of
+ * its divide: exact integers, so adding the records of several ranks is exact and order-free, and
+ * the merged grid is byte-identical to rplgpu_cloud_fused_voxel_dev over all of the group's scans
+ * (E5, de-skew, time offsets and pose are per scan: splitting a group's scans over ranks changes
+ * none of them).  32 bytes, little-endian: */
+typedef struct {
+  uint32_t key;      /* (iy + 32768) << 16 | (ix + 32768): ascending key == (iy, ix) order */
+  uint32_t count;    /* samples in the cell */
+  uint32_t isum;     /* sum of intensities */
+  uint32_t reserved; /* 0 */
+  double sx, sy;     /* sums of x and y in units of 2^-K m, K = 23 - ilogb(voxel_leaf) (28 at 5 cm):
+                        integers, |.| < 2^53 — the kernel's own fixed-point values (x * 2^K exactly
+                        for |x| >= 2^(23-K) m, i.e. 3.125 cm at a 5 cm leaf) */
+} rplgpu_cell_t;
+/* A cell's point (the rule the voxel kernel applies, and the merge below):
+ *   x = (float)(RN(sx / count) * 2^-K),  y likewise,  z = 0,  intensity = (float)RN(isum / count)
+ * with RN the correctly rounded fp64 quotient.
+ *
+ * Per step (INTEGRATION.md "One GPU per sensor, one fused grid"):
+ *   every rank   rplgpu_cloud_fused_cells_dev -> rplgpu_pack_cloud_meta_dev (counts in CELLS, one
+ *                entry per group) -> rplgpu_gather_cells_dev
+ *   root         rplgpu_comm_fence -> rplgpu_merge_cells_dev -> rplgpu_fused_cloud_msg_dev / ... */
+
+/* rplgpu_cloud_fused_voxel_dev (include/rplgpu_msg.h, E8) writing ONE rplgpu_cell_t per occupied
+ * cell of each group, in key order, instead of the cell's point.  Same group / d_motion / d_pose2d,
+ * time offsets (rplgpu_set_scan_time_offsets_dev), ROR mode (rplgpu_set_ror_mode), status bits and
+ * argument checks.  Arena semantics as there, in RECORDS: groups in completion order, group g's
+ * records at d_cells + d_group_start[g], d_n_cells[g] of them, *d_cursor = all records; a group that
+ * outgrows cells_capacity is cut and flagged RPLGPU_SCAN_OUT_TRUNCATED.  The optional cell-key
+ * output (rplgpu_set_cell_key_output) is not written: the record holds the key. */
+int32_t rplgpu_cloud_fused_cells_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes,
+                                     uint32_t n_stride, const uint32_t *d_n_per_scan, uint32_t B,
+                                     uint32_t group, const rplgpu_params_t *p,
+                                     const float *d_motion, const float *d_pose2d,
+                                     rplgpu_cell_t *d_cells, uint64_t cells_capacity,
+                                     uint64_t *d_cursor, uint64_t *d_group_start,
+                                     uint32_t *d_n_cells, uint32_t *d_status);
+/* rplgpu_gather_clouds_dev for 32-byte slots: rank r's slot of `slot_cells` records lands at
+ * d_cells_all + r * slot_cells on `root`, its META block (rplgpu_pack_cloud_meta_dev over the
+ * outputs above, slot_points = slot_cells) at d_meta_all + r * meta_words.  Same streams, fences
+ * and in-place rule. */
+int32_t rplgpu_gather_cells_dev(rplgpu_handle_t h, int32_t root, const rplgpu_cell_t *d_cells_local,
+                                uint64_t slot_cells, const uint32_t *d_meta_local,
+                                uint32_t meta_words, rplgpu_cell_t *d_cells_all,
+                                uint32_t *d_meta_all);
+/* Gathered cell slots (rank-major, as behind rplgpu_gather_cells_dev) -> the fused grid, outputs
+ * exactly those of rplgpu_cloud_fused_voxel_dev: 16-byte points (x, y, 0, intensity) in d_arena,
+ * d_group_start[g], d_n_points[g], d_status[g] (optional) for g < n_groups, *d_cursor = all points.
+ * Output group g is the union of every rank's group g (a rank with fewer groups contributes
+ * nothing); records of equal keys are summed (count, isum in u32, sx, sy in fp64: exact); cells
+ * come out in key order by the rule above, K from p->voxel_leaf (nothing else of *p is used).
+ * d_status[g] = RPLGPU_SCAN_OUT_TRUNCATED when a rank that holds group g flagged its slot as cut
+ * (META flag bit 0: the META block does not say which of its groups lost cells) or when the arena
+ * is too small (never written past arena_capacity).  Groups in completion order.  Runs on the main
+ * stream (rplgpu_comm_fence first behind a gather); no communicator needed, world <= 256.  The
+ * handle owns a scratch of world x slot_cells words (grown on first need, then kept). */
+int32_t rplgpu_merge_cells_dev(rplgpu_handle_t h, const rplgpu_cell_t *d_cells_all,
+                               uint64_t slot_cells, const uint32_t *d_meta_all, uint32_t meta_words,
+                               uint32_t world, uint32_t n_groups, const rplgpu_params_t *p,
+                               float *d_arena, uint64_t arena_capacity, uint64_t *d_cursor,
+                               uint64_t *d_group_start, uint32_t *d_n_points, uint32_t *d_status);
+
 /* ---- host twins of the layout functions ------------------------------------------------------
  * The same rules as the device kernels (one source: csrc/rpl_comm_layout.hpp), plain host loops,
  * no device and no handle: for transports other than RCCL and for world-size > 1 tests without
@@ -152,6 +216,13 @@ int32_t rplgpu_unpack_gathered_host(const float *points_all, uint64_t slot_point
                                     uint32_t meta_words, uint32_t world, uint32_t max_scans,
                                     float *packed, uint64_t *total, uint64_t *scan_start_all,
                                     uint32_t *n_points_all, uint32_t *status);
+/* rplgpu_merge_cells_dev as host loops (same rules, same checks, one source for the shared parts:
+ * csrc/rpl_cells.hpp); groups in order g = 0, 1, ... */
+int32_t rplgpu_merge_cells_host(const rplgpu_cell_t *cells_all, uint64_t slot_cells,
+                                const uint32_t *meta_all, uint32_t meta_words, uint32_t world,
+                                uint32_t n_groups, const rplgpu_params_t *p, float *arena,
+                                uint64_t arena_capacity, uint64_t *cursor, uint64_t *group_start,
+                                uint32_t *n_points, uint32_t *status);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,11 @@ assert NODE_DTYPE.itemsize == 8
 
 MAX_SAMPLES_PER_SCAN = 32768
 
+# == rplgpu_cell_t (include/rplgpu_comm.h): one voxel cell before the divide, the cell exchange's record
+CELL_DTYPE = np.dtype([("key", "<u4"), ("count", "<u4"), ("isum", "<u4"), ("reserved", "<u4"),
+                       ("sx", "<f8"), ("sy", "<f8")])
+assert CELL_DTYPE.itemsize == 32
+
 OK = 0
 ERR_INVALID_ARG = -1
 ERR_NO_DEVICE = -2
@@ -96,6 +101,10 @@ ABI_SYMBOLS = [
     "rplgpu_pack_cloud_meta_dev",
     "rplgpu_allgather_clouds_dev",
     "rplgpu_gather_clouds_dev",
+    "rplgpu_cloud_fused_cells_dev",
+    "rplgpu_gather_cells_dev",
+    "rplgpu_merge_cells_dev",
+    "rplgpu_merge_cells_host",
     "rplgpu_comm_fence",
     "rplgpu_comm_fence_lag",
     "rplgpu_unpack_gathered_dev",
@@ -299,6 +308,13 @@ def load_library() -> C.CDLL:
     lib.rplgpu_pack_cloud_meta_host.argtypes = [u64, vp, vp, u32, u64, u32, vp]
     lib.rplgpu_pack_cloud_xyi_host.argtypes = [vp, u64, u64, vp]
     lib.rplgpu_unpack_gathered_host.argtypes = [vp, u64, u32, vp, u32, u32, u32, vp, vp, vp, vp, vp]
+    lib.rplgpu_cloud_fused_cells_dev.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp, vp,
+                                                 u64, vp, vp, vp, vp]
+    lib.rplgpu_gather_cells_dev.argtypes = [vp, i32, vp, u64, vp, u32, vp, vp]
+    lib.rplgpu_merge_cells_dev.argtypes = [vp, vp, u64, vp, u32, u32, u32, C.POINTER(Params), vp, u64, vp,
+                                           vp, vp, vp]
+    lib.rplgpu_merge_cells_host.argtypes = [vp, u64, vp, u32, u32, u32, C.POINTER(Params), vp, u64, vp, vp,
+                                            vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -535,6 +551,15 @@ class RplGpu:
             self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d,
             d_arena, arena_capacity, d_cursor, d_group_start, d_n_points, d_status))
 
+    def cloud_fused_cells_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int,
+                              params: Params, d_motion: int, d_pose2d: int, d_cells: int,
+                              cells_capacity: int, d_cursor: int, d_group_start: int, d_n_cells: int,
+                              d_status: int = 0):
+        """cloud_fused_voxel_dev writing one CELL_DTYPE record per occupied cell (key order) per group."""
+        self._check(self._lib.rplgpu_cloud_fused_cells_dev(
+            self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d,
+            d_cells, cells_capacity, d_cursor, d_group_start, d_n_cells, d_status))
+
     def set_voxel_aggregation(self, mode: int = 0):
         """0 = auto (from the previous batch launch's statistics), 1 = plain, 2 = two-class
         (include/rplgpu.h RPLGPU_VOXEL_AGG_*).  Results are identical in every mode."""
@@ -612,6 +637,20 @@ class RplGpu:
         self._check(self._lib.rplgpu_gather_clouds_dev(
             self._h, root, d_points_local, slot_points, point_floats, d_meta_local, meta_words,
             d_points_all, d_meta_all))
+
+    def gather_cells_dev(self, root: int, d_cells_local: int, slot_cells: int, d_meta_local: int,
+                         meta_words: int, d_cells_all: int = 0, d_meta_all: int = 0):
+        """gather_clouds_dev for slots of 32-byte cell records."""
+        self._check(self._lib.rplgpu_gather_cells_dev(
+            self._h, root, d_cells_local, slot_cells, d_meta_local, meta_words, d_cells_all, d_meta_all))
+
+    def merge_cells_dev(self, d_cells_all: int, slot_cells: int, d_meta_all: int, meta_words: int,
+                        world: int, n_groups: int, params: Params, d_arena: int, arena_capacity: int,
+                        d_cursor: int, d_group_start: int, d_n_points: int, d_status: int = 0):
+        """Gathered cell slots -> one fused grid per group (the outputs of cloud_fused_voxel_dev)."""
+        self._check(self._lib.rplgpu_merge_cells_dev(
+            self._h, d_cells_all, slot_cells, d_meta_all, meta_words, world, n_groups, C.byref(params),
+            d_arena, arena_capacity, d_cursor, d_group_start, d_n_points, d_status))
 
     def allgather_clouds_xyi_dev(self, d_slot_local: int, slot_points: int, d_meta_local: int,
                                  meta_words: int, d_slots_all: int, d_meta_all: int):
@@ -825,3 +864,28 @@ def unpack_gathered_host(points_all: np.ndarray, slot_points: int, meta_all: np.
     if rc:
         raise RplGpuError(rc, "rplgpu_unpack_gathered_host")
     return packed[: int(total[0])], starts, npts, status
+
+
+def merge_cells_host(cells_all: np.ndarray, slot_cells: int, meta_all: np.ndarray, world: int,
+                     n_groups: int, params: Params, arena_capacity: int | None = None):
+    """Gathered cell slots ((world, slot_cells) CELL_DTYPE) + META blocks ((world, words) uint32) ->
+    (arena (arena_capacity, 4) float32, cursor, group_start (n_groups,) uint64, n_points (n_groups,)
+    uint32, status (n_groups,) uint32), by the library's own rules (rplgpu_merge_cells_host)."""
+    lib = load_library()
+    cells = np.ascontiguousarray(cells_all, CELL_DTYPE).reshape(-1)
+    meta = np.ascontiguousarray(meta_all, np.uint32).reshape(world, -1)
+    if cells.size < world * int(slot_cells):
+        raise ValueError("cells_all holds fewer than world x slot_cells records")
+    cap = int(world * int(slot_cells) if arena_capacity is None else arena_capacity)
+    arena = np.zeros((max(cap, 1), 4), np.float32)
+    cursor = np.zeros(1, np.uint64)
+    starts = np.zeros(max(n_groups, 1), np.uint64)
+    npts = np.zeros(max(n_groups, 1), np.uint32)
+    status = np.zeros(max(n_groups, 1), np.uint32)
+    rc = lib.rplgpu_merge_cells_host(cells.ctypes.data, int(slot_cells), meta.ctypes.data,
+                                     int(meta.shape[1]), int(world), int(n_groups), C.byref(params),
+                                     arena.ctypes.data, cap, cursor.ctypes.data, starts.ctypes.data,
+                                     npts.ctypes.data, status.ctypes.data)
+    if rc:
+        raise RplGpuError(rc, "rplgpu_merge_cells_host")
+    return arena[:cap], int(cursor[0]), starts[:n_groups], npts[:n_groups], status[:n_groups]

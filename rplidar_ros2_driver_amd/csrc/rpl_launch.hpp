@@ -72,8 +72,9 @@ hipError_t launch_cloud_voxel(hipStream_t s, const void *nodes, uint32_t n_strid
                               // (vx, vy, wz, dt) and planar pose (r00 r01 tx r10 r11 ty), optional
                               uint32_t group = 1, const float *motion = nullptr,
                               const float *pose2d = nullptr,
-                              // the arena holds 12-byte points (x, y, intensity): the exchange payload
-                              bool arena_xyi = false,
+                              // what the arena holds: 0 = 16-byte points, 1 = 12-byte points (x, y,
+                              // intensity: the exchange payload), 2 = 32-byte cell records (rplgpu_cell_t)
+                              int arena_form = 0,
                               // E5 (round 6): 1 = inside the pass (arena launches, validated divides; items it
                               // cannot settle go on T.redo), 2 = the items of T.redo with `keepmask`
                               int ror_mode = 0);
@@ -118,6 +119,14 @@ hipError_t launch_unpack_gathered(hipStream_t s, const float *points_all,
                                   float *packed, unsigned long long *total,
                                   unsigned long long *scan_start_all, uint32_t *n_points_all,
                                   uint32_t *status, uint32_t n_cu, bool xyi = false);
+// rpl_cells.hip: gathered cell records (rplgpu_cell_t) -> one fused grid per group; `unit` = 2^-K,
+// `scratch` = world x slot_cells words (see rplgpu_merge_cells_dev)
+hipError_t launch_merge_cells(hipStream_t s, const void *cells_all, unsigned long long slot_cells,
+                              const uint32_t *meta_all, uint32_t meta_words, uint32_t world,
+                              uint32_t n_groups, double unit, float *arena,
+                              unsigned long long capacity, unsigned long long *cursor,
+                              unsigned long long *group_start, uint32_t *n_points, uint32_t *status,
+                              uint32_t *scratch, uint32_t n_cu);
 hipError_t launch_pack_xyi(hipStream_t s, const float *arena, const unsigned long long *cursor,
                            unsigned long long slot_points, float *slot, uint32_t n_cu);
 

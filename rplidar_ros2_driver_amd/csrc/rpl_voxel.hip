@@ -493,6 +493,10 @@ struct VoxelArena {
   // 1: the arena holds 12-byte points (x, y, intensity) — the exchange payload of
   // include/rplgpu_comm.h written by the kernel itself (z is 0 for every point of this path).
   // `base` then only serves as the origin of point indices: point j is the floats 3 j .. 3 j + 2.
+  // 2: the arena holds 32-byte cell records (rplgpu_cell_t, include/rplgpu_comm.h: key, count,
+  // intensity sum and the fixed-point coordinate sums in front of the divide), record j at byte
+  // 32 j; `capacity` counts records.  A scan of several bands then counts before it writes
+  // (kEmitCountOnly / kEmitArenaKnown): the temporary cell area holds 16-byte points only.
   int xyi;
 };
 // kEmitArenaTemp (round 3): a scan of several bands writes its cells to the workgroup's temporary
@@ -521,10 +525,14 @@ struct PhaseClock {
 // ------------------------------------------------------------------------------
 // Phase R for one key band: the queue of run records in LDS -> output cells in (iy, ix) order.
 // `normalised`: the records already hold run sums (they came from the record store).
+// CELLS: the instance may write cell records (VoxelArena::xyi == 2).  Only the instances that are not
+// the plain one (SPLIT, or E5 inside: RORM != 0) have the branch; rplgpu_cloud_fused_cells_dev launches
+// those alone, so the code of the headline instance k_cloud_voxel<true, true, false, false, 0> — its
+// registers and spills — stays what it was.
 // Returns 0 = done (ncell written to *ncell_out), 1 = the band must be bisected (too many rows;
 // the record array is untouched in that case).
 // ------------------------------------------------------------------------------
-template <bool DBG>
+template <bool DBG, bool CELLS>
 __device__ __forceinline__ uint32_t voxel_reduce(VoxelLds &L, const KParams &p,
                                                  float4 *__restrict__ out, uint32_t out_stride,
                                                  uint32_t b, uint32_t *ncell_out, int mode,
@@ -772,7 +780,14 @@ __device__ __forceinline__ uint32_t voxel_reduce(VoxelLds &L, const KParams &p,
       qx = fma(fma(-qx, dc, Sx), rc, qx);
       qy = fma(fma(-qy, dc, Sy), rc, qy);
       qi = fma(fma(-qi, dc, si), rc, qi);
-      if (arena.xyi && (mode == kEmitArenaFirst || mode == kEmitArenaKnown)) {
+      if (CELLS && arena.xyi == 2) {  // the cell records (only kEmitArenaFirst / kEmitArenaKnown get here)
+        const size_t j = (size_t)((out - arena.base) + out_base + c);
+        uint4 *rec = reinterpret_cast<uint4 *>(arena.base) + 2u * j;
+        const unsigned long long bx = (unsigned long long)__double_as_longlong(Sx);
+        const unsigned long long by = (unsigned long long)__double_as_longlong(Sy);
+        rec[0] = make_uint4(key, cnt, isum, 0u);
+        rec[1] = make_uint4((uint32_t)bx, (uint32_t)(bx >> 32), (uint32_t)by, (uint32_t)(by >> 32));
+      } else if (arena.xyi && (mode == kEmitArenaFirst || mode == kEmitArenaKnown)) {
         float *f = reinterpret_cast<float *>(arena.base) + 3u * (size_t)((out - arena.base) + out_base + c);
         f[0] = (float)(qx * inv_scale);
         f[1] = (float)(qy * inv_scale);
@@ -1201,7 +1216,7 @@ __device__ __forceinline__ void voxel_stream_dispatch(QueueSink &sink, const KPa
 // an item whose scans hold more unsettled samples than the kernel resolves itself, the item then goes
 // on T.redo (count word, then the item numbers) and nothing of it is published here; 2 = the items
 // of that list (their E5 masks made by k_ror_mask in between), B read from the list's count word.
-template <bool DBG, int RORM = 0, class FirstBand>
+template <bool DBG, int RORM = 0, bool CELLS = false, class FirstBand>
 __device__ __forceinline__ void voxel_work_loop(VoxelLds &L, const KParams &p, const Tables &T,
                                                 uint4 *__restrict__ G, float4 *__restrict__ xyzi,
                                                 uint32_t out_stride, uint32_t *__restrict__ n_points,
@@ -1489,7 +1504,7 @@ __device__ __forceinline__ void voxel_work_loop(VoxelLds &L, const KParams &p, c
     };
     auto leave_single_band_mode = [&]() {  // block-uniform
       if (emit_mode != kEmitArenaFirst) return;
-      if (p.cell_keys) {
+      if (p.cell_keys || (CELLS && arena.xyi == 2)) {
         emit_mode = kEmitCountOnly;
       } else {
         emit_mode = kEmitArenaTemp;
@@ -1518,7 +1533,7 @@ __device__ __forceinline__ void voxel_work_loop(VoxelLds &L, const KParams &p, c
     } else if (emit_mode != kEmitLegacy) {
       out_limit = 0xFFFFFFFFu;  // (first band: bounded inside, at the reservation)
     }
-    if (voxel_reduce<DBG>(L, p, out, out_limit, b, &ncell, emit_mode, arena, from_store,
+    if (voxel_reduce<DBG, CELLS>(L, p, out, out_limit, b, &ncell, emit_mode, arena, from_store,
                           arena.base ? arena.base : xyzi)) {
       if (!from_store) {  // the LDS queue spans too many rows: cut bands from the record store
         for (uint32_t i = threadIdx.x; i < n_all; i += kVB) G[i] = L.rec[i];
@@ -1676,7 +1691,7 @@ __global__ __launch_bounds__(kVB) __attribute__((amdgpu_waves_per_eu(kVB * kVWG 
     }
     return false;
   };
-  voxel_work_loop<DBG, RORM>(L, p, T, G, xyzi, out_stride, n_points, status, B, 0u, arena, phase_s);
+  voxel_work_loop<DBG, RORM, SPLIT || RORM != 0>(L, p, T, G, xyzi, out_stride, n_points, status, B, 0u, arena, phase_s);
 }
 
 // ------------------------------------------------------------------------------
@@ -1723,10 +1738,12 @@ hipError_t launch_cloud_voxel(hipStream_t s, const void *nodes, uint32_t n_strid
                               uint32_t *status, float *arena, unsigned long long arena_capacity,
                               unsigned long long *arena_cursor, unsigned long long *scan_start,
                               uint32_t group, const float *motion, const float *pose2d,
-                              bool arena_xyi, int ror_mode) {
+                              int arena_form, int ror_mode) {
   if (B == 0) return hipSuccess;
   if (ror_mode && (!p.fast_div || !T.redo || p.dbg)) return hipErrorInvalidValue;
   if (ror_mode == 2 && !keepmask) return hipErrorInvalidValue;
+  // the cell records exist in the two-class and E5-inside instances only (voxel_reduce, CELLS)
+  if (arena_form == 2 && !ror_mode && (p.dbg || !T.voxel_split)) return hipErrorInvalidValue;
   if (group == 0) group = 1;
   group = std::min(group, B);  // (a group larger than the batch is the whole batch)
   const uint32_t n_scans = B;
@@ -1739,7 +1756,7 @@ hipError_t launch_cloud_voxel(hipStream_t s, const void *nodes, uint32_t n_strid
   ar.cursor = arena_cursor;
   ar.capacity = arena_capacity;
   ar.scan_start = scan_start;
-  ar.xyi = (arena && arena_xyi) ? 1 : 0;
+  ar.xyi = arena ? arena_form : 0;
   if (kVWG == 2 && group > 1) return hipErrorInvalidValue;  // (fused groups: 16-wave geometry only)
   // persistent workgroups of the handle's device (no more than the handle owns record stores
   // for); the item queue is cleared by a memset ahead of every launch (an aborted launch can

@@ -23,6 +23,7 @@
 #include "rpl_launch.hpp"
 #include "rpl_msg.hpp"
 #include "rpl_comm_layout.hpp"
+#include "rpl_cells.hpp"
 
 // which batch the voxel queue statistics in pinned memory describe (voxel_split_for)
 struct VoxelBatchId {
@@ -85,6 +86,8 @@ struct rplgpu_ctx {
   bool dec_stage = true;              // RPLGPU_DEC_STAGE=0: the plain decoder only (tests / A-B runs)
   uint32_t vstore_wgs = 0;
   uint32_t vstore_recs = 0;           // records per workgroup (grows with the largest E8 group seen)
+  uint32_t *d_merge = nullptr;        // rplgpu_merge_cells_dev scratch (world x slot_cells words, grown on demand)
+  size_t merge_cap = 0;               // (words)
   unsigned char *d_dec = nullptr;     // rplgpu_decode_stream staging (grown on demand, kept)
   size_t dec_cap = 0;
   unsigned char *d_scans = nullptr;   // rplgpu_decode_scans_dev scratch (node streams, sync lists)
@@ -332,6 +335,7 @@ void free_ctx(rplgpu_ctx *c) {
   if (c->d_scans) (void)hipFree(c->d_scans);
   if (c->d_dec_todo) (void)hipFree(c->d_dec_todo);
   if (c->d_vstore) (void)hipFree(c->d_vstore);
+  if (c->d_merge) (void)hipFree(c->d_merge);
   if (c->h_vstats) (void)hipHostFree(c->h_vstats);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -846,14 +850,14 @@ static int32_t voxel_with_ror(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, u
                               const rpl::Tables &T, uint32_t *d_n_points, uint32_t *d_status,
                               float *d_arena, uint64_t arena_capacity, uint64_t *d_cursor,
                               uint64_t *d_start, uint32_t group, const float *d_motion,
-                              const float *d_pose2d, bool xyi, float *d_xyzi = nullptr,
+                              const float *d_pose2d, int form, float *d_xyzi = nullptr,
                               uint32_t out_stride = 0, bool defer_listed = false) {
   RPL_HIP(h, hipMemsetAsync(h->d_redo, 0, 4, h->stream));
   RPL_HIP(h, rpl::launch_cloud_voxel(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, nullptr,
                                      kMaskStride, d_xyzi, out_stride, d_n_points, d_status, d_arena,
                                      arena_capacity, reinterpret_cast<unsigned long long *>(d_cursor),
                                      reinterpret_cast<unsigned long long *>(d_start), group, d_motion,
-                                     d_pose2d, xyi, 1));
+                                     d_pose2d, form, 1));
   if (defer_listed) return RPLGPU_OK;
   RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
                                   kMaskStride, true, std::max(1u, std::min(group, B))));
@@ -861,7 +865,7 @@ static int32_t voxel_with_ror(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, u
                                      kMaskStride, d_xyzi, out_stride, d_n_points, d_status, d_arena,
                                      arena_capacity, reinterpret_cast<unsigned long long *>(d_cursor),
                                      reinterpret_cast<unsigned long long *>(d_start), group, d_motion,
-                                     d_pose2d, xyi, 2));
+                                     d_pose2d, form, 2));
   return RPLGPU_OK;
 }
 
@@ -887,13 +891,13 @@ static int32_t cloud_arena_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes,
   T_arena.voxel_split = voxel_split_for(h, d_nodes, n_stride, B, 1u) ? 1 : 0;
   if (ror_inside)
     return voxel_with_ror(h, d_nodes, n_stride, d_n_per_scan, B, kp, T_arena, d_n_points, d_status, d_arena,
-                          arena_capacity, d_cursor, d_scan_start, 1u, nullptr, nullptr, xyi);
+                          arena_capacity, d_cursor, d_scan_start, 1u, nullptr, nullptr, xyi ? 1 : 0);
   RPL_HIP(h, rpl::launch_cloud_voxel(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp,
                                      T_arena, mask, kMaskStride, nullptr, 0, d_n_points,
                                      d_status, d_arena, arena_capacity,
                                      reinterpret_cast<unsigned long long *>(d_cursor),
                                      reinterpret_cast<unsigned long long *>(d_scan_start), 1u, nullptr,
-                                     nullptr, xyi));
+                                     nullptr, xyi ? 1 : 0));
   return RPLGPU_OK;
 }
 
@@ -914,19 +918,20 @@ int32_t rplgpu_cloud_arena_xyi_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nod
                           d_scan_start, d_n_points, d_status, true);
 }
 
-int32_t rplgpu_cloud_fused_voxel_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes,
-                                     uint32_t n_stride, const uint32_t *d_n_per_scan, uint32_t B,
-                                     uint32_t group, const rplgpu_params_t *p,
-                                     const float *d_motion, const float *d_pose2d, float *d_arena,
-                                     uint64_t arena_capacity, uint64_t *d_cursor,
-                                     uint64_t *d_group_start, uint32_t *d_n_points,
-                                     uint32_t *d_status) {
+// E8 (rplgpu_cloud_fused_voxel_dev) and its cell-record form (rplgpu_cloud_fused_cells_dev, include/rplgpu_comm.h):
+// `cells` = the arena holds rplgpu_cell_t records, capacity in records
+static int32_t fused_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                          const uint32_t *d_n_per_scan, uint32_t B, uint32_t group,
+                          const rplgpu_params_t *p, const float *d_motion, const float *d_pose2d,
+                          float *d_arena, uint64_t arena_capacity, uint64_t *d_cursor,
+                          uint64_t *d_group_start, uint32_t *d_n_points, uint32_t *d_status,
+                          bool cells) {
   int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
   if (rc) return rc;
   if (!p || !d_arena || !d_cursor || !d_group_start || !d_n_points || group == 0)
     return RPLGPU_ERR_INVALID_ARG;
   if (!p->voxel_enable) {
-    h->err = "rplgpu_cloud_fused_voxel_dev needs voxel_enable";
+    h->err = cells ? "rplgpu_cloud_fused_cells_dev needs voxel_enable" : "rplgpu_cloud_fused_voxel_dev needs voxel_enable";
     return RPLGPU_ERR_INVALID_ARG;
   }
   if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
@@ -961,19 +966,50 @@ int32_t rplgpu_cloud_fused_voxel_dev(rplgpu_handle_t h, const rplgpu_node_t *d_n
   const uint32_t *mask = nullptr;
   bool ror_inside = false;
   if ((rc = prepare_cloud(h, d_nodes, n_stride, d_n_per_scan, B, p, &kp, &mask, &ror_inside))) return rc;
+  if (cells) {  // the record holds the key (no cell-key words); the instrumented instance has no cell form
+    kp.cell_keys = nullptr;
+    kp.dbg = nullptr;
+  }
   RPL_HIP(h, hipMemsetAsync(d_cursor, 0, 8, h->stream));
   rpl::Tables T_fused = tables_of(h);
   T_fused.voxel_split = voxel_split_for(h, d_nodes, n_stride, B, group) ? 1 : 0;
+  const int form = cells ? 2 : 0;
   if (ror_inside)
     return voxel_with_ror(h, d_nodes, n_stride, d_n_per_scan, B, kp, T_fused, d_n_points, d_status, d_arena,
-                          arena_capacity, d_cursor, d_group_start, group, d_motion, d_pose2d, false);
+                          arena_capacity, d_cursor, d_group_start, group, d_motion, d_pose2d, form);
+  // (the cell form lives in the instances other than the plain one, csrc/rpl_voxel.hip voxel_reduce:
+  // without E5 inside, the records come from the two-class instance, whose results are the same)
+  if (cells) T_fused.voxel_split = 1;
   RPL_HIP(h, rpl::launch_cloud_voxel(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp,
                                      T_fused, mask, kMaskStride, nullptr, 0, d_n_points,
                                      d_status, d_arena, arena_capacity,
                                      reinterpret_cast<unsigned long long *>(d_cursor),
                                      reinterpret_cast<unsigned long long *>(d_group_start), group,
-                                     d_motion, d_pose2d));
+                                     d_motion, d_pose2d, form));
   return RPLGPU_OK;
+}
+
+int32_t rplgpu_cloud_fused_voxel_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes,
+                                     uint32_t n_stride, const uint32_t *d_n_per_scan, uint32_t B,
+                                     uint32_t group, const rplgpu_params_t *p,
+                                     const float *d_motion, const float *d_pose2d, float *d_arena,
+                                     uint64_t arena_capacity, uint64_t *d_cursor,
+                                     uint64_t *d_group_start, uint32_t *d_n_points,
+                                     uint32_t *d_status) {
+  return fused_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, d_arena,
+                    arena_capacity, d_cursor, d_group_start, d_n_points, d_status, false);
+}
+
+int32_t rplgpu_cloud_fused_cells_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes,
+                                     uint32_t n_stride, const uint32_t *d_n_per_scan, uint32_t B,
+                                     uint32_t group, const rplgpu_params_t *p,
+                                     const float *d_motion, const float *d_pose2d,
+                                     rplgpu_cell_t *d_cells, uint64_t cells_capacity,
+                                     uint64_t *d_cursor, uint64_t *d_group_start,
+                                     uint32_t *d_n_cells, uint32_t *d_status) {
+  return fused_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d,
+                    reinterpret_cast<float *>(d_cells), cells_capacity, d_cursor, d_group_start, d_n_cells,
+                    d_status, true);
 }
 
 // `defer_listed`: see voxel_with_ror (single-scan callers; d_status must be given then)
@@ -2188,12 +2224,38 @@ int32_t allgather_slots(rplgpu_handle_t h, const float *d_points_local, uint64_t
 }
 }  // namespace
 
+namespace {
+// grouped ncclSend / ncclRecv of slots of `slot_floats` 32-bit words (points or cell records) and META
+// blocks to `root` (rplgpu_gather_clouds_dev, rplgpu_gather_cells_dev)
+int32_t gather_slots(rplgpu_handle_t h, int32_t root, const float *d_points_local, size_t slot_floats,
+                     const uint32_t *d_meta_local, uint32_t meta_words, float *d_points_all,
+                     uint32_t *d_meta_all);
+}  // namespace
+
 int32_t rplgpu_gather_clouds_dev(rplgpu_handle_t h, int32_t root, const float *d_points_local,
                                  uint64_t slot_points, uint32_t point_floats,
                                  const uint32_t *d_meta_local, uint32_t meta_words,
                                  float *d_points_all, uint32_t *d_meta_all) {
   if (!h || !d_points_local || !d_meta_local || meta_words == 0 || (point_floats != 3u && point_floats != 4u))
     return RPLGPU_ERR_INVALID_ARG;
+  return gather_slots(h, root, d_points_local, (size_t)slot_points * point_floats, d_meta_local,
+                      meta_words, d_points_all, d_meta_all);
+}
+
+int32_t rplgpu_gather_cells_dev(rplgpu_handle_t h, int32_t root, const rplgpu_cell_t *d_cells_local,
+                                uint64_t slot_cells, const uint32_t *d_meta_local,
+                                uint32_t meta_words, rplgpu_cell_t *d_cells_all,
+                                uint32_t *d_meta_all) {
+  if (!h || !d_cells_local || !d_meta_local || meta_words == 0) return RPLGPU_ERR_INVALID_ARG;
+  constexpr size_t kWords = sizeof(rplgpu_cell_t) / 4u;
+  return gather_slots(h, root, reinterpret_cast<const float *>(d_cells_local), (size_t)slot_cells * kWords,
+                      d_meta_local, meta_words, reinterpret_cast<float *>(d_cells_all), d_meta_all);
+}
+
+namespace {
+int32_t gather_slots(rplgpu_handle_t h, int32_t root, const float *d_points_local, size_t slot_floats,
+                     const uint32_t *d_meta_local, uint32_t meta_words, float *d_points_all,
+                     uint32_t *d_meta_all) {
   if (!h->comm) {
     h->err = "rplgpu_comm_init has not been called";
     return RPLGPU_ERR_INVALID_ARG;
@@ -2213,7 +2275,6 @@ int32_t rplgpu_gather_clouds_dev(rplgpu_handle_t h, int32_t root, const float *d
   RPL_HIP(h, hipSetDevice(h->device));
   RPL_HIP(h, hipEventRecord(h->ev_main, h->stream));
   RPL_HIP(h, hipStreamWaitEvent(h->xstream, h->ev_main, 0));
-  const size_t slot_floats = (size_t)slot_points * point_floats;
   int rs = 0;
   hipError_t hs = hipSuccess;
   const int g0 = rccl().GroupStart();
@@ -2249,6 +2310,7 @@ int32_t rplgpu_gather_clouds_dev(rplgpu_handle_t h, int32_t root, const float *d
   RPL_HIP(h, hs);
   return RPLGPU_OK;
 }
+}  // namespace
 
 int32_t rplgpu_comm_fence_lag(rplgpu_handle_t h, uint32_t lag) {
   if (!h || lag > 3u) return RPLGPU_ERR_INVALID_ARG;
@@ -2315,6 +2377,57 @@ int32_t rplgpu_pack_cloud_xyi_dev(rplgpu_handle_t h, const float *d_arena, const
   return RPLGPU_OK;
 }
 
+// argument checks shared by rplgpu_merge_cells_dev and its host twin
+static bool merge_args_ok(const void *cells_all, const uint32_t *meta_all, uint32_t meta_words,
+                          uint32_t world, uint32_t n_groups, const rplgpu_params_t *p, const float *arena,
+                          const uint64_t *cursor, const uint64_t *group_start, const uint32_t *n_points) {
+  return cells_all && meta_all && p && arena && cursor && group_start && n_points && world >= 1u &&
+         world <= rpl::cells::kMaxWorld && n_groups <= (1u << 24) &&
+         meta_words >= rplgpu_cloud_meta_words(n_groups) && p->voxel_leaf >= 1e-6f &&
+         p->voxel_leaf <= 1024.0f;
+}
+
+int32_t rplgpu_merge_cells_dev(rplgpu_handle_t h, const rplgpu_cell_t *d_cells_all,
+                               uint64_t slot_cells, const uint32_t *d_meta_all, uint32_t meta_words,
+                               uint32_t world, uint32_t n_groups, const rplgpu_params_t *p,
+                               float *d_arena, uint64_t arena_capacity, uint64_t *d_cursor,
+                               uint64_t *d_group_start, uint32_t *d_n_points, uint32_t *d_status) {
+  if (!h || !merge_args_ok(d_cells_all, d_meta_all, meta_words, world, n_groups, p, d_arena, d_cursor,
+                           d_group_start, d_n_points))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!device_readable(h, d_cells_all, "d_cells_all") || !device_readable(h, d_meta_all, "d_meta_all") ||
+      !device_readable(h, d_arena, "d_arena") || !device_readable(h, d_cursor, "d_cursor"))
+    return RPLGPU_ERR_INVALID_ARG;
+  // a group's records of all ranks are indexed by 31 bits (the leader prefixes), and the scratch
+  // holds one word per record of the gathered buffer
+  if (slot_cells > (0x7FFFFFFFull / world)) {
+    h->err = "rplgpu_merge_cells_dev: world x slot_cells above 2^31 records";
+    return RPLGPU_ERR_CAPACITY;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  const size_t need = (size_t)world * slot_cells;
+  if (need > h->merge_cap) {  // grows (only ever grows) on the first call with larger slots
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    void *bigger = nullptr;
+    if (hipMalloc(&bigger, need * 4u) != hipSuccess) {
+      h->err = "merge scratch allocation failed";
+      (void)hipGetLastError();
+      return RPLGPU_ERR_HIP;
+    }
+    if (h->d_merge) (void)hipFree(h->d_merge);
+    h->d_merge = static_cast<uint32_t *>(bigger);
+    h->merge_cap = need;
+  }
+  const double unit = 1.0 / to_kparams(*p).vox_scale;
+  RPL_HIP(h, hipMemsetAsync(d_cursor, 0, 8, h->stream));
+  RPL_HIP(h, rpl::launch_merge_cells(h->stream, d_cells_all, slot_cells, d_meta_all, meta_words, world,
+                                     n_groups, unit, d_arena, arena_capacity,
+                                     reinterpret_cast<unsigned long long *>(d_cursor),
+                                     reinterpret_cast<unsigned long long *>(d_group_start), d_n_points,
+                                     d_status, h->d_merge, h->n_cu));
+  return RPLGPU_OK;
+}
+
 /* Host twins of the layout kernels: the same rules (rpl_comm_layout.hpp), plain loops, no device —
  * what a world-size-2 test over a CPU transport (gloo) drives. */
 int32_t rplgpu_pack_cloud_meta_host(uint64_t cursor, const uint64_t *scan_start,
@@ -2370,6 +2483,65 @@ int32_t rplgpu_unpack_gathered_host(const float *points_all, uint64_t slot_point
       }
     }
   }
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_merge_cells_host(const rplgpu_cell_t *cells_all, uint64_t slot_cells,
+                                const uint32_t *meta_all, uint32_t meta_words, uint32_t world,
+                                uint32_t n_groups, const rplgpu_params_t *p, float *arena,
+                                uint64_t arena_capacity, uint64_t *cursor, uint64_t *group_start,
+                                uint32_t *n_points, uint32_t *status) {
+  if (!merge_args_ok(cells_all, meta_all, meta_words, world, n_groups, p, arena, cursor, group_start,
+                     n_points) ||
+      slot_cells > (0x7FFFFFFFull / world))
+    return RPLGPU_ERR_INVALID_ARG;
+  const double unit = 1.0 / to_kparams(*p).vox_scale;
+  std::vector<unsigned long long> first(world), n(world), at(world);
+  unsigned long long total = 0ull;
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    bool cut = false;
+    for (uint32_t r = 0; r < world; ++r) {
+      const uint32_t *m = meta_all + (size_t)r * meta_words;
+      unsigned long long st;
+      rpl::cells::group_extent(m, g, n_groups, slot_cells, &st, &n[r]);
+      first[r] = (unsigned long long)r * slot_cells + st;
+      at[r] = 0ull;
+      cut = cut || rpl::cells::group_cut(m, g);
+    }
+    // k-way merge of the ranks' sorted lists: the smallest key left, summed over every rank holding it
+    const unsigned long long start = total;
+    unsigned long long cells = 0ull;
+    while (true) {
+      uint32_t key = 0xFFFFFFFFu;
+      bool any = false;
+      for (uint32_t r = 0; r < world; ++r)
+        if (at[r] < n[r] && (!any || cells_all[first[r] + at[r]].key < key)) {
+          key = cells_all[first[r] + at[r]].key;
+          any = true;
+        }
+      if (!any) break;
+      uint32_t cnt = 0u, isum = 0u;
+      double sx = 0.0, sy = 0.0;
+      for (uint32_t r = 0; r < world; ++r) {
+        if (at[r] < n[r] && cells_all[first[r] + at[r]].key == key) {
+          const rplgpu_cell_t &c = cells_all[first[r] + at[r]++];
+          cnt += c.count;
+          isum += c.isum;
+          sx += c.sx;
+          sy += c.sy;
+        }
+      }
+      const unsigned long long o = start + cells++;
+      if (o < arena_capacity) rpl::cells::cell_point(cnt, isum, sx, sy, unit, arena + 4u * o);
+    }
+    const unsigned long long room = start >= arena_capacity ? 0ull : arena_capacity - start;
+    const uint32_t kept = (uint32_t)std::min(cells, room);
+    group_start[g] = start;
+    n_points[g] = kept;
+    if (status) status[g] = (cut || kept < cells) ? RPLGPU_SCAN_OUT_TRUNCATED : 0u;
+    total += cells;
+  }
+  *cursor = total;
   return RPLGPU_OK;
 }
 
