@@ -235,6 +235,57 @@ int32_t rplgpu_fused_cloud_msg_dev(rplgpu_handle_t h, const float *d_arena,
                                    const char *frame_id, rplgpu_stamp_t stamp, uint8_t *d_msg,
                                    uint64_t msg_capacity, uint64_t *d_msg_len, uint32_t *d_status);
 
+/* ---- E9: several sensors -> ONE LaserScan in the common frame (row 4, the scan merger) ---------
+ * What Nav2 costmaps, AMCL and slam_toolbox read: a virtual scan of `count` beams over
+ * [angle_min, angle_max) that keeps, per beam, the nearest return of every sensor of a time step.
+ *   inc = (float)(((double)angle_max - (double)angle_min) / (double)count)   (Mode A's :634, any span)
+ * A spec is refused (RPLGPU_ERR_INVALID_ARG) when a value is not finite, count is 0 or above
+ * RPLGPU_MAX_MERGE_BEAMS, inc <= 0 or inc > (float)(pi / 2), angle_max - angle_min (fp64) > 2 pi (1 + 2^-20),
+ * or !(0 <= range_min < range_max). */
+#define RPLGPU_MAX_MERGE_BEAMS 16384u
+typedef struct rplgpu_scan_merge {
+  float angle_min, angle_max; /* the virtual scan covers [angle_min, angle_max) in the common frame */
+  uint32_t count;             /* beams, 1 .. RPLGPU_MAX_MERGE_BEAMS */
+  float range_min, range_max; /* range gate in the common frame; also LaserScan.range_min / range_max */
+  float scan_time;            /* LaserScan.scan_time of the merged message */
+} rplgpu_scan_merge_t;
+/* Host only (no handle, no device): validates the spec, writes inc and the edge table
+ *   phi_k = (double)angle_min + (double)k * (double)inc,  e_k = ((float)cos(phi_k), (float)sin(phi_k)),
+ * k = 0 .. count, as edges[2k], edges[2k + 1] (2 * (count + 1) floats; either pointer may be NULL).
+ * The device path builds its table with this very function. */
+int32_t rplgpu_scan_merge_edges(const rplgpu_scan_merge_t *m, float *edges, float *inc);
+/* E9 for groups of scans: scans [g*group, (g+1)*group) of the batch (group clamped to B as in E8) give
+ * merged scan g.  Every sample E1 keeps (and E5 too with p->ror_enable) becomes (x, y) by exactly the
+ * float32 operations of rplgpu_cloud_fused_voxel_dev: E2 (p->inverted honoured), E6 de-skew from d_motion
+ * with the offsets of rplgpu_set_scan_time_offsets_dev (offsets set and d_motion NULL: refused), the planar
+ * pose from d_pose2d.  voxel_enable and scan_processing are ignored.  Then
+ *   r2 = RN(RN(x*x) + RN(y*y)) (no FMA), range = sqrtf(r2) correctly rounded;
+ *   the point takes part iff range_min <= range <= range_max;
+ *   cross_k = (double)e_k.x * (double)y - (double)e_k.y * (double)x  (exact products, one rounding: exact sign);
+ *   its beam is the SMALLEST k in [0, count) with cross_k >= 0 && cross_k+1 < 0; none: dropped
+ *   (neighbouring beams share an edge, so the beams tile without gaps; on a full circle the sliver between
+ *   e_count and e_0 goes to the smaller k).
+ * Per beam the point with the smallest r2 wins, ties to the smallest (slot in group, sample index):
+ *   ranges[k] = sqrtf(r2), intensities[k] = its E3 intensity; an empty beam holds +inf and 0.
+ * Merged scan g at d_ranges + g*count, d_intensities + g*count; d_beams_hit[g] = its non-empty beams;
+ * d_status[g] (optional) = RPLGPU_SCAN_OUT_TRUNCATED when a scan of the group was longer than n_stride.
+ * Asynchronous on the handle's stream; the argument and capacity checks of rplgpu_cloud_fused_voxel_dev. */
+int32_t rplgpu_merge_scans_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group,
+                               const rplgpu_params_t *p, const float *d_motion, const float *d_pose2d,
+                               const rplgpu_scan_merge_t *m, float *d_ranges, float *d_intensities,
+                               uint32_t *d_beams_hit, uint32_t *d_status);
+/* G serialised LaserScans of merged scans (d_ranges / d_intensities as rplgpu_merge_scans_dev wrote them):
+ * angle_min, angle_max, range_min, range_max and scan_time of `m`, angle_increment = inc,
+ * time_increment = 0 (the points are already moved to one instant), always count beams.  Message g at
+ * d_msgs + g*msg_stride (a multiple of 4), its length in d_msg_len[g]; 0 + RPLGPU_SCAN_OUT_TRUNCATED in
+ * d_status[g] (optional) when msg_stride is too small.  d_stamps: G stamps (device). */
+int32_t rplgpu_merged_laserscan_msgs_dev(rplgpu_handle_t h, const float *d_ranges,
+                                         const float *d_intensities, uint32_t G,
+                                         const rplgpu_scan_merge_t *m, const char *frame_id,
+                                         const rplgpu_stamp_t *d_stamps, uint8_t *d_msgs,
+                                         uint32_t msg_stride, uint32_t *d_msg_len, uint32_t *d_status);
+
 #ifdef __cplusplus
 }
 #endif

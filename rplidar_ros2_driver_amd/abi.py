@@ -38,6 +38,8 @@ SCAN_CELL_RANGE = 0x2
 SCAN_TABLE_FULL = 0x4
 SCAN_OUT_TRUNCATED = 0x8
 
+MAX_MERGE_BEAMS = 16384  # RPLGPU_MAX_MERGE_BEAMS (include/rplgpu_msg.h)
+
 SL_RESULT_OK = 0
 SL_RESULT_OPERATION_FAIL = 0x80008001
 
@@ -92,6 +94,9 @@ ABI_SYMBOLS = [
     "rplgpu_set_scan_time_offsets_dev",
     "rplgpu_set_voxel_aggregation",
     "rplgpu_set_ror_mode",
+    "rplgpu_scan_merge_edges",
+    "rplgpu_merge_scans_dev",
+    "rplgpu_merged_laserscan_msgs_dev",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -187,6 +192,19 @@ class CloudLayout(C.Structure):
 
     _fields_ = [(k, C.c_uint32) for k in (
         "width_off", "row_step_off", "data_len_off", "data_off", "is_dense_off", "total_len")]
+
+
+class ScanMerge(C.Structure):
+    """Mirror of ``rplgpu_scan_merge_t`` (E9: the virtual scan the sensors of a group merge into)."""
+
+    _fields_ = [
+        ("angle_min", C.c_float),
+        ("angle_max", C.c_float),
+        ("count", C.c_uint32),
+        ("range_min", C.c_float),
+        ("range_max", C.c_float),
+        ("scan_time", C.c_float),
+    ]
 
 
 def library_path() -> Path:
@@ -315,6 +333,11 @@ def load_library() -> C.CDLL:
                                            vp, vp, vp]
     lib.rplgpu_merge_cells_host.argtypes = [vp, u64, vp, u32, u32, u32, C.POINTER(Params), vp, u64, vp, vp,
                                             vp, vp]
+    lib.rplgpu_scan_merge_edges.argtypes = [C.POINTER(ScanMerge), vp, vp]
+    lib.rplgpu_merge_scans_dev.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp,
+                                           C.POINTER(ScanMerge), vp, vp, vp, vp]
+    lib.rplgpu_merged_laserscan_msgs_dev.argtypes = [vp, vp, vp, u32, C.POINTER(ScanMerge), cs, vp, vp, u32,
+                                                     vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -550,6 +573,22 @@ class RplGpu:
         self._check(self._lib.rplgpu_cloud_fused_voxel_dev(
             self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d,
             d_arena, arena_capacity, d_cursor, d_group_start, d_n_points, d_status))
+
+    def merge_scans_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int,
+                        params: Params, d_motion: int, d_pose2d: int, merge: ScanMerge, d_ranges: int,
+                        d_intens: int, d_beams_hit: int, d_status: int = 0):
+        """E9: one merged LaserScan (merge.count beams) per group of `group` consecutive scans."""
+        self._check(self._lib.rplgpu_merge_scans_dev(
+            self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d,
+            C.byref(merge), d_ranges, d_intens, d_beams_hit, d_status))
+
+    def merged_laserscan_msgs_dev(self, d_ranges: int, d_intens: int, G: int, merge: ScanMerge,
+                                  frame_id: str, d_stamps: int, d_msgs: int, msg_stride: int,
+                                  d_msg_len: int, d_status: int = 0):
+        """G serialised LaserScans of merged scans (rplgpu_merged_laserscan_msgs_dev)."""
+        self._check(self._lib.rplgpu_merged_laserscan_msgs_dev(
+            self._h, d_ranges, d_intens, G, C.byref(merge), frame_id.encode(), d_stamps, d_msgs,
+            msg_stride, d_msg_len, d_status))
 
     def cloud_fused_cells_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int,
                               params: Params, d_motion: int, d_pose2d: int, d_cells: int,
@@ -889,3 +928,16 @@ def merge_cells_host(cells_all: np.ndarray, slot_cells: int, meta_all: np.ndarra
     if rc:
         raise RplGpuError(rc, "rplgpu_merge_cells_host")
     return arena[:cap], int(cursor[0]), starts[:n_groups], npts[:n_groups], status[:n_groups]
+
+
+def scan_merge_edges(merge: ScanMerge):
+    """Host only: (edges (count + 1, 2) float32, inc float32) of an E9 spec by the library's own
+    rplgpu_scan_merge_edges.  Raises RplGpuError(ERR_INVALID_ARG) for a spec the library refuses."""
+    lib = load_library()
+    n = int(merge.count) + 1 if 0 < int(merge.count) <= MAX_MERGE_BEAMS else 1
+    edges = np.zeros((n, 2), np.float32)
+    inc = np.zeros(1, np.float32)
+    rc = lib.rplgpu_scan_merge_edges(C.byref(merge), edges.ctypes.data, inc.ctypes.data)
+    if rc:
+        raise RplGpuError(rc, "rplgpu_scan_merge_edges")
+    return edges, inc[0]

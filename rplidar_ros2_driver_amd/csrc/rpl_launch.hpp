@@ -200,4 +200,29 @@ hipError_t launch_transform_clouds(hipStream_t s, float *xyzi, uint32_t out_stri
                                    uint32_t max_points, const unsigned long long *scan_start,
                                    const uint32_t *n_points, uint32_t B, const float *pose);
 
+// E9: the scans of a group merged into one LaserScan (rpl_merge.hip, include/rplgpu_msg.h)
+constexpr uint32_t kMergeMaxBeams = RPLGPU_MAX_MERGE_BEAMS;
+constexpr uint32_t kMergeSlotBits = 17;  // key: r2 bits << 32 | slot << 15 | sample index
+struct MergeK {
+  const float2 *edges;  // e_0 .. e_count (host-built, rplgpu_scan_merge_edges)
+  uint32_t count;
+  uint32_t monotone;    // 1: every step e_k -> e_k+1 and every quarter below turns by (0, pi) (host-checked)
+  uint32_t qb[5];       // quarter boundaries k = q * count / 4
+  float2 qe[5];         // their edge vectors
+  float a0;             // angle_min reduced to [0, 2 pi) (the first guess only)
+  float rinc;           // 1 / inc (the first guess only)
+  float range_min, range_max;
+};
+hipError_t launch_merge_scans(hipStream_t s, const void *nodes, uint32_t n_stride,
+                              const uint32_t *n_per_scan, uint32_t B, uint32_t group, const KParams &p,
+                              const Tables &T, const uint32_t *keepmask, uint32_t mask_stride,
+                              const float *motion, const float *pose2d, const MergeK &mk,
+                              unsigned long long *keys, uint32_t *status);
+hipError_t launch_merge_finish(hipStream_t s, unsigned long long *keys, uint32_t G, uint32_t count,
+                               const void *nodes, uint32_t n_stride, uint32_t group, int is_new_protocol,
+                               float *ranges, float *intens, uint32_t *beams_hit);
+hipError_t launch_msg_merged(hipStream_t s, const float *ranges, const float *intens, uint32_t count,
+                             uint32_t G, const rplgpu_stamp_t *stamps, const rplmsg::Prefix &P,
+                             uint8_t *msgs, uint32_t msg_stride, uint32_t *msg_len, uint32_t *status);
+
 }  // namespace rpl

@@ -88,6 +88,16 @@ struct rplgpu_ctx {
   uint32_t vstore_recs = 0;           // records per workgroup (grows with the largest E8 group seen)
   uint32_t *d_merge = nullptr;        // rplgpu_merge_cells_dev scratch (world x slot_cells words, grown on demand)
   size_t merge_cap = 0;               // (words)
+  // rplgpu_merge_scans_dev (E9): key rows (G x count u64, all ~0 between launches) and the edge table of
+  // the last spec (e_0 .. e_count), both grown on demand
+  unsigned long long *d_mkeys = nullptr;
+  size_t mkeys_cap = 0;               // (keys)
+  bool mkeys_clean = true;            // false from the merge launch until its finishing launch is queued
+  float2 *d_medges = nullptr;
+  size_t medges_cap = 0;              // (edges)
+  bool mspec_valid = false;           // d_medges / mspec_k hold the table of mspec
+  rplgpu_scan_merge_t mspec;
+  rpl::MergeK mspec_k;
   unsigned char *d_dec = nullptr;     // rplgpu_decode_stream staging (grown on demand, kept)
   size_t dec_cap = 0;
   unsigned char *d_scans = nullptr;   // rplgpu_decode_scans_dev scratch (node streams, sync lists)
@@ -336,6 +346,8 @@ void free_ctx(rplgpu_ctx *c) {
   if (c->d_dec_todo) (void)hipFree(c->d_dec_todo);
   if (c->d_vstore) (void)hipFree(c->d_vstore);
   if (c->d_merge) (void)hipFree(c->d_merge);
+  if (c->d_mkeys) (void)hipFree(c->d_mkeys);
+  if (c->d_medges) (void)hipFree(c->d_medges);
   if (c->h_vstats) (void)hipHostFree(c->h_vstats);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1010,6 +1022,204 @@ int32_t rplgpu_cloud_fused_cells_dev(rplgpu_handle_t h, const rplgpu_node_t *d_n
   return fused_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d,
                     reinterpret_cast<float *>(d_cells), cells_capacity, d_cursor, d_group_start, d_n_cells,
                     d_status, true);
+}
+
+// ---- E9: one merged LaserScan per group of scans (include/rplgpu_msg.h) ---------------------------
+
+int32_t rplgpu_scan_merge_edges(const rplgpu_scan_merge_t *m, float *edges, float *inc) {
+  if (!m) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(m->angle_min) || !std::isfinite(m->angle_max) || !std::isfinite(m->range_min) ||
+      !std::isfinite(m->range_max) || !std::isfinite(m->scan_time))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (m->count == 0 || m->count > RPLGPU_MAX_MERGE_BEAMS) return RPLGPU_ERR_INVALID_ARG;
+  const double span = (double)m->angle_max - (double)m->angle_min;
+  const float f_inc = (float)(span / (double)m->count);
+  if (!(f_inc > 0.0f) || f_inc > (float)(M_PI / 2)) return RPLGPU_ERR_INVALID_ARG;
+  if (span > 2.0 * M_PI * (1.0 + 0x1p-20)) return RPLGPU_ERR_INVALID_ARG;
+  if (!(0.0f <= m->range_min && m->range_min < m->range_max)) return RPLGPU_ERR_INVALID_ARG;
+  if (edges)
+    for (uint32_t k = 0; k <= m->count; ++k) {
+      const double phi = (double)m->angle_min + (double)k * (double)f_inc;
+      edges[2 * k] = (float)std::cos(phi);
+      edges[2 * k + 1] = (float)std::sin(phi);
+    }
+  if (inc) *inc = f_inc;
+  return RPLGPU_OK;
+}
+
+namespace {
+
+// e_a -> e_b turns by an angle in (0, pi): the exact sign of the fp64 cross product of float vectors
+bool turns_left(float2 a, float2 b) { return (double)a.x * (double)b.y - (double)a.y * (double)b.x > 0.0; }
+
+// the edge table of spec `m` on the device and the kernel's view of it (cached per spec)
+int32_t merge_spec_upload(rplgpu_ctx *c, const rplgpu_scan_merge_t &m, rpl::MergeK *out) {
+  if (c->mspec_valid && std::memcmp(&c->mspec, &m, sizeof(m)) == 0) {
+    *out = c->mspec_k;
+    return RPLGPU_OK;
+  }
+  std::vector<float2> e(m.count + 1u);
+  float inc = 0.0f;
+  if (rplgpu_scan_merge_edges(&m, reinterpret_cast<float *>(e.data()), &inc) != RPLGPU_OK) {
+    c->err = "rplgpu_scan_merge_t: invalid spec (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  // the table in use may still be read by queued launches
+  RPL_HIP(c, hipStreamSynchronize(c->stream));
+  c->mspec_valid = false;
+  if (e.size() > c->medges_cap) {
+    if (c->d_medges) (void)hipFree(c->d_medges);
+    c->d_medges = nullptr;
+    c->medges_cap = 0;
+    RPL_HIP(c, hipMalloc((void **)&c->d_medges, e.size() * sizeof(float2)));
+    c->medges_cap = e.size();
+  }
+  RPL_HIP(c, hipMemcpy(c->d_medges, e.data(), e.size() * sizeof(float2), hipMemcpyHostToDevice));
+  rpl::MergeK k;
+  k.edges = c->d_medges;
+  k.count = m.count;
+  bool mono = true;
+  for (uint32_t i = 0; i < m.count && mono; ++i) mono = turns_left(e[i], e[i + 1]);
+  for (int q = 0; q < 5; ++q) {
+    k.qb[q] = (uint32_t)((uint64_t)q * m.count / 4u);
+    k.qe[q] = e[k.qb[q]];
+  }
+  for (int q = 0; q < 4 && mono; ++q)
+    if (k.qb[q] != k.qb[q + 1]) mono = turns_left(k.qe[q], k.qe[q + 1]);
+  k.monotone = mono ? 1u : 0u;
+  double a0 = std::fmod((double)m.angle_min, 2.0 * M_PI);
+  if (a0 < 0.0) a0 += 2.0 * M_PI;
+  k.a0 = (float)a0;
+  k.rinc = 1.0f / inc;
+  k.range_min = m.range_min;
+  k.range_max = m.range_max;
+  c->mspec = m;
+  c->mspec_k = k;
+  c->mspec_valid = true;
+  *out = k;
+  return RPLGPU_OK;
+}
+
+}  // namespace
+
+int32_t rplgpu_merge_scans_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group,
+                               const rplgpu_params_t *p, const float *d_motion, const float *d_pose2d,
+                               const rplgpu_scan_merge_t *m, float *d_ranges, float *d_intensities,
+                               uint32_t *d_beams_hit, uint32_t *d_status) {
+  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
+  if (rc) return rc;
+  if (!p || !m || !d_ranges || !d_intensities || !d_beams_hit || group == 0) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_scan_merge_edges(m, nullptr, nullptr) != RPLGPU_OK) {
+    h->err = "rplgpu_merge_scans_dev: invalid rplgpu_scan_merge_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (B == 0) return RPLGPU_OK;
+  if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
+      (d_pose2d && !device_readable(h, d_pose2d, "d_pose2d")) ||
+      !device_readable(h, d_ranges, "d_ranges") || !device_readable(h, d_intensities, "d_intensities") ||
+      !device_readable(h, d_beams_hit, "d_beams_hit") || (d_status && !device_readable(h, d_status, "d_status")))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (h->scan_t0 && !d_motion) {
+    h->err = "rplgpu_merge_scans_dev: scan time offsets are set (rplgpu_set_scan_time_offsets_dev) but d_motion is NULL";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
+    h->err = "ror_radius must be in (0, 1e6] m";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  group = std::min(group, B);  // as E8: "all sensors in one scan" may be asked for with any group >= B
+  if ((uint64_t)group * std::min(n_stride, rpl::kMaxN) > (1ull << 24) || group > (1u << rpl::kMergeSlotBits)) {
+    h->err = "rplgpu_merge_scans_dev: group x n_stride above 2^24 samples";
+    return RPLGPU_ERR_CAPACITY;
+  }
+  const uint32_t G = (B + group - 1u) / group;
+  RPL_HIP(h, hipSetDevice(h->device));
+  rpl::MergeK mk;
+  if ((rc = merge_spec_upload(h, *m, &mk))) return rc;
+  const size_t need = (size_t)G * m->count;
+  if (need > h->mkeys_cap) {  // (only ever grows; fresh rows are empty)
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    if (h->d_mkeys) (void)hipFree(h->d_mkeys);
+    h->d_mkeys = nullptr;
+    h->mkeys_cap = 0;
+    if (hipMalloc((void **)&h->d_mkeys, need * sizeof(unsigned long long)) != hipSuccess) {
+      h->err = "merge key rows allocation failed";
+      (void)hipGetLastError();
+      return RPLGPU_ERR_HIP;
+    }
+    h->mkeys_cap = need;
+    h->mkeys_clean = false;
+  }
+  if (!h->mkeys_clean)  // a new allocation, or a call that failed between the two launches
+    RPL_HIP(h, hipMemsetAsync(h->d_mkeys, 0xFF, h->mkeys_cap * sizeof(unsigned long long), h->stream));
+  rpl::KParams kp = to_kparams(*p);
+  kp.fast_d4000 = h->div4000_ok ? 1 : 0;
+  const rpl::Tables T = tables_of(h);
+  const uint32_t *mask = nullptr;
+  if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E8's two-kernel path applies
+    RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
+                                    kMaskStride));
+    mask = h->d_rormask;
+  }
+  RPL_HIP(h, hipMemsetAsync(d_beams_hit, 0, (size_t)G * 4u, h->stream));
+  if (d_status) RPL_HIP(h, hipMemsetAsync(d_status, 0, (size_t)G * 4u, h->stream));
+  h->mkeys_clean = false;
+  RPL_HIP(h, rpl::launch_merge_scans(h->stream, d_nodes, n_stride, d_n_per_scan, B, group, kp, T, mask,
+                                     kMaskStride, d_motion, d_pose2d, mk, h->d_mkeys, d_status));
+  RPL_HIP(h, rpl::launch_merge_finish(h->stream, h->d_mkeys, G, m->count, d_nodes, n_stride, group,
+                                      p->is_new_protocol, d_ranges, d_intensities, d_beams_hit));
+  h->mkeys_clean = true;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_merged_laserscan_msgs_dev(rplgpu_handle_t h, const float *d_ranges,
+                                         const float *d_intensities, uint32_t G,
+                                         const rplgpu_scan_merge_t *m, const char *frame_id,
+                                         const rplgpu_stamp_t *d_stamps, uint8_t *d_msgs,
+                                         uint32_t msg_stride, uint32_t *d_msg_len, uint32_t *d_status) {
+  if (!h || !m || !frame_id) return RPLGPU_ERR_INVALID_ARG;
+  float inc = 0.0f;
+  if (rplgpu_scan_merge_edges(m, nullptr, &inc) != RPLGPU_OK) {
+    h->err = "rplgpu_merged_laserscan_msgs_dev: invalid rplgpu_scan_merge_t";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0) return RPLGPU_OK;
+  if (!d_ranges || !d_intensities || !d_stamps || !d_msgs || !d_msg_len || (msg_stride & 3u))
+    return RPLGPU_ERR_INVALID_ARG;
+  const size_t fl = std::strlen(frame_id);
+  if (fl > rplmsg::kMaxFrameId) {
+    h->err = "frame_id longer than 255 bytes";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  rplgpu_scan_meta_t meta;
+  std::memset(&meta, 0, sizeof(meta));
+  meta.angle_min = m->angle_min;
+  meta.angle_max = m->angle_max;
+  meta.angle_increment = inc;
+  meta.time_increment = 0.0f;  // every point is already moved to the fused instant
+  meta.scan_time = m->scan_time;
+  meta.range_min = m->range_min;
+  meta.range_max = m->range_max;
+  meta.count = m->count;
+  meta.published = 1;
+  rplmsg::Prefix P;
+  std::memset(&P, 0, sizeof(P));
+  rplmsg::Writer w(reinterpret_cast<uint8_t *>(P.words), sizeof(P.words));
+  rplgpu_laserscan_layout_t L;
+  rplmsg::write_laserscan(w, frame_id, fl, rplgpu_stamp_t{0, 0}, meta, &L);
+  P.stamp_off = 4;
+  P.len = L.ranges_off;  // every scalar and the ranges length word come with the template
+  P.a_off = L.scalars_off;
+  P.b_off = L.ranges_len_off;
+  if (P.len > sizeof(P.words) || (P.len & 3u)) {
+    h->err = "message prefix does not fit the device template";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_msg_merged(h->stream, d_ranges, d_intensities, m->count, G, d_stamps, P, d_msgs,
+                                    msg_stride, d_msg_len, d_status));
+  return RPLGPU_OK;
 }
 
 // `defer_listed`: see voxel_with_ror (single-scan callers; d_status must be given then)
