@@ -58,6 +58,11 @@ extern "C" {
 /* per-scan status bits written by the batch entry points (0 == clean) */
 #define RPLGPU_SCAN_ALL_INVALID 0x1u   /* ascend: SL_RESULT_OPERATION_FAIL, scan left untouched */
 #define RPLGPU_SCAN_CELL_RANGE 0x2u    /* voxel: |cell index| >= 32767 (range/leaf too large) */
+/* (RPLGPU_SCAN_CELL_RANGE, the rule: in float32 t = x / leaf, f = floor(t); a point with |f.x| >= 32767 or
+ * |f.y| >= 32767 is dropped and sets the bit for its work item (scan, or group of scans).  Only points that
+ * survived E1 AND E5 count — a far return that radius outlier removal discards flags nothing — in
+ * RPLGPU_ROR_INSIDE and RPLGPU_ROR_TWO_KERNELS alike; E5 itself runs in the sensor frame in front of the
+ * range test, so an out-of-range sample still counts as a neighbour.) */
 #define RPLGPU_SCAN_TABLE_FULL 0x4u    /* voxel: more occupied cells than the on-chip table holds */
 #define RPLGPU_SCAN_OUT_TRUNCATED 0x8u /* output region (out_stride) too small; count is clamped */
 /* 0x80u: reserved (rounds 4-5: RPLGPU_SCAN_NOT_PRODUCED of the pipelined two-kernel voxel form, removed) */

@@ -191,6 +191,7 @@ __device__ __forceinline__ void glb_store128(void *p, u32x4 v) {
 struct RorPre {
   f2 xy;    // E2 point in the sensor frame (in front of any E6 / E8 transform)
   bool e1;  // passed E1 (whatever the cell-range test says later)
+  bool far; // passed E1 and lies outside the cell range: flags the work item only if E5 keeps it
 };
 
 // Per-sample arithmetic of phase S for one 8-byte node (lo, hi) and its table entry `c`: the sort
@@ -230,8 +231,13 @@ __device__ __forceinline__ bool voxel_sample(uint32_t lo, uint32_t hi, float2 c,
   const f2 f = {__builtin_floorf(t.x), __builtin_floorf(t.y)};
   if (!SAFE || XF) {
     const bool inr = (fabsf(f.x) < 32767.0f) && (fabsf(f.y) < 32767.0f);
-    if (kept && !inr) flags |= RPLGPU_SCAN_CELL_RANGE;
+    // (the fused E5 instance: a far return that E5 removes must not flag its work item — the caller ORs
+    // the bit in once the sample is settled, voxel_stream HASROR; a late survivor comes through ror_append)
+    if (ror) ror->far = kept && !inr;
+    else if (kept && !inr) flags |= RPLGPU_SCAN_CELL_RANGE;
     kept = kept & inr;
+  } else if (ror) {
+    ror->far = false;
   }
   // iy + 32768 | ix + 32768 from the mantissas of f + (2^23 + 32768)
   const uint32_t kx = __float_as_uint(f.x + kKeyMagic);
@@ -941,6 +947,9 @@ __device__ __forceinline__ void voxel_stream(QueueSink &sink, const KParams &p,
               const uint32_t sl = atomicAdd(&rs->n_todo, 1u);
               if (sl < kRorTodoCap) rs->todo[sl] = (uint16_t)(i0 + 1u);
             }
+          }
+          if (!SAFE || XF) {  // the cell-range bit: only for samples that E5 keeps (as the two kernels do)
+            if (owned && ((sa && pre[0].far) || (sb && pre[1].far))) flags |= RPLGPU_SCAN_CELL_RANGE;
           }
           ok[0] = ok[0] && owned && sa;
           ok[1] = ok[1] && owned && sb;

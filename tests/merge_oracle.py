@@ -8,15 +8,8 @@ library the product's host code calls), never np.cos, whose SIMD paths may diffe
 from __future__ import annotations
 
 import math
-import sys
-from pathlib import Path
 
 import numpy as np
-
-from tests import oracle_lib
-
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "oracle"))
-import fusion_oracle as fo  # noqa: E402
 
 MAX_BEAMS = 16384
 F32 = np.float32
@@ -118,39 +111,9 @@ def bin_fast(E, x, y, angle_min, inc) -> np.ndarray:
     return out
 
 
-def group_points(oracle, scans, p, motion=None, pose2d=None, t0=None):
-    """(x, y, r2 float32, slot, sample index, intensity) of every point of a group, before the range gate."""
-    op = oracle_lib.copy_params(p)
-    op.voxel_enable = 0
-    op.ror_enable = 0
-    xs, ys, slots, idxs, ins = [], [], [], [], []
-    for s, nodes in enumerate(scans):
-        nodes = np.ascontiguousarray(nodes)
-        cloud = oracle.scan_to_cloud(nodes, op) if len(nodes) else np.zeros((0, 4), np.float32)
-        d = nodes["dist_mm_q2"]
-        keep = d != 0
-        if p.clip_enable:
-            dm = d.astype(np.float32) / F32(4000.0)
-            keep &= (dm >= F32(p.range_min)) & (dm <= F32(p.range_max)) & (nodes["quality"] >= p.q_min)
-        idx = np.flatnonzero(keep)
-        assert len(idx) == len(cloud)
-        if p.ror_enable and len(cloud):
-            k = oracle.ror_mask(cloud, p.ror_radius, p.ror_min_neighbors)
-            cloud, idx = cloud[k], idx[k]
-        if motion is not None:
-            cloud = fo.deskew_cloud(cloud, idx, motion[s], None if t0 is None else t0[s])
-        if pose2d is not None:
-            r00, r01, tx, r10, r11, ty = pose2d[s]
-            pose = np.array([[r00, r01, 0, tx], [r10, r11, 0, ty], [0, 0, 1, 0]], np.float32)
-            cloud = fo.transform_cloud(cloud, pose)
-        xs.append(cloud[:, 0])
-        ys.append(cloud[:, 1])
-        slots.append(np.full(len(idx), s, np.int64))
-        idxs.append(idx.astype(np.int64))
-        ins.append(cloud[:, 3])
-    x, y = np.concatenate(xs).astype(np.float32), np.concatenate(ys).astype(np.float32)
-    r2 = ((x * x).astype(np.float32) + (y * y).astype(np.float32)).astype(np.float32)
-    return x, y, r2, np.concatenate(slots), np.concatenate(idxs), np.concatenate(ins).astype(np.float32)
+# (the points of a group — E1, E2, E5 on the scan's own points, E6, pose — are the fused grid's too:
+# tests/fused_oracle.py holds the one composition)
+from tests.fused_oracle import group_points  # noqa: E402,F401
 
 
 def reduce_beams(count, k, r2, slot, idx, intens):

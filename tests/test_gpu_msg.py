@@ -502,28 +502,15 @@ def test_laserscan_to_cloud_matches_oracle(gpu, oracle):
 
 # ------------------------------------------------ E8: one voxel grid per group of scans (row 4)
 def _e8_oracle(oracle, scans, p, motion, pose2d, leaf, t0=None):
-    """Spec of rplgpu_cloud_fused_voxel_dev from its parts: E1 + E2 per scan (C oracle), E6
-    de-skew and the planar pose (numpy restatements in oracle/fusion_oracle.py), then E4 over all
-    points of the group (C oracle's voxel grid)."""
-    import fusion_oracle as fo
-    op = oracle_lib.copy_params(p)
-    op.voxel_enable = 0
-    pts = []
-    for s, nodes in enumerate(scans):
-        cloud = oracle.scan_to_cloud(nodes, op)  # kept samples in input order (E5 applied too)
-        dm = nodes["dist_mm_q2"].astype(np.float32) / np.float32(4000.0)
-        keep = (nodes["dist_mm_q2"] != 0) & (dm >= np.float32(p.range_min)) & (dm <= np.float32(p.range_max)) \
-            & (nodes["quality"] >= p.q_min)
-        idx = np.flatnonzero(keep)
-        assert not p.ror_enable and len(idx) == len(cloud)
-        if motion is not None:
-            cloud = fo.deskew_cloud(cloud, idx, motion[s], None if t0 is None else t0[s])
-        if pose2d is not None:
-            r00, r01, tx, r10, r11, ty = pose2d[s]
-            pose = np.array([[r00, r01, 0, tx], [r10, r11, 0, ty], [0, 0, 1, 0]], np.float32)
-            cloud = fo.transform_cloud(cloud, pose)
-        pts.append(cloud)
-    return oracle.voxel_grid(np.concatenate(pts), leaf)
+    """Spec of rplgpu_cloud_fused_voxel_dev from its parts (tests/fused_oracle.py): E1 + E2 per scan (C
+    oracle), E5 on every scan's own points when p.ror_enable, E6 de-skew and the planar pose (numpy
+    restatements in oracle/fusion_oracle.py), then E4 over all in-range points of the group (C oracle's
+    voxel grid)."""
+    from tests import fused_oracle
+    assert np.float32(leaf) == np.float32(p.voxel_leaf)
+    cloud, cells, counts, status = fused_oracle.fused_grid(oracle, scans, p, motion, pose2d, t0)
+    assert status == 0
+    return cloud, cells, counts
 
 
 def test_fused_voxel_groups_match_oracle(gpu, oracle):
