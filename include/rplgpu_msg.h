@@ -286,6 +286,77 @@ int32_t rplgpu_merged_laserscan_msgs_dev(rplgpu_handle_t h, const float *d_range
                                          const rplgpu_stamp_t *d_stamps, uint8_t *d_msgs,
                                          uint32_t msg_stride, uint32_t *d_msg_len, uint32_t *d_status);
 
+/* ---- E10: scan-shadow and speckle filters on LaserScan arrays (the `laser_filters` staples) ------
+ * A stage between the LaserScan producers (rplgpu_laserscan_batch_dev, rplgpu_ascend_laserscan_batch_dev,
+ * rplgpu_merge_scans_dev) and their consumers (the message functions, E7): same layout in and out.
+ * Nothing in the reference filters a scan, so these rules ARE the definition (parity unpinned, as E5-E9).
+ *
+ * A beam is finite when its range is a finite float.  With circular = 1 indices are taken modulo count
+ * and W and N are each limited to (count - 1) / 2, so no beam meets itself; with circular = 0 indices
+ * outside [0, count) do not exist.
+ * SHADOW, detection.  Beam i finite with range r1; neighbour j = i +- y, 1 <= y <= W, finite with range r2:
+ *   delta = (float)y * inc; the pair is examined only while delta <= 0.5f;
+ *   s, c = the E6 polynomials (rplgpu_cloud_deskew_batch_dev above) at a = delta, float32, no FMA;
+ *   a = r2 * s;  b = r1 - r2 * c            (float32: the product, then the difference)
+ *   it is a shadow pair iff (double)cmin*(double)a - (double)smin*(double)b < 0    (atan2(a, b) < min_angle)
+ *                        or (double)cmax*(double)a - (double)smax*(double)b > 0    (atan2(a, b) > max_angle)
+ *   (exact products, one rounding: exact sign; no angle is ever computed).  Beam i is DETECTED when it has
+ *   at least one shadow pair.
+ * SHADOW, removal.  Beam k is removed iff it is finite and some detected beam i with |i - k| <= N has
+ *   r[i] < r[k]: only the farther points go, and every decision reads the input ranges.
+ * SPECKLE, on the ranges after shadow removal (removed beams are not finite).  Beams k and k + 1 are
+ *   linked iff both are finite and fabsf(r[k+1] - r[k]) <= D (float32 difference); a run is a maximal
+ *   chain of linked beams; with circular the link count-1 -> 0 exists and a run that closes the circle has
+ *   count beams.  A finite beam is removed iff its run has fewer than L beams.  (A run's length is its true
+ *   length: an implementation may stop counting on either side of a beam after min(L, count) - 1 links and
+ *   take min(left + right + 1, count), which decides the same.)
+ * A removed beam's range is the quiet NaN 0x7FC00000 (what laser_filters leaves; E7 drops it); every
+ * other beam below count keeps its input bits (+inf empty bins and NaNs included); intensities are a bit
+ * copy; beams at or beyond count are not written.  Both filters off: a plain copy. */
+#define RPLGPU_MAX_FILTER_WINDOW 64u
+typedef struct rplgpu_scan_filter {
+  int32_t  shadow_enable;
+  float    shadow_min_angle, shadow_max_angle; /* rad; 0 < min < pi/2 < max < pi (defaults 10 deg, 170 deg) */
+  uint32_t shadow_window;     /* W: 1 .. RPLGPU_MAX_FILTER_WINDOW (default 2) */
+  uint32_t shadow_neighbors;  /* N: 0 .. RPLGPU_MAX_FILTER_WINDOW (default 1) */
+  int32_t  speckle_enable;
+  float    speckle_max_range_difference; /* D >= 0, metres (default 0.05) */
+  uint32_t speckle_min_run;   /* L: 1 .. RPLGPU_MAX_FILTER_WINDOW (default 4) */
+  int32_t  circular;          /* beams count-1 and 0 are neighbours (default 1: full-circle scans) */
+} rplgpu_scan_filter_t;
+
+/* Both filters on, with the defaults named above. */
+void rplgpu_default_scan_filter(rplgpu_scan_filter_t *f);
+/* Host only (no handle, no device): validates f — finite values and the ranges above (angles compared
+ * in fp64), whether or not a filter is enabled; dirs (may be NULL) receives
+ *   cmin, smin, cmax, smax = (float)cos((double)min_angle), (float)sin((double)min_angle), ... max_angle.
+ * The device path uses this function. */
+int32_t rplgpu_scan_filter_check(const rplgpu_scan_filter_t *f, float dirs[4]);
+
+/* The outputs of rplgpu_laserscan_batch_dev / rplgpu_ascend_laserscan_batch_dev, filtered: scan b has
+ * count = min(d_beam_count[b], n_stride) beams at d_ranges + b*n_stride and, computed on the device as
+ * the reference does (and E7),  inc = (float)(2 pi / (double)count) with p->scan_processing (Mode A, :635),
+ * else (float)(2 pi / (double)max(count - 1, 1)) (Mode B, :666-668); nothing else of *p is used.
+ * d_removed (optional): 2 words per scan — beams the shadow filter removed, beams the speckle filter
+ * removed in addition.  RPLGPU_ERR_INVALID_ARG for an output pointer equal to its input, a missing
+ * required pointer, n_stride = 0 or an invalid filter.  Only equal pointers are refused: output buffers that
+ * overlap the inputs in any other way are the caller's error and give undefined results (a tile reads
+ * its neighbours' beams while other tiles write).  Asynchronous on the handle's stream. */
+int32_t rplgpu_filter_laserscan_batch_dev(rplgpu_handle_t h, const float *d_ranges, const float *d_intensities,
+                                          uint32_t n_stride, const uint32_t *d_beam_count, uint32_t B,
+                                          const rplgpu_params_t *p, const rplgpu_scan_filter_t *f,
+                                          float *d_ranges_out, float *d_intensities_out, uint32_t *d_removed);
+/* The outputs of rplgpu_merge_scans_dev, filtered: G scans of m->count beams, m->count apart, inc from
+ * rplgpu_scan_merge_edges; f->circular is honoured as given (set it only for a full-circle spec). */
+int32_t rplgpu_filter_merged_scans_dev(rplgpu_handle_t h, const float *d_ranges, const float *d_intensities,
+                                       uint32_t G, const rplgpu_scan_merge_t *m, const rplgpu_scan_filter_t *f,
+                                       float *d_ranges_out, float *d_intensities_out, uint32_t *d_removed);
+/* One scan, HOST buffers: count <= max_samples_per_scan beams (else RPLGPU_ERR_CAPACITY) with the given
+ * angle_increment (finite, > 0); removed (optional) as above.  Returns when the results are in place. */
+int32_t rplgpu_filter_laserscan(rplgpu_handle_t h, const float *ranges, const float *intensities, uint32_t count,
+                                float angle_increment, const rplgpu_scan_filter_t *f, float *ranges_out,
+                                float *intensities_out, uint32_t removed[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ SCAN_TABLE_FULL = 0x4
 SCAN_OUT_TRUNCATED = 0x8
 
 MAX_MERGE_BEAMS = 16384  # RPLGPU_MAX_MERGE_BEAMS (include/rplgpu_msg.h)
+MAX_FILTER_WINDOW = 64   # RPLGPU_MAX_FILTER_WINDOW (include/rplgpu_msg.h)
 
 SL_RESULT_OK = 0
 SL_RESULT_OPERATION_FAIL = 0x80008001
@@ -97,6 +98,11 @@ ABI_SYMBOLS = [
     "rplgpu_scan_merge_edges",
     "rplgpu_merge_scans_dev",
     "rplgpu_merged_laserscan_msgs_dev",
+    "rplgpu_default_scan_filter",
+    "rplgpu_scan_filter_check",
+    "rplgpu_filter_laserscan_batch_dev",
+    "rplgpu_filter_merged_scans_dev",
+    "rplgpu_filter_laserscan",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -205,6 +211,33 @@ class ScanMerge(C.Structure):
         ("range_max", C.c_float),
         ("scan_time", C.c_float),
     ]
+
+
+class ScanFilter(C.Structure):
+    """Mirror of ``rplgpu_scan_filter_t`` (E10: scan-shadow and speckle filters on a LaserScan)."""
+
+    _fields_ = [
+        ("shadow_enable", C.c_int32),
+        ("shadow_min_angle", C.c_float),
+        ("shadow_max_angle", C.c_float),
+        ("shadow_window", C.c_uint32),
+        ("shadow_neighbors", C.c_uint32),
+        ("speckle_enable", C.c_int32),
+        ("speckle_max_range_difference", C.c_float),
+        ("speckle_min_run", C.c_uint32),
+        ("circular", C.c_int32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "ScanFilter":
+        """The library's own defaults (``rplgpu_default_scan_filter``), then the overrides."""
+        f = cls()
+        load_library().rplgpu_default_scan_filter(C.byref(f))
+        for k, v in kw.items():
+            if not hasattr(f, k):
+                raise AttributeError(k)
+            setattr(f, k, v)
+        return f
 
 
 def library_path() -> Path:
@@ -338,6 +371,14 @@ def load_library() -> C.CDLL:
                                            C.POINTER(ScanMerge), vp, vp, vp, vp]
     lib.rplgpu_merged_laserscan_msgs_dev.argtypes = [vp, vp, vp, u32, C.POINTER(ScanMerge), cs, vp, vp, u32,
                                                      vp, vp]
+    lib.rplgpu_default_scan_filter.argtypes = [C.POINTER(ScanFilter)]
+    lib.rplgpu_default_scan_filter.restype = None
+    lib.rplgpu_scan_filter_check.argtypes = [C.POINTER(ScanFilter), vp]
+    lib.rplgpu_filter_laserscan_batch_dev.argtypes = [vp, vp, vp, u32, vp, u32, C.POINTER(Params),
+                                                      C.POINTER(ScanFilter), vp, vp, vp]
+    lib.rplgpu_filter_merged_scans_dev.argtypes = [vp, vp, vp, u32, C.POINTER(ScanMerge),
+                                                   C.POINTER(ScanFilter), vp, vp, vp]
+    lib.rplgpu_filter_laserscan.argtypes = [vp, vp, vp, u32, C.c_float, C.POINTER(ScanFilter), vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -589,6 +630,36 @@ class RplGpu:
         self._check(self._lib.rplgpu_merged_laserscan_msgs_dev(
             self._h, d_ranges, d_intens, G, C.byref(merge), frame_id.encode(), d_stamps, d_msgs,
             msg_stride, d_msg_len, d_status))
+
+    def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
+                                   B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
+                                   d_intens_out: int, d_removed: int = 0):
+        """E10: the LaserScans of a batch through the scan-shadow and speckle filters (same layout out);
+        d_removed: 2 words per scan (by shadow, by speckle in addition)."""
+        self._check(self._lib.rplgpu_filter_laserscan_batch_dev(
+            self._h, d_ranges, d_intens, n_stride, d_beam_count, B, C.byref(params), C.byref(flt),
+            d_ranges_out, d_intens_out, d_removed))
+
+    def filter_merged_scans_dev(self, d_ranges: int, d_intens: int, G: int, merge: ScanMerge,
+                                flt: ScanFilter, d_ranges_out: int, d_intens_out: int, d_removed: int = 0):
+        """E10 on the G merged scans rplgpu_merge_scans_dev wrote."""
+        self._check(self._lib.rplgpu_filter_merged_scans_dev(
+            self._h, d_ranges, d_intens, G, C.byref(merge), C.byref(flt), d_ranges_out, d_intens_out,
+            d_removed))
+
+    def filter_laserscan(self, ranges: np.ndarray, intens: np.ndarray, angle_increment: float,
+                         flt: ScanFilter):
+        """E10, one scan, host buffers: ``(ranges_out, intensities_out, (by shadow, by speckle))``."""
+        ranges = np.ascontiguousarray(ranges, np.float32)
+        intens = np.ascontiguousarray(intens, np.float32)
+        count = len(ranges)
+        r_out = np.empty(max(count, 1), np.float32)
+        i_out = np.empty(max(count, 1), np.float32)
+        removed = np.zeros(2, np.uint32)
+        self._check(self._lib.rplgpu_filter_laserscan(
+            self._h, ranges.ctypes.data, intens.ctypes.data, count, angle_increment, C.byref(flt),
+            r_out.ctypes.data, i_out.ctypes.data, removed.ctypes.data))
+        return r_out[:count], i_out[:count], (int(removed[0]), int(removed[1]))
 
     def cloud_fused_cells_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int,
                               params: Params, d_motion: int, d_pose2d: int, d_cells: int,
@@ -941,3 +1012,13 @@ def scan_merge_edges(merge: ScanMerge):
     if rc:
         raise RplGpuError(rc, "rplgpu_scan_merge_edges")
     return edges, inc[0]
+
+
+def scan_filter_check(flt: ScanFilter) -> np.ndarray:
+    """Host only: validates an E10 filter by the library's own rplgpu_scan_filter_check and returns
+    (cmin, smin, cmax, smax) float32.  Raises RplGpuError(ERR_INVALID_ARG) for a filter it refuses."""
+    dirs = np.zeros(4, np.float32)
+    rc = load_library().rplgpu_scan_filter_check(C.byref(flt), dirs.ctypes.data)
+    if rc:
+        raise RplGpuError(rc, "rplgpu_scan_filter_check")
+    return dirs

@@ -225,4 +225,23 @@ hipError_t launch_msg_merged(hipStream_t s, const float *ranges, const float *in
                              uint32_t G, const rplgpu_stamp_t *stamps, const rplmsg::Prefix &P,
                              uint8_t *msgs, uint32_t msg_stride, uint32_t *msg_len, uint32_t *status);
 
+// E10: scan-shadow and speckle filters on LaserScan arrays (rpl_filter.hip, include/rplgpu_msg.h)
+constexpr uint32_t kFilterIncModeB = 0;  // inc per scan from its beam count, denominator max(count - 1, 1)
+constexpr uint32_t kFilterIncModeA = 1;  // ... denominator count
+constexpr uint32_t kFilterIncGiven = 2;  // FilterK::inc as it stands
+struct FilterK {
+  uint32_t shadow, speckle, circular;
+  uint32_t W, N, L;
+  float D;
+  float cmin, smin, cmax, smax;  // rplgpu_scan_filter_check's dirs
+  uint32_t inc_mode;
+  float inc;
+  uint32_t count;                // beams of every scan when there is no beam_count array
+};
+// beam_count == nullptr: B scans of k.count beams each, n_stride apart (the E9 layout with n_stride = count);
+// removed (optional): 2 words per scan, cleared by the caller
+hipError_t launch_filter_scans(hipStream_t s, const float *ranges, const float *intens, uint32_t n_stride,
+                               const uint32_t *beam_count, uint32_t B, const FilterK &k, float *ranges_out,
+                               float *intens_out, uint32_t *removed);
+
 }  // namespace rpl

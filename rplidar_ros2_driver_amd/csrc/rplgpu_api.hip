@@ -1222,6 +1222,157 @@ int32_t rplgpu_merged_laserscan_msgs_dev(rplgpu_handle_t h, const float *d_range
   return RPLGPU_OK;
 }
 
+// ---- E10: scan-shadow and speckle filters on LaserScan arrays (include/rplgpu_msg.h) ---------------
+
+void rplgpu_default_scan_filter(rplgpu_scan_filter_t *f) {
+  if (!f) return;
+  f->shadow_enable = 1;
+  f->shadow_min_angle = (float)(10.0 * M_PI / 180.0);
+  f->shadow_max_angle = (float)(170.0 * M_PI / 180.0);
+  f->shadow_window = 2;
+  f->shadow_neighbors = 1;
+  f->speckle_enable = 1;
+  f->speckle_max_range_difference = 0.05f;
+  f->speckle_min_run = 4;
+  f->circular = 1;
+}
+
+int32_t rplgpu_scan_filter_check(const rplgpu_scan_filter_t *f, float dirs[4]) {
+  if (!f) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(f->shadow_min_angle) || !std::isfinite(f->shadow_max_angle) ||
+      !std::isfinite(f->speckle_max_range_difference))
+    return RPLGPU_ERR_INVALID_ARG;
+  const double lo = (double)f->shadow_min_angle, hi = (double)f->shadow_max_angle;
+  if (!(0.0 < lo && lo < M_PI / 2 && M_PI / 2 < hi && hi < M_PI)) return RPLGPU_ERR_INVALID_ARG;
+  if (f->shadow_window < 1u || f->shadow_window > RPLGPU_MAX_FILTER_WINDOW ||
+      f->shadow_neighbors > RPLGPU_MAX_FILTER_WINDOW || f->speckle_min_run < 1u ||
+      f->speckle_min_run > RPLGPU_MAX_FILTER_WINDOW || !(f->speckle_max_range_difference >= 0.0f))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (dirs) {
+    dirs[0] = (float)std::cos(lo);
+    dirs[1] = (float)std::sin(lo);
+    dirs[2] = (float)std::cos(hi);
+    dirs[3] = (float)std::sin(hi);
+  }
+  return RPLGPU_OK;
+}
+
+namespace {
+
+int32_t filter_kernel_args(rplgpu_ctx *c, const rplgpu_scan_filter_t *f, rpl::FilterK *k) {
+  float dirs[4];
+  if (rplgpu_scan_filter_check(f, dirs) != RPLGPU_OK) {
+    c->err = "invalid rplgpu_scan_filter_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  std::memset(k, 0, sizeof(*k));
+  k->shadow = f->shadow_enable ? 1u : 0u;
+  k->speckle = f->speckle_enable ? 1u : 0u;
+  k->circular = f->circular ? 1u : 0u;
+  k->W = f->shadow_window;
+  k->N = f->shadow_neighbors;
+  k->L = f->speckle_min_run;
+  k->D = f->speckle_max_range_difference;
+  k->cmin = dirs[0];
+  k->smin = dirs[1];
+  k->cmax = dirs[2];
+  k->smax = dirs[3];
+  return RPLGPU_OK;
+}
+
+}  // namespace
+
+int32_t rplgpu_filter_laserscan_batch_dev(rplgpu_handle_t h, const float *d_ranges, const float *d_intensities,
+                                          uint32_t n_stride, const uint32_t *d_beam_count, uint32_t B,
+                                          const rplgpu_params_t *p, const rplgpu_scan_filter_t *f,
+                                          float *d_ranges_out, float *d_intensities_out, uint32_t *d_removed) {
+  if (!h || !p || !f) return RPLGPU_ERR_INVALID_ARG;
+  rpl::FilterK k;
+  if (int32_t rc = filter_kernel_args(h, f, &k)) return rc;
+  if (B == 0) return RPLGPU_OK;
+  if (!d_ranges || !d_intensities || !d_beam_count || !d_ranges_out || !d_intensities_out || n_stride == 0)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (d_ranges_out == d_ranges || d_intensities_out == d_intensities) {
+    h->err = "rplgpu_filter_laserscan_batch_dev: the filters do not work in place";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  k.inc_mode = p->scan_processing ? rpl::kFilterIncModeA : rpl::kFilterIncModeB;
+  RPL_HIP(h, hipSetDevice(h->device));
+  if (d_removed) RPL_HIP(h, hipMemsetAsync(d_removed, 0, (size_t)B * 8u, h->stream));
+  RPL_HIP(h, rpl::launch_filter_scans(h->stream, d_ranges, d_intensities, n_stride, d_beam_count, B, k,
+                                      d_ranges_out, d_intensities_out, d_removed));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_filter_merged_scans_dev(rplgpu_handle_t h, const float *d_ranges, const float *d_intensities,
+                                       uint32_t G, const rplgpu_scan_merge_t *m, const rplgpu_scan_filter_t *f,
+                                       float *d_ranges_out, float *d_intensities_out, uint32_t *d_removed) {
+  if (!h || !m || !f) return RPLGPU_ERR_INVALID_ARG;
+  rpl::FilterK k;
+  if (int32_t rc = filter_kernel_args(h, f, &k)) return rc;
+  float inc = 0.0f;
+  if (rplgpu_scan_merge_edges(m, nullptr, &inc) != RPLGPU_OK) {
+    h->err = "rplgpu_filter_merged_scans_dev: invalid rplgpu_scan_merge_t";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0) return RPLGPU_OK;
+  if (!d_ranges || !d_intensities || !d_ranges_out || !d_intensities_out) return RPLGPU_ERR_INVALID_ARG;
+  if (d_ranges_out == d_ranges || d_intensities_out == d_intensities) {
+    h->err = "rplgpu_filter_merged_scans_dev: the filters do not work in place";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  k.inc_mode = rpl::kFilterIncGiven;
+  k.inc = inc;
+  k.count = m->count;
+  RPL_HIP(h, hipSetDevice(h->device));
+  if (d_removed) RPL_HIP(h, hipMemsetAsync(d_removed, 0, (size_t)G * 8u, h->stream));
+  RPL_HIP(h, rpl::launch_filter_scans(h->stream, d_ranges, d_intensities, m->count, nullptr, G, k,
+                                      d_ranges_out, d_intensities_out, d_removed));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_filter_laserscan(rplgpu_handle_t h, const float *ranges, const float *intensities, uint32_t count,
+                                float angle_increment, const rplgpu_scan_filter_t *f, float *ranges_out,
+                                float *intensities_out, uint32_t removed[2]) {
+  if (!h || !f) return RPLGPU_ERR_INVALID_ARG;
+  rpl::FilterK k;
+  if (int32_t rc = filter_kernel_args(h, f, &k)) return rc;
+  if (!std::isfinite(angle_increment) || !(angle_increment > 0.0f)) {
+    h->err = "rplgpu_filter_laserscan: angle_increment must be finite and positive";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (count && (!ranges || !intensities || !ranges_out || !intensities_out)) return RPLGPU_ERR_INVALID_ARG;
+  if (count && (ranges_out == ranges || intensities_out == intensities)) {
+    h->err = "rplgpu_filter_laserscan: the filters do not work in place";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (count > h->max_n) return RPLGPU_ERR_CAPACITY;
+  if (removed) removed[0] = removed[1] = 0u;
+  if (count == 0) return RPLGPU_OK;
+  k.inc_mode = rpl::kFilterIncGiven;
+  k.inc = angle_increment;
+  k.count = count;
+  RPL_HIP(h, hipSetDevice(h->device));
+  // staging as rplgpu_laserscan_to_cloud: ranges | intensities in (d_nodes holds 8 B per sample),
+  // ranges | intensities | the two counts out (d_out holds 16 B per sample)
+  const size_t n = count;
+  std::memcpy(h->h_pin, ranges, n * 4);
+  std::memcpy(h->h_pin + n * 4, intensities, n * 4);
+  RPL_HIP(h, hipMemcpyAsync(h->d_nodes, h->h_pin, n * 8, hipMemcpyHostToDevice, h->stream));
+  const float *d_r = reinterpret_cast<const float *>(h->d_nodes);
+  float *d_o = reinterpret_cast<float *>(h->d_out);
+  uint32_t *d_rm = reinterpret_cast<uint32_t *>(h->d_out + n * 8);
+  RPL_HIP(h, hipMemsetAsync(d_rm, 0, 8, h->stream));
+  RPL_HIP(h, rpl::launch_filter_scans(h->stream, d_r, d_r + n, count, nullptr, 1, k, d_o, d_o + n, d_rm));
+  unsigned char *h_out = stage_out(h);
+  RPL_HIP(h, hipMemcpyAsync(h_out, h->d_out, n * 8 + 8, hipMemcpyDeviceToHost, h->stream));
+  RPL_HIP(h, hipStreamSynchronize(h->stream));
+  std::memcpy(ranges_out, h_out, n * 4);
+  std::memcpy(intensities_out, h_out + n * 4, n * 4);
+  if (removed) std::memcpy(removed, h_out + n * 8, 8);
+  return RPLGPU_OK;
+}
+
 // `defer_listed`: see voxel_with_ror (single-scan callers; d_status must be given then)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,
