@@ -110,7 +110,9 @@ int32_t rplgpu_scan_to_cloud_msg(rplgpu_handle_t h, const rplgpu_node_t *nodes, 
 /* From the outputs of rplgpu_laserscan_batch_dev (same d_ranges / d_intensities / n_stride /
  * d_beam_count): message b at d_msgs + b*msg_stride (msg_stride a multiple of 4), its length
  * in d_msg_len[b]; 0 = not published (beam count 0) or msg_stride too small (then d_status[b]
- * gets RPLGPU_SCAN_OUT_TRUNCATED).  The scalars are computed on the device with the
+ * gets RPLGPU_SCAN_OUT_TRUNCATED).  A scan has count = min(d_beam_count[b], n_stride) beams, as in
+ * E7 and E10: a count above the stride never reads the next scan's slot, and the message (its
+ * scalars and length words included) is that of n_stride beams.  The scalars are computed on the device with the
  * reference's own expressions (:623-627,:634-638,:665-669; IEEE fp64 divides).
  * d_stamps: B stamps; d_scan_duration: B doubles; both device pointers. */
 int32_t rplgpu_laserscan_msgs_dev(rplgpu_handle_t h, const float *d_ranges,

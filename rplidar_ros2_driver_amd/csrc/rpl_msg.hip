@@ -34,7 +34,7 @@ __global__ __launch_bounds__(kMsgThreads) void k_msg_laserscan(
     rplmsg::Prefix P, uint8_t *__restrict__ msgs, uint32_t msg_stride,
     uint32_t *__restrict__ msg_len, uint32_t *__restrict__ status) {
   const uint32_t b = blockIdx.y;
-  const uint32_t bc = beam_count[b];
+  const uint32_t bc = min(beam_count[b], n_stride);  // never past the scan's slot (as E7 and E10)
   const uint64_t total = (uint64_t)P.len + 8ull * bc + 4ull;
   const bool fits = total <= msg_stride;
   if (blockIdx.x == 0 && threadIdx.x == 0) {

@@ -123,6 +123,14 @@ namespace {
 constexpr uint32_t kMaskStride = rpl::kMaxN / 32u;  // keep-mask words per scan
 constexpr size_t kTail = 64;  // bytes behind a staging region for the words that travel with it
 
+// Single-scan staging (pinned, one allocation): nodes | tail | results (16 B / sample) | tail | flag.
+// Both regions are rounded up to 64 bytes, so that for EVERY capacity the result area (it receives
+// 16-byte stores) and the flag word's cache line start on a 64-byte boundary.
+constexpr size_t round64(size_t v) { return (v + 63u) & ~(size_t)63u; }
+constexpr size_t stage_out_off(size_t max_n) { return round64(max_n * 8) + kTail; }
+constexpr size_t stage_flag_off(size_t max_n) { return stage_out_off(max_n) + round64(max_n * 16) + kTail; }
+constexpr size_t stage_bytes(size_t max_n) { return stage_flag_off(max_n) + kTail; }
+
 thread_local std::string g_create_err;
 
 #define RPL_HIP(ctx, call)                                                              \
@@ -452,7 +460,7 @@ int32_t ensure_idx_checked(rplgpu_ctx *c) {
 }
 
 // Single-scan staging (pinned host side): nodes | length word ... results | result words.
-inline unsigned char *stage_out(const rplgpu_ctx *c) { return c->h_pin + (size_t)c->max_n * 8 + kTail; }
+inline unsigned char *stage_out(const rplgpu_ctx *c) { return c->h_pin + stage_out_off(c->max_n); }
 
 // nodes + their count to the device in ONE copy; *d_n = device address of the count word
 int32_t upload_scan(rplgpu_ctx *c, const rplgpu_node_t *nodes, size_t n, const uint32_t **d_n) {
@@ -505,7 +513,7 @@ inline ScanStage stage_scan(rplgpu_ctx *c, const rplgpu_node_t *nodes, size_t n)
   ScanStage s;
   s.d_nodes = reinterpret_cast<const rplgpu_node_t *>(c->d_pin);
   s.d_n = reinterpret_cast<const uint32_t *>(c->d_pin + n * 8);
-  const size_t out_off = (size_t)c->max_n * 8 + kTail;
+  const size_t out_off = stage_out_off(c->max_n);
   s.d_out = c->d_pin + out_off;
   s.h_out = c->h_pin + out_off;
   return s;
@@ -607,8 +615,8 @@ int32_t rplgpu_create(int32_t device_id, uint32_t max_samples_per_scan, uint32_t
   const size_t n = c->max_n;
   // single-scan staging: the length word travels right behind the nodes and the result words
   // right behind the results, so that a call is one copy in and one copy out
-  c->flag_off = n * 8 + n * 16 + 2 * kTail;  // (64-byte aligned: n * 24 + 128)
-  if (hipHostMalloc((void **)&c->h_pin, n * 8 + n * 16 + 3 * kTail, hipHostMallocDefault) != hipSuccess ||
+  c->flag_off = stage_flag_off(n);  // (a cache line of its own, 64-byte aligned for every n)
+  if (hipHostMalloc((void **)&c->h_pin, stage_bytes(n), hipHostMallocDefault) != hipSuccess ||
       hipMalloc((void **)&c->d_nodes, n * 8 + kTail) != hipSuccess ||
       hipMalloc((void **)&c->d_out, n * 16 + kTail) != hipSuccess ||
       hipMalloc((void **)&c->d_small, 128) != hipSuccess ||
@@ -732,6 +740,16 @@ int32_t rplgpu_debug_ascend_sorted(rplgpu_handle_t h, uint32_t *count) {
 }
 // Developer aid (tests): the block-aggregation instance the handle's last voxel batch launch took
 // (0 plain, 1 two-class) — what RPLGPU_VOXEL_AGG_AUTO decided for it.
+// developer aid (tests): the single-scan staging layout a handle of this capacity gets — byte offsets of
+// the result area and of the completion flag in the pinned buffer, and the buffer's size.  Host only.
+int32_t rplgpu_debug_staging_layout(uint32_t max_samples_per_scan, uint64_t out[3]) {
+  if (!out || max_samples_per_scan == 0 || max_samples_per_scan > RPLGPU_MAX_SAMPLES_PER_SCAN)
+    return RPLGPU_ERR_INVALID_ARG;
+  out[0] = stage_out_off(max_samples_per_scan);
+  out[1] = stage_flag_off(max_samples_per_scan);
+  out[2] = stage_bytes(max_samples_per_scan);
+  return RPLGPU_OK;
+}
 int32_t rplgpu_debug_voxel_instance(rplgpu_handle_t h) { return h ? h->last_split : RPLGPU_ERR_INVALID_ARG; }
 int32_t rplgpu_set_ror_mode(rplgpu_handle_t h, int32_t mode) {
   if (!h || (mode != RPLGPU_ROR_INSIDE && mode != RPLGPU_ROR_TWO_KERNELS)) return RPLGPU_ERR_INVALID_ARG;

@@ -640,3 +640,41 @@ def test_fused_voxel_time_alignment(gpu_mode, oracle):
     for g in range(G):
         assert after[0][after[1][g]: after[1][g] + after[2][g]].tobytes() == \
             base[0][base[1][g]: base[1][g] + base[2][g]].tobytes()
+
+
+def test_laserscan_msgs_dev_beam_count_above_the_stride(gpu):
+    """A beam count above n_stride is a scan of n_stride beams (as E7 and E10 clamp it): the message and its
+    length are those of 16 beams, built from the scan's own slot and never from the next one, and with a
+    msg_stride that a message of 100000 beams would fit nothing behind the message is written."""
+    import torch
+    dev = torch.device("cuda:0")
+    B, n = 5, 16
+    rng = np.random.default_rng(16)
+    r = rng.uniform(0.2, 30.0, (B, n)).astype(np.float32)
+    i = rng.uniform(0.0, 60.0, (B, n)).astype(np.float32)
+    p = Params.defaults(range_max=40.0)
+    stamps = np.stack([np.arange(B) + 5, np.arange(B) * 11], 1).astype(np.int32)
+    durs = 0.1 + 0.01 * np.arange(B)
+    want_len = abi.msg_laserscan_layout(len(FID), n).total_len
+    stride = (abi.msg_laserscan_layout(len(FID), 100000).total_len + 3) & ~3
+    # (the arrays are followed by 100000 more floats, so that a library without the clamp reads other values
+    # and never leaves the allocation)
+    pad = np.full(100000, 3.0, np.float32)
+    d_r = torch.from_numpy(np.concatenate([r.reshape(-1), pad])).to(dev)
+    d_i = torch.from_numpy(np.concatenate([i.reshape(-1), pad])).to(dev)
+    d_cnt = torch.full((B,), 100000, dtype=torch.int32, device=dev)
+    d_stamps, d_dur = torch.from_numpy(stamps).to(dev), torch.from_numpy(durs).to(dev)
+    d_msgs = torch.full((B, stride), 0xEE, dtype=torch.uint8, device=dev)
+    d_ml = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    d_st = torch.zeros(B, dtype=torch.int32, device=dev)
+    gpu.laserscan_msgs_dev(d_r.data_ptr(), d_i.data_ptr(), n, d_cnt.data_ptr(), B, p, FID, d_stamps.data_ptr(),
+                           d_dur.data_ptr(), d_msgs.data_ptr(), stride, d_ml.data_ptr(), d_st.data_ptr())
+    gpu.synchronize()
+    msgs, ml = d_msgs.cpu().numpy(), d_ml.cpu().numpy()
+    assert not d_st.cpu().numpy().any()
+    for b in range(B):
+        meta = gpu.fill_meta(p, n, float(durs[b]))
+        want = cdr.laserscan_msg(FID, int(stamps[b, 0]), int(stamps[b, 1]), meta, r[b], i[b])
+        assert ml[b] == len(want) == want_len
+        assert msgs[b, :want_len].tobytes() == want
+        assert np.all(msgs[b, want_len:] == 0xEE)  # the bytes behind it are untouched
