@@ -65,6 +65,9 @@ struct rplgpu_ctx {
   float leaf_checked = 0.0f;
   bool leaf_ok = false;
   bool idx_checked = false, idx_ok = false;  // Mode A bin-index divide, see k_validate_idx
+  // rplgpu_debug_force_ieee_div (tests): bits of rplgpu_debug_fast_div to treat as "validation failed".
+  // Kept apart from the *_ok flags: they go on recording what the validators found.
+  uint32_t force_ieee = 0;
   unsigned long long *dbg = nullptr;  // developer aid: per-block phase cycle counters
   uint32_t *cell_keys = nullptr;      // optional cell-key output of the voxel kernel (rplgpu_set_cell_key_output)
   const float *scan_t0 = nullptr;     // optional per-scan time offsets of E6 (rplgpu_set_scan_time_offsets_dev)
@@ -410,15 +413,27 @@ int32_t check_batch(rplgpu_ctx *c, const void *nodes, uint32_t n_stride, const v
 
 // Exhaustively compare the mul+2*FMA divide with the IEEE divide for divisor d on the
 // device (about 2.4e9 operands, a few ms).  Returns RPLGPU_OK and sets *ok.
-int32_t validate_divisor(rplgpu_ctx *c, float d, uint32_t e_lo, uint32_t e_hi, bool *ok) {
+// (`rd`: the reciprocal the cheap divide is given — RN(1/d) for every caller but rplgpu_debug_validate_div)
+int32_t count_div_mismatches(rplgpu_ctx *c, float d, float rd, uint32_t e_lo, uint32_t e_hi, uint32_t *count) {
   uint32_t zero = 0, bad = 1;
   RPL_HIP(c, hipMemcpyAsync(c->d_small + 8, &zero, 4, hipMemcpyHostToDevice, c->stream));
-  RPL_HIP(c, rpl::launch_validate_div(c->stream, d, 1.0f / d, e_lo, e_hi, c->d_small + 8));
+  RPL_HIP(c, rpl::launch_validate_div(c->stream, d, rd, e_lo, e_hi, c->d_small + 8));
   RPL_HIP(c, hipMemcpyAsync(&bad, c->d_small + 8, 4, hipMemcpyDeviceToHost, c->stream));
   RPL_HIP(c, hipStreamSynchronize(c->stream));
+  *count = bad;
+  return RPLGPU_OK;
+}
+int32_t validate_divisor(rplgpu_ctx *c, float d, uint32_t e_lo, uint32_t e_hi, bool *ok) {
+  uint32_t bad = 1;
+  if (int32_t rc = count_div_mismatches(c, d, 1.0f / d, e_lo, e_hi, &bad)) return rc;
   *ok = (bad == 0);
   return RPLGPU_OK;
 }
+
+// What the launch sites consult: the validators' verdicts, less what rplgpu_debug_force_ieee_div refuses.
+inline bool use_fast_d4000(const rplgpu_ctx *c) { return c->div4000_ok && !(c->force_ieee & 1u); }
+inline bool use_fast_leaf(const rplgpu_ctx *c) { return c->leaf_ok && !(c->force_ieee & 2u); }
+inline bool use_fast_idx(const rplgpu_ctx *c) { return c->idx_ok && !(c->force_ieee & 4u); }
 
 // publish_scan on the handle's stream: Mode A (rpl_laserscan.hip) or Mode B.  The cheap
 // bin-index divide of Mode A is used only after it was compared with the IEEE divide for
@@ -436,7 +451,7 @@ int32_t run_laserscan(rplgpu_ctx *c, const void *d_nodes, uint32_t n_stride,
   }
   if (int32_t vrc = ensure_idx_checked(c)) return vrc;
   RPL_HIP(c, rpl::launch_laserscan_a(c->stream, d_nodes, n_stride, d_n_per_scan, B, kp, tables_of(c),
-                                     c->d_inc, c->d_rinc, c->idx_ok && c->div4000_ok, d_ranges,
+                                     c->d_inc, c->d_rinc, use_fast_idx(c) && use_fast_d4000(c), d_ranges,
                                      d_intens, d_beam_count, n_given));
   return RPLGPU_OK;
 }
@@ -629,7 +644,9 @@ int32_t rplgpu_create(int32_t device_id, uint32_t max_samples_per_scan, uint32_t
     return fail(RPLGPU_ERR_HIP);
   }
   c->need_sort_cap = c->max_b;
-  if (hipMemset(c->d_need_sort, 0, 4) != hipSuccess) {  // (the list starts, and is kept, empty between calls)
+  // (the sort list starts, and is kept, empty between calls; the count of work items E5-inside listed is 0
+  // until a launch of voxel_with_ror says otherwise — rplgpu_debug_ror_listed reads it on any handle)
+  if (hipMemset(c->d_need_sort, 0, 4) != hipSuccess || hipMemset(c->d_redo, 0, 4) != hipSuccess) {
     c->err = "staging allocation failed";
     return fail(RPLGPU_ERR_HIP);
   }
@@ -722,7 +739,7 @@ int32_t rplgpu_set_voxel_aggregation(rplgpu_handle_t h, int32_t mode) {
 
 // Developer aid (not part of rplgpu.h): device buffer of 16*B u64 receiving, per work item, the
 // shader cycles k_cloud_voxel spent in its phases (slots 0-7: stream, ..., emit; 8-12: the
-// streaming loop's sub-phases).  0 = fast divides rejected, 1 = accepted, via rplgpu_debug_fast_div.
+// streaming loop's sub-phases).
 int32_t rplgpu_debug_set_cycle_buffer(rplgpu_handle_t h, void *d_buf) {
   if (!h) return RPLGPU_ERR_INVALID_ARG;
   h->dbg = (unsigned long long *)d_buf;
@@ -767,6 +784,25 @@ int32_t rplgpu_debug_ror_listed(rplgpu_handle_t h, uint32_t *count) {
 int32_t rplgpu_debug_fast_div(rplgpu_handle_t h) {
   if (!h) return RPLGPU_ERR_INVALID_ARG;
   return (h->div4000_ok ? 1 : 0) | (h->leaf_ok ? 2 : 0) | (h->idx_ok ? 4 : 0);
+}
+// Developer aid (tests): run the IEEE-divide kernel instances although validation passed.  `mask` has
+// the bits of rplgpu_debug_fast_div (1: / 4000, 2: / leaf, 4: Mode A's bin index); while a bit is set,
+// every launch site behaves as if that validation had failed.  Holds, across re-validations of the
+// leaf, until cleared with mask = 0; rplgpu_debug_fast_div goes on returning what validation found.
+int32_t rplgpu_debug_force_ieee_div(rplgpu_handle_t h, uint32_t mask) {
+  if (!h || mask > 7u) return RPLGPU_ERR_INVALID_ARG;
+  h->force_ieee = mask;
+  return RPLGPU_OK;
+}
+// Developer aid (tests): k_validate_div for divisor `d` with a reciprocal of the caller's choice, over
+// the operands of biased exponent e_lo .. e_hi — how many of the compared quotients differ from the
+// IEEE divide (three forms are compared per operand; the count is a 32-bit word, so a range of more than
+// 170 exponents can wrap it).  Waits for the stream.
+int32_t rplgpu_debug_validate_div(rplgpu_handle_t h, float d, float rd, uint32_t e_lo, uint32_t e_hi,
+                                  uint32_t *mismatches) {
+  if (!h || !mismatches || e_lo > e_hi || e_hi > 254u) return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  return count_div_mismatches(h, d, rd, e_lo, e_hi, mismatches);
 }
 
 int32_t rplgpu_synchronize(rplgpu_handle_t h) {
@@ -845,9 +881,9 @@ static int32_t prepare_cloud(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, ui
       if (vrc) return vrc;
       h->leaf_checked = p->voxel_leaf;
     }
-    kp.fast_div = (h->div4000_ok && h->leaf_ok) ? 1 : 0;
+    kp.fast_div = (use_fast_d4000(h) && use_fast_leaf(h)) ? 1 : 0;
   }
-  kp.fast_d4000 = h->div4000_ok ? 1 : 0;
+  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
   kp.dbg = h->dbg;
   kp.cell_keys = h->cell_keys;
   *mask_out = nullptr;
@@ -1172,7 +1208,7 @@ int32_t rplgpu_merge_scans_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, 
   if (!h->mkeys_clean)  // a new allocation, or a call that failed between the two launches
     RPL_HIP(h, hipMemsetAsync(h->d_mkeys, 0xFF, h->mkeys_cap * sizeof(unsigned long long), h->stream));
   rpl::KParams kp = to_kparams(*p);
-  kp.fast_d4000 = h->div4000_ok ? 1 : 0;
+  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
   const rpl::Tables T = tables_of(h);
   const uint32_t *mask = nullptr;
   if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E8's two-kernel path applies
@@ -2109,7 +2145,7 @@ int32_t rplgpu_scan_to_laserscan_msg(rplgpu_handle_t h, const rplgpu_node_t *nod
       // Mode A on the validated fast path: ONE kernel bins the scan and writes the message
       // around and into its arrays (the arrays never exist outside the message)
       if (int32_t vrc = ensure_idx_checked(h)) return vrc;
-      if (h->idx_ok && h->div4000_ok && (reinterpret_cast<uintptr_t>(d_msg) & 3u) == 0u) {
+      if (use_fast_idx(h) && use_fast_d4000(h) && (reinterpret_cast<uintptr_t>(d_msg) & 3u) == 0u) {
         rpl::LsMsgOut mo;
         mo.P = P;
         mo.msg = reinterpret_cast<uint32_t *>(d_msg);
