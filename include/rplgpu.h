@@ -356,9 +356,13 @@ int32_t rplgpu_set_voxel_aggregation(rplgpu_handle_t h, int32_t mode);
  * work item with more open samples than that (clutter: > 256 after the index test or > 8 after the
  * window) is redone by the two kernels of TWO_KERNELS behind the launch.  TWO_KERNELS: k_ror_mask
  * writes one keep bit per sample, the voxel kernel reads the scan again with the mask (rounds 1-5;
- * also what any launch uses whose divides were not validated on this device, and the single-scan call
- * rplgpu_scan_to_cloud below 8192 samples, where index neighbours are mostly farther apart than the
- * radius).  rplgpu_cloud_batch_dev (per-scan regions) follows the mode as well. */
+ * also what any launch uses whose divides were not validated on this device).
+ * rplgpu_cloud_batch_dev (per-scan regions) follows the mode as well.  The single-scan call
+ * rplgpu_scan_to_cloud depends on its staging: with zero-copy staging (the default) it uses the two
+ * kernels below 8192 samples, where index neighbours are mostly farther apart than the radius, and from
+ * 8192 samples on follows the mode, redoing a scan the kernel lists with the two kernels; with DMA
+ * staging (RPLGPU_ZERO_COPY=0) it is rplgpu_cloud_batch_dev with one scan and follows the mode at every
+ * size. */
 #define RPLGPU_ROR_INSIDE 0
 #define RPLGPU_ROR_TWO_KERNELS 1
 int32_t rplgpu_set_ror_mode(rplgpu_handle_t h, int32_t mode);

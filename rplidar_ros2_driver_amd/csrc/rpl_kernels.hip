@@ -1028,18 +1028,13 @@ hipError_t launch_laserscan_raw(hipStream_t s, const void *nodes, uint32_t n_str
 
 hipError_t launch_cloud(hipStream_t s, const void *nodes, uint32_t n_stride,
                         const uint32_t *n_per_scan, uint32_t B, const KParams &p, const Tables &T,
-                        bool voxel, const uint32_t *keepmask, uint32_t mask_stride, float *xyzi,
+                        const uint32_t *keepmask, uint32_t mask_stride, float *xyzi,
                         uint32_t out_stride, uint32_t *n_points, uint32_t *status,
                         const float *motion) {
   if (B == 0) return hipSuccess;
-  if (voxel) {
-    return launch_cloud_voxel(s, nodes, n_stride, n_per_scan, B, p, T, keepmask, mask_stride, xyzi,
-                              out_stride, n_points, status);
-  } else {
-    hipLaunchKernelGGL(k_cloud, dim3(B), dim3(kBlock), 0, s, (const uint2 *)nodes, n_stride,
-                       n_per_scan, p, T, keepmask, mask_stride, (float4 *)xyzi, out_stride,
-                       n_points, status, motion);
-  }
+  hipLaunchKernelGGL(k_cloud, dim3(B), dim3(kBlock), 0, s, (const uint2 *)nodes, n_stride,
+                     n_per_scan, p, T, keepmask, mask_stride, (float4 *)xyzi, out_stride,
+                     n_points, status, motion);
   return hipGetLastError();
 }
 

@@ -15,10 +15,19 @@ struct Prefix;
 
 namespace rpl {
 
-// `need_sort`: B + 1 words of scratch (how many / which scans the second, sorting kernel has to redo)
-// status bit of a scan that launch_ascend(..., defer_sort) left for launch_ascend_sort (internal: the
-// sorting kernel rewrites the status word without it)
+// Internal status bits, what a kernel leaves in a status word for the host code behind it.  kAscendUnsorted: a
+// scan that launch_ascend(..., defer_sort) left for launch_ascend_sort (the sorting kernel rewrites the word
+// without it).  kRorListedBit: a work item the voxel kernel's ROR instance left to the two kernels (the listed
+// launches overwrite it; the single-scan entry points look for it instead of launching them blind).  The shared
+// value is safe: the one is only ever written to an ascend status word, the other to a cloud status word, and
+// both are cleared before the word reaches the caller.
 constexpr uint32_t kAscendUnsorted = 0x80000000u;
+constexpr uint32_t kRorListedBit = 0x80000000u;
+constexpr uint32_t kScanStatusBits =
+    RPLGPU_SCAN_ALL_INVALID | RPLGPU_SCAN_CELL_RANGE | RPLGPU_SCAN_TABLE_FULL | RPLGPU_SCAN_OUT_TRUNCATED;
+static_assert((kAscendUnsorted & kScanStatusBits) == 0, "internal ascend bit overlaps RPLGPU_SCAN_*");
+static_assert((kRorListedBit & kScanStatusBits) == 0, "internal cloud bit overlaps RPLGPU_SCAN_*");
+// `need_sort`: B + 1 words of scratch (how many / which scans the second, sorting kernel has to redo)
 hipError_t launch_ascend(hipStream_t s, void *nodes, uint32_t n_stride, const uint32_t *n_per_scan,
                          uint32_t B, uint32_t *status, uint32_t *need_sort, bool defer_sort = false,
                          uint32_t *sort_stat = nullptr);
@@ -51,33 +60,44 @@ hipError_t launch_validate_idx(hipStream_t s, const Tables &T, const float *inc_
 hipError_t launch_laserscan_raw(hipStream_t s, const void *nodes, uint32_t n_stride,
                                 const uint32_t *n_per_scan, uint32_t B, const KParams &p,
                                 float *ranges, float *intens, uint32_t *beam_count);
-// status of a work item the voxel kernel's ROR instance left to the two kernels (internal: the listed launches
-// overwrite it; the single-scan entry points look for it instead of launching them blind)
-constexpr uint32_t kRorListedBit = 0x80000000u;
+// The plain cloud (E1 .. E3, E5 by mask; the voxelised one: launch_cloud_voxel).
 // `keepmask` (optional): one bit per sample from launch_ror_mask, `mask_stride` words per scan.
 hipError_t launch_cloud(hipStream_t s, const void *nodes, uint32_t n_stride,
                         const uint32_t *n_per_scan, uint32_t B, const KParams &p, const Tables &T,
-                        bool voxel, const uint32_t *keepmask, uint32_t mask_stride, float *xyzi,
+                        const uint32_t *keepmask, uint32_t mask_stride, float *xyzi,
                         uint32_t out_stride, uint32_t *n_points, uint32_t *status,
-                        const float *motion = nullptr);  // E6 de-skew (plain cloud only)
-hipError_t launch_cloud_voxel(hipStream_t s, const void *nodes, uint32_t n_stride,
-                              const uint32_t *n_per_scan, uint32_t B, const KParams &p,
-                              const Tables &T, const uint32_t *keepmask, uint32_t mask_stride,
-                              float *xyzi, uint32_t out_stride, uint32_t *n_points,
-                              uint32_t *status, float *arena = nullptr,
-                              unsigned long long arena_capacity = 0,
-                              unsigned long long *arena_cursor = nullptr,
-                              unsigned long long *scan_start = nullptr,
-                              // E8: `group` consecutive scans share one grid; per-scan motion
-                              // (vx, vy, wz, dt) and planar pose (r00 r01 tx r10 r11 ty), optional
-                              uint32_t group = 1, const float *motion = nullptr,
-                              const float *pose2d = nullptr,
-                              // what the arena holds: 0 = 16-byte points, 1 = 12-byte points (x, y,
-                              // intensity: the exchange payload), 2 = 32-byte cell records (rplgpu_cell_t)
-                              int arena_form = 0,
-                              // E5 (round 6): 1 = inside the pass (arena launches, validated divides; items it
-                              // cannot settle go on T.redo), 2 = the items of T.redo with `keepmask`
-                              int ror_mode = 0);
+                        const float *motion = nullptr);  // E6 de-skew
+// One launch of the voxel kernel (rpl_voxel.hip).  What the arena holds: 16-byte points, 12-byte points
+// (x, y, intensity: the exchange payload), 32-byte cell records (rplgpu_cell_t)
+enum class ArenaForm : int { kXyzi = 0, kXyi = 1, kCells = 2 };
+// E5 (round 6): not in the kernel (`keepmask`, if given, is all of it), inside the pass (validated divides; items
+// it cannot settle go on T.redo), the items of T.redo with `keepmask`
+enum class RorMode : int { kNone = 0, kInside = 1, kListed = 2 };
+struct VoxelLaunch {
+  // input: B scans of n_per_scan[b] samples, n_stride apart (the first four members, in this order)
+  const void *nodes = nullptr;
+  uint32_t n_stride = 0;
+  const uint32_t *n_per_scan = nullptr;
+  uint32_t B = 0;
+  // E8: `group` consecutive scans share one grid; per-scan motion (vx, vy, wz, dt) and planar pose
+  // (r00 r01 tx r10 r11 ty), optional
+  uint32_t group = 1;
+  const float *motion = nullptr, *pose2d = nullptr;
+  // (optional) one bit per sample from launch_ror_mask, `mask_stride` words per scan
+  const uint32_t *keepmask = nullptr;
+  uint32_t mask_stride = 0;
+  RorMode ror = RorMode::kNone;
+  // output: per-scan regions xyzi + b * out_stride, or (arena given) one arena in which item b is
+  // arena[scan_start[b] .. + n_points[b]) and *arena_cursor ends up as the total
+  float *xyzi = nullptr;
+  uint32_t out_stride = 0;
+  float *arena = nullptr;
+  uint64_t arena_capacity = 0;
+  uint64_t *arena_cursor = nullptr, *scan_start = nullptr;
+  ArenaForm form = ArenaForm::kXyzi;
+  uint32_t *n_points = nullptr, *status = nullptr;  // per work item
+};
+hipError_t launch_cloud_voxel(hipStream_t s, const VoxelLaunch &v, const KParams &p, const Tables &T);
 // record stores k_cloud_voxel needs: one per resident workgroup (two per CU) ...
 uint32_t voxel_max_workgroups(uint32_t n_cu);
 // ... of this many 16-byte entries for work items of `group` scans of `n_stride` samples: every

@@ -41,7 +41,7 @@
 // the scalar compare masks), one without is run past the wave's 128 samples, then listed for ror_resolve
 // (64 indices either side, then the whole scan); a sample settled late joins the queue as a record of its
 // own.  A scan with more open samples than that is handed to k_ror_mask + this kernel's masked instance
-// through a list of work items (RORM 1 / 2 below; rplgpu_api.hip voxel_with_ror).
+// through a list of work items (RORM 1 / 2 below; rplgpu_api.hip run_voxel).
 //
 // Fixed point: offset = (x - ix*leaf) * 2^K with 2^-K = ulp(leaf) (K = 28 for 5 cm), summed as
 // wrapping 32-bit integers (a block prefix stays below 2^32; the tiny negative offsets of a
@@ -1685,32 +1685,28 @@ hipError_t launch_validate_div(hipStream_t s, float d, float rd, uint32_t e_lo, 
 uint32_t voxel_max_workgroups(uint32_t n_cu) { return (uint32_t)kVWG * (n_cu ? n_cu : 256u); }
 
 
-hipError_t launch_cloud_voxel(hipStream_t s, const void *nodes, uint32_t n_stride,
-                              const uint32_t *n_per_scan, uint32_t B, const KParams &p,
-                              const Tables &T, const uint32_t *keepmask, uint32_t mask_stride,
-                              float *xyzi, uint32_t out_stride, uint32_t *n_points,
-                              uint32_t *status, float *arena, unsigned long long arena_capacity,
-                              unsigned long long *arena_cursor, unsigned long long *scan_start,
-                              uint32_t group, const float *motion, const float *pose2d,
-                              int arena_form, int ror_mode) {
+hipError_t launch_cloud_voxel(hipStream_t s, const VoxelLaunch &v, const KParams &p, const Tables &T) {
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit cursor");
+  uint32_t B = v.B, group = v.group;
+  const bool ror = v.ror != RorMode::kNone, listed = v.ror == RorMode::kListed;
   if (B == 0) return hipSuccess;
-  if (ror_mode && (!p.fast_div || !T.redo || p.dbg)) return hipErrorInvalidValue;
-  if (ror_mode == 2 && !keepmask) return hipErrorInvalidValue;
+  if (ror && (!p.fast_div || !T.redo || p.dbg)) return hipErrorInvalidValue;
+  if (listed && !v.keepmask) return hipErrorInvalidValue;
   // the cell records exist in the two-class and E5-inside instances only (voxel_reduce, CELLS)
-  if (arena_form == 2 && !ror_mode && (p.dbg || !T.voxel_split)) return hipErrorInvalidValue;
+  if (v.form == ArenaForm::kCells && !ror && (p.dbg || !T.voxel_split)) return hipErrorInvalidValue;
   if (group == 0) group = 1;
   group = std::min(group, B);  // (a group larger than the batch is the whole batch)
   const uint32_t n_scans = B;
   B = (B + group - 1u) / group;  // work items
   if (!T.voxel_store || T.voxel_store_wgs == 0) return hipErrorInvalidValue;
   // (the handle allocates 2 x voxel_store_recs entries per workgroup: records, then the cell area)
-  if (voxel_store_need(group, n_stride) > T.voxel_store_recs) return hipErrorInvalidValue;
+  if (voxel_store_need(group, v.n_stride) > T.voxel_store_recs) return hipErrorInvalidValue;
   VoxelArena ar;
-  ar.base = (float4 *)arena;
-  ar.cursor = arena_cursor;
-  ar.capacity = arena_capacity;
-  ar.scan_start = scan_start;
-  ar.xyi = arena ? arena_form : 0;
+  ar.base = (float4 *)v.arena;
+  ar.cursor = reinterpret_cast<unsigned long long *>(v.arena_cursor);
+  ar.capacity = v.arena_capacity;
+  ar.scan_start = reinterpret_cast<unsigned long long *>(v.scan_start);
+  ar.xyi = v.arena ? (int)v.form : 0;
   if (kVWG == 2 && group > 1) return hipErrorInvalidValue;  // (fused groups: 16-wave geometry only)
   // persistent workgroups of the handle's device (no more than the handle owns record stores
   // for); the item queue is cleared by a memset ahead of every launch (an aborted launch can
@@ -1722,35 +1718,35 @@ hipError_t launch_cloud_voxel(hipStream_t s, const void *nodes, uint32_t n_strid
     if (g > 0) grid = std::min<uint32_t>(grid, (uint32_t)g);
   }
   // queue statistics of the launch (they pick the NEXT launch's instance): batches only
-  const bool with_stats = T.voxel_stats && T.voxel_stats_host && B >= 64u && ror_mode != 2;
+  const bool with_stats = T.voxel_stats && T.voxel_stats_host && B >= 64u && !listed;
   Tables Tk = T;
   if (!with_stats) Tk.voxel_stats = nullptr;
   if (with_stats)
     if (hipError_t e = hipMemsetAsync(T.voxel_stats, 0, 16, s); e != hipSuccess) return e;
   // (a launch with a workgroup per item does not touch the queue: one command less in front of a
   // single-scan call)
-  if (grid < B || ror_mode == 2)
+  if (grid < B || listed)
     if (hipError_t e = hipMemsetAsync(T.work_ctr, 0, 4, s); e != hipSuccess) return e;
 #define RPL_LAUNCH_VOXEL(FD, SF, DB, SP)                                                          \
-  hipLaunchKernelGGL((k_cloud_voxel<FD, SF, DB, SP>), dim3(grid), dim3(kVB), 0, s, (const uint2 *)nodes, \
-                     n_stride, n_per_scan, p, Tk, keepmask, mask_stride, (float4 *)xyzi, out_stride, \
-                     n_points, status, B, ar, (uint4 *)T.voxel_store, group, n_scans, motion, pose2d)
+  hipLaunchKernelGGL((k_cloud_voxel<FD, SF, DB, SP>), dim3(grid), dim3(kVB), 0, s, (const uint2 *)v.nodes, \
+                     v.n_stride, v.n_per_scan, p, Tk, v.keepmask, v.mask_stride, (float4 *)v.xyzi, v.out_stride, \
+                     v.n_points, v.status, B, ar, (uint4 *)T.voxel_store, group, n_scans, v.motion, v.pose2d)
 #define RPL_LAUNCH_VOXEL_SF(FD, DB, SP)                                                           \
   do {                                                                                             \
     if (p.cell_range_safe) RPL_LAUNCH_VOXEL(FD, true, DB, SP); else RPL_LAUNCH_VOXEL(FD, false, DB, SP); \
   } while (0)
 #define RPL_LAUNCH_VOXEL_ROR(SF, SP, RM)                                                          \
   hipLaunchKernelGGL((k_cloud_voxel<true, SF, false, SP, RM>), dim3(grid), dim3(kVB), 0, s,         \
-                     (const uint2 *)nodes, n_stride, n_per_scan, p, Tk, keepmask, mask_stride,      \
-                     (float4 *)xyzi, out_stride, n_points, status, B, ar, (uint4 *)T.voxel_store,   \
-                     group, n_scans, motion, pose2d)
+                     (const uint2 *)v.nodes, v.n_stride, v.n_per_scan, p, Tk, v.keepmask, v.mask_stride, \
+                     (float4 *)v.xyzi, v.out_stride, v.n_points, v.status, B, ar, (uint4 *)T.voxel_store, \
+                     group, n_scans, v.motion, v.pose2d)
 #define RPL_LAUNCH_VOXEL_ROR_SF(SP, RM)                                                           \
   do {                                                                                             \
     if (p.cell_range_safe) RPL_LAUNCH_VOXEL_ROR(true, SP, RM); else RPL_LAUNCH_VOXEL_ROR(false, SP, RM); \
   } while (0)
-  if (ror_mode == 1) {  // E5 inside the pass
+  if (v.ror == RorMode::kInside) {  // E5 inside the pass
     if (T.voxel_split) RPL_LAUNCH_VOXEL_ROR_SF(true, 1); else RPL_LAUNCH_VOXEL_ROR_SF(false, 1);
-  } else if (ror_mode == 2) {  // the items it listed, behind k_ror_mask
+  } else if (listed) {  // the items it listed, behind k_ror_mask
     if (T.voxel_split) RPL_LAUNCH_VOXEL_ROR_SF(true, 2); else RPL_LAUNCH_VOXEL_ROR_SF(false, 2);
   } else
   if (p.dbg) {  // developer aid: the instrumented build of the kernel (plain instance only)

@@ -395,7 +395,7 @@ bool device_readable(rplgpu_ctx *c, const void *ptr, const char *what) {
 }
 
 int32_t check_batch(rplgpu_ctx *c, const void *nodes, uint32_t n_stride, const void *n_per_scan,
-                    uint32_t B) {
+                    uint32_t B, bool own_buffers = false) {  // (the handle's own staging: no pointer check)
   if (!c) return RPLGPU_ERR_INVALID_ARG;
   if (B == 0) return RPLGPU_OK;
   if (!nodes || !n_per_scan || n_stride == 0) {
@@ -406,7 +406,7 @@ int32_t check_batch(rplgpu_ctx *c, const void *nodes, uint32_t n_stride, const v
     c->err = "batch larger than max_batch given to rplgpu_create";
     return RPLGPU_ERR_CAPACITY;
   }
-  if (!device_readable(c, nodes, "d_nodes") || !device_readable(c, n_per_scan, "d_n_per_scan"))
+  if (!own_buffers && (!device_readable(c, nodes, "d_nodes") || !device_readable(c, n_per_scan, "d_n_per_scan")))
     return RPLGPU_ERR_INVALID_ARG;
   return RPLGPU_OK;
 }
@@ -645,7 +645,7 @@ int32_t rplgpu_create(int32_t device_id, uint32_t max_samples_per_scan, uint32_t
   }
   c->need_sort_cap = c->max_b;
   // (the sort list starts, and is kept, empty between calls; the count of work items E5-inside listed is 0
-  // until a launch of voxel_with_ror says otherwise — rplgpu_debug_ror_listed reads it on any handle)
+  // until a launch of run_voxel says otherwise — rplgpu_debug_ror_listed reads it on any handle)
   if (hipMemset(c->d_need_sort, 0, 4) != hipSuccess || hipMemset(c->d_redo, 0, 4) != hipSuccess) {
     c->err = "staging allocation failed";
     return fail(RPLGPU_ERR_HIP);
@@ -857,13 +857,34 @@ int32_t rplgpu_ascend_laserscan_batch_dev(rplgpu_handle_t h, rplgpu_node_t *d_no
   return RPLGPU_OK;
 }
 
-// parameter checks, divisor validation and the E5 mask shared by the cloud entry points
-// `ror_inside` (optional): the caller can run E5 inside the voxel kernel (arena launches); set when
-// that is what happens — no mask is made here then, see voxel_with_ror
+// What a cloud entry point asks of prepare_cloud, and the plan it gets back.
+struct CloudRequest {
+  bool force_two_kernels = false;  // E5 as k_ror_mask + the masked kernel whatever the handle's mode
+  bool defer_listed = false;       // see run_voxel (single-scan callers; d_status must be given then)
+  bool own_buffers = false;        // the handle's own staging: no pointer check
+  uint32_t group = 1;              // scans per work item (E8)
+  bool cells = false;              // the arena holds cell records (rplgpu_cloud_fused_cells_dev)
+};
+struct CloudPlan {
+  rpl::KParams kp;
+  rpl::Tables T;
+  const uint32_t *mask = nullptr;  // E5 as the two kernels: the keep bits (k_ror_mask is queued)
+  bool ror_inside = false;         // E5 inside the voxel kernel: no mask, see run_voxel
+};
+
+// E5 runs inside the voxel kernel unless the caller forces the two kernels, when the handle's mode says so
+// (rplgpu_set_ror_mode) and the ROR instance exists for the launch: voxel grid, validated divides, not
+// the instrumented build
+static bool ror_runs_inside(const rplgpu_ctx *h, const CloudRequest &req, const rplgpu_params_t &p,
+                            const rpl::KParams &kp) {
+  return !req.force_two_kernels && h->ror_fused && p.voxel_enable && kp.fast_div && !kp.dbg;
+}
+
+// parameter checks, divisor validation, the E5 path (with the mask of the two kernels queued) and the
+// voxel kernel instance, shared by the cloud entry points (`plan`: a fresh CloudPlan)
 static int32_t prepare_cloud(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                              const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,
-                             rpl::KParams *kp_out, const uint32_t **mask_out,
-                             bool *ror_inside = nullptr) {
+                             const CloudRequest &req, CloudPlan *plan) {
   if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
     h->err = "ror_radius must be in (0, 1e6] m";
     return RPLGPU_ERR_INVALID_ARG;
@@ -873,7 +894,8 @@ static int32_t prepare_cloud(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, ui
     return RPLGPU_ERR_INVALID_ARG;
   }
   RPL_HIP(h, hipSetDevice(h->device));
-  rpl::KParams kp = to_kparams(*p);
+  plan->kp = to_kparams(*p);
+  rpl::KParams &kp = plan->kp;
   if (p->voxel_enable) {
     // the cheap divides are used only for divisors proven bit-identical on this device
     if (h->leaf_checked != p->voxel_leaf) {
@@ -886,52 +908,54 @@ static int32_t prepare_cloud(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, ui
   kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
   kp.dbg = h->dbg;
   kp.cell_keys = h->cell_keys;
-  *mask_out = nullptr;
-  if (ror_inside) *ror_inside = false;
+  plan->T = tables_of(h);
   if (p->ror_enable) {  // E5 before E4: per-sample keep bits, then the cloud kernels apply them
-    if (ror_inside && h->ror_fused && p->voxel_enable && kp.fast_div && !kp.dbg) {
-      *ror_inside = true;
-    } else {
-      RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp,
-                                      tables_of(h), h->d_rormask, kMaskStride));
-      *mask_out = h->d_rormask;
+    plan->ror_inside = ror_runs_inside(h, req, *p, kp);
+    if (!plan->ror_inside) {
+      RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, plan->T,
+                                      h->d_rormask, kMaskStride));
+      plan->mask = h->d_rormask;
     }
   }
-  *kp_out = kp;
+  if (req.cells) {  // the record holds the key (no cell-key words); the instrumented instance has no cell form
+    kp.cell_keys = nullptr;
+    kp.dbg = nullptr;
+  }
+  if (p->voxel_enable) {
+    plan->T.voxel_split = voxel_split_for(h, d_nodes, n_stride, B, req.group) ? 1 : 0;
+    // (the cell form lives in the instances other than the plain one, csrc/rpl_voxel.hip voxel_reduce:
+    // without E5 inside, the records come from the two-class instance, whose results are the same)
+    if (req.cells && !plan->ror_inside) plan->T.voxel_split = 1;
+  }
   return RPLGPU_OK;
 }
 
-// E5 + E4 of an arena launch in ONE pass over the scans (round 6): the voxel kernel's ROR instance
+// The voxel launch(es) of a plan; `v` describes input and output, the plan supplies E5.
+// E5 + E4 of a launch in ONE pass over the scans (round 6): the voxel kernel's ROR instance
 // settles a sample by its index neighbours while it streams the scan and resolves the few that stay
 // open itself (csrc/rpl_voxel.hip: voxel_stream HASROR, ror_resolve).  A work item with more open
 // samples than that (clutter: hundreds of isolated returns) is put on a list instead, and the two
 // kernels of rounds 1-5 — k_ror_mask, then the voxel kernel with the mask — run over the LISTED
 // items behind it: two launches that find an empty list on ring-like data and end at once.
-// (d_arena null: per-scan regions d_xyzi + b * out_stride, rplgpu_cloud_batch_dev.  `defer_listed`: the two
-// launches over the list are left to the caller, who looks at the status word first — the single-scan
-// entry points wait for their one scan anyway and redo it only if it carries kRorListed.)
-constexpr uint32_t kRorListed = rpl::kRorListedBit;
-static int32_t voxel_with_ror(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
-                              const uint32_t *d_n_per_scan, uint32_t B, const rpl::KParams &kp,
-                              const rpl::Tables &T, uint32_t *d_n_points, uint32_t *d_status,
-                              float *d_arena, uint64_t arena_capacity, uint64_t *d_cursor,
-                              uint64_t *d_start, uint32_t group, const float *d_motion,
-                              const float *d_pose2d, int form, float *d_xyzi = nullptr,
-                              uint32_t out_stride = 0, bool defer_listed = false) {
-  RPL_HIP(h, hipMemsetAsync(h->d_redo, 0, 4, h->stream));
-  RPL_HIP(h, rpl::launch_cloud_voxel(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, nullptr,
-                                     kMaskStride, d_xyzi, out_stride, d_n_points, d_status, d_arena,
-                                     arena_capacity, reinterpret_cast<unsigned long long *>(d_cursor),
-                                     reinterpret_cast<unsigned long long *>(d_start), group, d_motion,
-                                     d_pose2d, form, 1));
-  if (defer_listed) return RPLGPU_OK;
-  RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
-                                  kMaskStride, true, std::max(1u, std::min(group, B))));
-  RPL_HIP(h, rpl::launch_cloud_voxel(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
-                                     kMaskStride, d_xyzi, out_stride, d_n_points, d_status, d_arena,
-                                     arena_capacity, reinterpret_cast<unsigned long long *>(d_cursor),
-                                     reinterpret_cast<unsigned long long *>(d_start), group, d_motion,
-                                     d_pose2d, form, 2));
+// (`defer_listed`: the two launches over the list are left to the caller, who looks at the status word
+// first — the single-scan entry points wait for their one scan anyway and redo it only if it carries
+// rpl::kRorListedBit.)
+static int32_t run_voxel(rplgpu_handle_t h, const CloudPlan &plan, rpl::VoxelLaunch v,
+                         bool defer_listed = false) {
+  if (v.arena) RPL_HIP(h, hipMemsetAsync(v.arena_cursor, 0, 8, h->stream));  // (the call resets *d_cursor)
+  v.keepmask = plan.mask;  // (none with E5 inside)
+  v.mask_stride = kMaskStride;
+  if (plan.ror_inside) {
+    RPL_HIP(h, hipMemsetAsync(h->d_redo, 0, 4, h->stream));
+    v.ror = rpl::RorMode::kInside;
+  }
+  RPL_HIP(h, rpl::launch_cloud_voxel(h->stream, v, plan.kp, plan.T));
+  if (!plan.ror_inside || defer_listed) return RPLGPU_OK;
+  RPL_HIP(h, rpl::launch_ror_mask(h->stream, v.nodes, v.n_stride, v.n_per_scan, v.B, plan.kp, plan.T,
+                                  h->d_rormask, kMaskStride, true, std::max(1u, std::min(v.group, v.B))));
+  v.keepmask = h->d_rormask;
+  v.ror = rpl::RorMode::kListed;
+  RPL_HIP(h, rpl::launch_cloud_voxel(h->stream, v, plan.kp, plan.T));
   return RPLGPU_OK;
 }
 
@@ -947,24 +971,17 @@ static int32_t cloud_arena_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes,
     h->err = "rplgpu_cloud_arena_dev needs voxel_enable";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  rpl::KParams kp;
-  const uint32_t *mask = nullptr;
-  bool ror_inside = false;
-  if ((rc = prepare_cloud(h, d_nodes, n_stride, d_n_per_scan, B, p, &kp, &mask, &ror_inside))) return rc;
-  RPL_HIP(h, hipMemsetAsync(d_cursor, 0, 8, h->stream));
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit cursor");
-  rpl::Tables T_arena = tables_of(h);
-  T_arena.voxel_split = voxel_split_for(h, d_nodes, n_stride, B, 1u) ? 1 : 0;
-  if (ror_inside)
-    return voxel_with_ror(h, d_nodes, n_stride, d_n_per_scan, B, kp, T_arena, d_n_points, d_status, d_arena,
-                          arena_capacity, d_cursor, d_scan_start, 1u, nullptr, nullptr, xyi ? 1 : 0);
-  RPL_HIP(h, rpl::launch_cloud_voxel(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp,
-                                     T_arena, mask, kMaskStride, nullptr, 0, d_n_points,
-                                     d_status, d_arena, arena_capacity,
-                                     reinterpret_cast<unsigned long long *>(d_cursor),
-                                     reinterpret_cast<unsigned long long *>(d_scan_start), 1u, nullptr,
-                                     nullptr, xyi ? 1 : 0));
-  return RPLGPU_OK;
+  CloudPlan plan;
+  if ((rc = prepare_cloud(h, d_nodes, n_stride, d_n_per_scan, B, p, CloudRequest{}, &plan))) return rc;
+  rpl::VoxelLaunch v{d_nodes, n_stride, d_n_per_scan, B};
+  v.arena = d_arena;
+  v.arena_capacity = arena_capacity;
+  v.arena_cursor = d_cursor;
+  v.scan_start = d_scan_start;
+  v.form = xyi ? rpl::ArenaForm::kXyi : rpl::ArenaForm::kXyzi;
+  v.n_points = d_n_points;
+  v.status = d_status;
+  return run_voxel(h, plan, v);
 }
 
 int32_t rplgpu_cloud_arena_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
@@ -1028,31 +1045,23 @@ static int32_t fused_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint3
     h->d_vstore = bigger;
     h->vstore_recs = (uint32_t)need;
   }
-  rpl::KParams kp;
-  const uint32_t *mask = nullptr;
-  bool ror_inside = false;
-  if ((rc = prepare_cloud(h, d_nodes, n_stride, d_n_per_scan, B, p, &kp, &mask, &ror_inside))) return rc;
-  if (cells) {  // the record holds the key (no cell-key words); the instrumented instance has no cell form
-    kp.cell_keys = nullptr;
-    kp.dbg = nullptr;
-  }
-  RPL_HIP(h, hipMemsetAsync(d_cursor, 0, 8, h->stream));
-  rpl::Tables T_fused = tables_of(h);
-  T_fused.voxel_split = voxel_split_for(h, d_nodes, n_stride, B, group) ? 1 : 0;
-  const int form = cells ? 2 : 0;
-  if (ror_inside)
-    return voxel_with_ror(h, d_nodes, n_stride, d_n_per_scan, B, kp, T_fused, d_n_points, d_status, d_arena,
-                          arena_capacity, d_cursor, d_group_start, group, d_motion, d_pose2d, form);
-  // (the cell form lives in the instances other than the plain one, csrc/rpl_voxel.hip voxel_reduce:
-  // without E5 inside, the records come from the two-class instance, whose results are the same)
-  if (cells) T_fused.voxel_split = 1;
-  RPL_HIP(h, rpl::launch_cloud_voxel(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp,
-                                     T_fused, mask, kMaskStride, nullptr, 0, d_n_points,
-                                     d_status, d_arena, arena_capacity,
-                                     reinterpret_cast<unsigned long long *>(d_cursor),
-                                     reinterpret_cast<unsigned long long *>(d_group_start), group,
-                                     d_motion, d_pose2d, form));
-  return RPLGPU_OK;
+  CloudRequest req;
+  req.group = group;
+  req.cells = cells;
+  CloudPlan plan;
+  if ((rc = prepare_cloud(h, d_nodes, n_stride, d_n_per_scan, B, p, req, &plan))) return rc;
+  rpl::VoxelLaunch v{d_nodes, n_stride, d_n_per_scan, B};
+  v.group = group;
+  v.motion = d_motion;
+  v.pose2d = d_pose2d;
+  v.arena = d_arena;
+  v.arena_capacity = arena_capacity;
+  v.arena_cursor = d_cursor;
+  v.scan_start = d_group_start;
+  v.form = cells ? rpl::ArenaForm::kCells : rpl::ArenaForm::kXyzi;
+  v.n_points = d_n_points;
+  v.status = d_status;
+  return run_voxel(h, plan, v);
 }
 
 int32_t rplgpu_cloud_fused_voxel_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes,
@@ -1427,30 +1436,27 @@ int32_t rplgpu_filter_laserscan(rplgpu_handle_t h, const float *ranges, const fl
   return RPLGPU_OK;
 }
 
-// `defer_listed`: see voxel_with_ror (single-scan callers; d_status must be given then)
+// (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,
                                 float *d_xyzi, uint32_t out_stride, uint32_t *d_n_points,
-                                uint32_t *d_status, bool defer_listed) {
-  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
+                                uint32_t *d_status, const CloudRequest &req) {
+  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B, req.own_buffers);
   if (rc) return rc;
   if (!p || !d_xyzi || !d_n_points || out_stride == 0) return RPLGPU_ERR_INVALID_ARG;
-  rpl::KParams kp;
-  const uint32_t *mask = nullptr;
-  bool ror_inside = false;
-  if ((rc = prepare_cloud(h, d_nodes, n_stride, d_n_per_scan, B, p, &kp, &mask,
-                          p->voxel_enable ? &ror_inside : nullptr)))
-    return rc;
-  rpl::Tables T_batch = tables_of(h);
-  if (p->voxel_enable) T_batch.voxel_split = voxel_split_for(h, d_nodes, n_stride, B, 1u) ? 1 : 0;
-  if (ror_inside)
-    return voxel_with_ror(h, d_nodes, n_stride, d_n_per_scan, B, kp, T_batch, d_n_points, d_status, nullptr, 0,
-                          nullptr, nullptr, 1u, nullptr, nullptr, false, d_xyzi, out_stride,
-                          defer_listed && d_status);
-  RPL_HIP(h, rpl::launch_cloud(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T_batch,
-                               p->voxel_enable != 0, mask, kMaskStride, d_xyzi, out_stride,
-                               d_n_points, d_status));
-  return RPLGPU_OK;
+  CloudPlan plan;
+  if ((rc = prepare_cloud(h, d_nodes, n_stride, d_n_per_scan, B, p, req, &plan))) return rc;
+  if (!p->voxel_enable) {
+    RPL_HIP(h, rpl::launch_cloud(h->stream, d_nodes, n_stride, d_n_per_scan, B, plan.kp, plan.T, plan.mask,
+                                 kMaskStride, d_xyzi, out_stride, d_n_points, d_status));
+    return RPLGPU_OK;
+  }
+  rpl::VoxelLaunch v{d_nodes, n_stride, d_n_per_scan, B};
+  v.xyzi = d_xyzi;
+  v.out_stride = out_stride;
+  v.n_points = d_n_points;
+  v.status = d_status;
+  return run_voxel(h, plan, v, req.defer_listed && d_status);
 }
 
 int32_t rplgpu_cloud_batch_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
@@ -1458,7 +1464,7 @@ int32_t rplgpu_cloud_batch_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, 
                                float *d_xyzi, uint32_t out_stride, uint32_t *d_n_points,
                                uint32_t *d_status) {
   return cloud_batch_impl(h, d_nodes, n_stride, d_n_per_scan, B, p, d_xyzi, out_stride, d_n_points, d_status,
-                          false);
+                          CloudRequest{});
 }
 
 int32_t rplgpu_pack_clouds_dev(rplgpu_handle_t h, const float *d_xyzi, uint32_t out_stride,
@@ -1569,10 +1575,11 @@ int32_t rplgpu_scan_to_cloud(rplgpu_handle_t h, const rplgpu_node_t *nodes, size
   if (status) *status = 0;
   if (n == 0) return RPLGPU_OK;
   unsigned char *h_out = stage_out(h);
+  uint32_t w[2];  // n_points, status: they travel behind the points
   RPL_HIP(h, hipSetDevice(h->device));
   if (h->zero_copy) {
     const ScanStage st = stage_scan(h, nodes, n);
-    uint32_t *d_words = reinterpret_cast<uint32_t *>(st.d_out + n * 16);  // n_points, status
+    uint32_t *d_words = reinterpret_cast<uint32_t *>(st.d_out + n * 16);
     const rplgpu_node_t *d_in = st.d_nodes;
     const uint32_t *d_in_n = st.d_n;
     if (p->ror_enable) {
@@ -1583,59 +1590,42 @@ int32_t rplgpu_scan_to_cloud(rplgpu_handle_t h, const rplgpu_node_t *nodes, size
       d_in = reinterpret_cast<const rplgpu_node_t *>(h->d_nodes);
       d_in_n = reinterpret_cast<const uint32_t *>(h->d_nodes + n * 8);
     }
-    // (the batch entry point's pointer check asks the runtime about each pointer: skip it for
-    // the handle's own staging)
-    const bool chk = h->check_ptrs;
-    h->check_ptrs = false;
     // (E5 + E4: the voxel kernel applies E5 itself, round 6; a scan it cannot settle comes back with the
     // internal "listed" status and is redone by the two kernels — this call waits for its scan anyway)
     // (Only for dense scans: below ~8 k samples per revolution the index neighbours of a sample are mostly
     // farther away than r — 360 samples at 10 m are 17 cm apart — the kernel gives the scan up at once and
     // the call would pay for both paths: 87 against 59 us at 360 samples, 61 against 73 us at 32 000.)
-    const int32_t fused_keep = h->ror_fused;
-    if (n < 8192u) h->ror_fused = 0;
-    int32_t rc = cloud_batch_impl(h, d_in, (uint32_t)n, d_in_n, 1, p, reinterpret_cast<float *>(st.d_out),
-                                  (uint32_t)n, d_words, d_words + 1, true);
-    h->ror_fused = fused_keep;
-    h->check_ptrs = chk;
-    if (rc) return rc;
-    if (int32_t wrc = wait_scan(h)) return wrc;
-    uint32_t w[2];
-    std::memcpy(w, st.h_out + n * 16, 8);
-    if (w[1] & kRorListed) {
-      const int32_t keep = h->ror_fused;
-      h->ror_fused = 0;
-      h->check_ptrs = false;
-      rc = cloud_batch_impl(h, d_in, (uint32_t)n, d_in_n, 1, p, reinterpret_cast<float *>(st.d_out), (uint32_t)n,
-                            d_words, d_words + 1, false);
-      h->check_ptrs = chk;
-      h->ror_fused = keep;
-      if (rc) return rc;
+    CloudRequest req;
+    req.own_buffers = true;
+    req.force_two_kernels = n < 8192u;
+    req.defer_listed = true;
+    for (int pass = 0; pass < 2; ++pass) {  // (the second one: the two kernels, which list nothing)
+      if (int32_t rc = cloud_batch_impl(h, d_in, (uint32_t)n, d_in_n, 1, p, reinterpret_cast<float *>(st.d_out),
+                                        (uint32_t)n, d_words, d_words + 1, req))
+        return rc;
       if (int32_t wrc = wait_scan(h)) return wrc;
-      std::memcpy(w, st.h_out + n * 16, 8);
+      std::memcpy(w, h_out + n * 16, 8);
+      if (!(w[1] & rpl::kRorListedBit)) break;
+      req.force_two_kernels = true;
+      req.defer_listed = false;
     }
-    *n_points = w[0];
-    if (status) *status = w[1];
-    std::memcpy(xyzi, st.h_out, (size_t)w[0] * 16);
-    return (w[1] & (RPLGPU_SCAN_CELL_RANGE | RPLGPU_SCAN_TABLE_FULL)) ? RPLGPU_ERR_SCAN_OVERFLOW
-                                                                     : RPLGPU_OK;
+  } else {
+    // (E5 follows the handle's mode at every size here: rplgpu_cloud_batch_dev with B = 1)
+    const uint32_t *d_n;
+    if (int32_t urc = upload_scan(h, nodes, n, &d_n)) return urc;
+    uint32_t *d_words = reinterpret_cast<uint32_t *>(h->d_out + n * 16);
+    int32_t rc = rplgpu_cloud_batch_dev(h, reinterpret_cast<const rplgpu_node_t *>(h->d_nodes),
+                                        (uint32_t)n, d_n, 1, p, reinterpret_cast<float *>(h->d_out),
+                                        (uint32_t)n, d_words, d_words + 1);
+    if (rc) return rc;
+    RPL_HIP(h, hipMemcpyAsync(h_out, h->d_out, n * 16 + 8, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    std::memcpy(w, h_out + n * 16, 8);
   }
-  const uint32_t *d_n;
-  if (int32_t urc = upload_scan(h, nodes, n, &d_n)) return urc;
-  uint32_t *d_words = reinterpret_cast<uint32_t *>(h->d_out + n * 16);  // n_points, status
-  int32_t rc = rplgpu_cloud_batch_dev(h, reinterpret_cast<const rplgpu_node_t *>(h->d_nodes),
-                                      (uint32_t)n, d_n, 1, p, reinterpret_cast<float *>(h->d_out),
-                                      (uint32_t)n, d_words, d_words + 1);
-  if (rc) return rc;
-  RPL_HIP(h, hipMemcpyAsync(h_out, h->d_out, n * 16 + 8, hipMemcpyDeviceToHost, h->stream));
-  RPL_HIP(h, hipStreamSynchronize(h->stream));
-  uint32_t h_small[3] = {0, 0, 0};
-  std::memcpy(h_small + 1, h_out + n * 16, 8);
-  *n_points = h_small[1];
-  if (status) *status = h_small[2];
-  std::memcpy(xyzi, h_out, (size_t)h_small[1] * 16);
-  return (h_small[2] & (RPLGPU_SCAN_CELL_RANGE | RPLGPU_SCAN_TABLE_FULL)) ? RPLGPU_ERR_SCAN_OVERFLOW
-                                                                          : RPLGPU_OK;
+  *n_points = w[0];
+  if (status) *status = w[1];
+  std::memcpy(xyzi, h_out, (size_t)w[0] * 16);
+  return (w[1] & (RPLGPU_SCAN_CELL_RANGE | RPLGPU_SCAN_TABLE_FULL)) ? RPLGPU_ERR_SCAN_OVERFLOW : RPLGPU_OK;
 }
 
 // ---- decode stage ------------------------------------------
@@ -2412,12 +2402,10 @@ int32_t rplgpu_cloud_deskew_batch_dev(rplgpu_handle_t h, const rplgpu_node_t *d_
     h->err = "de-skew works on the plain cloud (voxel_enable = 0)";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  rpl::KParams kp;
-  const uint32_t *mask = nullptr;
-  if ((rc = prepare_cloud(h, d_nodes, n_stride, d_n_per_scan, B, p, &kp, &mask))) return rc;
-  RPL_HIP(h, rpl::launch_cloud(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, tables_of(h),
-                               false, mask, kMaskStride, d_xyzi, out_stride, d_n_points, d_status,
-                               d_motion));
+  CloudPlan plan;
+  if ((rc = prepare_cloud(h, d_nodes, n_stride, d_n_per_scan, B, p, CloudRequest{}, &plan))) return rc;
+  RPL_HIP(h, rpl::launch_cloud(h->stream, d_nodes, n_stride, d_n_per_scan, B, plan.kp, plan.T, plan.mask,
+                               kMaskStride, d_xyzi, out_stride, d_n_points, d_status, d_motion));
   return RPLGPU_OK;
 }
 

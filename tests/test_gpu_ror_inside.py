@@ -243,6 +243,53 @@ def test_per_scan_regions_and_single_scan_calls(gpu, oracle):
     assert out[0] == out[1]
 
 
+@pytest.fixture(scope="module")
+def around_single_scans(gpu):
+    """Per ROR mode: a uniform batch through the arena call in RPLGPU_ROR_INSIDE (every item listed), then, in
+    the mode, two single-scan calls with E5 + E4 — 360 samples (below the 8192 from which the call runs E5 inside
+    the kernel) and 9000 uniform ones (inside, listed, redone by the two kernels) — and a ring batch through the
+    arena call.  B = 4: a workgroup per item, the launch form single scans take.
+    -> {mode: (single-scan clouds, items listed after the uniform batch, ... after the ring batch)}"""
+    B, n = 4, 9000
+    p = Params.defaults(**P_C5)
+    uniform = synth.make_batch(7, B, n, kind="uniform")
+    ring = synth.make_batch(2031, B, n, noise_m=0.01)
+    singles = [synth.make_scan(44, 0, 360, noise_m=0.005, r0_range=(1, 3)), uniform[0]]
+    out = {}
+    for mode in (0, 1):
+        try:
+            gpu.set_ror_mode(0)
+            _arena(gpu, uniform, [n] * B, p)
+            listed_before = gpu.debug_ror_listed()
+            gpu.set_ror_mode(mode)
+            clouds = []
+            for s in singles:
+                cloud, st = gpu.scan_to_cloud(s, p)
+                assert st == 0, hex(st)
+                clouds.append(cloud.tobytes())
+            _arena(gpu, ring, [n] * B, p)
+            out[mode] = (clouds, listed_before, gpu.debug_ror_listed())
+        finally:
+            gpu.set_ror_mode(0)
+    return out
+
+
+def test_inside_mode_survives_single_scan_calls(around_single_scans):
+    """rplgpu_scan_to_cloud picks its own E5 path per call; the handle's mode is what it was afterwards: the
+    ring batch behind the single scans runs inside the kernel again and clears the count of listed items."""
+    clouds, before, after = around_single_scans[0]
+    assert before == 4 and after == 0
+    assert clouds == around_single_scans[1][0]
+
+
+def test_two_kernels_mode_survives_single_scan_calls(around_single_scans):
+    """The converse: in RPLGPU_ROR_TWO_KERNELS nothing runs inside the kernel — not the 9000-sample single
+    scan, not the ring batch behind it — so the count the uniform batch left stays."""
+    clouds, before, after = around_single_scans[1]
+    assert before == 4 and after == 4
+    assert clouds == around_single_scans[0][0]
+
+
 @pytest.mark.parametrize("seed", range(int(os.environ.get("RPL_FUZZ_SEEDS", "12"))))
 def test_fuzz_inside_against_two_kernels_and_oracle(gpu, oracle, seed):
     """Random batches — the scans of tests/test_gpu_fuzz.py (any order of angle words, any u32 as a distance,
