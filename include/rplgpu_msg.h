@@ -359,6 +359,101 @@ int32_t rplgpu_filter_laserscan(rplgpu_handle_t h, const float *ranges, const fl
                                 float angle_increment, const rplgpu_scan_filter_t *f, float *ranges_out,
                                 float *intensities_out, uint32_t removed[2]);
 
+/* ---- E11: one ray-cast occupancy grid per group of scans (row 4; the costmap obstacle layer's mark-and-clear) --
+ * What Nav2 costmaps, AMCL and slam_toolbox do first with a time step's scans: every beam is traced from
+ * ITS sensor through the grid, the cells it passes are cleared and the cell it ends in is marked.  E8 gives
+ * occupied cells only and E9 beams that all start at the base origin; here every ray starts where its own
+ * sensor stands.  Nothing in the reference builds a grid, so these rules ARE the definition (parity unpinned,
+ * as E5-E10). */
+#define RPLGPU_MAX_OCC_DIM   4096u
+#define RPLGPU_MAX_OCC_STEPS 8192u
+typedef struct rplgpu_occ_grid {
+  float    origin_x, origin_y;  /* common-frame position of the lower-left corner of cell (0, 0) */
+  float    resolution;          /* metres per cell, > 0 */
+  uint32_t width, height;       /* cells, 1 .. RPLGPU_MAX_OCC_DIM each */
+  float    range_min;           /* returns nearer to their sensor than this are ignored (robot body), >= 0 */
+  float    obstacle_max;        /* a return marks its cell iff d <= obstacle_max */
+  float    raytrace_max;        /* rays clear up to this distance; longer rays are cut here */
+} rplgpu_occ_grid_t;
+/* resolution 0.05 m, 1024 x 1024 cells, origin (-25.6, -25.6), range_min 0, obstacle_max 25, raytrace_max 30 */
+void rplgpu_default_occ_grid(rplgpu_occ_grid_t *grid);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for a value that is not finite, resolution <= 0,
+ * a dimension of 0 or above RPLGPU_MAX_OCC_DIM, !(0 <= range_min < obstacle_max <= raytrace_max), or
+ * (double)raytrace_max / (double)resolution > RPLGPU_MAX_OCC_STEPS (which bounds every ray walk, however
+ * it is walked).  The device path uses this function. */
+int32_t rplgpu_occ_grid_check(const rplgpu_occ_grid_t *grid);
+/* POINTS: those of rplgpu_merge_scans_dev, from the same float32 operations — E1 (E5 too with p->ror_enable),
+ * E2 (p->inverted honoured), E6 de-skew from d_motion with the offsets of rplgpu_set_scan_time_offsets_dev
+ * (offsets set and d_motion NULL: refused), the planar pose.  voxel_enable and scan_processing are ignored.
+ * The sensor of scan sc stands at (sx, sy) = (d_pose2d[6 sc + 2], d_pose2d[6 sc + 5]) — where it is at the
+ * fused instant, to which E6 has moved every point; (0, 0) without d_pose2d.
+ * CELL of a position (x, y), float32, no FMA, IEEE divides:
+ *   u = (x - origin_x) / resolution;  fu = floorf(u);  fv likewise from y;
+ *   the position has NO cell when fu or fv is NaN or has magnitude >= 1048576 (the cell-range case);
+ *   otherwise its cell is (cx, cy) = ((int)fu, (int)fv), which may lie outside the grid.
+ * PER POINT, dx = x - sx, dy = y - sy:
+ *   d = sqrtf(RN(RN(dx*dx) + RN(dy*dy)));  the point is ignored when d is not finite or d < range_min
+ *   (so a NaN or Inf point, e.g. from a NaN in d_motion, is ignored HERE and never sets a status bit);
+ *   d <= raytrace_max: the end position is (x, y) and the ray is WHOLE;
+ *   else t = raytrace_max / d, the end position is (sx + dx * t, sy + dy * t) (one product, then one sum
+ *   per coordinate) and the ray is CUT;
+ *   a ray whose sensor position or end position has no cell is dropped and sets RPLGPU_SCAN_CELL_RANGE in
+ *   d_status[g].
+ * THE WALK, all-integer Bresenham from the sensor cell (x0, y0) to the end cell (x1, y1):
+ *   ax = |x1 - x0|, ay = |y1 - y0|, stepx = sign(x1 - x0), stepy = sign(y1 - y0), err = ax - ay;
+ *   visit (x0, y0); while the current cell is not (x1, y1): e2 = 2 err, and with this one e2
+ *     if (e2 > -ay) { err -= ay; x += stepx; }   if (e2 < ax) { err += ax; y += stepy; }   visit the cell.
+ *   Visits outside [0, width) x [0, height) do nothing.
+ * A whole ray CLEARS every visited cell except its end cell and MARKS the end cell iff d <= obstacle_max.  A
+ * cut ray clears every visited cell, the end cell included, and marks nothing.
+ * RESULT for group g (scans [g*group, (g+1)*group), group clamped to B as in E8), int8 in
+ * nav_msgs/OccupancyGrid row-major order at index cy * width + cx, at d_grid + g * grid_stride:
+ *   100 for a cell any ray marks;  0 for a cell some ray clears and none marks;  otherwise the cell's value
+ *   in d_prev + g * grid_stride (group g's previous grid, same layout), or -1 when d_prev is NULL.
+ * Marks beat clears and both beat history, so the result depends on no order.
+ * d_cells (optional): per group the number of result cells that are 0, 100 and -1 (3 words).  d_status[g]
+ * (optional): RPLGPU_SCAN_OUT_TRUNCATED when a scan of the group was longer than n_stride (as E9), and
+ * RPLGPU_SCAN_CELL_RANGE as above.
+ * grid_stride >= width * height and a multiple of 4, d_grid 4-byte aligned (the walk uses 32-bit atomics on
+ * the output itself: the grid is its own scratch, bytes at and beyond width * height of a group are left
+ * alone).  d_prev == d_grid is refused; any other overlap is the caller's error.  The argument and capacity
+ * checks of rplgpu_cloud_fused_voxel_dev.  Asynchronous on the handle's stream. */
+int32_t rplgpu_occupancy_grid_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                                  const uint32_t *d_n_per_scan, uint32_t B, uint32_t group,
+                                  const rplgpu_params_t *p, const float *d_motion, const float *d_pose2d,
+                                  const rplgpu_occ_grid_t *grid, const int8_t *d_prev, int8_t *d_grid,
+                                  uint64_t grid_stride, uint32_t *d_cells, uint32_t *d_status);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp): n_scans <= max_batch scans of n_per_scan[i]
+ * samples, n_stride apart; motion / pose2d / prev may be NULL; t0 (NULL: none) are the scans' time offsets
+ * for this call only; grid_out: width * height bytes; cells (optional): 3 words; status (optional): 1 word.
+ * Allocates its device buffers per call and returns when the result is in place. */
+int32_t rplgpu_occupancy_grid(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                              const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                              const float *motion, const float *pose2d, const float *t0,
+                              const rplgpu_occ_grid_t *grid, const int8_t *prev, int8_t *grid_out,
+                              uint32_t cells[3], uint32_t *status);
+/* Byte offsets inside one serialised nav_msgs/OccupancyGrid = Header, MapMetaData info { Time map_load_time,
+ * float32 resolution, uint32 width, height, Pose origin { float64 position x y z, orientation x y z w } },
+ * int8[] data.  float64 is aligned to 8 counted from the byte after the encapsulation header. */
+typedef struct rplgpu_occupancy_layout {
+  uint32_t map_load_time_off; /* int32 sec, uint32 nanosec */
+  uint32_t resolution_off;    /* float32 resolution; uint32 width and height follow */
+  uint32_t origin_off;        /* 7 float64 */
+  uint32_t data_len_off;      /* uint32 data.size() = width * height */
+  uint32_t data_off;          /* data[0]; a multiple of 4 */
+  uint32_t total_len;
+} rplgpu_occupancy_layout_t;
+int32_t rplgpu_msg_occupancy_layout(size_t frame_id_len, uint32_t width, uint32_t height,
+                                    rplgpu_occupancy_layout_t *out);
+/* G serialised OccupancyGrids of the grids rplgpu_occupancy_grid_dev wrote: header stamp and
+ * info.map_load_time = d_stamps[g], resolution / width / height of `grid`, origin position (origin_x,
+ * origin_y, 0) and orientation (0, 0, 0, 1).  Message g at d_msgs + g*msg_stride (a multiple of 4), its
+ * length in d_msg_len[g]; 0 + RPLGPU_SCAN_OUT_TRUNCATED in d_status[g] (optional) when msg_stride is too small. */
+int32_t rplgpu_occupancy_grid_msgs_dev(rplgpu_handle_t h, const int8_t *d_grid, uint64_t grid_stride, uint32_t G,
+                                       const rplgpu_occ_grid_t *grid, const char *frame_id,
+                                       const rplgpu_stamp_t *d_stamps, uint8_t *d_msgs, uint32_t msg_stride,
+                                       uint32_t *d_msg_len, uint32_t *d_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,8 @@ SCAN_OUT_TRUNCATED = 0x8
 
 MAX_MERGE_BEAMS = 16384  # RPLGPU_MAX_MERGE_BEAMS (include/rplgpu_msg.h)
 MAX_FILTER_WINDOW = 64   # RPLGPU_MAX_FILTER_WINDOW (include/rplgpu_msg.h)
+MAX_OCC_DIM = 4096       # RPLGPU_MAX_OCC_DIM (include/rplgpu_msg.h)
+MAX_OCC_STEPS = 8192     # RPLGPU_MAX_OCC_STEPS (include/rplgpu_msg.h)
 
 SL_RESULT_OK = 0
 SL_RESULT_OPERATION_FAIL = 0x80008001
@@ -103,6 +105,12 @@ ABI_SYMBOLS = [
     "rplgpu_filter_laserscan_batch_dev",
     "rplgpu_filter_merged_scans_dev",
     "rplgpu_filter_laserscan",
+    "rplgpu_default_occ_grid",
+    "rplgpu_occ_grid_check",
+    "rplgpu_occupancy_grid_dev",
+    "rplgpu_occupancy_grid",
+    "rplgpu_msg_occupancy_layout",
+    "rplgpu_occupancy_grid_msgs_dev",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -238,6 +246,39 @@ class ScanFilter(C.Structure):
                 raise AttributeError(k)
             setattr(f, k, v)
         return f
+
+
+class OccGrid(C.Structure):
+    """Mirror of ``rplgpu_occ_grid_t`` (E11: the ray-cast occupancy grid of a group of scans)."""
+
+    _fields_ = [
+        ("origin_x", C.c_float),
+        ("origin_y", C.c_float),
+        ("resolution", C.c_float),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("range_min", C.c_float),
+        ("obstacle_max", C.c_float),
+        ("raytrace_max", C.c_float),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "OccGrid":
+        """The library's own defaults (``rplgpu_default_occ_grid``), then the overrides."""
+        g = cls()
+        load_library().rplgpu_default_occ_grid(C.byref(g))
+        for k, v in kw.items():
+            if not hasattr(g, k):
+                raise AttributeError(k)
+            setattr(g, k, v)
+        return g
+
+
+class OccupancyLayout(C.Structure):
+    """Mirror of ``rplgpu_occupancy_layout_t``."""
+
+    _fields_ = [(k, C.c_uint32) for k in (
+        "map_load_time_off", "resolution_off", "origin_off", "data_len_off", "data_off", "total_len")]
 
 
 def library_path() -> Path:
@@ -379,6 +420,15 @@ def load_library() -> C.CDLL:
     lib.rplgpu_filter_merged_scans_dev.argtypes = [vp, vp, vp, u32, C.POINTER(ScanMerge),
                                                    C.POINTER(ScanFilter), vp, vp, vp]
     lib.rplgpu_filter_laserscan.argtypes = [vp, vp, vp, u32, C.c_float, C.POINTER(ScanFilter), vp, vp, vp]
+    lib.rplgpu_default_occ_grid.argtypes = [C.POINTER(OccGrid)]
+    lib.rplgpu_default_occ_grid.restype = None
+    lib.rplgpu_occ_grid_check.argtypes = [C.POINTER(OccGrid)]
+    lib.rplgpu_occupancy_grid_dev.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp,
+                                              C.POINTER(OccGrid), vp, vp, u64, vp, vp]
+    lib.rplgpu_occupancy_grid.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp,
+                                          C.POINTER(OccGrid), vp, vp, vp, vp]
+    lib.rplgpu_msg_occupancy_layout.argtypes = [sz, u32, u32, C.POINTER(OccupancyLayout)]
+    lib.rplgpu_occupancy_grid_msgs_dev.argtypes = [vp, vp, u64, u32, C.POINTER(OccGrid), cs, vp, vp, u32, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -630,6 +680,43 @@ class RplGpu:
         self._check(self._lib.rplgpu_merged_laserscan_msgs_dev(
             self._h, d_ranges, d_intens, G, C.byref(merge), frame_id.encode(), d_stamps, d_msgs,
             msg_stride, d_msg_len, d_status))
+
+    def occupancy_grid_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int,
+                           params: Params, d_motion: int, d_pose2d: int, grid: OccGrid, d_prev: int,
+                           d_grid: int, grid_stride: int, d_cells: int = 0, d_status: int = 0):
+        """E11: one ray-cast occupancy grid (int8, grid.width x grid.height) per group of scans."""
+        self._check(self._lib.rplgpu_occupancy_grid_dev(
+            self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d,
+            C.byref(grid), d_prev, d_grid, grid_stride, d_cells, d_status))
+
+    def occupancy_grid(self, scans: np.ndarray, lens, params: Params, grid: OccGrid, motion=None,
+                       pose2d=None, t0=None, prev=None):
+        """E11, one group, host buffers: scans (S, n) NODE_DTYPE -> ``(grid (height, width) int8,
+        (cells 0, cells 100, cells -1), status)``."""
+        scans = np.ascontiguousarray(scans)
+        if scans.dtype != NODE_DTYPE or scans.ndim != 2:
+            raise TypeError("scans must be a 2-D array of abi.NODE_DTYPE")
+        S, n = scans.shape
+        lens = np.ascontiguousarray(lens, np.uint32)
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
+        motion, pose2d, t0 = f32(motion), f32(pose2d), f32(t0)
+        prev = None if prev is None else np.ascontiguousarray(prev, np.int8)
+        out = np.empty((grid.height, grid.width), np.int8)
+        cells = np.zeros(3, np.uint32)
+        status = np.zeros(1, np.uint32)
+        ptr = lambda a: 0 if a is None else a.ctypes.data  # noqa: E731
+        self._check(self._lib.rplgpu_occupancy_grid(
+            self._h, scans.ctypes.data, n, lens.ctypes.data, S, C.byref(params), ptr(motion), ptr(pose2d),
+            ptr(t0), C.byref(grid), ptr(prev), out.ctypes.data, cells.ctypes.data, status.ctypes.data))
+        return out, tuple(int(c) for c in cells), int(status[0])
+
+    def occupancy_grid_msgs_dev(self, d_grid: int, grid_stride: int, G: int, grid: OccGrid, frame_id: str,
+                                d_stamps: int, d_msgs: int, msg_stride: int, d_msg_len: int,
+                                d_status: int = 0):
+        """G serialised nav_msgs/OccupancyGrid messages of the grids occupancy_grid_dev wrote."""
+        self._check(self._lib.rplgpu_occupancy_grid_msgs_dev(
+            self._h, d_grid, grid_stride, G, C.byref(grid), frame_id.encode(), d_stamps, d_msgs, msg_stride,
+            d_msg_len, d_status))
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -1022,3 +1109,20 @@ def scan_filter_check(flt: ScanFilter) -> np.ndarray:
     if rc:
         raise RplGpuError(rc, "rplgpu_scan_filter_check")
     return dirs
+
+
+def occ_grid_check(grid: OccGrid) -> None:
+    """Host only: validates an E11 grid spec by the library's own rplgpu_occ_grid_check; raises
+    RplGpuError(ERR_INVALID_ARG) for a spec the library refuses."""
+    rc = load_library().rplgpu_occ_grid_check(C.byref(grid))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_occ_grid_check")
+
+
+def msg_occupancy_layout(frame_id_len: int, width: int, height: int) -> OccupancyLayout:
+    """Host only: byte offsets inside one serialised nav_msgs/OccupancyGrid."""
+    lay = OccupancyLayout()
+    rc = load_library().rplgpu_msg_occupancy_layout(frame_id_len, width, height, C.byref(lay))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_msg_occupancy_layout")
+    return lay

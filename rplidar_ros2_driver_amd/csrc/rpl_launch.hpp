@@ -264,4 +264,26 @@ hipError_t launch_filter_scans(hipStream_t s, const float *ranges, const float *
                                const uint32_t *beam_count, uint32_t B, const FilterK &k, float *ranges_out,
                                float *intens_out, uint32_t *removed);
 
+// E11: one ray-cast occupancy grid per group of scans (rpl_occ.hip, include/rplgpu_msg.h).  The grid is its
+// own scratch: prepare zeroes the cells, walk ORs clear / mark bits into their bytes, finish maps the bytes
+// to 100 / 0 / prev-or--1 and counts them (cells: 3 words per group, cleared by the caller; may be null).
+struct OccK {  // a checked rplgpu_occ_grid_t
+  float origin_x, origin_y, resolution;
+  uint32_t width, height;
+  float range_min, obstacle_max, raytrace_max;
+};
+hipError_t launch_occ_prepare(hipStream_t s, int8_t *grid, unsigned long long grid_stride, uint32_t G,
+                              const OccK &k);
+hipError_t launch_occ_walk(hipStream_t s, const void *nodes, uint32_t n_stride, const uint32_t *n_per_scan,
+                           uint32_t B, uint32_t group, const KParams &p, const Tables &T,
+                           const uint32_t *keepmask, uint32_t mask_stride, const float *motion,
+                           const float *pose2d, const OccK &k, int8_t *grid, unsigned long long grid_stride,
+                           uint32_t *status);
+hipError_t launch_occ_finish(hipStream_t s, int8_t *grid, unsigned long long grid_stride, uint32_t G,
+                             const OccK &k, const int8_t *prev, uint32_t *cells);
+hipError_t launch_msg_occupancy(hipStream_t s, const int8_t *grid, unsigned long long grid_stride,
+                                uint32_t n_cells, uint32_t G, const rplgpu_stamp_t *stamps,
+                                const rplmsg::Prefix &P, uint8_t *msgs, uint32_t msg_stride, uint32_t *msg_len,
+                                uint32_t *status);
+
 }  // namespace rpl

@@ -24,14 +24,6 @@ namespace {
 typedef uint32_t mg_u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned long long kEmptyBeam = ~0ull;
 
-// a / 4000 as mul + 2 FMA: the form rpl_voxel.hip's div_by proves bit-identical to the IEEE divide
-// on the device (k_validate_div) before KParams::fast_d4000 is set
-__device__ __forceinline__ float merge_div4000(float a) {
-  const float q = a * 0.00025f;
-  const float e = fmaf(-q, 4000.0f, a);
-  return fmaf(e, 0.00025f, q);
-}
-
 // cross_k(p) >= 0: the products of two float32 values are exact in fp64 and the difference is rounded
 // once, so the sign is exact (-ffp-contract=off keeps the three operations apart)
 __device__ __forceinline__ bool on_left(float2 e, float x, float y) {
@@ -95,12 +87,7 @@ __device__ __forceinline__ void merge_sample(uint32_t lo, uint32_t hi, uint32_t 
                                              const MergeK &mk, unsigned long long slot_bits,
                                              unsigned long long *s_key) {
   if (!kept) return;
-  const uint32_t d = __builtin_amdgcn_alignbit(hi, lo, 16);
-  const float df = __uint2float_rn(d);
-  const float dm = FAST ? merge_div4000(df) : df / 4000.0f;  // :590
-  const float2 c = cs[lo & 0xFFFFu];
-  f2 xy = {c.x * dm, c.y * dm};                              // E2
-  xy = apply_xf(xy, i, xf);                                  // E6 + pose, as E8
+  const f2 xy = sample_xy<FAST>(lo, hi, i, cs, xf);  // E2, E6 + pose (rpl_xf.hpp)
   const float r2 = xy.x * xy.x + xy.y * xy.y;
   const float r = sqrtf(r2);
   if (!(r >= mk.range_min && r <= mk.range_max)) return;

@@ -24,6 +24,7 @@ struct Prefix {
   uint32_t a_off;      // LaserScan: angle_min (7 scalars follow) | PointCloud2: width
   uint32_t b_off;      // LaserScan: ranges length word         | PointCloud2: row_step
   uint32_t c_off;      // LaserScan: unused                      | PointCloud2: data length word
+                       // OccupancyGrid: a_off = info.map_load_time (the second stamp)
   uint32_t words[kPrefixWords];
 };
 
@@ -37,6 +38,7 @@ class Writer {
   void u32(uint32_t v) { align4(); put(&v, 4); }
   void i32(int32_t v) { align4(); put(&v, 4); }
   void f32(float v) { align4(); put(&v, 4); }
+  void f64(double v) { align8(); put(&v, 8); }
   void str(const char *s, size_t n) {  // uint32 length incl. NUL, bytes, NUL
     u32(static_cast<uint32_t>(n + 1));
     put(s, n);
@@ -44,6 +46,9 @@ class Writer {
   }
   void align4() {
     while ((pos_ - 4) & 3u) u8(0);
+  }
+  void align8() {
+    while ((pos_ - 4) & 7u) u8(0);
   }
   void skip(size_t n) { pos_ += n; }  // bulk array filled by someone else
  private:
@@ -115,6 +120,29 @@ inline size_t write_cloud(Writer &w, const char *frame_id, size_t fid_len, rplgp
   w.skip(static_cast<size_t>(n_points) * 16);
   L->is_dense_off = static_cast<uint32_t>(w.pos());
   w.u8(1);  // is_dense
+  L->total_len = static_cast<uint32_t>(w.pos());
+  return w.pos();
+}
+
+// Whole OccupancyGrid (include/rplgpu_msg.h, E11) but the cells.
+inline size_t write_occupancy(Writer &w, const char *frame_id, size_t fid_len, rplgpu_stamp_t stamp,
+                              float resolution, uint32_t width, uint32_t height, float origin_x,
+                              float origin_y, rplgpu_occupancy_layout_t *L) {
+  encapsulation(w);
+  header(w, frame_id, fid_len, stamp);
+  w.align4();
+  L->map_load_time_off = static_cast<uint32_t>(w.pos());
+  w.i32(stamp.sec), w.u32(stamp.nanosec);  // info.map_load_time
+  L->resolution_off = static_cast<uint32_t>(w.pos());
+  w.f32(resolution), w.u32(width), w.u32(height);
+  w.align8();
+  L->origin_off = static_cast<uint32_t>(w.pos());
+  w.f64(origin_x), w.f64(origin_y), w.f64(0.0);        // origin.position
+  w.f64(0.0), w.f64(0.0), w.f64(0.0), w.f64(1.0);      // origin.orientation
+  L->data_len_off = static_cast<uint32_t>(w.pos());
+  w.u32(width * height);
+  L->data_off = static_cast<uint32_t>(w.pos());
+  w.skip(static_cast<size_t>(width) * height);
   L->total_len = static_cast<uint32_t>(w.pos());
   return w.pos();
 }

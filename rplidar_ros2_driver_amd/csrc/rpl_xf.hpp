@@ -1,4 +1,4 @@
-// rpl_xf.hpp — the per-sample front end that E8 (rpl_voxel.hip) and E9 (rpl_merge.hip) share: where a
+// rpl_xf.hpp — the per-sample front end that E8 (rpl_voxel.hip), E9 (rpl_merge.hip) and E11 (rpl_occ.hip) share: where a
 // point of one scan of a group goes between polar->XY and the common frame (E6 de-skew, planar pose),
 // and what of the scan the streaming code needs besides its nodes (the E5 keep bits).
 #pragma once
@@ -40,6 +40,27 @@ __device__ __forceinline__ f2 apply_xf(f2 xy, uint32_t sample_index, const ScanX
   o.x = (m.r00 * x1 + m.r01 * y1) + m.tx;
   o.y = (m.r10 * x1 + m.r11 * y1) + m.ty;
   return o;
+}
+
+// a / 4000 as mul + 2 FMA: the form rpl_voxel.hip's div_by proves bit-identical to the IEEE divide
+// on the device (k_validate_div) before KParams::fast_d4000 is set
+__device__ __forceinline__ float xf_div4000(float a) {
+  const float q = a * 0.00025f;
+  const float e = fmaf(-q, 4000.0f, a);
+  return fmaf(e, 0.00025f, q);
+}
+
+// One packed node (lo, hi: its two dwords) to its point in the common frame, as E9 and E11 stream it:
+// E2 with the (cos, sin) table `cs`, then E6 + the planar pose.  FAST: the validated divide by 4000.
+template <bool FAST>
+__device__ __forceinline__ f2 sample_xy(uint32_t lo, uint32_t hi, uint32_t i, const float2 *__restrict__ cs,
+                                        const ScanXf &xf) {
+  const uint32_t d = __builtin_amdgcn_alignbit(hi, lo, 16);
+  const float df = __uint2float_rn(d);
+  const float dm = FAST ? xf_div4000(df) : df / 4000.0f;  // :590
+  const float2 c = cs[lo & 0xFFFFu];
+  f2 xy = {c.x * dm, c.y * dm};                            // E2
+  return apply_xf(xy, i, xf);                              // E6 + pose, as E8
 }
 
 // What of one scan the streaming code needs besides its nodes: the E5 keep bits and the E8 transform.

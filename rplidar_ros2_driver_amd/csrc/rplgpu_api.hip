@@ -1436,6 +1436,221 @@ int32_t rplgpu_filter_laserscan(rplgpu_handle_t h, const float *ranges, const fl
   return RPLGPU_OK;
 }
 
+// ---- E11: one ray-cast occupancy grid per group of scans (include/rplgpu_msg.h) ---------------------
+
+void rplgpu_default_occ_grid(rplgpu_occ_grid_t *grid) {
+  if (!grid) return;
+  grid->origin_x = -25.6f;
+  grid->origin_y = -25.6f;
+  grid->resolution = 0.05f;
+  grid->width = 1024;
+  grid->height = 1024;
+  grid->range_min = 0.0f;
+  grid->obstacle_max = 25.0f;
+  grid->raytrace_max = 30.0f;
+}
+
+int32_t rplgpu_occ_grid_check(const rplgpu_occ_grid_t *g) {
+  if (!g) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(g->origin_x) || !std::isfinite(g->origin_y) || !std::isfinite(g->resolution) ||
+      !std::isfinite(g->range_min) || !std::isfinite(g->obstacle_max) || !std::isfinite(g->raytrace_max))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!(g->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  if (g->width == 0 || g->width > RPLGPU_MAX_OCC_DIM || g->height == 0 || g->height > RPLGPU_MAX_OCC_DIM)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!(0.0f <= g->range_min && g->range_min < g->obstacle_max && g->obstacle_max <= g->raytrace_max))
+    return RPLGPU_ERR_INVALID_ARG;
+  if ((double)g->raytrace_max / (double)g->resolution > (double)RPLGPU_MAX_OCC_STEPS) return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+static rpl::OccK occ_kernel_args(const rplgpu_occ_grid_t &g) {
+  return rpl::OccK{g.origin_x, g.origin_y, g.resolution, g.width, g.height, g.range_min, g.obstacle_max,
+                   g.raytrace_max};
+}
+
+// d_t0: the per-scan time offsets of E6 for this call (the handle's, or the host door's own), or NULL
+static int32_t occ_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                        const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                        const float *d_motion, const float *d_pose2d, const float *d_t0,
+                        const rplgpu_occ_grid_t *grid, const int8_t *d_prev, int8_t *d_grid,
+                        uint64_t grid_stride, uint32_t *d_cells, uint32_t *d_status) {
+  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
+  if (rc) return rc;
+  if (!p || !grid || !d_grid || group == 0) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_occ_grid_check(grid) != RPLGPU_OK) {
+    h->err = "rplgpu_occupancy_grid_dev: invalid rplgpu_occ_grid_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (grid_stride < (uint64_t)grid->width * grid->height || (grid_stride & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_grid) & 3u)) {
+    h->err = "rplgpu_occupancy_grid_dev: grid_stride must be >= width * height and a multiple of 4, d_grid 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_prev == d_grid) {
+    h->err = "rplgpu_occupancy_grid_dev: d_prev must not be d_grid (the grid is its own scratch)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (B == 0) return RPLGPU_OK;
+  if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
+      (d_pose2d && !device_readable(h, d_pose2d, "d_pose2d")) ||
+      (d_prev && !device_readable(h, d_prev, "d_prev")) || !device_readable(h, d_grid, "d_grid") ||
+      (d_cells && !device_readable(h, d_cells, "d_cells")) || (d_status && !device_readable(h, d_status, "d_status")))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (d_t0 && !d_motion) {
+    h->err = "rplgpu_occupancy_grid_dev: scan time offsets are set (rplgpu_set_scan_time_offsets_dev) but d_motion is NULL";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
+    h->err = "ror_radius must be in (0, 1e6] m";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  group = std::min(group, B);  // as E8: "all sensors in one grid" may be asked for with any group >= B
+  if ((uint64_t)group * std::min(n_stride, rpl::kMaxN) > (1ull << 24)) {
+    h->err = "rplgpu_occupancy_grid_dev: group x n_stride above 2^24 samples";
+    return RPLGPU_ERR_CAPACITY;
+  }
+  const uint32_t G = (B + group - 1u) / group;
+  RPL_HIP(h, hipSetDevice(h->device));
+  rpl::KParams kp = to_kparams(*p);
+  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
+  rpl::Tables T = tables_of(h);
+  T.scan_t0 = d_t0;
+  const rpl::OccK k = occ_kernel_args(*grid);
+  const uint32_t *mask = nullptr;
+  if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E8's two-kernel path and E9 apply
+    RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
+                                    kMaskStride));
+    mask = h->d_rormask;
+  }
+  if (d_cells) RPL_HIP(h, hipMemsetAsync(d_cells, 0, (size_t)G * 12u, h->stream));
+  if (d_status) RPL_HIP(h, hipMemsetAsync(d_status, 0, (size_t)G * 4u, h->stream));
+  RPL_HIP(h, rpl::launch_occ_prepare(h->stream, d_grid, grid_stride, G, k));
+  RPL_HIP(h, rpl::launch_occ_walk(h->stream, d_nodes, n_stride, d_n_per_scan, B, group, kp, T, mask, kMaskStride,
+                                  d_motion, d_pose2d, k, d_grid, grid_stride, d_status));
+  RPL_HIP(h, rpl::launch_occ_finish(h->stream, d_grid, grid_stride, G, k, d_prev, d_cells));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_occupancy_grid_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                                  const uint32_t *d_n_per_scan, uint32_t B, uint32_t group,
+                                  const rplgpu_params_t *p, const float *d_motion, const float *d_pose2d,
+                                  const rplgpu_occ_grid_t *grid, const int8_t *d_prev, int8_t *d_grid,
+                                  uint64_t grid_stride, uint32_t *d_cells, uint32_t *d_status) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  return occ_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, h->scan_t0, grid, d_prev,
+                  d_grid, grid_stride, d_cells, d_status);
+}
+
+int32_t rplgpu_occupancy_grid(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                              const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                              const float *motion, const float *pose2d, const float *t0,
+                              const rplgpu_occ_grid_t *grid, const int8_t *prev, int8_t *grid_out,
+                              uint32_t cells[3], uint32_t *status) {
+  if (!h || !nodes || !n_per_scan || !p || !grid || !grid_out || n_scans == 0 || n_stride == 0)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_occ_grid_check(grid) != RPLGPU_OK) {
+    h->err = "rplgpu_occupancy_grid: invalid rplgpu_occ_grid_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
+  RPL_HIP(h, hipSetDevice(h->device));
+  const size_t cells_n = (size_t)grid->width * grid->height, stride = (cells_n + 3u) & ~(size_t)3u;
+  const size_t nb = (size_t)n_scans * n_stride * 8u;
+  // one allocation per call (a convenience door, not the hot path): grid | prev | nodes | lengths |
+  // motion | pose | t0 | cells + status, every part 16-byte aligned
+  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  const size_t o_prev = up16(stride), o_nodes = o_prev + up16(prev ? stride : 0), o_len = o_nodes + up16(nb),
+               o_mo = o_len + up16(4u * n_scans), o_po = o_mo + up16(motion ? 16u * n_scans : 0),
+               o_t0 = o_po + up16(pose2d ? 24u * n_scans : 0), o_small = o_t0 + up16(t0 ? 4u * n_scans : 0),
+               total = o_small + 16u;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_occupancy_grid: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t small[4] = {0, 0, 0, 0};
+  auto run = [&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(d + o_nodes, nodes, nb, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_len, n_per_scan, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (prev) RPL_HIP(h, hipMemcpyAsync(d + o_prev, prev, cells_n, hipMemcpyHostToDevice, h->stream));
+    if (motion) RPL_HIP(h, hipMemcpyAsync(d + o_mo, motion, 16u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (pose2d) RPL_HIP(h, hipMemcpyAsync(d + o_po, pose2d, 24u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (t0) RPL_HIP(h, hipMemcpyAsync(d + o_t0, t0, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
+    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);
+    const int32_t rc = occ_impl(
+        h, reinterpret_cast<const rplgpu_node_t *>(d + o_nodes), n_stride,
+        reinterpret_cast<const uint32_t *>(d + o_len), n_scans, n_scans, p,
+        motion ? reinterpret_cast<const float *>(d + o_mo) : nullptr,
+        pose2d ? reinterpret_cast<const float *>(d + o_po) : nullptr,
+        t0 ? reinterpret_cast<const float *>(d + o_t0) : nullptr, grid,
+        prev ? reinterpret_cast<const int8_t *>(d + o_prev) : nullptr, reinterpret_cast<int8_t *>(d), stride,
+        d_small, d_small + 3);
+    if (rc) return rc;
+    RPL_HIP(h, hipMemcpyAsync(grid_out, d, cells_n, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d_small, 16, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;
+  if (cells) std::memcpy(cells, small, 12);
+  if (status) *status = small[3];
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_msg_occupancy_layout(size_t frame_id_len, uint32_t width, uint32_t height,
+                                    rplgpu_occupancy_layout_t *out) {
+  if (!out || frame_id_len > (1u << 20) || width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 ||
+      height > RPLGPU_MAX_OCC_DIM)
+    return RPLGPU_ERR_INVALID_ARG;
+  rplmsg::Writer w(nullptr, 0);
+  std::string fid(frame_id_len, 'x');
+  rplmsg::write_occupancy(w, fid.data(), frame_id_len, rplgpu_stamp_t{0, 0}, 1.0f, width, height, 0.0f, 0.0f, out);
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_occupancy_grid_msgs_dev(rplgpu_handle_t h, const int8_t *d_grid, uint64_t grid_stride, uint32_t G,
+                                       const rplgpu_occ_grid_t *grid, const char *frame_id,
+                                       const rplgpu_stamp_t *d_stamps, uint8_t *d_msgs, uint32_t msg_stride,
+                                       uint32_t *d_msg_len, uint32_t *d_status) {
+  if (!h || !grid || !frame_id) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_occ_grid_check(grid) != RPLGPU_OK) {
+    h->err = "rplgpu_occupancy_grid_msgs_dev: invalid rplgpu_occ_grid_t";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0) return RPLGPU_OK;
+  if (!d_grid || !d_stamps || !d_msgs || !d_msg_len || (msg_stride & 3u) || (grid_stride & 3u) ||
+      grid_stride < (uint64_t)grid->width * grid->height || (reinterpret_cast<uintptr_t>(d_grid) & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_msgs) & 3u))
+    return RPLGPU_ERR_INVALID_ARG;
+  const size_t fl = std::strlen(frame_id);
+  if (fl > rplmsg::kMaxFrameId) {
+    h->err = "frame_id longer than 255 bytes";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  rplmsg::Prefix P;
+  std::memset(&P, 0, sizeof(P));
+  rplmsg::Writer w(reinterpret_cast<uint8_t *>(P.words), sizeof(P.words));
+  rplgpu_occupancy_layout_t L;
+  rplmsg::write_occupancy(w, frame_id, fl, rplgpu_stamp_t{0, 0}, grid->resolution, grid->width, grid->height,
+                          grid->origin_x, grid->origin_y, &L);
+  P.stamp_off = 4;
+  P.len = L.data_off;  // every scalar and the data length word come with the template
+  P.a_off = L.map_load_time_off;
+  if (P.len > sizeof(P.words) || (P.len & 3u)) {
+    h->err = "message prefix does not fit the device template";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_msg_occupancy(h->stream, d_grid, grid_stride, grid->width * grid->height, G, d_stamps, P,
+                                       d_msgs, msg_stride, d_msg_len, d_status));
+  return RPLGPU_OK;
+}
+
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,

@@ -12,10 +12,12 @@
 //   host_selftest serialized <nodes.bin> <out.bin> <is_new> <inverted> <scan_processing> <cloud 1|2>
 //   out.bin: u32 published, u32 len_scan, LaserScan message bytes, u32 len_cloud, PointCloud2
 //            message bytes   (frame_id "laser_frame", stamp 1727000000.123456789, duration 0.125)
-//   no arguments: config-1 smoke run (3 Dummy scans through the whole path).
+//   no arguments: config-1 smoke run (3 Dummy scans through the whole path), then the E11 mirror call once
+//   against a three-ray known answer.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -41,6 +43,17 @@ struct PointCloud2 {  // field names of sensor_msgs/msg/PointCloud2
   uint32_t point_step = 0, row_step = 0;
   std::vector<uint8_t> data;
   bool is_dense = false;
+};
+struct OccupancyGrid {  // field names of nav_msgs/msg/OccupancyGrid (header left out)
+  struct {
+    float resolution = 0;
+    uint32_t width = 0, height = 0;
+    struct {
+      struct { double x = 0, y = 0, z = 0; } position;
+      struct { double x = 0, y = 0, z = 0, w = 0; } orientation;
+    } origin;
+  } info;
+  std::vector<int8_t> data;
 };
 struct RclSerialized {  // the fields of rcl_serialized_message_t (rcutils_uint8_array_t) used here
   uint8_t *buffer = nullptr;
@@ -180,6 +193,33 @@ int main(int argc, char **argv) {
       std::printf("dummy scan %d: %zu beams, ranges[0]=%.6f intensities[0]=%.1f\n", s,
                   msg.ranges.size(), msg.ranges[0], msg.intensities[0]);
     }
+    // E11, three rays along +x from a sensor in cell (0, 1) of an 8 x 3 grid of 1 m cells: the return at 2 m
+    // marks cell 2, the one at 4 m (beyond obstacle_max) only clears up to cell 3, the one at 7 m is cut at
+    // 5 m and clears up to cell 5 — the cut end included.
+    std::vector<std::vector<rplgpu_node_t>> step(1);
+    for (uint32_t d : {8000u, 16000u, 28000u}) {
+      rplgpu_node_t nd{};
+      nd.dist_mm_q2 = d;
+      nd.quality = 200;
+      step[0].push_back(nd);
+    }
+    const rplgpu_occ_grid_t og = {-0.5f, -1.5f, 1.0f, 8, 3, 0.0f, 3.2f, 5.0f};
+    OccupancyGrid grid_msg;
+    uint32_t cells[3] = {0, 0, 0}, status = 99;
+    if (!path.fill_occupancy_grid(step, rplgpu_host::ScanConfig(), og, nullptr, nullptr, nullptr, grid_msg, cells,
+                                  &status)) {
+      std::fprintf(stderr, "occupancy grid failed: %s\n", path.last_error().c_str());
+      return 7;
+    }
+    static const int8_t want[24] = {-1, -1, -1, -1, -1, -1, -1, -1, 0, 0, 100, 0, 0, 0, -1, -1,
+                                    -1, -1, -1, -1, -1, -1, -1, -1};
+    if (grid_msg.data.size() != 24 || std::memcmp(grid_msg.data.data(), want, 24) != 0 || cells[0] != 5 ||
+        cells[1] != 1 || cells[2] != 18 || status != 0 || grid_msg.info.width != 8 ||
+        grid_msg.info.origin.orientation.w != 1.0) {
+      std::fprintf(stderr, "occupancy grid: wrong answer\n");
+      return 8;
+    }
+    std::printf("occupancy grid: 3 rays, cells 0/100/-1 = %u/%u/%u\n", cells[0], cells[1], cells[2]);
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

@@ -18,6 +18,8 @@
 //         (src/sdk/src/sl_lidar_driver.cpp:272-315), for RECORDED answer streams
 //         -> rplgpu_host::ScanPath::replay_recording(ans, bytes, n, listener) /
 //            rplgpu_host::ScanAssembler
+//   occ the consumer's first loop (a costmap obstacle layer's mark-and-clear over the beams of a time step):
+//         -> rplgpu_host::ScanPath::fill_occupancy_grid(scans, ..., grid_msg)   (E11)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -100,9 +102,10 @@ class ScanPath {
 
   // on_configure (src/rplidar_node.cpp:116): bind to a device.  The SDK never hands out more
   // than 8192 nodes per scan (src/lidar_driver_wrapper.cpp:316-318).
-  bool configure(int device_id = 0, uint32_t max_samples_per_scan = 8192) {
+  // `max_scans`: how many scans one call may hand in (only fill_occupancy_grid takes more than one).
+  bool configure(int device_id = 0, uint32_t max_samples_per_scan = 8192, uint32_t max_scans = 1) {
     cleanup();
-    const int32_t rc = rplgpu_create(device_id, max_samples_per_scan, 1, &h_);
+    const int32_t rc = rplgpu_create(device_id, max_samples_per_scan, max_scans ? max_scans : 1, &h_);
     if (rc != RPLGPU_OK) {
       last_error_ = std::string("rplgpu_create failed (") + std::to_string(rc) + "): " +
                     rplgpu_last_error(nullptr);
@@ -307,6 +310,53 @@ class ScanPath {
     return true;
   }
 
+  // ext E11 (include/rplgpu_msg.h): the scans of ONE time step (one per sensor, at most the `max_scans` of
+  // configure) ray-cast into a nav_msgs/OccupancyGrid-shaped message — what a costmap obstacle layer's
+  // raytraceFreespace + mark loop does per observation.  pose2d: 6 floats per scan (r00 r01 tx r10 r11 ty,
+  // sensor in the grid's frame), motion: 4 per scan (vx vy wz time_increment), t0: 1 per scan; each may be
+  // null.  `grid_msg.data` of the right size is the previous grid (cells no ray touches keep their value);
+  // any other size starts from unknown (-1).  Fills info.resolution / width / height / origin and data;
+  // header and info.map_load_time are the caller's.
+  template <class NodeT, class OccupancyGridT>
+  bool fill_occupancy_grid(const std::vector<std::vector<NodeT>> &scans, const ScanConfig &cfg,
+                           const rplgpu_occ_grid_t &grid, const float *pose2d, const float *motion,
+                           const float *t0, OccupancyGridT &grid_msg, uint32_t cells[3] = nullptr,
+                           uint32_t *status = nullptr) {
+    if (scans.empty()) return false;
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    size_t stride = 1;
+    for (const auto &s : scans) stride = s.size() > stride ? s.size() : stride;
+    if (stride > max_n_) return fail("scan larger than the configured capacity");
+    occ_nodes_.assign(scans.size() * stride, rplgpu_node_t{});
+    occ_len_.resize(scans.size());
+    for (size_t b = 0; b < scans.size(); ++b) {
+      if (!scans[b].empty()) std::memcpy(&occ_nodes_[b * stride], scans[b].data(), scans[b].size() * 8);
+      occ_len_[b] = static_cast<uint32_t>(scans[b].size());
+    }
+    const size_t n_cells = static_cast<size_t>(grid.width) * grid.height;
+    const bool has_prev = n_cells != 0 && grid_msg.data.size() == n_cells;
+    if (has_prev) occ_prev_.assign(grid_msg.data.begin(), grid_msg.data.end());
+    occ_out_.resize(n_cells ? n_cells : 1);
+    const rplgpu_params_t p = cfg.to_params();
+    if (rplgpu_occupancy_grid(h_, occ_nodes_.data(), static_cast<uint32_t>(stride), occ_len_.data(),
+                              static_cast<uint32_t>(scans.size()), &p, motion, pose2d, t0, &grid,
+                              has_prev ? occ_prev_.data() : nullptr, occ_out_.data(), cells, status) != RPLGPU_OK)
+      return note_error();
+    grid_msg.info.resolution = grid.resolution;
+    grid_msg.info.width = grid.width;
+    grid_msg.info.height = grid.height;
+    grid_msg.info.origin.position.x = grid.origin_x;
+    grid_msg.info.origin.position.y = grid.origin_y;
+    grid_msg.info.origin.position.z = 0.0;
+    grid_msg.info.origin.orientation.x = 0.0;
+    grid_msg.info.origin.orientation.y = 0.0;
+    grid_msg.info.origin.orientation.z = 0.0;
+    grid_msg.info.origin.orientation.w = 1.0;
+    grid_msg.data.assign(occ_out_.begin(), occ_out_.begin() + n_cells);
+    return true;
+  }
+
  private:
   bool fail(const char *msg) {
     last_error_ = msg;
@@ -321,6 +371,9 @@ class ScanPath {
   std::vector<float> ranges_, intens_, xyzi_;
   std::vector<rplgpu_node_t> dec_nodes_;
   std::vector<uint32_t> dec_resets_;
+  std::vector<rplgpu_node_t> occ_nodes_;
+  std::vector<uint32_t> occ_len_;
+  std::vector<int8_t> occ_prev_, occ_out_;
   std::string last_error_;
   uint32_t min_samples_ = 0;
 };
