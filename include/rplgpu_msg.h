@@ -454,6 +454,64 @@ int32_t rplgpu_occupancy_grid_msgs_dev(rplgpu_handle_t h, const int8_t *d_grid, 
                                        const rplgpu_stamp_t *d_stamps, uint8_t *d_msgs, uint32_t msg_stride,
                                        uint32_t *d_msg_len, uint32_t *d_status);
 
+/* ---- E12: the grids of E11 inflated into costmaps (row f7; the costmap inflation layer) ----------------------
+ * What every consumer of an obstacle grid runs first (Nav2 planners and controllers, anything that checks a
+ * footprint): each lethal cell is grown by the robot's inscribed radius and a decaying cost is laid around
+ * it, out to the inflation radius.  On the CPU a priority-queue flood over the whole grid per update; here
+ * one data-parallel pass over the bytes E11 left in device memory, on the same stream.  Nothing in the
+ * reference inflates a grid, so these rules ARE the definition (parity unpinned, as E5-E11). */
+#define RPLGPU_MAX_INFLATION_CELLS 64u
+typedef struct rplgpu_inflation {
+  float    inscribed_radius;     /* m, >= 0 */
+  float    inflation_radius;     /* m, >= inscribed_radius */
+  float    cost_scaling_factor;  /* 1/m, >= 0 */
+  uint32_t inflate_unknown;      /* 0 / 1 */
+} rplgpu_inflation_t;
+/* inscribed_radius 0.22 m, inflation_radius 0.55 m, cost_scaling_factor 3.0 / m, inflate_unknown 0 */
+void rplgpu_default_inflation(rplgpu_inflation_t *f);
+/* Host only (no handle, no device).  Rc = (uint32_t)ceil((double)inflation_radius / (double)resolution), the
+ * reach in cells, every float widened to double first: 12, not 11, for the defaults at 0.05 m, because
+ * (double)0.55f / (double)0.05f > 11.  RPLGPU_ERR_INVALID_ARG for a value that is not finite, a negative
+ * value, resolution <= 0, inflation_radius < inscribed_radius, inflate_unknown > 1 or
+ * Rc > RPLGPU_MAX_INFLATION_CELLS. */
+int32_t rplgpu_inflation_check(const rplgpu_inflation_t *f, float resolution);
+/* Host only.  The COST TABLE of a checked spec, Rc * Rc + 1 bytes indexed by the squared cell distance k:
+ *   table[0] = 100;  for k >= 1, d = sqrt((double)k) * (double)resolution:
+ *   d <= (double)inscribed_radius: 99;  otherwise
+ *   (uint8_t)(int)(98.0 * exp(-(double)cost_scaling_factor * (d - (double)inscribed_radius))), truncated: 0 .. 98.
+ * The scale in which Nav2 publishes a costmap as an OccupancyGrid (100 lethal, 99 inscribed, 1 .. 98 the
+ * rest), so the result goes straight into rplgpu_occupancy_grid_msgs_dev.  The table is non-increasing in k.
+ * *rc_out (optional) = Rc.  RPLGPU_ERR_CAPACITY when table_cap < Rc * Rc + 1 (rc_out is set all the same),
+ * RPLGPU_ERR_INVALID_ARG for a spec the check refuses. */
+int32_t rplgpu_inflation_table(const rplgpu_inflation_t *f, float resolution, uint8_t *table, uint32_t table_cap,
+                               uint32_t *rc_out);
+/* PER CELL c of grid g, input byte v (int8) at d_in + g * in_stride + cy * width + cx:
+ *   D2(c) = the minimum of dx*dx + dy*dy over all cells q of the SAME grid whose input is >= 100 (cells
+ *   outside [0, width) x [0, height) hold nothing);
+ *   cost = d_table[D2] when such a q exists and D2 <= rc * rc, otherwise 0;
+ *   v >= 100: 100;   0 <= v <= 99: max(v, cost) (the history values E11 copied from d_prev survive when
+ *   they are larger);   v < 0 (unknown): cost when (inflate_unknown ? cost > 0 : cost >= 99), otherwise -1.
+ * The result at d_out + g * out_stride + cy * width + cx is a function of the input set alone: no order, no
+ * ties.  d_table: rc * rc + 1 bytes in DEVICE memory that the caller uploads once (inflation parameters are
+ * node parameters); a table the caller made itself is allowed as long as it is non-increasing in k and holds
+ * values 0 .. 100 (the kernel may stop looking once no nearer lethal cell can exist).  Nothing is stored on the
+ * handle and nothing is copied from host memory.  d_cells (optional): per grid the number of result cells that
+ * are 100, 99, 1 .. 98 and -1 (4 words; cleared on the stream by the call).
+ * RPLGPU_ERR_INVALID_ARG for d_in == d_out (any other overlap is the caller's error), rc >
+ * RPLGPU_MAX_INFLATION_CELLS, inflate_unknown > 1, a dimension of 0 or above RPLGPU_MAX_OCC_DIM, a stride
+ * < width * height or not a multiple of 4, a pointer that is not 4-byte aligned (the E11 rules: the two calls
+ * chain), G == 0 or a NULL d_in / d_out / d_table.  d_in is read in whole 32-bit words (the up to 3 bytes
+ * behind the last cell of a grid, inside in_stride, are read and ignored); bytes of d_out at and beyond
+ * width * height of a grid are never changed.  Asynchronous on the handle's stream. */
+int32_t rplgpu_inflate_grids_dev(rplgpu_handle_t h, const int8_t *d_in, uint64_t in_stride, int8_t *d_out,
+                                 uint64_t out_stride, uint32_t G, uint32_t width, uint32_t height,
+                                 const uint8_t *d_table, uint32_t rc, uint32_t inflate_unknown, uint32_t *d_cells);
+/* ONE grid, HOST buffers (the node-side door, rplgpu_host.hpp): checks the spec, builds and uploads the table,
+ * allocates its device buffers per call and returns when `out` (width * height bytes, not `in`) is in place;
+ * cells (optional): 4 words as above. */
+int32_t rplgpu_inflate_grid(rplgpu_handle_t h, const int8_t *in, uint32_t width, uint32_t height, float resolution,
+                            const rplgpu_inflation_t *f, int8_t *out, uint32_t cells[4]);
+
 #ifdef __cplusplus
 }
 #endif

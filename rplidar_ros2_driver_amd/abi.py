@@ -42,6 +42,7 @@ MAX_MERGE_BEAMS = 16384  # RPLGPU_MAX_MERGE_BEAMS (include/rplgpu_msg.h)
 MAX_FILTER_WINDOW = 64   # RPLGPU_MAX_FILTER_WINDOW (include/rplgpu_msg.h)
 MAX_OCC_DIM = 4096       # RPLGPU_MAX_OCC_DIM (include/rplgpu_msg.h)
 MAX_OCC_STEPS = 8192     # RPLGPU_MAX_OCC_STEPS (include/rplgpu_msg.h)
+MAX_INFLATION_CELLS = 64  # RPLGPU_MAX_INFLATION_CELLS (include/rplgpu_msg.h)
 
 SL_RESULT_OK = 0
 SL_RESULT_OPERATION_FAIL = 0x80008001
@@ -111,6 +112,11 @@ ABI_SYMBOLS = [
     "rplgpu_occupancy_grid",
     "rplgpu_msg_occupancy_layout",
     "rplgpu_occupancy_grid_msgs_dev",
+    "rplgpu_default_inflation",
+    "rplgpu_inflation_check",
+    "rplgpu_inflation_table",
+    "rplgpu_inflate_grids_dev",
+    "rplgpu_inflate_grid",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -274,6 +280,28 @@ class OccGrid(C.Structure):
         return g
 
 
+class Inflation(C.Structure):
+    """Mirror of ``rplgpu_inflation_t`` (E12: the costmap inflation layer over the grids of E11)."""
+
+    _fields_ = [
+        ("inscribed_radius", C.c_float),
+        ("inflation_radius", C.c_float),
+        ("cost_scaling_factor", C.c_float),
+        ("inflate_unknown", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "Inflation":
+        """The library's own defaults (``rplgpu_default_inflation``), then the overrides."""
+        f = cls()
+        load_library().rplgpu_default_inflation(C.byref(f))
+        for k, v in kw.items():
+            if not hasattr(f, k):
+                raise AttributeError(k)
+            setattr(f, k, v)
+        return f
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -429,6 +457,12 @@ def load_library() -> C.CDLL:
                                           C.POINTER(OccGrid), vp, vp, vp, vp]
     lib.rplgpu_msg_occupancy_layout.argtypes = [sz, u32, u32, C.POINTER(OccupancyLayout)]
     lib.rplgpu_occupancy_grid_msgs_dev.argtypes = [vp, vp, u64, u32, C.POINTER(OccGrid), cs, vp, vp, u32, vp, vp]
+    lib.rplgpu_default_inflation.argtypes = [C.POINTER(Inflation)]
+    lib.rplgpu_default_inflation.restype = None
+    lib.rplgpu_inflation_check.argtypes = [C.POINTER(Inflation), C.c_float]
+    lib.rplgpu_inflation_table.argtypes = [C.POINTER(Inflation), C.c_float, vp, u32, vp]
+    lib.rplgpu_inflate_grids_dev.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u32, u32, vp]
+    lib.rplgpu_inflate_grid.argtypes = [vp, vp, u32, u32, C.c_float, C.POINTER(Inflation), vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -717,6 +751,27 @@ class RplGpu:
         self._check(self._lib.rplgpu_occupancy_grid_msgs_dev(
             self._h, d_grid, grid_stride, G, C.byref(grid), frame_id.encode(), d_stamps, d_msgs, msg_stride,
             d_msg_len, d_status))
+
+    def inflate_grids_dev(self, d_in: int, in_stride: int, d_out: int, out_stride: int, G: int, width: int,
+                          height: int, d_table: int, rc: int, inflate_unknown: int = 0, d_cells: int = 0):
+        """E12: G grids (int8, width x height) inflated into costmaps with the device table of
+        ``inflation_table`` (rc * rc + 1 bytes); d_cells: 4 words per grid (100, 99, 1 .. 98, -1)."""
+        self._check(self._lib.rplgpu_inflate_grids_dev(
+            self._h, d_in, in_stride, d_out, out_stride, G, width, height, d_table, rc, inflate_unknown,
+            d_cells))
+
+    def inflate_grid(self, grid: np.ndarray, resolution: float, inflation: Inflation):
+        """E12, one grid, host buffers: (height, width) int8 -> ``(costmap (height, width) int8,
+        (cells 100, cells 99, cells 1 .. 98, cells -1))``."""
+        grid = np.ascontiguousarray(grid, np.int8)
+        if grid.ndim != 2:
+            raise TypeError("grid must be a 2-D int8 array (height, width)")
+        out = np.empty_like(grid)
+        cells = np.zeros(4, np.uint32)
+        self._check(self._lib.rplgpu_inflate_grid(
+            self._h, grid.ctypes.data, grid.shape[1], grid.shape[0], resolution, C.byref(inflation),
+            out.ctypes.data, cells.ctypes.data))
+        return out, tuple(int(c) for c in cells)
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -1126,3 +1181,24 @@ def msg_occupancy_layout(frame_id_len: int, width: int, height: int) -> Occupanc
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_msg_occupancy_layout")
     return lay
+
+
+def inflation_check(inflation: Inflation, resolution: float) -> None:
+    """Host only: validates an E12 spec by the library's own rplgpu_inflation_check; raises
+    RplGpuError(ERR_INVALID_ARG) for a spec the library refuses."""
+    rc = load_library().rplgpu_inflation_check(C.byref(inflation), resolution)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_inflation_check")
+
+
+def inflation_table(inflation: Inflation, resolution: float):
+    """Host only: (table uint8 (Rc * Rc + 1,), Rc) of an E12 spec by the library's own
+    rplgpu_inflation_table: the cost by squared cell distance."""
+    table = np.zeros(MAX_INFLATION_CELLS * MAX_INFLATION_CELLS + 1, np.uint8)
+    reach = np.zeros(1, np.uint32)
+    rc = load_library().rplgpu_inflation_table(C.byref(inflation), resolution, table.ctypes.data, len(table),
+                                               reach.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_inflation_table")
+    r = int(reach[0])
+    return table[:r * r + 1].copy(), r

@@ -286,4 +286,11 @@ hipError_t launch_msg_occupancy(hipStream_t s, const int8_t *grid, unsigned long
                                 const rplmsg::Prefix &P, uint8_t *msgs, uint32_t msg_stride, uint32_t *msg_len,
                                 uint32_t *status);
 
+// E12: the costmap inflation layer over G grids (rpl_inflate.hip, include/rplgpu_msg.h): one gather launch,
+// `table` rc * rc + 1 cost bytes by squared cell distance, cells: 4 words per grid, cleared by the caller;
+// may be null.
+hipError_t launch_inflate(hipStream_t s, const int8_t *in, unsigned long long in_stride, int8_t *out,
+                          unsigned long long out_stride, uint32_t G, uint32_t width, uint32_t height,
+                          const uint8_t *table, uint32_t rc, uint32_t inflate_unknown, uint32_t *cells);
+
 }  // namespace rpl

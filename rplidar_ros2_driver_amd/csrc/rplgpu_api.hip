@@ -1651,6 +1651,144 @@ int32_t rplgpu_occupancy_grid_msgs_dev(rplgpu_handle_t h, const int8_t *d_grid, 
   return RPLGPU_OK;
 }
 
+// ---- E12: the grids of E11 inflated into costmaps (include/rplgpu_msg.h) -------------------------------
+
+void rplgpu_default_inflation(rplgpu_inflation_t *f) {
+  if (!f) return;
+  f->inscribed_radius = 0.22f;
+  f->inflation_radius = 0.55f;
+  f->cost_scaling_factor = 3.0f;
+  f->inflate_unknown = 0;
+}
+
+// the check, and Rc of a spec that passes it
+static int32_t inflation_reach(const rplgpu_inflation_t *f, float resolution, uint32_t *rc) {
+  if (!f) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(f->inscribed_radius) || !std::isfinite(f->inflation_radius) ||
+      !std::isfinite(f->cost_scaling_factor) || !std::isfinite(resolution))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (f->inscribed_radius < 0.0f || f->inflation_radius < 0.0f || f->cost_scaling_factor < 0.0f ||
+      !(resolution > 0.0f) || f->inflation_radius < f->inscribed_radius || f->inflate_unknown > 1u)
+    return RPLGPU_ERR_INVALID_ARG;
+  const double cells = std::ceil((double)f->inflation_radius / (double)resolution);
+  if (!(cells <= (double)RPLGPU_MAX_INFLATION_CELLS)) return RPLGPU_ERR_INVALID_ARG;
+  *rc = (uint32_t)cells;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_inflation_check(const rplgpu_inflation_t *f, float resolution) {
+  uint32_t rc = 0;
+  return inflation_reach(f, resolution, &rc);
+}
+
+int32_t rplgpu_inflation_table(const rplgpu_inflation_t *f, float resolution, uint8_t *table, uint32_t table_cap,
+                               uint32_t *rc_out) {
+  uint32_t rc = 0;
+  if (inflation_reach(f, resolution, &rc) != RPLGPU_OK) return RPLGPU_ERR_INVALID_ARG;
+  if (rc_out) *rc_out = rc;
+  if (!table) return RPLGPU_ERR_INVALID_ARG;
+  if (table_cap < rc * rc + 1u) return RPLGPU_ERR_CAPACITY;
+  const double res = (double)resolution, inscribed = (double)f->inscribed_radius;
+  table[0] = 100;
+  for (uint32_t k = 1; k <= rc * rc; ++k) {
+    const double d = std::sqrt((double)k) * res;
+    table[k] = d <= inscribed
+                   ? (uint8_t)99
+                   : (uint8_t)(int)(98.0 * std::exp(-(double)f->cost_scaling_factor * (d - inscribed)));
+  }
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_inflate_grids_dev(rplgpu_handle_t h, const int8_t *d_in, uint64_t in_stride, int8_t *d_out,
+                                 uint64_t out_stride, uint32_t G, uint32_t width, uint32_t height,
+                                 const uint8_t *d_table, uint32_t rc, uint32_t inflate_unknown, uint32_t *d_cells) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  if (!d_in || !d_out || !d_table || G == 0) {
+    h->err = "rplgpu_inflate_grids_dev: d_in, d_out and d_table must be given and G >= 1";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_in == d_out) {
+    h->err = "rplgpu_inflate_grids_dev: d_out must not be d_in (a tile reads the cells around it)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (rc > RPLGPU_MAX_INFLATION_CELLS || inflate_unknown > 1u) {
+    h->err = "rplgpu_inflate_grids_dev: rc above RPLGPU_MAX_INFLATION_CELLS or inflate_unknown above 1";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 || height > RPLGPU_MAX_OCC_DIM) {
+    h->err = "rplgpu_inflate_grids_dev: width and height must be 1 .. RPLGPU_MAX_OCC_DIM";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint64_t n_cells = (uint64_t)width * height;
+  if (in_stride < n_cells || (in_stride & 3u) || out_stride < n_cells || (out_stride & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_in) & 3u) || (reinterpret_cast<uintptr_t>(d_out) & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_table) & 3u) || (reinterpret_cast<uintptr_t>(d_cells) & 3u)) {
+    h->err = "rplgpu_inflate_grids_dev: strides must be >= width * height and multiples of 4, pointers 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint64_t tiles = (uint64_t)((width + 63u) / 64u) * ((height + 63u) / 64u);
+  if (G * tiles > 0x7FFFFFFFull) {
+    h->err = "rplgpu_inflate_grids_dev: G x tiles above 2^31";
+    return RPLGPU_ERR_CAPACITY;
+  }
+  if (!device_readable(h, d_in, "d_in") || !device_readable(h, d_out, "d_out") ||
+      !device_readable(h, d_table, "d_table") || (d_cells && !device_readable(h, d_cells, "d_cells")))
+    return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  if (d_cells) RPL_HIP(h, hipMemsetAsync(d_cells, 0, (size_t)G * 16u, h->stream));
+  RPL_HIP(h, rpl::launch_inflate(h->stream, d_in, in_stride, d_out, out_stride, G, width, height, d_table, rc,
+                                 inflate_unknown, d_cells));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_inflate_grid(rplgpu_handle_t h, const int8_t *in, uint32_t width, uint32_t height, float resolution,
+                            const rplgpu_inflation_t *f, int8_t *out, uint32_t cells[4]) {
+  if (!h || !in || !out || !f || in == out) return RPLGPU_ERR_INVALID_ARG;
+  if (width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 || height > RPLGPU_MAX_OCC_DIM) {
+    h->err = "rplgpu_inflate_grid: width and height must be 1 .. RPLGPU_MAX_OCC_DIM";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  std::vector<uint8_t> table((size_t)RPLGPU_MAX_INFLATION_CELLS * RPLGPU_MAX_INFLATION_CELLS + 1u);
+  uint32_t reach = 0;
+  if (rplgpu_inflation_table(f, resolution, table.data(), (uint32_t)table.size(), &reach) != RPLGPU_OK) {
+    h->err = "rplgpu_inflate_grid: invalid rplgpu_inflation_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  const size_t cells_n = (size_t)width * height, stride = (cells_n + 3u) & ~(size_t)3u;
+  const size_t n_table = (size_t)reach * reach + 1u;
+  // one allocation per call (a convenience door, not the hot path): in | out | table | cells, 16-byte aligned
+  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  const size_t o_out = up16(stride), o_table = o_out + up16(stride), o_cells = o_table + up16(n_table),
+               total = o_cells + 16u;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_inflate_grid: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t small[4] = {0, 0, 0, 0};
+  auto run = [&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(d, in, cells_n, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_table, table.data(), n_table, hipMemcpyHostToDevice, h->stream));
+    const int32_t rc = rplgpu_inflate_grids_dev(h, reinterpret_cast<const int8_t *>(d), stride,
+                                                reinterpret_cast<int8_t *>(d + o_out), stride, 1, width, height,
+                                                d + o_table, reach, f->inflate_unknown,
+                                                reinterpret_cast<uint32_t *>(d + o_cells));
+    if (rc) return rc;
+    RPL_HIP(h, hipMemcpyAsync(out, d + o_out, cells_n, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d + o_cells, 16, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;
+  if (cells) std::memcpy(cells, small, 16);
+  return RPLGPU_OK;
+}
+
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,

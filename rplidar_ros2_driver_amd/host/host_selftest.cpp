@@ -220,6 +220,24 @@ int main(int argc, char **argv) {
       return 8;
     }
     std::printf("occupancy grid: 3 rays, cells 0/100/-1 = %u/%u/%u\n", cells[0], cells[1], cells[2]);
+    // E12 over that grid: its one lethal cell (2, 1) with 1 m cells, inscribed 1 m, inflation 2 m, scaling 1 / m.
+    // The cleared cells 1 and 3 of its row become 99 and cells 0 and 4 become 36 (98 exp(-1) = 36.05); the
+    // unknown cells above and below it (distance 1) become 99, every other unknown cell stays -1 (64 < 99).
+    const rplgpu_inflation_t inf = {1.0f, 2.0f, 1.0f, 0};
+    OccupancyGrid cost_msg;
+    uint32_t icells[4] = {9, 9, 9, 9};
+    if (!path.inflate_grid(grid_msg, inf, cost_msg, icells)) {
+      std::fprintf(stderr, "inflation failed: %s\n", path.last_error().c_str());
+      return 9;
+    }
+    static const int8_t cost_want[24] = {-1, -1, 99, -1, -1, -1, -1, -1, 36, 99, 100, 99, 36, 0, -1, -1,
+                                         -1, -1, 99, -1, -1, -1, -1, -1};
+    if (cost_msg.data.size() != 24 || std::memcmp(cost_msg.data.data(), cost_want, 24) != 0 || icells[0] != 1 ||
+        icells[1] != 4 || icells[2] != 2 || icells[3] != 16 || cost_msg.info.width != 8) {
+      std::fprintf(stderr, "inflation: wrong answer\n");
+      return 10;
+    }
+    std::printf("inflation: cells 100/99/1..98/-1 = %u/%u/%u/%u\n", icells[0], icells[1], icells[2], icells[3]);
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

@@ -20,6 +20,8 @@
 //            rplgpu_host::ScanAssembler
 //   occ the consumer's first loop (a costmap obstacle layer's mark-and-clear over the beams of a time step):
 //         -> rplgpu_host::ScanPath::fill_occupancy_grid(scans, ..., grid_msg)   (E11)
+//   inf the consumer's second loop (a costmap inflation layer over that grid):
+//         -> rplgpu_host::ScanPath::inflate_grid(grid_msg, inflation, costmap_msg)  (E12)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -354,6 +356,29 @@ class ScanPath {
     grid_msg.info.origin.orientation.z = 0.0;
     grid_msg.info.origin.orientation.w = 1.0;
     grid_msg.data.assign(occ_out_.begin(), occ_out_.begin() + n_cells);
+    return true;
+  }
+
+  // ext E12 (include/rplgpu_msg.h): `grid_msg` (what fill_occupancy_grid left) inflated into `costmap_msg` —
+  // what a costmap inflation layer does per update: 100 lethal, 99 within the inscribed radius, 1 .. 98
+  // decaying out to the inflation radius, in the scale Nav2 publishes a costmap as an OccupancyGrid.  Copies
+  // info and fills data (the header is the caller's); cells (optional): result cells that are 100, 99, 1 .. 98 and -1.
+  // costmap_msg may not be grid_msg.
+  template <class OccupancyGridT>
+  bool inflate_grid(const OccupancyGridT &grid_msg, const rplgpu_inflation_t &inflation,
+                    OccupancyGridT &costmap_msg, uint32_t cells[4] = nullptr) {
+    if (!h_) return fail("rplgpu handle not configured");
+    if (&grid_msg == &costmap_msg) return fail("inflate_grid: the costmap may not be the grid");
+    last_error_.clear();
+    const size_t n_cells = static_cast<size_t>(grid_msg.info.width) * grid_msg.info.height;
+    if (n_cells == 0 || grid_msg.data.size() != n_cells) return fail("inflate_grid: data is not width x height");
+    occ_prev_.assign(grid_msg.data.begin(), grid_msg.data.end());
+    occ_out_.resize(n_cells);
+    if (rplgpu_inflate_grid(h_, occ_prev_.data(), grid_msg.info.width, grid_msg.info.height,
+                            grid_msg.info.resolution, &inflation, occ_out_.data(), cells) != RPLGPU_OK)
+      return note_error();
+    costmap_msg.info = grid_msg.info;
+    costmap_msg.data.assign(occ_out_.begin(), occ_out_.end());
     return true;
   }
 

@@ -1,0 +1,189 @@
+"""E12 on the device: rplgpu_inflate_grids_dev against tests/inflate_oracle.py byte for byte (costmaps,
+d_cells, the guard bytes behind every grid), chained behind rplgpu_occupancy_grid_dev and in front of
+rplgpu_occupancy_grid_msgs_dev, the host-buffer door, and every refusal.  The inputs and their regime checks
+live in tests/inflate_cases.py; every table is the library's own or hand-made, so no exp enters."""
+import numpy as np
+import pytest
+
+from rplidar_ros2_driver_amd import abi
+from tests import inflate_cases as ic
+from tests import inflate_oracle as io
+
+pytestmark = pytest.mark.gpu
+GUARD = 0x5A
+
+
+def _run(gpu, c, flag, in_pad=0, out_pad=4, cells=True):
+    """-> (results (G, H, W) int8, cells (G, 4), out guard bytes (G, out_stride - W * H))."""
+    import torch
+    dev = torch.device("cuda:0")
+    grids = c["grids"]
+    G, H, W = grids.shape
+    base = (W * H + 3) & ~3
+    s_in, s_out = base + in_pad, base + out_pad
+    host = np.full((G, s_in), GUARD, np.uint8)
+    host[:, :W * H] = grids.reshape(G, -1).view(np.uint8)
+    d_in = torch.from_numpy(host.reshape(-1)).to(dev)
+    d_out = torch.full((G * s_out,), GUARD, dtype=torch.uint8, device=dev)
+    d_table = torch.from_numpy(np.ascontiguousarray(c["table"])).to(dev)
+    d_cells = torch.full((G * 4,), 777, dtype=torch.int32, device=dev)
+    gpu.inflate_grids_dev(d_in.data_ptr(), s_in, d_out.data_ptr(), s_out, G, W, H, d_table.data_ptr(), c["rc"],
+                          flag, d_cells.data_ptr() if cells else 0)
+    gpu.synchronize()
+    raw = d_out.cpu().numpy().reshape(G, s_out)
+    assert d_in.cpu().numpy().tobytes() == host.tobytes()  # the input is only read
+    return (raw[:, :W * H].view(np.int8).reshape(G, H, W), d_cells.cpu().numpy().reshape(G, 4).astype(np.int64),
+            raw[:, W * H:])
+
+
+def _check(got, want):
+    res, cells, guard = got
+    assert len(res) == len(want)
+    for g, (wg, wc) in enumerate(want):
+        diff = np.argwhere(res[g] != wg)
+        print(f"grid {g}: cells {tuple(cells[g])} want {wc}, {len(diff)} cells differ")
+        assert len(diff) == 0, (g, diff[:8], res[g][tuple(diff[:8].T)], wg[tuple(diff[:8].T)])
+        assert tuple(cells[g]) == wc, g
+    assert (guard == GUARD).all()
+
+
+@pytest.mark.parametrize("rc", [0, 1, 64])
+def test_tiny_grids(gpu, rc):
+    ic.tiny_regime(rc)
+    for c in ic.tiny_cases(rc):
+        for flag in (0, 1):
+            _check(_run(gpu, c, flag), ic.want(c, flag))
+
+
+@pytest.mark.parametrize("flag", [0, 1])
+@pytest.mark.parametrize("rc", [5, 64])
+def test_tile_edges_and_corners(gpu, rc, flag):
+    ic.edges_regime()
+    c = ic.edges_case(rc)
+    got = _run(gpu, c, flag)
+    _check(got, ic.want(c, flag, f"edges{rc}"))
+    if rc == 5:  # and what the header's formula gives by hand: 98 exp(-3 * (0.25 - 0.175)) = 78.25
+        cx, cy = ic.CORNER
+        assert got[0][0][cy - 4, cx - 3] == 78 and got[0][0][cy - 3, cx - 4] == 78 and got[0][0][cy - 4, cx - 4] == 0
+
+
+@pytest.mark.parametrize("name", ["free", "unknown", "lethal", "cut_disc"])
+def test_uniform_grids_and_a_cut_disc(gpu, name):
+    ic.uniform_regime()
+    c = ic.uniform_cases()[name]
+    for flag in (0, 1):
+        _check(_run(gpu, c, flag), ic.want(c, flag))
+
+
+def test_three_grids_padded_strides(gpu):
+    ic.batch_regime()
+    c = ic.batch_case()
+    _check(_run(gpu, c, 0, in_pad=8, out_pad=20), ic.want(c, 0, "batch"))
+    _check(_run(gpu, c, 1, in_pad=12, out_pad=4), ic.want(c, 1, "batch"))
+    got = _run(gpu, c, 0, cells=False)  # d_cells is optional
+    _check((got[0], np.array([w[1] for w in ic.want(c, 0, "batch")]), got[2]), ic.want(c, 0, "batch"))
+    assert (got[1] == 777).all()
+
+
+def test_caller_made_table(gpu):
+    ic.step_regime()
+    c = ic.step_case()
+    for flag in (0, 1):
+        _check(_run(gpu, c, flag), ic.want(c, flag, "step"))
+
+
+def test_chain_behind_e11_and_into_the_message(gpu, oracle):
+    """1024 x 1024, the defaults: E11's grid of occ_cases.full_case on the device, inflated on the device,
+    serialised on the device; every stage against its oracle."""
+    import torch
+
+    from tests import occ_cases as oc
+    from tests import occ_oracle as oo
+    from tests.test_gpu_occ import _run as occ_run, _struct
+    dev = torch.device("cuda:0")
+    case = oc.full_case(0, B=8)
+    occ_want = oc.case_want(oracle, oc.full_case(0), "full0")[0]
+    occ = occ_run(gpu, case)[0][0]
+    assert occ.tobytes() == occ_want[0].tobytes()
+    c = ic.chain_case(occ)
+    ic.chain_regime(c)
+    f = abi.Inflation.defaults()
+    table, rc = abi.inflation_table(f, case["spec"]["resolution"])
+    assert rc == 12 and table.tobytes() == c["table"].tobytes()
+    s = case["spec"]
+    W, H = s["width"], s["height"]
+    d_occ = torch.from_numpy(occ.reshape(-1).copy()).to(dev)
+    d_cost = torch.full((W * H,), GUARD, dtype=torch.int8, device=dev)
+    d_table = torch.from_numpy(table).to(dev)
+    d_cells = torch.zeros(4, dtype=torch.int32, device=dev)
+    lay = abi.msg_occupancy_layout(3, W, H)
+    d_stamp = torch.from_numpy(np.array([(7, 9)], dtype=[("sec", "<i4"), ("nanosec", "<u4")]).view(np.uint8)).to(dev)
+    d_msg = torch.zeros((lay.total_len + 3) & ~3, dtype=torch.uint8, device=dev)
+    d_len = torch.zeros(1, dtype=torch.int32, device=dev)
+    gpu.inflate_grids_dev(d_occ.data_ptr(), W * H, d_cost.data_ptr(), W * H, 1, W, H, d_table.data_ptr(), rc,
+                          f.inflate_unknown, d_cells.data_ptr())
+    gpu.occupancy_grid_msgs_dev(d_cost.data_ptr(), W * H, 1, _struct(s), "map", d_stamp.data_ptr(),
+                                d_msg.data_ptr(), d_msg.numel(), d_len.data_ptr(), 0)
+    gpu.synchronize()
+    want, cells = ic.want(c, 0, "chain")[0]
+    cost = d_cost.cpu().numpy().reshape(H, W)
+    diff = np.argwhere(cost != want)
+    print(f"cells {d_cells.cpu().numpy().tolist()} want {cells}, {len(diff)} cells differ")
+    assert len(diff) == 0, (diff[:8], cost[tuple(diff[:8].T)], want[tuple(diff[:8].T)])
+    assert tuple(d_cells.cpu().numpy().tolist()) == cells
+    msg = d_msg.cpu().numpy()
+    assert int(d_len[0]) == lay.total_len
+    assert msg[lay.data_off:lay.total_len].tobytes() == want.tobytes()
+    assert msg[:lay.total_len].tobytes() == oo.occupancy_msg("map", 7, 9, s["resolution"], W, H, s["origin_x"],
+                                                            s["origin_y"], want)
+
+
+def test_host_buffers(gpu):
+    g = ic.edges_grid()
+    for rc, flag, key in ((5, 1, "edges5"), (64, 0, "edges64")):
+        res = ic.SPECS[rc][0]
+        out, cells = gpu.inflate_grid(g, res, ic.inflation(rc, flag))
+        want, wc = ic.want(ic.edges_case(rc), flag, key)[0]
+        assert out.tobytes() == want.tobytes() and cells == wc
+    c = ic.uniform_cases()["cut_disc"]
+    out, cells = gpu.inflate_grid(c["grids"][0], 0.05, ic.inflation(5))
+    want, wc = ic.want(c, 0)[0]
+    assert out.tobytes() == want.tobytes() and cells == wc
+    with pytest.raises(abi.RplGpuError) as e:
+        gpu.inflate_grid(g, 0.05, abi.Inflation.defaults(inflation_radius=3.25))
+    assert e.value.code == abi.ERR_INVALID_ARG
+
+
+def test_refusals_leave_the_output_and_the_handle(gpu):
+    import torch
+    dev = torch.device("cuda:0")
+    c = ic.edges_case(5)
+    g = c["grids"][0]
+    H, W = g.shape
+    n = W * H
+    stride = (n + 3) & ~3
+    d_in = torch.from_numpy(np.resize(g.reshape(-1), stride + 8)).to(dev)
+    d_out = torch.full((stride + 8,), GUARD, dtype=torch.uint8, device=dev)
+    d_table = torch.from_numpy(np.resize(c["table"], 32)).to(dev)
+    d_cells = torch.full((4,), 777, dtype=torch.int32, device=dev)
+    host = np.zeros(stride, np.int8)
+
+    def call(**kw):
+        a = dict(inp=d_in.data_ptr(), s_in=stride, out=d_out.data_ptr(), s_out=stride, G=1, W=W, H=H,
+                 table=d_table.data_ptr(), rc=5, flag=0, cells=d_cells.data_ptr())
+        a.update(kw)
+        with pytest.raises(abi.RplGpuError) as e:
+            gpu.inflate_grids_dev(a["inp"], a["s_in"], a["out"], a["s_out"], a["G"], a["W"], a["H"], a["table"],
+                                  a["rc"], a["flag"], a["cells"])
+        return e.value.code
+
+    bad = [dict(out=d_in.data_ptr()), dict(rc=65), dict(flag=2), dict(W=0), dict(H=0), dict(W=abi.MAX_OCC_DIM + 1),
+           dict(H=abi.MAX_OCC_DIM + 1), dict(s_in=stride - 4), dict(s_out=stride - 4), dict(s_in=stride + 2),
+           dict(s_out=stride + 2), dict(inp=d_in.data_ptr() + 1), dict(out=d_out.data_ptr() + 2),
+           dict(table=d_table.data_ptr() + 1), dict(cells=d_cells.data_ptr() + 2), dict(G=0), dict(inp=0),
+           dict(out=0), dict(table=0), dict(out=host.ctypes.data)]
+    for kw in bad:
+        assert call(**kw) == abi.ERR_INVALID_ARG, kw
+    gpu.synchronize()
+    assert (d_out.cpu().numpy() == GUARD).all() and (d_cells.cpu().numpy() == 777).all()
+    _check(_run(gpu, c, 0), ic.want(c, 0, "edges5"))
