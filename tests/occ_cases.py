@@ -314,3 +314,305 @@ def cell_range_regime(oracle, case):
     bad = r1["slot"] == 1
     assert bad.sum() > 100 and np.isnan(r1["x"][bad]).all() and not r1["ray"][bad].any()
     assert r1["ray"][~bad].sum() > 1000
+
+
+# ---- beyond the LDS window ---------------------------------------------------------------------------------------
+WIN = 640  # k_occ_walk keeps a scan's clears in a WIN x WIN bit window in LDS, its corner WIN / 2 below the sensor cell
+SLOT_KEYS = ("ray", "dropped", "x0", "y0", "x1", "y1", "cut", "mark")
+
+
+def slot_rays(r, slot):
+    """The rays of one scan of a group."""
+    m = r["slot"] == slot
+    return {k: r[k][m] for k in SLOT_KEYS}
+
+
+def slot_bits(r, slot, W, H):
+    """(cleared, marked) (H, W) bool by the rays of ONE scan of a group."""
+    return oo.bits_vector(*oo.live_rays(slot_rays(r, slot)), W, H)
+
+
+def sensor_cell(r, slot):
+    i = int(np.flatnonzero(r["slot"] == slot)[0])
+    return int(r["x0"][i]), int(r["y0"][i])
+
+
+def in_window(x0, y0, W, H):
+    """(H, W) bool: the grid cells inside the window of a scan whose sensor cell is (x0, y0)."""
+    cx, cy = np.arange(W)[None, :], np.arange(H)[:, None]
+    return (cx >= x0 - WIN // 2) & (cx < x0 + WIN // 2) & (cy >= y0 - WIN // 2) & (cy < y0 + WIN // 2)
+
+
+FAR_SPEC = oo.spec(origin_x=-11.0, origin_y=-9.0, resolution=0.02, width=1101, height=899, range_min=0.0,
+                   obstacle_max=9.0, raytrace_max=10.0)
+FAR_SENSORS = ((550, 450), (1075, 875), (-450, 450))
+
+
+def far_case():
+    """One group of three sensors over 1101 x 899 cells of 2 cm, returns of 5 .. 14 m at random angles (whole and
+    marking up to 9 m, whole and unmarked up to 10 m, cut at 500 cells beyond): a in the middle, its window
+    inside the grid on all four sides; b 25 cells inside the top-right corner, its window over two grid edges;
+    c 450 cells left of the grid, its window wholly off it."""
+    rng = np.random.default_rng(1160)
+    n = 1501
+    scans = [polar_nodes(rng.uniform(0, 2 * math.pi, n), rng.uniform(5.0, 14.0, n)) for _ in range(3)]
+    batch, lens = pad(scans, n)
+    s = FAR_SPEC
+    tx = [s["origin_x"] + (cx + 0.5) * s["resolution"] for cx, _ in FAR_SENSORS]
+    ty = [s["origin_y"] + (cy + 0.5) * s["resolution"] for _, cy in FAR_SENSORS]
+    return dict(batch=batch, lens=lens, group=3, p=Params.defaults(clip_enable=0), spec=s,
+                pose2d=rot_poses([0.4, -1.1, 2.0], tx, ty))
+
+
+def far_prev(case):
+    s = case["spec"]
+    rng = np.random.default_rng(1161)
+    return rng.choice(np.array([-1, 0, 100, 37], np.int8), size=(1, s["height"], s["width"]))
+
+
+def far_regime(oracle, case):
+    s = case["spec"]
+    W, H = s["width"], s["height"]
+    r = case_rays(oracle, case, 0)
+    assert not r["dropped"].any()
+    assert r["cut"].sum() >= 100 and r["mark"].sum() >= 100 and (r["ray"] & ~r["cut"] & ~r["mark"]).sum() >= 100
+    clear, win = [], []
+    for slot, cell in enumerate(FAR_SENSORS):
+        assert sensor_cell(r, slot) == cell
+        clear.append(slot_bits(r, slot, W, H)[0])
+        win.append(in_window(*cell, W, H))
+    # a: at least 1000 clears beyond each side of its window, and cleared cells in the two columns and the two
+    # rows on either side of every window border
+    (x0, y0), ys, xs = FAR_SENSORS[0], *np.nonzero(clear[0])
+    sides = dict(left=(xs < x0 - WIN // 2).sum(), right=(xs >= x0 + WIN // 2).sum(),
+                 below=(ys < y0 - WIN // 2).sum(), above=(ys >= y0 + WIN // 2).sum())
+    assert min(sides.values()) >= 1000 and (clear[0] & win[0]).sum() >= 1000, sides
+    for d in (-WIN // 2 - 1, -WIN // 2, WIN // 2 - 1, WIN // 2):
+        assert clear[0][:, x0 + d].any() and clear[0][y0 + d, :].any(), d
+    # b: its window hangs over the right and the top edge; clears beyond it on the two other sides
+    (x0, y0), ys, xs = FAR_SENSORS[1], *np.nonzero(clear[1])
+    assert x0 + WIN // 2 > W and y0 + WIN // 2 > H
+    assert (xs < x0 - WIN // 2).sum() >= 1000 and (ys < y0 - WIN // 2).sum() >= 1000
+    # c: every in-grid clear is beyond its window
+    assert clear[2].sum() >= 1000 and not (clear[2] & win[2]).any() and not win[2].any()
+    assert (clear[2] & ~clear[0] & ~clear[1]).any()
+    assert (clear[0] & win[0] & clear[1] & ~win[1]).any()
+    return sides
+
+
+# ---- the window flush: every byte alignment, tiny grids --------------------------------------------------------------
+FLUSH_WIDTHS = (64, 61, 62, 63)
+FLUSH_H = 40
+FLUSH_SENSORS = ((8, 20), (21, 9), (34, 30), (47, 15))  # x0 mod 4 = 0, 1, 2, 3: so is the window corner x0 - 320
+
+
+def flush_case(W):
+    """Four sensors inside a W x 40 grid of 5 cm cells, their window corners at the four residues mod 4, returns
+    of 0.3 .. 6 m (up to 120 cells) at random angles: rays clear columns 0 and W - 1 and leave on both sides.
+    Run as one group of four and as four groups of one."""
+    rng = np.random.default_rng(1170 + W)
+    n = 600
+    scans = [polar_nodes(rng.uniform(0, 2 * math.pi, n), rng.uniform(0.3, 6.0, n)) for _ in FLUSH_SENSORS]
+    batch, lens = pad(scans, n)
+    s = oo.spec(origin_x=0.0, origin_y=0.0, resolution=0.05, width=W, height=FLUSH_H)
+    pose2d = rot_poses([0.0, 0.9, -0.5, 2.2], [(cx + 0.5) * 0.05 for cx, _ in FLUSH_SENSORS],
+                       [(cy + 0.5) * 0.05 for _, cy in FLUSH_SENSORS])
+    return dict(batch=batch, lens=lens, group=len(FLUSH_SENSORS), p=Params.defaults(clip_enable=0), spec=s,
+                pose2d=pose2d)
+
+
+def flush_regime(oracle, cases):
+    """cases: {W: flush_case(W)}.  -> the set of (W mod 4, corner mod 4) pairs seen."""
+    pairs, starts = set(), set()
+    below, beyond = False, False
+    for W, case in cases.items():
+        r = case_rays(oracle, case, 0)
+        assert not r["dropped"].any()
+        for slot, cell in enumerate(FLUSH_SENSORS):
+            assert sensor_cell(r, slot) == cell
+            sr = slot_rays(r, slot)
+            live = sr["ray"] & ~sr["dropped"]
+            assert (live & (sr["x1"] < 0)).any() and (live & (sr["x1"] >= W)).any()  # leave on both sides
+            grid = oo.compose(*slot_bits(r, slot, W, FLUSH_H))
+            for col in (0, W - 1):  # cleared (and not marked over) in two consecutive rows
+                z = grid[:, col] == 0
+                assert (z[:-1] & z[1:]).any(), (W, slot, col)
+            corner = cell[0] - WIN // 2
+            pairs.add((W % 4, corner % 4))
+            ys, xs = np.nonzero(grid == 0)
+            nib = corner + 4 * ((xs - corner) // 4)  # first cell of the window nibble that holds the cell
+            starts |= set(((ys * W + nib) & 3).tolist())
+            below |= bool((nib < 0).any())
+            beyond |= bool((nib + 3 >= W).any())
+    assert pairs == {(a, b) for a in range(4) for b in range(4)} and starts == {0, 1, 2, 3}, (pairs, starts)
+    assert below and beyond  # nibbles that begin left of column 0 and that end right of column W - 1
+    return pairs
+
+
+TINY_GRIDS = ((1, 1), (1, 3), (3, 1), (2, 2), (5, 3))
+
+
+def tiny_case(W, H, outside):
+    """One scan of returns at random angles over W x H cells of 25 cm: from a sensor in the middle cell of the
+    grid 2 of 0.05 m (they end in the sensor cell), 6 of 0.2 .. 0.6 m and 16 of 0.5 .. 3 m (rays end inside and
+    leave; few enough to leave cleared cells unmarked), or, 512 `outside`, of 2.5 .. 4 m from a sensor three cells
+    left of and two below the grid's corner (at least 10 cells: every ray that meets the grid crosses it)."""
+    rng = np.random.default_rng(1180 + 16 * W + 2 * H + int(outside))
+    n = 512 if outside else 24
+    rr = rng.uniform(2.5, 4.0, n) if outside else np.concatenate([np.full(2, 0.05), rng.uniform(0.2, 0.6, 6),
+                                                                  rng.uniform(0.5, 3.0, 16)])
+    scan = polar_nodes(rng.uniform(0, 2 * math.pi, n), rr)
+    batch, lens = pad([scan], n)
+    s = oo.spec(origin_x=0.0, origin_y=0.0, resolution=0.25, width=W, height=H)
+    cx, cy = (-3, -2) if outside else (W // 2, H // 2)
+    pose2d = rot_poses([0.3], [(cx + 0.5) * 0.25], [(cy + 0.5) * 0.25])
+    return dict(batch=batch, lens=lens, group=1, p=Params.defaults(clip_enable=0), spec=s, pose2d=pose2d,
+                sensor=(cx, cy))
+
+
+def tiny_regime(oracle, case):
+    s = case["spec"]
+    W, H = s["width"], s["height"]
+    r = case_rays(oracle, case, 0)
+    assert sensor_cell(r, 0) == case["sensor"] and not r["dropped"].any()
+    live = r["ray"] & ~r["dropped"]
+    inside = (0 <= case["sensor"][0] < W) and (0 <= case["sensor"][1] < H)
+    clear, marked = oo.bits_vector(*oo.live_rays(r), W, H)
+    assert clear.any() and marked.any() == inside
+    in1 = (r["x1"] >= 0) & (r["x1"] < W) & (r["y1"] >= 0) & (r["y1"] < H)
+    assert (live & ~in1).sum() >= 10  # rays that leave (or cross and leave) the grid
+    return inside
+
+
+# ---- rays near the step cap -----------------------------------------------------------------------------------------
+LONG_RES = 0.005
+LONG_FAR = 3950  # cells between a sensor and the near edge of its grid
+
+
+def _long_scan(offsets, whole, marked_in, cut):
+    """A fan of beams `offsets` angle units (2 pi / 65536) around angle 0, each at every range of the lists."""
+    rr = list(whole) + list(marked_in) + list(cut)
+    q = np.repeat(np.asarray(offsets, np.int64) % 65536, len(rr))
+    return nodes(q, np.round(np.tile(np.asarray(rr, float), len(offsets)) * 4000.0).astype(np.int64))
+
+
+def long_cases():
+    """Three inputs at 5 mm cells with raytrace_max = obstacle_max = 40 m (8000 steps), at most 64 rays each:
+    4096 x 8 cells with a sensor 3950 cells left and one 3950 cells right of the grid, beams along +x / -x;
+    the same turned by 90 degrees (8 x 4096, +y / -y); 96 x 96 cells with a pair of diagonal beams through it.
+    Ranges: 39.6 and 39.9 m (whole, marking, some end cells in the grid), 45 and 60 m (cut at 8000 steps)."""
+    fan = (-4, -2, -1, 0, 1, 3)
+    scan = _long_scan(fan, [39.9], [39.6, 39.7], [45.0, 60.0])  # 30 samples
+    p = Params.defaults(clip_enable=0)
+    kw = dict(resolution=LONG_RES, origin_x=0.0, origin_y=0.0, range_min=0.0, obstacle_max=40.0, raytrace_max=40.0)
+    at = lambda c: (c + 0.5) * LONG_RES  # noqa: E731
+    batch, lens = pad([scan, scan], 32)
+    out = []
+    lo, hi = -LONG_FAR, 4095 + LONG_FAR
+    out.append(dict(batch=batch, lens=lens, group=2, p=p, spec=oo.spec(width=4096, height=8, **kw),
+                    pose2d=np.array([[1, 0, at(lo), 0, 1, at(4)], [-1, 0, at(hi), 0, -1, at(3)]], F32)))
+    out.append(dict(batch=batch, lens=lens, group=2, p=p, spec=oo.spec(width=8, height=4096, **kw),
+                    pose2d=np.array([[0, -1, at(4), 1, 0, at(lo)], [0, 1, at(3), -1, 0, at(hi)]], F32)))
+    diag = _long_scan((-40, -8, 0, 8, 40), [39.9], [20.0, 20.2], [45.0])  # the grid's middle is 20.1 m away
+    batch, lens = pad([diag, diag], 32)
+    out.append(dict(batch=batch, lens=lens, group=2, p=p, spec=oo.spec(width=96, height=96, **kw),
+                    pose2d=rot_poses([math.pi / 4, -3 * math.pi / 4], [at(-2800), at(2895)], [at(-2800), at(2895)])))
+    return out
+
+
+def long_regime(oracle, cases):
+    seen = dict(px=False, nx=False, py=False, ny=False, diag=False, marked_in=False, cut_in=False)
+    for case in cases:
+        s = case["spec"]
+        W, H = s["width"], s["height"]
+        assert oo.spec_valid(s) and case["lens"].max() <= 64
+        r = case_rays(oracle, case, 0)
+        assert not r["dropped"].any()  # no CELL_RANGE
+        live = r["ray"] & ~r["dropped"]
+        ddx, ddy = (r["x1"] - r["x0"])[live], (r["y1"] - r["y0"])[live]
+        assert max(np.abs(ddx).max(), np.abs(ddy).max()) <= oo.MAX_STEPS
+        seen["px"] |= bool((ddx >= 7900).any())
+        seen["nx"] |= bool((ddx <= -7900).any())
+        seen["py"] |= bool((ddy >= 7900).any())
+        seen["ny"] |= bool((ddy <= -7900).any())
+        seen["diag"] |= bool(((np.abs(ddx) >= 5000) & (np.abs(ddy) >= 5000)).any())
+        in1 = (r["x1"] >= 0) & (r["x1"] < W) & (r["y1"] >= 0) & (r["y1"] < H)
+        seen["marked_in"] |= bool((live & in1 & r["mark"] & ~r["cut"]).any())
+        seen["cut_in"] |= bool((live & in1 & r["cut"]).any())
+    assert all(seen.values()), seen
+
+
+# ---- lengths ------------------------------------------------------------------------------------------------------
+RAGGED_N = 4096
+RAGGED_LENS = (0, 1, 129, 1501, 2047, 2048, 2049, 4096, 0, 700, 131)  # a group of 8, then one of 3
+RAGGED_X = (-3.5, -2.5, -1.5, -0.5, 0.5, 1.5, 2.5, 3.5, -2.0, 0.25, 2.75)
+
+
+def ragged_case():
+    """wall_case's geometry (sensors on the x axis facing the wall y = 5, so runs of consecutive samples end in
+    one cell) at every length that matters to the 2048-sample passes of k_occ_walk: empty, one sample, odd
+    above one wave, one below / at / one above a pass, two passes; a second, short group that begins with an
+    empty scan.  5 % of the samples have no return (E1 removes them); the LAST sample of every scan is a return
+    1 m + 0.3 m * scan in front of its sensor, which no other ray ends in."""
+    rng = np.random.default_rng(1190)
+    scans = []
+    for b, L in enumerate(RAGGED_LENS):
+        th = np.linspace(math.radians(25), math.radians(155), L) if L > 1 else np.full(L, math.pi / 2)
+        s = polar_nodes(th, 5.0 / np.sin(th))
+        s["dist_mm_q2"][rng.random(L) < 0.05] = 0
+        if L:
+            s[-1] = polar_nodes([math.pi / 2], [1.0 + 0.3 * (b % 8)])[0]
+        scans.append(s)
+    batch, lens = pad(scans, RAGGED_N)
+    pose2d = rot_poses(np.zeros(len(scans)), RAGGED_X, np.zeros(len(scans)))
+    return dict(batch=batch, lens=lens, group=8, p=Params.defaults(clip_enable=0), spec=WALL_SPEC, pose2d=pose2d)
+
+
+def ragged_regime(oracle, case):
+    s = case["spec"]
+    W, H = s["width"], s["height"]
+    at128, at_odd, removed = 0, 0, 0
+    for g, sl in enumerate(case_groups(case)):
+        r = case_rays(oracle, case, g)
+        assert not r["dropped"].any()
+        live = r["ray"] & ~r["dropped"]
+        word = np.stack([r["x1"], r["y1"], r["cut"], r["mark"]], 1)
+        marks = live & r["mark"] & ~r["cut"]
+        for slot, b in enumerate(range(sl.start, sl.stop)):
+            L = int(case["lens"][b])
+            m = np.flatnonzero(r["slot"] == slot)
+            removed += L - len(m)
+            if L == 0:
+                assert len(m) == 0  # the empty scan contributes nothing
+                continue
+            idx = r["idx"][m]
+            assert (np.diff(idx) > 0).all()
+            # the ray of a sample equals the ray of the sample before it
+            dup = (np.diff(idx) == 1) & live[m][1:] & live[m][:-1] & (word[m][1:] == word[m][:-1]).all(1)
+            at = idx[1:][dup]
+            at128 += int((at % 128 == 0).sum())
+            at_odd += int((at % 2 == 1).sum())
+            # the last sample: a live, marking ray into a cell of the grid that no other ray of the group marks
+            last = m[-1]
+            assert idx[-1] == L - 1 and marks[last]
+            x1, y1 = int(r["x1"][last]), int(r["y1"][last])
+            assert 0 <= x1 < W and 0 <= y1 < H
+            assert (marks & (r["x1"] == x1) & (r["y1"] == y1)).sum() == 1, b
+    assert at128 >= 1 and at_odd >= 1 and removed >= 100, (at128, at_odd, removed)
+    return at128, at_odd
+
+
+# ---- messages from more than one workgroup ----------------------------------------------------------------------------
+MSG_GRIDS = ((300, 300), (2051, 2049))
+
+
+def msg_kernel_constants():
+    """(kChunk, the most workgroups per message) as csrc/rpl_occ.hip has them."""
+    import re
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    src = (root / "rplidar_ros2_driver_amd" / "csrc" / "rpl_occ.hip").read_text()
+    chunk = re.search(r"constexpr uint32_t kChunk = (\d+);", src)
+    most = re.search(r"const uint32_t gx = min\(\(n_cells / 4u \+ kChunk - 1\) / kChunk, (\d+)u\);", src)
+    assert chunk and most, "k_msg_occupancy's launch geometry moved: look at MSG_GRIDS again"
+    return int(chunk.group(1)), int(most.group(1))

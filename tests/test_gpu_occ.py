@@ -20,8 +20,9 @@ def _struct(s):
                        s["obstacle_max"], s["raytrace_max"])
 
 
-def _run(gpu, case, prev=None, p=None, same_prev=False):
-    """-> (grids (G, H, W) int8, cells (G, 3), status (G,), guard bytes (G, 4))."""
+def _run(gpu, case, prev=None, p=None, same_prev=False, cells=True, status=True):
+    """-> (grids (G, H, W) int8, cells (G, 3), status (G,), guard bytes (G, 4)).  cells / status False: NULL
+    goes in for d_cells / d_status, and the buffer comes back as it was filled (777 / 99)."""
     import torch
     dev = torch.device("cuda:0")
     batch, s = case["batch"], case["spec"]
@@ -46,7 +47,8 @@ def _run(gpu, case, prev=None, p=None, same_prev=False):
     try:
         gpu.occupancy_grid_dev(d_nodes.data_ptr(), n, d_len.data_ptr(), B, case["group"], p or case["p"], ptr(d_mo),
                                ptr(d_po), _struct(s), d_grid.data_ptr() if same_prev else ptr(d_prev),
-                               d_grid.data_ptr(), stride, d_cells.data_ptr(), d_st.data_ptr())
+                               d_grid.data_ptr(), stride, d_cells.data_ptr() if cells else 0,
+                               d_st.data_ptr() if status else 0)
         gpu.synchronize()
     finally:
         gpu.set_scan_time_offsets_dev(0)
@@ -55,8 +57,15 @@ def _run(gpu, case, prev=None, p=None, same_prev=False):
             d_st.cpu().numpy().astype(np.int64), raw[:, W * H:])
 
 
-def _check(got, want):
+def _check(got, want, has_cells=True, has_status=True):
+    """has_cells / has_status False: the call was made without d_cells / d_status, and nothing wrote there."""
     grids, cells, status, guard = got
+    if not has_cells:
+        assert (cells == 777).all()
+        cells = np.array([wc for _, wc, _ in want])
+    if not has_status:
+        assert (status == 99).all()
+        status = np.array([ws for _, _, ws in want])
     assert len(grids) == len(want)
     for g, (wg, wc, ws) in enumerate(want):
         diff = np.argwhere(grids[g] != wg)
@@ -98,6 +107,67 @@ def test_marks_beat_clears_and_history_is_kept(gpu, oracle):
     with pytest.raises(abi.RplGpuError) as e:
         _run(gpu, case, same_prev=True)
     assert e.value.code == abi.ERR_INVALID_ARG
+
+
+def test_clears_beyond_the_window(gpu, oracle):
+    """Rays of 500 cells from three sensors: clears on all four sides of a window inside the grid, from a window
+    over two grid edges, and from a sensor whose window is wholly off the grid; then over a previous grid."""
+    case = oc.far_case()
+    oc.far_regime(oracle, case)
+    _check(_run(gpu, case), oc.case_want(oracle, case, "far"))
+    prev = oc.far_prev(case)
+    _check(_run(gpu, case, prev=prev), oc.case_want(oracle, case, "far_prev", prev=prev))
+
+
+def test_window_flush_alignments(gpu, oracle):
+    """Every (width mod 4, window corner mod 4): the four sensors in one grid, then each in a grid of its own."""
+    cases = {W: oc.flush_case(W) for W in oc.FLUSH_WIDTHS}
+    oc.flush_regime(oracle, cases)
+    for W, case in cases.items():
+        _check(_run(gpu, case), oc.case_want(oracle, case, f"flush{W}"))
+        alone = dict(case, group=1)
+        _check(_run(gpu, alone), oc.case_want(oracle, alone, f"flush{W}_alone"))
+
+
+@pytest.mark.parametrize("outside", [False, True], ids=["inside", "outside"])
+@pytest.mark.parametrize("wh", oc.TINY_GRIDS, ids=[f"{w}x{h}" for w, h in oc.TINY_GRIDS])
+def test_tiny_grids(gpu, oracle, wh, outside):
+    """Grids narrower than a word or a nibble: the tail of the last word and the guard behind it stay."""
+    case = oc.tiny_case(*wh, outside)
+    oc.tiny_regime(oracle, case)
+    want = oc.case_want(oracle, case, f"tiny{wh}{outside}")
+    _check(_run(gpu, case), want)
+    prev = np.full((1, wh[1], wh[0]), 37, np.int8)
+    _check(_run(gpu, case, prev=prev), oc.case_want(oracle, case, f"tiny{wh}{outside}_prev", prev=prev))
+
+
+def test_rays_near_the_step_cap(gpu, oracle):
+    cases = oc.long_cases()
+    oc.long_regime(oracle, cases)
+    for i, case in enumerate(cases):
+        want = oc.case_want(oracle, case, f"long{i}")
+        assert want[0][2] == 0
+        _check(_run(gpu, case), want)
+
+
+def test_ragged_lengths(gpu, oracle):
+    case = oc.ragged_case()
+    oc.ragged_regime(oracle, case)
+    _check(_run(gpu, case), oc.case_want(oracle, case, "ragged"))
+
+
+def test_optional_outputs(gpu, oracle):
+    """d_cells and d_status are optional: without either, or both, the same grids."""
+    case = oc.far_case()
+    want = oc.case_want(oracle, case, "far")
+    for cells, status in ((False, True), (True, False), (False, False)):
+        _check(_run(gpu, case, cells=cells, status=status), want, cells, status)
+    cut = dict(case, lens=case["lens"].copy())
+    cut["lens"][1] = case["batch"].shape[1] + 7  # more than the stride holds: the truncated bit, were it asked for
+    wcut = oc.case_want(oracle, cut)
+    assert wcut[0][2] == abi.SCAN_OUT_TRUNCATED and np.array_equal(wcut[0][0], want[0][0])
+    _check(_run(gpu, cut, status=False), wcut, True, False)
+    _check(_run(gpu, cut), wcut)
 
 
 @pytest.mark.parametrize("ror_mode", [0, 1], ids=["ror_inside", "ror_two_kernels"])  # RPLGPU_ROR_INSIDE / _TWO_KERNELS
@@ -184,6 +254,41 @@ def test_messages_match_restatement(gpu, oracle, frame):
                                     grids[g])
             assert lens[g] == len(want) == lay.total_len and st[g] == 0
             assert msgs[g * slot: g * slot + lens[g]].tobytes() == want
+
+
+@pytest.mark.parametrize("wh", oc.MSG_GRIDS, ids=[f"{w}x{h}" for w, h in oc.MSG_GRIDS])
+def test_messages_from_several_workgroups(gpu, wh):
+    """Two workgroups per message, and the second trip of the grid-stride loop (tests/test_occ_cpu.py holds the
+    two sizes against the kernel's constants).  The call takes any grid: random bytes."""
+    import torch
+    dev = torch.device("cuda:0")
+    W, H = wh
+    G, frame = 2, "map"
+    s = oo.spec(width=W, height=H)
+    stride = (W * H + 3) & ~3
+    host = np.random.default_rng(1195).integers(-128, 128, (G, stride), dtype=np.int8)
+    d_grid = torch.from_numpy(host.reshape(-1)).to(dev)
+    lay = abi.msg_occupancy_layout(len(frame), W, H)
+    stamps = np.array([(100 + g, 1000 * g) for g in range(G)], dtype=[("sec", "<i4"), ("nanosec", "<u4")])
+    d_stamps = torch.from_numpy(stamps.view(np.uint8)).to(dev)
+    full = (lay.total_len + 3) & ~3
+    for slot in (full + 4, (lay.total_len - 1) & ~3):
+        d_msgs = torch.full((G * slot,), GUARD, dtype=torch.uint8, device=dev)
+        d_len = torch.full((G,), 77, dtype=torch.int32, device=dev)
+        d_st = torch.zeros(G, dtype=torch.int32, device=dev)
+        gpu.occupancy_grid_msgs_dev(d_grid.data_ptr(), stride, G, _struct(s), frame, d_stamps.data_ptr(),
+                                    d_msgs.data_ptr(), slot, d_len.data_ptr(), d_st.data_ptr())
+        gpu.synchronize()
+        msgs, lens, st = d_msgs.cpu().numpy().reshape(G, slot), d_len.cpu().numpy(), d_st.cpu().numpy()
+        for g in range(G):
+            if slot < lay.total_len:
+                assert lens[g] == 0 and st[g] == abi.SCAN_OUT_TRUNCATED and (msgs[g] == GUARD).all()
+                continue
+            want = oo.occupancy_msg(frame, 100 + g, 1000 * g, s["resolution"], W, H, s["origin_x"], s["origin_y"],
+                                    host[g, :W * H])
+            assert lens[g] == len(want) == lay.total_len and st[g] == 0
+            assert msgs[g, :lens[g]].tobytes() == want
+            assert (msgs[g, lens[g]:] == GUARD).all()  # nothing behind the message
 
 
 def test_marked_cells_hold_e9_points(gpu, oracle):

@@ -175,6 +175,50 @@ def test_regime_full(oracle):
     oc.full_regime(oracle, case, oc.case_want(oracle, case, "full0"))
 
 
+def test_regime_far(oracle):
+    sides = oc.far_regime(oracle, oc.far_case())
+    print(sides)
+
+
+def test_regime_flush(oracle):
+    pairs = oc.flush_regime(oracle, {W: oc.flush_case(W) for W in oc.FLUSH_WIDTHS})
+    assert len(pairs) == 16
+
+
+@pytest.mark.parametrize("outside", [False, True], ids=["inside", "outside"])
+@pytest.mark.parametrize("wh", oc.TINY_GRIDS, ids=[f"{w}x{h}" for w, h in oc.TINY_GRIDS])
+def test_regime_tiny(oracle, wh, outside):
+    assert oc.tiny_regime(oracle, oc.tiny_case(*wh, outside)) == (not outside)
+
+
+def test_regime_long(oracle):
+    cases = oc.long_cases()
+    oc.long_regime(oracle, cases)
+    for case in cases:  # what the library's own check says of these specs
+        s = case["spec"]
+        abi.occ_grid_check(abi.OccGrid(s["origin_x"], s["origin_y"], s["resolution"], s["width"], s["height"],
+                                       s["range_min"], s["obstacle_max"], s["raytrace_max"]))
+
+
+def test_regime_ragged(oracle):
+    case = oc.ragged_case()
+    assert list(case["lens"][:8]) == [0, 1, 129, 1501, 2047, 2048, 2049, 4096] and case["lens"][8] == 0
+    assert case["batch"].shape == (11, 4096) and case["group"] == 8
+    oc.ragged_regime(oracle, case)
+
+
+def test_message_grids_sit_on_the_intended_sides_of_the_launch_geometry():
+    """tests/test_gpu_occ.py's message grids against k_msg_occupancy's kChunk words per workgroup and step and
+    its cap of workgroups per message, both read from the source: one grid needs two workgroups and one trip,
+    the other a second trip of the grid-stride loop and has three tail bytes."""
+    chunk, most = oc.msg_kernel_constants()
+    (w0, h0), (w1, h1) = oc.MSG_GRIDS
+    assert chunk < (w0 * h0) // 4 <= 2 * chunk and 2 <= most
+    assert most * chunk < (w1 * h1) // 4 <= 2 * most * chunk and (w1 * h1) % 4 == 3
+    assert (257 * 203) // 4 <= chunk  # the grid of test_messages_match_restatement: one workgroup
+    assert max(w0, h0, w1, h1) <= abi.MAX_OCC_DIM
+
+
 def test_host_mirror_compiles_against_a_ros_shaped_occupancy_grid(tmp_path):
     import subprocess
     from pathlib import Path
