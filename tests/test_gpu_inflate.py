@@ -187,3 +187,58 @@ def test_refusals_leave_the_output_and_the_handle(gpu):
     gpu.synchronize()
     assert (d_out.cpu().numpy() == GUARD).all() and (d_cells.cpu().numpy() == 777).all()
     _check(_run(gpu, c, 0), ic.want(c, 0, "edges5"))
+
+
+# ---- tests across the window: single cells where one code path of k_inflate alone decides a byte ---------------------
+@pytest.mark.parametrize("W", ic.LONE_WIDTHS)
+def test_lone_cell_sweep(gpu, W):
+    """One lethal cell per grid, rc 64: every byte within 64 cells is table[D2] of that cell, through all six
+    words of a mask row and both clz / ffs branches."""
+    ic.lone_regime()
+    c = ic.lone_case(W)
+    for flag in (0, 1):
+        _check(_run(gpu, c, flag), ic.want(c, flag, ("lone", W)))
+
+
+@pytest.mark.parametrize("name", list(ic.stage_cases()))
+def test_stage_switch_points(gpu, name):
+    """Window rows of 57 .. 63, 122 .. 127, 124 and 126 cells with a lethal cell alone in their first and last
+    column: either side of the 16 | 32 and the 32 | 64 lanes-per-row switch."""
+    ic.stage_regime()
+    c = ic.stage_cases()[name]
+    for flag in (0, 1):
+        _check(_run(gpu, c, flag), ic.want(c, flag, ("stage", name)))
+
+
+@pytest.mark.parametrize("W,H", ic.REACH_SHAPES)
+@pytest.mark.parametrize("rc", ic.REACH_RCS)
+def test_reaches_at_the_word_boundaries(gpu, rc, W, H):
+    ic.reach_regime(rc, W, H)
+    c = ic.reach_case(rc, W, H)
+    for flag in (0, 1):
+        _check(_run(gpu, c, flag), ic.want(c, flag, ("reach", rc, W)))
+
+
+@pytest.mark.parametrize("W", ic.COUNT_WIDTHS)
+@pytest.mark.parametrize("table", list(ic.COUNT_TABLES))
+def test_counters_at_full_tiles(gpu, table, W):
+    ic.count_regime()
+    c = ic.count_case(W, table)
+    for flag in (0, 1):
+        _check(_run(gpu, c, flag), ic.want(c, flag))
+
+
+@pytest.mark.parametrize("name", list(ic.SHAPES))
+def test_extreme_shapes(gpu, name):
+    ic.shape_regime()
+    c = ic.shape_case(name)
+    for flag in (0, 1):
+        _check(_run(gpu, c, flag), ic.want(c, flag, ("shape", name)))
+
+
+def test_three_hundred_grids(gpu):
+    """G = 300 in one call, every third grid empty, strides larger than the grid, the counts per grid."""
+    ic.shape_regime()
+    c = ic.many_case()
+    _check(_run(gpu, c, 0, in_pad=8, out_pad=12), ic.want(c, 0, "many"))
+    _check(_run(gpu, c, 1, in_pad=4, out_pad=20), ic.want(c, 1, "many"))

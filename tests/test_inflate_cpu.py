@@ -164,6 +164,55 @@ def test_regimes():
     ic.step_regime()
 
 
+def test_linear_table():
+    for rc in sorted({64, 3} | set(ic.REACH_RCS) | {rc for _, rc in ic.STAGE_INNER} | {s[2] for s in ic.SHAPES.values()}):
+        t = ic.linear_table(rc)
+        assert t.dtype == np.uint8 and len(t) == rc * rc + 1 and t[0] == 100
+        assert (np.diff(t.astype(int)) <= 0).all() and 1 <= t[1:].min() and t[1:].max() <= 98 and t[-1] == 1
+        for k in (1, 2, rc * rc // 2, rc * rc - 1, rc * rc):  # the formula, in integers: floor(97 sqrt(k) / rc) = n
+            n = 98 - int(t[k])
+            assert n * n * rc * rc <= 97 * 97 * k and (t[k] == 1 or (n + 1) ** 2 * rc * rc > 97 * 97 * k), (rc, k)
+    assert len(set(ic.linear_table(64).tolist())) == 98
+    assert ic.linear_table(0).tolist() == [100] and ic.linear_table(1).tolist() == [100, 1]
+
+
+def test_regimes_across_the_window():
+    ic.lone_regime()
+    ic.stage_regime()
+    ic.count_regime()
+    ic.shape_regime()
+
+
+@pytest.mark.parametrize("W,H", ic.REACH_SHAPES)
+@pytest.mark.parametrize("rc", ic.REACH_RCS)
+def test_reach_regime(rc, W, H):
+    ic.reach_regime(rc, W, H)
+
+
+def _window_cases():
+    """(name, case, grids to run the brute writer on): every grid below rc 63, at most 8 grids in all at rc 63 / 64
+    (the brute writer takes over a second per 192 x 192 grid there)."""
+    out = [(f"lone{W}", ic.lone_case(W), (7 * i,)) for i, W in enumerate(ic.LONE_WIDTHS)]
+    for name, c in ic.stage_cases().items():
+        out.append((name, c, (0,) if c["rc"] < 63 or name in ("wide124", "wide127") else ()))
+    for name, c in ic.reach_cases().items():
+        out.append((name, c, (0,) if c["rc"] < 63 or name.endswith("197x131") else ()))
+    out += [(f"count{W}_{t}", ic.count_case(W, t), (0,)) for W in ic.COUNT_WIDTHS for t in ic.COUNT_TABLES]
+    out += [(name, ic.shape_case(name), (0,)) for name in ic.SHAPES]
+    out.append(("many", ic.many_case(), range(ic.MANY_G)))
+    return out
+
+
+def test_writers_agree_across_the_window():
+    slow = 0
+    for name, c, which in _window_cases():
+        slow += len(which) if c["rc"] >= 63 else 0
+        for i in which:
+            g = c["grids"][i]
+            assert np.array_equal(io.d2_brute(g, c["rc"]), io.d2_separable(g, c["rc"])), (name, i)
+    assert 1 <= slow <= 8
+
+
 def test_chain_input_and_writers(oracle):
     from tests import occ_cases as oc
     occ = oc.case_want(oracle, oc.full_case(0), "full0")[0][0]
