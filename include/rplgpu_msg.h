@@ -512,6 +512,98 @@ int32_t rplgpu_inflate_grids_dev(rplgpu_handle_t h, const int8_t *d_in, uint64_t
 int32_t rplgpu_inflate_grid(rplgpu_handle_t h, const int8_t *in, uint32_t width, uint32_t height, float resolution,
                             const rplgpu_inflation_t *f, int8_t *out, uint32_t cells[4]);
 
+/* ---- E13: a time step's scans matched to a likelihood field (row 4; the localisation side's scan matcher) ------
+ * What AMCL and slam_toolbox, the second and third reader of everything above, do with a time step's scans and a
+ * map: correlative scan matching (Olson's real-time correlative matcher, Cartographer's
+ * RealTimeCorrelativeScanMatcher2D, Karto's CorrelateScan, the sensor half of a likelihood-field model).  The
+ * points are laid over a field at every pose of a small search window, the field values under them are added up
+ * and the best pose is kept: points x rotations x shifts look-ups per time step.  The field is any int8 grid in
+ * the E11 layout; rplgpu_inflate_grids_dev with a caller-made non-increasing table turns an E11 grid into exactly
+ * a likelihood field table[D2].  Nothing in the reference matches scans, so these rules ARE the definition (parity
+ * unpinned, as E5-E12).  After the float32 rotation everything is integers: the result depends on no order. */
+#define RPLGPU_MAX_MATCH_SHIFT 32u   /* cells, per axis */
+#define RPLGPU_MAX_MATCH_ROT   64u   /* rotation steps either side of 0 */
+typedef struct rplgpu_scan_match {
+  float    origin_x, origin_y;   /* the field's grid: as rplgpu_occ_grid_t */
+  float    resolution;
+  uint32_t width, height;        /* 1 .. RPLGPU_MAX_OCC_DIM */
+  uint32_t shift_x, shift_y;     /* Tx, Ty: candidates shift by i in [-Tx, Tx], j in [-Ty, Ty] whole cells; 0 .. RPLGPU_MAX_MATCH_SHIFT */
+  uint32_t rot_steps;            /* K: candidates rotate by k * rot_step, k in [-K, K]; 0 .. RPLGPU_MAX_MATCH_ROT */
+  float    rot_step;             /* rad, > 0 when K > 0; K * rot_step <= pi/2 (fp64) */
+} rplgpu_scan_match_t;
+/* E11's default grid (0.05 m, 1024 x 1024 cells, origin (-25.6, -25.6)), Tx = Ty = 6, K = 10,
+ * rot_step = (float)(0.25 * pi / 180) */
+void rplgpu_default_scan_match(rplgpu_scan_match_t *m);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for a value that is not finite, resolution <= 0, a
+ * dimension of 0 or above RPLGPU_MAX_OCC_DIM, a shift above RPLGPU_MAX_MATCH_SHIFT, K above RPLGPU_MAX_MATCH_ROT,
+ * or K > 0 with rot_step <= 0 or (double)K * (double)rot_step > pi/2 (M_PI / 2 as a double).  With K = 0
+ * rot_step only has to be finite.  The device path uses this function. */
+int32_t rplgpu_scan_match_check(const rplgpu_scan_match_t *m);
+/* Host only.  The ROTATION TABLE of a checked spec, 2 * (2K + 1) floats:
+ *   cs[2 (k + K)], cs[2 (k + K) + 1] = (float)cos((double)k * (double)rot_step), (float)sin(the same), k = -K .. K;
+ * entry k = 0 is exactly (1, 0).  The device path builds its table with this very function. */
+int32_t rplgpu_scan_match_rotations(const rplgpu_scan_match_t *m, float *cs);
+/* Host only.  (2K + 1) * (2Ty + 1) * (2Tx + 1), the words of one group's score volume; 0 for a spec the check
+ * refuses. */
+uint32_t rplgpu_scan_match_volume(const rplgpu_scan_match_t *m);
+/* POINTS: those of rplgpu_occupancy_grid_dev, from the same float32 operations — E1 (E5 too with p->ror_enable),
+ * E2 (p->inverted honoured), E6 de-skew from d_motion with the offsets of rplgpu_set_scan_time_offsets_dev
+ * (offsets set and d_motion NULL: refused), the planar pose d_pose2d — here the caller's PRIOR for each sensor in
+ * the field's frame.  Groups as E8 / E9 / E11 (group clamped to B).  A point whose x or y is not finite is
+ * ignored and sets no status bit.  (px, py) = (d_pivot[2g], d_pivot[2g + 1]) is the point about which group g's
+ * candidates rotate, the base's prior position; d_pivot NULL: (0, 0).
+ * CANDIDATE (k, j, i), k in [-K, K], j in [-Ty, Ty], i in [-Tx, Tx]; per point (x, y), float32, no FMA, (c, s)
+ * the rotation table's entry k:
+ *   qx = x - px;  qy = y - py;
+ *   rx = (c*qx - s*qy) + px;  ry = (s*qx + c*qy) + py      (each product rounded, then the difference, then the sum)
+ *   (cx, cy) = the E11 CELL of (rx, ry) in the spec's grid (same rule, same IEEE divides);  a rotated position
+ *   with no cell contributes nothing to rotation k and sets RPLGPU_SCAN_CELL_RANGE in d_status[g];
+ *   the candidate's cell for the point is (cx + i, cy + j): shifts are whole cells;
+ *   f = max((int8)d_field[g_f * field_stride + (cy + j) * width + (cx + i)], 0);  a cell outside
+ *   [0, width) x [0, height) gives 0, and so does an unknown (negative) byte;  g_f = g when field_per_group is
+ *   not 0, else 0 (one map serves every time step).
+ * SCORE: score[g][k][j][i] = the sum of f over the group's points, uint32, at
+ *   d_scores + g * score_stride + ((k + K) * (2Ty + 1) + (j + Ty)) * (2Tx + 1) + (i + Tx);
+ * score_stride >= the volume size, in words; words at and beyond the volume of a group are never changed.  With
+ * group * n_stride <= 2^24 (otherwise RPLGPU_ERR_INVALID_ARG) 127 * points < 2^32: no sum wraps.
+ * BEST: eight 32-bit words per group at d_best + 8 g:
+ *   0      the largest score of the group's volume
+ *   1 - 3  k, j, i (int32) of the candidate that has it;  among candidates with that score, in this order: the
+ *          smallest i*i + j*j, the smallest |k|, the smallest k, the smallest j, the smallest i — the prior wins
+ *          a tie and a uniform field returns (0, 0, 0)
+ *   4      the number of the group's finite points
+ *   5      the score of candidate (0, 0, 0)
+ *   6      the number of candidates whose score equals the best (1: unambiguous)
+ *   7      0
+ * A group without points has score 0 everywhere and best 0 at (0, 0, 0).
+ * APPLYING IT: the correction is the rigid motion "rotate by k * rot_step about (px, py), then translate by
+ * (i, j) * resolution", composed in front of every d_pose2d of the group: with (c, s) the table's entry k,
+ *   R' = [c -s; s c] R;   t' = [c -s; s c] (t - pivot) + pivot + (i, j) * resolution
+ * is the pose the next rplgpu_occupancy_grid_dev call takes.
+ * d_field 4-byte aligned, field_stride >= width * height and a multiple of 4 (the E11 / E12 rules: the three
+ * calls chain); the field is only read, and only its width * height bytes per grid.  d_scores and d_best are
+ * required and 4-byte aligned; the volume is the call's own scratch (as E11's grid is): nothing is stored on the
+ * handle, nothing is copied from pageable memory.  d_status[g] (optional): RPLGPU_SCAN_OUT_TRUNCATED as E9 / E11
+ * and RPLGPU_SCAN_CELL_RANGE as above.  The argument and capacity checks of rplgpu_cloud_fused_voxel_dev;
+ * RPLGPU_ERR_INVALID_ARG also for a spec the check refuses, group = 0, a missing d_field / d_scores / d_best, the
+ * alignment and stride rules above, score_stride below the volume size, and offsets set with d_motion NULL.  A
+ * refused call changes no output.  Asynchronous on the handle's stream. */
+int32_t rplgpu_match_scans_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                               const float *d_motion, const float *d_pose2d, const float *d_pivot,
+                               const rplgpu_scan_match_t *m, const int8_t *d_field, uint64_t field_stride,
+                               uint32_t field_per_group, uint32_t *d_scores, uint64_t score_stride,
+                               uint32_t *d_best, uint32_t *d_status);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp): n_scans <= max_batch scans as
+ * rplgpu_occupancy_grid takes them; pivot: 2 floats or NULL; field: width * height bytes; scores_out (optional):
+ * the volume, rplgpu_scan_match_volume words; best: 8 words; status (optional): 1 word.  Allocates its device
+ * buffers per call and returns when the results are in place. */
+int32_t rplgpu_match_scans(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                           const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                           const float *motion, const float *pose2d, const float *t0, const float *pivot,
+                           const rplgpu_scan_match_t *m, const int8_t *field, uint32_t *scores_out,
+                           uint32_t best[8], uint32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,12 @@ ABI_SYMBOLS = [
     "rplgpu_inflation_table",
     "rplgpu_inflate_grids_dev",
     "rplgpu_inflate_grid",
+    "rplgpu_default_scan_match",
+    "rplgpu_scan_match_check",
+    "rplgpu_scan_match_rotations",
+    "rplgpu_scan_match_volume",
+    "rplgpu_match_scans_dev",
+    "rplgpu_match_scans",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -302,6 +308,33 @@ class Inflation(C.Structure):
         return f
 
 
+class ScanMatch(C.Structure):
+    """Mirror of ``rplgpu_scan_match_t`` (E13: a time step's scans matched to a likelihood field)."""
+
+    _fields_ = [
+        ("origin_x", C.c_float),
+        ("origin_y", C.c_float),
+        ("resolution", C.c_float),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("shift_x", C.c_uint32),
+        ("shift_y", C.c_uint32),
+        ("rot_steps", C.c_uint32),
+        ("rot_step", C.c_float),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "ScanMatch":
+        """The library's own defaults (``rplgpu_default_scan_match``), then the overrides."""
+        m = cls()
+        load_library().rplgpu_default_scan_match(C.byref(m))
+        for k, v in kw.items():
+            if not hasattr(m, k):
+                raise AttributeError(k)
+            setattr(m, k, v)
+        return m
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -463,6 +496,16 @@ def load_library() -> C.CDLL:
     lib.rplgpu_inflation_table.argtypes = [C.POINTER(Inflation), C.c_float, vp, u32, vp]
     lib.rplgpu_inflate_grids_dev.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, vp, u32, u32, vp]
     lib.rplgpu_inflate_grid.argtypes = [vp, vp, u32, u32, C.c_float, C.POINTER(Inflation), vp, vp]
+    lib.rplgpu_default_scan_match.argtypes = [C.POINTER(ScanMatch)]
+    lib.rplgpu_default_scan_match.restype = None
+    lib.rplgpu_scan_match_check.argtypes = [C.POINTER(ScanMatch)]
+    lib.rplgpu_scan_match_rotations.argtypes = [C.POINTER(ScanMatch), vp]
+    lib.rplgpu_scan_match_volume.argtypes = [C.POINTER(ScanMatch)]
+    lib.rplgpu_scan_match_volume.restype = u32
+    lib.rplgpu_match_scans_dev.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp, vp,
+                                           C.POINTER(ScanMatch), vp, u64, u32, vp, u64, vp, vp]
+    lib.rplgpu_match_scans.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp, vp,
+                                       C.POINTER(ScanMatch), vp, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -772,6 +815,41 @@ class RplGpu:
             self._h, grid.ctypes.data, grid.shape[1], grid.shape[0], resolution, C.byref(inflation),
             out.ctypes.data, cells.ctypes.data))
         return out, tuple(int(c) for c in cells)
+
+    def match_scans_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int, params: Params,
+                        d_motion: int, d_pose2d: int, d_pivot: int, match: ScanMatch, d_field: int,
+                        field_stride: int, field_per_group: int, d_scores: int, score_stride: int, d_best: int,
+                        d_status: int = 0):
+        """E13: per group of scans the score volume (uint32, ``scan_match_volume`` words, score_stride apart) of
+        the search window over the int8 field(s) at d_field, and eight result words at d_best + 8 g."""
+        self._check(self._lib.rplgpu_match_scans_dev(
+            self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d, d_pivot,
+            C.byref(match), d_field, field_stride, field_per_group, d_scores, score_stride, d_best, d_status))
+
+    def match_scans(self, scans: np.ndarray, lens, params: Params, match: ScanMatch, field: np.ndarray,
+                    motion=None, pose2d=None, t0=None, pivot=None, want_scores: bool = True):
+        """E13, one group, host buffers: scans (S, n) NODE_DTYPE and a (height, width) int8 field ->
+        ``(scores (2K+1, 2Ty+1, 2Tx+1) uint32 or None, best (8,) uint32, status)``."""
+        scans = np.ascontiguousarray(scans)
+        if scans.dtype != NODE_DTYPE or scans.ndim != 2:
+            raise TypeError("scans must be a 2-D array of abi.NODE_DTYPE")
+        field = np.ascontiguousarray(field, np.int8)
+        if field.shape != (match.height, match.width):
+            raise TypeError("field must be a (height, width) int8 array")
+        S, n = scans.shape
+        lens = np.ascontiguousarray(lens, np.uint32)
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
+        motion, pose2d, t0, pivot = f32(motion), f32(pose2d), f32(t0), f32(pivot)
+        scores = None
+        if want_scores:
+            scores = np.zeros((2 * match.rot_steps + 1, 2 * match.shift_y + 1, 2 * match.shift_x + 1), np.uint32)
+        best = np.zeros(8, np.uint32)
+        status = np.zeros(1, np.uint32)
+        ptr = lambda a: 0 if a is None else a.ctypes.data  # noqa: E731
+        self._check(self._lib.rplgpu_match_scans(
+            self._h, scans.ctypes.data, n, lens.ctypes.data, S, C.byref(params), ptr(motion), ptr(pose2d), ptr(t0),
+            ptr(pivot), C.byref(match), field.ctypes.data, ptr(scores), best.ctypes.data, status.ctypes.data))
+        return scores, best, int(status[0])
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -1202,3 +1280,26 @@ def inflation_table(inflation: Inflation, resolution: float):
         raise RplGpuError(rc, "rplgpu_inflation_table")
     r = int(reach[0])
     return table[:r * r + 1].copy(), r
+
+
+def scan_match_check(match: ScanMatch) -> None:
+    """Host only: validates an E13 spec by the library's own rplgpu_scan_match_check; raises
+    RplGpuError(ERR_INVALID_ARG) for a spec the device path would refuse."""
+    rc = load_library().rplgpu_scan_match_check(C.byref(match))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_scan_match_check")
+
+
+def scan_match_rotations(match: ScanMatch) -> np.ndarray:
+    """Host only: the (2K + 1, 2) float32 rotation table (cos, sin of k * rot_step, k = -K .. K) by the library's
+    own rplgpu_scan_match_rotations."""
+    cs = np.zeros((2 * match.rot_steps + 1, 2), np.float32)
+    rc = load_library().rplgpu_scan_match_rotations(C.byref(match), cs.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_scan_match_rotations")
+    return cs
+
+
+def scan_match_volume(match: ScanMatch) -> int:
+    """Host only: the words of one group's score volume, (2K + 1)(2Ty + 1)(2Tx + 1); 0 for an invalid spec."""
+    return int(load_library().rplgpu_scan_match_volume(C.byref(match)))

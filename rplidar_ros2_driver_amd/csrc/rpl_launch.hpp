@@ -293,4 +293,29 @@ hipError_t launch_inflate(hipStream_t s, const int8_t *in, unsigned long long in
                           unsigned long long out_stride, uint32_t G, uint32_t width, uint32_t height,
                           const uint8_t *table, uint32_t rc, uint32_t inflate_unknown, uint32_t *cells);
 
+// E13: correlative scan matching of groups of scans against a likelihood field (rpl_match.hip,
+// include/rplgpu_msg.h).  The score volume is the call's scratch: prepare zeroes the volumes and the eight
+// result words of every group, score adds the field values under the points into the volumes (and the finite
+// points into result word 4), best reduces a volume to the other seven words.
+struct MatchK {  // a checked rplgpu_scan_match_t
+  float origin_x, origin_y, resolution;
+  uint32_t width, height;
+  uint32_t tx, ty, rot;
+};
+struct MatchRot {  // rplgpu_scan_match_rotations: (cos, sin) of k * rot_step at 2 (k + K), by value
+  float cs[2u * (2u * RPLGPU_MAX_MATCH_ROT + 1u)];
+};
+uint32_t match_volume(const MatchK &k);
+hipError_t launch_match_prepare(hipStream_t s, uint32_t *scores, unsigned long long score_stride, uint32_t G,
+                                const MatchK &k, uint32_t *best);
+hipError_t launch_match_score(hipStream_t s, const void *nodes, uint32_t n_stride, const uint32_t *n_per_scan,
+                              uint32_t B, uint32_t group, const KParams &p, const Tables &T,
+                              const uint32_t *keepmask, uint32_t mask_stride, const float *motion,
+                              const float *pose2d, const float *pivot, const MatchK &k, const MatchRot &rot,
+                              const int8_t *field, unsigned long long field_stride, uint32_t field_per_group,
+                              uint32_t *scores, unsigned long long score_stride, uint32_t *best,
+                              uint32_t *status);
+hipError_t launch_match_best(hipStream_t s, const uint32_t *scores, unsigned long long score_stride, uint32_t G,
+                             const MatchK &k, uint32_t *best);
+
 }  // namespace rpl

@@ -1,0 +1,362 @@
+// rpl_match.hip — E13: correlative scan matching of a group of scans (the sensors of one time step) against a
+// likelihood field, include/rplgpu_msg.h, rplgpu_match_scans_dev: the group's points are laid over the field at
+// every pose of a search window (2K+1 rotations about a pivot x (2Ty+1) x (2Tx+1) whole-cell shifts), the field
+// values under them are added up per pose and the best pose is kept.
+//
+// The score volume is the call's own scratch, three launches and nothing on the handle:
+//   k_match_prepare  zeroes every group's volume and its eight result words;
+//   k_match_score    adds the field values under the points into the volume;
+//   k_match_best     reduces a group's volume to its eight result words.
+//
+// k_match_score: one 1024-thread workgroup per (scan, rotation, slice of the scan's 2048-sample passes), the
+// front end of k_occ_walk as it stands (two nodes per bounds-checked buffer_load_dwordx4, E1 / E5 keep bits, the
+// (cos, sin) table, rpl_xf.hpp's sample_xy), so a point lands where E8, E9 and E11 put it, bit for bit.  Behind
+// it, per 2048 samples:
+//   * a sample becomes a CELL: the E11 cell of its rotated position.  A cell farther than the window from the
+//     grid scores nothing at any shift and is dropped; the others fit 13 bits per axis.
+//   * consecutive samples of a wave half that land in one cell (a wall's neighbours) become ONE list entry with
+//     a weight of up to 64: the run lengths come from two ballots, no scan.  The entries are compacted into an
+//     LDS list (one atomic per wave).
+//   * then the threads own candidates, not points: the (j, i) shifts are laid out flat, i fastest, over
+//     consecutive threads, so a wave's look-ups of one entry are consecutive bytes of one or two field rows.  A
+//     window of up to 1024 candidates is repeated over the workgroup as often as it fits and each copy walks its
+//     share of the list; a larger one gives every thread up to kMaxOwn candidates in registers.
+//   * the copies are added up through LDS and leave with one no-return atomic add per candidate.
+// All integers behind the cell rule: the volume depends on no order.
+#include <hip/hip_runtime.h>
+
+#include "rpl_device.hpp"
+#include "rpl_launch.hpp"
+#include "rpl_xf.hpp"
+
+namespace rpl {
+namespace {
+
+typedef uint32_t mt_u32x4 __attribute__((ext_vector_type(4)));
+constexpr uint32_t kList = 2u * kBlock;  // entries per pass: two samples per thread
+constexpr float kCellLimit = 1048576.0f;
+constexpr int kCellBias = 64;            // cell + kCellBias >= 32 for every listed cell: an entry is never 0
+constexpr uint32_t kCellBits = 13;       // -32 .. 4096 + 31, biased, per axis
+constexpr uint32_t kCellMask = (1u << kCellBits) - 1u;
+constexpr int kMaxOwn = 5;               // candidates a thread owns when the window is above kBlock (65 * 65 / 1024)
+static_assert((2u * RPLGPU_MAX_MATCH_SHIFT + 1u) * (2u * RPLGPU_MAX_MATCH_SHIFT + 1u) <= (uint32_t)kMaxOwn * kBlock,
+              "the window does not fit the registers of a workgroup");
+static_assert(RPLGPU_MAX_OCC_DIM + RPLGPU_MAX_MATCH_SHIFT + kCellBias <= (1u << kCellBits), "cell bits");
+static_assert(RPLGPU_MAX_MATCH_SHIFT <= (uint32_t)kCellBias / 2u, "cell bias");
+
+// the E11 cell rule; false: the position has no cell (NaN fails the compares too)
+__device__ __forceinline__ bool match_cell(float x, float y, const MatchK &k, int *cx, int *cy) {
+  const float fu = floorf((x - k.origin_x) / k.resolution);
+  const float fv = floorf((y - k.origin_y) / k.resolution);
+  if (!(fabsf(fu) < kCellLimit && fabsf(fv) < kCellLimit)) return false;
+  *cx = (int)fu;
+  *cy = (int)fv;
+  return true;
+}
+
+// One sample to its list word (biased cell, weight field 0), or 0: not kept, not finite, without a cell, or
+// out of every candidate's reach.
+template <bool FAST>
+__device__ __forceinline__ uint32_t match_word(uint32_t lo, uint32_t hi, uint32_t i, bool kept,
+                                               const float2 *__restrict__ cs, const ScanXf &xf, const MatchK &k,
+                                               float c, float s, float px, float py, uint32_t *finite,
+                                               bool *cell_range) {
+  if (!kept) return 0u;
+  const f2 xy = sample_xy<FAST>(lo, hi, i, cs, xf);
+  if (!(fabsf(xy.x) < __builtin_huge_valf() && fabsf(xy.y) < __builtin_huge_valf())) return 0u;
+  *finite += 1u;
+  const float qx = xy.x - px, qy = xy.y - py;
+  const float rx = (c * qx - s * qy) + px;
+  const float ry = (s * qx + c * qy) + py;
+  int cx, cy;
+  if (!match_cell(rx, ry, k, &cx, &cy)) {
+    *cell_range = true;
+    return 0u;
+  }
+  if (cx < -(int)k.tx || cx >= (int)(k.width + k.tx) || cy < -(int)k.ty || cy >= (int)(k.height + k.ty)) return 0u;
+  return ((uint32_t)(cy + kCellBias) << kCellBits) | (uint32_t)(cx + kCellBias);
+}
+
+// Samples that continue a run, counted from sample 0 of lane L + 1: `both` has a lane's bit when its two
+// samples continue, `first` when its sample 0 does.
+__device__ __forceinline__ uint32_t run_behind(uint32_t L, unsigned long long both, unsigned long long first) {
+  if (L >= 63u) return 0u;
+  const unsigned long long stop = (~both >> (L + 1u)) | (~0ull << (63u - L));
+  const uint32_t n = (uint32_t)__builtin_ctzll(stop);
+  const uint32_t at = L + 1u + n;
+  return 2u * n + (at < 64u ? (uint32_t)((first >> at) & 1ull) : 0u);
+}
+
+// field value under (cx + di, cy + dj): 0 outside the grid and for an unknown (negative) byte
+__device__ __forceinline__ uint32_t match_look(const int8_t *__restrict__ field, int cx, int cy, uint32_t W,
+                                               uint32_t H) {
+  if ((uint32_t)cx >= W || (uint32_t)cy >= H) return 0u;
+  const int v = field[(uint32_t)cy * W + (uint32_t)cx];
+  return (uint32_t)max(v, 0);
+}
+
+template <bool FAST>
+__global__ __launch_bounds__(kBlock) void k_match_score(
+    const uint2 *__restrict__ nodes, uint32_t n_stride, const uint32_t *__restrict__ n_per_scan, uint32_t group,
+    KParams p, Tables T, const uint32_t *__restrict__ keepmask, uint32_t mask_stride,
+    const float *__restrict__ motion, const float *__restrict__ pose2d, const float *__restrict__ pivot, MatchK k,
+    MatchRot rot, const int8_t *__restrict__ field, unsigned long long field_stride, uint32_t field_per_group,
+    uint32_t *__restrict__ scores, unsigned long long score_stride, uint32_t *__restrict__ best,
+    uint32_t *__restrict__ status) {
+  __shared__ uint32_t s_list[kList];
+  __shared__ uint32_t s_sum[kBlock];
+  __shared__ uint32_t s_cnt[2];  // the list's length, by the pass's parity: a reset never meets a late reader
+  const uint32_t sc = blockIdx.x;
+  const uint32_t kk = blockIdx.y;  // k + K
+  const uint32_t g = sc / group;
+  const uint32_t n_in = n_per_scan[sc];
+  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(n_in, min(n_stride, kMaxN)));
+  const bool first_of_scan = kk == 0u && blockIdx.z == 0u;
+  if (threadIdx.x == 0 && status && first_of_scan && n_in > n) atomicOr(&status[g], RPLGPU_SCAN_OUT_TRUNCATED);
+  if (blockIdx.z * kList >= n) return;  // (block-uniform)
+  const ScanSide sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
+  const float2 *cs = p.inverted ? T.cs_inv : T.cs;
+  const uint32_t q_min16 = p.clip_enable ? (min(p.q_min, 256u) << 16) : 0u;
+  const uint2 *scan = nodes + (size_t)sc * n_stride;
+  // bounds-checked over the scan's n * 8 bytes: a node beyond it reads as zero (and i < n drops it)
+  const __amdgpu_buffer_rsrc_t rsrc =
+      __builtin_amdgcn_make_buffer_rsrc((void *)scan, 0, (int)(n * 8u), 0x00020000);
+  const float rc = rot.cs[2u * kk], rs = rot.cs[2u * kk + 1u];
+  const float px = pivot ? pivot[2u * g] : 0.0f, py = pivot ? pivot[2u * g + 1u] : 0.0f;
+  const int8_t *fld = field + (size_t)(field_per_group ? g : 0u) * field_stride;
+  const uint32_t W = k.width, H = k.height;
+  // the candidates of this thread: window position c = (j + Ty) * nx + (i + Tx), copy `slice` of `slices`
+  const uint32_t nx = 2u * k.tx + 1u, nc = nx * (2u * k.ty + 1u);
+  const uint32_t per = min((nc + 63u) & ~63u, (uint32_t)kBlock);  // threads of one copy of the window
+  const uint32_t slices = nc <= (uint32_t)kBlock ? (uint32_t)kBlock / per : 1u;
+  const uint32_t slice = threadIdx.x / per, c0 = threadIdx.x - slice * per;
+  int di[kMaxOwn], dj[kMaxOwn];
+  bool own[kMaxOwn];
+  uint32_t acc[kMaxOwn];
+#pragma unroll
+  for (int r = 0; r < kMaxOwn; ++r) {
+    const uint32_t c = c0 + (uint32_t)r * kBlock;
+    own[r] = slice < slices && c < nc && (r == 0 || nc > (uint32_t)kBlock);
+    di[r] = (int)(c % nx) - (int)k.tx;
+    dj[r] = (int)(c / nx) - (int)k.ty;
+    acc[r] = 0u;
+  }
+  const bool wide = nc > (uint32_t)kBlock;  // (block-uniform)
+  uint32_t finite = 0u;
+  bool cell_range = false;
+  uint32_t pass = 0u;
+  for (uint32_t base = blockIdx.z * kList; base < n; base += gridDim.z * kList) {
+    uint32_t *cnt_at = &s_cnt[pass++ & 1u];
+    if (threadIdx.x == 0) *cnt_at = 0u;
+    __syncthreads();  // (also: the last pass's readers are done with the list)
+    const uint32_t pr = base / 2u + threadIdx.x;
+    if (2u * pr < n) {  // (the active lanes of a wave are its first ones: a lane's predecessor is active)
+      const mt_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(pr * 16u), 0, 0);
+      const uint32_t i0 = 2u * pr, i1 = i0 + 1u;
+      bool k0 = i0 < n && (__builtin_amdgcn_alignbit(t.y, t.x, 16) - p.d_lo) <= p.d_span &&
+                (t.y & 0x00FF0000u) >= q_min16;  // E1
+      bool k1 = i1 < n && (__builtin_amdgcn_alignbit(t.w, t.z, 16) - p.d_lo) <= p.d_span &&
+                (t.w & 0x00FF0000u) >= q_min16;
+      if (sd.ror_bits) {  // E1 AND E5 (launch_ror_mask); both samples sit in one word (i0 is even)
+        const uint32_t w = sd.ror_bits[i0 >> 5];
+        k0 = k0 && ((w >> (i0 & 31u)) & 1u);
+        k1 = k1 && ((w >> (i1 & 31u)) & 1u);
+      }
+      const uint32_t w0 = match_word<FAST>(t.x, t.y, i0, k0, cs, sd.xf, k, rc, rs, px, py, &finite, &cell_range);
+      const uint32_t w1 = match_word<FAST>(t.z, t.w, i1, k1, cs, sd.xf, k, rc, rs, px, py, &finite, &cell_range);
+      // A sample continues a run when it has the cell of the sample before it; sample 0 of lanes 0 and 32 never
+      // does, so a run holds at most 64 samples and its weight - 1 fits the six bits above the cell.
+      const uint32_t before = __shfl_up(w1, 1, 64);  // the word of sample i0 - 1
+      const bool e0 = w0 && (lane_id() & 31u) != 0u && w0 == before, e1 = w1 && w1 == w0;
+      const bool h0 = w0 && !e0, h1 = w1 && !e1;
+      const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1);
+      const unsigned long long c_first = __ballot(e0), c_both = c_first & __ballot(e1);
+      const uint32_t behind = run_behind(lane_id(), c_both, c_first);
+      const uint32_t wt0 = e1 ? 2u + behind : 1u, wt1 = 1u + behind;
+      // one LDS atomic per wave: the wave's entries stay together in the list, in sample order
+      const unsigned long long below = (1ull << lane_id()) - 1ull;
+      uint32_t at = 0u;
+      if (lane_id() == 0) at = atomicAdd(cnt_at, (uint32_t)(__popcll(m0) + __popcll(m1)));
+      at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at) + (uint32_t)(__popcll(m0 & below) + __popcll(m1 & below));
+      if (h0) s_list[at] = w0 | ((wt0 - 1u) << (2u * kCellBits));
+      if (h1) s_list[at + (h0 ? 1u : 0u)] = w1 | ((wt1 - 1u) << (2u * kCellBits));
+    }
+    __syncthreads();
+    const uint32_t cnt = *cnt_at;  // <= kList
+    if (!wide) {
+      if (own[0]) {
+#pragma unroll 4
+        for (uint32_t e = slice; e < cnt; e += slices) {
+          const uint32_t w = s_list[e];
+          const int cx = (int)(w & kCellMask) - kCellBias, cy = (int)((w >> kCellBits) & kCellMask) - kCellBias;
+          acc[0] += ((w >> (2u * kCellBits)) + 1u) * match_look(fld, cx + di[0], cy + dj[0], W, H);
+        }
+      }
+    } else {
+      for (uint32_t e = 0; e < cnt; ++e) {
+        const uint32_t w = s_list[e];
+        const int cx = (int)(w & kCellMask) - kCellBias, cy = (int)((w >> kCellBits) & kCellMask) - kCellBias;
+        const uint32_t wt = (w >> (2u * kCellBits)) + 1u;
+#pragma unroll
+        for (int r = 0; r < kMaxOwn; ++r)
+          if (own[r]) acc[r] += wt * match_look(fld, cx + di[r], cy + dj[r], W, H);
+      }
+    }
+  }
+  if (status && __any(cell_range) && lane_id() == 0) atomicOr(&status[g], RPLGPU_SCAN_CELL_RANGE);
+  if (kk == 0u) {  // word 4, the group's finite points: once per sample, by the workgroups of the first rotation
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) finite += __shfl_xor(finite, d, 64);
+    if (lane_id() == 0 && finite) atomicAdd(&best[8u * g + 4u], finite);
+  }
+  uint32_t *vol = scores + (size_t)g * score_stride + (size_t)kk * nc;
+  if (wide) {
+#pragma unroll
+    for (int r = 0; r < kMaxOwn; ++r)
+      if (own[r] && acc[r]) atomicAdd(&vol[c0 + (uint32_t)r * kBlock], acc[r]);
+    return;
+  }
+  __syncthreads();
+  s_sum[threadIdx.x] = own[0] ? acc[0] : 0u;  // copy `slice` at [slice * per, slice * per + per)
+  __syncthreads();
+  if (threadIdx.x < nc) {
+    uint32_t sum = 0u;
+    for (uint32_t s = 0; s < slices; ++s) sum += s_sum[s * per + threadIdx.x];
+    if (sum) atomicAdd(&vol[threadIdx.x], sum);
+  }
+}
+
+constexpr uint32_t kPrepThreads = 256;
+
+__global__ __launch_bounds__(kPrepThreads) void k_match_prepare(uint32_t *__restrict__ scores,
+                                                                unsigned long long score_stride, uint32_t volume,
+                                                                uint32_t blocks_per_group,
+                                                                uint32_t *__restrict__ best) {
+  const uint32_t g = blockIdx.x / blocks_per_group;
+  const uint32_t b = blockIdx.x - g * blocks_per_group;
+  const uint32_t w = b * kPrepThreads + threadIdx.x;
+  if (w < volume) scores[(size_t)g * score_stride + w] = 0u;
+  if (b == 0 && threadIdx.x < 8u) best[8u * g + threadIdx.x] = 0u;
+}
+
+// The tie rule as one number, smaller is better: i*i + j*j (12 bits), |k| (7), k > 0 (1), j + Ty (7), i > 0 (1).
+// With i*i + j*j and j equal two candidates differ in the sign of i alone, so one bit orders i.
+__device__ __forceinline__ uint32_t match_penalty(int kr, int j, int i, uint32_t ty) {
+  return ((uint32_t)(i * i + j * j) << 16) | ((uint32_t)abs(kr) << 9) | ((kr > 0 ? 1u : 0u) << 8) |
+         ((uint32_t)(j + (int)ty) << 1) | (i > 0 ? 1u : 0u);
+}
+
+__global__ __launch_bounds__(kBlock) void k_match_best(const uint32_t *__restrict__ scores,
+                                                       unsigned long long score_stride, MatchK k,
+                                                       uint32_t *__restrict__ best) {
+  __shared__ unsigned long long s_key[kWaves];
+  __shared__ uint32_t s_eq[kWaves];
+  const uint32_t g = blockIdx.x;
+  const uint32_t *vol = scores + (size_t)g * score_stride;
+  const uint32_t nx = 2u * k.tx + 1u, ny = 2u * k.ty + 1u, nc = nx * ny, volume = nc * (2u * k.rot + 1u);
+  // the largest (score, ~penalty): the score in the high word, the tie rule below it
+  unsigned long long key = 0ull;
+  for (uint32_t v = threadIdx.x; v < volume; v += kBlock) {
+    const uint32_t kk = v / nc, c = v - kk * nc;
+    const int kr = (int)kk - (int)k.rot, j = (int)(c / nx) - (int)k.ty, i = (int)(c % nx) - (int)k.tx;
+    const unsigned long long cand = ((unsigned long long)vol[v] << 32) | (uint32_t)~match_penalty(kr, j, i, k.ty);
+    key = cand > key ? cand : key;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const unsigned long long o = __shfl_xor(key, d, 64);
+    key = o > key ? o : key;
+  }
+  if (lane_id() == 0) s_key[wave_id()] = key;
+  __syncthreads();
+  key = s_key[0];
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) key = s_key[w] > key ? s_key[w] : key;
+  const uint32_t top = (uint32_t)(key >> 32);
+  // second pass: how many candidates have the best score, and which one carries the key
+  uint32_t eq = 0u;
+  for (uint32_t v = threadIdx.x; v < volume; v += kBlock) {
+    if (vol[v] != top) continue;
+    ++eq;
+    const uint32_t kk = v / nc, c = v - kk * nc;
+    const int kr = (int)kk - (int)k.rot, j = (int)(c / nx) - (int)k.ty, i = (int)(c % nx) - (int)k.tx;
+    if ((uint32_t)~match_penalty(kr, j, i, k.ty) == (uint32_t)key) {  // (penalties are distinct: one thread)
+      best[8u * g + 0u] = top;
+      best[8u * g + 1u] = (uint32_t)kr;
+      best[8u * g + 2u] = (uint32_t)j;
+      best[8u * g + 3u] = (uint32_t)i;
+      best[8u * g + 7u] = 0u;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) eq += __shfl_xor(eq, d, 64);
+  if (lane_id() == 0) s_eq[wave_id()] = eq;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t sum = 0u;
+    for (int w = 0; w < kWaves; ++w) sum += s_eq[w];
+    best[8u * g + 5u] = vol[(size_t)k.rot * nc + (size_t)k.ty * nx + k.tx];
+    best[8u * g + 6u] = sum;
+  }
+}
+
+// blocks of kPrepThreads words per group, or 0 when G groups do not fit a 1-D grid
+uint32_t match_blocks_per_group(uint32_t G, uint32_t volume) {
+  const uint64_t bpg = ((uint64_t)volume + kPrepThreads - 1u) / kPrepThreads;
+  return (uint64_t)G * bpg > 0x7FFFFFFFull ? 0u : (uint32_t)bpg;
+}
+
+bool match_args_ok(const MatchK &k) {
+  return k.width != 0 && k.height != 0 && k.width <= RPLGPU_MAX_OCC_DIM && k.height <= RPLGPU_MAX_OCC_DIM &&
+         k.tx <= RPLGPU_MAX_MATCH_SHIFT && k.ty <= RPLGPU_MAX_MATCH_SHIFT && k.rot <= RPLGPU_MAX_MATCH_ROT;
+}
+
+}  // namespace
+
+uint32_t match_volume(const MatchK &k) { return (2u * k.rot + 1u) * (2u * k.ty + 1u) * (2u * k.tx + 1u); }
+
+hipError_t launch_match_prepare(hipStream_t s, uint32_t *scores, unsigned long long score_stride, uint32_t G,
+                                const MatchK &k, uint32_t *best) {
+  if (G == 0) return hipSuccess;
+  if (!match_args_ok(k) || score_stride < match_volume(k)) return hipErrorInvalidValue;
+  const uint32_t bpg = match_blocks_per_group(G, match_volume(k));
+  if (!bpg) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_match_prepare, dim3(G * bpg), dim3(kPrepThreads), 0, s, scores, score_stride,
+                     match_volume(k), bpg, best);
+  return hipGetLastError();
+}
+
+hipError_t launch_match_score(hipStream_t s, const void *nodes, uint32_t n_stride, const uint32_t *n_per_scan,
+                              uint32_t B, uint32_t group, const KParams &p, const Tables &T,
+                              const uint32_t *keepmask, uint32_t mask_stride, const float *motion,
+                              const float *pose2d, const float *pivot, const MatchK &k, const MatchRot &rot,
+                              const int8_t *field, unsigned long long field_stride, uint32_t field_per_group,
+                              uint32_t *scores, unsigned long long score_stride, uint32_t *best,
+                              uint32_t *status) {
+  if (B == 0) return hipSuccess;
+  if (group == 0 || !match_args_ok(k) || field_stride < (unsigned long long)k.width * k.height ||
+      score_stride < match_volume(k))
+    return hipErrorInvalidValue;
+  // slices of a scan's passes: enough workgroups for a time step of a few scans, and at most 8 x the atomics
+  const uint32_t passes = (min(n_stride, kMaxN) + kList - 1u) / kList;
+  const dim3 grid(B, 2u * k.rot + 1u, min(passes, 8u));
+  if (p.fast_d4000)
+    hipLaunchKernelGGL(k_match_score<true>, grid, dim3(kBlock), 0, s, (const uint2 *)nodes, n_stride, n_per_scan,
+                       group, p, T, keepmask, mask_stride, motion, pose2d, pivot, k, rot, field, field_stride,
+                       field_per_group, scores, score_stride, best, status);
+  else
+    hipLaunchKernelGGL(k_match_score<false>, grid, dim3(kBlock), 0, s, (const uint2 *)nodes, n_stride, n_per_scan,
+                       group, p, T, keepmask, mask_stride, motion, pose2d, pivot, k, rot, field, field_stride,
+                       field_per_group, scores, score_stride, best, status);
+  return hipGetLastError();
+}
+
+hipError_t launch_match_best(hipStream_t s, const uint32_t *scores, unsigned long long score_stride, uint32_t G,
+                             const MatchK &k, uint32_t *best) {
+  if (G == 0) return hipSuccess;
+  if (!match_args_ok(k) || score_stride < match_volume(k)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_match_best, dim3(G), dim3(kBlock), 0, s, scores, score_stride, k, best);
+  return hipGetLastError();
+}
+
+}  // namespace rpl

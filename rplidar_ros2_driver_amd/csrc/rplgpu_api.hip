@@ -1789,6 +1789,198 @@ int32_t rplgpu_inflate_grid(rplgpu_handle_t h, const int8_t *in, uint32_t width,
   return RPLGPU_OK;
 }
 
+// ---- E13: a time step's scans matched to a likelihood field (include/rplgpu_msg.h) ---------------------------
+
+void rplgpu_default_scan_match(rplgpu_scan_match_t *m) {
+  if (!m) return;
+  m->origin_x = -25.6f;
+  m->origin_y = -25.6f;
+  m->resolution = 0.05f;
+  m->width = 1024;
+  m->height = 1024;
+  m->shift_x = 6;
+  m->shift_y = 6;
+  m->rot_steps = 10;
+  m->rot_step = (float)(0.25 * M_PI / 180.0);
+}
+
+int32_t rplgpu_scan_match_check(const rplgpu_scan_match_t *m) {
+  if (!m) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(m->origin_x) || !std::isfinite(m->origin_y) || !std::isfinite(m->resolution) ||
+      !std::isfinite(m->rot_step))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!(m->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  if (m->width == 0 || m->width > RPLGPU_MAX_OCC_DIM || m->height == 0 || m->height > RPLGPU_MAX_OCC_DIM)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (m->shift_x > RPLGPU_MAX_MATCH_SHIFT || m->shift_y > RPLGPU_MAX_MATCH_SHIFT ||
+      m->rot_steps > RPLGPU_MAX_MATCH_ROT)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (m->rot_steps > 0 && (!(m->rot_step > 0.0f) || (double)m->rot_steps * (double)m->rot_step > M_PI / 2.0))
+    return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_scan_match_rotations(const rplgpu_scan_match_t *m, float *cs) {
+  if (!cs || rplgpu_scan_match_check(m) != RPLGPU_OK) return RPLGPU_ERR_INVALID_ARG;
+  const int K = (int)m->rot_steps;
+  for (int k = -K; k <= K; ++k) {
+    const double a = (double)k * (double)m->rot_step;
+    cs[2 * (k + K)] = (float)std::cos(a);
+    cs[2 * (k + K) + 1] = (float)std::sin(a);
+  }
+  return RPLGPU_OK;
+}
+
+uint32_t rplgpu_scan_match_volume(const rplgpu_scan_match_t *m) {
+  if (rplgpu_scan_match_check(m) != RPLGPU_OK) return 0;
+  return (2u * m->rot_steps + 1u) * (2u * m->shift_y + 1u) * (2u * m->shift_x + 1u);
+}
+
+// d_t0: the per-scan time offsets of E6 for this call (the handle's, or the host door's own), or NULL
+static int32_t match_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                          const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                          const float *d_motion, const float *d_pose2d, const float *d_t0, const float *d_pivot,
+                          const rplgpu_scan_match_t *m, const int8_t *d_field, uint64_t field_stride,
+                          uint32_t field_per_group, uint32_t *d_scores, uint64_t score_stride, uint32_t *d_best,
+                          uint32_t *d_status) {
+  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
+  if (rc) return rc;
+  if (!p || !m || !d_field || !d_scores || !d_best || group == 0) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_scan_match_check(m) != RPLGPU_OK) {
+    h->err = "rplgpu_match_scans_dev: invalid rplgpu_scan_match_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (field_stride < (uint64_t)m->width * m->height || (field_stride & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_field) & 3u)) {
+    h->err = "rplgpu_match_scans_dev: field_stride must be >= width * height and a multiple of 4, d_field 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint32_t volume = rplgpu_scan_match_volume(m);
+  if (score_stride < volume || (reinterpret_cast<uintptr_t>(d_scores) & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_best) & 3u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
+    h->err = "rplgpu_match_scans_dev: score_stride must be >= the volume size, d_scores / d_best / d_status 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (B == 0) return RPLGPU_OK;
+  if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
+      (d_pose2d && !device_readable(h, d_pose2d, "d_pose2d")) ||
+      (d_pivot && !device_readable(h, d_pivot, "d_pivot")) || !device_readable(h, d_field, "d_field") ||
+      !device_readable(h, d_scores, "d_scores") || !device_readable(h, d_best, "d_best") ||
+      (d_status && !device_readable(h, d_status, "d_status")))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (d_t0 && !d_motion) {
+    h->err = "rplgpu_match_scans_dev: scan time offsets are set (rplgpu_set_scan_time_offsets_dev) but d_motion is NULL";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
+    h->err = "ror_radius must be in (0, 1e6] m";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  group = std::min(group, B);  // as E8: "all sensors in one match" may be asked for with any group >= B
+  if ((uint64_t)group * n_stride > (1ull << 24)) {  // 127 x points stays below 2^32: no score wraps
+    h->err = "rplgpu_match_scans_dev: group x n_stride above 2^24 samples";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint32_t G = (B + group - 1u) / group;
+  const rpl::MatchK k{m->origin_x, m->origin_y, m->resolution, m->width, m->height,
+                      m->shift_x, m->shift_y, m->rot_steps};
+  rpl::MatchRot rot;  // at most 129 pairs, handed to the kernel by value: no copy on the stream
+  std::memset(&rot, 0, sizeof(rot));
+  if (rplgpu_scan_match_rotations(m, rot.cs) != RPLGPU_OK) return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  rpl::KParams kp = to_kparams(*p);
+  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
+  rpl::Tables T = tables_of(h);
+  T.scan_t0 = d_t0;
+  const uint32_t *mask = nullptr;
+  if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E9 and E11 apply
+    RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
+                                    kMaskStride));
+    mask = h->d_rormask;
+  }
+  if (d_status) RPL_HIP(h, hipMemsetAsync(d_status, 0, (size_t)G * 4u, h->stream));
+  RPL_HIP(h, rpl::launch_match_prepare(h->stream, d_scores, score_stride, G, k, d_best));
+  RPL_HIP(h, rpl::launch_match_score(h->stream, d_nodes, n_stride, d_n_per_scan, B, group, kp, T, mask, kMaskStride,
+                                     d_motion, d_pose2d, d_pivot, k, rot, d_field, field_stride, field_per_group,
+                                     d_scores, score_stride, d_best, d_status));
+  RPL_HIP(h, rpl::launch_match_best(h->stream, d_scores, score_stride, G, k, d_best));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_match_scans_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                               const float *d_motion, const float *d_pose2d, const float *d_pivot,
+                               const rplgpu_scan_match_t *m, const int8_t *d_field, uint64_t field_stride,
+                               uint32_t field_per_group, uint32_t *d_scores, uint64_t score_stride,
+                               uint32_t *d_best, uint32_t *d_status) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  return match_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, h->scan_t0, d_pivot, m,
+                    d_field, field_stride, field_per_group, d_scores, score_stride, d_best, d_status);
+}
+
+int32_t rplgpu_match_scans(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                           const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                           const float *motion, const float *pose2d, const float *t0, const float *pivot,
+                           const rplgpu_scan_match_t *m, const int8_t *field, uint32_t *scores_out,
+                           uint32_t best[8], uint32_t *status) {
+  if (!h || !nodes || !n_per_scan || !p || !m || !field || !best || n_scans == 0 || n_stride == 0)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_scan_match_check(m) != RPLGPU_OK) {
+    h->err = "rplgpu_match_scans: invalid rplgpu_scan_match_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
+  RPL_HIP(h, hipSetDevice(h->device));
+  const size_t cells_n = (size_t)m->width * m->height, stride = (cells_n + 3u) & ~(size_t)3u;
+  const size_t nb = (size_t)n_scans * n_stride * 8u;
+  const size_t volume = rplgpu_scan_match_volume(m);
+  // one allocation per call (a convenience door, not the hot path): field | scores | nodes | lengths | motion |
+  // pose | t0 | pivot | best + status, every part 16-byte aligned
+  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  const size_t o_sc = up16(stride), o_nodes = o_sc + up16(4u * volume), o_len = o_nodes + up16(nb),
+               o_mo = o_len + up16(4u * n_scans), o_po = o_mo + up16(motion ? 16u * n_scans : 0),
+               o_t0 = o_po + up16(pose2d ? 24u * n_scans : 0), o_pv = o_t0 + up16(t0 ? 4u * n_scans : 0),
+               o_small = o_pv + up16(pivot ? 8u : 0), total = o_small + 48u;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_match_scans: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t small[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  auto run = [&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(d, field, cells_n, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_nodes, nodes, nb, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_len, n_per_scan, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (motion) RPL_HIP(h, hipMemcpyAsync(d + o_mo, motion, 16u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (pose2d) RPL_HIP(h, hipMemcpyAsync(d + o_po, pose2d, 24u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (t0) RPL_HIP(h, hipMemcpyAsync(d + o_t0, t0, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (pivot) RPL_HIP(h, hipMemcpyAsync(d + o_pv, pivot, 8u, hipMemcpyHostToDevice, h->stream));
+    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);
+    const int32_t rc = match_impl(
+        h, reinterpret_cast<const rplgpu_node_t *>(d + o_nodes), n_stride,
+        reinterpret_cast<const uint32_t *>(d + o_len), n_scans, n_scans, p,
+        motion ? reinterpret_cast<const float *>(d + o_mo) : nullptr,
+        pose2d ? reinterpret_cast<const float *>(d + o_po) : nullptr,
+        t0 ? reinterpret_cast<const float *>(d + o_t0) : nullptr,
+        pivot ? reinterpret_cast<const float *>(d + o_pv) : nullptr, m, reinterpret_cast<const int8_t *>(d), stride, 0,
+        reinterpret_cast<uint32_t *>(d + o_sc), volume, d_small, d_small + 8);
+    if (rc) return rc;
+    if (scores_out)
+      RPL_HIP(h, hipMemcpyAsync(scores_out, d + o_sc, 4u * volume, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d_small, 36, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;
+  std::memcpy(best, small, 32);
+  if (status) *status = small[8];
+  return RPLGPU_OK;
+}
+
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,

@@ -238,6 +238,32 @@ int main(int argc, char **argv) {
       return 10;
     }
     std::printf("inflation: cells 100/99/1..98/-1 = %u/%u/%u/%u\n", icells[0], icells[1], icells[2], icells[3]);
+    // E13 against that costmap: the return at 2 m alone, seen from a prior 1 m behind the true pose (sensor in
+    // cell (-1, 1)), lands in cell (1, 1) = 99; one cell to the right it meets the lethal cell (2, 1) = 100, and
+    // no other shift of a 2 x 1 window reaches 100: best (k, j, i) = (0, 0, 1), unambiguous.
+    std::vector<std::vector<rplgpu_node_t>> one(1);
+    one[0].push_back(step[0][0]);
+    const float prior[6] = {1.0f, 0.0f, -1.0f, 0.0f, 1.0f, 0.0f};
+    rplgpu_scan_match_t win;
+    rplgpu_default_scan_match(&win);
+    win.shift_x = 2;
+    win.shift_y = 1;
+    win.rot_steps = 0;
+    rplgpu_host::ScanPath::MatchResult mr;
+    uint32_t mstatus = 99;
+    if (!path.match_scans(one, rplgpu_host::ScanConfig(), prior, nullptr, nullptr, nullptr, cost_msg, win, mr,
+                          &mstatus)) {
+      std::fprintf(stderr, "scan match failed: %s\n", path.last_error().c_str());
+      return 11;
+    }
+    if (mr.score != 100 || mr.k != 0 || mr.j != 0 || mr.i != 1 || mr.points != 1 || mr.score_at_prior != 99 ||
+        mr.ties != 1 || mstatus != 0) {
+      std::fprintf(stderr, "scan match: wrong answer (%u at %d %d %d, %u points, %u at the prior, %u ties)\n", mr.score,
+                   mr.k, mr.j, mr.i, mr.points, mr.score_at_prior, mr.ties);
+      return 12;
+    }
+    std::printf("scan match: best %u at (k, j, i) = (%d, %d, %d), %u at the prior\n", mr.score, mr.k, mr.j, mr.i,
+                mr.score_at_prior);
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

@@ -22,6 +22,8 @@
 //         -> rplgpu_host::ScanPath::fill_occupancy_grid(scans, ..., grid_msg)   (E11)
 //   inf the consumer's second loop (a costmap inflation layer over that grid):
 //         -> rplgpu_host::ScanPath::inflate_grid(grid_msg, inflation, costmap_msg)  (E12)
+//   mat the localisation side's loop (a correlative scan matcher's search window over a likelihood field):
+//         -> rplgpu_host::ScanPath::match_scans(scans, ..., field_msg, window, result)  (E13)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -379,6 +381,58 @@ class ScanPath {
       return note_error();
     costmap_msg.info = grid_msg.info;
     costmap_msg.data.assign(occ_out_.begin(), occ_out_.end());
+    return true;
+  }
+
+  // ext E13 (include/rplgpu_msg.h): the scans of ONE time step matched to `field_msg`, a likelihood field in a
+  // nav_msgs/OccupancyGrid-shaped message (e.g. what inflate_grid left for a map) — what a correlative scan
+  // matcher does per update.  pose2d is the PRIOR of every sensor in the field's frame, pivot (2 floats or null)
+  // the base's prior position; shift_x / shift_y / rot_steps / rot_step of `window` are used, its grid comes
+  // from field_msg.info (origin orientation must be the identity).  result: the eight words of the header's BEST
+  // table — score, k, j, i, finite points, score of (0, 0, 0), candidates that tie, 0.
+  struct MatchResult {
+    uint32_t score = 0;
+    int32_t k = 0, j = 0, i = 0;
+    uint32_t points = 0, score_at_prior = 0, ties = 0;
+  };
+  template <class NodeT, class OccupancyGridT>
+  bool match_scans(const std::vector<std::vector<NodeT>> &scans, const ScanConfig &cfg, const float *pose2d,
+                   const float *motion, const float *t0, const float *pivot, const OccupancyGridT &field_msg,
+                   const rplgpu_scan_match_t &window, MatchResult &result, uint32_t *status = nullptr) {
+    if (scans.empty()) return false;
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    rplgpu_scan_match_t m = window;
+    m.origin_x = static_cast<float>(field_msg.info.origin.position.x);
+    m.origin_y = static_cast<float>(field_msg.info.origin.position.y);
+    m.resolution = field_msg.info.resolution;
+    m.width = field_msg.info.width;
+    m.height = field_msg.info.height;
+    const size_t n_cells = static_cast<size_t>(m.width) * m.height;
+    if (n_cells == 0 || field_msg.data.size() != n_cells) return fail("match_scans: data is not width x height");
+    size_t stride = 1;
+    for (const auto &s : scans) stride = s.size() > stride ? s.size() : stride;
+    if (stride > max_n_) return fail("scan larger than the configured capacity");
+    occ_nodes_.assign(scans.size() * stride, rplgpu_node_t{});
+    occ_len_.resize(scans.size());
+    for (size_t b = 0; b < scans.size(); ++b) {
+      if (!scans[b].empty()) std::memcpy(&occ_nodes_[b * stride], scans[b].data(), scans[b].size() * 8);
+      occ_len_[b] = static_cast<uint32_t>(scans[b].size());
+    }
+    occ_prev_.assign(field_msg.data.begin(), field_msg.data.end());
+    const rplgpu_params_t p = cfg.to_params();
+    uint32_t best[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_match_scans(h_, occ_nodes_.data(), static_cast<uint32_t>(stride), occ_len_.data(),
+                           static_cast<uint32_t>(scans.size()), &p, motion, pose2d, t0, pivot, &m, occ_prev_.data(),
+                           nullptr, best, status) != RPLGPU_OK)
+      return note_error();
+    result.score = best[0];
+    result.k = static_cast<int32_t>(best[1]);
+    result.j = static_cast<int32_t>(best[2]);
+    result.i = static_cast<int32_t>(best[3]);
+    result.points = best[4];
+    result.score_at_prior = best[5];
+    result.ties = best[6];
     return true;
   }
 
