@@ -604,6 +604,95 @@ int32_t rplgpu_match_scans(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32
                            const rplgpu_scan_match_t *m, const int8_t *field, uint32_t *scores_out,
                            uint32_t best[8], uint32_t *status);
 
+/* ---- E14: time steps accumulated into a hit / miss map at matched poses (row 4; the mapping side's map update) ----
+ * What slam_toolbox / Karto and every 2-D mapper among E11's readers keep: a map that MANY time steps have voted on,
+ * each at its own (matched) pose.  E11 gives the grid of one time step and E13 matches against one field; here a
+ * persistent count map sums the rays of every call, a cell rule turns the counts into the int8 grid E12 and E13
+ * take, and a small kernel applies E13's eight result words to the poses, so match -> correct -> map -> field ->
+ * match stays on one stream with no host round trip.  Counts are integer sums: the result depends on no order.
+ * Nothing in the reference builds a map, so these rules ARE the definition (parity unpinned, as E5-E13).
+ *
+ * THE COUNT MAP: two uint32_t per cell in E11's row-major cell order, d_counts[2 * (cy * width + cx)] = misses,
+ * [... + 1] = hits; 8-byte aligned, caller-owned and PERSISTENT: a call ADDS to what is there.  The caller zeroes
+ * it (a plain hipMemsetAsync on the handle's stream); there is no prepare kernel and nothing is kept on the handle.
+ * Words at and beyond 2 * width * height are never touched.
+ *
+ * rplgpu_map_update_dev: POINTS, the sensor position, CELL, the PER POINT rules (ignored / WHOLE / CUT / dropped
+ * with RPLGPU_SCAN_CELL_RANGE) and THE WALK are those of rplgpu_occupancy_grid_dev, word for word; `grid` is
+ * checked by rplgpu_occ_grid_check.  Every ray of ALL B scans goes into the ONE map; `group` (clamped to B as
+ * elsewhere) only picks the status word d_status[g] (optional: RPLGPU_SCAN_OUT_TRUNCATED and RPLGPU_SCAN_CELL_RANGE
+ * as E11; cleared on the stream by the call).  Per ray, in E11's words: every cell the ray CLEARS gets misses += 1,
+ * the cell it MARKS gets hits += 1; so a whole ray beyond obstacle_max leaves its end cell alone, a cut ray counts
+ * a miss in its end cell, and visits outside the grid do nothing.  Equal rays are NOT a set here: each counts.
+ * Defined while every counter stays below 2^32; beyond that is the caller's error, like overlap.
+ * On a zeroed map and for one group this makes one identity exact: hits > 0 <=> E11 says 100, and
+ * hits == 0 && misses > 0 <=> E11 says 0.
+ * The argument and capacity checks of rplgpu_occupancy_grid_dev, plus RPLGPU_ERR_INVALID_ARG for a d_counts that
+ * is NULL or not 8-byte aligned.  A refused call changes nothing.  Asynchronous on the handle's stream. */
+int32_t rplgpu_map_update_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                              const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                              const float *d_motion, const float *d_pose2d, const rplgpu_occ_grid_t *grid,
+                              uint32_t *d_counts, uint32_t *d_status);
+/* THE CELL RULE, per cell with h = hits, m = misses, n = h + m, every product and sum in 64 bits:
+ *   n < min_observations: the cell's byte in d_prev (E11's layout), or -1 when d_prev is NULL;
+ *   mode 0: 100 when h > 0 and 100 * h >= occupied_percent * n, else 0 (with occupied_percent 0 and
+ *           min_observations 1 this is E11's "marks beat clears"; the defaults are Karto's min_pass_through and
+ *           occupancy_threshold);
+ *   mode 1: (200 * h + n) / (2 * n), integer division: the percentage of hits rounded half up, 0 .. 100. */
+typedef struct rplgpu_map_rule {
+  uint32_t min_observations;  /* >= 1 */
+  uint32_t occupied_percent;  /* 0 .. 100 */
+  uint32_t mode;              /* 0: three-valued, 1: percentage */
+} rplgpu_map_rule_t;
+/* min_observations 2, occupied_percent 10, mode 0 */
+void rplgpu_default_map_rule(rplgpu_map_rule_t *rule);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL, min_observations 0, occupied_percent above
+ * 100 or a mode above 1.  The device path uses this function. */
+int32_t rplgpu_map_rule_check(const rplgpu_map_rule_t *rule);
+/* The count map as ONE int8 grid at d_grid in E11's layout and under E11's rules: d_grid 4-byte aligned,
+ * grid_stride >= width * height and a multiple of 4, bytes at and beyond width * height never changed, d_prev ==
+ * d_grid refused.  The result therefore goes straight into rplgpu_inflate_grids_dev,
+ * rplgpu_occupancy_grid_msgs_dev, rplgpu_match_scans_dev and E11's own d_prev.  d_counts is only read.  d_cells
+ * (optional): 4 words, the cells that are -1, 0, 100 and anything else; cleared on the stream by the call.
+ * RPLGPU_ERR_INVALID_ARG for a rule the check refuses, a dimension of 0 or above RPLGPU_MAX_OCC_DIM, a missing or
+ * misaligned d_counts (8 bytes) / d_grid / d_cells (4 bytes) and the stride rules above.  A refused call changes
+ * nothing.  Asynchronous on the handle's stream. */
+int32_t rplgpu_map_grid_dev(rplgpu_handle_t h, const uint32_t *d_counts, uint32_t width, uint32_t height,
+                            const rplgpu_map_rule_t *rule, const int8_t *d_prev, int8_t *d_grid,
+                            uint64_t grid_stride, uint32_t *d_cells);
+/* E13's APPLYING IT on the device.  `m` is a checked rplgpu_scan_match_t: its resolution, K and rot_step are used,
+ * and the rotation table is that of rplgpu_scan_match_rotations.  For scan sc of group g (group clamped to B),
+ * (k, j, i) are words 1 - 3 of d_best + 8 g, (c, s) is the table's entry k and (px, py) = (d_pivot[2g],
+ * d_pivot[2g + 1]), (0, 0) when d_pivot is NULL.  With the pose (r00 r01 tx r10 r11 ty) = d_pose2d_in + 6 sc
+ * (NULL: identity poses), in float32, no FMA, each product rounded, then the difference or sum, in this order:
+ *   r00' = c*r00 - s*r10;  r01' = c*r01 - s*r11;  r10' = s*r00 + c*r10;  r11' = s*r01 + c*r11;
+ *   qx = tx - px;  qy = ty - py;
+ *   tx' = ((c*qx - s*qy) + px) + (float)i * resolution;  ty' = ((s*qx + c*qy) + py) + (float)j * resolution
+ * go to d_pose2d_out + 6 sc, and d_pivot_out (optional) gets (px + (float)i * resolution, py + (float)j *
+ * resolution) for every group.  d_pose2d_out == d_pose2d_in is allowed (element-wise); d_pivot_out == d_pivot is
+ * refused (every scan of a group reads the pivot).  flags bit 0: a group whose word 6 != 1 or whose word 0 == 0
+ * (ambiguous or empty) keeps its poses and pivot unchanged, bit for bit; other bits must be 0.  A k outside
+ * [-K, K] in d_best (a caller's error) is treated as that group's "keep": no table index leaves the table.
+ * k = 0 is numerically the identity, not a bit identity: +0 + -0 can change a sign bit.
+ * RPLGPU_ERR_INVALID_ARG for a spec the check refuses, group = 0, a missing d_best / d_pose2d_out, a pointer that
+ * is not 4-byte aligned, flags above 1; RPLGPU_ERR_CAPACITY for B above the handle's max_batch.  A refused call
+ * changes nothing.  Asynchronous on the handle's stream. */
+int32_t rplgpu_apply_match_dev(rplgpu_handle_t h, const uint32_t *d_best, const rplgpu_scan_match_t *m,
+                               const float *d_pivot, const float *d_pose2d_in, uint32_t B, uint32_t group,
+                               uint32_t flags, float *d_pose2d_out, float *d_pivot_out);
+/* ONE call's scans, HOST buffers (the node-side door, rplgpu_host.hpp): n_scans <= max_batch scans as
+ * rplgpu_occupancy_grid takes them, all into the one map; counts: 2 * width * height words, read, added to and
+ * written back; status (optional): 1 word.  Allocates its device buffers per call and returns when the counts are
+ * in place: a door, not a hot path. */
+int32_t rplgpu_map_update(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                          const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                          const float *motion, const float *pose2d, const float *t0, const rplgpu_occ_grid_t *grid,
+                          uint32_t *counts, uint32_t *status);
+/* HOST buffers: counts (2 * width * height words) through the rule into grid_out (width * height bytes); prev
+ * (optional): width * height bytes; cells (optional): 4 words as above.  Allocates per call as well. */
+int32_t rplgpu_map_grid(rplgpu_handle_t h, const uint32_t *counts, uint32_t width, uint32_t height,
+                        const rplgpu_map_rule_t *rule, const int8_t *prev, int8_t *grid_out, uint32_t cells[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,13 @@ ABI_SYMBOLS = [
     "rplgpu_scan_match_volume",
     "rplgpu_match_scans_dev",
     "rplgpu_match_scans",
+    "rplgpu_map_update_dev",
+    "rplgpu_default_map_rule",
+    "rplgpu_map_rule_check",
+    "rplgpu_map_grid_dev",
+    "rplgpu_apply_match_dev",
+    "rplgpu_map_update",
+    "rplgpu_map_grid",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -335,6 +342,27 @@ class ScanMatch(C.Structure):
         return m
 
 
+class MapRule(C.Structure):
+    """Mirror of ``rplgpu_map_rule_t`` (E14: hit / miss counts to the cells of an occupancy grid)."""
+
+    _fields_ = [
+        ("min_observations", C.c_uint32),
+        ("occupied_percent", C.c_uint32),
+        ("mode", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "MapRule":
+        """The library's own defaults (``rplgpu_default_map_rule``), then the overrides."""
+        r = cls()
+        load_library().rplgpu_default_map_rule(C.byref(r))
+        for k, v in kw.items():
+            if not hasattr(r, k):
+                raise AttributeError(k)
+            setattr(r, k, v)
+        return r
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -506,6 +534,16 @@ def load_library() -> C.CDLL:
                                            C.POINTER(ScanMatch), vp, u64, u32, vp, u64, vp, vp]
     lib.rplgpu_match_scans.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp, vp,
                                        C.POINTER(ScanMatch), vp, vp, vp, vp]
+    lib.rplgpu_map_update_dev.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp,
+                                          C.POINTER(OccGrid), vp, vp]
+    lib.rplgpu_default_map_rule.argtypes = [C.POINTER(MapRule)]
+    lib.rplgpu_default_map_rule.restype = None
+    lib.rplgpu_map_rule_check.argtypes = [C.POINTER(MapRule)]
+    lib.rplgpu_map_grid_dev.argtypes = [vp, vp, u32, u32, C.POINTER(MapRule), vp, vp, u64, vp]
+    lib.rplgpu_apply_match_dev.argtypes = [vp, vp, C.POINTER(ScanMatch), vp, vp, u32, u32, u32, vp, vp]
+    lib.rplgpu_map_update.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp, C.POINTER(OccGrid),
+                                      vp, vp]
+    lib.rplgpu_map_grid.argtypes = [vp, vp, u32, u32, C.POINTER(MapRule), vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -850,6 +888,62 @@ class RplGpu:
             self._h, scans.ctypes.data, n, lens.ctypes.data, S, C.byref(params), ptr(motion), ptr(pose2d), ptr(t0),
             ptr(pivot), C.byref(match), field.ctypes.data, ptr(scores), best.ctypes.data, status.ctypes.data))
         return scores, best, int(status[0])
+
+    def map_update_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int, params: Params,
+                       d_motion: int, d_pose2d: int, grid: OccGrid, d_counts: int, d_status: int = 0):
+        """E14: the rays of all B scans ADDED into the one count map at d_counts (uint32 misses, hits per cell)."""
+        self._check(self._lib.rplgpu_map_update_dev(
+            self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d, C.byref(grid),
+            d_counts, d_status))
+
+    def map_grid_dev(self, d_counts: int, width: int, height: int, rule: MapRule, d_prev: int, d_grid: int,
+                     grid_stride: int, d_cells: int = 0):
+        """E14: the count map through the cell rule into one int8 grid of E11's layout; d_cells: 4 words
+        (-1, 0, 100, anything else)."""
+        self._check(self._lib.rplgpu_map_grid_dev(
+            self._h, d_counts, width, height, C.byref(rule), d_prev, d_grid, grid_stride, d_cells))
+
+    def apply_match_dev(self, d_best: int, match: ScanMatch, d_pivot: int, d_pose2d_in: int, B: int, group: int,
+                        flags: int, d_pose2d_out: int, d_pivot_out: int = 0):
+        """E14: E13's result words at d_best composed in front of the poses (and pivots) of their groups."""
+        self._check(self._lib.rplgpu_apply_match_dev(
+            self._h, d_best, C.byref(match), d_pivot, d_pose2d_in, B, group, flags, d_pose2d_out, d_pivot_out))
+
+    def map_update(self, scans: np.ndarray, lens, params: Params, grid: OccGrid, counts: np.ndarray, motion=None,
+                   pose2d=None, t0=None):
+        """E14, one call's scans, host buffers: scans (S, n) NODE_DTYPE added into ``counts`` ((height, width, 2)
+        uint32, misses and hits, changed in place) -> status."""
+        scans = np.ascontiguousarray(scans)
+        if scans.dtype != NODE_DTYPE or scans.ndim != 2:
+            raise TypeError("scans must be a 2-D array of abi.NODE_DTYPE")
+        if (counts.dtype != np.uint32 or not counts.flags.c_contiguous
+                or counts.shape != (grid.height, grid.width, 2)):
+            raise TypeError("counts must be a C-contiguous (height, width, 2) uint32 array")
+        S, n = scans.shape
+        lens = np.ascontiguousarray(lens, np.uint32)
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
+        motion, pose2d, t0 = f32(motion), f32(pose2d), f32(t0)
+        status = np.zeros(1, np.uint32)
+        ptr = lambda a: 0 if a is None else a.ctypes.data  # noqa: E731
+        self._check(self._lib.rplgpu_map_update(
+            self._h, scans.ctypes.data, n, lens.ctypes.data, S, C.byref(params), ptr(motion), ptr(pose2d), ptr(t0),
+            C.byref(grid), counts.ctypes.data, status.ctypes.data))
+        return int(status[0])
+
+    def map_grid(self, counts: np.ndarray, rule: MapRule, prev=None):
+        """E14, host buffers: counts (height, width, 2) uint32 -> ``(grid (height, width) int8,
+        (cells -1, cells 0, cells 100, other cells))``."""
+        counts = np.ascontiguousarray(counts, np.uint32)
+        if counts.ndim != 3 or counts.shape[2] != 2:
+            raise TypeError("counts must be a (height, width, 2) uint32 array")
+        H, W = counts.shape[:2]
+        prev = None if prev is None else np.ascontiguousarray(prev, np.int8)
+        out = np.empty((H, W), np.int8)
+        cells = np.zeros(4, np.uint32)
+        self._check(self._lib.rplgpu_map_grid(
+            self._h, counts.ctypes.data, W, H, C.byref(rule), 0 if prev is None else prev.ctypes.data,
+            out.ctypes.data, cells.ctypes.data))
+        return out, tuple(int(c) for c in cells)
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -1288,6 +1382,14 @@ def scan_match_check(match: ScanMatch) -> None:
     rc = load_library().rplgpu_scan_match_check(C.byref(match))
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_scan_match_check")
+
+
+def map_rule_check(rule: MapRule) -> None:
+    """Host only: validates an E14 cell rule by the library's own rplgpu_map_rule_check; raises
+    RplGpuError(ERR_INVALID_ARG) for a rule the device path would refuse."""
+    rc = load_library().rplgpu_map_rule_check(C.byref(rule))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_map_rule_check")
 
 
 def scan_match_rotations(match: ScanMatch) -> np.ndarray:

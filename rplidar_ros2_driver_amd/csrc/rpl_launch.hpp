@@ -318,4 +318,19 @@ hipError_t launch_match_score(hipStream_t s, const void *nodes, uint32_t n_strid
 hipError_t launch_match_best(hipStream_t s, const uint32_t *scores, unsigned long long score_stride, uint32_t G,
                              const MatchK &k, uint32_t *best);
 
+// E14: the persistent hit / miss count map, its cell rule and E13's result applied to the poses (rpl_map.hip,
+// include/rplgpu_msg.h).  walk ADDS the rays of all B scans into the one map (two uint32 per cell, misses then
+// hits; `group` only picks the status word); grid turns the counts into the int8 grid of E11's layout (cells:
+// 4 words, cleared by the caller; may be null); apply composes each group's (k, j, i) in front of its poses.
+hipError_t launch_map_walk(hipStream_t s, const void *nodes, uint32_t n_stride, const uint32_t *n_per_scan,
+                           uint32_t B, uint32_t group, const KParams &p, const Tables &T,
+                           const uint32_t *keepmask, uint32_t mask_stride, const float *motion,
+                           const float *pose2d, const OccK &k, uint32_t *counts, uint32_t *status);
+hipError_t launch_map_grid(hipStream_t s, const uint32_t *counts, uint32_t width, uint32_t height,
+                           uint32_t min_observations, uint32_t occupied_percent, uint32_t mode, const int8_t *prev,
+                           int8_t *grid, uint32_t *cells);
+hipError_t launch_apply_match(hipStream_t s, const uint32_t *best, const MatchK &k, const MatchRot &rot,
+                              const float *pivot, const float *pose_in, uint32_t B, uint32_t group, uint32_t flags,
+                              float *pose_out, float *pivot_out);
+
 }  // namespace rpl

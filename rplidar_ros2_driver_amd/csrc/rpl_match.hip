@@ -27,6 +27,7 @@
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
+#include "rpl_ray.hpp"  // run_behind, shared with rpl_map.hip
 #include "rpl_xf.hpp"
 
 namespace rpl {
@@ -75,16 +76,6 @@ __device__ __forceinline__ uint32_t match_word(uint32_t lo, uint32_t hi, uint32_
   }
   if (cx < -(int)k.tx || cx >= (int)(k.width + k.tx) || cy < -(int)k.ty || cy >= (int)(k.height + k.ty)) return 0u;
   return ((uint32_t)(cy + kCellBias) << kCellBits) | (uint32_t)(cx + kCellBias);
-}
-
-// Samples that continue a run, counted from sample 0 of lane L + 1: `both` has a lane's bit when its two
-// samples continue, `first` when its sample 0 does.
-__device__ __forceinline__ uint32_t run_behind(uint32_t L, unsigned long long both, unsigned long long first) {
-  if (L >= 63u) return 0u;
-  const unsigned long long stop = (~both >> (L + 1u)) | (~0ull << (63u - L));
-  const uint32_t n = (uint32_t)__builtin_ctzll(stop);
-  const uint32_t at = L + 1u + n;
-  return 2u * n + (at < 64u ? (uint32_t)((first >> at) & 1ull) : 0u);
 }
 
 // field value under (cx + di, cy + dj): 0 outside the grid and for an unknown (negative) byte

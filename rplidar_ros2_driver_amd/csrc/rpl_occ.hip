@@ -27,6 +27,7 @@
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
 #include "rpl_msg.hpp"
+#include "rpl_ray.hpp"  // the cell rule and the ray word, shared with rpl_map.hip
 #include "rpl_xf.hpp"
 
 namespace rpl {
@@ -36,52 +37,7 @@ typedef uint32_t oc_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kWin = 640;                    // window side in cells: 50 KB of bits
 constexpr int kWinWords = kWin / 32;         // words per window row
 constexpr uint32_t kQueue = 2u * kBlock;     // rays per pass: two samples per thread
-constexpr float kCellLimit = 1048576.0f;
-constexpr int kRayBias = 16384;              // |end cell - sensor cell| < kRayBias (host-checked spec: <= 8195)
-constexpr uint32_t kRayCut = 1u << 30, kRayMark = 1u << 31;
 constexpr uint32_t kClearBit = 1u, kMarkBit = 2u;
-
-// the cell rule of the spec; false: the position has no cell (NaN fails the compares too)
-__device__ __forceinline__ bool occ_cell(float x, float y, const OccK &k, int *cx, int *cy) {
-  const float fu = floorf((x - k.origin_x) / k.resolution);
-  const float fv = floorf((y - k.origin_y) / k.resolution);
-  if (!(fabsf(fu) < kCellLimit && fabsf(fv) < kCellLimit)) return false;
-  *cx = (int)fu;
-  *cy = (int)fv;
-  return true;
-}
-
-// One sample to its ray word, or 0: no ray (not kept, ignored by the range rules, or dropped).
-template <bool FAST>
-__device__ __forceinline__ uint32_t occ_ray(uint32_t lo, uint32_t hi, uint32_t i, bool kept,
-                                            const float2 *__restrict__ cs, const ScanXf &xf, const OccK &k,
-                                            bool sensor_ok, int x0, int y0, bool *cell_range) {
-  if (!kept) return 0u;
-  const f2 xy = sample_xy<FAST>(lo, hi, i, cs, xf);
-  const float sx = xf.tx, sy = xf.ty;
-  const float dx = xy.x - sx, dy = xy.y - sy;
-  const float d = sqrtf(dx * dx + dy * dy);
-  if (!(d < __builtin_huge_valf()) || d < k.range_min) return 0u;  // (not finite: NaN fails the compare)
-  float ex = xy.x, ey = xy.y;
-  uint32_t bits = d <= k.obstacle_max ? kRayMark : 0u;
-  if (!(d <= k.raytrace_max)) {
-    const float t = k.raytrace_max / d;
-    ex = sx + dx * t;
-    ey = sy + dy * t;
-    bits = kRayCut;
-  }
-  int x1, y1;
-  if (!sensor_ok || !occ_cell(ex, ey, k, &x1, &y1)) {
-    *cell_range = true;
-    return 0u;
-  }
-  const int ddx = x1 - x0, ddy = y1 - y0;
-  if (abs(ddx) >= kRayBias || abs(ddy) >= kRayBias) {  // (not reachable with a checked spec)
-    *cell_range = true;
-    return 0u;
-  }
-  return bits | ((uint32_t)(ddy + kRayBias) << 15) | (uint32_t)(ddx + kRayBias);
-}
 
 struct OccWalk {
   uint32_t *s_win;   // kWin rows of kWinWords words: the cleared bits around the sensor

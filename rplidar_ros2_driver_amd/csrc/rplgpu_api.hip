@@ -1981,6 +1981,254 @@ int32_t rplgpu_match_scans(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32
   return RPLGPU_OK;
 }
 
+// ---- E14: time steps accumulated into a hit / miss map at matched poses (include/rplgpu_msg.h) ----------------
+
+void rplgpu_default_map_rule(rplgpu_map_rule_t *rule) {
+  if (!rule) return;
+  rule->min_observations = 2;
+  rule->occupied_percent = 10;
+  rule->mode = 0;
+}
+
+int32_t rplgpu_map_rule_check(const rplgpu_map_rule_t *rule) {
+  if (!rule || rule->min_observations == 0 || rule->occupied_percent > 100u || rule->mode > 1u)
+    return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+// d_t0: the per-scan time offsets of E6 for this call (the handle's, or the host door's own), or NULL
+static int32_t map_update_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                               const float *d_motion, const float *d_pose2d, const float *d_t0,
+                               const rplgpu_occ_grid_t *grid, uint32_t *d_counts, uint32_t *d_status) {
+  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
+  if (rc) return rc;
+  if (!p || !grid || !d_counts || group == 0) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_occ_grid_check(grid) != RPLGPU_OK) {
+    h->err = "rplgpu_map_update_dev: invalid rplgpu_occ_grid_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(d_counts) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
+    h->err = "rplgpu_map_update_dev: d_counts must be 8-byte aligned, d_status 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (B == 0) return RPLGPU_OK;
+  if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
+      (d_pose2d && !device_readable(h, d_pose2d, "d_pose2d")) || !device_readable(h, d_counts, "d_counts") ||
+      (d_status && !device_readable(h, d_status, "d_status")))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (d_t0 && !d_motion) {
+    h->err = "rplgpu_map_update_dev: scan time offsets are set (rplgpu_set_scan_time_offsets_dev) but d_motion is NULL";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
+    h->err = "ror_radius must be in (0, 1e6] m";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  group = std::min(group, B);  // as E8: "all sensors in one group" may be asked for with any group >= B
+  if ((uint64_t)group * std::min(n_stride, rpl::kMaxN) > (1ull << 24)) {
+    h->err = "rplgpu_map_update_dev: group x n_stride above 2^24 samples";
+    return RPLGPU_ERR_CAPACITY;
+  }
+  const uint32_t G = (B + group - 1u) / group;
+  RPL_HIP(h, hipSetDevice(h->device));
+  rpl::KParams kp = to_kparams(*p);
+  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
+  rpl::Tables T = tables_of(h);
+  T.scan_t0 = d_t0;
+  const rpl::OccK k = occ_kernel_args(*grid);
+  const uint32_t *mask = nullptr;
+  if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E9, E11 and E13 apply
+    RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
+                                    kMaskStride));
+    mask = h->d_rormask;
+  }
+  if (d_status) RPL_HIP(h, hipMemsetAsync(d_status, 0, (size_t)G * 4u, h->stream));
+  RPL_HIP(h, rpl::launch_map_walk(h->stream, d_nodes, n_stride, d_n_per_scan, B, group, kp, T, mask, kMaskStride,
+                                  d_motion, d_pose2d, k, d_counts, d_status));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_map_update_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                              const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                              const float *d_motion, const float *d_pose2d, const rplgpu_occ_grid_t *grid,
+                              uint32_t *d_counts, uint32_t *d_status) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  return map_update_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, h->scan_t0, grid,
+                         d_counts, d_status);
+}
+
+int32_t rplgpu_map_grid_dev(rplgpu_handle_t h, const uint32_t *d_counts, uint32_t width, uint32_t height,
+                            const rplgpu_map_rule_t *rule, const int8_t *d_prev, int8_t *d_grid,
+                            uint64_t grid_stride, uint32_t *d_cells) {
+  if (!h || !d_counts || !rule || !d_grid) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_map_rule_check(rule) != RPLGPU_OK) {
+    h->err = "rplgpu_map_grid_dev: invalid rplgpu_map_rule_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 || height > RPLGPU_MAX_OCC_DIM) {
+    h->err = "rplgpu_map_grid_dev: width and height must be 1 .. RPLGPU_MAX_OCC_DIM";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (grid_stride < (uint64_t)width * height || (grid_stride & 3u) || (reinterpret_cast<uintptr_t>(d_grid) & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_counts) & 7u) || (reinterpret_cast<uintptr_t>(d_cells) & 3u)) {
+    h->err = "rplgpu_map_grid_dev: grid_stride must be >= width * height and a multiple of 4, d_grid / d_cells 4-byte and d_counts 8-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_prev == d_grid) {
+    h->err = "rplgpu_map_grid_dev: d_prev must not be d_grid";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, d_counts, "d_counts") || (d_prev && !device_readable(h, d_prev, "d_prev")) ||
+      !device_readable(h, d_grid, "d_grid") || (d_cells && !device_readable(h, d_cells, "d_cells")))
+    return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  if (d_cells) RPL_HIP(h, hipMemsetAsync(d_cells, 0, 16u, h->stream));
+  RPL_HIP(h, rpl::launch_map_grid(h->stream, d_counts, width, height, rule->min_observations,
+                                  rule->occupied_percent, rule->mode, d_prev, d_grid, d_cells));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_apply_match_dev(rplgpu_handle_t h, const uint32_t *d_best, const rplgpu_scan_match_t *m,
+                               const float *d_pivot, const float *d_pose2d_in, uint32_t B, uint32_t group,
+                               uint32_t flags, float *d_pose2d_out, float *d_pivot_out) {
+  if (!h || !d_best || !m || !d_pose2d_out || group == 0 || flags > 1u) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_scan_match_check(m) != RPLGPU_OK) {
+    h->err = "rplgpu_apply_match_dev: invalid rplgpu_scan_match_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(d_best) & 3u) || (reinterpret_cast<uintptr_t>(d_pivot) & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_pose2d_in) & 3u) || (reinterpret_cast<uintptr_t>(d_pose2d_out) & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_pivot_out) & 3u)) {
+    h->err = "rplgpu_apply_match_dev: every pointer must be 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_pivot_out && d_pivot_out == d_pivot) {
+    h->err = "rplgpu_apply_match_dev: d_pivot_out must not be d_pivot (every scan of a group reads the pivot)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (B > h->max_b) {
+    h->err = "batch larger than max_batch given to rplgpu_create";
+    return RPLGPU_ERR_CAPACITY;
+  }
+  if (B == 0) return RPLGPU_OK;
+  if (!device_readable(h, d_best, "d_best") || (d_pivot && !device_readable(h, d_pivot, "d_pivot")) ||
+      (d_pose2d_in && !device_readable(h, d_pose2d_in, "d_pose2d_in")) ||
+      !device_readable(h, d_pose2d_out, "d_pose2d_out") ||
+      (d_pivot_out && !device_readable(h, d_pivot_out, "d_pivot_out")))
+    return RPLGPU_ERR_INVALID_ARG;
+  group = std::min(group, B);
+  const rpl::MatchK k{m->origin_x, m->origin_y, m->resolution, m->width, m->height,
+                      m->shift_x, m->shift_y, m->rot_steps};
+  rpl::MatchRot rot;  // by value, as k_match_score takes it
+  std::memset(&rot, 0, sizeof(rot));
+  if (rplgpu_scan_match_rotations(m, rot.cs) != RPLGPU_OK) return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_apply_match(h->stream, d_best, k, rot, d_pivot, d_pose2d_in, B, group, flags, d_pose2d_out,
+                                     d_pivot_out));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_map_update(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                          const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                          const float *motion, const float *pose2d, const float *t0, const rplgpu_occ_grid_t *grid,
+                          uint32_t *counts, uint32_t *status) {
+  if (!h || !nodes || !n_per_scan || !p || !grid || !counts || n_scans == 0 || n_stride == 0)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_occ_grid_check(grid) != RPLGPU_OK) {
+    h->err = "rplgpu_map_update: invalid rplgpu_occ_grid_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
+  RPL_HIP(h, hipSetDevice(h->device));
+  const size_t cells_n = (size_t)grid->width * grid->height;
+  const size_t nb = (size_t)n_scans * n_stride * 8u;
+  // one allocation per call (a convenience door, not the hot path): counts | nodes | lengths | motion | pose |
+  // t0 | status, every part 16-byte aligned
+  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  const size_t o_nodes = up16(8u * cells_n), o_len = o_nodes + up16(nb), o_mo = o_len + up16(4u * n_scans),
+               o_po = o_mo + up16(motion ? 16u * n_scans : 0), o_t0 = o_po + up16(pose2d ? 24u * n_scans : 0),
+               o_small = o_t0 + up16(t0 ? 4u * n_scans : 0), total = o_small + 16u;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_map_update: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t small = 0;
+  auto run = [&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(d, counts, 8u * cells_n, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_nodes, nodes, nb, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_len, n_per_scan, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (motion) RPL_HIP(h, hipMemcpyAsync(d + o_mo, motion, 16u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (pose2d) RPL_HIP(h, hipMemcpyAsync(d + o_po, pose2d, 24u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (t0) RPL_HIP(h, hipMemcpyAsync(d + o_t0, t0, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
+    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);
+    const int32_t rc = map_update_impl(
+        h, reinterpret_cast<const rplgpu_node_t *>(d + o_nodes), n_stride,
+        reinterpret_cast<const uint32_t *>(d + o_len), n_scans, n_scans, p,
+        motion ? reinterpret_cast<const float *>(d + o_mo) : nullptr,
+        pose2d ? reinterpret_cast<const float *>(d + o_po) : nullptr,
+        t0 ? reinterpret_cast<const float *>(d + o_t0) : nullptr, grid, reinterpret_cast<uint32_t *>(d), d_small);
+    if (rc) return rc;
+    RPL_HIP(h, hipMemcpyAsync(counts, d, 8u * cells_n, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(&small, d_small, 4, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;
+  if (status) *status = small;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_map_grid(rplgpu_handle_t h, const uint32_t *counts, uint32_t width, uint32_t height,
+                        const rplgpu_map_rule_t *rule, const int8_t *prev, int8_t *grid_out, uint32_t cells[4]) {
+  if (!h || !counts || !rule || !grid_out) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_map_rule_check(rule) != RPLGPU_OK) {
+    h->err = "rplgpu_map_grid: invalid rplgpu_map_rule_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 || height > RPLGPU_MAX_OCC_DIM) {
+    h->err = "rplgpu_map_grid: width and height must be 1 .. RPLGPU_MAX_OCC_DIM";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  const size_t cells_n = (size_t)width * height, stride = (cells_n + 3u) & ~(size_t)3u;
+  // one allocation per call: counts | grid | prev | cells, every part 16-byte aligned
+  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  const size_t o_grid = up16(8u * cells_n), o_prev = o_grid + up16(stride), o_small = o_prev + up16(prev ? stride : 0),
+               total = o_small + 16u;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_map_grid: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t small[4] = {0, 0, 0, 0};
+  auto run = [&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(d, counts, 8u * cells_n, hipMemcpyHostToDevice, h->stream));
+    if (prev) RPL_HIP(h, hipMemcpyAsync(d + o_prev, prev, cells_n, hipMemcpyHostToDevice, h->stream));
+    const int32_t rc = rplgpu_map_grid_dev(h, reinterpret_cast<const uint32_t *>(d), width, height, rule,
+                                           prev ? reinterpret_cast<const int8_t *>(d + o_prev) : nullptr,
+                                           reinterpret_cast<int8_t *>(d + o_grid), stride,
+                                           reinterpret_cast<uint32_t *>(d + o_small));
+    if (rc) return rc;
+    RPL_HIP(h, hipMemcpyAsync(grid_out, d + o_grid, cells_n, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d + o_small, 16, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;
+  if (cells) std::memcpy(cells, small, 16);
+  return RPLGPU_OK;
+}
+
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,

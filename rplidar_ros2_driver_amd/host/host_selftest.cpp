@@ -264,6 +264,33 @@ int main(int argc, char **argv) {
     }
     std::printf("scan match: best %u at (k, j, i) = (%d, %d, %d), %u at the prior\n", mr.score, mr.k, mr.j, mr.i,
                 mr.score_at_prior);
+    // E14: the three rays of the E11 leg added twice into a count map.  Per call the row of the sensor gets
+    // misses 3 3 2 2 1 1 (the whole ray beyond obstacle_max leaves its end cell 4 alone, the cut one counts its
+    // end cell 5) and one hit in cell 2; after two calls the default rule (2 observations, 10 %) gives the E11 row.
+    std::vector<uint32_t> counts;
+    uint32_t ustatus = 99;
+    for (int call = 0; call < 2; ++call) {
+      if (!path.update_map(step, rplgpu_host::ScanConfig(), og, nullptr, nullptr, nullptr, counts, &ustatus)) {
+        std::fprintf(stderr, "map update failed: %s\n", path.last_error().c_str());
+        return 13;
+      }
+    }
+    static const uint32_t row_want[16] = {6, 0, 6, 0, 4, 2, 4, 0, 2, 0, 2, 0, 0, 0, 0, 0};
+    rplgpu_map_rule_t rule;
+    rplgpu_default_map_rule(&rule);
+    OccupancyGrid map_msg;
+    uint32_t mcells[4] = {9, 9, 9, 9};
+    if (!path.fill_map_grid(counts, og, rule, map_msg, mcells)) {
+      std::fprintf(stderr, "map grid failed: %s\n", path.last_error().c_str());
+      return 14;
+    }
+    if (counts.size() != 48 || std::memcmp(&counts[16], row_want, 64) != 0 || ustatus != 0 ||
+        map_msg.data.size() != 24 || std::memcmp(map_msg.data.data(), want, 24) != 0 || mcells[0] != 18 ||
+        mcells[1] != 5 || mcells[2] != 1 || mcells[3] != 0 || rplgpu_map_rule_check(&rule) != RPLGPU_OK) {
+      std::fprintf(stderr, "map update / map grid: wrong answer\n");
+      return 15;
+    }
+    std::printf("map: 2 x 3 rays, cells -1/0/100/other = %u/%u/%u/%u\n", mcells[0], mcells[1], mcells[2], mcells[3]);
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

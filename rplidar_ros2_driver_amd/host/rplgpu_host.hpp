@@ -24,6 +24,8 @@
 //         -> rplgpu_host::ScanPath::inflate_grid(grid_msg, inflation, costmap_msg)  (E12)
 //   mat the localisation side's loop (a correlative scan matcher's search window over a likelihood field):
 //         -> rplgpu_host::ScanPath::match_scans(scans, ..., field_msg, window, result)  (E13)
+//   map the mapping side's loop (a map that many time steps vote on, each at its matched pose):
+//         -> rplgpu_host::ScanPath::update_map(scans, ..., counts) and fill_map_grid(counts, ..., grid_msg)  (E14)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -433,6 +435,68 @@ class ScanPath {
     result.points = best[4];
     result.score_at_prior = best[5];
     result.ties = best[6];
+    return true;
+  }
+
+  // ext E14 (include/rplgpu_msg.h): the scans of ONE time step ADDED into a persistent hit / miss count map at the
+  // poses given (e.g. the ones match_scans corrected) — what a mapper's map update does per accepted scan.
+  // `counts` holds two words per cell (misses, hits); any other size than 2 x width x height starts a zeroed map.
+  // pose2d / motion / t0 as in fill_occupancy_grid.
+  template <class NodeT>
+  bool update_map(const std::vector<std::vector<NodeT>> &scans, const ScanConfig &cfg, const rplgpu_occ_grid_t &grid,
+                  const float *pose2d, const float *motion, const float *t0, std::vector<uint32_t> &counts,
+                  uint32_t *status = nullptr) {
+    if (scans.empty()) return false;
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    size_t stride = 1;
+    for (const auto &s : scans) stride = s.size() > stride ? s.size() : stride;
+    if (stride > max_n_) return fail("scan larger than the configured capacity");
+    occ_nodes_.assign(scans.size() * stride, rplgpu_node_t{});
+    occ_len_.resize(scans.size());
+    for (size_t b = 0; b < scans.size(); ++b) {
+      if (!scans[b].empty()) std::memcpy(&occ_nodes_[b * stride], scans[b].data(), scans[b].size() * 8);
+      occ_len_[b] = static_cast<uint32_t>(scans[b].size());
+    }
+    const size_t n_words = 2 * static_cast<size_t>(grid.width) * grid.height;
+    if (n_words == 0) return fail("update_map: the grid has no cells");
+    if (counts.size() != n_words) counts.assign(n_words, 0u);
+    const rplgpu_params_t p = cfg.to_params();
+    if (rplgpu_map_update(h_, occ_nodes_.data(), static_cast<uint32_t>(stride), occ_len_.data(),
+                          static_cast<uint32_t>(scans.size()), &p, motion, pose2d, t0, &grid, counts.data(),
+                          status) != RPLGPU_OK)
+      return note_error();
+    return true;
+  }
+
+  // ext E14: the count map through the cell rule into a nav_msgs/OccupancyGrid-shaped message, which inflate_grid,
+  // match_scans and fill_occupancy_grid (as the previous grid) take.  `grid_msg.data` of the right size is the
+  // previous grid (cells seen fewer than rule.min_observations times keep their value); any other size starts
+  // from unknown (-1).  cells (optional): result cells that are -1, 0, 100 and anything else.
+  template <class OccupancyGridT>
+  bool fill_map_grid(const std::vector<uint32_t> &counts, const rplgpu_occ_grid_t &grid,
+                     const rplgpu_map_rule_t &rule, OccupancyGridT &grid_msg, uint32_t cells[4] = nullptr) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    const size_t n_cells = static_cast<size_t>(grid.width) * grid.height;
+    if (n_cells == 0 || counts.size() != 2 * n_cells) return fail("fill_map_grid: counts is not 2 x width x height");
+    const bool has_prev = grid_msg.data.size() == n_cells;
+    if (has_prev) occ_prev_.assign(grid_msg.data.begin(), grid_msg.data.end());
+    occ_out_.resize(n_cells);
+    if (rplgpu_map_grid(h_, counts.data(), grid.width, grid.height, &rule, has_prev ? occ_prev_.data() : nullptr,
+                        occ_out_.data(), cells) != RPLGPU_OK)
+      return note_error();
+    grid_msg.info.resolution = grid.resolution;
+    grid_msg.info.width = grid.width;
+    grid_msg.info.height = grid.height;
+    grid_msg.info.origin.position.x = grid.origin_x;
+    grid_msg.info.origin.position.y = grid.origin_y;
+    grid_msg.info.origin.position.z = 0.0;
+    grid_msg.info.origin.orientation.x = 0.0;
+    grid_msg.info.origin.orientation.y = 0.0;
+    grid_msg.info.origin.orientation.z = 0.0;
+    grid_msg.info.origin.orientation.w = 1.0;
+    grid_msg.data.assign(occ_out_.begin(), occ_out_.begin() + n_cells);
     return true;
   }
 
