@@ -693,6 +693,94 @@ int32_t rplgpu_map_update(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_
 int32_t rplgpu_map_grid(rplgpu_handle_t h, const uint32_t *counts, uint32_t width, uint32_t height,
                         const rplgpu_map_rule_t *rule, const int8_t *prev, int8_t *grid_out, uint32_t cells[4]);
 
+/* ---- E15: a list of arbitrary poses weighed against a likelihood field (row 4; the localisation side's particle
+ * weights) ----
+ * What AMCL, the localisation reader among E11's three, does with a time step's scans and a map: a particle filter
+ * asks E13's question not on a lattice around one prior but at a LIST of arbitrary poses, thousands of them,
+ * anywhere on the map and at any heading.  Global localisation, recovery after a kidnap and seeding E13 with a
+ * prior worth refining have the same shape.  The field is what E13 takes (rplgpu_inflate_grids_dev with a
+ * caller-made table over an E11 or E14 grid), and the weight of a pose is E13's score: the sum of the field bytes
+ * under the points.  That sum is AMCL's form too; the per-beam term is whatever monotone function the caller wrote
+ * into the table.  poses x points look-ups per time step, all of them on the device, which is why nothing is
+ * sub-sampled here.  Nothing in the reference weighs poses, so these rules ARE the definition (parity unpinned, as
+ * E5-E14).  After the float32 pose transform everything is integers: the result depends on no order. */
+#define RPLGPU_MAX_POSES 1048576u
+typedef struct rplgpu_pose_score {
+  float    origin_x, origin_y;   /* the field's grid: as rplgpu_occ_grid_t / rplgpu_scan_match_t */
+  float    resolution;
+  uint32_t width, height;        /* 1 .. RPLGPU_MAX_OCC_DIM */
+} rplgpu_pose_score_t;
+/* E11's default grid (0.05 m, 1024 x 1024 cells, origin (-25.6, -25.6)) */
+void rplgpu_default_pose_score(rplgpu_pose_score_t *s);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL, a value that is not finite, resolution <= 0
+ * or a dimension of 0 or above RPLGPU_MAX_OCC_DIM.  The device path uses this function. */
+int32_t rplgpu_pose_score_check(const rplgpu_pose_score_t *s);
+/* Host only.  THE POSE LIST: n poses (x, y, theta), 3 doubles each at xyt, become 4 floats each at poses_out:
+ *   ((float)cos(theta), (float)sin(theta), (float)x, (float)y),
+ * cos and sin taken in fp64 and rounded once; theta == 0 gives exactly (1, 0).  A value that is not finite is
+ * passed on as it rounds (the device defines such a pose, see below).  RPLGPU_ERR_INVALID_ARG for n above
+ * RPLGPU_MAX_POSES or a NULL pointer with n > 0.  A caller may fill the four floats itself: any (c, s) is defined. */
+int32_t rplgpu_pose_list(const double *xyt, uint32_t n, float *poses_out);
+/* POINTS: those of rplgpu_occupancy_grid_dev, from the same float32 operations — E1 (E5 too with p->ror_enable),
+ * E2 (p->inverted honoured), E6 de-skew from d_motion with the offsets of rplgpu_set_scan_time_offsets_dev
+ * (offsets set and d_motion NULL: refused), the planar pose d_pose2d — here each sensor's MOUNT pose in the base
+ * frame (E9's use of it; NULL: identity), so the points are in the base frame and a pose of the list is the base in
+ * the field's frame.  Groups as E8 / E9 / E11 / E13 (group clamped to B).  A point whose x or y is not finite is
+ * ignored and sets no status bit.
+ * POSE q of group g, q in [0, P): (c, s, tx, ty) = the four floats at d_poses + g_p * pose_stride + 4 q, g_p = g
+ * when poses_per_group is not 0, else 0 (one list serves every time step).  pose_stride is counted in floats, is
+ * >= 4 P and a multiple of 4; d_poses is 16-byte aligned.  The device evaluates no trigonometric function and does
+ * not check c*c + s*s = 1: any matrix [c -s; s c] is defined (a scale, the zero matrix).  Per point (x, y), float32,
+ * no FMA, each product rounded, then the difference or sum, then the translation:
+ *   rx = (c*x - s*y) + tx;   ry = (s*x + c*y) + ty
+ *   (cx, cy) = the E11 CELL of (rx, ry) in the spec's grid (same rule, same IEEE divides);  a position with no cell
+ *   (NaN or Inf, e.g. from a pose entry that is not finite, or a magnitude >= 1048576 cells) contributes nothing
+ *   and sets RPLGPU_SCAN_CELL_RANGE in d_status[g];
+ *   f = max((int8)d_field[g_f * field_stride + cy * width + cx], 0);  a cell outside [0, width) x [0, height)
+ *   gives 0, and so does an unknown (negative) byte;  g_f = g when field_per_group is not 0, else 0.
+ * WEIGHT: d_weights[g * weight_stride + q] = the sum of f over the group's points, uint32; weight_stride >= P, in
+ * words; words at and beyond P of a group are never changed.  With group * n_stride <= 2^24 (otherwise
+ * RPLGPU_ERR_INVALID_ARG, as E13) 127 * points < 2^32: no sum wraps.
+ * RESULT: eight 32-bit words per group at d_result + 8 g:
+ *   0      the largest weight of the group's list
+ *   1      the smallest q that has it
+ *   2      the number of poses that have it (1: unambiguous)
+ *   3      the number of poses whose weight is 0
+ *   4      the number of the group's finite points
+ *   5      the weight of pose 0 (by convention the caller's odometry pose, as E13's word 5)
+ *   6, 7   the sum of all P weights, low and high word (the filter's normaliser: P * 127 * 2^24 needs 64 bits)
+ * A group without points has every weight 0: words 0 and 1 are 0, words 2 and 3 are P.
+ * TWO IDENTITIES follow from the rules and hold independent kernels to each other:
+ *   (a) with d_pivot NULL, candidate (k, 0, 0) of rplgpu_match_scans_dev sees exactly the positions of the pose
+ *       (c_k, s_k, 0, 0) of rplgpu_scan_match_rotations: on the same points and field, with the table's 2K + 1
+ *       entries as the list, weights[k + K] == score[k][0][0] for every k;
+ *   (b) for an E11 spec with range_min 0 in which every kept point lies within obstacle_max of its sensor, the pose
+ *       (1, 0, 0, 0) on the same d_pose2d has the weight  sum over cells of hits[cell] * max(field[cell], 0),  hits
+ *       from rplgpu_map_update_dev on a zeroed map.
+ * d_field 4-byte aligned, field_stride >= width * height and a multiple of 4 (E13's rules: the calls chain); the
+ * field and the pose list are only read.  d_weights and d_result are required and 4-byte aligned; the weights are
+ * the call's own scratch and result (as E13's volume is): nothing is stored on the handle, nothing is copied from
+ * pageable memory.  d_status[g] (optional): RPLGPU_SCAN_OUT_TRUNCATED as E9 / E11 / E13 and RPLGPU_SCAN_CELL_RANGE
+ * as above.  The argument and capacity checks of rplgpu_cloud_fused_voxel_dev; RPLGPU_ERR_INVALID_ARG also for a
+ * spec the check refuses, group = 0, P = 0 or above RPLGPU_MAX_POSES, a missing or misaligned d_poses / d_field /
+ * d_weights / d_result, a misaligned d_status, the stride rules above, and offsets set with d_motion NULL.  A
+ * refused call changes no output.  Asynchronous on the handle's stream. */
+int32_t rplgpu_score_poses_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                               const float *d_motion, const float *d_pose2d, const rplgpu_pose_score_t *s,
+                               const float *d_poses, uint32_t P, uint64_t pose_stride, uint32_t poses_per_group,
+                               const int8_t *d_field, uint64_t field_stride, uint32_t field_per_group,
+                               uint32_t *d_weights, uint64_t weight_stride, uint32_t *d_result, uint32_t *d_status);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp): n_scans <= max_batch scans as
+ * rplgpu_occupancy_grid takes them; poses: 4 P floats as rplgpu_pose_list writes them; field: width * height
+ * bytes; weights_out (optional): P words; result: 8 words; status (optional): 1 word.  Allocates its device
+ * buffers per call and returns when the results are in place. */
+int32_t rplgpu_score_poses(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                           const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                           const float *motion, const float *pose2d, const float *t0,
+                           const rplgpu_pose_score_t *s, const float *poses, uint32_t P, const int8_t *field,
+                           uint32_t *weights_out, uint32_t result[8], uint32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,7 @@ MAX_FILTER_WINDOW = 64   # RPLGPU_MAX_FILTER_WINDOW (include/rplgpu_msg.h)
 MAX_OCC_DIM = 4096       # RPLGPU_MAX_OCC_DIM (include/rplgpu_msg.h)
 MAX_OCC_STEPS = 8192     # RPLGPU_MAX_OCC_STEPS (include/rplgpu_msg.h)
 MAX_INFLATION_CELLS = 64  # RPLGPU_MAX_INFLATION_CELLS (include/rplgpu_msg.h)
+MAX_POSES = 1048576       # RPLGPU_MAX_POSES (include/rplgpu_msg.h)
 
 SL_RESULT_OK = 0
 SL_RESULT_OPERATION_FAIL = 0x80008001
@@ -130,6 +131,11 @@ ABI_SYMBOLS = [
     "rplgpu_apply_match_dev",
     "rplgpu_map_update",
     "rplgpu_map_grid",
+    "rplgpu_default_pose_score",
+    "rplgpu_pose_score_check",
+    "rplgpu_pose_list",
+    "rplgpu_score_poses_dev",
+    "rplgpu_score_poses",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -363,6 +369,29 @@ class MapRule(C.Structure):
         return r
 
 
+class PoseScore(C.Structure):
+    """Mirror of ``rplgpu_pose_score_t`` (E15: a list of poses weighed against a likelihood field)."""
+
+    _fields_ = [
+        ("origin_x", C.c_float),
+        ("origin_y", C.c_float),
+        ("resolution", C.c_float),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "PoseScore":
+        """The library's own defaults (``rplgpu_default_pose_score``), then the overrides."""
+        s = cls()
+        load_library().rplgpu_default_pose_score(C.byref(s))
+        for k, v in kw.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -544,6 +573,14 @@ def load_library() -> C.CDLL:
     lib.rplgpu_map_update.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp, C.POINTER(OccGrid),
                                       vp, vp]
     lib.rplgpu_map_grid.argtypes = [vp, vp, u32, u32, C.POINTER(MapRule), vp, vp, vp]
+    lib.rplgpu_default_pose_score.argtypes = [C.POINTER(PoseScore)]
+    lib.rplgpu_default_pose_score.restype = None
+    lib.rplgpu_pose_score_check.argtypes = [C.POINTER(PoseScore)]
+    lib.rplgpu_pose_list.argtypes = [vp, u32, vp]
+    lib.rplgpu_score_poses_dev.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp,
+                                           C.POINTER(PoseScore), vp, u32, u64, u32, vp, u64, u32, vp, u64, vp, vp]
+    lib.rplgpu_score_poses.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp,
+                                       C.POINTER(PoseScore), vp, u32, vp, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -944,6 +981,45 @@ class RplGpu:
             self._h, counts.ctypes.data, W, H, C.byref(rule), 0 if prev is None else prev.ctypes.data,
             out.ctypes.data, cells.ctypes.data))
         return out, tuple(int(c) for c in cells)
+
+    def score_poses_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int, params: Params,
+                        d_motion: int, d_pose2d: int, spec: PoseScore, d_poses: int, P: int, pose_stride: int,
+                        poses_per_group: int, d_field: int, field_stride: int, field_per_group: int, d_weights: int,
+                        weight_stride: int, d_result: int, d_status: int = 0):
+        """E15: per group of scans the weights (uint32, P words, weight_stride apart) of the P poses (c, s, tx, ty)
+        at d_poses over the int8 field(s) at d_field, and eight result words at d_result + 8 g."""
+        self._check(self._lib.rplgpu_score_poses_dev(
+            self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d, C.byref(spec),
+            d_poses, P, pose_stride, poses_per_group, d_field, field_stride, field_per_group, d_weights,
+            weight_stride, d_result, d_status))
+
+    def score_poses(self, scans: np.ndarray, lens, params: Params, spec: PoseScore, poses: np.ndarray,
+                    field: np.ndarray, motion=None, pose2d=None, t0=None, want_weights: bool = True):
+        """E15, one group, host buffers: scans (S, n) NODE_DTYPE, poses (P, 4) float32 as ``pose_list`` makes them
+        and a (height, width) int8 field -> ``(weights (P,) uint32 or None, result (8,) uint32, status)``."""
+        scans = np.ascontiguousarray(scans)
+        if scans.dtype != NODE_DTYPE or scans.ndim != 2:
+            raise TypeError("scans must be a 2-D array of abi.NODE_DTYPE")
+        field = np.ascontiguousarray(field, np.int8)
+        if field.shape != (spec.height, spec.width):
+            raise TypeError("field must be a (height, width) int8 array")
+        poses = np.ascontiguousarray(poses, np.float32)
+        if poses.ndim != 2 or poses.shape[1] != 4:
+            raise TypeError("poses must be a (P, 4) float32 array")
+        S, n = scans.shape
+        P = len(poses)
+        lens = np.ascontiguousarray(lens, np.uint32)
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
+        motion, pose2d, t0 = f32(motion), f32(pose2d), f32(t0)
+        weights = np.zeros(P, np.uint32) if want_weights else None
+        result = np.zeros(8, np.uint32)
+        status = np.zeros(1, np.uint32)
+        ptr = lambda a: 0 if a is None else a.ctypes.data  # noqa: E731
+        self._check(self._lib.rplgpu_score_poses(
+            self._h, scans.ctypes.data, n, lens.ctypes.data, S, C.byref(params), ptr(motion), ptr(pose2d), ptr(t0),
+            C.byref(spec), poses.ctypes.data, P, field.ctypes.data, ptr(weights), result.ctypes.data,
+            status.ctypes.data))
+        return weights, result, int(status[0])
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -1405,3 +1481,22 @@ def scan_match_rotations(match: ScanMatch) -> np.ndarray:
 def scan_match_volume(match: ScanMatch) -> int:
     """Host only: the words of one group's score volume, (2K + 1)(2Ty + 1)(2Tx + 1); 0 for an invalid spec."""
     return int(load_library().rplgpu_scan_match_volume(C.byref(match)))
+
+
+def pose_score_check(spec: PoseScore) -> None:
+    """Host only: validates an E15 spec by the library's own rplgpu_pose_score_check; raises
+    RplGpuError(ERR_INVALID_ARG) for a spec the device path would refuse."""
+    rc = load_library().rplgpu_pose_score_check(C.byref(spec))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_pose_score_check")
+
+
+def pose_list(xyt) -> np.ndarray:
+    """Host only: poses (P, 3) float64 (x, y, theta) -> the (P, 4) float32 list (cos, sin, x, y) that
+    score_poses_dev takes, by the library's own rplgpu_pose_list."""
+    xyt = np.ascontiguousarray(xyt, np.float64).reshape(-1, 3)
+    out = np.zeros((len(xyt), 4), np.float32)
+    rc = load_library().rplgpu_pose_list(xyt.ctypes.data, len(xyt), out.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_pose_list")
+    return out

@@ -333,4 +333,24 @@ hipError_t launch_apply_match(hipStream_t s, const uint32_t *best, const MatchK 
                               const float *pivot, const float *pose_in, uint32_t B, uint32_t group, uint32_t flags,
                               float *pose_out, float *pivot_out);
 
+// E15: a list of arbitrary poses weighed against a likelihood field (rpl_pose.hip, include/rplgpu_msg.h).  The
+// weights are the call's scratch and result: prepare zeroes the P weights and the eight result words of every
+// group, score adds the field values under the points into the weights (and the finite points into result word
+// 4), best reduces the weights to the other seven words.
+struct PoseK {  // a checked rplgpu_pose_score_t
+  float origin_x, origin_y, resolution;
+  uint32_t width, height;
+};
+hipError_t launch_pose_prepare(hipStream_t s, uint32_t *weights, unsigned long long weight_stride, uint32_t G,
+                               uint32_t P, uint32_t *result);
+hipError_t launch_pose_score(hipStream_t s, const void *nodes, uint32_t n_stride, const uint32_t *n_per_scan,
+                             uint32_t B, uint32_t group, const KParams &p, const Tables &T,
+                             const uint32_t *keepmask, uint32_t mask_stride, const float *motion,
+                             const float *pose2d, const PoseK &k, const float *poses, uint32_t P,
+                             unsigned long long pose_stride, uint32_t poses_per_group, const int8_t *field,
+                             unsigned long long field_stride, uint32_t field_per_group, uint32_t *weights,
+                             unsigned long long weight_stride, uint32_t *result, uint32_t *status);
+hipError_t launch_pose_best(hipStream_t s, const uint32_t *weights, unsigned long long weight_stride, uint32_t G,
+                            uint32_t P, uint32_t *result);
+
 }  // namespace rpl

@@ -2229,6 +2229,196 @@ int32_t rplgpu_map_grid(rplgpu_handle_t h, const uint32_t *counts, uint32_t widt
   return RPLGPU_OK;
 }
 
+// ---- E15: a list of arbitrary poses weighed against a likelihood field (include/rplgpu_msg.h) ------------------
+
+void rplgpu_default_pose_score(rplgpu_pose_score_t *s) {
+  if (!s) return;
+  s->origin_x = -25.6f;
+  s->origin_y = -25.6f;
+  s->resolution = 0.05f;
+  s->width = 1024;
+  s->height = 1024;
+}
+
+int32_t rplgpu_pose_score_check(const rplgpu_pose_score_t *s) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(s->origin_x) || !std::isfinite(s->origin_y) || !std::isfinite(s->resolution))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!(s->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  if (s->width == 0 || s->width > RPLGPU_MAX_OCC_DIM || s->height == 0 || s->height > RPLGPU_MAX_OCC_DIM)
+    return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_pose_list(const double *xyt, uint32_t n, float *poses_out) {
+  if (n > RPLGPU_MAX_POSES || (n && (!xyt || !poses_out))) return RPLGPU_ERR_INVALID_ARG;
+  for (uint32_t q = 0; q < n; ++q) {
+    const double th = xyt[3u * q + 2u];
+    poses_out[4u * q] = th == 0.0 ? 1.0f : (float)std::cos(th);
+    poses_out[4u * q + 1u] = th == 0.0 ? 0.0f : (float)std::sin(th);  // (+0 for theta = -0 too)
+    poses_out[4u * q + 2u] = (float)xyt[3u * q];
+    poses_out[4u * q + 3u] = (float)xyt[3u * q + 1u];
+  }
+  return RPLGPU_OK;
+}
+
+// d_t0: the per-scan time offsets of E6 for this call (the handle's, or the host door's own), or NULL
+static int32_t pose_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                         const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                         const float *d_motion, const float *d_pose2d, const float *d_t0,
+                         const rplgpu_pose_score_t *s, const float *d_poses, uint32_t P, uint64_t pose_stride,
+                         uint32_t poses_per_group, const int8_t *d_field, uint64_t field_stride,
+                         uint32_t field_per_group, uint32_t *d_weights, uint64_t weight_stride, uint32_t *d_result,
+                         uint32_t *d_status) {
+  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
+  if (rc) return rc;
+  if (!p || !s || !d_poses || !d_field || !d_weights || !d_result || group == 0) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_score_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_score_poses_dev: invalid rplgpu_pose_score_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_score_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (pose_stride < 4ull * P || (pose_stride & 3u) || (reinterpret_cast<uintptr_t>(d_poses) & 15u)) {
+    h->err = "rplgpu_score_poses_dev: pose_stride must be >= 4 P floats and a multiple of 4, d_poses 16-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (field_stride < (uint64_t)s->width * s->height || (field_stride & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_field) & 3u)) {
+    h->err = "rplgpu_score_poses_dev: field_stride must be >= width * height and a multiple of 4, d_field 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (weight_stride < P || (reinterpret_cast<uintptr_t>(d_weights) & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_result) & 3u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
+    h->err = "rplgpu_score_poses_dev: weight_stride must be >= P, d_weights / d_result / d_status 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (B == 0) return RPLGPU_OK;
+  if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
+      (d_pose2d && !device_readable(h, d_pose2d, "d_pose2d")) || !device_readable(h, d_poses, "d_poses") ||
+      !device_readable(h, d_field, "d_field") || !device_readable(h, d_weights, "d_weights") ||
+      !device_readable(h, d_result, "d_result") || (d_status && !device_readable(h, d_status, "d_status")))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (d_t0 && !d_motion) {
+    h->err = "rplgpu_score_poses_dev: scan time offsets are set (rplgpu_set_scan_time_offsets_dev) but d_motion is NULL";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
+    h->err = "ror_radius must be in (0, 1e6] m";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  group = std::min(group, B);  // as E8: "all sensors in one time step" may be asked for with any group >= B
+  if ((uint64_t)group * n_stride > (1ull << 24)) {  // 127 x points stays below 2^32: no weight wraps
+    h->err = "rplgpu_score_poses_dev: group x n_stride above 2^24 samples";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint32_t G = (B + group - 1u) / group;
+  if ((uint64_t)G * ((P + 255u) / 256u) > 0x7FFFFFFFull) {  // (launch_pose_prepare's grid; before anything is queued)
+    h->err = "rplgpu_score_poses_dev: groups x P too large for one call";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const rpl::PoseK k{s->origin_x, s->origin_y, s->resolution, s->width, s->height};
+  RPL_HIP(h, hipSetDevice(h->device));
+  rpl::KParams kp = to_kparams(*p);
+  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
+  rpl::Tables T = tables_of(h);
+  T.scan_t0 = d_t0;
+  const uint32_t *mask = nullptr;
+  if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E9, E11 and E13 apply
+    RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
+                                    kMaskStride));
+    mask = h->d_rormask;
+  }
+  if (d_status) RPL_HIP(h, hipMemsetAsync(d_status, 0, (size_t)G * 4u, h->stream));
+  RPL_HIP(h, rpl::launch_pose_prepare(h->stream, d_weights, weight_stride, G, P, d_result));
+  RPL_HIP(h, rpl::launch_pose_score(h->stream, d_nodes, n_stride, d_n_per_scan, B, group, kp, T, mask, kMaskStride,
+                                    d_motion, d_pose2d, k, d_poses, P, pose_stride, poses_per_group, d_field,
+                                    field_stride, field_per_group, d_weights, weight_stride, d_result, d_status));
+  RPL_HIP(h, rpl::launch_pose_best(h->stream, d_weights, weight_stride, G, P, d_result));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_score_poses_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                               const float *d_motion, const float *d_pose2d, const rplgpu_pose_score_t *s,
+                               const float *d_poses, uint32_t P, uint64_t pose_stride, uint32_t poses_per_group,
+                               const int8_t *d_field, uint64_t field_stride, uint32_t field_per_group,
+                               uint32_t *d_weights, uint64_t weight_stride, uint32_t *d_result,
+                               uint32_t *d_status) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  return pose_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, h->scan_t0, s, d_poses, P,
+                   pose_stride, poses_per_group, d_field, field_stride, field_per_group, d_weights, weight_stride,
+                   d_result, d_status);
+}
+
+int32_t rplgpu_score_poses(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                           const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                           const float *motion, const float *pose2d, const float *t0,
+                           const rplgpu_pose_score_t *s, const float *poses, uint32_t P, const int8_t *field,
+                           uint32_t *weights_out, uint32_t result[8], uint32_t *status) {
+  if (!h || !nodes || !n_per_scan || !p || !s || !poses || !field || !result || n_scans == 0 || n_stride == 0)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_score_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_score_poses: invalid rplgpu_pose_score_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_score_poses: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
+  RPL_HIP(h, hipSetDevice(h->device));
+  const size_t cells_n = (size_t)s->width * s->height, stride = (cells_n + 3u) & ~(size_t)3u;
+  const size_t nb = (size_t)n_scans * n_stride * 8u;
+  // one allocation per call (a convenience door, not the hot path): field | poses | weights | nodes | lengths |
+  // motion | pose | t0 | result + status, every part 16-byte aligned
+  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  const size_t o_ps = up16(stride), o_wt = o_ps + up16(16u * (size_t)P), o_nodes = o_wt + up16(4u * (size_t)P),
+               o_len = o_nodes + up16(nb), o_mo = o_len + up16(4u * n_scans),
+               o_po = o_mo + up16(motion ? 16u * n_scans : 0), o_t0 = o_po + up16(pose2d ? 24u * n_scans : 0),
+               o_small = o_t0 + up16(t0 ? 4u * n_scans : 0), total = o_small + 48u;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_score_poses: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t small[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  auto run = [&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(d, field, cells_n, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_ps, poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_nodes, nodes, nb, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_len, n_per_scan, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (motion) RPL_HIP(h, hipMemcpyAsync(d + o_mo, motion, 16u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (pose2d) RPL_HIP(h, hipMemcpyAsync(d + o_po, pose2d, 24u * n_scans, hipMemcpyHostToDevice, h->stream));
+    if (t0) RPL_HIP(h, hipMemcpyAsync(d + o_t0, t0, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
+    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);
+    const int32_t rc = pose_impl(
+        h, reinterpret_cast<const rplgpu_node_t *>(d + o_nodes), n_stride,
+        reinterpret_cast<const uint32_t *>(d + o_len), n_scans, n_scans, p,
+        motion ? reinterpret_cast<const float *>(d + o_mo) : nullptr,
+        pose2d ? reinterpret_cast<const float *>(d + o_po) : nullptr,
+        t0 ? reinterpret_cast<const float *>(d + o_t0) : nullptr, s, reinterpret_cast<const float *>(d + o_ps), P,
+        4ull * P, 0, reinterpret_cast<const int8_t *>(d), stride, 0, reinterpret_cast<uint32_t *>(d + o_wt), P,
+        d_small, d_small + 8);
+    if (rc) return rc;
+    if (weights_out)
+      RPL_HIP(h, hipMemcpyAsync(weights_out, d + o_wt, 4u * (size_t)P, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d_small, 36, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;
+  std::memcpy(result, small, 32);
+  if (status) *status = small[8];
+  return RPLGPU_OK;
+}
+
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,

@@ -291,6 +291,28 @@ int main(int argc, char **argv) {
       return 15;
     }
     std::printf("map: 2 x 3 rays, cells -1/0/100/other = %u/%u/%u/%u\n", mcells[0], mcells[1], mcells[2], mcells[3]);
+    // E15 against the E12 costmap, whose row of the sensor is 36 99 100 99 36 0 -1 -1: the three returns at 2, 4 and
+    // 7 m on an identity mount.  At the base pose (0, 0, 0) they lie in cells 2, 4 and 7: 100 + 36 + 0 (unknown);
+    // one metre back in cells 1, 3, 6: 99 + 99 + 0; two metres back in cells 0, 2, 5: 36 + 100 + 0; turned by pi they
+    // leave the grid.  Best 198 at pose 1, alone; one pose weighs nothing; the sum is 470.
+    const std::vector<double> xyt = {0.0, 0.0, 0.0, -1.0, 0.0, 0.0, -2.0, 0.0, 0.0, 0.0, 0.0, 3.14159265358979323846};
+    std::vector<uint32_t> weights;
+    rplgpu_host::ScanPath::PoseResult pr;
+    uint32_t pstatus = 99;
+    if (!path.score_poses(step, rplgpu_host::ScanConfig(), nullptr, nullptr, nullptr, cost_msg, xyt, weights, pr,
+                          &pstatus)) {
+      std::fprintf(stderr, "pose score failed: %s\n", path.last_error().c_str());
+      return 16;
+    }
+    if (weights.size() != 4 || weights[0] != 136 || weights[1] != 198 || weights[2] != 136 || weights[3] != 0 ||
+        pr.best != 198 || pr.best_index != 1 || pr.ties != 1 || pr.zeros != 1 || pr.points != 3 ||
+        pr.weight_of_first != 136 || pr.sum != 470 || pstatus != 0) {
+      std::fprintf(stderr, "pose score: wrong answer (%u at %u, %u ties, %u zeros, %u points, sum %llu)\n", pr.best,
+                   pr.best_index, pr.ties, pr.zeros, pr.points, static_cast<unsigned long long>(pr.sum));
+      return 17;
+    }
+    std::printf("pose score: best %u at pose %u of 4, sum %llu\n", pr.best, pr.best_index,
+                static_cast<unsigned long long>(pr.sum));
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

@@ -26,6 +26,8 @@
 //         -> rplgpu_host::ScanPath::match_scans(scans, ..., field_msg, window, result)  (E13)
 //   map the mapping side's loop (a map that many time steps vote on, each at its matched pose):
 //         -> rplgpu_host::ScanPath::update_map(scans, ..., counts) and fill_map_grid(counts, ..., grid_msg)  (E14)
+//   pf  the localisation side's other loop (a particle filter's sensor update over a list of arbitrary poses):
+//         -> rplgpu_host::ScanPath::score_poses(scans, ..., field_msg, xyt, weights, result)  (E15)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -438,6 +440,65 @@ class ScanPath {
     return true;
   }
 
+  // ext E15 (include/rplgpu_msg.h): a list of poses of the BASE weighed against `field_msg` by the scans of ONE time
+  // step — what a particle filter's sensor update does.  xyt: (x, y, theta) per pose, in the field's frame (they go
+  // through rplgpu_pose_list); pose2d: every sensor's MOUNT pose in the base frame (null: identity); the grid comes
+  // from field_msg.info (origin orientation must be the identity).  weights: one per pose; result: the eight
+  // words of the header's RESULT table.
+  struct PoseResult {
+    uint32_t best = 0, best_index = 0, ties = 0, zeros = 0, points = 0, weight_of_first = 0;
+    uint64_t sum = 0;
+  };
+  template <class NodeT, class OccupancyGridT>
+  bool score_poses(const std::vector<std::vector<NodeT>> &scans, const ScanConfig &cfg, const float *pose2d,
+                   const float *motion, const float *t0, const OccupancyGridT &field_msg,
+                   const std::vector<double> &xyt, std::vector<uint32_t> &weights, PoseResult &result,
+                   uint32_t *status = nullptr) {
+    if (scans.empty()) return false;
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    rplgpu_pose_score_t spec;
+    spec.origin_x = static_cast<float>(field_msg.info.origin.position.x);
+    spec.origin_y = static_cast<float>(field_msg.info.origin.position.y);
+    spec.resolution = field_msg.info.resolution;
+    spec.width = field_msg.info.width;
+    spec.height = field_msg.info.height;
+    const size_t n_cells = static_cast<size_t>(spec.width) * spec.height;
+    if (n_cells == 0 || field_msg.data.size() != n_cells) return fail("score_poses: data is not width x height");
+    const size_t n_poses = xyt.size() / 3;
+    if (n_poses == 0 || xyt.size() != 3 * n_poses || n_poses > RPLGPU_MAX_POSES)
+      return fail("score_poses: xyt must hold 1 .. RPLGPU_MAX_POSES poses of 3 values");
+    size_t stride = 1;
+    for (const auto &s : scans) stride = s.size() > stride ? s.size() : stride;
+    if (stride > max_n_) return fail("scan larger than the configured capacity");
+    occ_nodes_.assign(scans.size() * stride, rplgpu_node_t{});
+    occ_len_.resize(scans.size());
+    for (size_t b = 0; b < scans.size(); ++b) {
+      if (!scans[b].empty()) std::memcpy(&occ_nodes_[b * stride], scans[b].data(), scans[b].size() * 8);
+      occ_len_[b] = static_cast<uint32_t>(scans[b].size());
+    }
+    occ_prev_.assign(field_msg.data.begin(), field_msg.data.end());
+    pose_list_.resize(4 * n_poses);
+    if (rplgpu_pose_list(xyt.data(), static_cast<uint32_t>(n_poses), pose_list_.data()) != RPLGPU_OK)
+      return fail("score_poses: rplgpu_pose_list refused the list");
+    weights.assign(n_poses, 0u);
+    const rplgpu_params_t p = cfg.to_params();
+    uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_score_poses(h_, occ_nodes_.data(), static_cast<uint32_t>(stride), occ_len_.data(),
+                           static_cast<uint32_t>(scans.size()), &p, motion, pose2d, t0, &spec, pose_list_.data(),
+                           static_cast<uint32_t>(n_poses), occ_prev_.data(), weights.data(), words,
+                           status) != RPLGPU_OK)
+      return note_error();
+    result.best = words[0];
+    result.best_index = words[1];
+    result.ties = words[2];
+    result.zeros = words[3];
+    result.points = words[4];
+    result.weight_of_first = words[5];
+    result.sum = static_cast<uint64_t>(words[6]) | (static_cast<uint64_t>(words[7]) << 32);
+    return true;
+  }
+
   // ext E14 (include/rplgpu_msg.h): the scans of ONE time step ADDED into a persistent hit / miss count map at the
   // poses given (e.g. the ones match_scans corrected) — what a mapper's map update does per accepted scan.
   // `counts` holds two words per cell (misses, hits); any other size than 2 x width x height starts a zeroed map.
@@ -517,6 +578,7 @@ class ScanPath {
   std::vector<rplgpu_node_t> occ_nodes_;
   std::vector<uint32_t> occ_len_;
   std::vector<int8_t> occ_prev_, occ_out_;
+  std::vector<float> pose_list_;
   std::string last_error_;
   uint32_t min_samples_ = 0;
 };
