@@ -781,6 +781,78 @@ int32_t rplgpu_score_poses(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32
                            const rplgpu_pose_score_t *s, const float *poses, uint32_t P, const int8_t *field,
                            uint32_t *weights_out, uint32_t result[8], uint32_t *status);
 
+/* ---- E16: a weighted pose list resampled and moved (row 4; the particle filter's step between two sensor updates)
+ * ----
+ * E15 ends with one uint32 weight per pose; the filter's next step draws a new list in proportion to the weights
+ * and moves it by the odometry increment.  Here that step runs on the device, so that score -> resample -> score
+ * queues on one stream without a read: the weights and the list of one rplgpu_score_poses_dev call go in, the list
+ * for the next one comes out.  Nothing in the reference resamples, so these rules ARE the definition (parity
+ * unpinned, as E5-E15).  The draw is integers and the move is fixed float32 operations: the result is byte-exact,
+ * depends on no order and uses no atomic on a value.  The device owns no random generator: the caller supplies ONE
+ * uint32 per group.
+ *
+ * INPUTS, per group g of G: P weights w[i] = d_weights[g * weight_stride + i] (E15's output layout: the calls
+ * chain); P poses of four floats at d_poses + g_p * pose_stride + 4 i, g_p = g when poses_per_group is not 0, else 0
+ * (pose_stride in floats, >= 4 P and a multiple of 4, d_poses 16-byte aligned: E15's rules); u = d_u[g], or 0 for
+ * every group when d_u is NULL; M, the number of outputs.  1 <= P, M <= RPLGPU_MAX_POSES.
+ * SYSTEMATIC (LOW-VARIANCE) RESAMPLING, all in integers:
+ *   S = the sum of the w[i] (below 2^52);  C[i] = w[0] + ... + w[i];
+ *   r = floor(u * S / 2^32) = u * (S >> 32) + ((u * (S & 0xffffffff)) >> 32), 64-bit; always r < S when S > 0;
+ *   t_j = floor((j * S + r) / M) for output j in [0, M) = j * q + (j * rho + r) / M with S = q * M + rho (every term
+ *   below 2^63; j * S itself does not fit);
+ *   ancestor a[j] = the smallest i with C[i] > t_j.
+ * It follows that t_j < S (every output has an ancestor), that a weight of 0 is never drawn, that pose i is drawn
+ * floor or ceil of M * w[i] / S times and that a[] is non-decreasing.
+ *   S = 0 (every pose dead): a[j] = j mod P and bit 0 of result word 7 is set; nothing divides by zero.
+ * MOVE: with d_delta NULL output j is the 16 bytes of pose a[j], bit for bit (NaN payloads and -0 are kept).
+ * Otherwise a delta (dc, ds, dx, dy) is composed on the right — the base moves in its own frame by the odometry
+ * increment — in float32, no FMA, each product rounded, then the difference or sum, the shape of E15's transform:
+ *   c' = c*dc - s*ds;   s' = s*dc + c*ds;   x' = (c*dx - s*dy) + x;   y' = (s*dx + c*dy) + y
+ * A result that is NaN is stored as 0x7FC00000 (which payload and sign a produced NaN carries is left to the
+ * implementation by IEEE 754; this keeps the output byte-exact everywhere).  n_delta is 1 (one delta per group: plain
+ * odometry) or M (one per output at d_delta + g_d * delta_stride + 4 j: odometry with the caller's noise already
+ * folded in); g_d = g when delta_per_group is not 0, else 0; delta_stride in floats, >= 4 n_delta and a multiple of
+ * 4; d_delta 16-byte aligned.  The device evaluates no trigonometric function and does not renormalise (c, s): a
+ * caller rebuilds the list through rplgpu_pose_list when the drift of c*c + s*s matters.  The delta (1, 0, 0, 0) is
+ * NOT the bit copy: c = -0 with a negative s becomes +0 (-0 * 1 - s * 0 = -0 - -0 = +0).
+ * OUTPUTS: output j of group g at d_poses_out + g * out_stride + 4 j (out_stride in floats, >= 4 M and a multiple of
+ * 4; 16-byte aligned; it must not overlap d_poses over the ranges used: refused); a[j] at d_ancestors + g *
+ * anc_stride + j (optional; anc_stride >= M); eight 32-bit words per group at d_result + 8 g:
+ *   0, 1      S, low and high word
+ *   2, 3, 4   the sum of the w[i]^2, 96 bits, low to high (the host forms N_eff = S^2 / sum w^2 from words 0 - 4)
+ *   5         the number of weights that are not 0
+ *   6         the number of distinct ancestors among the M outputs (min(M, P) when S = 0)
+ *   7         flags: bit 0 = S was 0
+ * Words of an output array at and beyond M of a group are never changed.  d_weights, d_poses, d_delta and d_u are
+ * only read (and must not change while the call runs: its launches read the weights twice).
+ * SCRATCH is the caller's, as E13's volume is: rplgpu_resample_scratch_words(G, P) uint32 words at d_scratch, 8-byte
+ * aligned; the function is host only and returns 0 for G = 0 or a P outside 1 .. RPLGPU_MAX_POSES.
+ * RPLGPU_ERR_INVALID_ARG, no output changed and nothing queued, for G = 0 or above 65535 (groups x tiles is a
+ * launch grid), P or M of 0 or above RPLGPU_MAX_POSES, a missing d_weights / d_poses / d_poses_out / d_result /
+ * d_scratch, a misaligned pointer (16 bytes: d_poses, d_poses_out, d_delta; 8: d_scratch; 4: the others), the stride
+ * rules above with weight_stride >= P, n_delta not in {1, M} with d_delta set, and the overlap.  Asynchronous on the
+ * handle's stream. */
+uint64_t rplgpu_resample_scratch_words(uint32_t G, uint32_t P);
+int32_t rplgpu_resample_poses_dev(rplgpu_handle_t h, const uint32_t *d_weights, uint64_t weight_stride,
+                                  const float *d_poses, uint64_t pose_stride, uint32_t poses_per_group, uint32_t G,
+                                  uint32_t P, uint32_t M, const uint32_t *d_u, const float *d_delta,
+                                  uint32_t n_delta, uint64_t delta_stride, uint32_t delta_per_group,
+                                  float *d_poses_out, uint64_t out_stride, uint32_t *d_ancestors,
+                                  uint64_t anc_stride, uint32_t *d_result, uint32_t *d_scratch);
+/* Host only (no handle, no device): the same rule in plain C++ for ONE group — the definition a reader can run.
+ * weights: P words; poses: 4 P floats; delta: NULL, or 4 n_delta floats with n_delta 1 or M; poses_out: 4 M floats;
+ * ancestors_out (optional): M words; result: 8 words.  RPLGPU_ERR_INVALID_ARG and nothing written for a NULL
+ * weights / poses / poses_out / result, P or M of 0 or above RPLGPU_MAX_POSES, n_delta not in {1, M} with delta set,
+ * and a poses_out that overlaps poses. */
+int32_t rplgpu_resample_host(const uint32_t *weights, uint32_t P, uint32_t M, uint32_t u, const float *poses,
+                             const float *delta, uint32_t n_delta, float *poses_out, uint32_t *ancestors_out,
+                             uint32_t result[8]);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp), arguments as rplgpu_resample_host.  Allocates its
+ * device buffers and scratch per call and returns when the results are in place: a door, not a hot path. */
+int32_t rplgpu_resample_poses(rplgpu_handle_t h, const uint32_t *weights, uint32_t P, uint32_t M, uint32_t u,
+                              const float *poses, const float *delta, uint32_t n_delta, float *poses_out,
+                              uint32_t *ancestors_out, uint32_t result[8]);
+
 #ifdef __cplusplus
 }
 #endif

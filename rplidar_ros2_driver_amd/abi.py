@@ -136,6 +136,10 @@ ABI_SYMBOLS = [
     "rplgpu_pose_list",
     "rplgpu_score_poses_dev",
     "rplgpu_score_poses",
+    "rplgpu_resample_scratch_words",
+    "rplgpu_resample_poses_dev",
+    "rplgpu_resample_host",
+    "rplgpu_resample_poses",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -581,6 +585,12 @@ def load_library() -> C.CDLL:
                                            C.POINTER(PoseScore), vp, u32, u64, u32, vp, u64, u32, vp, u64, vp, vp]
     lib.rplgpu_score_poses.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp,
                                        C.POINTER(PoseScore), vp, u32, vp, vp, vp, vp]
+    lib.rplgpu_resample_scratch_words.argtypes = [u32, u32]
+    lib.rplgpu_resample_scratch_words.restype = C.c_uint64
+    lib.rplgpu_resample_poses_dev.argtypes = [vp, vp, u64, vp, u64, u32, u32, u32, u32, vp, vp, u32, u64, u32, vp,
+                                              u64, vp, u64, vp, vp]
+    lib.rplgpu_resample_host.argtypes = [vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]
+    lib.rplgpu_resample_poses.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1020,6 +1030,30 @@ class RplGpu:
             C.byref(spec), poses.ctypes.data, P, field.ctypes.data, ptr(weights), result.ctypes.data,
             status.ctypes.data))
         return weights, result, int(status[0])
+
+    def resample_poses_dev(self, d_weights: int, weight_stride: int, d_poses: int, pose_stride: int,
+                           poses_per_group: int, G: int, P: int, M: int, d_u: int, d_delta: int, n_delta: int,
+                           delta_stride: int, delta_per_group: int, d_poses_out: int, out_stride: int,
+                           d_ancestors: int, anc_stride: int, d_result: int, d_scratch: int):
+        """E16: per group the P weighted poses at d_poses resampled (systematic, the group's random word at d_u) into
+        M poses at d_poses_out, moved by the delta(s) at d_delta when that is not 0; ancestors (optional) and eight
+        result words at d_result + 8 g.  d_scratch: ``resample_scratch_words(G, P)`` uint32 words."""
+        self._check(self._lib.rplgpu_resample_poses_dev(
+            self._h, d_weights, weight_stride, d_poses, pose_stride, poses_per_group, G, P, M, d_u, d_delta, n_delta,
+            delta_stride, delta_per_group, d_poses_out, out_stride, d_ancestors, anc_stride, d_result, d_scratch))
+
+    def resample_poses(self, weights: np.ndarray, poses: np.ndarray, M: int, u: int = 0, delta=None):
+        """E16, one group, host buffers: weights (P,) uint32 and poses (P, 4) float32 -> ``(poses_out (M, 4)
+        float32, ancestors (M,) uint32, result (8,) uint32)``; delta: None, (4,) / (1, 4) or (M, 4) float32."""
+        weights, poses, delta, n_delta = _resample_args(weights, poses, M, delta)
+        out = np.zeros((M, 4), np.float32)
+        anc = np.zeros(M, np.uint32)
+        result = np.zeros(8, np.uint32)
+        self._check(self._lib.rplgpu_resample_poses(
+            self._h, weights.ctypes.data, len(weights), M, u, poses.ctypes.data,
+            0 if delta is None else delta.ctypes.data, n_delta, out.ctypes.data, anc.ctypes.data,
+            result.ctypes.data))
+        return out, anc, result
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -1500,3 +1534,37 @@ def pose_list(xyt) -> np.ndarray:
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_pose_list")
     return out
+
+
+def resample_scratch_words(G: int, P: int) -> int:
+    """Host only: the uint32 words of scratch resample_poses_dev needs for G groups of P poses; 0 for G = 0 or a P
+    outside 1 .. MAX_POSES."""
+    return int(load_library().rplgpu_resample_scratch_words(G, P))
+
+
+def _resample_args(weights, poses, M, delta):
+    weights = np.ascontiguousarray(weights, np.uint32)
+    poses = np.ascontiguousarray(poses, np.float32)
+    if weights.ndim != 1 or poses.shape != (len(weights), 4):
+        raise TypeError("weights must be (P,) uint32 and poses (P, 4) float32")
+    n_delta = 0
+    if delta is not None:
+        delta = np.ascontiguousarray(delta, np.float32).reshape(-1, 4)
+        n_delta = len(delta)
+    return weights, poses, delta, n_delta
+
+
+def resample_host(weights, poses, M: int, u: int = 0, delta=None):
+    """Host only: E16's rule for one group by the library's own rplgpu_resample_host (no handle, no device);
+    arguments and results as ``RplGpu.resample_poses``."""
+    weights, poses, delta, n_delta = _resample_args(weights, poses, M, delta)
+    ok = 0 < M <= MAX_POSES
+    out = np.zeros((M if ok else 1, 4), np.float32)
+    anc = np.zeros(M if ok else 1, np.uint32)
+    result = np.zeros(8, np.uint32)
+    rc = load_library().rplgpu_resample_host(
+        weights.ctypes.data, len(weights), M, u, poses.ctypes.data, 0 if delta is None else delta.ctypes.data,
+        n_delta, out.ctypes.data, anc.ctypes.data, result.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_resample_host")
+    return out, anc, result

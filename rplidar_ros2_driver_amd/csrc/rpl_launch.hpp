@@ -353,4 +353,16 @@ hipError_t launch_pose_score(hipStream_t s, const void *nodes, uint32_t n_stride
 hipError_t launch_pose_best(hipStream_t s, const uint32_t *weights, unsigned long long weight_stride, uint32_t G,
                             uint32_t P, uint32_t *result);
 
+// E16: a weighted pose list resampled and moved (rpl_resample.hip, include/rplgpu_msg.h).  Three launches on the
+// stream: per-tile sums into the scratch, one workgroup per group for the scan, the tile boundaries and result
+// words 0 - 5 and 7, then the outputs, the ancestors and word 6.  The scratch holds resample_scratch_words(G, P)
+// uint32 words (0 for a G or P that the call refuses) and is 8-byte aligned.
+unsigned long long resample_scratch_words(uint32_t G, uint32_t P);
+hipError_t launch_resample(hipStream_t s, const uint32_t *weights, unsigned long long weight_stride,
+                           const float *poses, unsigned long long pose_stride, uint32_t poses_per_group, uint32_t G,
+                           uint32_t P, uint32_t M, const uint32_t *u, const float *delta, uint32_t n_delta,
+                           unsigned long long delta_stride, uint32_t delta_per_group, float *out,
+                           unsigned long long out_stride, uint32_t *ancestors, unsigned long long anc_stride,
+                           uint32_t *result, uint32_t *scratch);
+
 }  // namespace rpl

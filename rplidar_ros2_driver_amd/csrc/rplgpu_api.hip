@@ -2419,6 +2419,188 @@ int32_t rplgpu_score_poses(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32
   return RPLGPU_OK;
 }
 
+// ---- E16: a weighted pose list resampled and moved (include/rplgpu_msg.h) ---------------------------------------
+
+uint64_t rplgpu_resample_scratch_words(uint32_t G, uint32_t P) { return rpl::resample_scratch_words(G, P); }
+
+// the byte ranges [a, a + na) and [b, b + nb) share a byte
+static bool ranges_overlap(const void *a, uint64_t na, const void *b, uint64_t nb) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+
+// E16's move: the delta composed on the right, float32, each product rounded, then the difference or sum (this
+// unit is built with -ffp-contract=off); a NaN that the move makes is stored as 0x7FC00000
+static void resample_move(const float *pose, const float *d, float *out) {
+  const float c = pose[0], s = pose[1], x = pose[2], y = pose[3];
+  const float dc = d[0], ds = d[1], dx = d[2], dy = d[3];
+  const float p0 = c * dc, p1 = s * ds, p2 = s * dc, p3 = c * ds, p4 = c * dx, p5 = s * dy, p6 = s * dx, p7 = c * dy;
+  float v[4] = {p0 - p1, p2 + p3, (p4 - p5) + x, (p6 + p7) + y};
+  const uint32_t qnan = 0x7FC00000u;
+  for (int k = 0; k < 4; ++k) {
+    if (v[k] != v[k]) std::memcpy(&v[k], &qnan, 4);
+  }
+  std::memcpy(out, v, 16);
+}
+
+int32_t rplgpu_resample_host(const uint32_t *weights, uint32_t P, uint32_t M, uint32_t u, const float *poses,
+                             const float *delta, uint32_t n_delta, float *poses_out, uint32_t *ancestors_out,
+                             uint32_t result[8]) {
+  if (!weights || !poses || !poses_out || !result || P == 0 || P > RPLGPU_MAX_POSES || M == 0 ||
+      M > RPLGPU_MAX_POSES || (delta && n_delta != 1u && n_delta != M) ||
+      ranges_overlap(poses, 16ull * P, poses_out, 16ull * M))
+    return RPLGPU_ERR_INVALID_ARG;
+  uint64_t S = 0, sq = 0;
+  uint32_t carry = 0, nz = 0;
+  for (uint32_t i = 0; i < P; ++i) {
+    const uint64_t w = weights[i], w2 = w * w;
+    S += w;
+    sq += w2;
+    carry += sq < w2 ? 1u : 0u;
+    nz += w != 0 ? 1u : 0u;
+  }
+  const uint64_t q = S / M, rho = S % M;
+  const uint64_t r = (uint64_t)u * (S >> 32) + (((uint64_t)u * (S & 0xffffffffull)) >> 32);
+  uint32_t i = 0, distinct = 0, last = 0xFFFFFFFFu;
+  uint64_t C = weights[0];  // C[i], inclusive
+  for (uint32_t j = 0; j < M; ++j) {
+    uint32_t a;
+    if (S == 0) {
+      a = j % P;
+    } else {
+      const uint64_t t = (uint64_t)j * q + ((uint64_t)j * rho + r) / M;  // < S: the walk ends inside the list
+      while (C <= t) C += weights[++i];
+      a = i;
+    }
+    if (a != last) ++distinct;  // (a is non-decreasing)
+    last = a;
+    if (delta)
+      resample_move(poses + 4u * (size_t)a, delta + (n_delta == 1u ? 0u : 4u * (size_t)j), poses_out + 4u * (size_t)j);
+    else
+      std::memcpy(poses_out + 4u * (size_t)j, poses + 4u * (size_t)a, 16);
+    if (ancestors_out) ancestors_out[j] = a;
+  }
+  result[0] = (uint32_t)S;
+  result[1] = (uint32_t)(S >> 32);
+  result[2] = (uint32_t)sq;
+  result[3] = (uint32_t)(sq >> 32);
+  result[4] = carry;
+  result[5] = nz;
+  result[6] = S == 0 ? std::min(M, P) : distinct;
+  result[7] = S == 0 ? 1u : 0u;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_resample_poses_dev(rplgpu_handle_t h, const uint32_t *d_weights, uint64_t weight_stride,
+                                  const float *d_poses, uint64_t pose_stride, uint32_t poses_per_group, uint32_t G,
+                                  uint32_t P, uint32_t M, const uint32_t *d_u, const float *d_delta,
+                                  uint32_t n_delta, uint64_t delta_stride, uint32_t delta_per_group,
+                                  float *d_poses_out, uint64_t out_stride, uint32_t *d_ancestors,
+                                  uint64_t anc_stride, uint32_t *d_result, uint32_t *d_scratch) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_resample_poses_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES || M == 0 || M > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_resample_poses_dev: P and M must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_weights || !d_poses || !d_poses_out || !d_result || !d_scratch || off(d_weights, 3) || off(d_poses, 15) ||
+      off(d_poses_out, 15) || off(d_result, 3) || off(d_scratch, 7) || off(d_u, 3) || off(d_delta, 15) ||
+      off(d_ancestors, 3)) {
+    h->err = "rplgpu_resample_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for pose "
+             "lists and deltas, 8 for d_scratch, 4 otherwise)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (weight_stride < P || pose_stride < 4ull * P || (pose_stride & 3u) || out_stride < 4ull * M ||
+      (out_stride & 3u) || (d_ancestors && anc_stride < M)) {
+    h->err = "rplgpu_resample_poses_dev: weight_stride >= P, pose_stride >= 4 P, out_stride >= 4 M (both multiples "
+             "of 4) and anc_stride >= M are required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_delta && ((n_delta != 1u && n_delta != M) || delta_stride < 4ull * n_delta || (delta_stride & 3u))) {
+    h->err = "rplgpu_resample_poses_dev: n_delta must be 1 or M, delta_stride >= 4 n_delta and a multiple of 4";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint64_t in_bytes = 4ull * ((poses_per_group ? (uint64_t)(G - 1u) * pose_stride : 0ull) + 4ull * P);
+  const uint64_t out_bytes = 4ull * ((uint64_t)(G - 1u) * out_stride + 4ull * M);
+  if (ranges_overlap(d_poses, in_bytes, d_poses_out, out_bytes)) {
+    h->err = "rplgpu_resample_poses_dev: d_poses_out overlaps d_poses";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, d_weights, "d_weights") || !device_readable(h, d_poses, "d_poses") ||
+      !device_readable(h, d_poses_out, "d_poses_out") || !device_readable(h, d_result, "d_result") ||
+      !device_readable(h, d_scratch, "d_scratch") || (d_u && !device_readable(h, d_u, "d_u")) ||
+      (d_delta && !device_readable(h, d_delta, "d_delta")) ||
+      (d_ancestors && !device_readable(h, d_ancestors, "d_ancestors")))
+    return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_resample(h->stream, d_weights, weight_stride, d_poses, pose_stride, poses_per_group, G, P,
+                                  M, d_u, d_delta, d_delta ? n_delta : 1u, delta_stride, delta_per_group,
+                                  d_poses_out, out_stride, d_ancestors, anc_stride, d_result, d_scratch));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_resample_poses(rplgpu_handle_t h, const uint32_t *weights, uint32_t P, uint32_t M, uint32_t u,
+                              const float *poses, const float *delta, uint32_t n_delta, float *poses_out,
+                              uint32_t *ancestors_out, uint32_t result[8]) {
+  if (!h || !weights || !poses || !poses_out || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (P == 0 || P > RPLGPU_MAX_POSES || M == 0 || M > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_resample_poses: P and M must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (delta && n_delta != 1u && n_delta != M) {
+    h->err = "rplgpu_resample_poses: n_delta must be 1 or M";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (ranges_overlap(poses, 16ull * P, poses_out, 16ull * M)) {
+    h->err = "rplgpu_resample_poses: poses_out overlaps poses";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // one allocation per call (a convenience door, not the hot path): poses | out | deltas | weights | ancestors |
+  // scratch | u + result, every part 16-byte aligned
+  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  const size_t nd = delta ? n_delta : 0u;
+  const size_t o_out = up16(16u * (size_t)P), o_dl = o_out + up16(16u * (size_t)M), o_wt = o_dl + up16(16u * nd),
+               o_anc = o_wt + up16(4u * (size_t)P), o_scr = o_anc + up16(4u * (size_t)M),
+               o_small = o_scr + up16(4u * (size_t)rplgpu_resample_scratch_words(1, P)), total = o_small + 48u;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_resample_poses: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  auto run = [&]() -> int32_t {
+    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);  // u, then the result at + 4 words
+    RPL_HIP(h, hipMemcpyAsync(d, poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_wt, weights, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d_small, &u, 4, hipMemcpyHostToDevice, h->stream));
+    if (delta) RPL_HIP(h, hipMemcpyAsync(d + o_dl, delta, 16u * nd, hipMemcpyHostToDevice, h->stream));
+    const int32_t rc = rplgpu_resample_poses_dev(
+        h, reinterpret_cast<const uint32_t *>(d + o_wt), P, reinterpret_cast<const float *>(d), 4ull * P, 0, 1, P, M,
+        d_small, delta ? reinterpret_cast<const float *>(d + o_dl) : nullptr, n_delta, 4ull * nd, 0,
+        reinterpret_cast<float *>(d + o_out), 4ull * M, reinterpret_cast<uint32_t *>(d + o_anc), M, d_small + 4,
+        reinterpret_cast<uint32_t *>(d + o_scr));
+    if (rc) return rc;
+    RPL_HIP(h, hipMemcpyAsync(poses_out, d + o_out, 16u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    if (ancestors_out)
+      RPL_HIP(h, hipMemcpyAsync(ancestors_out, d + o_anc, 4u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d_small + 4, 32, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;
+  std::memcpy(result, small, 32);
+  return RPLGPU_OK;
+}
+
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,

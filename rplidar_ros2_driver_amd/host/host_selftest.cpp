@@ -313,6 +313,30 @@ int main(int argc, char **argv) {
     }
     std::printf("pose score: best %u at pose %u of 4, sum %llu\n", pr.best, pr.best_index,
                 static_cast<unsigned long long>(pr.sum));
+    // E16 on those weights (136, 198, 136, 0; S = 470), four outputs, u = 0: t = (0, 117, 235, 352) against
+    // C = (136, 334, 470, 470) gives the ancestors (0, 0, 1, 2): the dead pose is gone and pose 0 is there twice.
+    // The device call against the library's own host-only twin, byte for byte, with one metre ahead as the delta.
+    std::vector<float> plist(16), moved, twin(16);
+    if (rplgpu_pose_list(xyt.data(), 4, plist.data()) != RPLGPU_OK) return 18;
+    const std::vector<float> ahead = {1.0f, 0.0f, 1.0f, 0.0f};
+    std::vector<uint32_t> anc, twin_anc(4);
+    uint32_t twin_words[8];
+    rplgpu_host::ScanPath::ResampleResult rr;
+    if (!path.resample_poses(weights, plist, 4, 0u, ahead, moved, anc, rr)) {
+      std::fprintf(stderr, "resample failed: %s\n", path.last_error().c_str());
+      return 18;
+    }
+    if (rplgpu_resample_host(weights.data(), 4, 4, 0u, plist.data(), ahead.data(), 1, twin.data(), twin_anc.data(),
+                             twin_words) != RPLGPU_OK)
+      return 19;
+    if (anc != std::vector<uint32_t>({0, 0, 1, 2}) || anc != twin_anc ||
+        std::memcmp(moved.data(), twin.data(), 64) != 0 || rr.sum != 470 || rr.alive != 3 || rr.distinct != 3 ||
+        rr.all_dead || rr.sum_squares != 76196.0 || moved[2] != 1.0f || moved[10] != 0.0f || twin_words[6] != 3) {
+      std::fprintf(stderr, "resample: wrong answer (ancestors %u %u %u %u, S %llu, %u alive, %u distinct)\n", anc[0],
+                   anc[1], anc[2], anc[3], static_cast<unsigned long long>(rr.sum), rr.alive, rr.distinct);
+      return 19;
+    }
+    std::printf("resample: ancestors %u %u %u %u, N_eff %.3f of 4\n", anc[0], anc[1], anc[2], anc[3], rr.n_eff);
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

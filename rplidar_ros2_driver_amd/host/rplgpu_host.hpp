@@ -28,6 +28,8 @@
 //         -> rplgpu_host::ScanPath::update_map(scans, ..., counts) and fill_map_grid(counts, ..., grid_msg)  (E14)
 //   pf  the localisation side's other loop (a particle filter's sensor update over a list of arbitrary poses):
 //         -> rplgpu_host::ScanPath::score_poses(scans, ..., field_msg, xyt, weights, result)  (E15)
+//         and its step between two sensor updates (the list redrawn by its weights and moved by the odometry):
+//         -> rplgpu_host::ScanPath::resample_poses(weights, poses, count, u, delta, poses_out, ancestors, result)  (E16)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -496,6 +498,47 @@ class ScanPath {
     result.points = words[4];
     result.weight_of_first = words[5];
     result.sum = static_cast<uint64_t>(words[6]) | (static_cast<uint64_t>(words[7]) << 32);
+    return true;
+  }
+
+  // ext E16 (include/rplgpu_msg.h): the list `poses` (four floats per pose, as rplgpu_pose_list writes them)
+  // redrawn by `weights` (what score_poses returned) into `count` poses — systematic resampling from the caller's
+  // one random word u — and moved by `delta` (dc, ds, dx, dy): empty for a plain copy, 4 floats for one odometry
+  // increment, 4 x count for one per output.  ancestors: the index each new pose descends from; result: the
+  // header's RESULT table.  The new list goes into score_poses's device call as it is, or back through xyt.
+  struct ResampleResult {
+    uint64_t sum = 0;           // S
+    double sum_squares = 0.0;   // the 96-bit sum of the squared weights, rounded
+    double n_eff = 0.0;         // S^2 / sum of squares (0 when every weight is 0)
+    uint32_t alive = 0, distinct = 0;
+    bool all_dead = false;
+  };
+  bool resample_poses(const std::vector<uint32_t> &weights, const std::vector<float> &poses, uint32_t count,
+                      uint32_t u, const std::vector<float> &delta, std::vector<float> &poses_out,
+                      std::vector<uint32_t> &ancestors, ResampleResult &result) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    const size_t n_poses = weights.size();
+    if (n_poses == 0 || n_poses > RPLGPU_MAX_POSES || poses.size() != 4 * n_poses)
+      return fail("resample_poses: 1 .. RPLGPU_MAX_POSES weights and four floats per pose");
+    if (count == 0 || count > RPLGPU_MAX_POSES) return fail("resample_poses: count must be in 1 .. RPLGPU_MAX_POSES");
+    if (!delta.empty() && delta.size() != 4 && delta.size() != 4 * static_cast<size_t>(count))
+      return fail("resample_poses: delta must hold 0, 1 or count increments of four floats");
+    poses_out.assign(4 * static_cast<size_t>(count), 0.0f);
+    ancestors.assign(count, 0u);
+    uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_resample_poses(h_, weights.data(), static_cast<uint32_t>(n_poses), count, u, poses.data(),
+                              delta.empty() ? nullptr : delta.data(), static_cast<uint32_t>(delta.size() / 4),
+                              poses_out.data(), ancestors.data(), words) != RPLGPU_OK)
+      return note_error();
+    result.sum = static_cast<uint64_t>(words[0]) | (static_cast<uint64_t>(words[1]) << 32);
+    result.sum_squares = static_cast<double>(words[2]) + 4294967296.0 * static_cast<double>(words[3]) +
+                         18446744073709551616.0 * static_cast<double>(words[4]);
+    const double s = static_cast<double>(result.sum);
+    result.n_eff = result.sum_squares > 0.0 ? s * s / result.sum_squares : 0.0;
+    result.alive = words[5];
+    result.distinct = words[6];
+    result.all_dead = (words[7] & 1u) != 0;
     return true;
   }
 
