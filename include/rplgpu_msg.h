@@ -853,6 +853,87 @@ int32_t rplgpu_resample_poses(rplgpu_handle_t h, const uint32_t *weights, uint32
                               const float *poses, const float *delta, uint32_t n_delta, float *poses_out,
                               uint32_t *ancestors_out, uint32_t result[8]);
 
+/* ---- E17: a weighted pose list reduced to a pose estimate (row 4; what the filter is built to produce) ----
+ * E15 weighs a list and E16 redraws and moves it; what a localiser publishes is ONE pose with a covariance (AMCL's
+ * PoseWithCovarianceStamped).  Here the sums that pose is formed from are made on the device, so that
+ * score -> estimate -> resample -> move -> score queues on one stream without a read of the list.  Nothing in the
+ * reference estimates, so these rules ARE the definition (parity unpinned, as E5-E16).  After one float32 product
+ * and one round-to-nearest-even per pose entry everything is integers: the result has one answer, no order of
+ * summation matters and no atomic touches a value.
+ * SPEC: xy_scale, the quantum of x and y (1024: about 1 mm); gate_r2, the gate's squared radius in quanta; gate_dot,
+ * the least C*C + S*S product in Q40 (the cosine of the gate's half angle).  The default is 1024, 512^2 (0.5 m) and
+ * 15 * 2^36 (15/16 in Q40, about 20 degrees: it needs no cosine). */
+#define RPLGPU_ESTIMATE_WORDS 72u
+typedef struct rplgpu_pose_estimate {
+  float    xy_scale;
+  uint64_t gate_r2;
+  int64_t  gate_dot;
+} rplgpu_pose_estimate_t;
+void rplgpu_default_pose_estimate(rplgpu_pose_estimate_t *s);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL and an xy_scale that is not finite or not > 0.
+ * The device path uses this function. */
+int32_t rplgpu_pose_estimate_check(const rplgpu_pose_estimate_t *s);
+/* INPUTS, per group g of G: P poses of four floats (c, s, x, y) at d_poses + g_p * pose_stride + 4 i, g_p = g when
+ * poses_per_group is not 0, else 0 (pose_stride in floats, >= 4 P and a multiple of 4, d_poses 16-byte aligned:
+ * E15's and E16's rules); weights w[i] = d_weights[g * weight_stride + i] (E15's output layout, weight_stride >= P),
+ * or w = 1 at every pose when d_weights is NULL (the list as E16 leaves it; weight_stride is then not looked at); the
+ * centre word d_center[g * center_stride], a uint32 — meant to be E15's result word 1: d_center = d_result + 1 with
+ * center_stride = 8 — and the centre index q_c = min(word, P - 1); q_c = 0 (E15's odometry pose by convention) when
+ * d_center is NULL.  1 <= P <= RPLGPU_MAX_POSES.
+ * QUANTISATION, float32, one product and one rounding, no FMA, no trigonometric function:
+ *   tx = x * xy_scale;  ty = y * xy_scale;  tc = c * 1048576.0f;  ts = s * 1048576.0f;
+ *   a pose is IN RANGE iff fabsf(t) < 8388608.0f for all four (false for NaN and +-Inf);
+ *   X, Y, C, S = (int32) rintf(t), ties to even, so |.| <= 2^23.
+ * A pose that is not in range contributes to nothing and sets flag bit 1.
+ * GATE: empty, with flag bit 0 set, when the centre pose is not in range.  Otherwise an in-range pose i is in the
+ * gate iff  (uint64)(dX*dX + dY*dY) <= gate_r2  with dX = X_i - X_c, dY = Y_i - Y_c  and
+ * (int64)C_i*C_c + (int64)S_i*S_c >= gate_dot.  gate_r2 = 2^64 - 1 with gate_dot = INT64_MIN admits every in-range
+ * pose.
+ * SUMS: two sets — set 0 over every in-range pose, set 1 over the gate — of eight exact signed integers each:
+ *   W = sum w,  sum wX,  sum wY,  sum wC,  sum wS,  sum wXX,  sum wXY,  sum wYY.
+ * With w < 2^32, |X| <= 2^23 and P <= 2^20 every sum is below 2^98 in magnitude; each is stored as 128-bit two's
+ * complement in four uint32 words, low to high.
+ * RESULT: RPLGPU_ESTIMATE_WORDS words per group at d_result + 72 g:
+ *   0                      flags: bit 0 = the centre is not in range, bit 1 = some pose is not in range,
+ *                          bit 2 = set 0 has W = 0, bit 3 = set 1 has W = 0
+ *   1                      q_c
+ *   2, 3                   the poses in range;  those among them with w != 0
+ *   4, 5                   the poses in the gate;  those among them with w != 0
+ *   6, 7                   0
+ *   8 + 32 k + 4 m .. + 3  sum m of set k, in the order above
+ * d_poses, d_weights and d_center are only read (and must not change while the call runs: both launches read the
+ * centre).  The means, the heading and the covariance are divisions the host does once: rplgpu_estimate_pose.
+ * SCRATCH is the caller's, as E16's: rplgpu_estimate_scratch_words(G, P) uint32 words at d_scratch, 8-byte aligned
+ * (its layout: the head of rpl_estimate.hip); the function is host only and returns 0 for arguments the call refuses.
+ * RPLGPU_ERR_INVALID_ARG, no output changed and nothing queued, for a spec the check refuses, G = 0 or above 65535
+ * (groups x tiles is a launch grid), P = 0 or above RPLGPU_MAX_POSES, a missing d_poses / d_result / d_scratch, a
+ * misaligned pointer (16 bytes: d_poses; 8: d_scratch; 4: the others), the stride rules above, and center_stride = 0
+ * with d_center set and G > 1.  Asynchronous on the handle's stream. */
+uint64_t rplgpu_estimate_scratch_words(uint32_t G, uint32_t P);
+int32_t rplgpu_estimate_poses_dev(rplgpu_handle_t h, const float *d_poses, uint64_t pose_stride,
+                                  uint32_t poses_per_group, const uint32_t *d_weights, uint64_t weight_stride,
+                                  uint32_t G, uint32_t P, const rplgpu_pose_estimate_t *s, const uint32_t *d_center,
+                                  uint64_t center_stride, uint32_t *d_result, uint32_t *d_scratch);
+/* Host only (no handle, no device): the same rule in plain C++ with __int128 for ONE group — the definition a reader
+ * can run.  poses: 4 P floats; weights: P words or NULL (w = 1); center: the centre WORD (clamped as above); result:
+ * 72 words.  RPLGPU_ERR_INVALID_ARG and nothing written for a NULL poses / result, a spec the check refuses and P = 0
+ * or above RPLGPU_MAX_POSES. */
+int32_t rplgpu_estimate_host(const float *poses, uint32_t P, const uint32_t *weights,
+                             const rplgpu_pose_estimate_t *s, uint32_t center, uint32_t result[72]);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp), arguments as rplgpu_estimate_host.  Allocates its
+ * device buffers and scratch per call and returns when the result is in place: a door, not a hot path. */
+int32_t rplgpu_estimate_poses(rplgpu_handle_t h, const float *poses, uint32_t P, const uint32_t *weights,
+                              const rplgpu_pose_estimate_t *s, uint32_t center, uint32_t result[72]);
+/* Host only: set `set` (0 or 1) of one group's result words as a pose, fp64 formed from the 128-bit integers:
+ *   out[0], out[1]  mean x, mean y = (sum wX / W) / xy_scale, ...
+ *   out[2]          theta = atan2(sum wS, sum wC)
+ *   out[3 .. 5]     covariance xx, xy, yy = (sum wXX / W) / xy_scale^2 - mean x * mean x, ...
+ *   out[6]          R = hypot(sum wC, sum wS) / (W * 2^20), the mean resultant length (1: every heading equal)
+ *   out[7]          W
+ * RPLGPU_ERR_INVALID_ARG and nothing written for NULL, a set above 1, an xy_scale that is not finite or not > 0, and
+ * a set whose W is 0.  A convenience, NOT part of the byte-exact contract: every step is one fp64 rounding. */
+int32_t rplgpu_estimate_pose(const uint32_t result[72], float xy_scale, uint32_t set, double out[8]);
+
 #ifdef __cplusplus
 }
 #endif

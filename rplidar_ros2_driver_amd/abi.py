@@ -44,6 +44,7 @@ MAX_OCC_DIM = 4096       # RPLGPU_MAX_OCC_DIM (include/rplgpu_msg.h)
 MAX_OCC_STEPS = 8192     # RPLGPU_MAX_OCC_STEPS (include/rplgpu_msg.h)
 MAX_INFLATION_CELLS = 64  # RPLGPU_MAX_INFLATION_CELLS (include/rplgpu_msg.h)
 MAX_POSES = 1048576       # RPLGPU_MAX_POSES (include/rplgpu_msg.h)
+ESTIMATE_WORDS = 72       # RPLGPU_ESTIMATE_WORDS
 
 SL_RESULT_OK = 0
 SL_RESULT_OPERATION_FAIL = 0x80008001
@@ -140,6 +141,13 @@ ABI_SYMBOLS = [
     "rplgpu_resample_poses_dev",
     "rplgpu_resample_host",
     "rplgpu_resample_poses",
+    "rplgpu_default_pose_estimate",
+    "rplgpu_pose_estimate_check",
+    "rplgpu_estimate_scratch_words",
+    "rplgpu_estimate_poses_dev",
+    "rplgpu_estimate_host",
+    "rplgpu_estimate_poses",
+    "rplgpu_estimate_pose",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -396,6 +404,32 @@ class PoseScore(C.Structure):
         return s
 
 
+class PoseEstimate(C.Structure):
+    """Mirror of ``rplgpu_pose_estimate_t`` (E17: a weighted pose list reduced to a pose estimate)."""
+
+    _fields_ = [
+        ("xy_scale", C.c_float),
+        ("gate_r2", C.c_uint64),
+        ("gate_dot", C.c_int64),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "PoseEstimate":
+        """The library's own defaults (``rplgpu_default_pose_estimate``), then the overrides."""
+        s = cls()
+        load_library().rplgpu_default_pose_estimate(C.byref(s))
+        for k, v in kw.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s
+
+    @classmethod
+    def open_gate(cls, **kw) -> "PoseEstimate":
+        """The defaults with the gate that admits every in-range pose (set 1 == set 0)."""
+        return cls.defaults(**dict(dict(gate_r2=(1 << 64) - 1, gate_dot=-(1 << 63)), **kw))
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -591,6 +625,16 @@ def load_library() -> C.CDLL:
                                               u64, vp, u64, vp, vp]
     lib.rplgpu_resample_host.argtypes = [vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]
     lib.rplgpu_resample_poses.argtypes = [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]
+    lib.rplgpu_default_pose_estimate.argtypes = [C.POINTER(PoseEstimate)]
+    lib.rplgpu_default_pose_estimate.restype = None
+    lib.rplgpu_pose_estimate_check.argtypes = [C.POINTER(PoseEstimate)]
+    lib.rplgpu_estimate_scratch_words.argtypes = [u32, u32]
+    lib.rplgpu_estimate_scratch_words.restype = C.c_uint64
+    lib.rplgpu_estimate_poses_dev.argtypes = [vp, vp, u64, u32, vp, u64, u32, u32, C.POINTER(PoseEstimate), vp, u64,
+                                              vp, vp]
+    lib.rplgpu_estimate_host.argtypes = [vp, u32, vp, C.POINTER(PoseEstimate), u32, vp]
+    lib.rplgpu_estimate_poses.argtypes = [vp, vp, u32, vp, C.POINTER(PoseEstimate), u32, vp]
+    lib.rplgpu_estimate_pose.argtypes = [vp, C.c_float, u32, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1054,6 +1098,27 @@ class RplGpu:
             0 if delta is None else delta.ctypes.data, n_delta, out.ctypes.data, anc.ctypes.data,
             result.ctypes.data))
         return out, anc, result
+
+    def estimate_poses_dev(self, d_poses: int, pose_stride: int, poses_per_group: int, d_weights: int,
+                           weight_stride: int, G: int, P: int, spec: "PoseEstimate", d_center: int,
+                           center_stride: int, d_result: int, d_scratch: int):
+        """E17: per group the P poses at d_poses, weighed by d_weights (0: every weight 1), reduced to the
+        ``ESTIMATE_WORDS`` result words at d_result + 72 g: two sets of eight 128-bit sums (every in-range pose; the
+        gate around pose min(d_center[g * center_stride], P - 1), pose 0 when d_center is 0), counts and flags.
+        d_scratch: ``estimate_scratch_words(G, P)`` uint32 words."""
+        self._check(self._lib.rplgpu_estimate_poses_dev(
+            self._h, d_poses, pose_stride, poses_per_group, d_weights, weight_stride, G, P, C.byref(spec), d_center,
+            center_stride, d_result, d_scratch))
+
+    def estimate_poses(self, poses: np.ndarray, weights=None, spec: "PoseEstimate" = None, center: int = 0):
+        """E17, one group, host buffers: poses (P, 4) float32 and weights (P,) uint32 or None (every weight 1) ->
+        result (72,) uint32."""
+        poses, weights, spec = _estimate_args(poses, weights, spec)
+        result = np.zeros(ESTIMATE_WORDS, np.uint32)
+        self._check(self._lib.rplgpu_estimate_poses(
+            self._h, poses.ctypes.data, len(poses), 0 if weights is None else weights.ctypes.data, C.byref(spec),
+            center, result.ctypes.data))
+        return result
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -1568,3 +1633,53 @@ def resample_host(weights, poses, M: int, u: int = 0, delta=None):
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_resample_host")
     return out, anc, result
+
+
+def estimate_scratch_words(G: int, P: int) -> int:
+    """Host only: the uint32 words of scratch estimate_poses_dev needs for G groups of P poses; 0 for arguments the
+    call refuses."""
+    return int(load_library().rplgpu_estimate_scratch_words(G, P))
+
+
+def pose_estimate_check(spec: PoseEstimate) -> None:
+    """Host only: validates an E17 spec by the library's own rplgpu_pose_estimate_check; raises RplGpuError."""
+    rc = load_library().rplgpu_pose_estimate_check(C.byref(spec))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_pose_estimate_check")
+
+
+def _estimate_args(poses, weights, spec):
+    poses = np.ascontiguousarray(poses, np.float32)
+    if poses.ndim != 2 or poses.shape[1] != 4:
+        raise TypeError("poses must be (P, 4) float32")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.uint32)
+        if weights.shape != (len(poses),):
+            raise TypeError("weights must be (P,) uint32 or None")
+    return poses, weights, PoseEstimate.defaults() if spec is None else spec
+
+
+def estimate_host(poses, weights=None, spec: PoseEstimate = None, center: int = 0) -> np.ndarray:
+    """Host only: E17's rule for one group by the library's own rplgpu_estimate_host (no handle, no device);
+    arguments and result as ``RplGpu.estimate_poses``."""
+    poses, weights, spec = _estimate_args(poses, weights, spec)
+    result = np.zeros(ESTIMATE_WORDS, np.uint32)
+    rc = load_library().rplgpu_estimate_host(poses.ctypes.data, len(poses),
+                                             0 if weights is None else weights.ctypes.data, C.byref(spec), center,
+                                             result.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_estimate_host")
+    return result
+
+
+def estimate_pose(result, xy_scale: float, set_: int = 0) -> np.ndarray:
+    """Host only: set ``set_`` of one group's E17 result words as (mean x, mean y, theta, cov xx, xy, yy, R, W),
+    fp64, by the library's own rplgpu_estimate_pose; raises RplGpuError for a set whose W is 0."""
+    result = np.ascontiguousarray(result, np.uint32)
+    if result.shape != (ESTIMATE_WORDS,):
+        raise TypeError("result must be (72,) uint32")
+    out = np.zeros(8, np.float64)
+    rc = load_library().rplgpu_estimate_pose(result.ctypes.data, xy_scale, set_, out.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_estimate_pose")
+    return out

@@ -365,4 +365,15 @@ hipError_t launch_resample(hipStream_t s, const uint32_t *weights, unsigned long
                            unsigned long long out_stride, uint32_t *ancestors, unsigned long long anc_stride,
                            uint32_t *result, uint32_t *scratch);
 
+// E17: a weighted pose list reduced to the sums of a pose estimate (rpl_estimate.hip, include/rplgpu_msg.h).  Two
+// launches on the stream: per-tile sums and counts into the scratch, then one workgroup per group for the
+// RPLGPU_ESTIMATE_WORDS result words.  weights and center may be null (w = 1, centre 0).  The scratch holds
+// estimate_scratch_words(G, P) uint32 words (0 for a G or P that the call refuses) and is 8-byte aligned.
+unsigned long long estimate_scratch_words(uint32_t G, uint32_t P);
+hipError_t launch_estimate(hipStream_t s, const float *poses, unsigned long long pose_stride,
+                           uint32_t poses_per_group, const uint32_t *weights, unsigned long long weight_stride,
+                           uint32_t G, uint32_t P, float xy_scale, unsigned long long gate_r2, long long gate_dot,
+                           const uint32_t *center, unsigned long long center_stride, uint32_t *result,
+                           uint32_t *scratch);
+
 }  // namespace rpl

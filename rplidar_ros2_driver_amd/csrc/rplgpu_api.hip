@@ -2601,6 +2601,184 @@ int32_t rplgpu_resample_poses(rplgpu_handle_t h, const uint32_t *weights, uint32
   return RPLGPU_OK;
 }
 
+// ---- E17: a weighted pose list reduced to a pose estimate (include/rplgpu_msg.h) -------------------------------------
+
+void rplgpu_default_pose_estimate(rplgpu_pose_estimate_t *s) {
+  if (!s) return;
+  s->xy_scale = 1024.0f;
+  s->gate_r2 = 512ull * 512ull;
+  s->gate_dot = 15ll << 36;
+}
+
+int32_t rplgpu_pose_estimate_check(const rplgpu_pose_estimate_t *s) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(s->xy_scale) || !(s->xy_scale > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+uint64_t rplgpu_estimate_scratch_words(uint32_t G, uint32_t P) { return rpl::estimate_scratch_words(G, P); }
+
+// E17's quantisation of one pose entry: one float32 product (this unit is built with -ffp-contract=off), the range
+// test, one round-to-nearest-even (the default rounding mode)
+static bool estimate_quantise(const float *pose, float xy_scale, int32_t q[4]) {
+  const float t[4] = {pose[2] * xy_scale, pose[3] * xy_scale, pose[0] * 1048576.0f, pose[1] * 1048576.0f};
+  for (int k = 0; k < 4; ++k) {
+    if (!(std::fabs(t[k]) < 8388608.0f)) return false;
+  }
+  for (int k = 0; k < 4; ++k) q[k] = (int32_t)std::rint(t[k]);  // X, Y, C, S
+  return true;
+}
+
+int32_t rplgpu_estimate_host(const float *poses, uint32_t P, const uint32_t *weights,
+                             const rplgpu_pose_estimate_t *s, uint32_t center, uint32_t result[72]) {
+  if (!poses || !result || rplgpu_pose_estimate_check(s) != RPLGPU_OK || P == 0 || P > RPLGPU_MAX_POSES)
+    return RPLGPU_ERR_INVALID_ARG;
+  const uint32_t qc = std::min(center, P - 1u);
+  int32_t c[4] = {0, 0, 0, 0};
+  const bool c_in = estimate_quantise(poses + 4u * (size_t)qc, s->xy_scale, c);
+  __int128 sum[2][8] = {};
+  uint32_t count[2][2] = {{0, 0}, {0, 0}};
+  for (uint32_t i = 0; i < P; ++i) {
+    int32_t q[4];
+    if (!estimate_quantise(poses + 4u * (size_t)i, s->xy_scale, q)) continue;
+    const int64_t X = q[0], Y = q[1], C = q[2], S = q[3];
+    const int64_t dX = X - c[0], dY = Y - c[1];
+    const bool gate = c_in && (uint64_t)(dX * dX + dY * dY) <= s->gate_r2 && C * c[2] + S * c[3] >= s->gate_dot;
+    const __int128 w = weights ? weights[i] : 1u;
+    const __int128 term[8] = {w, w * X, w * Y, w * C, w * S, w * (X * X), w * (X * Y), w * (Y * Y)};
+    for (int k = 0; k < (gate ? 2 : 1); ++k) {
+      for (int m = 0; m < 8; ++m) sum[k][m] += term[m];
+      count[k][0] += 1u;
+      count[k][1] += w != 0 ? 1u : 0u;
+    }
+  }
+  result[0] = (c_in ? 0u : 1u) | (count[0][0] != P ? 2u : 0u) | (sum[0][0] == 0 ? 4u : 0u) | (sum[1][0] == 0 ? 8u : 0u);
+  result[1] = qc;
+  result[2] = count[0][0];
+  result[3] = count[0][1];
+  result[4] = count[1][0];
+  result[5] = count[1][1];
+  result[6] = result[7] = 0u;
+  for (int k = 0; k < 2; ++k) {
+    for (int m = 0; m < 8; ++m) {
+      const unsigned __int128 v = (unsigned __int128)sum[k][m];
+      for (int j = 0; j < 4; ++j) result[8 + 32 * k + 4 * m + j] = (uint32_t)(v >> (32 * j));
+    }
+  }
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_estimate_pose(const uint32_t result[72], float xy_scale, uint32_t set, double out[8]) {
+  if (!result || !out || set > 1u || !std::isfinite(xy_scale) || !(xy_scale > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  double v[8];  // each sum rounded to fp64 once
+  for (int m = 0; m < 8; ++m) {
+    unsigned __int128 u = 0;
+    for (int j = 3; j >= 0; --j) u = (u << 32) | result[8 + 32 * set + 4 * m + j];
+    v[m] = (double)(__int128)u;
+  }
+  if (v[0] == 0.0) return RPLGPU_ERR_INVALID_ARG;  // (W < 2^52 is exact, so this is W == 0)
+  const double scale = (double)xy_scale, scale2 = scale * scale;  // (24 x 24 bits: exact)
+  const double mx = v[1] / v[0] / scale, my = v[2] / v[0] / scale;
+  out[0] = mx;
+  out[1] = my;
+  out[2] = std::atan2(v[4], v[3]);
+  out[3] = v[5] / v[0] / scale2 - mx * mx;
+  out[4] = v[6] / v[0] / scale2 - mx * my;
+  out[5] = v[7] / v[0] / scale2 - my * my;
+  out[6] = std::hypot(v[3], v[4]) / (v[0] * 1048576.0);
+  out[7] = v[0];
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_estimate_poses_dev(rplgpu_handle_t h, const float *d_poses, uint64_t pose_stride,
+                                  uint32_t poses_per_group, const uint32_t *d_weights, uint64_t weight_stride,
+                                  uint32_t G, uint32_t P, const rplgpu_pose_estimate_t *s, const uint32_t *d_center,
+                                  uint64_t center_stride, uint32_t *d_result, uint32_t *d_scratch) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+  if (rplgpu_pose_estimate_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_estimate_poses_dev: invalid rplgpu_pose_estimate_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_estimate_poses_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_estimate_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_poses || !d_result || !d_scratch || off(d_poses, 15) || off(d_result, 3) || off(d_scratch, 7) ||
+      off(d_weights, 3) || off(d_center, 3)) {
+    h->err = "rplgpu_estimate_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for the "
+             "pose list, 8 for d_scratch, 4 otherwise)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (pose_stride < 4ull * P || (pose_stride & 3u) || (d_weights && weight_stride < P)) {
+    h->err = "rplgpu_estimate_poses_dev: pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_center && center_stride == 0 && G > 1u) {
+    h->err = "rplgpu_estimate_poses_dev: center_stride must not be 0 with more than one group";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, d_poses, "d_poses") || !device_readable(h, d_result, "d_result") ||
+      !device_readable(h, d_scratch, "d_scratch") || (d_weights && !device_readable(h, d_weights, "d_weights")) ||
+      (d_center && !device_readable(h, d_center, "d_center")))
+    return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_estimate(h->stream, d_poses, pose_stride, poses_per_group, d_weights, weight_stride, G, P,
+                                  s->xy_scale, s->gate_r2, s->gate_dot, d_center, center_stride, d_result,
+                                  d_scratch));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_estimate_poses(rplgpu_handle_t h, const float *poses, uint32_t P, const uint32_t *weights,
+                              const rplgpu_pose_estimate_t *s, uint32_t center, uint32_t result[72]) {
+  if (!h || !poses || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_estimate_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_estimate_poses: invalid rplgpu_pose_estimate_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_estimate_poses: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // one allocation per call (a convenience door, not the hot path): poses | weights | scratch | centre + result,
+  // every part 16-byte aligned
+  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  const size_t o_wt = up16(16u * (size_t)P), o_scr = o_wt + up16(4u * (size_t)P),
+               o_small = o_scr + up16(4u * (size_t)rplgpu_estimate_scratch_words(1, P)),
+               total = o_small + 16u + 4u * RPLGPU_ESTIMATE_WORDS;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_estimate_poses: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t words[RPLGPU_ESTIMATE_WORDS];
+  auto run = [&]() -> int32_t {
+    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);  // the centre word, then the result at + 4 words
+    RPL_HIP(h, hipMemcpyAsync(d, poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    if (weights) RPL_HIP(h, hipMemcpyAsync(d + o_wt, weights, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d_small, &center, 4, hipMemcpyHostToDevice, h->stream));
+    const int32_t rc = rplgpu_estimate_poses_dev(
+        h, reinterpret_cast<const float *>(d), 4ull * P, 0, weights ? reinterpret_cast<const uint32_t *>(d + o_wt) : nullptr,
+        P, 1, P, s, d_small, 0, d_small + 4, reinterpret_cast<uint32_t *>(d + o_scr));
+    if (rc) return rc;
+    RPL_HIP(h, hipMemcpyAsync(words, d_small + 4, sizeof(words), hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;
+  std::memcpy(result, words, sizeof(words));
+  return RPLGPU_OK;
+}
+
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,

@@ -337,6 +337,30 @@ int main(int argc, char **argv) {
       return 19;
     }
     std::printf("resample: ancestors %u %u %u %u, N_eff %.3f of 4\n", anc[0], anc[1], anc[2], anc[3], rr.n_eff);
+    // E17 on the same weights and list, the open gate: W = 470 over four poses of which three are alive; the device
+    // call against the library's own host-only twin, word for word, then the resampled list with every weight 1.
+    rplgpu_pose_estimate_t est;
+    rplgpu_default_pose_estimate(&est);
+    est.gate_r2 = ~0ull;
+    est.gate_dot = INT64_MIN;
+    rplgpu_host::ScanPath::PoseEstimateResult er, er2;
+    uint32_t est_twin[RPLGPU_ESTIMATE_WORDS];
+    if (!path.estimate_pose(plist, weights, est, pr.best_index, er) ||
+        !path.estimate_pose(moved, std::vector<uint32_t>(), est, 0u, er2)) {
+      std::fprintf(stderr, "estimate failed: %s\n", path.last_error().c_str());
+      return 20;
+    }
+    if (rplgpu_estimate_host(plist.data(), 4, weights.data(), &est, pr.best_index, est_twin) != RPLGPU_OK) return 21;
+    if (std::memcmp(er.words, est_twin, sizeof(est_twin)) != 0 || !er.all.valid || er.all.weight != 470.0 ||
+        er.all.poses != 4 || er.all.alive != 3 || er.center != pr.best_index || !er.gated.valid ||
+        std::memcmp(er.words + 8, er.words + 40, 128) != 0 || !er2.all.valid || er2.all.weight != 4.0 ||
+        er2.all.alive != 4) {
+      std::fprintf(stderr, "estimate: wrong answer (W %.0f, %u poses, %u alive, centre %u)\n", er.all.weight,
+                   er.all.poses, er.all.alive, er.center);
+      return 21;
+    }
+    std::printf("estimate: (%.4f, %.4f) heading %.4f, R %.4f; after the move (%.4f, %.4f)\n", er.all.x, er.all.y,
+                er.all.theta, er.all.resultant, er2.all.x, er2.all.y);
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

@@ -30,6 +30,8 @@
 //         -> rplgpu_host::ScanPath::score_poses(scans, ..., field_msg, xyt, weights, result)  (E15)
 //         and its step between two sensor updates (the list redrawn by its weights and moved by the odometry):
 //         -> rplgpu_host::ScanPath::resample_poses(weights, poses, count, u, delta, poses_out, ancestors, result)  (E16)
+//         and what the filter publishes (the weighted list reduced to one pose with a covariance):
+//         -> rplgpu_host::ScanPath::estimate_pose(poses, weights, spec, center, estimate)  (E17)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -539,6 +541,59 @@ class ScanPath {
     result.alive = words[5];
     result.distinct = words[6];
     result.all_dead = (words[7] & 1u) != 0;
+    return true;
+  }
+
+  // ext E17 (include/rplgpu_msg.h): the list `poses` weighed by `weights` (what score_poses returned; empty: every
+  // weight 1, the list as resample_poses leaves it) reduced to a pose with a covariance — what AMCL publishes as
+  // PoseWithCovarianceStamped.  The gate of `spec` is laid around pose `center` (score_poses's best_index).  `all`
+  // is formed over every pose in range, `gated` over the gate; a part whose weight is 0 has valid == false.
+  struct PoseMoments {
+    bool valid = false;
+    double x = 0.0, y = 0.0, theta = 0.0;          // the means; theta = atan2(sum w sin, sum w cos)
+    double cov_xx = 0.0, cov_xy = 0.0, cov_yy = 0.0;
+    double resultant = 0.0;                        // the mean resultant length of the headings (1: all equal)
+    double weight = 0.0;                           // W
+    uint32_t poses = 0, alive = 0;                 // the poses of the set; those with a weight that is not 0
+  };
+  struct PoseEstimateResult {
+    PoseMoments all, gated;
+    uint32_t center = 0;                           // q_c
+    bool center_out_of_range = false, some_out_of_range = false;
+    uint32_t words[RPLGPU_ESTIMATE_WORDS] = {};    // the exact integers (the header's RESULT table)
+  };
+  bool estimate_pose(const std::vector<float> &poses, const std::vector<uint32_t> &weights,
+                     const rplgpu_pose_estimate_t &spec, uint32_t center, PoseEstimateResult &result) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    const size_t n_poses = poses.size() / 4;
+    if (n_poses == 0 || n_poses > RPLGPU_MAX_POSES || poses.size() != 4 * n_poses)
+      return fail("estimate_pose: 1 .. RPLGPU_MAX_POSES poses of four floats");
+    if (!weights.empty() && weights.size() != n_poses) return fail("estimate_pose: one weight per pose, or none");
+    if (rplgpu_estimate_poses(h_, poses.data(), static_cast<uint32_t>(n_poses),
+                              weights.empty() ? nullptr : weights.data(), &spec, center, result.words) != RPLGPU_OK)
+      return note_error();
+    result.center = result.words[1];
+    result.center_out_of_range = (result.words[0] & 1u) != 0;
+    result.some_out_of_range = (result.words[0] & 2u) != 0;
+    PoseMoments *parts[2] = {&result.all, &result.gated};
+    for (uint32_t k = 0; k < 2; ++k) {
+      PoseMoments &m = *parts[k];
+      m = PoseMoments();
+      m.poses = result.words[2 + 2 * k];
+      m.alive = result.words[3 + 2 * k];
+      double v[8];
+      if (rplgpu_estimate_pose(result.words, spec.xy_scale, k, v) != RPLGPU_OK) continue;  // W = 0
+      m.valid = true;
+      m.x = v[0];
+      m.y = v[1];
+      m.theta = v[2];
+      m.cov_xx = v[3];
+      m.cov_xy = v[4];
+      m.cov_yy = v[5];
+      m.resultant = v[6];
+      m.weight = v[7];
+    }
     return true;
   }
 
