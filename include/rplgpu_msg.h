@@ -934,6 +934,95 @@ int32_t rplgpu_estimate_poses(rplgpu_handle_t h, const float *poses, uint32_t P,
  * a set whose W is 0.  A convenience, NOT part of the byte-exact contract: every step is one fp64 rounding. */
 int32_t rplgpu_estimate_pose(const uint32_t result[72], float xy_scale, uint32_t set, double out[8]);
 
+/* ---- E18: a pose list's motion noise drawn on the device (row 4; the step that kept the filter's loop on the host)
+ * ----
+ * A particle filter without motion noise collapses after a few resamplings, so a real caller of E16 takes its
+ * n_delta = M path: one delta per output with the noise folded in.  Drawn on the host that is 3 M normal variates,
+ * M rotations and 16 M bytes copied per time step.  Here a kernel writes E16's d_delta (M deltas per group) from an
+ * odometry increment, three noise scales and a counter-based generator, so that
+ * sample -> resample and move -> score -> estimate queues on one stream without the host.  E16 is unchanged: its
+ * n_delta = M, delta_per_group = 1 input is what this call produces.  Nothing in the reference draws noise, so these
+ * rules ARE the definition (parity unpinned, as E5-E17).  The generator is integers and the rest is fixed float32
+ * operations: the result is byte-exact and depends on no order.
+ *
+ * GENERATOR: Philox4x32-10.  One round maps the counter (c0, c1, c2, c3) under the key (k0, k1) to
+ *   (hi(M1*c2) ^ c1 ^ k0,  lo(M1*c2),  hi(M0*c0) ^ c3 ^ k1,  lo(M0*c0)),   M0 = 0xD2511F53, M1 = 0xCD9E8D57,
+ * hi and lo the halves of the 64-bit product; ten rounds, the key incremented by (0x9E3779B9, 0xBB67AE85) before
+ * rounds 2 .. 10.  Counter 0 0 0 0 under key 0 0 gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8.
+ * For output j of group g, draw i in {0, 1, 2} (rot1, trans, rot2):
+ *   key     = (seed low word, seed high word)
+ *   counter = ((first + j) mod 2^32,  (g << 2) | i,  step low word,  step high word).
+ * step is the caller's time-step number: a new stream per step without reseeding.  first lets a list be made in
+ * pieces or on several devices: output j of a call with first = f is output f + j of a call with first = 0, whatever M.
+ * THE INTEGER NORMAL: Z = the sum of the eight 16-bit halves of the four output words, minus 262140.  An integer,
+ * symmetric, |Z| <= 262140 (exact as a float32), of variance exactly 2863311530 (sigma_Z about 53509.92): Irwin-Hall
+ * with eight terms, cut off at +-4.9 sigma.  That is the definition, not an approximation of something else.
+ * ODOMETRY: eight floats per group at d_odom + 8 g_o, g_o = g when odom_per_group is not 0, else 0; d_odom 16-byte
+ * aligned:  (c1, s1, trans, c2, s2, k1, kt, k2)  — rot1 as a unit vector, the translation along the heading after
+ * rot1, rot2 as a unit vector, and the three noise scales per unit of Z (rplgpu_motion_odometry makes them from an
+ * increment).  Any values are defined, as in E15: the device checks nothing and evaluates no trigonometric function.
+ * ONE OUTPUT, float32, no FMA, every operation rounded once, divides the IEEE divide:
+ *   t = (float)Z_i * k;  q = t*t;  den = 1.0f + q;  nc = (1.0f - q) / den;  ns = (t + t) / den
+ *       (i = 0 with k1 -> n1;  i = 2 with k2 -> n2): the rotation by 2 atan(t), a unit vector without a cosine,
+ *       exactly (1, +-0) at Z = 0
+ *   tr = trans + (float)Z_1 * kt
+ *   a = r1 o n1:  ac = c1*nc1 - s1*ns1;  as = s1*nc1 + c1*ns1       b = r2 o n2 likewise from (c2, s2) and n2
+ *   dc = ac*bc - as*bs;   ds = as*bc + ac*bs;   dx = ac*tr;   dy = as*tr
+ * A NaN is stored as 0x7FC00000 (E16's rule).  Output j of group g is the four floats (dc, ds, dx, dy) at
+ * d_delta + g * delta_stride + 4 j: E16's layout with delta_per_group = 1.  delta_stride in floats, >= 4 M and a
+ * multiple of 4; d_delta 16-byte aligned.  Words at and beyond 4 M of a group are never changed; d_odom is only read.
+ * RESULT: eight 32-bit words per group at d_result + 8 g (4-byte aligned), zeroed by the call on the stream and then
+ * accumulated with integer atomics (the values depend on no order):
+ *   0      the outputs with at least one canonical-NaN entry
+ *   1      the largest |Z| over the 3 M draws
+ *   2, 3   the sum of Z, int64 two's complement, low and high word
+ *   4, 5   the sum of Z^2 (below 2^58), low and high word
+ *   6      0
+ *   7      flags: bit 0 = word 0 is not 0
+ * Words 1 - 5 let a caller see the generator's health at no cost: the mean of Z is 0 and its variance 2863311530.
+ * RPLGPU_ERR_INVALID_ARG, no output changed and nothing queued, for a NULL spec, G = 0 or above 65535 (tiles x groups
+ * is a launch grid), M = 0 or above RPLGPU_MAX_POSES, a missing d_odom / d_delta / d_result, a misaligned pointer
+ * (16 bytes: d_odom, d_delta; 4: d_result) and a delta_stride below 4 M or no multiple of 4.  Asynchronous on the
+ * handle's stream. */
+typedef struct rplgpu_motion_noise {
+  uint64_t seed;   /* the key */
+  uint64_t step;   /* counter words 2 and 3: the time-step number */
+  uint32_t first;  /* the index of the call's output 0 in the group's list */
+  uint32_t reserved;  /* not looked at */
+} rplgpu_motion_noise_t;
+/* seed 0, step 0, first 0 */
+void rplgpu_default_motion_noise(rplgpu_motion_noise_t *s);
+int32_t rplgpu_sample_motion_dev(rplgpu_handle_t h, const float *d_odom, uint32_t odom_per_group, uint32_t G,
+                                 uint32_t M, const rplgpu_motion_noise_t *s, float *d_delta, uint64_t delta_stride,
+                                 uint32_t *d_result);
+/* Host only (no handle, no device): the same rule in plain C++ for ONE group, whose number `group` (below 65535)
+ * enters the counter as g above — the definition a reader can run.  odom: 8 floats; delta_out: 4 M floats; result: 8
+ * words.  RPLGPU_ERR_INVALID_ARG and nothing written for a NULL pointer, a group above 65534 and M = 0 or above
+ * RPLGPU_MAX_POSES. */
+int32_t rplgpu_sample_motion_host(const float odom[8], uint32_t group, uint32_t M, const rplgpu_motion_noise_t *s,
+                                  float *delta_out, uint32_t result[8]);
+/* ONE group (group 0), HOST buffers (the node-side door, rplgpu_host.hpp), arguments as rplgpu_sample_motion_host.
+ * Allocates its device buffers per call and returns when the results are in place: a door, not a hot path. */
+int32_t rplgpu_sample_motion(rplgpu_handle_t h, const float odom[8], uint32_t M, const rplgpu_motion_noise_t *s,
+                             float *delta_out, uint32_t result[8]);
+/* Host only: one Philox4x32-10 block by the rule above, ctr: 4 words, key: 2 words, out: 4 words (out may be ctr).
+ * RPLGPU_ERR_INVALID_ARG for a NULL pointer. */
+int32_t rplgpu_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* Host only: an odometry increment (dx, dy, dtheta) in the OLD base frame and the four coefficients alpha of the
+ * usual differential-drive model become the eight floats of ODOMETRY.  fp64, only * + - sqrt atan2 cos sin, products
+ * and sums from left to right:
+ *   trans = sqrt(dx*dx + dy*dy);   rot1 = atan2(dy, dx) when trans >= 0.01, else 0;
+ *   d = dtheta - rot1;   rot2 = atan2(sin(d), cos(d));
+ *   f1 = min(|rot1|, pi - |rot1|),  f2 = min(|rot2|, pi - |rot2|)  (a backward motion is not a large rotation);
+ *   v1 = alpha[0]*f1*f1 + alpha[1]*trans*trans;   vt = alpha[2]*trans*trans + alpha[3]*(f1*f1 + f2*f2);
+ *   v2 = alpha[0]*f2*f2 + alpha[1]*trans*trans;   sigma_Z = sqrt(2863311530.0);
+ *   out = ((float)cos(rot1), (float)sin(rot1), (float)trans, (float)cos(rot2), (float)sin(rot2),
+ *          (float)(sqrt(v1) / (2.0 * sigma_Z)),  (float)(sqrt(vt) / sigma_Z),  (float)(sqrt(v2) / (2.0 * sigma_Z))).
+ * The rotation noise 2 atan(Z k) is 2 Z k for small angles, hence the 2.  RPLGPU_ERR_INVALID_ARG and nothing written
+ * for a NULL alpha or out; values are not checked (a negative alpha gives a NaN scale).  A convenience, NOT part of
+ * the byte-exact contract: every step is one fp64 rounding of this machine's libm. */
+int32_t rplgpu_motion_odometry(double dx, double dy, double dtheta, const double alpha[4], float out[8]);
+
 #ifdef __cplusplus
 }
 #endif

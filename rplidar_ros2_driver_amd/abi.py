@@ -148,6 +148,12 @@ ABI_SYMBOLS = [
     "rplgpu_estimate_host",
     "rplgpu_estimate_poses",
     "rplgpu_estimate_pose",
+    "rplgpu_default_motion_noise",
+    "rplgpu_sample_motion_dev",
+    "rplgpu_sample_motion_host",
+    "rplgpu_sample_motion",
+    "rplgpu_philox4x32",
+    "rplgpu_motion_odometry",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -430,6 +436,28 @@ class PoseEstimate(C.Structure):
         return cls.defaults(**dict(dict(gate_r2=(1 << 64) - 1, gate_dot=-(1 << 63)), **kw))
 
 
+class MotionNoise(C.Structure):
+    """Mirror of ``rplgpu_motion_noise_t`` (E18: a pose list's motion noise drawn on the device)."""
+
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("step", C.c_uint64),
+        ("first", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "MotionNoise":
+        """The library's own defaults (``rplgpu_default_motion_noise``), then the overrides."""
+        s = cls()
+        load_library().rplgpu_default_motion_noise(C.byref(s))
+        for k, v in kw.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -635,6 +663,13 @@ def load_library() -> C.CDLL:
     lib.rplgpu_estimate_host.argtypes = [vp, u32, vp, C.POINTER(PoseEstimate), u32, vp]
     lib.rplgpu_estimate_poses.argtypes = [vp, vp, u32, vp, C.POINTER(PoseEstimate), u32, vp]
     lib.rplgpu_estimate_pose.argtypes = [vp, C.c_float, u32, vp]
+    lib.rplgpu_default_motion_noise.argtypes = [C.POINTER(MotionNoise)]
+    lib.rplgpu_default_motion_noise.restype = None
+    lib.rplgpu_sample_motion_dev.argtypes = [vp, vp, u32, u32, u32, C.POINTER(MotionNoise), vp, u64, vp]
+    lib.rplgpu_sample_motion_host.argtypes = [vp, u32, u32, C.POINTER(MotionNoise), vp, vp]
+    lib.rplgpu_sample_motion.argtypes = [vp, vp, u32, C.POINTER(MotionNoise), vp, vp]
+    lib.rplgpu_philox4x32.argtypes = [vp, vp, vp]
+    lib.rplgpu_motion_odometry.argtypes = [C.c_double, C.c_double, C.c_double, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1119,6 +1154,24 @@ class RplGpu:
             self._h, poses.ctypes.data, len(poses), 0 if weights is None else weights.ctypes.data, C.byref(spec),
             center, result.ctypes.data))
         return result
+
+    def sample_motion_dev(self, d_odom: int, odom_per_group: int, G: int, M: int, spec: "MotionNoise", d_delta: int,
+                          delta_stride: int, d_result: int):
+        """E18: per group M deltas (E16's ``n_delta = M`` layout) at d_delta + g * delta_stride, drawn from the
+        group's eight odometry floats at d_odom + 8 g (group 0's for every group when odom_per_group is 0) by
+        Philox4x32-10 under ``spec``; eight result words at d_result + 8 g."""
+        self._check(self._lib.rplgpu_sample_motion_dev(
+            self._h, d_odom, odom_per_group, G, M, C.byref(spec), d_delta, delta_stride, d_result))
+
+    def sample_motion(self, odom: np.ndarray, M: int, spec: "MotionNoise" = None):
+        """E18, one group (group 0), host buffers: odom (8,) float32 -> ``(delta (M, 4) float32, result (8,)
+        uint32)``."""
+        odom, spec = _motion_args(odom, spec)
+        delta = np.zeros((M, 4), np.float32)
+        result = np.zeros(8, np.uint32)
+        self._check(self._lib.rplgpu_sample_motion(
+            self._h, odom.ctypes.data, M, C.byref(spec), delta.ctypes.data, result.ctypes.data))
+        return delta, result
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -1682,4 +1735,52 @@ def estimate_pose(result, xy_scale: float, set_: int = 0) -> np.ndarray:
     rc = load_library().rplgpu_estimate_pose(result.ctypes.data, xy_scale, set_, out.ctypes.data)
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_estimate_pose")
+    return out
+
+
+def _motion_args(odom, spec):
+    odom = np.ascontiguousarray(odom, np.float32)
+    if odom.shape != (8,):
+        raise TypeError("odom must be (8,) float32")
+    return odom, MotionNoise.defaults() if spec is None else spec
+
+
+def sample_motion_host(odom, M: int, spec: MotionNoise = None, group: int = 0):
+    """Host only: E18's rule for one group (number ``group``) by the library's own rplgpu_sample_motion_host (no
+    handle, no device); arguments and results as ``RplGpu.sample_motion``."""
+    odom, spec = _motion_args(odom, spec)
+    ok = 0 < M <= MAX_POSES
+    delta = np.zeros((M if ok else 1, 4), np.float32)
+    result = np.zeros(8, np.uint32)
+    rc = load_library().rplgpu_sample_motion_host(odom.ctypes.data, group, M, C.byref(spec), delta.ctypes.data,
+                                                  result.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_sample_motion_host")
+    return delta, result
+
+
+def philox4x32(ctr, key) -> np.ndarray:
+    """Host only: one Philox4x32-10 block, ctr (4,) and key (2,) uint32 -> (4,) uint32, by the library's own
+    rplgpu_philox4x32."""
+    ctr = np.ascontiguousarray(ctr, np.uint32)
+    key = np.ascontiguousarray(key, np.uint32)
+    if ctr.shape != (4,) or key.shape != (2,):
+        raise TypeError("ctr must be (4,) and key (2,) uint32")
+    out = np.zeros(4, np.uint32)
+    rc = load_library().rplgpu_philox4x32(ctr.ctypes.data, key.ctypes.data, out.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_philox4x32")
+    return out
+
+
+def motion_odometry(dx: float, dy: float, dtheta: float, alpha) -> np.ndarray:
+    """Host only: an odometry increment in the old base frame and the model's four alphas -> E18's eight odometry
+    floats (c1, s1, trans, c2, s2, k1, kt, k2), by the library's own rplgpu_motion_odometry."""
+    alpha = np.ascontiguousarray(alpha, np.float64)
+    if alpha.shape != (4,):
+        raise TypeError("alpha must be (4,) float64")
+    out = np.zeros(8, np.float32)
+    rc = load_library().rplgpu_motion_odometry(dx, dy, dtheta, alpha.ctypes.data, out.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_motion_odometry")
     return out

@@ -376,4 +376,11 @@ hipError_t launch_estimate(hipStream_t s, const float *poses, unsigned long long
                            const uint32_t *center, unsigned long long center_stride, uint32_t *result,
                            uint32_t *scratch);
 
+// E18: a pose list's motion noise drawn on the device (rpl_motion.hip, include/rplgpu_msg.h).  Two launches on the
+// stream: the eight result words of every group zeroed, then one thread per output — three Philox4x32-10 blocks, the
+// float32 steps of the header, one 16-byte store — and the tile's statistics added to the words with integer atomics.
+hipError_t launch_motion(hipStream_t s, const float *odom, uint32_t odom_per_group, uint32_t G, uint32_t M,
+                         unsigned long long seed, unsigned long long step, uint32_t first, float *delta,
+                         unsigned long long delta_stride, uint32_t *result);
+
 }  // namespace rpl

@@ -2779,6 +2779,206 @@ int32_t rplgpu_estimate_poses(rplgpu_handle_t h, const float *poses, uint32_t P,
   return RPLGPU_OK;
 }
 
+// ---- E18: a pose list's motion noise drawn on the device (include/rplgpu_msg.h) --------------------------------------
+
+void rplgpu_default_motion_noise(rplgpu_motion_noise_t *s) {
+  if (!s) return;
+  s->seed = 0;
+  s->step = 0;
+  s->first = 0;
+  s->reserved = 0;
+}
+
+static void philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  uint32_t c[4] = {ctr[0], ctr[1], ctr[2], ctr[3]}, k0 = key[0], k1 = key[1];
+  for (int r = 0; r < 10; ++r) {
+    if (r) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const uint64_t p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = (uint32_t)p1;
+    c[2] = n2;
+    c[3] = (uint32_t)p0;
+  }
+  std::memcpy(out, c, 16);
+}
+
+int32_t rplgpu_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  if (!ctr || !key || !out) return RPLGPU_ERR_INVALID_ARG;
+  philox4x32(ctr, key, out);
+  return RPLGPU_OK;
+}
+
+// E18's integer normal of one draw: the eight 16-bit halves of the block, minus their mean
+static int32_t motion_draw(const rplgpu_motion_noise_t *s, uint32_t g, uint32_t j, uint32_t i) {
+  const uint32_t ctr[4] = {s->first + j, (g << 2) | i, (uint32_t)s->step, (uint32_t)(s->step >> 32)};
+  const uint32_t key[2] = {(uint32_t)s->seed, (uint32_t)(s->seed >> 32)};
+  uint32_t w[4];
+  philox4x32(ctr, key, w);
+  int32_t z = -262140;
+  for (int k = 0; k < 4; ++k) z += (int32_t)(w[k] & 0xFFFFu) + (int32_t)(w[k] >> 16);
+  return z;
+}
+
+// E18's noise rotation by 2 atan(Z k) and the composition r o n: float32, every operation rounded once (this unit is
+// built with -ffp-contract=off)
+static void motion_noise(int32_t z, float k, float n[2]) {
+  const float t = (float)z * k, q = t * t, den = 1.0f + q;
+  n[0] = (1.0f - q) / den;
+  n[1] = (t + t) / den;
+}
+static void motion_compose(const float r[2], const float n[2], float a[2]) {
+  const float p0 = r[0] * n[0], p1 = r[1] * n[1], p2 = r[1] * n[0], p3 = r[0] * n[1];
+  a[0] = p0 - p1;
+  a[1] = p2 + p3;
+}
+
+int32_t rplgpu_sample_motion_host(const float odom[8], uint32_t group, uint32_t M, const rplgpu_motion_noise_t *s,
+                                  float *delta_out, uint32_t result[8]) {
+  if (!odom || !s || !delta_out || !result || group > 65534u || M == 0 || M > RPLGPU_MAX_POSES)
+    return RPLGPU_ERR_INVALID_ARG;
+  const float r1[2] = {odom[0], odom[1]}, r2[2] = {odom[3], odom[4]};
+  const float trans = odom[2], k1 = odom[5], kt = odom[6], k2 = odom[7];
+  uint32_t nans = 0, zmax = 0;
+  int64_t sum = 0;
+  uint64_t squares = 0;
+  for (uint32_t j = 0; j < M; ++j) {
+    int32_t z[3];
+    for (uint32_t i = 0; i < 3; ++i) {
+      z[i] = motion_draw(s, group, j, i);
+      zmax = std::max(zmax, (uint32_t)std::abs(z[i]));
+      sum += z[i];
+      squares += (uint64_t)((int64_t)z[i] * z[i]);
+    }
+    float n1[2], n2[2], a[2], b[2], d[2];
+    motion_noise(z[0], k1, n1);
+    motion_noise(z[2], k2, n2);
+    motion_compose(r1, n1, a);
+    motion_compose(r2, n2, b);
+    motion_compose(a, b, d);
+    const float noise = (float)z[1] * kt;
+    const float tr = trans + noise;
+    float v[4] = {d[0], d[1], a[0] * tr, a[1] * tr};
+    const uint32_t qnan = 0x7FC00000u;
+    bool any = false;
+    for (int k = 0; k < 4; ++k) {
+      if (v[k] != v[k]) {
+        std::memcpy(&v[k], &qnan, 4);
+        any = true;
+      }
+    }
+    nans += any ? 1u : 0u;
+    std::memcpy(delta_out + 4u * (size_t)j, v, 16);
+  }
+  result[0] = nans;
+  result[1] = zmax;
+  result[2] = (uint32_t)(uint64_t)sum;
+  result[3] = (uint32_t)((uint64_t)sum >> 32);
+  result[4] = (uint32_t)squares;
+  result[5] = (uint32_t)(squares >> 32);
+  result[6] = 0u;
+  result[7] = nans ? 1u : 0u;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_motion_odometry(double dx, double dy, double dtheta, const double alpha[4], float out[8]) {
+  if (!alpha || !out) return RPLGPU_ERR_INVALID_ARG;
+  const double pi = 3.14159265358979323846;
+  const double trans = std::sqrt(dx * dx + dy * dy);
+  const double rot1 = trans >= 0.01 ? std::atan2(dy, dx) : 0.0;
+  const double d = dtheta - rot1;
+  const double rot2 = std::atan2(std::sin(d), std::cos(d));
+  const double f1 = std::min(std::fabs(rot1), pi - std::fabs(rot1));
+  const double f2 = std::min(std::fabs(rot2), pi - std::fabs(rot2));
+  const double v1 = alpha[0] * f1 * f1 + alpha[1] * trans * trans;
+  const double vt = alpha[2] * trans * trans + alpha[3] * (f1 * f1 + f2 * f2);
+  const double v2 = alpha[0] * f2 * f2 + alpha[1] * trans * trans;
+  const double sigma_z = std::sqrt(2863311530.0);
+  out[0] = (float)std::cos(rot1);
+  out[1] = (float)std::sin(rot1);
+  out[2] = (float)trans;
+  out[3] = (float)std::cos(rot2);
+  out[4] = (float)std::sin(rot2);
+  out[5] = (float)(std::sqrt(v1) / (2.0 * sigma_z));
+  out[6] = (float)(std::sqrt(vt) / sigma_z);
+  out[7] = (float)(std::sqrt(v2) / (2.0 * sigma_z));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_sample_motion_dev(rplgpu_handle_t h, const float *d_odom, uint32_t odom_per_group, uint32_t G,
+                                 uint32_t M, const rplgpu_motion_noise_t *s, float *d_delta, uint64_t delta_stride,
+                                 uint32_t *d_result) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+  if (!s) {
+    h->err = "rplgpu_sample_motion_dev: the rplgpu_motion_noise_t is missing";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_sample_motion_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (M == 0 || M > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_sample_motion_dev: M must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_odom || !d_delta || !d_result || off(d_odom, 15) || off(d_delta, 15) || off(d_result, 3)) {
+    h->err = "rplgpu_sample_motion_dev: a required pointer is missing or a pointer is misaligned (16 bytes for d_odom "
+             "and d_delta, 4 for d_result)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (delta_stride < 4ull * M || (delta_stride & 3u)) {
+    h->err = "rplgpu_sample_motion_dev: delta_stride >= 4 M and a multiple of 4 is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, d_odom, "d_odom") || !device_readable(h, d_delta, "d_delta") ||
+      !device_readable(h, d_result, "d_result"))
+    return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_motion(h->stream, d_odom, odom_per_group, G, M, s->seed, s->step, s->first, d_delta,
+                                delta_stride, d_result));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_sample_motion(rplgpu_handle_t h, const float odom[8], uint32_t M, const rplgpu_motion_noise_t *s,
+                             float *delta_out, uint32_t result[8]) {
+  if (!h || !odom || !s || !delta_out || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (M == 0 || M > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_sample_motion: M must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // one allocation per call (a convenience door, not the hot path): odometry | result | deltas, 16-byte aligned
+  const size_t o_res = 32u, o_dl = 64u, total = o_dl + 16u * (size_t)M;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_sample_motion: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  auto run = [&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(d, odom, 32, hipMemcpyHostToDevice, h->stream));
+    const int32_t rc = rplgpu_sample_motion_dev(h, reinterpret_cast<const float *>(d), 0, 1, M, s,
+                                                reinterpret_cast<float *>(d + o_dl), 4ull * M,
+                                                reinterpret_cast<uint32_t *>(d + o_res));
+    if (rc) return rc;
+    RPL_HIP(h, hipMemcpyAsync(delta_out, d + o_dl, 16u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d + o_res, 32, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;
+  std::memcpy(result, small, 32);
+  return RPLGPU_OK;
+}
+
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,

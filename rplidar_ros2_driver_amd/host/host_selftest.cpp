@@ -361,6 +361,43 @@ int main(int argc, char **argv) {
     }
     std::printf("estimate: (%.4f, %.4f) heading %.4f, R %.4f; after the move (%.4f, %.4f)\n", er.all.x, er.all.y,
                 er.all.theta, er.all.resultant, er2.all.x, er2.all.y);
+    // E18: one metre ahead with every alpha 0 is the delta (1, 0, 1, 0) four times — what the E16 leg above used; with
+    // noise the device call against the library's own host-only twin, byte for byte, and the noisy deltas through
+    // E16's one-delta-per-output path against its twin.
+    const double no_noise[4] = {0.0, 0.0, 0.0, 0.0}, some_noise[4] = {0.05, 0.02, 0.04, 0.01};
+    rplgpu_motion_noise_t mspec;
+    rplgpu_default_motion_noise(&mspec);
+    mspec.seed = 2026;
+    mspec.step = 18;
+    std::vector<float> quiet, noisy, noisy_twin(16), moved2, twin2(16);
+    rplgpu_host::ScanPath::MotionNoiseResult noise0, noise1;
+    if (!path.sample_motion(1.0, 0.0, 0.0, no_noise, mspec, 4, quiet, noise0) ||
+        !path.sample_motion(1.0, 0.0, 0.1, some_noise, mspec, 4, noisy, noise1)) {
+      std::fprintf(stderr, "sample motion failed: %s\n", path.last_error().c_str());
+      return 22;
+    }
+    float odom[8];
+    uint32_t motion_twin[8];
+    if (rplgpu_motion_odometry(1.0, 0.0, 0.1, some_noise, odom) != RPLGPU_OK ||
+        rplgpu_sample_motion_host(odom, 0, 4, &mspec, noisy_twin.data(), motion_twin) != RPLGPU_OK)
+      return 23;
+    bool quiet_ok = quiet.size() == 16;
+    for (size_t k = 0; quiet_ok && k < 16; ++k) quiet_ok = quiet[k] == ahead[k % 4];
+    if (!quiet_ok || noisy.size() != 16 || std::memcmp(noisy.data(), noisy_twin.data(), 64) != 0 ||
+        noise1.nan_outputs != 0 || noise1.max_abs != motion_twin[1] || noise1.max_abs == 0 || noise1.max_abs > 262140 ||
+        noise1.sum != noise0.sum || noise1.sum_squares != noise0.sum_squares || std::memcmp(noisy.data(), noisy.data() + 4, 16) == 0) {
+      std::fprintf(stderr, "sample motion: wrong answer (%u NaN, max |Z| %u)\n", noise1.nan_outputs, noise1.max_abs);
+      return 23;
+    }
+    if (!path.resample_poses(weights, plist, 4, 0u, noisy, moved2, anc, rr) ||
+        rplgpu_resample_host(weights.data(), 4, 4, 0u, plist.data(), noisy.data(), 4, twin2.data(), twin_anc.data(),
+                             twin_words) != RPLGPU_OK ||
+        std::memcmp(moved2.data(), twin2.data(), 64) != 0 || std::memcmp(moved2.data(), moved.data(), 64) == 0) {
+      std::fprintf(stderr, "sample motion -> resample: wrong answer\n");
+      return 24;
+    }
+    std::printf("motion noise: 4 deltas, max |Z| %u, first (%.4f, %.4f, %.4f, %.4f)\n", noise1.max_abs, noisy[0], noisy[1],
+                noisy[2], noisy[3]);
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

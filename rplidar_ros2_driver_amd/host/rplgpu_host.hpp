@@ -32,6 +32,8 @@
 //         -> rplgpu_host::ScanPath::resample_poses(weights, poses, count, u, delta, poses_out, ancestors, result)  (E16)
 //         and what the filter publishes (the weighted list reduced to one pose with a covariance):
 //         -> rplgpu_host::ScanPath::estimate_pose(poses, weights, spec, center, estimate)  (E17)
+//         and the motion noise that step needs (one delta per output, drawn from the odometry increment):
+//         -> rplgpu_host::ScanPath::sample_motion(dx, dy, dtheta, alpha, spec, count, delta, result)  (E18)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -594,6 +596,38 @@ class ScanPath {
       m.resultant = v[6];
       m.weight = v[7];
     }
+    return true;
+  }
+
+  // ext E18 (include/rplgpu_msg.h): `count` deltas (dc, ds, dx, dy) for resample_poses, each the odometry increment
+  // (dx, dy, dtheta in the old base frame) with its own motion noise — the differential-drive model's four alphas
+  // through rplgpu_motion_odometry, the draws from Philox4x32-10 under `spec` (seed; step: the time-step number, a
+  // new stream per step; first: where this call's outputs start in a list made in pieces).  result: the health of
+  // the draws, whose mean is 0 and whose variance is 2863311530.
+  struct MotionNoiseResult {
+    uint32_t nan_outputs = 0;   // deltas with a NaN entry (stored as 0x7FC00000)
+    uint32_t max_abs = 0;       // the largest |Z| (at most 262140)
+    int64_t sum = 0;            // the sum of Z over the 3 x count draws
+    uint64_t sum_squares = 0;   // the sum of Z^2
+    double mean = 0.0, variance = 0.0;
+  };
+  bool sample_motion(double dx, double dy, double dtheta, const double alpha[4], const rplgpu_motion_noise_t &spec,
+                     uint32_t count, std::vector<float> &delta, MotionNoiseResult &result) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    if (count == 0 || count > RPLGPU_MAX_POSES) return fail("sample_motion: count must be in 1 .. RPLGPU_MAX_POSES");
+    float odom[8];
+    if (rplgpu_motion_odometry(dx, dy, dtheta, alpha, odom) != RPLGPU_OK) return fail("sample_motion: alpha is missing");
+    delta.assign(4 * static_cast<size_t>(count), 0.0f);
+    uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_sample_motion(h_, odom, count, &spec, delta.data(), words) != RPLGPU_OK) return note_error();
+    result.nan_outputs = words[0];
+    result.max_abs = words[1];
+    result.sum = static_cast<int64_t>(static_cast<uint64_t>(words[2]) | (static_cast<uint64_t>(words[3]) << 32));
+    result.sum_squares = static_cast<uint64_t>(words[4]) | (static_cast<uint64_t>(words[5]) << 32);
+    const double n = 3.0 * static_cast<double>(count);
+    result.mean = static_cast<double>(result.sum) / n;
+    result.variance = static_cast<double>(result.sum_squares) / n - result.mean * result.mean;
     return true;
   }
 
