@@ -1023,6 +1023,98 @@ int32_t rplgpu_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t
  * the byte-exact contract: every step is one fp64 rounding of this machine's libm. */
 int32_t rplgpu_motion_odometry(double dx, double dy, double dtheta, const double alpha[4], float out[8]);
 
+/* ---- E19: a pose list seeded over a grid's free cells on the device (row 4; how the filter's list comes to be) ----
+ * E15 - E18 run a particle filter's loop on the device; this call makes the list the loop starts from, and the
+ * poses AMCL's recovery injects when the average weight drops: M poses in E15 / E16's layout, drawn uniformly over
+ * the FREE cells of a grid that is already on the device (E14's rplgpu_map_grid_dev output, an E11 / E12 grid),
+ * written wherever the caller points — the tail of E16's output list is such a place.  So
+ * initialise -> score -> estimate -> resample, move and inject -> score queues on one stream with no read of a map
+ * or a list.  Nothing in the reference seeds poses, so these rules ARE the definition (parity unpinned, as E5-E18).
+ * Everything is integers except four fixed float32 operations per coordinate: the output is byte-exact and depends
+ * on no order.
+ *
+ * GRID: group g reads int8 cells at d_grid + g_f * grid_stride, g_f = g when grid_per_group is not 0, else 0; E11's
+ * layout and rules (4-byte aligned, grid_stride >= width * height and a multiple of 4).  The grid is only read and
+ * must not change while the call runs; bytes at and beyond width * height never count.  A cell is FREE iff
+ * free_lo <= (int8)byte <= free_hi.  F = the number of free cells, ordered by their index cy * width + cx.
+ * F = 0: every cell counts as free (F := width * height) and flag bit 0 is set; nothing divides by zero (E16's
+ * S = 0 convention).
+ * HEADING TABLE: H entries (c, s), 2 floats each, at d_headings (8-byte aligned), 1 <= H <= 65536, shared by all
+ * groups; entries are copied bit for bit: the device evaluates no trigonometric function.
+ * DRAW for output j of group g: one Philox4x32-10 block by E18's rule under E18's rplgpu_motion_noise_t,
+ *   key     = (seed low word, seed high word)
+ *   counter = ((first + j) mod 2^32,  (g << 2) | 3,  step low word,  step high word)
+ * — draw index 3 is the one E18 leaves unused, so E19's stream never meets E18's under the same seed and step.  Of
+ * the output words (p0, p1, p2, p3):
+ *   r = (p0 * F) >> 32 (a 64-bit product, F <= 2^24): the cell is the r-th free cell, so each free cell is drawn
+ *       with probability floor or ceil of 2^32 / F over 2^32;  (cx, cy) = (index mod width, index / width)
+ *   k = (p1 * H) >> 32;  (c, s) = table entry k
+ *   fx = ((float)(p2 >> 24) + 0.5f) * (1.0f / 256.0f), fy likewise from p3; both 0.5f with flags bit 0
+ *   ux = (float)cx + fx (exact: 12 + 9 bits);  x = origin_x + ux * resolution, float32, no FMA: the product is
+ *       rounded, then the sum;  y likewise.
+ * OUTPUT j of group g is (c, s, x, y) at d_poses_out + g * out_stride + 4 j: E15 / E16's layout, out_stride in
+ * floats, >= 4 M and a multiple of 4, d_poses_out 16-byte aligned — it may point into the middle of a longer list
+ * (the injection).  Optionally the chosen cell index goes to d_cells_out + g * cell_stride + j (cell_stride >= M).
+ * Words at and beyond M of a group are never changed.  With first = f output j is output f + j of a call with
+ * first = 0, whatever M: a list can be made in pieces.
+ * ROUND TRIP: float32 rounding can put (x, y) into a neighbouring cell when the origin is far from 0.  The rule does
+ * not promise otherwise; it counts: an output is OFF-CELL when the E11 CELL of (x, y) (same rule, same IEEE divides,
+ * the spec's origin and resolution) does not exist or is not (cx, cy).
+ * RESULT: eight 32-bit words per group at d_result + 8 g (4-byte aligned), set by the call on the stream:
+ *   0      F, after the F = 0 substitution
+ *   1      the OFF-CELL outputs
+ *   2      the smallest chosen cell index
+ *   3      the largest chosen cell index
+ *   4 - 6  0
+ *   7      flags: bit 0 = no cell was free; bit 1 = word 1 is not 0
+ * SCRATCH is the caller's, as in E16 / E17: rplgpu_seed_scratch_words(G_f, width, height) uint32 words, 8-byte
+ * aligned, G_f = G when grid_per_group is not 0, else 1 (about 1.3 bits per cell: a bit mask of the free cells and
+ * running counts, never a list of their indices).
+ * RPLGPU_ERR_INVALID_ARG, no output changed and nothing queued, for a spec the check refuses, a NULL noise spec,
+ * G = 0 or above 65535, M = 0 or above RPLGPU_MAX_POSES, H = 0 or above 65536, a missing d_grid / d_headings /
+ * d_poses_out / d_result / d_scratch, a misaligned pointer (16 bytes: d_poses_out; 8: d_headings, d_scratch; 4:
+ * d_grid, d_cells_out, d_result), a grid_stride below width * height or no multiple of 4, an out_stride below 4 M or
+ * no multiple of 4, and a cell_stride below M with d_cells_out set.  Asynchronous on the handle's stream. */
+typedef struct rplgpu_pose_seed {
+  float    origin_x, origin_y, resolution;  /* the grid: as rplgpu_pose_score_t */
+  uint32_t width, height;                   /* 1 .. RPLGPU_MAX_OCC_DIM */
+  int32_t  free_lo, free_hi;                /* a cell is FREE iff free_lo <= (int8)byte <= free_hi */
+  uint32_t flags;                           /* bit 0: cell centres, no jitter; other bits 0 */
+} rplgpu_pose_seed_t;
+/* E11's default grid (0.05 m, 1024 x 1024 cells, origin (-25.6, -25.6)), free_lo = free_hi = 0 (the cells E11 or
+ * E14 cleared), flags 0 */
+void rplgpu_default_pose_seed(rplgpu_pose_seed_t *s);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL, a value that is not finite, resolution <= 0,
+ * a dimension of 0 or above RPLGPU_MAX_OCC_DIM, free_lo or free_hi outside [-128, 127], free_lo > free_hi, or flags
+ * above 1.  The device path uses this function. */
+int32_t rplgpu_pose_seed_check(const rplgpu_pose_seed_t *s);
+/* Host only: the scratch of rplgpu_seed_poses_dev in uint32 words; 0 for G_f = 0 or above 65535 or a dimension of 0
+ * or above RPLGPU_MAX_OCC_DIM. */
+uint64_t rplgpu_seed_scratch_words(uint32_t G_f, uint32_t width, uint32_t height);
+/* Host only: entry k of the H entries at cs = ((float)cos(2 pi k / H), (float)sin(the same)), taken in fp64 and
+ * rounded once; entry 0 is exactly (1, 0).  RPLGPU_ERR_INVALID_ARG and nothing written for a NULL cs, H = 0 or above
+ * 65536.  A convenience, NOT part of the byte-exact contract: every step is one fp64 rounding of this machine's
+ * libm. */
+int32_t rplgpu_seed_headings(uint32_t H, float *cs);
+int32_t rplgpu_seed_poses_dev(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, const int8_t *d_grid,
+                              uint64_t grid_stride, uint32_t grid_per_group, const float *d_headings, uint32_t H,
+                              uint32_t G, uint32_t M, const rplgpu_motion_noise_t *noise, float *d_poses_out,
+                              uint64_t out_stride, uint32_t *d_cells_out, uint64_t cell_stride, uint32_t *d_result,
+                              uint32_t *d_scratch);
+/* Host only (no handle, no device): the same rule in plain C++ for ONE group, whose number `group` (below 65535)
+ * enters the counter as g above — the definition a reader can run.  grid: width * height bytes; headings: 2 H
+ * floats; poses_out: 4 M floats; cells_out (optional): M words; result: 8 words.  RPLGPU_ERR_INVALID_ARG and nothing
+ * written for a spec the check refuses, a NULL pointer other than cells_out, a group above 65534, H = 0 or above
+ * 65536 and M = 0 or above RPLGPU_MAX_POSES. */
+int32_t rplgpu_seed_poses_host(const rplgpu_pose_seed_t *s, const int8_t *grid, const float *headings, uint32_t H,
+                               uint32_t group, uint32_t M, const rplgpu_motion_noise_t *noise, float *poses_out,
+                               uint32_t *cells_out, uint32_t result[8]);
+/* ONE group (group 0), HOST buffers (the node-side door, rplgpu_host.hpp), arguments as rplgpu_seed_poses_host.
+ * Allocates its device buffers per call and returns when the results are in place: a door, not a hot path. */
+int32_t rplgpu_seed_poses(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, const int8_t *grid, const float *headings,
+                          uint32_t H, uint32_t M, const rplgpu_motion_noise_t *noise, float *poses_out,
+                          uint32_t *cells_out, uint32_t result[8]);
+
 #ifdef __cplusplus
 }
 #endif

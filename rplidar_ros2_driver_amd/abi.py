@@ -154,6 +154,13 @@ ABI_SYMBOLS = [
     "rplgpu_sample_motion",
     "rplgpu_philox4x32",
     "rplgpu_motion_odometry",
+    "rplgpu_default_pose_seed",
+    "rplgpu_pose_seed_check",
+    "rplgpu_seed_scratch_words",
+    "rplgpu_seed_headings",
+    "rplgpu_seed_poses_dev",
+    "rplgpu_seed_poses_host",
+    "rplgpu_seed_poses",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -458,6 +465,36 @@ class MotionNoise(C.Structure):
         return s
 
 
+class PoseSeed(C.Structure):
+    """Mirror of ``rplgpu_pose_seed_t`` (E19: a pose list seeded over a grid's free cells on the device)."""
+
+    _fields_ = [
+        ("origin_x", C.c_float),
+        ("origin_y", C.c_float),
+        ("resolution", C.c_float),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("free_lo", C.c_int32),
+        ("free_hi", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "PoseSeed":
+        """The library's own defaults (``rplgpu_default_pose_seed``), then the overrides."""
+        s = cls()
+        load_library().rplgpu_default_pose_seed(C.byref(s))
+        for k, v in kw.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s
+
+    def check(self) -> int:
+        """``rplgpu_pose_seed_check``: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_pose_seed_check(C.byref(self)))
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -670,6 +707,17 @@ def load_library() -> C.CDLL:
     lib.rplgpu_sample_motion.argtypes = [vp, vp, u32, C.POINTER(MotionNoise), vp, vp]
     lib.rplgpu_philox4x32.argtypes = [vp, vp, vp]
     lib.rplgpu_motion_odometry.argtypes = [C.c_double, C.c_double, C.c_double, vp, vp]
+    lib.rplgpu_default_pose_seed.argtypes = [C.POINTER(PoseSeed)]
+    lib.rplgpu_default_pose_seed.restype = None
+    lib.rplgpu_pose_seed_check.argtypes = [C.POINTER(PoseSeed)]
+    lib.rplgpu_seed_scratch_words.argtypes = [u32, u32, u32]
+    lib.rplgpu_seed_scratch_words.restype = C.c_uint64
+    lib.rplgpu_seed_headings.argtypes = [u32, vp]
+    lib.rplgpu_seed_poses_dev.argtypes = [vp, C.POINTER(PoseSeed), vp, u64, u32, vp, u32, u32, u32,
+                                          C.POINTER(MotionNoise), vp, u64, vp, u64, vp, vp]
+    lib.rplgpu_seed_poses_host.argtypes = [C.POINTER(PoseSeed), vp, vp, u32, u32, u32, C.POINTER(MotionNoise), vp, vp,
+                                           vp]
+    lib.rplgpu_seed_poses.argtypes = [vp, C.POINTER(PoseSeed), vp, vp, u32, u32, C.POINTER(MotionNoise), vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1172,6 +1220,31 @@ class RplGpu:
         self._check(self._lib.rplgpu_sample_motion(
             self._h, odom.ctypes.data, M, C.byref(spec), delta.ctypes.data, result.ctypes.data))
         return delta, result
+
+    def seed_poses_dev(self, spec: "PoseSeed", d_grid: int, grid_stride: int, grid_per_group: int, d_headings: int,
+                       H: int, G: int, M: int, noise: "MotionNoise", d_poses_out: int, out_stride: int,
+                       d_cells_out: int, cell_stride: int, d_result: int, d_scratch: int):
+        """E19: per group M poses (E15 / E16's layout) at d_poses_out + g * out_stride, drawn uniformly over the free
+        cells of the group's grid at d_grid + g * grid_stride (group 0's for every group when grid_per_group is 0),
+        headings from the H-entry table, by Philox4x32-10 under ``noise`` (draw index 3); the chosen cell indices at
+        d_cells_out (optional), eight result words at d_result + 8 g.  d_scratch: ``seed_scratch_words(G_f, width,
+        height)`` uint32 words."""
+        self._check(self._lib.rplgpu_seed_poses_dev(
+            self._h, C.byref(spec), d_grid, grid_stride, grid_per_group, d_headings, H, G, M, C.byref(noise),
+            d_poses_out, out_stride, d_cells_out, cell_stride, d_result, d_scratch))
+
+    def seed_poses(self, grid: np.ndarray, headings: np.ndarray, M: int, spec: "PoseSeed" = None,
+                   noise: "MotionNoise" = None):
+        """E19, one group (group 0), host buffers: grid (height, width) int8, headings (H, 2) float32 -> ``(poses
+        (M, 4) float32, cells (M,) uint32, result (8,) uint32)``."""
+        grid, headings, spec, noise = _seed_args(grid, headings, spec, noise)
+        poses = np.zeros((M, 4), np.float32)
+        cells = np.zeros(M, np.uint32)
+        result = np.zeros(8, np.uint32)
+        self._check(self._lib.rplgpu_seed_poses(
+            self._h, C.byref(spec), grid.ctypes.data, headings.ctypes.data, len(headings), M, C.byref(noise),
+            poses.ctypes.data, cells.ctypes.data, result.ctypes.data))
+        return poses, cells, result
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -1784,3 +1857,46 @@ def motion_odometry(dx: float, dy: float, dtheta: float, alpha) -> np.ndarray:
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_motion_odometry")
     return out
+
+
+def _seed_args(grid, headings, spec, noise):
+    spec = PoseSeed.defaults() if spec is None else spec
+    grid = np.ascontiguousarray(grid, np.int8)
+    headings = np.ascontiguousarray(headings, np.float32)
+    if grid.size != spec.width * spec.height:
+        raise TypeError("grid must hold width * height int8 cells")
+    if headings.ndim != 2 or headings.shape[1] != 2:
+        raise TypeError("headings must be (H, 2) float32")
+    return grid, headings, spec, MotionNoise.defaults() if noise is None else noise
+
+
+def seed_scratch_words(G_f: int, width: int, height: int) -> int:
+    """Host only: the uint32 words of scratch seed_poses_dev needs for G_f grids of width x height cells; 0 for
+    arguments the call refuses."""
+    return int(load_library().rplgpu_seed_scratch_words(G_f, width, height))
+
+
+def seed_headings(H: int) -> np.ndarray:
+    """Host only: the H headings (cos, sin)(2 pi k / H) as (H, 2) float32, by the library's own
+    rplgpu_seed_headings."""
+    out = np.zeros((max(H, 1), 2), np.float32)
+    rc = load_library().rplgpu_seed_headings(H, out.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_seed_headings")
+    return out
+
+
+def seed_poses_host(grid, headings, M: int, spec: PoseSeed = None, noise: MotionNoise = None, group: int = 0):
+    """Host only: E19's rule for one group (number ``group``) by the library's own rplgpu_seed_poses_host (no handle,
+    no device); arguments and results as ``RplGpu.seed_poses``."""
+    grid, headings, spec, noise = _seed_args(grid, headings, spec, noise)
+    ok = 0 < M <= MAX_POSES
+    poses = np.zeros((M if ok else 1, 4), np.float32)
+    cells = np.zeros(M if ok else 1, np.uint32)
+    result = np.zeros(8, np.uint32)
+    rc = load_library().rplgpu_seed_poses_host(C.byref(spec), grid.ctypes.data, headings.ctypes.data, len(headings),
+                                               group, M, C.byref(noise), poses.ctypes.data, cells.ctypes.data,
+                                               result.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_seed_poses_host")
+    return poses, cells, result

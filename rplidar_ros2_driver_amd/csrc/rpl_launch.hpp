@@ -383,4 +383,22 @@ hipError_t launch_motion(hipStream_t s, const float *odom, uint32_t odom_per_gro
                          unsigned long long seed, unsigned long long step, uint32_t first, float *delta,
                          unsigned long long delta_stride, uint32_t *result);
 
+// E19: a pose list seeded over a grid's free cells (rpl_seed.hip, include/rplgpu_msg.h).  Three launches on the
+// stream: the free cells of every grid indexed as bit masks with running counts (the scratch), the block counts
+// scanned and the result words started, then one thread per output — one Philox4x32-10 block, three bisections to the
+// r-th free cell, the float32 steps of the header, one 16-byte store — and the tile's statistics added to the words
+// with integer atomics.  seed_scratch_words: uint32 words for n_grids grids; 0 for arguments launch_seed refuses.
+struct SeedK {
+  float origin_x, origin_y, resolution;
+  uint32_t width, height;
+  int32_t free_lo, free_hi;
+  uint32_t centres;  // flags bit 0: no jitter
+};
+unsigned long long seed_scratch_words(uint32_t n_grids, uint32_t width, uint32_t height);
+hipError_t launch_seed(hipStream_t s, const SeedK &k, const int8_t *grid, unsigned long long grid_stride,
+                       uint32_t grid_per_group, const float *headings, uint32_t H, uint32_t G, uint32_t M,
+                       unsigned long long seed, unsigned long long step, uint32_t first, float *poses_out,
+                       unsigned long long out_stride, uint32_t *cells_out, unsigned long long cell_stride,
+                       uint32_t *result, uint32_t *scratch);
+
 }  // namespace rpl

@@ -19,6 +19,7 @@
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
+#include "rpl_philox.hpp"
 #include "rplgpu_msg.h"
 
 namespace rpl {
@@ -28,29 +29,14 @@ typedef unsigned long long u64;
 typedef long long i64;
 typedef float mo_f32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kMoTile = kBlock;  // outputs per tile: one per thread
-constexpr uint32_t kMoMul0 = 0xD2511F53u, kMoMul1 = 0xCD9E8D57u;
-constexpr uint32_t kMoKey0 = 0x9E3779B9u, kMoKey1 = 0xBB67AE85u;
-constexpr int kMoRounds = 10;
 constexpr int32_t kMoZBias = 262140;  // 4 * 65535: the mean of the eight halves
 
-// Philox4x32-10 on the counter (c0, c1, c2, c3) under the key (k0, k1), reduced to Z
+// Philox4x32-10 (rpl_philox.hpp) on the counter (c0, c1, c2, c3) under the key (k0, k1), reduced to Z
 __device__ __forceinline__ int32_t mo_draw(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                            uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < kMoRounds; ++r) {
-    if (r) {
-      k0 += kMoKey0;
-      k1 += kMoKey1;
-    }
-    const uint32_t h0 = __umulhi(kMoMul0, c0), l0 = kMoMul0 * c0;
-    const uint32_t h1 = __umulhi(kMoMul1, c2), l1 = kMoMul1 * c2;
-    c0 = h1 ^ c1 ^ k0;
-    c1 = l1;
-    c2 = h0 ^ c3 ^ k1;
-    c3 = l0;
-  }
-  const uint32_t halves = (c0 & 0xFFFFu) + (c0 >> 16) + (c1 & 0xFFFFu) + (c1 >> 16) + (c2 & 0xFFFFu) + (c2 >> 16) +
-                          (c3 & 0xFFFFu) + (c3 >> 16);
+  const Philox4 p = philox4x32_10(c0, c1, c2, c3, k0, k1);
+  const uint32_t halves = (p.w0 & 0xFFFFu) + (p.w0 >> 16) + (p.w1 & 0xFFFFu) + (p.w1 >> 16) + (p.w2 & 0xFFFFu) +
+                          (p.w2 >> 16) + (p.w3 & 0xFFFFu) + (p.w3 >> 16);
   return (int32_t)halves - kMoZBias;
 }
 

@@ -2979,6 +2979,237 @@ int32_t rplgpu_sample_motion(rplgpu_handle_t h, const float odom[8], uint32_t M,
   return RPLGPU_OK;
 }
 
+// ---- E19: a pose list seeded over a grid's free cells on the device (include/rplgpu_msg.h) ---------------------------
+
+void rplgpu_default_pose_seed(rplgpu_pose_seed_t *s) {
+  if (!s) return;
+  s->origin_x = -25.6f;
+  s->origin_y = -25.6f;
+  s->resolution = 0.05f;
+  s->width = 1024;
+  s->height = 1024;
+  s->free_lo = 0;
+  s->free_hi = 0;
+  s->flags = 0;
+}
+
+int32_t rplgpu_pose_seed_check(const rplgpu_pose_seed_t *s) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(s->origin_x) || !std::isfinite(s->origin_y) || !std::isfinite(s->resolution))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!(s->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  if (s->width == 0 || s->width > RPLGPU_MAX_OCC_DIM || s->height == 0 || s->height > RPLGPU_MAX_OCC_DIM)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (s->free_lo < -128 || s->free_lo > 127 || s->free_hi < -128 || s->free_hi > 127 || s->free_lo > s->free_hi)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (s->flags > 1u) return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+uint64_t rplgpu_seed_scratch_words(uint32_t G_f, uint32_t width, uint32_t height) {
+  return rpl::seed_scratch_words(G_f, width, height);
+}
+
+int32_t rplgpu_seed_headings(uint32_t H, float *cs) {
+  if (!cs || H == 0 || H > 65536u) return RPLGPU_ERR_INVALID_ARG;
+  const double two_pi = 6.283185307179586476925286766559;
+  for (uint32_t k = 0; k < H; ++k) {
+    const double a = two_pi * (double)k / (double)H;
+    cs[2u * k] = k == 0 ? 1.0f : (float)std::cos(a);
+    cs[2u * k + 1u] = k == 0 ? 0.0f : (float)std::sin(a);
+  }
+  return RPLGPU_OK;
+}
+
+// the E11 cell rule on the host: float32, every operation rounded once (this unit is built with -ffp-contract=off)
+static bool seed_cell(float x, float y, const rplgpu_pose_seed_t *s, int32_t *cx, int32_t *cy) {
+  const float du = x - s->origin_x, dv = y - s->origin_y;
+  const float u = du / s->resolution, v = dv / s->resolution;
+  const float fu = std::floor(u), fv = std::floor(v);
+  if (!(std::fabs(fu) < 1048576.0f && std::fabs(fv) < 1048576.0f)) return false;
+  *cx = (int32_t)fu;
+  *cy = (int32_t)fv;
+  return true;
+}
+
+int32_t rplgpu_seed_poses_host(const rplgpu_pose_seed_t *s, const int8_t *grid, const float *headings, uint32_t H,
+                               uint32_t group, uint32_t M, const rplgpu_motion_noise_t *noise, float *poses_out,
+                               uint32_t *cells_out, uint32_t result[8]) {
+  if (rplgpu_pose_seed_check(s) != RPLGPU_OK || !grid || !headings || !noise || !poses_out || !result ||
+      group > 65534u || H == 0 || H > 65536u || M == 0 || M > RPLGPU_MAX_POSES)
+    return RPLGPU_ERR_INVALID_ARG;
+  const uint32_t cells = s->width * s->height;
+  auto is_free = [&](uint32_t i) { return grid[i] >= s->free_lo && grid[i] <= s->free_hi; };
+  uint32_t F = 0;
+  for (uint32_t i = 0; i < cells; ++i) F += is_free(i) ? 1u : 0u;
+  const bool none = F == 0;
+  if (none) F = cells;
+  // the draws first, then ONE walk over the cells in index order hands every draw its cell: the outputs sorted by r
+  std::vector<uint32_t> words(4u * (size_t)M), order(M), cell(M);
+  const uint32_t key[2] = {(uint32_t)noise->seed, (uint32_t)(noise->seed >> 32)};
+  for (uint32_t j = 0; j < M; ++j) {
+    const uint32_t ctr[4] = {noise->first + j, (group << 2) | 3u, (uint32_t)noise->step,
+                             (uint32_t)(noise->step >> 32)};
+    philox4x32(ctr, key, &words[4u * (size_t)j]);
+    order[j] = j;
+  }
+  auto rank = [&](uint32_t j) { return (uint32_t)(((uint64_t)words[4u * (size_t)j] * F) >> 32); };
+  if (none) {
+    for (uint32_t j = 0; j < M; ++j) cell[j] = rank(j);
+  } else {
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rank(a) < rank(b); });
+    uint32_t seen = 0, q = 0;  // free cells in front of cell i; outputs served
+    for (uint32_t i = 0; i < cells && q < M; ++i) {
+      if (!is_free(i)) continue;
+      while (q < M && rank(order[q]) == seen) cell[order[q++]] = i;
+      ++seen;
+    }
+  }
+  uint32_t off = 0, lo = 0xFFFFFFFFu, hi = 0;
+  const bool centres = (s->flags & 1u) != 0;
+  for (uint32_t j = 0; j < M; ++j) {
+    const uint32_t *p = &words[4u * (size_t)j];
+    const uint32_t k = (uint32_t)(((uint64_t)p[1] * H) >> 32);
+    const uint32_t cy = cell[j] / s->width, cx = cell[j] - cy * s->width;
+    const float fx = centres ? 0.5f : ((float)(p[2] >> 24) + 0.5f) * (1.0f / 256.0f);
+    const float fy = centres ? 0.5f : ((float)(p[3] >> 24) + 0.5f) * (1.0f / 256.0f);
+    const float ux = (float)cx + fx, uy = (float)cy + fy;
+    const float mx = ux * s->resolution, my = uy * s->resolution;
+    const float x = s->origin_x + mx, y = s->origin_y + my;
+    int32_t bx = 0, by = 0;
+    if (!(seed_cell(x, y, s, &bx, &by) && bx == (int32_t)cx && by == (int32_t)cy)) ++off;
+    lo = std::min(lo, cell[j]);
+    hi = std::max(hi, cell[j]);
+    std::memcpy(poses_out + 4u * (size_t)j, headings + 2u * (size_t)k, 8);  // bit for bit
+    poses_out[4u * (size_t)j + 2u] = x;
+    poses_out[4u * (size_t)j + 3u] = y;
+    if (cells_out) cells_out[j] = cell[j];
+  }
+  result[0] = F;
+  result[1] = off;
+  result[2] = lo;
+  result[3] = hi;
+  result[4] = result[5] = result[6] = 0u;
+  result[7] = (none ? 1u : 0u) | (off ? 2u : 0u);
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_seed_poses_dev(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, const int8_t *d_grid,
+                              uint64_t grid_stride, uint32_t grid_per_group, const float *d_headings, uint32_t H,
+                              uint32_t G, uint32_t M, const rplgpu_motion_noise_t *noise, float *d_poses_out,
+                              uint64_t out_stride, uint32_t *d_cells_out, uint64_t cell_stride, uint32_t *d_result,
+                              uint32_t *d_scratch) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+  if (rplgpu_pose_seed_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_seed_poses_dev: the rplgpu_pose_seed_t is missing or rplgpu_pose_seed_check refuses it";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!noise) {
+    h->err = "rplgpu_seed_poses_dev: the rplgpu_motion_noise_t is missing";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_seed_poses_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (M == 0 || M > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_seed_poses_dev: M must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (H == 0 || H > 65536u) {
+    h->err = "rplgpu_seed_poses_dev: H must be in 1 .. 65536";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_grid || !d_headings || !d_poses_out || !d_result || !d_scratch || off(d_grid, 3) || off(d_headings, 7) ||
+      off(d_poses_out, 15) || off(d_cells_out, 3) || off(d_result, 3) || off(d_scratch, 7)) {
+    h->err = "rplgpu_seed_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for "
+             "d_poses_out, 8 for d_headings and d_scratch, 4 for d_grid, d_cells_out and d_result)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint64_t cells = (uint64_t)s->width * s->height;
+  if (grid_stride < cells || (grid_stride & 3u)) {
+    h->err = "rplgpu_seed_poses_dev: grid_stride >= width * height and a multiple of 4 is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (out_stride < 4ull * M || (out_stride & 3u)) {
+    h->err = "rplgpu_seed_poses_dev: out_stride >= 4 M and a multiple of 4 is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_cells_out && cell_stride < M) {
+    h->err = "rplgpu_seed_poses_dev: cell_stride >= M is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, d_grid, "d_grid") || !device_readable(h, d_headings, "d_headings") ||
+      !device_readable(h, d_poses_out, "d_poses_out") || !device_readable(h, d_result, "d_result") ||
+      !device_readable(h, d_scratch, "d_scratch") || (d_cells_out && !device_readable(h, d_cells_out, "d_cells_out")))
+    return RPLGPU_ERR_INVALID_ARG;
+  rpl::SeedK k;
+  k.origin_x = s->origin_x;
+  k.origin_y = s->origin_y;
+  k.resolution = s->resolution;
+  k.width = s->width;
+  k.height = s->height;
+  k.free_lo = s->free_lo;
+  k.free_hi = s->free_hi;
+  k.centres = s->flags & 1u;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_seed(h->stream, k, d_grid, grid_stride, grid_per_group, d_headings, H, G, M, noise->seed,
+                              noise->step, noise->first, d_poses_out, out_stride, d_cells_out, cell_stride, d_result,
+                              d_scratch));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_seed_poses(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, const int8_t *grid, const float *headings,
+                          uint32_t H, uint32_t M, const rplgpu_motion_noise_t *noise, float *poses_out,
+                          uint32_t *cells_out, uint32_t result[8]) {
+  if (!h || !grid || !headings || !noise || !poses_out || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_seed_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_seed_poses: the rplgpu_pose_seed_t is missing or rplgpu_pose_seed_check refuses it";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (M == 0 || M > RPLGPU_MAX_POSES || H == 0 || H > 65536u) {
+    h->err = "rplgpu_seed_poses: M must be in 1 .. RPLGPU_MAX_POSES and H in 1 .. 65536";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // one allocation per call (a convenience door, not the hot path): result | headings | grid | scratch | cells | poses
+  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  const size_t cells = (size_t)s->width * s->height, gstride = (cells + 3u) & ~(size_t)3u;
+  const size_t o_head = 32u, o_grid = o_head + up16(8u * (size_t)H), o_scr = o_grid + up16(gstride),
+               o_cells = o_scr + up16(4u * (size_t)rplgpu_seed_scratch_words(1, s->width, s->height)),
+               o_poses = o_cells + up16(4u * (size_t)M), total = o_poses + 16u * (size_t)M;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_seed_poses: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  auto run = [&]() -> int32_t {
+    RPL_HIP(h, hipMemsetAsync(d + o_grid, 0, up16(gstride), h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_head, headings, 8u * (size_t)H, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_grid, grid, cells, hipMemcpyHostToDevice, h->stream));
+    const int32_t rc = rplgpu_seed_poses_dev(h, s, reinterpret_cast<const int8_t *>(d + o_grid), gstride, 0,
+                                             reinterpret_cast<const float *>(d + o_head), H, 1, M, noise,
+                                             reinterpret_cast<float *>(d + o_poses), 4ull * M,
+                                             reinterpret_cast<uint32_t *>(d + o_cells), M,
+                                             reinterpret_cast<uint32_t *>(d), reinterpret_cast<uint32_t *>(d + o_scr));
+    if (rc) return rc;
+    RPL_HIP(h, hipMemcpyAsync(poses_out, d + o_poses, 16u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    if (cells_out) RPL_HIP(h, hipMemcpyAsync(cells_out, d + o_cells, 4u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d, 32, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;
+  std::memcpy(result, small, 32);
+  return RPLGPU_OK;
+}
+
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,

@@ -398,6 +398,41 @@ int main(int argc, char **argv) {
     }
     std::printf("motion noise: 4 deltas, max |Z| %u, first (%.4f, %.4f, %.4f, %.4f)\n", noise1.max_abs, noisy[0], noisy[1],
                 noisy[2], noisy[3]);
+    // E19: 64 poses over a 16 x 8 grid whose only free cells are its top row, against the library's own host-only
+    // twin byte for byte; with no free cell the poses lie anywhere and the result says so.
+    rplgpu_pose_seed_t sspec;
+    rplgpu_default_pose_seed(&sspec);
+    sspec.origin_x = -0.4f;
+    sspec.origin_y = -0.2f;
+    sspec.width = 16;
+    sspec.height = 8;
+    std::vector<int8_t> sgrid(128, 100);
+    for (int cx = 0; cx < 16; ++cx) sgrid[7 * 16 + cx] = 0;
+    std::vector<float> seeded, seeded_twin(256), anywhere, table(2 * 8);
+    uint32_t seed_twin[8];
+    rplgpu_host::ScanPath::SeedResult sr, sr_none;
+    if (!path.seed_poses(sspec, sgrid, 8, mspec, 64, seeded, sr) ||
+        !path.seed_poses(sspec, std::vector<int8_t>(128, 100), 8, mspec, 64, anywhere, sr_none)) {
+      std::fprintf(stderr, "seed poses failed: %s\n", path.last_error().c_str());
+      return 25;
+    }
+    if (rplgpu_seed_headings(8, table.data()) != RPLGPU_OK ||
+        rplgpu_seed_poses_host(&sspec, sgrid.data(), table.data(), 8, 0, 64, &mspec, seeded_twin.data(), nullptr,
+                               seed_twin) != RPLGPU_OK)
+      return 26;
+    bool seed_ok = seeded.size() == 256 && std::memcmp(seeded.data(), seeded_twin.data(), 1024) == 0 &&
+                   sr.free_cells == 16 && sr.free_cells == seed_twin[0] && sr.off_cell == 0 && !sr.none_free &&
+                   sr.min_cell >= 112 && sr.max_cell <= 127 && sr_none.none_free && sr_none.free_cells == 128;
+    for (size_t k = 0; seed_ok && k < 64; ++k)  // the top row: y in [0.15, 0.2), x inside the grid
+      seed_ok = seeded[4 * k + 3] >= 0.15f && seeded[4 * k + 3] < 0.2f && seeded[4 * k + 2] >= -0.4f &&
+                seeded[4 * k + 2] < 0.4f;
+    if (!seed_ok) {
+      std::fprintf(stderr, "seed poses: wrong answer (F %u, off-cell %u, cells %u .. %u)\n", sr.free_cells, sr.off_cell,
+                   sr.min_cell, sr.max_cell);
+      return 26;
+    }
+    std::printf("seed poses: 64 poses over %u free cells (%u .. %u), first (%.4f, %.4f, %.4f, %.4f)\n", sr.free_cells,
+                sr.min_cell, sr.max_cell, seeded[0], seeded[1], seeded[2], seeded[3]);
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

@@ -34,6 +34,8 @@
 //         -> rplgpu_host::ScanPath::estimate_pose(poses, weights, spec, center, estimate)  (E17)
 //         and the motion noise that step needs (one delta per output, drawn from the odometry increment):
 //         -> rplgpu_host::ScanPath::sample_motion(dx, dy, dtheta, alpha, spec, count, delta, result)  (E18)
+//         and the list the loop starts from, or the poses a recovery injects (uniform over a grid's free cells):
+//         -> rplgpu_host::ScanPath::seed_poses(spec, grid, headings, noise, count, poses, result)  (E19)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -628,6 +630,44 @@ class ScanPath {
     const double n = 3.0 * static_cast<double>(count);
     result.mean = static_cast<double>(result.sum) / n;
     result.variance = static_cast<double>(result.sum_squares) / n - result.mean * result.mean;
+    return true;
+  }
+
+  // ext E19 (include/rplgpu_msg.h): `count` poses (c, s, x, y) for score_poses / resample_poses, drawn uniformly over
+  // the free cells of `grid` (width x height int8 cells as occupancy_grid or map_grid give them; free: spec.free_lo
+  // <= cell <= spec.free_hi, by default the cells that are 0), each at one of `headings` evenly spaced headings
+  // (rplgpu_seed_headings) and at a random place inside its cell, from Philox4x32-10 under `noise` (draw index 3: the
+  // stream never meets sample_motion's under the same seed and step; first: where this call's outputs start in a list
+  // made in pieces).  To inject count poses into a resampled list of M, seed with first = M - count and copy the
+  // result over the list's last count poses.
+  struct SeedResult {
+    uint32_t free_cells = 0;    // F (width x height when no cell was free)
+    uint32_t off_cell = 0;      // outputs float32 rounding put into a neighbouring cell (an origin far from 0)
+    uint32_t min_cell = 0;      // the smallest and the largest chosen cell index cy * width + cx
+    uint32_t max_cell = 0;
+    bool none_free = false;     // no cell was free: the poses lie anywhere on the grid
+  };
+  bool seed_poses(const rplgpu_pose_seed_t &spec, const std::vector<int8_t> &grid, uint32_t headings,
+                  const rplgpu_motion_noise_t &noise, uint32_t count, std::vector<float> &poses, SeedResult &result) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    if (rplgpu_pose_seed_check(&spec) != RPLGPU_OK) return fail("seed_poses: rplgpu_pose_seed_check refuses the spec");
+    if (grid.size() != static_cast<size_t>(spec.width) * spec.height)
+      return fail("seed_poses: the grid must hold width x height cells");
+    if (count == 0 || count > RPLGPU_MAX_POSES) return fail("seed_poses: count must be in 1 .. RPLGPU_MAX_POSES");
+    std::vector<float> table(2 * static_cast<size_t>(headings ? headings : 1));
+    if (rplgpu_seed_headings(headings, table.data()) != RPLGPU_OK)
+      return fail("seed_poses: headings must be in 1 .. 65536");
+    poses.assign(4 * static_cast<size_t>(count), 0.0f);
+    uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_seed_poses(h_, &spec, grid.data(), table.data(), headings, count, &noise, poses.data(), nullptr,
+                          words) != RPLGPU_OK)
+      return note_error();
+    result.free_cells = words[0];
+    result.off_cell = words[1];
+    result.min_cell = words[2];
+    result.max_cell = words[3];
+    result.none_free = (words[7] & 1u) != 0;
     return true;
   }
 
