@@ -1115,6 +1115,107 @@ int32_t rplgpu_seed_poses(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, const 
                           uint32_t H, uint32_t M, const rplgpu_motion_noise_t *noise, float *poses_out,
                           uint32_t *cells_out, uint32_t result[8]);
 
+/* ---- E20: a pose list's occupied bins counted on the device (row 4; how the filter sizes its next list) ----
+ * E15 - E19 run a particle filter's loop on the device with M, the size of the next list, as the caller's number.
+ * AMCL takes M from the list itself (KLD sampling): it bins the samples in (x, y, heading), counts the occupied bins
+ * k and draws pf_resample_limit(k) samples — 500 when the filter has converged, 100 000 during global localisation.
+ * This call is that count: the poses are binned by fixed float32 and integer rules and marked in a bit map; k and
+ * the map come back byte-exact on the handle's stream, the host reads eight words, forms M with
+ * rplgpu_kld_samples and passes it to E16, as it already does with N_eff.  Nothing in the reference bins poses, so
+ * these rules ARE the definition (parity unpinned, as E5-E19).  Everything is integers after two float32 operations
+ * per coordinate: the result depends on no order.
+ *
+ * INPUTS per group g of G: P poses (c, s, x, y) in E15 / E16 / E17's layout and under their rules (d_poses,
+ * pose_stride in floats, >= 4 P and a multiple of 4, poses_per_group, 16-byte aligned); weights
+ * d_weights[g * weight_stride + i] (weight_stride >= P).  With d_weights NULL every pose counts; otherwise a pose
+ * with w == 0 is SKIPPED, so the call runs on E15's output before the resampling as well as on E16's after it.
+ * 1 <= P <= RPLGPU_MAX_POSES, 1 <= G <= 65535.
+ * POSITION BIN, float32, no FMA, every operation rounded once:
+ *   fx = (x - origin_x) * inv_size;  fy likewise;
+ *   in range iff fx >= 0.0f && fx < (float)nx, and the same for y (false for NaN; -0 is in range, bin 0);
+ *   bx = (uint32) floorf(fx);  by likewise.
+ * HEADING BIN, no trigonometric function on the device:
+ *   (c, s) is quantised by E17's rule: tc = c * 1048576.0f, in range iff fabsf(tc) < 8388608.0f,
+ *   C = (int32) rintf(tc), S likewise; a pose whose (C, S) is out of range or is (0, 0) is out of range.
+ *   The T bin EDGES are a caller-made table of T entries (c, s) at d_edges (8-byte aligned, shared by all groups,
+ *   only read), quantised the same way; rplgpu_seed_headings(T, ...) makes such a table, so E19's table serves.
+ *   ANGULAR ORDER: half(C, S) = 0 when S > 0 || (S == 0 && C > 0), else 1;  a <= b iff half(a) < half(b), or the
+ *   halves are equal and (int64) Ca * Sb - (int64) Sa * Cb >= 0 (exact: the products are below 2^47).  An edge that
+ *   is out of range or (0, 0) is never <= anything.
+ *   The bin is this bisection, for ANY table:
+ *     lo = 0, hi = T;  while (hi - lo > 1) { mid = (lo + hi) >> 1;  if (e_mid <= h) lo = mid; else hi = mid; }
+ *     ktheta = lo                                                                        (at most 10 steps)
+ *   A table is VALID when entry 0 quantises to (2^20, 0) and the entries strictly increase in the order
+ *   (rplgpu_heading_edges_check).  For a valid table ktheta = (the number of edges <= h) - 1: a heading exactly on
+ *   an edge belongs to the bin that starts there.
+ * BIN ID b = (ktheta * ny + by) * nx + bx;  NB = nx * ny * T.
+ * MAP: group g's bit map is ceil(NB / 32) uint32 words at d_map + g * map_stride (map_stride in words, >=
+ * ceil(NB / 32) and even; d_map 8-byte aligned); bin b is bit b & 31 of word b >> 5.  Without KEEP (flags bit 0)
+ * the call clears those words on the stream first; with KEEP it ORs into what is there.  After the call a bit is
+ * set iff it was set before (KEEP only) or some counted pose of the group has that bin.  Words at and beyond
+ * ceil(NB / 32) are never changed, bits at and beyond NB never set.  The map is an OUTPUT, not scratch.
+ * d_bins_out + g * bin_stride + i (optional, bin_stride >= P) receives b, or 0xFFFFFFFF for a pose that was skipped
+ * or out of range; words at and beyond P are never changed.
+ * RESULT: eight 32-bit words per group at d_result + 8 g (4-byte aligned), set by the call on the stream:
+ *   0      K: the bits this call turned from 0 to 1 (without KEEP: the number of occupied bins)
+ *   1      the poses counted
+ *   2      the poses out of range (position or heading)
+ *   3      the poses skipped for w == 0 (a pose both skipped and out of range counts here only)
+ *   4, 5   the smallest and the largest bin id of a counted pose (0xFFFFFFFF and 0 when none was counted)
+ *   6      0
+ *   7      flags: bit 0 = word 1 is 0; bit 1 = word 2 is not 0; bit 2 = KEEP was set
+ * Words 1 + 2 + 3 = P.  A list counted in pieces with KEEP (the first piece without it) has the whole list's map,
+ * and its K values add up to the whole list's K.
+ * RPLGPU_ERR_INVALID_ARG, no output changed and nothing queued, for a spec the check refuses, G = 0 or above 65535,
+ * P = 0 or above RPLGPU_MAX_POSES, a missing d_poses / d_edges / d_map / d_result, a misaligned pointer (16 bytes:
+ * d_poses; 8: d_edges, d_map; 4: the others), a pose_stride below 4 P or no multiple of 4, a weight_stride below P
+ * with d_weights set, a map_stride below ceil(NB / 32) or odd, and a bin_stride below P with d_bins_out set.
+ * Asynchronous on the handle's stream; no scratch beyond the map. */
+#define RPLGPU_MAX_POSE_BINS 67108864u
+#define RPLGPU_MAX_HEADING_BINS 1024u
+typedef struct rplgpu_pose_bins {
+  float    origin_x, origin_y;  /* the corner of bin (0, 0) */
+  float    inv_size;            /* bins per metre (2.0f: 0.5 m) */
+  uint32_t nx, ny;              /* 1 .. 65536 each */
+  uint32_t flags;               /* bit 0: KEEP the map (do not clear it); other bits 0 */
+} rplgpu_pose_bins_t;
+/* origin (-25.6, -25.6), inv_size 2.0, 103 x 103 bins, flags 0: E11's default grid at AMCL's bin size (0.5 m) */
+void rplgpu_default_pose_bins(rplgpu_pose_bins_t *s);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL, a value that is not finite, inv_size <= 0,
+ * nx or ny of 0 or above 65536, T of 0 or above RPLGPU_MAX_HEADING_BINS, (uint64) nx * ny * T above
+ * RPLGPU_MAX_POSE_BINS, or flags above 1.  The device path uses this function. */
+int32_t rplgpu_pose_bins_check(const rplgpu_pose_bins_t *s, uint32_t T);
+/* Host only: the words of one group's map, ceil(nx * ny * T / 32) rounded up to even (a valid map_stride); 0 for
+ * arguments rplgpu_pose_bins_check refuses. */
+uint64_t rplgpu_bin_map_words(uint32_t nx, uint32_t ny, uint32_t T);
+/* Host only: RPLGPU_OK when the T entries (c, s) at cs are a VALID table of edges (above), RPLGPU_ERR_INVALID_ARG
+ * otherwise (a NULL cs, T = 0 or above RPLGPU_MAX_HEADING_BINS included). */
+int32_t rplgpu_heading_edges_check(const float *cs, uint32_t T);
+int32_t rplgpu_bin_poses_dev(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, const float *d_poses,
+                             uint64_t pose_stride, uint32_t poses_per_group, const uint32_t *d_weights,
+                             uint64_t weight_stride, uint32_t G, uint32_t P, const float *d_edges, uint32_t T,
+                             uint32_t *d_map, uint64_t map_stride, uint32_t *d_bins_out, uint64_t bin_stride,
+                             uint32_t *d_result);
+/* Host only (no handle, no device): the same rule in plain C++ for ONE group — the definition a reader can run.
+ * poses: 4 P floats; weights (optional): P words; edges: 2 T floats; map: ceil(NB / 32) words, cleared or ORed
+ * into by the KEEP flag as above; bins_out (optional): P words; result: 8 words.  RPLGPU_ERR_INVALID_ARG and
+ * nothing written for a spec the check refuses, a NULL poses / edges / map / result and P = 0 or above
+ * RPLGPU_MAX_POSES. */
+int32_t rplgpu_bin_poses_host(const rplgpu_pose_bins_t *s, const float *poses, uint32_t P, const uint32_t *weights,
+                              const float *edges, uint32_t T, uint32_t *map, uint32_t *bins_out,
+                              uint32_t result[8]);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp), arguments as rplgpu_bin_poses_host (with KEEP the
+ * map at `map` is copied up first).  Allocates its device buffers per call and returns when the results are in
+ * place: a door, not a hot path. */
+int32_t rplgpu_bin_poses(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, const float *poses, uint32_t P,
+                         const uint32_t *weights, const float *edges, uint32_t T, uint32_t *map, uint32_t *bins_out,
+                         uint32_t result[8]);
+/* Host only, fp64: AMCL's pf_resample_limit.  k <= 1 gives m_max; otherwise b = 2 / (9 (k - 1)),
+ * x = 1 - b + sqrt(b) * z, n = ceil((k - 1) / (2 epsilon) * x^3), clamped to [m_min, m_max] (epsilon = 0.01, z = 3:
+ * k = 2 -> 527, 10 -> 1363, 100 -> 7332, 1000 -> 56 923 before the clamp).  A convenience, NOT part of the
+ * byte-exact contract. */
+uint32_t rplgpu_kld_samples(uint32_t k, double epsilon, double z, uint32_t m_min, uint32_t m_max);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,8 @@ MAX_OCC_STEPS = 8192     # RPLGPU_MAX_OCC_STEPS (include/rplgpu_msg.h)
 MAX_INFLATION_CELLS = 64  # RPLGPU_MAX_INFLATION_CELLS (include/rplgpu_msg.h)
 MAX_POSES = 1048576       # RPLGPU_MAX_POSES (include/rplgpu_msg.h)
 ESTIMATE_WORDS = 72       # RPLGPU_ESTIMATE_WORDS
+MAX_POSE_BINS = 67108864  # RPLGPU_MAX_POSE_BINS (include/rplgpu_msg.h)
+MAX_HEADING_BINS = 1024   # RPLGPU_MAX_HEADING_BINS (include/rplgpu_msg.h)
 
 SL_RESULT_OK = 0
 SL_RESULT_OPERATION_FAIL = 0x80008001
@@ -161,6 +163,14 @@ ABI_SYMBOLS = [
     "rplgpu_seed_poses_dev",
     "rplgpu_seed_poses_host",
     "rplgpu_seed_poses",
+    "rplgpu_default_pose_bins",
+    "rplgpu_pose_bins_check",
+    "rplgpu_bin_map_words",
+    "rplgpu_heading_edges_check",
+    "rplgpu_bin_poses_dev",
+    "rplgpu_bin_poses_host",
+    "rplgpu_bin_poses",
+    "rplgpu_kld_samples",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -495,6 +505,34 @@ class PoseSeed(C.Structure):
         return int(load_library().rplgpu_pose_seed_check(C.byref(self)))
 
 
+class PoseBins(C.Structure):
+    """Mirror of ``rplgpu_pose_bins_t`` (E20: a pose list's occupied bins counted on the device)."""
+
+    _fields_ = [
+        ("origin_x", C.c_float),
+        ("origin_y", C.c_float),
+        ("inv_size", C.c_float),
+        ("nx", C.c_uint32),
+        ("ny", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "PoseBins":
+        """The library's own defaults (``rplgpu_default_pose_bins``), then the overrides."""
+        s = cls()
+        load_library().rplgpu_default_pose_bins(C.byref(s))
+        for k, v in kw.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s
+
+    def check(self, T: int) -> int:
+        """``rplgpu_pose_bins_check`` with T heading bins: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_pose_bins_check(C.byref(self), T))
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -718,6 +756,18 @@ def load_library() -> C.CDLL:
     lib.rplgpu_seed_poses_host.argtypes = [C.POINTER(PoseSeed), vp, vp, u32, u32, u32, C.POINTER(MotionNoise), vp, vp,
                                            vp]
     lib.rplgpu_seed_poses.argtypes = [vp, C.POINTER(PoseSeed), vp, vp, u32, u32, C.POINTER(MotionNoise), vp, vp, vp]
+    lib.rplgpu_default_pose_bins.argtypes = [C.POINTER(PoseBins)]
+    lib.rplgpu_default_pose_bins.restype = None
+    lib.rplgpu_pose_bins_check.argtypes = [C.POINTER(PoseBins), u32]
+    lib.rplgpu_bin_map_words.argtypes = [u32, u32, u32]
+    lib.rplgpu_bin_map_words.restype = C.c_uint64
+    lib.rplgpu_heading_edges_check.argtypes = [vp, u32]
+    lib.rplgpu_bin_poses_dev.argtypes = [vp, C.POINTER(PoseBins), vp, u64, u32, vp, u64, u32, u32, vp, u32, vp, u64, vp,
+                                         u64, vp]
+    lib.rplgpu_bin_poses_host.argtypes = [C.POINTER(PoseBins), vp, u32, vp, vp, u32, vp, vp, vp]
+    lib.rplgpu_bin_poses.argtypes = [vp, C.POINTER(PoseBins), vp, u32, vp, vp, u32, vp, vp, vp]
+    lib.rplgpu_kld_samples.argtypes = [u32, C.c_double, C.c_double, u32, u32]
+    lib.rplgpu_kld_samples.restype = C.c_uint32
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1245,6 +1295,29 @@ class RplGpu:
             self._h, C.byref(spec), grid.ctypes.data, headings.ctypes.data, len(headings), M, C.byref(noise),
             poses.ctypes.data, cells.ctypes.data, result.ctypes.data))
         return poses, cells, result
+
+    def bin_poses_dev(self, spec: "PoseBins", d_poses: int, pose_stride: int, poses_per_group: int, d_weights: int,
+                      weight_stride: int, G: int, P: int, d_edges: int, T: int, d_map: int, map_stride: int,
+                      d_bins_out: int, bin_stride: int, d_result: int):
+        """E20: per group the P poses at d_poses (E15 / E16 / E17's layout) binned in (x, y, heading) under ``spec``
+        and the T-entry edge table, marked in the group's bit map at d_map + g * map_stride (words); the bin ids at
+        d_bins_out (optional), eight result words at d_result + 8 g.  A pose whose weight is 0 is skipped
+        (d_weights 0: every pose counts)."""
+        self._check(self._lib.rplgpu_bin_poses_dev(
+            self._h, C.byref(spec), d_poses, pose_stride, poses_per_group, d_weights, weight_stride, G, P, d_edges, T,
+            d_map, map_stride, d_bins_out, bin_stride, d_result))
+
+    def bin_poses(self, poses: np.ndarray, edges: np.ndarray, weights: np.ndarray = None, spec: "PoseBins" = None,
+                  map_in: np.ndarray = None):
+        """E20, one group, host buffers: poses (P, 4) float32, edges (T, 2) float32, weights (P,) uint32 or None ->
+        ``(map (ceil(NB / 32),) uint32, bins (P,) uint32, result (8,) uint32)``; ``map_in`` is the map KEEP ORs into."""
+        poses, edges, weights, spec, bmap = _bins_args(poses, edges, weights, spec, map_in)
+        bins = np.zeros(len(poses), np.uint32)
+        result = np.zeros(8, np.uint32)
+        self._check(self._lib.rplgpu_bin_poses(
+            self._h, C.byref(spec), poses.ctypes.data, len(poses), weights.ctypes.data if weights is not None else None,
+            edges.ctypes.data, len(edges), bmap.ctypes.data, bins.ctypes.data, result.ctypes.data))
+        return bmap, bins, result
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -1900,3 +1973,55 @@ def seed_poses_host(grid, headings, M: int, spec: PoseSeed = None, noise: Motion
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_seed_poses_host")
     return poses, cells, result
+
+
+def _bins_args(poses, edges, weights, spec, map_in):
+    spec = PoseBins.defaults() if spec is None else spec
+    poses = np.ascontiguousarray(poses, np.float32)
+    edges = np.ascontiguousarray(edges, np.float32)
+    if poses.ndim != 2 or poses.shape[1] != 4:
+        raise TypeError("poses must be (P, 4) float32")
+    if edges.ndim != 2 or edges.shape[1] != 2:
+        raise TypeError("edges must be (T, 2) float32")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.uint32)
+        if weights.shape != (len(poses),):
+            raise TypeError("weights must be (P,) uint32")
+    if spec.check(len(edges)) != OK:
+        raise RplGpuError(ERR_INVALID_ARG, "rplgpu_pose_bins_check")
+    words = (spec.nx * spec.ny * len(edges) + 31) // 32
+    bmap = np.zeros(words, np.uint32) if map_in is None else np.array(map_in, np.uint32).reshape(-1)
+    if bmap.size != words:
+        raise TypeError("map_in must hold ceil(nx * ny * T / 32) words")
+    return poses, edges, weights, spec, bmap
+
+
+def bin_map_words(nx: int, ny: int, T: int) -> int:
+    """Host only: the even number of uint32 words of one group's bit map (a valid map_stride); 0 for arguments the
+    call refuses."""
+    return int(load_library().rplgpu_bin_map_words(nx, ny, T))
+
+
+def heading_edges_check(edges) -> int:
+    """Host only: OK when the (T, 2) float32 table is a VALID table of bin edges (rplgpu_heading_edges_check)."""
+    edges = np.ascontiguousarray(edges, np.float32)
+    return int(load_library().rplgpu_heading_edges_check(edges.ctypes.data, len(edges)))
+
+
+def kld_samples(k: int, epsilon: float = 0.01, z: float = 3.0, m_min: int = 500, m_max: int = 100000) -> int:
+    """Host only: AMCL's pf_resample_limit by the library's own rplgpu_kld_samples."""
+    return int(load_library().rplgpu_kld_samples(k, epsilon, z, m_min, m_max))
+
+
+def bin_poses_host(poses, edges, weights=None, spec: PoseBins = None, map_in=None):
+    """Host only: E20's rule for one group by the library's own rplgpu_bin_poses_host (no handle, no device);
+    arguments and results as ``RplGpu.bin_poses``."""
+    poses, edges, weights, spec, bmap = _bins_args(poses, edges, weights, spec, map_in)
+    bins = np.zeros(max(len(poses), 1), np.uint32)
+    result = np.zeros(8, np.uint32)
+    rc = load_library().rplgpu_bin_poses_host(
+        C.byref(spec), poses.ctypes.data, len(poses), weights.ctypes.data if weights is not None else None,
+        edges.ctypes.data, len(edges), bmap.ctypes.data, bins.ctypes.data, result.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_bin_poses_host")
+    return bmap, bins[:len(poses)], result

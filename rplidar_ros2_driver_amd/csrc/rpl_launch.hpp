@@ -401,4 +401,20 @@ hipError_t launch_seed(hipStream_t s, const SeedK &k, const int8_t *grid, unsign
                        unsigned long long out_stride, uint32_t *cells_out, unsigned long long cell_stride,
                        uint32_t *result, uint32_t *scratch);
 
+// E20: a pose list's occupied bins (rpl_bins.hip, include/rplgpu_msg.h).  Two launches on the stream: the map words
+// cleared (not under KEEP) and the result words started, then one thread per pose — one 16-byte load, the float32
+// position bin, a bounded bisection over the quantised edge table in LDS, the wave's marks merged per map word, a
+// device-scope read and a returning atomic OR only where a bit is missing — and the tile's statistics added to the
+// words with integer atomics.  No scratch.
+struct BinsK {
+  float origin_x, origin_y, inv_size;
+  uint32_t nx, ny;
+  uint32_t keep;  // flags bit 0: OR into the map, do not clear it
+};
+hipError_t launch_bins(hipStream_t s, const BinsK &k, const float *poses, unsigned long long pose_stride,
+                       uint32_t poses_per_group, const uint32_t *weights, unsigned long long weight_stride,
+                       uint32_t G, uint32_t P, const float *edges, uint32_t T, uint32_t *map,
+                       unsigned long long map_stride, uint32_t *bins_out, unsigned long long bin_stride,
+                       uint32_t *result);
+
 }  // namespace rpl

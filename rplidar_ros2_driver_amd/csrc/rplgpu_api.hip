@@ -3210,6 +3210,251 @@ int32_t rplgpu_seed_poses(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, const 
   return RPLGPU_OK;
 }
 
+// ---- E20: a pose list's occupied bins counted on the device (include/rplgpu_msg.h) -----------------------------------
+
+void rplgpu_default_pose_bins(rplgpu_pose_bins_t *s) {
+  if (!s) return;
+  s->origin_x = -25.6f;
+  s->origin_y = -25.6f;
+  s->inv_size = 2.0f;
+  s->nx = 103;
+  s->ny = 103;
+  s->flags = 0;
+}
+
+int32_t rplgpu_pose_bins_check(const rplgpu_pose_bins_t *s, uint32_t T) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(s->origin_x) || !std::isfinite(s->origin_y) || !std::isfinite(s->inv_size))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!(s->inv_size > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  if (s->nx == 0 || s->nx > 65536u || s->ny == 0 || s->ny > 65536u) return RPLGPU_ERR_INVALID_ARG;
+  if (T == 0 || T > RPLGPU_MAX_HEADING_BINS) return RPLGPU_ERR_INVALID_ARG;
+  if ((uint64_t)s->nx * s->ny * T > (uint64_t)RPLGPU_MAX_POSE_BINS) return RPLGPU_ERR_INVALID_ARG;
+  if (s->flags > 1u) return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+uint64_t rplgpu_bin_map_words(uint32_t nx, uint32_t ny, uint32_t T) {
+  rplgpu_pose_bins_t s;
+  rplgpu_default_pose_bins(&s);
+  s.nx = nx;
+  s.ny = ny;
+  if (rplgpu_pose_bins_check(&s, T) != RPLGPU_OK) return 0;
+  const uint64_t words = ((uint64_t)nx * ny * T + 31u) >> 5;
+  return (words + 1u) & ~(uint64_t)1u;
+}
+
+// E20's quantisation of (c, s), E17's rule: one float32 product, the range test, one round-to-nearest-even; false for
+// an entry that is out of range or quantises to (0, 0)
+static bool bins_quantise(const float *cs, int32_t q[2]) {
+  const float tc = cs[0] * 1048576.0f, ts = cs[1] * 1048576.0f;
+  q[0] = q[1] = 0;
+  if (!(std::fabs(tc) < 8388608.0f && std::fabs(ts) < 8388608.0f)) return false;
+  q[0] = (int32_t)std::rint(tc);
+  q[1] = (int32_t)std::rint(ts);
+  return q[0] != 0 || q[1] != 0;
+}
+static uint32_t bins_half(const int32_t a[2]) { return (a[1] > 0 || (a[1] == 0 && a[0] > 0)) ? 0u : 1u; }
+// a <= b in the angular order, both in range and not (0, 0)
+static bool bins_le(const int32_t a[2], const int32_t b[2]) {
+  const uint32_t ha = bins_half(a), hb = bins_half(b);
+  if (ha != hb) return ha < hb;
+  return (int64_t)a[0] * b[1] - (int64_t)a[1] * b[0] >= 0;
+}
+
+int32_t rplgpu_heading_edges_check(const float *cs, uint32_t T) {
+  if (!cs || T == 0 || T > RPLGPU_MAX_HEADING_BINS) return RPLGPU_ERR_INVALID_ARG;
+  int32_t prev[2], cur[2];
+  if (!bins_quantise(cs, prev) || prev[0] != 1048576 || prev[1] != 0) return RPLGPU_ERR_INVALID_ARG;
+  for (uint32_t k = 1; k < T; ++k) {
+    if (!bins_quantise(cs + 2u * (size_t)k, cur)) return RPLGPU_ERR_INVALID_ARG;
+    if (bins_le(cur, prev)) return RPLGPU_ERR_INVALID_ARG;  // not strictly behind its predecessor
+    prev[0] = cur[0];
+    prev[1] = cur[1];
+  }
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_bin_poses_host(const rplgpu_pose_bins_t *s, const float *poses, uint32_t P, const uint32_t *weights,
+                              const float *edges, uint32_t T, uint32_t *map, uint32_t *bins_out,
+                              uint32_t result[8]) {
+  if (rplgpu_pose_bins_check(s, T) != RPLGPU_OK || !poses || !edges || !map || !result || P == 0 ||
+      P > RPLGPU_MAX_POSES)
+    return RPLGPU_ERR_INVALID_ARG;
+  const uint32_t nb = s->nx * s->ny * T, words = (nb + 31u) >> 5;
+  const bool keep = (s->flags & 1u) != 0;
+  if (!keep) std::memset(map, 0, 4u * (size_t)words);
+  std::vector<int32_t> eq(2u * (size_t)T);
+  std::vector<unsigned char> e_ok(T);
+  for (uint32_t k = 0; k < T; ++k) e_ok[k] = bins_quantise(edges + 2u * (size_t)k, &eq[2u * (size_t)k]) ? 1 : 0;
+  uint32_t K = 0, counted = 0, outside = 0, skipped = 0, lo_bin = 0xFFFFFFFFu, hi_bin = 0;
+  for (uint32_t i = 0; i < P; ++i) {
+    const float *p = poses + 4u * (size_t)i;
+    uint32_t b = 0xFFFFFFFFu;
+    if (weights && weights[i] == 0u) {
+      ++skipped;  // (whether or not it is in range)
+    } else {
+      const float dx = p[2] - s->origin_x, dy = p[3] - s->origin_y;
+      const float fx = dx * s->inv_size, fy = dy * s->inv_size;  // (-ffp-contract=off: the difference rounded first)
+      const bool x_in = fx >= 0.0f && fx < (float)s->nx;
+      const bool y_in = fy >= 0.0f && fy < (float)s->ny;
+      int32_t h[2];
+      const bool h_in = bins_quantise(p, h);
+      if (x_in && y_in && h_in) {
+        const uint32_t bx = (uint32_t)std::floor(fx), by = (uint32_t)std::floor(fy);
+        uint32_t lo = 0, hi = T;
+        while (hi - lo > 1u) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (e_ok[mid] && bins_le(&eq[2u * (size_t)mid], h))
+            lo = mid;
+          else
+            hi = mid;
+        }
+        b = (lo * s->ny + by) * s->nx + bx;
+        ++counted;
+        lo_bin = std::min(lo_bin, b);
+        hi_bin = std::max(hi_bin, b);
+        const uint32_t bit = 1u << (b & 31u);
+        if (!(map[b >> 5] & bit)) ++K;  // a bit this call turns from 0 to 1
+        map[b >> 5] |= bit;
+      } else {
+        ++outside;
+      }
+    }
+    if (bins_out) bins_out[i] = b;
+  }
+  result[0] = K;
+  result[1] = counted;
+  result[2] = outside;
+  result[3] = skipped;
+  result[4] = lo_bin;
+  result[5] = hi_bin;
+  result[6] = 0u;
+  result[7] = (counted == 0 ? 1u : 0u) | (outside != 0 ? 2u : 0u) | (keep ? 4u : 0u);
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_bin_poses_dev(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, const float *d_poses,
+                             uint64_t pose_stride, uint32_t poses_per_group, const uint32_t *d_weights,
+                             uint64_t weight_stride, uint32_t G, uint32_t P, const float *d_edges, uint32_t T,
+                             uint32_t *d_map, uint64_t map_stride, uint32_t *d_bins_out, uint64_t bin_stride,
+                             uint32_t *d_result) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+  if (rplgpu_pose_bins_check(s, T) != RPLGPU_OK) {
+    h->err = "rplgpu_bin_poses_dev: the rplgpu_pose_bins_t is missing or rplgpu_pose_bins_check refuses it or T";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_bin_poses_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_bin_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_poses || !d_edges || !d_map || !d_result || off(d_poses, 15) || off(d_edges, 7) || off(d_map, 7) ||
+      off(d_weights, 3) || off(d_bins_out, 3) || off(d_result, 3)) {
+    h->err = "rplgpu_bin_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for d_poses, "
+             "8 for d_edges and d_map, 4 for d_weights, d_bins_out and d_result)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (pose_stride < 4ull * P || (pose_stride & 3u) || (d_weights && weight_stride < P)) {
+    h->err = "rplgpu_bin_poses_dev: pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint64_t words = ((uint64_t)s->nx * s->ny * T + 31u) >> 5;
+  if (map_stride < words || (map_stride & 1u)) {
+    h->err = "rplgpu_bin_poses_dev: map_stride >= ceil(nx * ny * T / 32) and even is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_bins_out && bin_stride < P) {
+    h->err = "rplgpu_bin_poses_dev: bin_stride >= P is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, d_poses, "d_poses") || !device_readable(h, d_edges, "d_edges") ||
+      !device_readable(h, d_map, "d_map") || !device_readable(h, d_result, "d_result") ||
+      (d_weights && !device_readable(h, d_weights, "d_weights")) ||
+      (d_bins_out && !device_readable(h, d_bins_out, "d_bins_out")))
+    return RPLGPU_ERR_INVALID_ARG;
+  rpl::BinsK k;
+  k.origin_x = s->origin_x;
+  k.origin_y = s->origin_y;
+  k.inv_size = s->inv_size;
+  k.nx = s->nx;
+  k.ny = s->ny;
+  k.keep = s->flags & 1u;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_bins(h->stream, k, d_poses, pose_stride, poses_per_group, d_weights, weight_stride, G, P,
+                              d_edges, T, d_map, map_stride, d_bins_out, bin_stride, d_result));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_bin_poses(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, const float *poses, uint32_t P,
+                         const uint32_t *weights, const float *edges, uint32_t T, uint32_t *map, uint32_t *bins_out,
+                         uint32_t result[8]) {
+  if (!h || !poses || !edges || !map || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_bins_check(s, T) != RPLGPU_OK) {
+    h->err = "rplgpu_bin_poses: the rplgpu_pose_bins_t is missing or rplgpu_pose_bins_check refuses it or T";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_bin_poses: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // one allocation per call (a convenience door, not the hot path): result | edges | map | weights | bins | poses
+  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  const size_t words = ((size_t)s->nx * s->ny * T + 31u) >> 5, stride = (size_t)rplgpu_bin_map_words(s->nx, s->ny, T);
+  const size_t o_edge = 32u, o_map = o_edge + up16(8u * (size_t)T), o_wt = o_map + up16(4u * stride),
+               o_bins = o_wt + up16(4u * (size_t)P), o_poses = o_bins + up16(4u * (size_t)P),
+               total = o_poses + 16u * (size_t)P;
+  unsigned char *d = nullptr;
+  if (hipMalloc((void **)&d, total) != hipSuccess) {
+    h->err = "rplgpu_bin_poses: device allocation failed";
+    (void)hipGetLastError();
+    return RPLGPU_ERR_HIP;
+  }
+  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<uint32_t> map_back(words), bins_back(bins_out ? P : 0u);
+  auto run = [&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(d + o_poses, poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d + o_edge, edges, 8u * (size_t)T, hipMemcpyHostToDevice, h->stream));
+    if (weights) RPL_HIP(h, hipMemcpyAsync(d + o_wt, weights, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    if (s->flags & 1u) RPL_HIP(h, hipMemcpyAsync(d + o_map, map, 4u * words, hipMemcpyHostToDevice, h->stream));
+    const int32_t rc = rplgpu_bin_poses_dev(
+        h, s, reinterpret_cast<const float *>(d + o_poses), 4ull * P, 0,
+        weights ? reinterpret_cast<const uint32_t *>(d + o_wt) : nullptr, P, 1, P,
+        reinterpret_cast<const float *>(d + o_edge), T, reinterpret_cast<uint32_t *>(d + o_map), stride,
+        bins_out ? reinterpret_cast<uint32_t *>(d + o_bins) : nullptr, P, reinterpret_cast<uint32_t *>(d));
+    if (rc) return rc;
+    RPL_HIP(h, hipMemcpyAsync(map_back.data(), d + o_map, 4u * words, hipMemcpyDeviceToHost, h->stream));
+    if (bins_out)
+      RPL_HIP(h, hipMemcpyAsync(bins_back.data(), d + o_bins, 4u * (size_t)P, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d, 32, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  };
+  const int32_t rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
+  (void)hipFree(d);
+  if (rc) return rc;  // (no output changed)
+  std::memcpy(map, map_back.data(), 4u * words);
+  if (bins_out) std::memcpy(bins_out, bins_back.data(), 4u * (size_t)P);
+  std::memcpy(result, small, 32);
+  return RPLGPU_OK;
+}
+
+uint32_t rplgpu_kld_samples(uint32_t k, double epsilon, double z, uint32_t m_min, uint32_t m_max) {
+  if (k <= 1u) return m_max;
+  const double b = 2.0 / (9.0 * ((double)k - 1.0));
+  const double x = 1.0 - b + std::sqrt(b) * z;
+  const double n = std::ceil(((double)k - 1.0) / (2.0 * epsilon) * x * x * x);
+  if (!(n >= (double)m_min)) return m_min;  // (NaN too)
+  if (n > (double)m_max) return m_max;
+  return (uint32_t)n;
+}
+
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,

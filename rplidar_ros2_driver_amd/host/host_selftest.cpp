@@ -433,6 +433,44 @@ int main(int argc, char **argv) {
     }
     std::printf("seed poses: 64 poses over %u free cells (%u .. %u), first (%.4f, %.4f, %.4f, %.4f)\n", sr.free_cells,
                 sr.min_cell, sr.max_cell, seeded[0], seeded[1], seeded[2], seeded[3]);
+    // E20: those 64 poses lie in the grid's top row (0.8 m x 0.05 m) at 8 headings: with 0.5 m bins from the grid's
+    // corner they occupy at most 2 x 1 x 8 bins; against the library's own host-only twin byte for byte, then the
+    // same list again under KEEP (nothing new) and the size KLD sampling gives the next list.
+    rplgpu_pose_bins_t bspec;
+    rplgpu_default_pose_bins(&bspec);
+    bspec.origin_x = -0.4f;
+    bspec.origin_y = -0.2f;
+    bspec.nx = 2;
+    bspec.ny = 1;
+    std::vector<uint32_t> bmap, bmap_twin(1, 0xFFFFFFFFu), no_weights;
+    uint32_t bin_twin[8];
+    rplgpu_host::ScanPath::BinResult br, br_again;
+    if (!path.bin_poses(bspec, seeded, no_weights, 8, bmap, br)) {
+      std::fprintf(stderr, "bin poses failed: %s\n", path.last_error().c_str());
+      return 27;
+    }
+    if (rplgpu_bin_poses_host(&bspec, seeded.data(), 64, nullptr, table.data(), 8, bmap_twin.data(), nullptr,
+                              bin_twin) != RPLGPU_OK)
+      return 28;
+    bspec.flags = 1;  // KEEP
+    std::vector<uint32_t> bmap_again = bmap;
+    if (!path.bin_poses(bspec, seeded, no_weights, 8, bmap_again, br_again)) {
+      std::fprintf(stderr, "bin poses (KEEP) failed: %s\n", path.last_error().c_str());
+      return 27;
+    }
+    const bool bin_ok = bmap.size() == 1 && bmap == bmap_twin && bmap_again == bmap && br.new_bins == bin_twin[0] &&
+                        br.counted == 64 && br.counted == bin_twin[1] && br.out_of_range == 0 && br.skipped == 0 &&
+                        br.min_bin == bin_twin[4] && br.max_bin == bin_twin[5] && br.new_bins >= 1 &&
+                        br.new_bins <= 16 && br.max_bin < 16 && !br.none_counted && br_again.new_bins == 0 &&
+                        br_again.counted == 64 && rplgpu_kld_samples(2, 0.01, 3.0, 1, 1000000) == 527 &&
+                        br.samples() >= 500;
+    if (!bin_ok) {
+      std::fprintf(stderr, "bin poses: wrong answer (K %u / %u, counted %u, map %08x / %08x, again K %u)\n",
+                   br.new_bins, bin_twin[0], br.counted, bmap.empty() ? 0u : bmap[0], bmap_twin[0], br_again.new_bins);
+      return 28;
+    }
+    std::printf("bin poses: 64 poses in %u bins (%u .. %u), map %08x, next list %u poses\n", br.new_bins, br.min_bin,
+                br.max_bin, bmap[0], br.samples());
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

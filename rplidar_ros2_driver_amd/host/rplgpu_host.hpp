@@ -36,6 +36,8 @@
 //         -> rplgpu_host::ScanPath::sample_motion(dx, dy, dtheta, alpha, spec, count, delta, result)  (E18)
 //         and the list the loop starts from, or the poses a recovery injects (uniform over a grid's free cells):
 //         -> rplgpu_host::ScanPath::seed_poses(spec, grid, headings, noise, count, poses, result)  (E19)
+//         and the size of the next list from the bins the list occupies (AMCL's KLD sampling):
+//         -> rplgpu_host::ScanPath::bin_poses(spec, poses, weights, headings, map, result)  (E20)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -668,6 +670,53 @@ class ScanPath {
     result.min_cell = words[2];
     result.max_cell = words[3];
     result.none_free = (words[7] & 1u) != 0;
+    return true;
+  }
+
+  // ext E20 (include/rplgpu_msg.h): the poses (c, s, x, y) of score_poses / resample_poses binned in (x, y, heading) —
+  // spec.inv_size bins per metre from the corner (origin_x, origin_y), `headings` evenly spaced heading bins
+  // (rplgpu_seed_headings' table as the edges) — and marked in the bit map `map` (bin b: bit b & 31 of word b >> 5);
+  // a pose whose weight is 0 is skipped (weights empty: every pose counts).  With spec.flags bit 0 (KEEP) the bits
+  // are ORed into `map` as it stands, so a list can be counted in pieces.  result.samples(...) is the size AMCL's
+  // KLD sampling gives the next list (the M of resample_poses).
+  struct BinResult {
+    uint32_t new_bins = 0;      // K: the bits this call set (without KEEP: the occupied bins)
+    uint32_t counted = 0;       // poses binned
+    uint32_t out_of_range = 0;  // poses outside the bins, or with a heading that has no direction
+    uint32_t skipped = 0;       // poses whose weight is 0
+    uint32_t min_bin = 0;       // the smallest and the largest bin id of a counted pose
+    uint32_t max_bin = 0;
+    bool none_counted = false;
+    uint32_t samples(double epsilon = 0.01, double z = 3.0, uint32_t m_min = 500, uint32_t m_max = 100000) const {
+      return rplgpu_kld_samples(new_bins, epsilon, z, m_min, m_max);
+    }
+  };
+  bool bin_poses(const rplgpu_pose_bins_t &spec, const std::vector<float> &poses, const std::vector<uint32_t> &weights,
+                 uint32_t headings, std::vector<uint32_t> &map, BinResult &result) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    if (rplgpu_pose_bins_check(&spec, headings) != RPLGPU_OK)
+      return fail("bin_poses: rplgpu_pose_bins_check refuses the spec or the number of heading bins");
+    const size_t count = poses.size() / 4;
+    if (count == 0 || count > RPLGPU_MAX_POSES || poses.size() != 4 * count)
+      return fail("bin_poses: poses must hold 1 .. RPLGPU_MAX_POSES entries of four floats");
+    if (!weights.empty() && weights.size() != count) return fail("bin_poses: one weight per pose, or none");
+    std::vector<float> table(2 * static_cast<size_t>(headings));
+    if (rplgpu_seed_headings(headings, table.data()) != RPLGPU_OK) return fail("bin_poses: no heading table");
+    const size_t words = (static_cast<size_t>(spec.nx) * spec.ny * headings + 31) / 32;
+    if (map.size() != words) map.assign(words, 0u);  // (any other size starts an empty map)
+    uint32_t out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_bin_poses(h_, &spec, poses.data(), static_cast<uint32_t>(count),
+                         weights.empty() ? nullptr : weights.data(), table.data(), headings, map.data(), nullptr,
+                         out) != RPLGPU_OK)
+      return note_error();
+    result.new_bins = out[0];
+    result.counted = out[1];
+    result.out_of_range = out[2];
+    result.skipped = out[3];
+    result.min_bin = out[4];
+    result.max_bin = out[5];
+    result.none_counted = (out[7] & 1u) != 0;
     return true;
   }
 
