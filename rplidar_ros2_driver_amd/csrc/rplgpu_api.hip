@@ -1,9 +1,12 @@
-// rplgpu_api.hip — the extern "C" boundary declared in include/rplgpu.h.
+// rplgpu_api.hip — the extern "C" boundary declared in include/rplgpu.h, less the stages that
+// have units of their own (rplgpu_scan_stages.hip, rplgpu_pose_stages.hip).
 //
 // Host side only: context/stream management, the host-evaluated lookup tables, the
-// pinned staging used by the single-scan (host buffer) entry points, and argument
-// checking.  All arithmetic on samples happens in rpl_kernels.hip.  There is no CPU
-// fallback: if no gfx950 device is usable, rplgpu_create fails.
+// pinned staging used by the single-scan (host buffer) entry points, argument checking and
+// the launch sizing of the batch, cloud / voxel, decode, message and exchange entry points.
+// All arithmetic on samples happens in the kernel units (rpl_*.hip).  There is no CPU
+// fallback: if no gfx950 device is usable, rplgpu_create fails.  What the three host units
+// share (the handle, RPL_HIP, the helpers in rpl::host) is in rpl_host.hpp.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -21,129 +24,24 @@
 #include "rplgpu.h"
 #include "rplgpu_msg.h"
 #include "rpl_launch.hpp"
+#include "rpl_host.hpp"
 #include "rpl_msg.hpp"
 #include "rpl_comm_layout.hpp"
 #include "rpl_cells.hpp"
-
-// which batch the voxel queue statistics in pinned memory describe (voxel_split_for)
-struct VoxelBatchId {
-  const void *nodes = nullptr;
-  uint32_t n_stride = 0, B = 0, group = 0;
-  bool operator==(const VoxelBatchId &o) const {
-    return nodes == o.nodes && n_stride == o.n_stride && B == o.B && group == o.group;
-  }
-};
-
-struct rplgpu_ctx {
-  int device = -1;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  uint32_t max_n = 0, max_b = 0;
-  // tables
-  float *d_angle = nullptr, *d_angle_inv = nullptr, *d_inc = nullptr, *d_rinc = nullptr;
-  float2 *d_cs = nullptr, *d_cs_inv = nullptr;
-  double *d_rcp = nullptr;
-  // single-scan staging
-  unsigned char *h_pin = nullptr;  // pinned: nodes | out (16 B / sample) | 2 x u32
-  unsigned char *d_pin = nullptr;  // the same memory as the device sees it (zero-copy single scans)
-  bool zero_copy = true;           // single-scan entry points: kernels read / write h_pin directly
-  bool spin_sync = true;           // ... and complete through a flag in pinned memory (wait_scan)
-  size_t flag_off = 0;             // offset of that flag in h_pin
-  uint32_t scan_seq = 0;
-  struct Pinned { unsigned char *host, *dev; size_t bytes; };
-  std::vector<Pinned> pinned;      // buffers handed out by rplgpu_host_alloc (device-addressable)
-  unsigned char *d_nodes = nullptr, *d_out = nullptr;
-  uint32_t *d_rormask = nullptr;  // E5 keep bits, max_b scans x kMaskStride words
-  uint32_t *d_redo = nullptr;     // E5 inside the voxel kernel: [0] work items left to the two-kernel path, [4 ...] which
-  int32_t ror_fused = 1;          // RPLGPU_ROR_FUSED=0: always the two kernels (tests / A-B runs)
-  uint32_t *d_need_sort = nullptr;  // ascend: [0] how many scans the sorting kernel must redo, [1..] which (B + 1 words)
-  uint32_t need_sort_cap = 0;
-  uint32_t *d_small = nullptr;  // [0]=n, [1]=count, [2]=status, [8]=divide-validation mismatches, [16] voxel work
-                                // counter, [20..21] single-scan ascend list, [24..27] voxel queue statistics
-  // fast-divide validation cache (see k_validate_div)
-  bool div4000_ok = false;
-  float leaf_checked = 0.0f;
-  bool leaf_ok = false;
-  bool idx_checked = false, idx_ok = false;  // Mode A bin-index divide, see k_validate_idx
-  // rplgpu_debug_force_ieee_div (tests): bits of rplgpu_debug_fast_div to treat as "validation failed".
-  // Kept apart from the *_ok flags: they go on recording what the validators found.
-  uint32_t force_ieee = 0;
-  unsigned long long *dbg = nullptr;  // developer aid: per-block phase cycle counters
-  uint32_t *cell_keys = nullptr;      // optional cell-key output of the voxel kernel (rplgpu_set_cell_key_output)
-  const float *scan_t0 = nullptr;     // optional per-scan time offsets of E6 (rplgpu_set_scan_time_offsets_dev)
-  // k_cloud_voxel's queue statistics of the previous launch, copied to pinned memory behind every
-  // launch (no synchronisation): they choose the kernel instance of the NEXT launch (voxel_split)
-  unsigned long long *h_vstats = nullptr;
-  uint32_t stats_group = 1;           // scans per work item of the launch the statistics come from
-  bool stats_valid = false;           // ... and which batch that launch was over (voxel_split_for)
-  VoxelBatchId stats_id;
-  // the decision per batch identity, for the last few identities (a caller that alternates two staging
-  // buffers, or launches a batch in chunks — rplgpu's own exchange pipeline does — has several alive)
-  struct VoxelDecision { VoxelBatchId id; bool split = false; bool valid = false; };
-  VoxelDecision decisions[8];
-  uint32_t next_decision = 0;
-  int32_t last_split = 0;             // the instance the last batch launch took (rplgpu_debug_voxel_instance)
-  uint32_t n_cu = 0;                  // compute units of `device`
-  void *d_vstore = nullptr;           // k_cloud_voxel record stores (one per resident workgroup)
-  int32_t force_split = -1;           // RPLGPU_VOXEL_SPLIT: -1 follow the statistics, 0 / 1 forced
-  bool dec_stage = true;              // RPLGPU_DEC_STAGE=0: the plain decoder only (tests / A-B runs)
-  uint32_t vstore_wgs = 0;
-  uint32_t vstore_recs = 0;           // records per workgroup (grows with the largest E8 group seen)
-  uint32_t *d_merge = nullptr;        // rplgpu_merge_cells_dev scratch (world x slot_cells words, grown on demand)
-  size_t merge_cap = 0;               // (words)
-  // rplgpu_merge_scans_dev (E9): key rows (G x count u64, all ~0 between launches) and the edge table of
-  // the last spec (e_0 .. e_count), both grown on demand
-  unsigned long long *d_mkeys = nullptr;
-  size_t mkeys_cap = 0;               // (keys)
-  bool mkeys_clean = true;            // false from the merge launch until its finishing launch is queued
-  float2 *d_medges = nullptr;
-  size_t medges_cap = 0;              // (edges)
-  bool mspec_valid = false;           // d_medges / mspec_k hold the table of mspec
-  rplgpu_scan_merge_t mspec;
-  rpl::MergeK mspec_k;
-  unsigned char *d_dec = nullptr;     // rplgpu_decode_stream staging (grown on demand, kept)
-  size_t dec_cap = 0;
-  unsigned char *d_scans = nullptr;   // rplgpu_decode_scans_dev scratch (node streams, sync lists)
-  size_t scans_cap = 0;
-  uint32_t *d_dec_todo = nullptr;     // rplgpu_decode_batch_dev with frame offsets: streams the staged decoder leaves to the plain one
-  size_t dec_todo_cap = 0;            // (words)
-  bool check_ptrs = true;             // batch entry points verify that buffers are device memory
-  // multi-GPU exchange (include/rplgpu_comm.h)
-  void *comm = nullptr;               // ncclComm_t
-  int32_t comm_rank = 0, comm_world = 0;
-  hipStream_t xstream = nullptr;      // exchange stream
-  hipEvent_t ev_main = nullptr, ev_x[4] = {nullptr, nullptr, nullptr, nullptr};  // ring of exchange-done events
-  uint32_t n_exchanges = 0;
-  std::string err;
-};
 
 struct rplgpu_nccl_id_t {
   char internal[128];  // == ncclUniqueId (rccl.h: NCCL_UNIQUE_ID_BYTES)
 };
 
+using namespace rpl::host;
+
 namespace {
 
-constexpr uint32_t kMaskStride = rpl::kMaxN / 32u;  // keep-mask words per scan
-constexpr size_t kTail = 64;  // bytes behind a staging region for the words that travel with it
-
-// Single-scan staging (pinned, one allocation): nodes | tail | results (16 B / sample) | tail | flag.
-// Both regions are rounded up to 64 bytes, so that for EVERY capacity the result area (it receives
-// 16-byte stores) and the flag word's cache line start on a 64-byte boundary.
-constexpr size_t round64(size_t v) { return (v + 63u) & ~(size_t)63u; }
-constexpr size_t stage_out_off(size_t max_n) { return round64(max_n * 8) + kTail; }
+// Single-scan staging (rpl_host.hpp: nodes | tail | results | tail | flag): the flag word and the whole size.
 constexpr size_t stage_flag_off(size_t max_n) { return stage_out_off(max_n) + round64(max_n * 16) + kTail; }
 constexpr size_t stage_bytes(size_t max_n) { return stage_flag_off(max_n) + kTail; }
 
 thread_local std::string g_create_err;
-
-#define RPL_HIP(ctx, call)                                                              \
-  do {                                                                                  \
-    hipError_t e_ = (call);                                                             \
-    if (e_ != hipSuccess) {                                                             \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-      return RPLGPU_ERR_HIP;                                                            \
-    }                                                                                   \
-  } while (0)
 
 // dist_m exactly as src/rplidar_node.cpp:590 evaluates it (u32 -> f32 RNE, IEEE divide).
 inline float host_dist_m(uint32_t d) { return static_cast<float>(d) / 4000.0f; }
@@ -169,56 +67,6 @@ bool make_keep_interval(float range_min, float range_max, uint32_t *lo, uint32_t
   }
   *hi = a;
   return *lo <= *hi;
-}
-
-rpl::KParams to_kparams(const rplgpu_params_t &p) {
-  rpl::KParams k;
-  k.is_new_protocol = p.is_new_protocol != 0;
-  k.inverted = p.inverted != 0;
-  k.scan_processing = p.scan_processing != 0;
-  k.clip_enable = p.clip_enable != 0;
-  k.q_min = p.q_min;
-  k.range_min = p.range_min;
-  k.range_max = p.range_max;
-  k.voxel_leaf = p.voxel_leaf;
-  k.ror_r2 = p.ror_radius * p.ror_radius;
-  k.ror_k = p.ror_min_neighbors;
-  // voxel fixed point: 2^-K = ulp(leaf), so L = leaf*2^K is the leaf's integer significand
-  k.vox_scale = 1.0;
-  k.vox_scale_f = 1.0f;
-  k.vox_L = 1;
-  k.vox_bias = 0;  // (round 3: offsets are summed as wrapping two's complement, no bias)
-  k.inv_leaf = 1.0f;
-  k.leaf_s = 1.0f;
-  k.inv_leaf_s = 1.0f;
-  k.fast_div = 0;
-  k.fast_d4000 = 0;
-  k.dbg = nullptr;
-  k.cell_keys = nullptr;
-  k.d_lo = 1u;  // :584 alone: dist_mm_q2 != 0
-  k.d_span = 0xFFFFFFFEu;
-  k.cell_range_safe = 0;
-  if (k.clip_enable) {
-    uint32_t lo, hi;
-    if (make_keep_interval(p.range_min, p.range_max, &lo, &hi)) {
-      k.d_lo = lo;
-      k.d_span = hi - lo;
-      if (p.voxel_leaf > 0.0f && host_dist_m(hi) / p.voxel_leaf < 32000.0f) k.cell_range_safe = 1;
-    } else {
-      k.d_span = 0u;
-      k.q_min = 256u;  // no quality byte reaches 256: nothing is kept
-    }
-  }
-  if (p.voxel_leaf > 0.0f && std::isfinite(p.voxel_leaf)) {
-    int K = 23 - std::ilogb(p.voxel_leaf);
-    k.vox_scale = std::ldexp(1.0, K);
-    k.vox_scale_f = (float)k.vox_scale;
-    k.vox_L = (int32_t)std::llround((double)p.voxel_leaf * k.vox_scale);
-    k.inv_leaf = 1.0f / p.voxel_leaf;
-    k.leaf_s = p.voxel_leaf * k.vox_scale_f;
-    k.inv_leaf_s = k.inv_leaf / k.vox_scale_f;
-  }
-  return k;
 }
 
 // Which instance of k_cloud_voxel a batch launch uses: the one whose blocks may be aggregated in
@@ -270,26 +118,6 @@ bool voxel_split_for(rplgpu_ctx *c, const void *d_nodes, uint32_t n_stride, uint
   }
   c->last_split = (c->force_split >= 0 ? c->force_split != 0 : split) ? 1 : 0;
   return c->last_split != 0;
-}
-
-rpl::Tables tables_of(rplgpu_ctx *c) {
-  rpl::Tables t;
-  t.angle = c->d_angle;
-  t.angle_inv = c->d_angle_inv;
-  t.cs = c->d_cs;
-  t.cs_inv = c->d_cs_inv;
-  t.rcp = c->d_rcp;
-  t.work_ctr = c->d_small + 16;  // [16] next scan of k_cloud_voxel's queue (cleared per launch)
-  t.n_cu = c->n_cu;
-  t.voxel_store = c->d_vstore;
-  t.voxel_store_wgs = c->vstore_wgs;
-  t.voxel_store_recs = c->vstore_recs;
-  t.voxel_stats = reinterpret_cast<unsigned long long *>(c->d_small + 24);  // [24..27]
-  t.voxel_stats_host = c->h_vstats;
-  t.voxel_split = c->force_split > 0 ? 1 : 0;  // (batch launches: voxel_split_for)
-  t.scan_t0 = c->scan_t0;
-  t.redo = c->d_redo;
-  return t;
 }
 
 // The reference's per-sample angle arithmetic, evaluated once per possible u16 input
@@ -365,52 +193,6 @@ void free_ctx(rplgpu_ctx *c) {
   delete c;
 }
 
-// A wrong pointer handed to a kernel is a GPU memory fault, and on this platform a fault ends
-// the whole process (the node would die instead of falling back to its CPU loop, cf.
-// src/rplidar_node.cpp:453-474).  So the batch entry points ask the runtime what a pointer is
-// before launching: it has to be device (or managed / mapped host) memory reachable from the
-// handle's device.  ~1 us per pointer against launches of >= tens of us.
-bool device_readable(rplgpu_ctx *c, const void *ptr, const char *what) {
-  if (!c->check_ptrs) return true;
-  hipPointerAttribute_t a;
-  std::memset(&a, 0, sizeof(a));
-  const hipError_t e = hipPointerGetAttributes(&a, ptr);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();  // unregistered host memory: not an error state worth keeping
-    c->err = std::string(what) + " is not device-accessible memory";
-    return false;
-  }
-  if (a.type == hipMemoryTypeDevice && a.device != c->device) {
-    int can = 0;
-    if (hipDeviceCanAccessPeer(&can, c->device, a.device) != hipSuccess || !can) {
-      c->err = std::string(what) + " lives on another device without peer access";
-      return false;
-    }
-  }
-  if (a.type == hipMemoryTypeUnregistered) {
-    c->err = std::string(what) + " is plain host memory";
-    return false;
-  }
-  return true;
-}
-
-int32_t check_batch(rplgpu_ctx *c, const void *nodes, uint32_t n_stride, const void *n_per_scan,
-                    uint32_t B, bool own_buffers = false) {  // (the handle's own staging: no pointer check)
-  if (!c) return RPLGPU_ERR_INVALID_ARG;
-  if (B == 0) return RPLGPU_OK;
-  if (!nodes || !n_per_scan || n_stride == 0) {
-    c->err = "null buffer or zero stride";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (B > c->max_b) {
-    c->err = "batch larger than max_batch given to rplgpu_create";
-    return RPLGPU_ERR_CAPACITY;
-  }
-  if (!own_buffers && (!device_readable(c, nodes, "d_nodes") || !device_readable(c, n_per_scan, "d_n_per_scan")))
-    return RPLGPU_ERR_INVALID_ARG;
-  return RPLGPU_OK;
-}
-
 // Exhaustively compare the mul+2*FMA divide with the IEEE divide for divisor d on the
 // device (about 2.4e9 operands, a few ms).  Returns RPLGPU_OK and sets *ok.
 // (`rd`: the reciprocal the cheap divide is given — RN(1/d) for every caller but rplgpu_debug_validate_div)
@@ -429,11 +211,6 @@ int32_t validate_divisor(rplgpu_ctx *c, float d, uint32_t e_lo, uint32_t e_hi, b
   *ok = (bad == 0);
   return RPLGPU_OK;
 }
-
-// What the launch sites consult: the validators' verdicts, less what rplgpu_debug_force_ieee_div refuses.
-inline bool use_fast_d4000(const rplgpu_ctx *c) { return c->div4000_ok && !(c->force_ieee & 1u); }
-inline bool use_fast_leaf(const rplgpu_ctx *c) { return c->leaf_ok && !(c->force_ieee & 2u); }
-inline bool use_fast_idx(const rplgpu_ctx *c) { return c->idx_ok && !(c->force_ieee & 4u); }
 
 // publish_scan on the handle's stream: Mode A (rpl_laserscan.hip) or Mode B.  The cheap
 // bin-index divide of Mode A is used only after it was compared with the IEEE divide for
@@ -473,9 +250,6 @@ int32_t ensure_idx_checked(rplgpu_ctx *c) {
   }
   return RPLGPU_OK;
 }
-
-// Single-scan staging (pinned host side): nodes | length word ... results | result words.
-inline unsigned char *stage_out(const rplgpu_ctx *c) { return c->h_pin + stage_out_off(c->max_n); }
 
 // nodes + their count to the device in ONE copy; *d_n = device address of the count word
 int32_t upload_scan(rplgpu_ctx *c, const rplgpu_node_t *nodes, size_t n, const uint32_t **d_n) {
@@ -535,6 +309,130 @@ inline ScanStage stage_scan(rplgpu_ctx *c, const rplgpu_node_t *nodes, size_t n)
 }
 
 }  // namespace
+
+// ---- the helpers the stage units use as well (declared in rpl_host.hpp) ------------------------
+
+namespace rpl {
+namespace host {
+
+rpl::KParams to_kparams(const rplgpu_params_t &p) {
+  rpl::KParams k;
+  k.is_new_protocol = p.is_new_protocol != 0;
+  k.inverted = p.inverted != 0;
+  k.scan_processing = p.scan_processing != 0;
+  k.clip_enable = p.clip_enable != 0;
+  k.q_min = p.q_min;
+  k.range_min = p.range_min;
+  k.range_max = p.range_max;
+  k.voxel_leaf = p.voxel_leaf;
+  k.ror_r2 = p.ror_radius * p.ror_radius;
+  k.ror_k = p.ror_min_neighbors;
+  // voxel fixed point: 2^-K = ulp(leaf), so L = leaf*2^K is the leaf's integer significand
+  k.vox_scale = 1.0;
+  k.vox_scale_f = 1.0f;
+  k.vox_L = 1;
+  k.vox_bias = 0;  // (round 3: offsets are summed as wrapping two's complement, no bias)
+  k.inv_leaf = 1.0f;
+  k.leaf_s = 1.0f;
+  k.inv_leaf_s = 1.0f;
+  k.fast_div = 0;
+  k.fast_d4000 = 0;
+  k.dbg = nullptr;
+  k.cell_keys = nullptr;
+  k.d_lo = 1u;  // :584 alone: dist_mm_q2 != 0
+  k.d_span = 0xFFFFFFFEu;
+  k.cell_range_safe = 0;
+  if (k.clip_enable) {
+    uint32_t lo, hi;
+    if (make_keep_interval(p.range_min, p.range_max, &lo, &hi)) {
+      k.d_lo = lo;
+      k.d_span = hi - lo;
+      if (p.voxel_leaf > 0.0f && host_dist_m(hi) / p.voxel_leaf < 32000.0f) k.cell_range_safe = 1;
+    } else {
+      k.d_span = 0u;
+      k.q_min = 256u;  // no quality byte reaches 256: nothing is kept
+    }
+  }
+  if (p.voxel_leaf > 0.0f && std::isfinite(p.voxel_leaf)) {
+    int K = 23 - std::ilogb(p.voxel_leaf);
+    k.vox_scale = std::ldexp(1.0, K);
+    k.vox_scale_f = (float)k.vox_scale;
+    k.vox_L = (int32_t)std::llround((double)p.voxel_leaf * k.vox_scale);
+    k.inv_leaf = 1.0f / p.voxel_leaf;
+    k.leaf_s = p.voxel_leaf * k.vox_scale_f;
+    k.inv_leaf_s = k.inv_leaf / k.vox_scale_f;
+  }
+  return k;
+}
+
+rpl::Tables tables_of(rplgpu_ctx *c) {
+  rpl::Tables t;
+  t.angle = c->d_angle;
+  t.angle_inv = c->d_angle_inv;
+  t.cs = c->d_cs;
+  t.cs_inv = c->d_cs_inv;
+  t.rcp = c->d_rcp;
+  t.work_ctr = c->d_small + 16;  // [16] next scan of k_cloud_voxel's queue (cleared per launch)
+  t.n_cu = c->n_cu;
+  t.voxel_store = c->d_vstore;
+  t.voxel_store_wgs = c->vstore_wgs;
+  t.voxel_store_recs = c->vstore_recs;
+  t.voxel_stats = reinterpret_cast<unsigned long long *>(c->d_small + 24);  // [24..27]
+  t.voxel_stats_host = c->h_vstats;
+  t.voxel_split = c->force_split > 0 ? 1 : 0;  // (batch launches: voxel_split_for)
+  t.scan_t0 = c->scan_t0;
+  t.redo = c->d_redo;
+  return t;
+}
+
+// A wrong pointer handed to a kernel is a GPU memory fault, and on this platform a fault ends
+// the whole process (the node would die instead of falling back to its CPU loop, cf.
+// src/rplidar_node.cpp:453-474).  So the batch entry points ask the runtime what a pointer is
+// before launching: it has to be device (or managed / mapped host) memory reachable from the
+// handle's device.  ~1 us per pointer against launches of >= tens of us.
+bool device_readable(rplgpu_ctx *c, const void *ptr, const char *what) {
+  if (!c->check_ptrs) return true;
+  hipPointerAttribute_t a;
+  std::memset(&a, 0, sizeof(a));
+  const hipError_t e = hipPointerGetAttributes(&a, ptr);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();  // unregistered host memory: not an error state worth keeping
+    c->err = std::string(what) + " is not device-accessible memory";
+    return false;
+  }
+  if (a.type == hipMemoryTypeDevice && a.device != c->device) {
+    int can = 0;
+    if (hipDeviceCanAccessPeer(&can, c->device, a.device) != hipSuccess || !can) {
+      c->err = std::string(what) + " lives on another device without peer access";
+      return false;
+    }
+  }
+  if (a.type == hipMemoryTypeUnregistered) {
+    c->err = std::string(what) + " is plain host memory";
+    return false;
+  }
+  return true;
+}
+
+int32_t check_batch(rplgpu_ctx *c, const void *nodes, uint32_t n_stride, const void *n_per_scan,
+                    uint32_t B, bool own_buffers) {
+  if (!c) return RPLGPU_ERR_INVALID_ARG;
+  if (B == 0) return RPLGPU_OK;
+  if (!nodes || !n_per_scan || n_stride == 0) {
+    c->err = "null buffer or zero stride";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (B > c->max_b) {
+    c->err = "batch larger than max_batch given to rplgpu_create";
+    return RPLGPU_ERR_CAPACITY;
+  }
+  if (!own_buffers && (!device_readable(c, nodes, "d_nodes") || !device_readable(c, n_per_scan, "d_n_per_scan")))
+    return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+}  // namespace host
+}  // namespace rpl
 
 extern "C" {
 
@@ -1087,2374 +985,6 @@ int32_t rplgpu_cloud_fused_cells_dev(rplgpu_handle_t h, const rplgpu_node_t *d_n
                     d_status, true);
 }
 
-// ---- E9: one merged LaserScan per group of scans (include/rplgpu_msg.h) ---------------------------
-
-int32_t rplgpu_scan_merge_edges(const rplgpu_scan_merge_t *m, float *edges, float *inc) {
-  if (!m) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(m->angle_min) || !std::isfinite(m->angle_max) || !std::isfinite(m->range_min) ||
-      !std::isfinite(m->range_max) || !std::isfinite(m->scan_time))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (m->count == 0 || m->count > RPLGPU_MAX_MERGE_BEAMS) return RPLGPU_ERR_INVALID_ARG;
-  const double span = (double)m->angle_max - (double)m->angle_min;
-  const float f_inc = (float)(span / (double)m->count);
-  if (!(f_inc > 0.0f) || f_inc > (float)(M_PI / 2)) return RPLGPU_ERR_INVALID_ARG;
-  if (span > 2.0 * M_PI * (1.0 + 0x1p-20)) return RPLGPU_ERR_INVALID_ARG;
-  if (!(0.0f <= m->range_min && m->range_min < m->range_max)) return RPLGPU_ERR_INVALID_ARG;
-  if (edges)
-    for (uint32_t k = 0; k <= m->count; ++k) {
-      const double phi = (double)m->angle_min + (double)k * (double)f_inc;
-      edges[2 * k] = (float)std::cos(phi);
-      edges[2 * k + 1] = (float)std::sin(phi);
-    }
-  if (inc) *inc = f_inc;
-  return RPLGPU_OK;
-}
-
-namespace {
-
-// e_a -> e_b turns by an angle in (0, pi): the exact sign of the fp64 cross product of float vectors
-bool turns_left(float2 a, float2 b) { return (double)a.x * (double)b.y - (double)a.y * (double)b.x > 0.0; }
-
-// the edge table of spec `m` on the device and the kernel's view of it (cached per spec)
-int32_t merge_spec_upload(rplgpu_ctx *c, const rplgpu_scan_merge_t &m, rpl::MergeK *out) {
-  if (c->mspec_valid && std::memcmp(&c->mspec, &m, sizeof(m)) == 0) {
-    *out = c->mspec_k;
-    return RPLGPU_OK;
-  }
-  std::vector<float2> e(m.count + 1u);
-  float inc = 0.0f;
-  if (rplgpu_scan_merge_edges(&m, reinterpret_cast<float *>(e.data()), &inc) != RPLGPU_OK) {
-    c->err = "rplgpu_scan_merge_t: invalid spec (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  // the table in use may still be read by queued launches
-  RPL_HIP(c, hipStreamSynchronize(c->stream));
-  c->mspec_valid = false;
-  if (e.size() > c->medges_cap) {
-    if (c->d_medges) (void)hipFree(c->d_medges);
-    c->d_medges = nullptr;
-    c->medges_cap = 0;
-    RPL_HIP(c, hipMalloc((void **)&c->d_medges, e.size() * sizeof(float2)));
-    c->medges_cap = e.size();
-  }
-  RPL_HIP(c, hipMemcpy(c->d_medges, e.data(), e.size() * sizeof(float2), hipMemcpyHostToDevice));
-  rpl::MergeK k;
-  k.edges = c->d_medges;
-  k.count = m.count;
-  bool mono = true;
-  for (uint32_t i = 0; i < m.count && mono; ++i) mono = turns_left(e[i], e[i + 1]);
-  for (int q = 0; q < 5; ++q) {
-    k.qb[q] = (uint32_t)((uint64_t)q * m.count / 4u);
-    k.qe[q] = e[k.qb[q]];
-  }
-  for (int q = 0; q < 4 && mono; ++q)
-    if (k.qb[q] != k.qb[q + 1]) mono = turns_left(k.qe[q], k.qe[q + 1]);
-  k.monotone = mono ? 1u : 0u;
-  double a0 = std::fmod((double)m.angle_min, 2.0 * M_PI);
-  if (a0 < 0.0) a0 += 2.0 * M_PI;
-  k.a0 = (float)a0;
-  k.rinc = 1.0f / inc;
-  k.range_min = m.range_min;
-  k.range_max = m.range_max;
-  c->mspec = m;
-  c->mspec_k = k;
-  c->mspec_valid = true;
-  *out = k;
-  return RPLGPU_OK;
-}
-
-}  // namespace
-
-int32_t rplgpu_merge_scans_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
-                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group,
-                               const rplgpu_params_t *p, const float *d_motion, const float *d_pose2d,
-                               const rplgpu_scan_merge_t *m, float *d_ranges, float *d_intensities,
-                               uint32_t *d_beams_hit, uint32_t *d_status) {
-  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
-  if (rc) return rc;
-  if (!p || !m || !d_ranges || !d_intensities || !d_beams_hit || group == 0) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_scan_merge_edges(m, nullptr, nullptr) != RPLGPU_OK) {
-    h->err = "rplgpu_merge_scans_dev: invalid rplgpu_scan_merge_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (B == 0) return RPLGPU_OK;
-  if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
-      (d_pose2d && !device_readable(h, d_pose2d, "d_pose2d")) ||
-      !device_readable(h, d_ranges, "d_ranges") || !device_readable(h, d_intensities, "d_intensities") ||
-      !device_readable(h, d_beams_hit, "d_beams_hit") || (d_status && !device_readable(h, d_status, "d_status")))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (h->scan_t0 && !d_motion) {
-    h->err = "rplgpu_merge_scans_dev: scan time offsets are set (rplgpu_set_scan_time_offsets_dev) but d_motion is NULL";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
-    h->err = "ror_radius must be in (0, 1e6] m";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  group = std::min(group, B);  // as E8: "all sensors in one scan" may be asked for with any group >= B
-  if ((uint64_t)group * std::min(n_stride, rpl::kMaxN) > (1ull << 24) || group > (1u << rpl::kMergeSlotBits)) {
-    h->err = "rplgpu_merge_scans_dev: group x n_stride above 2^24 samples";
-    return RPLGPU_ERR_CAPACITY;
-  }
-  const uint32_t G = (B + group - 1u) / group;
-  RPL_HIP(h, hipSetDevice(h->device));
-  rpl::MergeK mk;
-  if ((rc = merge_spec_upload(h, *m, &mk))) return rc;
-  const size_t need = (size_t)G * m->count;
-  if (need > h->mkeys_cap) {  // (only ever grows; fresh rows are empty)
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->d_mkeys) (void)hipFree(h->d_mkeys);
-    h->d_mkeys = nullptr;
-    h->mkeys_cap = 0;
-    if (hipMalloc((void **)&h->d_mkeys, need * sizeof(unsigned long long)) != hipSuccess) {
-      h->err = "merge key rows allocation failed";
-      (void)hipGetLastError();
-      return RPLGPU_ERR_HIP;
-    }
-    h->mkeys_cap = need;
-    h->mkeys_clean = false;
-  }
-  if (!h->mkeys_clean)  // a new allocation, or a call that failed between the two launches
-    RPL_HIP(h, hipMemsetAsync(h->d_mkeys, 0xFF, h->mkeys_cap * sizeof(unsigned long long), h->stream));
-  rpl::KParams kp = to_kparams(*p);
-  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
-  const rpl::Tables T = tables_of(h);
-  const uint32_t *mask = nullptr;
-  if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E8's two-kernel path applies
-    RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
-                                    kMaskStride));
-    mask = h->d_rormask;
-  }
-  RPL_HIP(h, hipMemsetAsync(d_beams_hit, 0, (size_t)G * 4u, h->stream));
-  if (d_status) RPL_HIP(h, hipMemsetAsync(d_status, 0, (size_t)G * 4u, h->stream));
-  h->mkeys_clean = false;
-  RPL_HIP(h, rpl::launch_merge_scans(h->stream, d_nodes, n_stride, d_n_per_scan, B, group, kp, T, mask,
-                                     kMaskStride, d_motion, d_pose2d, mk, h->d_mkeys, d_status));
-  RPL_HIP(h, rpl::launch_merge_finish(h->stream, h->d_mkeys, G, m->count, d_nodes, n_stride, group,
-                                      p->is_new_protocol, d_ranges, d_intensities, d_beams_hit));
-  h->mkeys_clean = true;
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_merged_laserscan_msgs_dev(rplgpu_handle_t h, const float *d_ranges,
-                                         const float *d_intensities, uint32_t G,
-                                         const rplgpu_scan_merge_t *m, const char *frame_id,
-                                         const rplgpu_stamp_t *d_stamps, uint8_t *d_msgs,
-                                         uint32_t msg_stride, uint32_t *d_msg_len, uint32_t *d_status) {
-  if (!h || !m || !frame_id) return RPLGPU_ERR_INVALID_ARG;
-  float inc = 0.0f;
-  if (rplgpu_scan_merge_edges(m, nullptr, &inc) != RPLGPU_OK) {
-    h->err = "rplgpu_merged_laserscan_msgs_dev: invalid rplgpu_scan_merge_t";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (G == 0) return RPLGPU_OK;
-  if (!d_ranges || !d_intensities || !d_stamps || !d_msgs || !d_msg_len || (msg_stride & 3u))
-    return RPLGPU_ERR_INVALID_ARG;
-  const size_t fl = std::strlen(frame_id);
-  if (fl > rplmsg::kMaxFrameId) {
-    h->err = "frame_id longer than 255 bytes";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  rplgpu_scan_meta_t meta;
-  std::memset(&meta, 0, sizeof(meta));
-  meta.angle_min = m->angle_min;
-  meta.angle_max = m->angle_max;
-  meta.angle_increment = inc;
-  meta.time_increment = 0.0f;  // every point is already moved to the fused instant
-  meta.scan_time = m->scan_time;
-  meta.range_min = m->range_min;
-  meta.range_max = m->range_max;
-  meta.count = m->count;
-  meta.published = 1;
-  rplmsg::Prefix P;
-  std::memset(&P, 0, sizeof(P));
-  rplmsg::Writer w(reinterpret_cast<uint8_t *>(P.words), sizeof(P.words));
-  rplgpu_laserscan_layout_t L;
-  rplmsg::write_laserscan(w, frame_id, fl, rplgpu_stamp_t{0, 0}, meta, &L);
-  P.stamp_off = 4;
-  P.len = L.ranges_off;  // every scalar and the ranges length word come with the template
-  P.a_off = L.scalars_off;
-  P.b_off = L.ranges_len_off;
-  if (P.len > sizeof(P.words) || (P.len & 3u)) {
-    h->err = "message prefix does not fit the device template";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  RPL_HIP(h, hipSetDevice(h->device));
-  RPL_HIP(h, rpl::launch_msg_merged(h->stream, d_ranges, d_intensities, m->count, G, d_stamps, P, d_msgs,
-                                    msg_stride, d_msg_len, d_status));
-  return RPLGPU_OK;
-}
-
-// ---- E10: scan-shadow and speckle filters on LaserScan arrays (include/rplgpu_msg.h) ---------------
-
-void rplgpu_default_scan_filter(rplgpu_scan_filter_t *f) {
-  if (!f) return;
-  f->shadow_enable = 1;
-  f->shadow_min_angle = (float)(10.0 * M_PI / 180.0);
-  f->shadow_max_angle = (float)(170.0 * M_PI / 180.0);
-  f->shadow_window = 2;
-  f->shadow_neighbors = 1;
-  f->speckle_enable = 1;
-  f->speckle_max_range_difference = 0.05f;
-  f->speckle_min_run = 4;
-  f->circular = 1;
-}
-
-int32_t rplgpu_scan_filter_check(const rplgpu_scan_filter_t *f, float dirs[4]) {
-  if (!f) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(f->shadow_min_angle) || !std::isfinite(f->shadow_max_angle) ||
-      !std::isfinite(f->speckle_max_range_difference))
-    return RPLGPU_ERR_INVALID_ARG;
-  const double lo = (double)f->shadow_min_angle, hi = (double)f->shadow_max_angle;
-  if (!(0.0 < lo && lo < M_PI / 2 && M_PI / 2 < hi && hi < M_PI)) return RPLGPU_ERR_INVALID_ARG;
-  if (f->shadow_window < 1u || f->shadow_window > RPLGPU_MAX_FILTER_WINDOW ||
-      f->shadow_neighbors > RPLGPU_MAX_FILTER_WINDOW || f->speckle_min_run < 1u ||
-      f->speckle_min_run > RPLGPU_MAX_FILTER_WINDOW || !(f->speckle_max_range_difference >= 0.0f))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (dirs) {
-    dirs[0] = (float)std::cos(lo);
-    dirs[1] = (float)std::sin(lo);
-    dirs[2] = (float)std::cos(hi);
-    dirs[3] = (float)std::sin(hi);
-  }
-  return RPLGPU_OK;
-}
-
-namespace {
-
-int32_t filter_kernel_args(rplgpu_ctx *c, const rplgpu_scan_filter_t *f, rpl::FilterK *k) {
-  float dirs[4];
-  if (rplgpu_scan_filter_check(f, dirs) != RPLGPU_OK) {
-    c->err = "invalid rplgpu_scan_filter_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  std::memset(k, 0, sizeof(*k));
-  k->shadow = f->shadow_enable ? 1u : 0u;
-  k->speckle = f->speckle_enable ? 1u : 0u;
-  k->circular = f->circular ? 1u : 0u;
-  k->W = f->shadow_window;
-  k->N = f->shadow_neighbors;
-  k->L = f->speckle_min_run;
-  k->D = f->speckle_max_range_difference;
-  k->cmin = dirs[0];
-  k->smin = dirs[1];
-  k->cmax = dirs[2];
-  k->smax = dirs[3];
-  return RPLGPU_OK;
-}
-
-}  // namespace
-
-int32_t rplgpu_filter_laserscan_batch_dev(rplgpu_handle_t h, const float *d_ranges, const float *d_intensities,
-                                          uint32_t n_stride, const uint32_t *d_beam_count, uint32_t B,
-                                          const rplgpu_params_t *p, const rplgpu_scan_filter_t *f,
-                                          float *d_ranges_out, float *d_intensities_out, uint32_t *d_removed) {
-  if (!h || !p || !f) return RPLGPU_ERR_INVALID_ARG;
-  rpl::FilterK k;
-  if (int32_t rc = filter_kernel_args(h, f, &k)) return rc;
-  if (B == 0) return RPLGPU_OK;
-  if (!d_ranges || !d_intensities || !d_beam_count || !d_ranges_out || !d_intensities_out || n_stride == 0)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (d_ranges_out == d_ranges || d_intensities_out == d_intensities) {
-    h->err = "rplgpu_filter_laserscan_batch_dev: the filters do not work in place";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  k.inc_mode = p->scan_processing ? rpl::kFilterIncModeA : rpl::kFilterIncModeB;
-  RPL_HIP(h, hipSetDevice(h->device));
-  if (d_removed) RPL_HIP(h, hipMemsetAsync(d_removed, 0, (size_t)B * 8u, h->stream));
-  RPL_HIP(h, rpl::launch_filter_scans(h->stream, d_ranges, d_intensities, n_stride, d_beam_count, B, k,
-                                      d_ranges_out, d_intensities_out, d_removed));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_filter_merged_scans_dev(rplgpu_handle_t h, const float *d_ranges, const float *d_intensities,
-                                       uint32_t G, const rplgpu_scan_merge_t *m, const rplgpu_scan_filter_t *f,
-                                       float *d_ranges_out, float *d_intensities_out, uint32_t *d_removed) {
-  if (!h || !m || !f) return RPLGPU_ERR_INVALID_ARG;
-  rpl::FilterK k;
-  if (int32_t rc = filter_kernel_args(h, f, &k)) return rc;
-  float inc = 0.0f;
-  if (rplgpu_scan_merge_edges(m, nullptr, &inc) != RPLGPU_OK) {
-    h->err = "rplgpu_filter_merged_scans_dev: invalid rplgpu_scan_merge_t";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (G == 0) return RPLGPU_OK;
-  if (!d_ranges || !d_intensities || !d_ranges_out || !d_intensities_out) return RPLGPU_ERR_INVALID_ARG;
-  if (d_ranges_out == d_ranges || d_intensities_out == d_intensities) {
-    h->err = "rplgpu_filter_merged_scans_dev: the filters do not work in place";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  k.inc_mode = rpl::kFilterIncGiven;
-  k.inc = inc;
-  k.count = m->count;
-  RPL_HIP(h, hipSetDevice(h->device));
-  if (d_removed) RPL_HIP(h, hipMemsetAsync(d_removed, 0, (size_t)G * 8u, h->stream));
-  RPL_HIP(h, rpl::launch_filter_scans(h->stream, d_ranges, d_intensities, m->count, nullptr, G, k,
-                                      d_ranges_out, d_intensities_out, d_removed));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_filter_laserscan(rplgpu_handle_t h, const float *ranges, const float *intensities, uint32_t count,
-                                float angle_increment, const rplgpu_scan_filter_t *f, float *ranges_out,
-                                float *intensities_out, uint32_t removed[2]) {
-  if (!h || !f) return RPLGPU_ERR_INVALID_ARG;
-  rpl::FilterK k;
-  if (int32_t rc = filter_kernel_args(h, f, &k)) return rc;
-  if (!std::isfinite(angle_increment) || !(angle_increment > 0.0f)) {
-    h->err = "rplgpu_filter_laserscan: angle_increment must be finite and positive";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (count && (!ranges || !intensities || !ranges_out || !intensities_out)) return RPLGPU_ERR_INVALID_ARG;
-  if (count && (ranges_out == ranges || intensities_out == intensities)) {
-    h->err = "rplgpu_filter_laserscan: the filters do not work in place";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (count > h->max_n) return RPLGPU_ERR_CAPACITY;
-  if (removed) removed[0] = removed[1] = 0u;
-  if (count == 0) return RPLGPU_OK;
-  k.inc_mode = rpl::kFilterIncGiven;
-  k.inc = angle_increment;
-  k.count = count;
-  RPL_HIP(h, hipSetDevice(h->device));
-  // staging as rplgpu_laserscan_to_cloud: ranges | intensities in (d_nodes holds 8 B per sample),
-  // ranges | intensities | the two counts out (d_out holds 16 B per sample)
-  const size_t n = count;
-  std::memcpy(h->h_pin, ranges, n * 4);
-  std::memcpy(h->h_pin + n * 4, intensities, n * 4);
-  RPL_HIP(h, hipMemcpyAsync(h->d_nodes, h->h_pin, n * 8, hipMemcpyHostToDevice, h->stream));
-  const float *d_r = reinterpret_cast<const float *>(h->d_nodes);
-  float *d_o = reinterpret_cast<float *>(h->d_out);
-  uint32_t *d_rm = reinterpret_cast<uint32_t *>(h->d_out + n * 8);
-  RPL_HIP(h, hipMemsetAsync(d_rm, 0, 8, h->stream));
-  RPL_HIP(h, rpl::launch_filter_scans(h->stream, d_r, d_r + n, count, nullptr, 1, k, d_o, d_o + n, d_rm));
-  unsigned char *h_out = stage_out(h);
-  RPL_HIP(h, hipMemcpyAsync(h_out, h->d_out, n * 8 + 8, hipMemcpyDeviceToHost, h->stream));
-  RPL_HIP(h, hipStreamSynchronize(h->stream));
-  std::memcpy(ranges_out, h_out, n * 4);
-  std::memcpy(intensities_out, h_out + n * 4, n * 4);
-  if (removed) std::memcpy(removed, h_out + n * 8, 8);
-  return RPLGPU_OK;
-}
-
-// ---- E11: one ray-cast occupancy grid per group of scans (include/rplgpu_msg.h) ---------------------
-
-void rplgpu_default_occ_grid(rplgpu_occ_grid_t *grid) {
-  if (!grid) return;
-  grid->origin_x = -25.6f;
-  grid->origin_y = -25.6f;
-  grid->resolution = 0.05f;
-  grid->width = 1024;
-  grid->height = 1024;
-  grid->range_min = 0.0f;
-  grid->obstacle_max = 25.0f;
-  grid->raytrace_max = 30.0f;
-}
-
-int32_t rplgpu_occ_grid_check(const rplgpu_occ_grid_t *g) {
-  if (!g) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(g->origin_x) || !std::isfinite(g->origin_y) || !std::isfinite(g->resolution) ||
-      !std::isfinite(g->range_min) || !std::isfinite(g->obstacle_max) || !std::isfinite(g->raytrace_max))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (!(g->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
-  if (g->width == 0 || g->width > RPLGPU_MAX_OCC_DIM || g->height == 0 || g->height > RPLGPU_MAX_OCC_DIM)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (!(0.0f <= g->range_min && g->range_min < g->obstacle_max && g->obstacle_max <= g->raytrace_max))
-    return RPLGPU_ERR_INVALID_ARG;
-  if ((double)g->raytrace_max / (double)g->resolution > (double)RPLGPU_MAX_OCC_STEPS) return RPLGPU_ERR_INVALID_ARG;
-  return RPLGPU_OK;
-}
-
-static rpl::OccK occ_kernel_args(const rplgpu_occ_grid_t &g) {
-  return rpl::OccK{g.origin_x, g.origin_y, g.resolution, g.width, g.height, g.range_min, g.obstacle_max,
-                   g.raytrace_max};
-}
-
-// d_t0: the per-scan time offsets of E6 for this call (the handle's, or the host door's own), or NULL
-static int32_t occ_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
-                        const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
-                        const float *d_motion, const float *d_pose2d, const float *d_t0,
-                        const rplgpu_occ_grid_t *grid, const int8_t *d_prev, int8_t *d_grid,
-                        uint64_t grid_stride, uint32_t *d_cells, uint32_t *d_status) {
-  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
-  if (rc) return rc;
-  if (!p || !grid || !d_grid || group == 0) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_occ_grid_check(grid) != RPLGPU_OK) {
-    h->err = "rplgpu_occupancy_grid_dev: invalid rplgpu_occ_grid_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (grid_stride < (uint64_t)grid->width * grid->height || (grid_stride & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_grid) & 3u)) {
-    h->err = "rplgpu_occupancy_grid_dev: grid_stride must be >= width * height and a multiple of 4, d_grid 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (d_prev == d_grid) {
-    h->err = "rplgpu_occupancy_grid_dev: d_prev must not be d_grid (the grid is its own scratch)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (B == 0) return RPLGPU_OK;
-  if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
-      (d_pose2d && !device_readable(h, d_pose2d, "d_pose2d")) ||
-      (d_prev && !device_readable(h, d_prev, "d_prev")) || !device_readable(h, d_grid, "d_grid") ||
-      (d_cells && !device_readable(h, d_cells, "d_cells")) || (d_status && !device_readable(h, d_status, "d_status")))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (d_t0 && !d_motion) {
-    h->err = "rplgpu_occupancy_grid_dev: scan time offsets are set (rplgpu_set_scan_time_offsets_dev) but d_motion is NULL";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
-    h->err = "ror_radius must be in (0, 1e6] m";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  group = std::min(group, B);  // as E8: "all sensors in one grid" may be asked for with any group >= B
-  if ((uint64_t)group * std::min(n_stride, rpl::kMaxN) > (1ull << 24)) {
-    h->err = "rplgpu_occupancy_grid_dev: group x n_stride above 2^24 samples";
-    return RPLGPU_ERR_CAPACITY;
-  }
-  const uint32_t G = (B + group - 1u) / group;
-  RPL_HIP(h, hipSetDevice(h->device));
-  rpl::KParams kp = to_kparams(*p);
-  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
-  rpl::Tables T = tables_of(h);
-  T.scan_t0 = d_t0;
-  const rpl::OccK k = occ_kernel_args(*grid);
-  const uint32_t *mask = nullptr;
-  if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E8's two-kernel path and E9 apply
-    RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
-                                    kMaskStride));
-    mask = h->d_rormask;
-  }
-  if (d_cells) RPL_HIP(h, hipMemsetAsync(d_cells, 0, (size_t)G * 12u, h->stream));
-  if (d_status) RPL_HIP(h, hipMemsetAsync(d_status, 0, (size_t)G * 4u, h->stream));
-  RPL_HIP(h, rpl::launch_occ_prepare(h->stream, d_grid, grid_stride, G, k));
-  RPL_HIP(h, rpl::launch_occ_walk(h->stream, d_nodes, n_stride, d_n_per_scan, B, group, kp, T, mask, kMaskStride,
-                                  d_motion, d_pose2d, k, d_grid, grid_stride, d_status));
-  RPL_HIP(h, rpl::launch_occ_finish(h->stream, d_grid, grid_stride, G, k, d_prev, d_cells));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_occupancy_grid_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
-                                  const uint32_t *d_n_per_scan, uint32_t B, uint32_t group,
-                                  const rplgpu_params_t *p, const float *d_motion, const float *d_pose2d,
-                                  const rplgpu_occ_grid_t *grid, const int8_t *d_prev, int8_t *d_grid,
-                                  uint64_t grid_stride, uint32_t *d_cells, uint32_t *d_status) {
-  if (!h) return RPLGPU_ERR_INVALID_ARG;
-  return occ_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, h->scan_t0, grid, d_prev,
-                  d_grid, grid_stride, d_cells, d_status);
-}
-
-int32_t rplgpu_occupancy_grid(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
-                              const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
-                              const float *motion, const float *pose2d, const float *t0,
-                              const rplgpu_occ_grid_t *grid, const int8_t *prev, int8_t *grid_out,
-                              uint32_t cells[3], uint32_t *status) {
-  if (!h || !nodes || !n_per_scan || !p || !grid || !grid_out || n_scans == 0 || n_stride == 0)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_occ_grid_check(grid) != RPLGPU_OK) {
-    h->err = "rplgpu_occupancy_grid: invalid rplgpu_occ_grid_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
-  RPL_HIP(h, hipSetDevice(h->device));
-  const size_t cells_n = (size_t)grid->width * grid->height, stride = (cells_n + 3u) & ~(size_t)3u;
-  const size_t nb = (size_t)n_scans * n_stride * 8u;
-  // one allocation per call (a convenience door, not the hot path): grid | prev | nodes | lengths |
-  // motion | pose | t0 | cells + status, every part 16-byte aligned
-  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  const size_t o_prev = up16(stride), o_nodes = o_prev + up16(prev ? stride : 0), o_len = o_nodes + up16(nb),
-               o_mo = o_len + up16(4u * n_scans), o_po = o_mo + up16(motion ? 16u * n_scans : 0),
-               o_t0 = o_po + up16(pose2d ? 24u * n_scans : 0), o_small = o_t0 + up16(t0 ? 4u * n_scans : 0),
-               total = o_small + 16u;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_occupancy_grid: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t small[4] = {0, 0, 0, 0};
-  auto run = [&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(d + o_nodes, nodes, nb, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_len, n_per_scan, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (prev) RPL_HIP(h, hipMemcpyAsync(d + o_prev, prev, cells_n, hipMemcpyHostToDevice, h->stream));
-    if (motion) RPL_HIP(h, hipMemcpyAsync(d + o_mo, motion, 16u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (pose2d) RPL_HIP(h, hipMemcpyAsync(d + o_po, pose2d, 24u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (t0) RPL_HIP(h, hipMemcpyAsync(d + o_t0, t0, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
-    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);
-    const int32_t rc = occ_impl(
-        h, reinterpret_cast<const rplgpu_node_t *>(d + o_nodes), n_stride,
-        reinterpret_cast<const uint32_t *>(d + o_len), n_scans, n_scans, p,
-        motion ? reinterpret_cast<const float *>(d + o_mo) : nullptr,
-        pose2d ? reinterpret_cast<const float *>(d + o_po) : nullptr,
-        t0 ? reinterpret_cast<const float *>(d + o_t0) : nullptr, grid,
-        prev ? reinterpret_cast<const int8_t *>(d + o_prev) : nullptr, reinterpret_cast<int8_t *>(d), stride,
-        d_small, d_small + 3);
-    if (rc) return rc;
-    RPL_HIP(h, hipMemcpyAsync(grid_out, d, cells_n, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(small, d_small, 16, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;
-  if (cells) std::memcpy(cells, small, 12);
-  if (status) *status = small[3];
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_msg_occupancy_layout(size_t frame_id_len, uint32_t width, uint32_t height,
-                                    rplgpu_occupancy_layout_t *out) {
-  if (!out || frame_id_len > (1u << 20) || width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 ||
-      height > RPLGPU_MAX_OCC_DIM)
-    return RPLGPU_ERR_INVALID_ARG;
-  rplmsg::Writer w(nullptr, 0);
-  std::string fid(frame_id_len, 'x');
-  rplmsg::write_occupancy(w, fid.data(), frame_id_len, rplgpu_stamp_t{0, 0}, 1.0f, width, height, 0.0f, 0.0f, out);
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_occupancy_grid_msgs_dev(rplgpu_handle_t h, const int8_t *d_grid, uint64_t grid_stride, uint32_t G,
-                                       const rplgpu_occ_grid_t *grid, const char *frame_id,
-                                       const rplgpu_stamp_t *d_stamps, uint8_t *d_msgs, uint32_t msg_stride,
-                                       uint32_t *d_msg_len, uint32_t *d_status) {
-  if (!h || !grid || !frame_id) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_occ_grid_check(grid) != RPLGPU_OK) {
-    h->err = "rplgpu_occupancy_grid_msgs_dev: invalid rplgpu_occ_grid_t";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (G == 0) return RPLGPU_OK;
-  if (!d_grid || !d_stamps || !d_msgs || !d_msg_len || (msg_stride & 3u) || (grid_stride & 3u) ||
-      grid_stride < (uint64_t)grid->width * grid->height || (reinterpret_cast<uintptr_t>(d_grid) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_msgs) & 3u))
-    return RPLGPU_ERR_INVALID_ARG;
-  const size_t fl = std::strlen(frame_id);
-  if (fl > rplmsg::kMaxFrameId) {
-    h->err = "frame_id longer than 255 bytes";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  rplmsg::Prefix P;
-  std::memset(&P, 0, sizeof(P));
-  rplmsg::Writer w(reinterpret_cast<uint8_t *>(P.words), sizeof(P.words));
-  rplgpu_occupancy_layout_t L;
-  rplmsg::write_occupancy(w, frame_id, fl, rplgpu_stamp_t{0, 0}, grid->resolution, grid->width, grid->height,
-                          grid->origin_x, grid->origin_y, &L);
-  P.stamp_off = 4;
-  P.len = L.data_off;  // every scalar and the data length word come with the template
-  P.a_off = L.map_load_time_off;
-  if (P.len > sizeof(P.words) || (P.len & 3u)) {
-    h->err = "message prefix does not fit the device template";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  RPL_HIP(h, hipSetDevice(h->device));
-  RPL_HIP(h, rpl::launch_msg_occupancy(h->stream, d_grid, grid_stride, grid->width * grid->height, G, d_stamps, P,
-                                       d_msgs, msg_stride, d_msg_len, d_status));
-  return RPLGPU_OK;
-}
-
-// ---- E12: the grids of E11 inflated into costmaps (include/rplgpu_msg.h) -------------------------------
-
-void rplgpu_default_inflation(rplgpu_inflation_t *f) {
-  if (!f) return;
-  f->inscribed_radius = 0.22f;
-  f->inflation_radius = 0.55f;
-  f->cost_scaling_factor = 3.0f;
-  f->inflate_unknown = 0;
-}
-
-// the check, and Rc of a spec that passes it
-static int32_t inflation_reach(const rplgpu_inflation_t *f, float resolution, uint32_t *rc) {
-  if (!f) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(f->inscribed_radius) || !std::isfinite(f->inflation_radius) ||
-      !std::isfinite(f->cost_scaling_factor) || !std::isfinite(resolution))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (f->inscribed_radius < 0.0f || f->inflation_radius < 0.0f || f->cost_scaling_factor < 0.0f ||
-      !(resolution > 0.0f) || f->inflation_radius < f->inscribed_radius || f->inflate_unknown > 1u)
-    return RPLGPU_ERR_INVALID_ARG;
-  const double cells = std::ceil((double)f->inflation_radius / (double)resolution);
-  if (!(cells <= (double)RPLGPU_MAX_INFLATION_CELLS)) return RPLGPU_ERR_INVALID_ARG;
-  *rc = (uint32_t)cells;
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_inflation_check(const rplgpu_inflation_t *f, float resolution) {
-  uint32_t rc = 0;
-  return inflation_reach(f, resolution, &rc);
-}
-
-int32_t rplgpu_inflation_table(const rplgpu_inflation_t *f, float resolution, uint8_t *table, uint32_t table_cap,
-                               uint32_t *rc_out) {
-  uint32_t rc = 0;
-  if (inflation_reach(f, resolution, &rc) != RPLGPU_OK) return RPLGPU_ERR_INVALID_ARG;
-  if (rc_out) *rc_out = rc;
-  if (!table) return RPLGPU_ERR_INVALID_ARG;
-  if (table_cap < rc * rc + 1u) return RPLGPU_ERR_CAPACITY;
-  const double res = (double)resolution, inscribed = (double)f->inscribed_radius;
-  table[0] = 100;
-  for (uint32_t k = 1; k <= rc * rc; ++k) {
-    const double d = std::sqrt((double)k) * res;
-    table[k] = d <= inscribed
-                   ? (uint8_t)99
-                   : (uint8_t)(int)(98.0 * std::exp(-(double)f->cost_scaling_factor * (d - inscribed)));
-  }
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_inflate_grids_dev(rplgpu_handle_t h, const int8_t *d_in, uint64_t in_stride, int8_t *d_out,
-                                 uint64_t out_stride, uint32_t G, uint32_t width, uint32_t height,
-                                 const uint8_t *d_table, uint32_t rc, uint32_t inflate_unknown, uint32_t *d_cells) {
-  if (!h) return RPLGPU_ERR_INVALID_ARG;
-  if (!d_in || !d_out || !d_table || G == 0) {
-    h->err = "rplgpu_inflate_grids_dev: d_in, d_out and d_table must be given and G >= 1";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (d_in == d_out) {
-    h->err = "rplgpu_inflate_grids_dev: d_out must not be d_in (a tile reads the cells around it)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (rc > RPLGPU_MAX_INFLATION_CELLS || inflate_unknown > 1u) {
-    h->err = "rplgpu_inflate_grids_dev: rc above RPLGPU_MAX_INFLATION_CELLS or inflate_unknown above 1";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 || height > RPLGPU_MAX_OCC_DIM) {
-    h->err = "rplgpu_inflate_grids_dev: width and height must be 1 .. RPLGPU_MAX_OCC_DIM";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const uint64_t n_cells = (uint64_t)width * height;
-  if (in_stride < n_cells || (in_stride & 3u) || out_stride < n_cells || (out_stride & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_in) & 3u) || (reinterpret_cast<uintptr_t>(d_out) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_table) & 3u) || (reinterpret_cast<uintptr_t>(d_cells) & 3u)) {
-    h->err = "rplgpu_inflate_grids_dev: strides must be >= width * height and multiples of 4, pointers 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const uint64_t tiles = (uint64_t)((width + 63u) / 64u) * ((height + 63u) / 64u);
-  if (G * tiles > 0x7FFFFFFFull) {
-    h->err = "rplgpu_inflate_grids_dev: G x tiles above 2^31";
-    return RPLGPU_ERR_CAPACITY;
-  }
-  if (!device_readable(h, d_in, "d_in") || !device_readable(h, d_out, "d_out") ||
-      !device_readable(h, d_table, "d_table") || (d_cells && !device_readable(h, d_cells, "d_cells")))
-    return RPLGPU_ERR_INVALID_ARG;
-  RPL_HIP(h, hipSetDevice(h->device));
-  if (d_cells) RPL_HIP(h, hipMemsetAsync(d_cells, 0, (size_t)G * 16u, h->stream));
-  RPL_HIP(h, rpl::launch_inflate(h->stream, d_in, in_stride, d_out, out_stride, G, width, height, d_table, rc,
-                                 inflate_unknown, d_cells));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_inflate_grid(rplgpu_handle_t h, const int8_t *in, uint32_t width, uint32_t height, float resolution,
-                            const rplgpu_inflation_t *f, int8_t *out, uint32_t cells[4]) {
-  if (!h || !in || !out || !f || in == out) return RPLGPU_ERR_INVALID_ARG;
-  if (width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 || height > RPLGPU_MAX_OCC_DIM) {
-    h->err = "rplgpu_inflate_grid: width and height must be 1 .. RPLGPU_MAX_OCC_DIM";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  std::vector<uint8_t> table((size_t)RPLGPU_MAX_INFLATION_CELLS * RPLGPU_MAX_INFLATION_CELLS + 1u);
-  uint32_t reach = 0;
-  if (rplgpu_inflation_table(f, resolution, table.data(), (uint32_t)table.size(), &reach) != RPLGPU_OK) {
-    h->err = "rplgpu_inflate_grid: invalid rplgpu_inflation_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  RPL_HIP(h, hipSetDevice(h->device));
-  const size_t cells_n = (size_t)width * height, stride = (cells_n + 3u) & ~(size_t)3u;
-  const size_t n_table = (size_t)reach * reach + 1u;
-  // one allocation per call (a convenience door, not the hot path): in | out | table | cells, 16-byte aligned
-  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  const size_t o_out = up16(stride), o_table = o_out + up16(stride), o_cells = o_table + up16(n_table),
-               total = o_cells + 16u;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_inflate_grid: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t small[4] = {0, 0, 0, 0};
-  auto run = [&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(d, in, cells_n, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_table, table.data(), n_table, hipMemcpyHostToDevice, h->stream));
-    const int32_t rc = rplgpu_inflate_grids_dev(h, reinterpret_cast<const int8_t *>(d), stride,
-                                                reinterpret_cast<int8_t *>(d + o_out), stride, 1, width, height,
-                                                d + o_table, reach, f->inflate_unknown,
-                                                reinterpret_cast<uint32_t *>(d + o_cells));
-    if (rc) return rc;
-    RPL_HIP(h, hipMemcpyAsync(out, d + o_out, cells_n, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(small, d + o_cells, 16, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;
-  if (cells) std::memcpy(cells, small, 16);
-  return RPLGPU_OK;
-}
-
-// ---- E13: a time step's scans matched to a likelihood field (include/rplgpu_msg.h) ---------------------------
-
-void rplgpu_default_scan_match(rplgpu_scan_match_t *m) {
-  if (!m) return;
-  m->origin_x = -25.6f;
-  m->origin_y = -25.6f;
-  m->resolution = 0.05f;
-  m->width = 1024;
-  m->height = 1024;
-  m->shift_x = 6;
-  m->shift_y = 6;
-  m->rot_steps = 10;
-  m->rot_step = (float)(0.25 * M_PI / 180.0);
-}
-
-int32_t rplgpu_scan_match_check(const rplgpu_scan_match_t *m) {
-  if (!m) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(m->origin_x) || !std::isfinite(m->origin_y) || !std::isfinite(m->resolution) ||
-      !std::isfinite(m->rot_step))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (!(m->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
-  if (m->width == 0 || m->width > RPLGPU_MAX_OCC_DIM || m->height == 0 || m->height > RPLGPU_MAX_OCC_DIM)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (m->shift_x > RPLGPU_MAX_MATCH_SHIFT || m->shift_y > RPLGPU_MAX_MATCH_SHIFT ||
-      m->rot_steps > RPLGPU_MAX_MATCH_ROT)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (m->rot_steps > 0 && (!(m->rot_step > 0.0f) || (double)m->rot_steps * (double)m->rot_step > M_PI / 2.0))
-    return RPLGPU_ERR_INVALID_ARG;
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_scan_match_rotations(const rplgpu_scan_match_t *m, float *cs) {
-  if (!cs || rplgpu_scan_match_check(m) != RPLGPU_OK) return RPLGPU_ERR_INVALID_ARG;
-  const int K = (int)m->rot_steps;
-  for (int k = -K; k <= K; ++k) {
-    const double a = (double)k * (double)m->rot_step;
-    cs[2 * (k + K)] = (float)std::cos(a);
-    cs[2 * (k + K) + 1] = (float)std::sin(a);
-  }
-  return RPLGPU_OK;
-}
-
-uint32_t rplgpu_scan_match_volume(const rplgpu_scan_match_t *m) {
-  if (rplgpu_scan_match_check(m) != RPLGPU_OK) return 0;
-  return (2u * m->rot_steps + 1u) * (2u * m->shift_y + 1u) * (2u * m->shift_x + 1u);
-}
-
-// d_t0: the per-scan time offsets of E6 for this call (the handle's, or the host door's own), or NULL
-static int32_t match_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
-                          const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
-                          const float *d_motion, const float *d_pose2d, const float *d_t0, const float *d_pivot,
-                          const rplgpu_scan_match_t *m, const int8_t *d_field, uint64_t field_stride,
-                          uint32_t field_per_group, uint32_t *d_scores, uint64_t score_stride, uint32_t *d_best,
-                          uint32_t *d_status) {
-  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
-  if (rc) return rc;
-  if (!p || !m || !d_field || !d_scores || !d_best || group == 0) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_scan_match_check(m) != RPLGPU_OK) {
-    h->err = "rplgpu_match_scans_dev: invalid rplgpu_scan_match_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (field_stride < (uint64_t)m->width * m->height || (field_stride & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_field) & 3u)) {
-    h->err = "rplgpu_match_scans_dev: field_stride must be >= width * height and a multiple of 4, d_field 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const uint32_t volume = rplgpu_scan_match_volume(m);
-  if (score_stride < volume || (reinterpret_cast<uintptr_t>(d_scores) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_best) & 3u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
-    h->err = "rplgpu_match_scans_dev: score_stride must be >= the volume size, d_scores / d_best / d_status 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (B == 0) return RPLGPU_OK;
-  if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
-      (d_pose2d && !device_readable(h, d_pose2d, "d_pose2d")) ||
-      (d_pivot && !device_readable(h, d_pivot, "d_pivot")) || !device_readable(h, d_field, "d_field") ||
-      !device_readable(h, d_scores, "d_scores") || !device_readable(h, d_best, "d_best") ||
-      (d_status && !device_readable(h, d_status, "d_status")))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (d_t0 && !d_motion) {
-    h->err = "rplgpu_match_scans_dev: scan time offsets are set (rplgpu_set_scan_time_offsets_dev) but d_motion is NULL";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
-    h->err = "ror_radius must be in (0, 1e6] m";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  group = std::min(group, B);  // as E8: "all sensors in one match" may be asked for with any group >= B
-  if ((uint64_t)group * n_stride > (1ull << 24)) {  // 127 x points stays below 2^32: no score wraps
-    h->err = "rplgpu_match_scans_dev: group x n_stride above 2^24 samples";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const uint32_t G = (B + group - 1u) / group;
-  const rpl::MatchK k{m->origin_x, m->origin_y, m->resolution, m->width, m->height,
-                      m->shift_x, m->shift_y, m->rot_steps};
-  rpl::MatchRot rot;  // at most 129 pairs, handed to the kernel by value: no copy on the stream
-  std::memset(&rot, 0, sizeof(rot));
-  if (rplgpu_scan_match_rotations(m, rot.cs) != RPLGPU_OK) return RPLGPU_ERR_INVALID_ARG;
-  RPL_HIP(h, hipSetDevice(h->device));
-  rpl::KParams kp = to_kparams(*p);
-  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
-  rpl::Tables T = tables_of(h);
-  T.scan_t0 = d_t0;
-  const uint32_t *mask = nullptr;
-  if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E9 and E11 apply
-    RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
-                                    kMaskStride));
-    mask = h->d_rormask;
-  }
-  if (d_status) RPL_HIP(h, hipMemsetAsync(d_status, 0, (size_t)G * 4u, h->stream));
-  RPL_HIP(h, rpl::launch_match_prepare(h->stream, d_scores, score_stride, G, k, d_best));
-  RPL_HIP(h, rpl::launch_match_score(h->stream, d_nodes, n_stride, d_n_per_scan, B, group, kp, T, mask, kMaskStride,
-                                     d_motion, d_pose2d, d_pivot, k, rot, d_field, field_stride, field_per_group,
-                                     d_scores, score_stride, d_best, d_status));
-  RPL_HIP(h, rpl::launch_match_best(h->stream, d_scores, score_stride, G, k, d_best));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_match_scans_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
-                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
-                               const float *d_motion, const float *d_pose2d, const float *d_pivot,
-                               const rplgpu_scan_match_t *m, const int8_t *d_field, uint64_t field_stride,
-                               uint32_t field_per_group, uint32_t *d_scores, uint64_t score_stride,
-                               uint32_t *d_best, uint32_t *d_status) {
-  if (!h) return RPLGPU_ERR_INVALID_ARG;
-  return match_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, h->scan_t0, d_pivot, m,
-                    d_field, field_stride, field_per_group, d_scores, score_stride, d_best, d_status);
-}
-
-int32_t rplgpu_match_scans(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
-                           const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
-                           const float *motion, const float *pose2d, const float *t0, const float *pivot,
-                           const rplgpu_scan_match_t *m, const int8_t *field, uint32_t *scores_out,
-                           uint32_t best[8], uint32_t *status) {
-  if (!h || !nodes || !n_per_scan || !p || !m || !field || !best || n_scans == 0 || n_stride == 0)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_scan_match_check(m) != RPLGPU_OK) {
-    h->err = "rplgpu_match_scans: invalid rplgpu_scan_match_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
-  RPL_HIP(h, hipSetDevice(h->device));
-  const size_t cells_n = (size_t)m->width * m->height, stride = (cells_n + 3u) & ~(size_t)3u;
-  const size_t nb = (size_t)n_scans * n_stride * 8u;
-  const size_t volume = rplgpu_scan_match_volume(m);
-  // one allocation per call (a convenience door, not the hot path): field | scores | nodes | lengths | motion |
-  // pose | t0 | pivot | best + status, every part 16-byte aligned
-  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  const size_t o_sc = up16(stride), o_nodes = o_sc + up16(4u * volume), o_len = o_nodes + up16(nb),
-               o_mo = o_len + up16(4u * n_scans), o_po = o_mo + up16(motion ? 16u * n_scans : 0),
-               o_t0 = o_po + up16(pose2d ? 24u * n_scans : 0), o_pv = o_t0 + up16(t0 ? 4u * n_scans : 0),
-               o_small = o_pv + up16(pivot ? 8u : 0), total = o_small + 48u;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_match_scans: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t small[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  auto run = [&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(d, field, cells_n, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_nodes, nodes, nb, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_len, n_per_scan, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (motion) RPL_HIP(h, hipMemcpyAsync(d + o_mo, motion, 16u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (pose2d) RPL_HIP(h, hipMemcpyAsync(d + o_po, pose2d, 24u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (t0) RPL_HIP(h, hipMemcpyAsync(d + o_t0, t0, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (pivot) RPL_HIP(h, hipMemcpyAsync(d + o_pv, pivot, 8u, hipMemcpyHostToDevice, h->stream));
-    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);
-    const int32_t rc = match_impl(
-        h, reinterpret_cast<const rplgpu_node_t *>(d + o_nodes), n_stride,
-        reinterpret_cast<const uint32_t *>(d + o_len), n_scans, n_scans, p,
-        motion ? reinterpret_cast<const float *>(d + o_mo) : nullptr,
-        pose2d ? reinterpret_cast<const float *>(d + o_po) : nullptr,
-        t0 ? reinterpret_cast<const float *>(d + o_t0) : nullptr,
-        pivot ? reinterpret_cast<const float *>(d + o_pv) : nullptr, m, reinterpret_cast<const int8_t *>(d), stride, 0,
-        reinterpret_cast<uint32_t *>(d + o_sc), volume, d_small, d_small + 8);
-    if (rc) return rc;
-    if (scores_out)
-      RPL_HIP(h, hipMemcpyAsync(scores_out, d + o_sc, 4u * volume, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(small, d_small, 36, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;
-  std::memcpy(best, small, 32);
-  if (status) *status = small[8];
-  return RPLGPU_OK;
-}
-
-// ---- E14: time steps accumulated into a hit / miss map at matched poses (include/rplgpu_msg.h) ----------------
-
-void rplgpu_default_map_rule(rplgpu_map_rule_t *rule) {
-  if (!rule) return;
-  rule->min_observations = 2;
-  rule->occupied_percent = 10;
-  rule->mode = 0;
-}
-
-int32_t rplgpu_map_rule_check(const rplgpu_map_rule_t *rule) {
-  if (!rule || rule->min_observations == 0 || rule->occupied_percent > 100u || rule->mode > 1u)
-    return RPLGPU_ERR_INVALID_ARG;
-  return RPLGPU_OK;
-}
-
-// d_t0: the per-scan time offsets of E6 for this call (the handle's, or the host door's own), or NULL
-static int32_t map_update_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
-                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
-                               const float *d_motion, const float *d_pose2d, const float *d_t0,
-                               const rplgpu_occ_grid_t *grid, uint32_t *d_counts, uint32_t *d_status) {
-  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
-  if (rc) return rc;
-  if (!p || !grid || !d_counts || group == 0) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_occ_grid_check(grid) != RPLGPU_OK) {
-    h->err = "rplgpu_map_update_dev: invalid rplgpu_occ_grid_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if ((reinterpret_cast<uintptr_t>(d_counts) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
-    h->err = "rplgpu_map_update_dev: d_counts must be 8-byte aligned, d_status 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (B == 0) return RPLGPU_OK;
-  if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
-      (d_pose2d && !device_readable(h, d_pose2d, "d_pose2d")) || !device_readable(h, d_counts, "d_counts") ||
-      (d_status && !device_readable(h, d_status, "d_status")))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (d_t0 && !d_motion) {
-    h->err = "rplgpu_map_update_dev: scan time offsets are set (rplgpu_set_scan_time_offsets_dev) but d_motion is NULL";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
-    h->err = "ror_radius must be in (0, 1e6] m";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  group = std::min(group, B);  // as E8: "all sensors in one group" may be asked for with any group >= B
-  if ((uint64_t)group * std::min(n_stride, rpl::kMaxN) > (1ull << 24)) {
-    h->err = "rplgpu_map_update_dev: group x n_stride above 2^24 samples";
-    return RPLGPU_ERR_CAPACITY;
-  }
-  const uint32_t G = (B + group - 1u) / group;
-  RPL_HIP(h, hipSetDevice(h->device));
-  rpl::KParams kp = to_kparams(*p);
-  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
-  rpl::Tables T = tables_of(h);
-  T.scan_t0 = d_t0;
-  const rpl::OccK k = occ_kernel_args(*grid);
-  const uint32_t *mask = nullptr;
-  if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E9, E11 and E13 apply
-    RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
-                                    kMaskStride));
-    mask = h->d_rormask;
-  }
-  if (d_status) RPL_HIP(h, hipMemsetAsync(d_status, 0, (size_t)G * 4u, h->stream));
-  RPL_HIP(h, rpl::launch_map_walk(h->stream, d_nodes, n_stride, d_n_per_scan, B, group, kp, T, mask, kMaskStride,
-                                  d_motion, d_pose2d, k, d_counts, d_status));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_map_update_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
-                              const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
-                              const float *d_motion, const float *d_pose2d, const rplgpu_occ_grid_t *grid,
-                              uint32_t *d_counts, uint32_t *d_status) {
-  if (!h) return RPLGPU_ERR_INVALID_ARG;
-  return map_update_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, h->scan_t0, grid,
-                         d_counts, d_status);
-}
-
-int32_t rplgpu_map_grid_dev(rplgpu_handle_t h, const uint32_t *d_counts, uint32_t width, uint32_t height,
-                            const rplgpu_map_rule_t *rule, const int8_t *d_prev, int8_t *d_grid,
-                            uint64_t grid_stride, uint32_t *d_cells) {
-  if (!h || !d_counts || !rule || !d_grid) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_map_rule_check(rule) != RPLGPU_OK) {
-    h->err = "rplgpu_map_grid_dev: invalid rplgpu_map_rule_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 || height > RPLGPU_MAX_OCC_DIM) {
-    h->err = "rplgpu_map_grid_dev: width and height must be 1 .. RPLGPU_MAX_OCC_DIM";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (grid_stride < (uint64_t)width * height || (grid_stride & 3u) || (reinterpret_cast<uintptr_t>(d_grid) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_counts) & 7u) || (reinterpret_cast<uintptr_t>(d_cells) & 3u)) {
-    h->err = "rplgpu_map_grid_dev: grid_stride must be >= width * height and a multiple of 4, d_grid / d_cells 4-byte and d_counts 8-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (d_prev == d_grid) {
-    h->err = "rplgpu_map_grid_dev: d_prev must not be d_grid";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!device_readable(h, d_counts, "d_counts") || (d_prev && !device_readable(h, d_prev, "d_prev")) ||
-      !device_readable(h, d_grid, "d_grid") || (d_cells && !device_readable(h, d_cells, "d_cells")))
-    return RPLGPU_ERR_INVALID_ARG;
-  RPL_HIP(h, hipSetDevice(h->device));
-  if (d_cells) RPL_HIP(h, hipMemsetAsync(d_cells, 0, 16u, h->stream));
-  RPL_HIP(h, rpl::launch_map_grid(h->stream, d_counts, width, height, rule->min_observations,
-                                  rule->occupied_percent, rule->mode, d_prev, d_grid, d_cells));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_apply_match_dev(rplgpu_handle_t h, const uint32_t *d_best, const rplgpu_scan_match_t *m,
-                               const float *d_pivot, const float *d_pose2d_in, uint32_t B, uint32_t group,
-                               uint32_t flags, float *d_pose2d_out, float *d_pivot_out) {
-  if (!h || !d_best || !m || !d_pose2d_out || group == 0 || flags > 1u) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_scan_match_check(m) != RPLGPU_OK) {
-    h->err = "rplgpu_apply_match_dev: invalid rplgpu_scan_match_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if ((reinterpret_cast<uintptr_t>(d_best) & 3u) || (reinterpret_cast<uintptr_t>(d_pivot) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_pose2d_in) & 3u) || (reinterpret_cast<uintptr_t>(d_pose2d_out) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_pivot_out) & 3u)) {
-    h->err = "rplgpu_apply_match_dev: every pointer must be 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (d_pivot_out && d_pivot_out == d_pivot) {
-    h->err = "rplgpu_apply_match_dev: d_pivot_out must not be d_pivot (every scan of a group reads the pivot)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (B > h->max_b) {
-    h->err = "batch larger than max_batch given to rplgpu_create";
-    return RPLGPU_ERR_CAPACITY;
-  }
-  if (B == 0) return RPLGPU_OK;
-  if (!device_readable(h, d_best, "d_best") || (d_pivot && !device_readable(h, d_pivot, "d_pivot")) ||
-      (d_pose2d_in && !device_readable(h, d_pose2d_in, "d_pose2d_in")) ||
-      !device_readable(h, d_pose2d_out, "d_pose2d_out") ||
-      (d_pivot_out && !device_readable(h, d_pivot_out, "d_pivot_out")))
-    return RPLGPU_ERR_INVALID_ARG;
-  group = std::min(group, B);
-  const rpl::MatchK k{m->origin_x, m->origin_y, m->resolution, m->width, m->height,
-                      m->shift_x, m->shift_y, m->rot_steps};
-  rpl::MatchRot rot;  // by value, as k_match_score takes it
-  std::memset(&rot, 0, sizeof(rot));
-  if (rplgpu_scan_match_rotations(m, rot.cs) != RPLGPU_OK) return RPLGPU_ERR_INVALID_ARG;
-  RPL_HIP(h, hipSetDevice(h->device));
-  RPL_HIP(h, rpl::launch_apply_match(h->stream, d_best, k, rot, d_pivot, d_pose2d_in, B, group, flags, d_pose2d_out,
-                                     d_pivot_out));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_map_update(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
-                          const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
-                          const float *motion, const float *pose2d, const float *t0, const rplgpu_occ_grid_t *grid,
-                          uint32_t *counts, uint32_t *status) {
-  if (!h || !nodes || !n_per_scan || !p || !grid || !counts || n_scans == 0 || n_stride == 0)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_occ_grid_check(grid) != RPLGPU_OK) {
-    h->err = "rplgpu_map_update: invalid rplgpu_occ_grid_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
-  RPL_HIP(h, hipSetDevice(h->device));
-  const size_t cells_n = (size_t)grid->width * grid->height;
-  const size_t nb = (size_t)n_scans * n_stride * 8u;
-  // one allocation per call (a convenience door, not the hot path): counts | nodes | lengths | motion | pose |
-  // t0 | status, every part 16-byte aligned
-  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  const size_t o_nodes = up16(8u * cells_n), o_len = o_nodes + up16(nb), o_mo = o_len + up16(4u * n_scans),
-               o_po = o_mo + up16(motion ? 16u * n_scans : 0), o_t0 = o_po + up16(pose2d ? 24u * n_scans : 0),
-               o_small = o_t0 + up16(t0 ? 4u * n_scans : 0), total = o_small + 16u;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_map_update: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t small = 0;
-  auto run = [&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(d, counts, 8u * cells_n, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_nodes, nodes, nb, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_len, n_per_scan, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (motion) RPL_HIP(h, hipMemcpyAsync(d + o_mo, motion, 16u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (pose2d) RPL_HIP(h, hipMemcpyAsync(d + o_po, pose2d, 24u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (t0) RPL_HIP(h, hipMemcpyAsync(d + o_t0, t0, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
-    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);
-    const int32_t rc = map_update_impl(
-        h, reinterpret_cast<const rplgpu_node_t *>(d + o_nodes), n_stride,
-        reinterpret_cast<const uint32_t *>(d + o_len), n_scans, n_scans, p,
-        motion ? reinterpret_cast<const float *>(d + o_mo) : nullptr,
-        pose2d ? reinterpret_cast<const float *>(d + o_po) : nullptr,
-        t0 ? reinterpret_cast<const float *>(d + o_t0) : nullptr, grid, reinterpret_cast<uint32_t *>(d), d_small);
-    if (rc) return rc;
-    RPL_HIP(h, hipMemcpyAsync(counts, d, 8u * cells_n, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(&small, d_small, 4, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;
-  if (status) *status = small;
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_map_grid(rplgpu_handle_t h, const uint32_t *counts, uint32_t width, uint32_t height,
-                        const rplgpu_map_rule_t *rule, const int8_t *prev, int8_t *grid_out, uint32_t cells[4]) {
-  if (!h || !counts || !rule || !grid_out) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_map_rule_check(rule) != RPLGPU_OK) {
-    h->err = "rplgpu_map_grid: invalid rplgpu_map_rule_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 || height > RPLGPU_MAX_OCC_DIM) {
-    h->err = "rplgpu_map_grid: width and height must be 1 .. RPLGPU_MAX_OCC_DIM";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  RPL_HIP(h, hipSetDevice(h->device));
-  const size_t cells_n = (size_t)width * height, stride = (cells_n + 3u) & ~(size_t)3u;
-  // one allocation per call: counts | grid | prev | cells, every part 16-byte aligned
-  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  const size_t o_grid = up16(8u * cells_n), o_prev = o_grid + up16(stride), o_small = o_prev + up16(prev ? stride : 0),
-               total = o_small + 16u;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_map_grid: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t small[4] = {0, 0, 0, 0};
-  auto run = [&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(d, counts, 8u * cells_n, hipMemcpyHostToDevice, h->stream));
-    if (prev) RPL_HIP(h, hipMemcpyAsync(d + o_prev, prev, cells_n, hipMemcpyHostToDevice, h->stream));
-    const int32_t rc = rplgpu_map_grid_dev(h, reinterpret_cast<const uint32_t *>(d), width, height, rule,
-                                           prev ? reinterpret_cast<const int8_t *>(d + o_prev) : nullptr,
-                                           reinterpret_cast<int8_t *>(d + o_grid), stride,
-                                           reinterpret_cast<uint32_t *>(d + o_small));
-    if (rc) return rc;
-    RPL_HIP(h, hipMemcpyAsync(grid_out, d + o_grid, cells_n, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(small, d + o_small, 16, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;
-  if (cells) std::memcpy(cells, small, 16);
-  return RPLGPU_OK;
-}
-
-// ---- E15: a list of arbitrary poses weighed against a likelihood field (include/rplgpu_msg.h) ------------------
-
-void rplgpu_default_pose_score(rplgpu_pose_score_t *s) {
-  if (!s) return;
-  s->origin_x = -25.6f;
-  s->origin_y = -25.6f;
-  s->resolution = 0.05f;
-  s->width = 1024;
-  s->height = 1024;
-}
-
-int32_t rplgpu_pose_score_check(const rplgpu_pose_score_t *s) {
-  if (!s) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(s->origin_x) || !std::isfinite(s->origin_y) || !std::isfinite(s->resolution))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (!(s->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
-  if (s->width == 0 || s->width > RPLGPU_MAX_OCC_DIM || s->height == 0 || s->height > RPLGPU_MAX_OCC_DIM)
-    return RPLGPU_ERR_INVALID_ARG;
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_pose_list(const double *xyt, uint32_t n, float *poses_out) {
-  if (n > RPLGPU_MAX_POSES || (n && (!xyt || !poses_out))) return RPLGPU_ERR_INVALID_ARG;
-  for (uint32_t q = 0; q < n; ++q) {
-    const double th = xyt[3u * q + 2u];
-    poses_out[4u * q] = th == 0.0 ? 1.0f : (float)std::cos(th);
-    poses_out[4u * q + 1u] = th == 0.0 ? 0.0f : (float)std::sin(th);  // (+0 for theta = -0 too)
-    poses_out[4u * q + 2u] = (float)xyt[3u * q];
-    poses_out[4u * q + 3u] = (float)xyt[3u * q + 1u];
-  }
-  return RPLGPU_OK;
-}
-
-// d_t0: the per-scan time offsets of E6 for this call (the handle's, or the host door's own), or NULL
-static int32_t pose_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
-                         const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
-                         const float *d_motion, const float *d_pose2d, const float *d_t0,
-                         const rplgpu_pose_score_t *s, const float *d_poses, uint32_t P, uint64_t pose_stride,
-                         uint32_t poses_per_group, const int8_t *d_field, uint64_t field_stride,
-                         uint32_t field_per_group, uint32_t *d_weights, uint64_t weight_stride, uint32_t *d_result,
-                         uint32_t *d_status) {
-  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
-  if (rc) return rc;
-  if (!p || !s || !d_poses || !d_field || !d_weights || !d_result || group == 0) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_pose_score_check(s) != RPLGPU_OK) {
-    h->err = "rplgpu_score_poses_dev: invalid rplgpu_pose_score_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_score_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (pose_stride < 4ull * P || (pose_stride & 3u) || (reinterpret_cast<uintptr_t>(d_poses) & 15u)) {
-    h->err = "rplgpu_score_poses_dev: pose_stride must be >= 4 P floats and a multiple of 4, d_poses 16-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (field_stride < (uint64_t)s->width * s->height || (field_stride & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_field) & 3u)) {
-    h->err = "rplgpu_score_poses_dev: field_stride must be >= width * height and a multiple of 4, d_field 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (weight_stride < P || (reinterpret_cast<uintptr_t>(d_weights) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_result) & 3u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
-    h->err = "rplgpu_score_poses_dev: weight_stride must be >= P, d_weights / d_result / d_status 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (B == 0) return RPLGPU_OK;
-  if ((d_motion && !device_readable(h, d_motion, "d_motion")) ||
-      (d_pose2d && !device_readable(h, d_pose2d, "d_pose2d")) || !device_readable(h, d_poses, "d_poses") ||
-      !device_readable(h, d_field, "d_field") || !device_readable(h, d_weights, "d_weights") ||
-      !device_readable(h, d_result, "d_result") || (d_status && !device_readable(h, d_status, "d_status")))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (d_t0 && !d_motion) {
-    h->err = "rplgpu_score_poses_dev: scan time offsets are set (rplgpu_set_scan_time_offsets_dev) but d_motion is NULL";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (p->ror_enable && !(p->ror_radius > 0.0f && p->ror_radius <= 1.0e6f)) {
-    h->err = "ror_radius must be in (0, 1e6] m";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  group = std::min(group, B);  // as E8: "all sensors in one time step" may be asked for with any group >= B
-  if ((uint64_t)group * n_stride > (1ull << 24)) {  // 127 x points stays below 2^32: no weight wraps
-    h->err = "rplgpu_score_poses_dev: group x n_stride above 2^24 samples";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const uint32_t G = (B + group - 1u) / group;
-  if ((uint64_t)G * ((P + 255u) / 256u) > 0x7FFFFFFFull) {  // (launch_pose_prepare's grid; before anything is queued)
-    h->err = "rplgpu_score_poses_dev: groups x P too large for one call";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const rpl::PoseK k{s->origin_x, s->origin_y, s->resolution, s->width, s->height};
-  RPL_HIP(h, hipSetDevice(h->device));
-  rpl::KParams kp = to_kparams(*p);
-  kp.fast_d4000 = use_fast_d4000(h) ? 1 : 0;
-  rpl::Tables T = tables_of(h);
-  T.scan_t0 = d_t0;
-  const uint32_t *mask = nullptr;
-  if (p->ror_enable) {  // E1 AND E5 keep bits, the mask E9, E11 and E13 apply
-    RPL_HIP(h, rpl::launch_ror_mask(h->stream, d_nodes, n_stride, d_n_per_scan, B, kp, T, h->d_rormask,
-                                    kMaskStride));
-    mask = h->d_rormask;
-  }
-  if (d_status) RPL_HIP(h, hipMemsetAsync(d_status, 0, (size_t)G * 4u, h->stream));
-  RPL_HIP(h, rpl::launch_pose_prepare(h->stream, d_weights, weight_stride, G, P, d_result));
-  RPL_HIP(h, rpl::launch_pose_score(h->stream, d_nodes, n_stride, d_n_per_scan, B, group, kp, T, mask, kMaskStride,
-                                    d_motion, d_pose2d, k, d_poses, P, pose_stride, poses_per_group, d_field,
-                                    field_stride, field_per_group, d_weights, weight_stride, d_result, d_status));
-  RPL_HIP(h, rpl::launch_pose_best(h->stream, d_weights, weight_stride, G, P, d_result));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_score_poses_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
-                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
-                               const float *d_motion, const float *d_pose2d, const rplgpu_pose_score_t *s,
-                               const float *d_poses, uint32_t P, uint64_t pose_stride, uint32_t poses_per_group,
-                               const int8_t *d_field, uint64_t field_stride, uint32_t field_per_group,
-                               uint32_t *d_weights, uint64_t weight_stride, uint32_t *d_result,
-                               uint32_t *d_status) {
-  if (!h) return RPLGPU_ERR_INVALID_ARG;
-  return pose_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, h->scan_t0, s, d_poses, P,
-                   pose_stride, poses_per_group, d_field, field_stride, field_per_group, d_weights, weight_stride,
-                   d_result, d_status);
-}
-
-int32_t rplgpu_score_poses(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
-                           const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
-                           const float *motion, const float *pose2d, const float *t0,
-                           const rplgpu_pose_score_t *s, const float *poses, uint32_t P, const int8_t *field,
-                           uint32_t *weights_out, uint32_t result[8], uint32_t *status) {
-  if (!h || !nodes || !n_per_scan || !p || !s || !poses || !field || !result || n_scans == 0 || n_stride == 0)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_pose_score_check(s) != RPLGPU_OK) {
-    h->err = "rplgpu_score_poses: invalid rplgpu_pose_score_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_score_poses: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
-  RPL_HIP(h, hipSetDevice(h->device));
-  const size_t cells_n = (size_t)s->width * s->height, stride = (cells_n + 3u) & ~(size_t)3u;
-  const size_t nb = (size_t)n_scans * n_stride * 8u;
-  // one allocation per call (a convenience door, not the hot path): field | poses | weights | nodes | lengths |
-  // motion | pose | t0 | result + status, every part 16-byte aligned
-  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  const size_t o_ps = up16(stride), o_wt = o_ps + up16(16u * (size_t)P), o_nodes = o_wt + up16(4u * (size_t)P),
-               o_len = o_nodes + up16(nb), o_mo = o_len + up16(4u * n_scans),
-               o_po = o_mo + up16(motion ? 16u * n_scans : 0), o_t0 = o_po + up16(pose2d ? 24u * n_scans : 0),
-               o_small = o_t0 + up16(t0 ? 4u * n_scans : 0), total = o_small + 48u;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_score_poses: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t small[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  auto run = [&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(d, field, cells_n, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_ps, poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_nodes, nodes, nb, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_len, n_per_scan, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (motion) RPL_HIP(h, hipMemcpyAsync(d + o_mo, motion, 16u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (pose2d) RPL_HIP(h, hipMemcpyAsync(d + o_po, pose2d, 24u * n_scans, hipMemcpyHostToDevice, h->stream));
-    if (t0) RPL_HIP(h, hipMemcpyAsync(d + o_t0, t0, 4u * n_scans, hipMemcpyHostToDevice, h->stream));
-    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);
-    const int32_t rc = pose_impl(
-        h, reinterpret_cast<const rplgpu_node_t *>(d + o_nodes), n_stride,
-        reinterpret_cast<const uint32_t *>(d + o_len), n_scans, n_scans, p,
-        motion ? reinterpret_cast<const float *>(d + o_mo) : nullptr,
-        pose2d ? reinterpret_cast<const float *>(d + o_po) : nullptr,
-        t0 ? reinterpret_cast<const float *>(d + o_t0) : nullptr, s, reinterpret_cast<const float *>(d + o_ps), P,
-        4ull * P, 0, reinterpret_cast<const int8_t *>(d), stride, 0, reinterpret_cast<uint32_t *>(d + o_wt), P,
-        d_small, d_small + 8);
-    if (rc) return rc;
-    if (weights_out)
-      RPL_HIP(h, hipMemcpyAsync(weights_out, d + o_wt, 4u * (size_t)P, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(small, d_small, 36, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;
-  std::memcpy(result, small, 32);
-  if (status) *status = small[8];
-  return RPLGPU_OK;
-}
-
-// ---- E16: a weighted pose list resampled and moved (include/rplgpu_msg.h) ---------------------------------------
-
-uint64_t rplgpu_resample_scratch_words(uint32_t G, uint32_t P) { return rpl::resample_scratch_words(G, P); }
-
-// the byte ranges [a, a + na) and [b, b + nb) share a byte
-static bool ranges_overlap(const void *a, uint64_t na, const void *b, uint64_t nb) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + nb && pb < pa + na;
-}
-
-// E16's move: the delta composed on the right, float32, each product rounded, then the difference or sum (this
-// unit is built with -ffp-contract=off); a NaN that the move makes is stored as 0x7FC00000
-static void resample_move(const float *pose, const float *d, float *out) {
-  const float c = pose[0], s = pose[1], x = pose[2], y = pose[3];
-  const float dc = d[0], ds = d[1], dx = d[2], dy = d[3];
-  const float p0 = c * dc, p1 = s * ds, p2 = s * dc, p3 = c * ds, p4 = c * dx, p5 = s * dy, p6 = s * dx, p7 = c * dy;
-  float v[4] = {p0 - p1, p2 + p3, (p4 - p5) + x, (p6 + p7) + y};
-  const uint32_t qnan = 0x7FC00000u;
-  for (int k = 0; k < 4; ++k) {
-    if (v[k] != v[k]) std::memcpy(&v[k], &qnan, 4);
-  }
-  std::memcpy(out, v, 16);
-}
-
-int32_t rplgpu_resample_host(const uint32_t *weights, uint32_t P, uint32_t M, uint32_t u, const float *poses,
-                             const float *delta, uint32_t n_delta, float *poses_out, uint32_t *ancestors_out,
-                             uint32_t result[8]) {
-  if (!weights || !poses || !poses_out || !result || P == 0 || P > RPLGPU_MAX_POSES || M == 0 ||
-      M > RPLGPU_MAX_POSES || (delta && n_delta != 1u && n_delta != M) ||
-      ranges_overlap(poses, 16ull * P, poses_out, 16ull * M))
-    return RPLGPU_ERR_INVALID_ARG;
-  uint64_t S = 0, sq = 0;
-  uint32_t carry = 0, nz = 0;
-  for (uint32_t i = 0; i < P; ++i) {
-    const uint64_t w = weights[i], w2 = w * w;
-    S += w;
-    sq += w2;
-    carry += sq < w2 ? 1u : 0u;
-    nz += w != 0 ? 1u : 0u;
-  }
-  const uint64_t q = S / M, rho = S % M;
-  const uint64_t r = (uint64_t)u * (S >> 32) + (((uint64_t)u * (S & 0xffffffffull)) >> 32);
-  uint32_t i = 0, distinct = 0, last = 0xFFFFFFFFu;
-  uint64_t C = weights[0];  // C[i], inclusive
-  for (uint32_t j = 0; j < M; ++j) {
-    uint32_t a;
-    if (S == 0) {
-      a = j % P;
-    } else {
-      const uint64_t t = (uint64_t)j * q + ((uint64_t)j * rho + r) / M;  // < S: the walk ends inside the list
-      while (C <= t) C += weights[++i];
-      a = i;
-    }
-    if (a != last) ++distinct;  // (a is non-decreasing)
-    last = a;
-    if (delta)
-      resample_move(poses + 4u * (size_t)a, delta + (n_delta == 1u ? 0u : 4u * (size_t)j), poses_out + 4u * (size_t)j);
-    else
-      std::memcpy(poses_out + 4u * (size_t)j, poses + 4u * (size_t)a, 16);
-    if (ancestors_out) ancestors_out[j] = a;
-  }
-  result[0] = (uint32_t)S;
-  result[1] = (uint32_t)(S >> 32);
-  result[2] = (uint32_t)sq;
-  result[3] = (uint32_t)(sq >> 32);
-  result[4] = carry;
-  result[5] = nz;
-  result[6] = S == 0 ? std::min(M, P) : distinct;
-  result[7] = S == 0 ? 1u : 0u;
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_resample_poses_dev(rplgpu_handle_t h, const uint32_t *d_weights, uint64_t weight_stride,
-                                  const float *d_poses, uint64_t pose_stride, uint32_t poses_per_group, uint32_t G,
-                                  uint32_t P, uint32_t M, const uint32_t *d_u, const float *d_delta,
-                                  uint32_t n_delta, uint64_t delta_stride, uint32_t delta_per_group,
-                                  float *d_poses_out, uint64_t out_stride, uint32_t *d_ancestors,
-                                  uint64_t anc_stride, uint32_t *d_result, uint32_t *d_scratch) {
-  if (!h) return RPLGPU_ERR_INVALID_ARG;
-  auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_resample_poses_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (P == 0 || P > RPLGPU_MAX_POSES || M == 0 || M > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_resample_poses_dev: P and M must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!d_weights || !d_poses || !d_poses_out || !d_result || !d_scratch || off(d_weights, 3) || off(d_poses, 15) ||
-      off(d_poses_out, 15) || off(d_result, 3) || off(d_scratch, 7) || off(d_u, 3) || off(d_delta, 15) ||
-      off(d_ancestors, 3)) {
-    h->err = "rplgpu_resample_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for pose "
-             "lists and deltas, 8 for d_scratch, 4 otherwise)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (weight_stride < P || pose_stride < 4ull * P || (pose_stride & 3u) || out_stride < 4ull * M ||
-      (out_stride & 3u) || (d_ancestors && anc_stride < M)) {
-    h->err = "rplgpu_resample_poses_dev: weight_stride >= P, pose_stride >= 4 P, out_stride >= 4 M (both multiples "
-             "of 4) and anc_stride >= M are required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (d_delta && ((n_delta != 1u && n_delta != M) || delta_stride < 4ull * n_delta || (delta_stride & 3u))) {
-    h->err = "rplgpu_resample_poses_dev: n_delta must be 1 or M, delta_stride >= 4 n_delta and a multiple of 4";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const uint64_t in_bytes = 4ull * ((poses_per_group ? (uint64_t)(G - 1u) * pose_stride : 0ull) + 4ull * P);
-  const uint64_t out_bytes = 4ull * ((uint64_t)(G - 1u) * out_stride + 4ull * M);
-  if (ranges_overlap(d_poses, in_bytes, d_poses_out, out_bytes)) {
-    h->err = "rplgpu_resample_poses_dev: d_poses_out overlaps d_poses";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!device_readable(h, d_weights, "d_weights") || !device_readable(h, d_poses, "d_poses") ||
-      !device_readable(h, d_poses_out, "d_poses_out") || !device_readable(h, d_result, "d_result") ||
-      !device_readable(h, d_scratch, "d_scratch") || (d_u && !device_readable(h, d_u, "d_u")) ||
-      (d_delta && !device_readable(h, d_delta, "d_delta")) ||
-      (d_ancestors && !device_readable(h, d_ancestors, "d_ancestors")))
-    return RPLGPU_ERR_INVALID_ARG;
-  RPL_HIP(h, hipSetDevice(h->device));
-  RPL_HIP(h, rpl::launch_resample(h->stream, d_weights, weight_stride, d_poses, pose_stride, poses_per_group, G, P,
-                                  M, d_u, d_delta, d_delta ? n_delta : 1u, delta_stride, delta_per_group,
-                                  d_poses_out, out_stride, d_ancestors, anc_stride, d_result, d_scratch));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_resample_poses(rplgpu_handle_t h, const uint32_t *weights, uint32_t P, uint32_t M, uint32_t u,
-                              const float *poses, const float *delta, uint32_t n_delta, float *poses_out,
-                              uint32_t *ancestors_out, uint32_t result[8]) {
-  if (!h || !weights || !poses || !poses_out || !result) return RPLGPU_ERR_INVALID_ARG;
-  if (P == 0 || P > RPLGPU_MAX_POSES || M == 0 || M > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_resample_poses: P and M must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (delta && n_delta != 1u && n_delta != M) {
-    h->err = "rplgpu_resample_poses: n_delta must be 1 or M";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (ranges_overlap(poses, 16ull * P, poses_out, 16ull * M)) {
-    h->err = "rplgpu_resample_poses: poses_out overlaps poses";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  RPL_HIP(h, hipSetDevice(h->device));
-  // one allocation per call (a convenience door, not the hot path): poses | out | deltas | weights | ancestors |
-  // scratch | u + result, every part 16-byte aligned
-  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  const size_t nd = delta ? n_delta : 0u;
-  const size_t o_out = up16(16u * (size_t)P), o_dl = o_out + up16(16u * (size_t)M), o_wt = o_dl + up16(16u * nd),
-               o_anc = o_wt + up16(4u * (size_t)P), o_scr = o_anc + up16(4u * (size_t)M),
-               o_small = o_scr + up16(4u * (size_t)rplgpu_resample_scratch_words(1, P)), total = o_small + 48u;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_resample_poses: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  auto run = [&]() -> int32_t {
-    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);  // u, then the result at + 4 words
-    RPL_HIP(h, hipMemcpyAsync(d, poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_wt, weights, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d_small, &u, 4, hipMemcpyHostToDevice, h->stream));
-    if (delta) RPL_HIP(h, hipMemcpyAsync(d + o_dl, delta, 16u * nd, hipMemcpyHostToDevice, h->stream));
-    const int32_t rc = rplgpu_resample_poses_dev(
-        h, reinterpret_cast<const uint32_t *>(d + o_wt), P, reinterpret_cast<const float *>(d), 4ull * P, 0, 1, P, M,
-        d_small, delta ? reinterpret_cast<const float *>(d + o_dl) : nullptr, n_delta, 4ull * nd, 0,
-        reinterpret_cast<float *>(d + o_out), 4ull * M, reinterpret_cast<uint32_t *>(d + o_anc), M, d_small + 4,
-        reinterpret_cast<uint32_t *>(d + o_scr));
-    if (rc) return rc;
-    RPL_HIP(h, hipMemcpyAsync(poses_out, d + o_out, 16u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
-    if (ancestors_out)
-      RPL_HIP(h, hipMemcpyAsync(ancestors_out, d + o_anc, 4u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(small, d_small + 4, 32, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;
-  std::memcpy(result, small, 32);
-  return RPLGPU_OK;
-}
-
-// ---- E17: a weighted pose list reduced to a pose estimate (include/rplgpu_msg.h) -------------------------------------
-
-void rplgpu_default_pose_estimate(rplgpu_pose_estimate_t *s) {
-  if (!s) return;
-  s->xy_scale = 1024.0f;
-  s->gate_r2 = 512ull * 512ull;
-  s->gate_dot = 15ll << 36;
-}
-
-int32_t rplgpu_pose_estimate_check(const rplgpu_pose_estimate_t *s) {
-  if (!s) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(s->xy_scale) || !(s->xy_scale > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
-  return RPLGPU_OK;
-}
-
-uint64_t rplgpu_estimate_scratch_words(uint32_t G, uint32_t P) { return rpl::estimate_scratch_words(G, P); }
-
-// E17's quantisation of one pose entry: one float32 product (this unit is built with -ffp-contract=off), the range
-// test, one round-to-nearest-even (the default rounding mode)
-static bool estimate_quantise(const float *pose, float xy_scale, int32_t q[4]) {
-  const float t[4] = {pose[2] * xy_scale, pose[3] * xy_scale, pose[0] * 1048576.0f, pose[1] * 1048576.0f};
-  for (int k = 0; k < 4; ++k) {
-    if (!(std::fabs(t[k]) < 8388608.0f)) return false;
-  }
-  for (int k = 0; k < 4; ++k) q[k] = (int32_t)std::rint(t[k]);  // X, Y, C, S
-  return true;
-}
-
-int32_t rplgpu_estimate_host(const float *poses, uint32_t P, const uint32_t *weights,
-                             const rplgpu_pose_estimate_t *s, uint32_t center, uint32_t result[72]) {
-  if (!poses || !result || rplgpu_pose_estimate_check(s) != RPLGPU_OK || P == 0 || P > RPLGPU_MAX_POSES)
-    return RPLGPU_ERR_INVALID_ARG;
-  const uint32_t qc = std::min(center, P - 1u);
-  int32_t c[4] = {0, 0, 0, 0};
-  const bool c_in = estimate_quantise(poses + 4u * (size_t)qc, s->xy_scale, c);
-  __int128 sum[2][8] = {};
-  uint32_t count[2][2] = {{0, 0}, {0, 0}};
-  for (uint32_t i = 0; i < P; ++i) {
-    int32_t q[4];
-    if (!estimate_quantise(poses + 4u * (size_t)i, s->xy_scale, q)) continue;
-    const int64_t X = q[0], Y = q[1], C = q[2], S = q[3];
-    const int64_t dX = X - c[0], dY = Y - c[1];
-    const bool gate = c_in && (uint64_t)(dX * dX + dY * dY) <= s->gate_r2 && C * c[2] + S * c[3] >= s->gate_dot;
-    const __int128 w = weights ? weights[i] : 1u;
-    const __int128 term[8] = {w, w * X, w * Y, w * C, w * S, w * (X * X), w * (X * Y), w * (Y * Y)};
-    for (int k = 0; k < (gate ? 2 : 1); ++k) {
-      for (int m = 0; m < 8; ++m) sum[k][m] += term[m];
-      count[k][0] += 1u;
-      count[k][1] += w != 0 ? 1u : 0u;
-    }
-  }
-  result[0] = (c_in ? 0u : 1u) | (count[0][0] != P ? 2u : 0u) | (sum[0][0] == 0 ? 4u : 0u) | (sum[1][0] == 0 ? 8u : 0u);
-  result[1] = qc;
-  result[2] = count[0][0];
-  result[3] = count[0][1];
-  result[4] = count[1][0];
-  result[5] = count[1][1];
-  result[6] = result[7] = 0u;
-  for (int k = 0; k < 2; ++k) {
-    for (int m = 0; m < 8; ++m) {
-      const unsigned __int128 v = (unsigned __int128)sum[k][m];
-      for (int j = 0; j < 4; ++j) result[8 + 32 * k + 4 * m + j] = (uint32_t)(v >> (32 * j));
-    }
-  }
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_estimate_pose(const uint32_t result[72], float xy_scale, uint32_t set, double out[8]) {
-  if (!result || !out || set > 1u || !std::isfinite(xy_scale) || !(xy_scale > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
-  double v[8];  // each sum rounded to fp64 once
-  for (int m = 0; m < 8; ++m) {
-    unsigned __int128 u = 0;
-    for (int j = 3; j >= 0; --j) u = (u << 32) | result[8 + 32 * set + 4 * m + j];
-    v[m] = (double)(__int128)u;
-  }
-  if (v[0] == 0.0) return RPLGPU_ERR_INVALID_ARG;  // (W < 2^52 is exact, so this is W == 0)
-  const double scale = (double)xy_scale, scale2 = scale * scale;  // (24 x 24 bits: exact)
-  const double mx = v[1] / v[0] / scale, my = v[2] / v[0] / scale;
-  out[0] = mx;
-  out[1] = my;
-  out[2] = std::atan2(v[4], v[3]);
-  out[3] = v[5] / v[0] / scale2 - mx * mx;
-  out[4] = v[6] / v[0] / scale2 - mx * my;
-  out[5] = v[7] / v[0] / scale2 - my * my;
-  out[6] = std::hypot(v[3], v[4]) / (v[0] * 1048576.0);
-  out[7] = v[0];
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_estimate_poses_dev(rplgpu_handle_t h, const float *d_poses, uint64_t pose_stride,
-                                  uint32_t poses_per_group, const uint32_t *d_weights, uint64_t weight_stride,
-                                  uint32_t G, uint32_t P, const rplgpu_pose_estimate_t *s, const uint32_t *d_center,
-                                  uint64_t center_stride, uint32_t *d_result, uint32_t *d_scratch) {
-  if (!h) return RPLGPU_ERR_INVALID_ARG;
-  auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
-  if (rplgpu_pose_estimate_check(s) != RPLGPU_OK) {
-    h->err = "rplgpu_estimate_poses_dev: invalid rplgpu_pose_estimate_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_estimate_poses_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_estimate_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!d_poses || !d_result || !d_scratch || off(d_poses, 15) || off(d_result, 3) || off(d_scratch, 7) ||
-      off(d_weights, 3) || off(d_center, 3)) {
-    h->err = "rplgpu_estimate_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for the "
-             "pose list, 8 for d_scratch, 4 otherwise)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (pose_stride < 4ull * P || (pose_stride & 3u) || (d_weights && weight_stride < P)) {
-    h->err = "rplgpu_estimate_poses_dev: pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (d_center && center_stride == 0 && G > 1u) {
-    h->err = "rplgpu_estimate_poses_dev: center_stride must not be 0 with more than one group";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!device_readable(h, d_poses, "d_poses") || !device_readable(h, d_result, "d_result") ||
-      !device_readable(h, d_scratch, "d_scratch") || (d_weights && !device_readable(h, d_weights, "d_weights")) ||
-      (d_center && !device_readable(h, d_center, "d_center")))
-    return RPLGPU_ERR_INVALID_ARG;
-  RPL_HIP(h, hipSetDevice(h->device));
-  RPL_HIP(h, rpl::launch_estimate(h->stream, d_poses, pose_stride, poses_per_group, d_weights, weight_stride, G, P,
-                                  s->xy_scale, s->gate_r2, s->gate_dot, d_center, center_stride, d_result,
-                                  d_scratch));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_estimate_poses(rplgpu_handle_t h, const float *poses, uint32_t P, const uint32_t *weights,
-                              const rplgpu_pose_estimate_t *s, uint32_t center, uint32_t result[72]) {
-  if (!h || !poses || !result) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_pose_estimate_check(s) != RPLGPU_OK) {
-    h->err = "rplgpu_estimate_poses: invalid rplgpu_pose_estimate_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_estimate_poses: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  RPL_HIP(h, hipSetDevice(h->device));
-  // one allocation per call (a convenience door, not the hot path): poses | weights | scratch | centre + result,
-  // every part 16-byte aligned
-  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  const size_t o_wt = up16(16u * (size_t)P), o_scr = o_wt + up16(4u * (size_t)P),
-               o_small = o_scr + up16(4u * (size_t)rplgpu_estimate_scratch_words(1, P)),
-               total = o_small + 16u + 4u * RPLGPU_ESTIMATE_WORDS;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_estimate_poses: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t words[RPLGPU_ESTIMATE_WORDS];
-  auto run = [&]() -> int32_t {
-    uint32_t *d_small = reinterpret_cast<uint32_t *>(d + o_small);  // the centre word, then the result at + 4 words
-    RPL_HIP(h, hipMemcpyAsync(d, poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
-    if (weights) RPL_HIP(h, hipMemcpyAsync(d + o_wt, weights, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d_small, &center, 4, hipMemcpyHostToDevice, h->stream));
-    const int32_t rc = rplgpu_estimate_poses_dev(
-        h, reinterpret_cast<const float *>(d), 4ull * P, 0, weights ? reinterpret_cast<const uint32_t *>(d + o_wt) : nullptr,
-        P, 1, P, s, d_small, 0, d_small + 4, reinterpret_cast<uint32_t *>(d + o_scr));
-    if (rc) return rc;
-    RPL_HIP(h, hipMemcpyAsync(words, d_small + 4, sizeof(words), hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;
-  std::memcpy(result, words, sizeof(words));
-  return RPLGPU_OK;
-}
-
-// ---- E18: a pose list's motion noise drawn on the device (include/rplgpu_msg.h) --------------------------------------
-
-void rplgpu_default_motion_noise(rplgpu_motion_noise_t *s) {
-  if (!s) return;
-  s->seed = 0;
-  s->step = 0;
-  s->first = 0;
-  s->reserved = 0;
-}
-
-static void philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
-  uint32_t c[4] = {ctr[0], ctr[1], ctr[2], ctr[3]}, k0 = key[0], k1 = key[1];
-  for (int r = 0; r < 10; ++r) {
-    if (r) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const uint64_t p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = (uint32_t)p1;
-    c[2] = n2;
-    c[3] = (uint32_t)p0;
-  }
-  std::memcpy(out, c, 16);
-}
-
-int32_t rplgpu_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
-  if (!ctr || !key || !out) return RPLGPU_ERR_INVALID_ARG;
-  philox4x32(ctr, key, out);
-  return RPLGPU_OK;
-}
-
-// E18's integer normal of one draw: the eight 16-bit halves of the block, minus their mean
-static int32_t motion_draw(const rplgpu_motion_noise_t *s, uint32_t g, uint32_t j, uint32_t i) {
-  const uint32_t ctr[4] = {s->first + j, (g << 2) | i, (uint32_t)s->step, (uint32_t)(s->step >> 32)};
-  const uint32_t key[2] = {(uint32_t)s->seed, (uint32_t)(s->seed >> 32)};
-  uint32_t w[4];
-  philox4x32(ctr, key, w);
-  int32_t z = -262140;
-  for (int k = 0; k < 4; ++k) z += (int32_t)(w[k] & 0xFFFFu) + (int32_t)(w[k] >> 16);
-  return z;
-}
-
-// E18's noise rotation by 2 atan(Z k) and the composition r o n: float32, every operation rounded once (this unit is
-// built with -ffp-contract=off)
-static void motion_noise(int32_t z, float k, float n[2]) {
-  const float t = (float)z * k, q = t * t, den = 1.0f + q;
-  n[0] = (1.0f - q) / den;
-  n[1] = (t + t) / den;
-}
-static void motion_compose(const float r[2], const float n[2], float a[2]) {
-  const float p0 = r[0] * n[0], p1 = r[1] * n[1], p2 = r[1] * n[0], p3 = r[0] * n[1];
-  a[0] = p0 - p1;
-  a[1] = p2 + p3;
-}
-
-int32_t rplgpu_sample_motion_host(const float odom[8], uint32_t group, uint32_t M, const rplgpu_motion_noise_t *s,
-                                  float *delta_out, uint32_t result[8]) {
-  if (!odom || !s || !delta_out || !result || group > 65534u || M == 0 || M > RPLGPU_MAX_POSES)
-    return RPLGPU_ERR_INVALID_ARG;
-  const float r1[2] = {odom[0], odom[1]}, r2[2] = {odom[3], odom[4]};
-  const float trans = odom[2], k1 = odom[5], kt = odom[6], k2 = odom[7];
-  uint32_t nans = 0, zmax = 0;
-  int64_t sum = 0;
-  uint64_t squares = 0;
-  for (uint32_t j = 0; j < M; ++j) {
-    int32_t z[3];
-    for (uint32_t i = 0; i < 3; ++i) {
-      z[i] = motion_draw(s, group, j, i);
-      zmax = std::max(zmax, (uint32_t)std::abs(z[i]));
-      sum += z[i];
-      squares += (uint64_t)((int64_t)z[i] * z[i]);
-    }
-    float n1[2], n2[2], a[2], b[2], d[2];
-    motion_noise(z[0], k1, n1);
-    motion_noise(z[2], k2, n2);
-    motion_compose(r1, n1, a);
-    motion_compose(r2, n2, b);
-    motion_compose(a, b, d);
-    const float noise = (float)z[1] * kt;
-    const float tr = trans + noise;
-    float v[4] = {d[0], d[1], a[0] * tr, a[1] * tr};
-    const uint32_t qnan = 0x7FC00000u;
-    bool any = false;
-    for (int k = 0; k < 4; ++k) {
-      if (v[k] != v[k]) {
-        std::memcpy(&v[k], &qnan, 4);
-        any = true;
-      }
-    }
-    nans += any ? 1u : 0u;
-    std::memcpy(delta_out + 4u * (size_t)j, v, 16);
-  }
-  result[0] = nans;
-  result[1] = zmax;
-  result[2] = (uint32_t)(uint64_t)sum;
-  result[3] = (uint32_t)((uint64_t)sum >> 32);
-  result[4] = (uint32_t)squares;
-  result[5] = (uint32_t)(squares >> 32);
-  result[6] = 0u;
-  result[7] = nans ? 1u : 0u;
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_motion_odometry(double dx, double dy, double dtheta, const double alpha[4], float out[8]) {
-  if (!alpha || !out) return RPLGPU_ERR_INVALID_ARG;
-  const double pi = 3.14159265358979323846;
-  const double trans = std::sqrt(dx * dx + dy * dy);
-  const double rot1 = trans >= 0.01 ? std::atan2(dy, dx) : 0.0;
-  const double d = dtheta - rot1;
-  const double rot2 = std::atan2(std::sin(d), std::cos(d));
-  const double f1 = std::min(std::fabs(rot1), pi - std::fabs(rot1));
-  const double f2 = std::min(std::fabs(rot2), pi - std::fabs(rot2));
-  const double v1 = alpha[0] * f1 * f1 + alpha[1] * trans * trans;
-  const double vt = alpha[2] * trans * trans + alpha[3] * (f1 * f1 + f2 * f2);
-  const double v2 = alpha[0] * f2 * f2 + alpha[1] * trans * trans;
-  const double sigma_z = std::sqrt(2863311530.0);
-  out[0] = (float)std::cos(rot1);
-  out[1] = (float)std::sin(rot1);
-  out[2] = (float)trans;
-  out[3] = (float)std::cos(rot2);
-  out[4] = (float)std::sin(rot2);
-  out[5] = (float)(std::sqrt(v1) / (2.0 * sigma_z));
-  out[6] = (float)(std::sqrt(vt) / sigma_z);
-  out[7] = (float)(std::sqrt(v2) / (2.0 * sigma_z));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_sample_motion_dev(rplgpu_handle_t h, const float *d_odom, uint32_t odom_per_group, uint32_t G,
-                                 uint32_t M, const rplgpu_motion_noise_t *s, float *d_delta, uint64_t delta_stride,
-                                 uint32_t *d_result) {
-  if (!h) return RPLGPU_ERR_INVALID_ARG;
-  auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
-  if (!s) {
-    h->err = "rplgpu_sample_motion_dev: the rplgpu_motion_noise_t is missing";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_sample_motion_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (M == 0 || M > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_sample_motion_dev: M must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!d_odom || !d_delta || !d_result || off(d_odom, 15) || off(d_delta, 15) || off(d_result, 3)) {
-    h->err = "rplgpu_sample_motion_dev: a required pointer is missing or a pointer is misaligned (16 bytes for d_odom "
-             "and d_delta, 4 for d_result)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (delta_stride < 4ull * M || (delta_stride & 3u)) {
-    h->err = "rplgpu_sample_motion_dev: delta_stride >= 4 M and a multiple of 4 is required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!device_readable(h, d_odom, "d_odom") || !device_readable(h, d_delta, "d_delta") ||
-      !device_readable(h, d_result, "d_result"))
-    return RPLGPU_ERR_INVALID_ARG;
-  RPL_HIP(h, hipSetDevice(h->device));
-  RPL_HIP(h, rpl::launch_motion(h->stream, d_odom, odom_per_group, G, M, s->seed, s->step, s->first, d_delta,
-                                delta_stride, d_result));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_sample_motion(rplgpu_handle_t h, const float odom[8], uint32_t M, const rplgpu_motion_noise_t *s,
-                             float *delta_out, uint32_t result[8]) {
-  if (!h || !odom || !s || !delta_out || !result) return RPLGPU_ERR_INVALID_ARG;
-  if (M == 0 || M > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_sample_motion: M must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  RPL_HIP(h, hipSetDevice(h->device));
-  // one allocation per call (a convenience door, not the hot path): odometry | result | deltas, 16-byte aligned
-  const size_t o_res = 32u, o_dl = 64u, total = o_dl + 16u * (size_t)M;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_sample_motion: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  auto run = [&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(d, odom, 32, hipMemcpyHostToDevice, h->stream));
-    const int32_t rc = rplgpu_sample_motion_dev(h, reinterpret_cast<const float *>(d), 0, 1, M, s,
-                                                reinterpret_cast<float *>(d + o_dl), 4ull * M,
-                                                reinterpret_cast<uint32_t *>(d + o_res));
-    if (rc) return rc;
-    RPL_HIP(h, hipMemcpyAsync(delta_out, d + o_dl, 16u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(small, d + o_res, 32, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;
-  std::memcpy(result, small, 32);
-  return RPLGPU_OK;
-}
-
-// ---- E19: a pose list seeded over a grid's free cells on the device (include/rplgpu_msg.h) ---------------------------
-
-void rplgpu_default_pose_seed(rplgpu_pose_seed_t *s) {
-  if (!s) return;
-  s->origin_x = -25.6f;
-  s->origin_y = -25.6f;
-  s->resolution = 0.05f;
-  s->width = 1024;
-  s->height = 1024;
-  s->free_lo = 0;
-  s->free_hi = 0;
-  s->flags = 0;
-}
-
-int32_t rplgpu_pose_seed_check(const rplgpu_pose_seed_t *s) {
-  if (!s) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(s->origin_x) || !std::isfinite(s->origin_y) || !std::isfinite(s->resolution))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (!(s->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
-  if (s->width == 0 || s->width > RPLGPU_MAX_OCC_DIM || s->height == 0 || s->height > RPLGPU_MAX_OCC_DIM)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (s->free_lo < -128 || s->free_lo > 127 || s->free_hi < -128 || s->free_hi > 127 || s->free_lo > s->free_hi)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (s->flags > 1u) return RPLGPU_ERR_INVALID_ARG;
-  return RPLGPU_OK;
-}
-
-uint64_t rplgpu_seed_scratch_words(uint32_t G_f, uint32_t width, uint32_t height) {
-  return rpl::seed_scratch_words(G_f, width, height);
-}
-
-int32_t rplgpu_seed_headings(uint32_t H, float *cs) {
-  if (!cs || H == 0 || H > 65536u) return RPLGPU_ERR_INVALID_ARG;
-  const double two_pi = 6.283185307179586476925286766559;
-  for (uint32_t k = 0; k < H; ++k) {
-    const double a = two_pi * (double)k / (double)H;
-    cs[2u * k] = k == 0 ? 1.0f : (float)std::cos(a);
-    cs[2u * k + 1u] = k == 0 ? 0.0f : (float)std::sin(a);
-  }
-  return RPLGPU_OK;
-}
-
-// the E11 cell rule on the host: float32, every operation rounded once (this unit is built with -ffp-contract=off)
-static bool seed_cell(float x, float y, const rplgpu_pose_seed_t *s, int32_t *cx, int32_t *cy) {
-  const float du = x - s->origin_x, dv = y - s->origin_y;
-  const float u = du / s->resolution, v = dv / s->resolution;
-  const float fu = std::floor(u), fv = std::floor(v);
-  if (!(std::fabs(fu) < 1048576.0f && std::fabs(fv) < 1048576.0f)) return false;
-  *cx = (int32_t)fu;
-  *cy = (int32_t)fv;
-  return true;
-}
-
-int32_t rplgpu_seed_poses_host(const rplgpu_pose_seed_t *s, const int8_t *grid, const float *headings, uint32_t H,
-                               uint32_t group, uint32_t M, const rplgpu_motion_noise_t *noise, float *poses_out,
-                               uint32_t *cells_out, uint32_t result[8]) {
-  if (rplgpu_pose_seed_check(s) != RPLGPU_OK || !grid || !headings || !noise || !poses_out || !result ||
-      group > 65534u || H == 0 || H > 65536u || M == 0 || M > RPLGPU_MAX_POSES)
-    return RPLGPU_ERR_INVALID_ARG;
-  const uint32_t cells = s->width * s->height;
-  auto is_free = [&](uint32_t i) { return grid[i] >= s->free_lo && grid[i] <= s->free_hi; };
-  uint32_t F = 0;
-  for (uint32_t i = 0; i < cells; ++i) F += is_free(i) ? 1u : 0u;
-  const bool none = F == 0;
-  if (none) F = cells;
-  // the draws first, then ONE walk over the cells in index order hands every draw its cell: the outputs sorted by r
-  std::vector<uint32_t> words(4u * (size_t)M), order(M), cell(M);
-  const uint32_t key[2] = {(uint32_t)noise->seed, (uint32_t)(noise->seed >> 32)};
-  for (uint32_t j = 0; j < M; ++j) {
-    const uint32_t ctr[4] = {noise->first + j, (group << 2) | 3u, (uint32_t)noise->step,
-                             (uint32_t)(noise->step >> 32)};
-    philox4x32(ctr, key, &words[4u * (size_t)j]);
-    order[j] = j;
-  }
-  auto rank = [&](uint32_t j) { return (uint32_t)(((uint64_t)words[4u * (size_t)j] * F) >> 32); };
-  if (none) {
-    for (uint32_t j = 0; j < M; ++j) cell[j] = rank(j);
-  } else {
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rank(a) < rank(b); });
-    uint32_t seen = 0, q = 0;  // free cells in front of cell i; outputs served
-    for (uint32_t i = 0; i < cells && q < M; ++i) {
-      if (!is_free(i)) continue;
-      while (q < M && rank(order[q]) == seen) cell[order[q++]] = i;
-      ++seen;
-    }
-  }
-  uint32_t off = 0, lo = 0xFFFFFFFFu, hi = 0;
-  const bool centres = (s->flags & 1u) != 0;
-  for (uint32_t j = 0; j < M; ++j) {
-    const uint32_t *p = &words[4u * (size_t)j];
-    const uint32_t k = (uint32_t)(((uint64_t)p[1] * H) >> 32);
-    const uint32_t cy = cell[j] / s->width, cx = cell[j] - cy * s->width;
-    const float fx = centres ? 0.5f : ((float)(p[2] >> 24) + 0.5f) * (1.0f / 256.0f);
-    const float fy = centres ? 0.5f : ((float)(p[3] >> 24) + 0.5f) * (1.0f / 256.0f);
-    const float ux = (float)cx + fx, uy = (float)cy + fy;
-    const float mx = ux * s->resolution, my = uy * s->resolution;
-    const float x = s->origin_x + mx, y = s->origin_y + my;
-    int32_t bx = 0, by = 0;
-    if (!(seed_cell(x, y, s, &bx, &by) && bx == (int32_t)cx && by == (int32_t)cy)) ++off;
-    lo = std::min(lo, cell[j]);
-    hi = std::max(hi, cell[j]);
-    std::memcpy(poses_out + 4u * (size_t)j, headings + 2u * (size_t)k, 8);  // bit for bit
-    poses_out[4u * (size_t)j + 2u] = x;
-    poses_out[4u * (size_t)j + 3u] = y;
-    if (cells_out) cells_out[j] = cell[j];
-  }
-  result[0] = F;
-  result[1] = off;
-  result[2] = lo;
-  result[3] = hi;
-  result[4] = result[5] = result[6] = 0u;
-  result[7] = (none ? 1u : 0u) | (off ? 2u : 0u);
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_seed_poses_dev(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, const int8_t *d_grid,
-                              uint64_t grid_stride, uint32_t grid_per_group, const float *d_headings, uint32_t H,
-                              uint32_t G, uint32_t M, const rplgpu_motion_noise_t *noise, float *d_poses_out,
-                              uint64_t out_stride, uint32_t *d_cells_out, uint64_t cell_stride, uint32_t *d_result,
-                              uint32_t *d_scratch) {
-  if (!h) return RPLGPU_ERR_INVALID_ARG;
-  auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
-  if (rplgpu_pose_seed_check(s) != RPLGPU_OK) {
-    h->err = "rplgpu_seed_poses_dev: the rplgpu_pose_seed_t is missing or rplgpu_pose_seed_check refuses it";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!noise) {
-    h->err = "rplgpu_seed_poses_dev: the rplgpu_motion_noise_t is missing";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_seed_poses_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (M == 0 || M > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_seed_poses_dev: M must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (H == 0 || H > 65536u) {
-    h->err = "rplgpu_seed_poses_dev: H must be in 1 .. 65536";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!d_grid || !d_headings || !d_poses_out || !d_result || !d_scratch || off(d_grid, 3) || off(d_headings, 7) ||
-      off(d_poses_out, 15) || off(d_cells_out, 3) || off(d_result, 3) || off(d_scratch, 7)) {
-    h->err = "rplgpu_seed_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for "
-             "d_poses_out, 8 for d_headings and d_scratch, 4 for d_grid, d_cells_out and d_result)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const uint64_t cells = (uint64_t)s->width * s->height;
-  if (grid_stride < cells || (grid_stride & 3u)) {
-    h->err = "rplgpu_seed_poses_dev: grid_stride >= width * height and a multiple of 4 is required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (out_stride < 4ull * M || (out_stride & 3u)) {
-    h->err = "rplgpu_seed_poses_dev: out_stride >= 4 M and a multiple of 4 is required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (d_cells_out && cell_stride < M) {
-    h->err = "rplgpu_seed_poses_dev: cell_stride >= M is required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!device_readable(h, d_grid, "d_grid") || !device_readable(h, d_headings, "d_headings") ||
-      !device_readable(h, d_poses_out, "d_poses_out") || !device_readable(h, d_result, "d_result") ||
-      !device_readable(h, d_scratch, "d_scratch") || (d_cells_out && !device_readable(h, d_cells_out, "d_cells_out")))
-    return RPLGPU_ERR_INVALID_ARG;
-  rpl::SeedK k;
-  k.origin_x = s->origin_x;
-  k.origin_y = s->origin_y;
-  k.resolution = s->resolution;
-  k.width = s->width;
-  k.height = s->height;
-  k.free_lo = s->free_lo;
-  k.free_hi = s->free_hi;
-  k.centres = s->flags & 1u;
-  RPL_HIP(h, hipSetDevice(h->device));
-  RPL_HIP(h, rpl::launch_seed(h->stream, k, d_grid, grid_stride, grid_per_group, d_headings, H, G, M, noise->seed,
-                              noise->step, noise->first, d_poses_out, out_stride, d_cells_out, cell_stride, d_result,
-                              d_scratch));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_seed_poses(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, const int8_t *grid, const float *headings,
-                          uint32_t H, uint32_t M, const rplgpu_motion_noise_t *noise, float *poses_out,
-                          uint32_t *cells_out, uint32_t result[8]) {
-  if (!h || !grid || !headings || !noise || !poses_out || !result) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_pose_seed_check(s) != RPLGPU_OK) {
-    h->err = "rplgpu_seed_poses: the rplgpu_pose_seed_t is missing or rplgpu_pose_seed_check refuses it";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (M == 0 || M > RPLGPU_MAX_POSES || H == 0 || H > 65536u) {
-    h->err = "rplgpu_seed_poses: M must be in 1 .. RPLGPU_MAX_POSES and H in 1 .. 65536";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  RPL_HIP(h, hipSetDevice(h->device));
-  // one allocation per call (a convenience door, not the hot path): result | headings | grid | scratch | cells | poses
-  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  const size_t cells = (size_t)s->width * s->height, gstride = (cells + 3u) & ~(size_t)3u;
-  const size_t o_head = 32u, o_grid = o_head + up16(8u * (size_t)H), o_scr = o_grid + up16(gstride),
-               o_cells = o_scr + up16(4u * (size_t)rplgpu_seed_scratch_words(1, s->width, s->height)),
-               o_poses = o_cells + up16(4u * (size_t)M), total = o_poses + 16u * (size_t)M;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_seed_poses: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  auto run = [&]() -> int32_t {
-    RPL_HIP(h, hipMemsetAsync(d + o_grid, 0, up16(gstride), h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_head, headings, 8u * (size_t)H, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_grid, grid, cells, hipMemcpyHostToDevice, h->stream));
-    const int32_t rc = rplgpu_seed_poses_dev(h, s, reinterpret_cast<const int8_t *>(d + o_grid), gstride, 0,
-                                             reinterpret_cast<const float *>(d + o_head), H, 1, M, noise,
-                                             reinterpret_cast<float *>(d + o_poses), 4ull * M,
-                                             reinterpret_cast<uint32_t *>(d + o_cells), M,
-                                             reinterpret_cast<uint32_t *>(d), reinterpret_cast<uint32_t *>(d + o_scr));
-    if (rc) return rc;
-    RPL_HIP(h, hipMemcpyAsync(poses_out, d + o_poses, 16u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
-    if (cells_out) RPL_HIP(h, hipMemcpyAsync(cells_out, d + o_cells, 4u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(small, d, 32, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;
-  std::memcpy(result, small, 32);
-  return RPLGPU_OK;
-}
-
-// ---- E20: a pose list's occupied bins counted on the device (include/rplgpu_msg.h) -----------------------------------
-
-void rplgpu_default_pose_bins(rplgpu_pose_bins_t *s) {
-  if (!s) return;
-  s->origin_x = -25.6f;
-  s->origin_y = -25.6f;
-  s->inv_size = 2.0f;
-  s->nx = 103;
-  s->ny = 103;
-  s->flags = 0;
-}
-
-int32_t rplgpu_pose_bins_check(const rplgpu_pose_bins_t *s, uint32_t T) {
-  if (!s) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(s->origin_x) || !std::isfinite(s->origin_y) || !std::isfinite(s->inv_size))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (!(s->inv_size > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
-  if (s->nx == 0 || s->nx > 65536u || s->ny == 0 || s->ny > 65536u) return RPLGPU_ERR_INVALID_ARG;
-  if (T == 0 || T > RPLGPU_MAX_HEADING_BINS) return RPLGPU_ERR_INVALID_ARG;
-  if ((uint64_t)s->nx * s->ny * T > (uint64_t)RPLGPU_MAX_POSE_BINS) return RPLGPU_ERR_INVALID_ARG;
-  if (s->flags > 1u) return RPLGPU_ERR_INVALID_ARG;
-  return RPLGPU_OK;
-}
-
-uint64_t rplgpu_bin_map_words(uint32_t nx, uint32_t ny, uint32_t T) {
-  rplgpu_pose_bins_t s;
-  rplgpu_default_pose_bins(&s);
-  s.nx = nx;
-  s.ny = ny;
-  if (rplgpu_pose_bins_check(&s, T) != RPLGPU_OK) return 0;
-  const uint64_t words = ((uint64_t)nx * ny * T + 31u) >> 5;
-  return (words + 1u) & ~(uint64_t)1u;
-}
-
-// E20's quantisation of (c, s), E17's rule: one float32 product, the range test, one round-to-nearest-even; false for
-// an entry that is out of range or quantises to (0, 0)
-static bool bins_quantise(const float *cs, int32_t q[2]) {
-  const float tc = cs[0] * 1048576.0f, ts = cs[1] * 1048576.0f;
-  q[0] = q[1] = 0;
-  if (!(std::fabs(tc) < 8388608.0f && std::fabs(ts) < 8388608.0f)) return false;
-  q[0] = (int32_t)std::rint(tc);
-  q[1] = (int32_t)std::rint(ts);
-  return q[0] != 0 || q[1] != 0;
-}
-static uint32_t bins_half(const int32_t a[2]) { return (a[1] > 0 || (a[1] == 0 && a[0] > 0)) ? 0u : 1u; }
-// a <= b in the angular order, both in range and not (0, 0)
-static bool bins_le(const int32_t a[2], const int32_t b[2]) {
-  const uint32_t ha = bins_half(a), hb = bins_half(b);
-  if (ha != hb) return ha < hb;
-  return (int64_t)a[0] * b[1] - (int64_t)a[1] * b[0] >= 0;
-}
-
-int32_t rplgpu_heading_edges_check(const float *cs, uint32_t T) {
-  if (!cs || T == 0 || T > RPLGPU_MAX_HEADING_BINS) return RPLGPU_ERR_INVALID_ARG;
-  int32_t prev[2], cur[2];
-  if (!bins_quantise(cs, prev) || prev[0] != 1048576 || prev[1] != 0) return RPLGPU_ERR_INVALID_ARG;
-  for (uint32_t k = 1; k < T; ++k) {
-    if (!bins_quantise(cs + 2u * (size_t)k, cur)) return RPLGPU_ERR_INVALID_ARG;
-    if (bins_le(cur, prev)) return RPLGPU_ERR_INVALID_ARG;  // not strictly behind its predecessor
-    prev[0] = cur[0];
-    prev[1] = cur[1];
-  }
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_bin_poses_host(const rplgpu_pose_bins_t *s, const float *poses, uint32_t P, const uint32_t *weights,
-                              const float *edges, uint32_t T, uint32_t *map, uint32_t *bins_out,
-                              uint32_t result[8]) {
-  if (rplgpu_pose_bins_check(s, T) != RPLGPU_OK || !poses || !edges || !map || !result || P == 0 ||
-      P > RPLGPU_MAX_POSES)
-    return RPLGPU_ERR_INVALID_ARG;
-  const uint32_t nb = s->nx * s->ny * T, words = (nb + 31u) >> 5;
-  const bool keep = (s->flags & 1u) != 0;
-  if (!keep) std::memset(map, 0, 4u * (size_t)words);
-  std::vector<int32_t> eq(2u * (size_t)T);
-  std::vector<unsigned char> e_ok(T);
-  for (uint32_t k = 0; k < T; ++k) e_ok[k] = bins_quantise(edges + 2u * (size_t)k, &eq[2u * (size_t)k]) ? 1 : 0;
-  uint32_t K = 0, counted = 0, outside = 0, skipped = 0, lo_bin = 0xFFFFFFFFu, hi_bin = 0;
-  for (uint32_t i = 0; i < P; ++i) {
-    const float *p = poses + 4u * (size_t)i;
-    uint32_t b = 0xFFFFFFFFu;
-    if (weights && weights[i] == 0u) {
-      ++skipped;  // (whether or not it is in range)
-    } else {
-      const float dx = p[2] - s->origin_x, dy = p[3] - s->origin_y;
-      const float fx = dx * s->inv_size, fy = dy * s->inv_size;  // (-ffp-contract=off: the difference rounded first)
-      const bool x_in = fx >= 0.0f && fx < (float)s->nx;
-      const bool y_in = fy >= 0.0f && fy < (float)s->ny;
-      int32_t h[2];
-      const bool h_in = bins_quantise(p, h);
-      if (x_in && y_in && h_in) {
-        const uint32_t bx = (uint32_t)std::floor(fx), by = (uint32_t)std::floor(fy);
-        uint32_t lo = 0, hi = T;
-        while (hi - lo > 1u) {
-          const uint32_t mid = (lo + hi) >> 1;
-          if (e_ok[mid] && bins_le(&eq[2u * (size_t)mid], h))
-            lo = mid;
-          else
-            hi = mid;
-        }
-        b = (lo * s->ny + by) * s->nx + bx;
-        ++counted;
-        lo_bin = std::min(lo_bin, b);
-        hi_bin = std::max(hi_bin, b);
-        const uint32_t bit = 1u << (b & 31u);
-        if (!(map[b >> 5] & bit)) ++K;  // a bit this call turns from 0 to 1
-        map[b >> 5] |= bit;
-      } else {
-        ++outside;
-      }
-    }
-    if (bins_out) bins_out[i] = b;
-  }
-  result[0] = K;
-  result[1] = counted;
-  result[2] = outside;
-  result[3] = skipped;
-  result[4] = lo_bin;
-  result[5] = hi_bin;
-  result[6] = 0u;
-  result[7] = (counted == 0 ? 1u : 0u) | (outside != 0 ? 2u : 0u) | (keep ? 4u : 0u);
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_bin_poses_dev(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, const float *d_poses,
-                             uint64_t pose_stride, uint32_t poses_per_group, const uint32_t *d_weights,
-                             uint64_t weight_stride, uint32_t G, uint32_t P, const float *d_edges, uint32_t T,
-                             uint32_t *d_map, uint64_t map_stride, uint32_t *d_bins_out, uint64_t bin_stride,
-                             uint32_t *d_result) {
-  if (!h) return RPLGPU_ERR_INVALID_ARG;
-  auto off = [](const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
-  if (rplgpu_pose_bins_check(s, T) != RPLGPU_OK) {
-    h->err = "rplgpu_bin_poses_dev: the rplgpu_pose_bins_t is missing or rplgpu_pose_bins_check refuses it or T";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_bin_poses_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_bin_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!d_poses || !d_edges || !d_map || !d_result || off(d_poses, 15) || off(d_edges, 7) || off(d_map, 7) ||
-      off(d_weights, 3) || off(d_bins_out, 3) || off(d_result, 3)) {
-    h->err = "rplgpu_bin_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for d_poses, "
-             "8 for d_edges and d_map, 4 for d_weights, d_bins_out and d_result)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (pose_stride < 4ull * P || (pose_stride & 3u) || (d_weights && weight_stride < P)) {
-    h->err = "rplgpu_bin_poses_dev: pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const uint64_t words = ((uint64_t)s->nx * s->ny * T + 31u) >> 5;
-  if (map_stride < words || (map_stride & 1u)) {
-    h->err = "rplgpu_bin_poses_dev: map_stride >= ceil(nx * ny * T / 32) and even is required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (d_bins_out && bin_stride < P) {
-    h->err = "rplgpu_bin_poses_dev: bin_stride >= P is required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!device_readable(h, d_poses, "d_poses") || !device_readable(h, d_edges, "d_edges") ||
-      !device_readable(h, d_map, "d_map") || !device_readable(h, d_result, "d_result") ||
-      (d_weights && !device_readable(h, d_weights, "d_weights")) ||
-      (d_bins_out && !device_readable(h, d_bins_out, "d_bins_out")))
-    return RPLGPU_ERR_INVALID_ARG;
-  rpl::BinsK k;
-  k.origin_x = s->origin_x;
-  k.origin_y = s->origin_y;
-  k.inv_size = s->inv_size;
-  k.nx = s->nx;
-  k.ny = s->ny;
-  k.keep = s->flags & 1u;
-  RPL_HIP(h, hipSetDevice(h->device));
-  RPL_HIP(h, rpl::launch_bins(h->stream, k, d_poses, pose_stride, poses_per_group, d_weights, weight_stride, G, P,
-                              d_edges, T, d_map, map_stride, d_bins_out, bin_stride, d_result));
-  return RPLGPU_OK;
-}
-
-int32_t rplgpu_bin_poses(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, const float *poses, uint32_t P,
-                         const uint32_t *weights, const float *edges, uint32_t T, uint32_t *map, uint32_t *bins_out,
-                         uint32_t result[8]) {
-  if (!h || !poses || !edges || !map || !result) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_pose_bins_check(s, T) != RPLGPU_OK) {
-    h->err = "rplgpu_bin_poses: the rplgpu_pose_bins_t is missing or rplgpu_pose_bins_check refuses it or T";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_bin_poses: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  RPL_HIP(h, hipSetDevice(h->device));
-  // one allocation per call (a convenience door, not the hot path): result | edges | map | weights | bins | poses
-  auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  const size_t words = ((size_t)s->nx * s->ny * T + 31u) >> 5, stride = (size_t)rplgpu_bin_map_words(s->nx, s->ny, T);
-  const size_t o_edge = 32u, o_map = o_edge + up16(8u * (size_t)T), o_wt = o_map + up16(4u * stride),
-               o_bins = o_wt + up16(4u * (size_t)P), o_poses = o_bins + up16(4u * (size_t)P),
-               total = o_poses + 16u * (size_t)P;
-  unsigned char *d = nullptr;
-  if (hipMalloc((void **)&d, total) != hipSuccess) {
-    h->err = "rplgpu_bin_poses: device allocation failed";
-    (void)hipGetLastError();
-    return RPLGPU_ERR_HIP;
-  }
-  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  std::vector<uint32_t> map_back(words), bins_back(bins_out ? P : 0u);
-  auto run = [&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(d + o_poses, poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(d + o_edge, edges, 8u * (size_t)T, hipMemcpyHostToDevice, h->stream));
-    if (weights) RPL_HIP(h, hipMemcpyAsync(d + o_wt, weights, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
-    if (s->flags & 1u) RPL_HIP(h, hipMemcpyAsync(d + o_map, map, 4u * words, hipMemcpyHostToDevice, h->stream));
-    const int32_t rc = rplgpu_bin_poses_dev(
-        h, s, reinterpret_cast<const float *>(d + o_poses), 4ull * P, 0,
-        weights ? reinterpret_cast<const uint32_t *>(d + o_wt) : nullptr, P, 1, P,
-        reinterpret_cast<const float *>(d + o_edge), T, reinterpret_cast<uint32_t *>(d + o_map), stride,
-        bins_out ? reinterpret_cast<uint32_t *>(d + o_bins) : nullptr, P, reinterpret_cast<uint32_t *>(d));
-    if (rc) return rc;
-    RPL_HIP(h, hipMemcpyAsync(map_back.data(), d + o_map, 4u * words, hipMemcpyDeviceToHost, h->stream));
-    if (bins_out)
-      RPL_HIP(h, hipMemcpyAsync(bins_back.data(), d + o_bins, 4u * (size_t)P, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(small, d, 32, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipStreamSynchronize(h->stream));
-    return RPLGPU_OK;
-  };
-  const int32_t rc = run();
-  if (rc) (void)hipStreamSynchronize(h->stream);  // nothing queued may outlive the buffer
-  (void)hipFree(d);
-  if (rc) return rc;  // (no output changed)
-  std::memcpy(map, map_back.data(), 4u * words);
-  if (bins_out) std::memcpy(bins_out, bins_back.data(), 4u * (size_t)P);
-  std::memcpy(result, small, 32);
-  return RPLGPU_OK;
-}
-
-uint32_t rplgpu_kld_samples(uint32_t k, double epsilon, double z, uint32_t m_min, uint32_t m_max) {
-  if (k <= 1u) return m_max;
-  const double b = 2.0 / (9.0 * ((double)k - 1.0));
-  const double x = 1.0 - b + std::sqrt(b) * z;
-  const double n = std::ceil(((double)k - 1.0) / (2.0 * epsilon) * x * x * x);
-  if (!(n >= (double)m_min)) return m_min;  // (NaN too)
-  if (n > (double)m_max) return m_max;
-  return (uint32_t)n;
-}
-
 // (`req`: how rplgpu_scan_to_cloud drives this over the handle's own staging; the batch entry point: defaults)
 static int32_t cloud_batch_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                                 const uint32_t *d_n_per_scan, uint32_t B, const rplgpu_params_t *p,
@@ -3949,7 +1479,6 @@ int32_t rplgpu_decode_stream(rplgpu_handle_t h, uint8_t ans_type, uint32_t sampl
   const size_t piece = std::min<size_t>(nf, rpl::decode_max_frames(ans_type));
   // device staging kept in the handle (grown when a longer recording arrives, never shrunk):
   // every sub-buffer starts on a 16-byte boundary (the decoder stores nodes as 8-byte words)
-  auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
   const size_t node_cap = piece * npf, rcap = piece + 1;
   const size_t sz_bytes = up16(nbytes), sz_off = up16(piece * 4), sz_gap = up16(piece);
   const size_t sz_nodes = up16(node_cap * 8), sz_rst = up16(rcap * 4), sz_small = 128;

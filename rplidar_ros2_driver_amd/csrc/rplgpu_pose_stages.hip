@@ -1,0 +1,1156 @@
+// rplgpu_pose_stages.hip — the extern "C" entry points of the stages that work on pose lists
+// (include/rplgpu_msg.h): E15 scoring, E16 resampling, E17 the pose estimate, E18 motion noise, E19 seeding,
+// E20 occupied bins and the KLD sample count.
+//
+// Host side only: argument checks, the launches, the host-buffer doors and the host twins of the integer and
+// float32 rules (this unit is built with -ffp-contract=off -fno-fast-math like every other: the twins' comments rely
+// on it); the kernels are in rpl_pose.hip, rpl_resample.hip, rpl_estimate.hip, rpl_motion.hip, rpl_seed.hip and
+// rpl_bins.hip.  The handle, the helpers of rplgpu_api.hip, the scan-stage prologue and the doors' per-call buffer
+// come from rpl_host.hpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "rplgpu.h"
+#include "rplgpu_msg.h"
+#include "rpl_launch.hpp"
+#include "rpl_host.hpp"
+
+using namespace rpl::host;
+
+extern "C" {
+
+// ---- E15: a list of arbitrary poses weighed against a likelihood field (include/rplgpu_msg.h) ------------------
+
+void rplgpu_default_pose_score(rplgpu_pose_score_t *s) {
+  if (!s) return;
+  s->origin_x = -25.6f;
+  s->origin_y = -25.6f;
+  s->resolution = 0.05f;
+  s->width = 1024;
+  s->height = 1024;
+}
+
+int32_t rplgpu_pose_score_check(const rplgpu_pose_score_t *s) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(s->origin_x) || !std::isfinite(s->origin_y) || !std::isfinite(s->resolution))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!(s->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  if (s->width == 0 || s->width > RPLGPU_MAX_OCC_DIM || s->height == 0 || s->height > RPLGPU_MAX_OCC_DIM)
+    return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_pose_list(const double *xyt, uint32_t n, float *poses_out) {
+  if (n > RPLGPU_MAX_POSES || (n && (!xyt || !poses_out))) return RPLGPU_ERR_INVALID_ARG;
+  for (uint32_t q = 0; q < n; ++q) {
+    const double th = xyt[3u * q + 2u];
+    poses_out[4u * q] = th == 0.0 ? 1.0f : (float)std::cos(th);
+    poses_out[4u * q + 1u] = th == 0.0 ? 0.0f : (float)std::sin(th);  // (+0 for theta = -0 too)
+    poses_out[4u * q + 2u] = (float)xyt[3u * q];
+    poses_out[4u * q + 3u] = (float)xyt[3u * q + 1u];
+  }
+  return RPLGPU_OK;
+}
+
+// d_t0: the per-scan time offsets of E6 for this call (the handle's, or the host door's own), or NULL
+static int32_t pose_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                         const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                         const float *d_motion, const float *d_pose2d, const float *d_t0,
+                         const rplgpu_pose_score_t *s, const float *d_poses, uint32_t P, uint64_t pose_stride,
+                         uint32_t poses_per_group, const int8_t *d_field, uint64_t field_stride,
+                         uint32_t field_per_group, uint32_t *d_weights, uint64_t weight_stride, uint32_t *d_result,
+                         uint32_t *d_status) {
+  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
+  if (rc) return rc;
+  if (!p || !s || !d_poses || !d_field || !d_weights || !d_result || group == 0) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_score_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_score_poses_dev: invalid rplgpu_pose_score_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_score_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (pose_stride < 4ull * P || (pose_stride & 3u) || (reinterpret_cast<uintptr_t>(d_poses) & 15u)) {
+    h->err = "rplgpu_score_poses_dev: pose_stride must be >= 4 P floats and a multiple of 4, d_poses 16-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (field_stride < (uint64_t)s->width * s->height || (field_stride & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_field) & 3u)) {
+    h->err = "rplgpu_score_poses_dev: field_stride must be >= width * height and a multiple of 4, d_field 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (weight_stride < P || (reinterpret_cast<uintptr_t>(d_weights) & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_result) & 3u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
+    h->err = "rplgpu_score_poses_dev: weight_stride must be >= P, d_weights / d_result / d_status 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (B == 0) return RPLGPU_OK;
+  if (!device_readable(h, {{d_motion, "d_motion", false}, {d_pose2d, "d_pose2d", false}, {d_poses, "d_poses", true},
+                           {d_field, "d_field", true}, {d_weights, "d_weights", true}, {d_result, "d_result", true},
+                           {d_status, "d_status", false}}))
+    return RPLGPU_ERR_INVALID_ARG;
+  ScanPrologue pro;
+  if ((rc = pro.admit(h, "rplgpu_score_poses_dev", p, d_motion, d_t0, B, group))) return rc;
+  if ((uint64_t)pro.group * n_stride > (1ull << 24)) {  // 127 x points stays below 2^32: no weight wraps
+    h->err = "rplgpu_score_poses_dev: group x n_stride above 2^24 samples";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if ((uint64_t)pro.G * ((P + 255u) / 256u) > 0x7FFFFFFFull) {  // (launch_pose_prepare's grid; before anything is queued)
+    h->err = "rplgpu_score_poses_dev: groups x P too large for one call";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const rpl::PoseK k{s->origin_x, s->origin_y, s->resolution, s->width, s->height};
+  if ((rc = pro.begin(h, d_nodes, n_stride, d_n_per_scan, B, p, d_t0, d_status))) return rc;
+  RPL_HIP(h, rpl::launch_pose_prepare(h->stream, d_weights, weight_stride, pro.G, P, d_result));
+  RPL_HIP(h, rpl::launch_pose_score(h->stream, d_nodes, n_stride, d_n_per_scan, B, pro.group, pro.kp, pro.T, pro.mask,
+                                    kMaskStride, d_motion, d_pose2d, k, d_poses, P, pose_stride, poses_per_group,
+                                    d_field, field_stride, field_per_group, d_weights, weight_stride, d_result,
+                                    d_status));
+  RPL_HIP(h, rpl::launch_pose_best(h->stream, d_weights, weight_stride, pro.G, P, d_result));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_score_poses_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                               const float *d_motion, const float *d_pose2d, const rplgpu_pose_score_t *s,
+                               const float *d_poses, uint32_t P, uint64_t pose_stride, uint32_t poses_per_group,
+                               const int8_t *d_field, uint64_t field_stride, uint32_t field_per_group,
+                               uint32_t *d_weights, uint64_t weight_stride, uint32_t *d_result,
+                               uint32_t *d_status) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  return pose_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, h->scan_t0, s, d_poses, P,
+                   pose_stride, poses_per_group, d_field, field_stride, field_per_group, d_weights, weight_stride,
+                   d_result, d_status);
+}
+
+int32_t rplgpu_score_poses(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                           const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                           const float *motion, const float *pose2d, const float *t0,
+                           const rplgpu_pose_score_t *s, const float *poses, uint32_t P, const int8_t *field,
+                           uint32_t *weights_out, uint32_t result[8], uint32_t *status) {
+  if (!h || !nodes || !n_per_scan || !p || !s || !poses || !field || !result || n_scans == 0 || n_stride == 0)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_score_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_score_poses: invalid rplgpu_pose_score_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_score_poses: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
+  RPL_HIP(h, hipSetDevice(h->device));
+  const size_t cells_n = (size_t)s->width * s->height, stride = (cells_n + 3u) & ~(size_t)3u;
+  // field | poses | weights | the scans | result + status
+  DoorBuffer buf(h, "rplgpu_score_poses");
+  const size_t o_field = buf.part(stride), o_ps = buf.part(16u * (size_t)P), o_wt = buf.part(4u * (size_t)P);
+  DoorScans scans(buf, nodes, n_stride, n_per_scan, n_scans, motion, pose2d, t0);
+  const size_t o_small = buf.part(48);
+  uint32_t small[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int32_t rc = buf.run([&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_field), field, cells_n, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_ps), poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    if (int32_t urc = scans.upload(h, buf)) return urc;
+    uint32_t *d_small = buf.at<uint32_t>(o_small);
+    const int32_t irc = pose_impl(h, scans.d_nodes, n_stride, scans.d_n_per_scan, n_scans, n_scans, p, scans.d_motion,
+                                  scans.d_pose2d, scans.d_t0, s, buf.at<const float>(o_ps), P, 4ull * P, 0,
+                                  buf.at<const int8_t>(o_field), stride, 0, buf.at<uint32_t>(o_wt), P, d_small,
+                                  d_small + 8);
+    if (irc) return irc;
+    if (weights_out)
+      RPL_HIP(h, hipMemcpyAsync(weights_out, buf.at(o_wt), 4u * (size_t)P, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d_small, 36, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  });
+  if (rc) return rc;
+  std::memcpy(result, small, 32);
+  if (status) *status = small[8];
+  return RPLGPU_OK;
+}
+
+// ---- E16: a weighted pose list resampled and moved (include/rplgpu_msg.h) ---------------------------------------
+
+uint64_t rplgpu_resample_scratch_words(uint32_t G, uint32_t P) { return rpl::resample_scratch_words(G, P); }
+
+// the byte ranges [a, a + na) and [b, b + nb) share a byte
+static bool ranges_overlap(const void *a, uint64_t na, const void *b, uint64_t nb) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+
+// E16's move: the delta composed on the right, float32, each product rounded, then the difference or sum (this
+// unit is built with -ffp-contract=off); a NaN that the move makes is stored as 0x7FC00000
+static void resample_move(const float *pose, const float *d, float *out) {
+  const float c = pose[0], s = pose[1], x = pose[2], y = pose[3];
+  const float dc = d[0], ds = d[1], dx = d[2], dy = d[3];
+  const float p0 = c * dc, p1 = s * ds, p2 = s * dc, p3 = c * ds, p4 = c * dx, p5 = s * dy, p6 = s * dx, p7 = c * dy;
+  float v[4] = {p0 - p1, p2 + p3, (p4 - p5) + x, (p6 + p7) + y};
+  const uint32_t qnan = 0x7FC00000u;
+  for (int k = 0; k < 4; ++k) {
+    if (v[k] != v[k]) std::memcpy(&v[k], &qnan, 4);
+  }
+  std::memcpy(out, v, 16);
+}
+
+int32_t rplgpu_resample_host(const uint32_t *weights, uint32_t P, uint32_t M, uint32_t u, const float *poses,
+                             const float *delta, uint32_t n_delta, float *poses_out, uint32_t *ancestors_out,
+                             uint32_t result[8]) {
+  if (!weights || !poses || !poses_out || !result || P == 0 || P > RPLGPU_MAX_POSES || M == 0 ||
+      M > RPLGPU_MAX_POSES || (delta && n_delta != 1u && n_delta != M) ||
+      ranges_overlap(poses, 16ull * P, poses_out, 16ull * M))
+    return RPLGPU_ERR_INVALID_ARG;
+  uint64_t S = 0, sq = 0;
+  uint32_t carry = 0, nz = 0;
+  for (uint32_t i = 0; i < P; ++i) {
+    const uint64_t w = weights[i], w2 = w * w;
+    S += w;
+    sq += w2;
+    carry += sq < w2 ? 1u : 0u;
+    nz += w != 0 ? 1u : 0u;
+  }
+  const uint64_t q = S / M, rho = S % M;
+  const uint64_t r = (uint64_t)u * (S >> 32) + (((uint64_t)u * (S & 0xffffffffull)) >> 32);
+  uint32_t i = 0, distinct = 0, last = 0xFFFFFFFFu;
+  uint64_t C = weights[0];  // C[i], inclusive
+  for (uint32_t j = 0; j < M; ++j) {
+    uint32_t a;
+    if (S == 0) {
+      a = j % P;
+    } else {
+      const uint64_t t = (uint64_t)j * q + ((uint64_t)j * rho + r) / M;  // < S: the walk ends inside the list
+      while (C <= t) C += weights[++i];
+      a = i;
+    }
+    if (a != last) ++distinct;  // (a is non-decreasing)
+    last = a;
+    if (delta)
+      resample_move(poses + 4u * (size_t)a, delta + (n_delta == 1u ? 0u : 4u * (size_t)j), poses_out + 4u * (size_t)j);
+    else
+      std::memcpy(poses_out + 4u * (size_t)j, poses + 4u * (size_t)a, 16);
+    if (ancestors_out) ancestors_out[j] = a;
+  }
+  result[0] = (uint32_t)S;
+  result[1] = (uint32_t)(S >> 32);
+  result[2] = (uint32_t)sq;
+  result[3] = (uint32_t)(sq >> 32);
+  result[4] = carry;
+  result[5] = nz;
+  result[6] = S == 0 ? std::min(M, P) : distinct;
+  result[7] = S == 0 ? 1u : 0u;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_resample_poses_dev(rplgpu_handle_t h, const uint32_t *d_weights, uint64_t weight_stride,
+                                  const float *d_poses, uint64_t pose_stride, uint32_t poses_per_group, uint32_t G,
+                                  uint32_t P, uint32_t M, const uint32_t *d_u, const float *d_delta,
+                                  uint32_t n_delta, uint64_t delta_stride, uint32_t delta_per_group,
+                                  float *d_poses_out, uint64_t out_stride, uint32_t *d_ancestors,
+                                  uint64_t anc_stride, uint32_t *d_result, uint32_t *d_scratch) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_resample_poses_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES || M == 0 || M > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_resample_poses_dev: P and M must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_weights || !d_poses || !d_poses_out || !d_result || !d_scratch || misaligned(d_weights, 3) || misaligned(d_poses, 15) ||
+      misaligned(d_poses_out, 15) || misaligned(d_result, 3) || misaligned(d_scratch, 7) || misaligned(d_u, 3) || misaligned(d_delta, 15) ||
+      misaligned(d_ancestors, 3)) {
+    h->err = "rplgpu_resample_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for pose "
+             "lists and deltas, 8 for d_scratch, 4 otherwise)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (weight_stride < P || pose_stride < 4ull * P || (pose_stride & 3u) || out_stride < 4ull * M ||
+      (out_stride & 3u) || (d_ancestors && anc_stride < M)) {
+    h->err = "rplgpu_resample_poses_dev: weight_stride >= P, pose_stride >= 4 P, out_stride >= 4 M (both multiples "
+             "of 4) and anc_stride >= M are required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_delta && ((n_delta != 1u && n_delta != M) || delta_stride < 4ull * n_delta || (delta_stride & 3u))) {
+    h->err = "rplgpu_resample_poses_dev: n_delta must be 1 or M, delta_stride >= 4 n_delta and a multiple of 4";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint64_t in_bytes = 4ull * ((poses_per_group ? (uint64_t)(G - 1u) * pose_stride : 0ull) + 4ull * P);
+  const uint64_t out_bytes = 4ull * ((uint64_t)(G - 1u) * out_stride + 4ull * M);
+  if (ranges_overlap(d_poses, in_bytes, d_poses_out, out_bytes)) {
+    h->err = "rplgpu_resample_poses_dev: d_poses_out overlaps d_poses";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, {{d_weights, "d_weights", true}, {d_poses, "d_poses", true},
+                           {d_poses_out, "d_poses_out", true}, {d_result, "d_result", true},
+                           {d_scratch, "d_scratch", true}, {d_u, "d_u", false}, {d_delta, "d_delta", false},
+                           {d_ancestors, "d_ancestors", false}}))
+    return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_resample(h->stream, d_weights, weight_stride, d_poses, pose_stride, poses_per_group, G, P,
+                                  M, d_u, d_delta, d_delta ? n_delta : 1u, delta_stride, delta_per_group,
+                                  d_poses_out, out_stride, d_ancestors, anc_stride, d_result, d_scratch));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_resample_poses(rplgpu_handle_t h, const uint32_t *weights, uint32_t P, uint32_t M, uint32_t u,
+                              const float *poses, const float *delta, uint32_t n_delta, float *poses_out,
+                              uint32_t *ancestors_out, uint32_t result[8]) {
+  if (!h || !weights || !poses || !poses_out || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (P == 0 || P > RPLGPU_MAX_POSES || M == 0 || M > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_resample_poses: P and M must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (delta && n_delta != 1u && n_delta != M) {
+    h->err = "rplgpu_resample_poses: n_delta must be 1 or M";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (ranges_overlap(poses, 16ull * P, poses_out, 16ull * M)) {
+    h->err = "rplgpu_resample_poses: poses_out overlaps poses";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // poses | out | deltas | weights | ancestors | scratch | u + result
+  const size_t nd = delta ? n_delta : 0u;
+  DoorBuffer buf(h, "rplgpu_resample_poses");
+  const size_t o_in = buf.part(16u * (size_t)P), o_out = buf.part(16u * (size_t)M), o_dl = buf.part_if(delta, 16u * nd),
+               o_wt = buf.part(4u * (size_t)P), o_anc = buf.part(4u * (size_t)M),
+               o_scr = buf.part(4u * (size_t)rplgpu_resample_scratch_words(1, P)), o_small = buf.part(48);
+  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int32_t rc = buf.run([&]() -> int32_t {
+    uint32_t *d_small = buf.at<uint32_t>(o_small);  // u, then the result at + 4 words
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_in), poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_wt), weights, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d_small, &u, 4, hipMemcpyHostToDevice, h->stream));
+    if (delta) RPL_HIP(h, hipMemcpyAsync(buf.at(o_dl), delta, 16u * nd, hipMemcpyHostToDevice, h->stream));
+    const int32_t irc = rplgpu_resample_poses_dev(
+        h, buf.at<const uint32_t>(o_wt), P, buf.at<const float>(o_in), 4ull * P, 0, 1, P, M, d_small,
+        buf.at<const float>(o_dl), n_delta, 4ull * nd, 0, buf.at<float>(o_out), 4ull * M, buf.at<uint32_t>(o_anc), M,
+        d_small + 4, buf.at<uint32_t>(o_scr));
+    if (irc) return irc;
+    RPL_HIP(h, hipMemcpyAsync(poses_out, buf.at(o_out), 16u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    if (ancestors_out)
+      RPL_HIP(h, hipMemcpyAsync(ancestors_out, buf.at(o_anc), 4u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d_small + 4, 32, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  });
+  if (rc) return rc;
+  std::memcpy(result, small, 32);
+  return RPLGPU_OK;
+}
+
+// ---- E17: a weighted pose list reduced to a pose estimate (include/rplgpu_msg.h) -------------------------------------
+
+void rplgpu_default_pose_estimate(rplgpu_pose_estimate_t *s) {
+  if (!s) return;
+  s->xy_scale = 1024.0f;
+  s->gate_r2 = 512ull * 512ull;
+  s->gate_dot = 15ll << 36;
+}
+
+int32_t rplgpu_pose_estimate_check(const rplgpu_pose_estimate_t *s) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(s->xy_scale) || !(s->xy_scale > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+uint64_t rplgpu_estimate_scratch_words(uint32_t G, uint32_t P) { return rpl::estimate_scratch_words(G, P); }
+
+// E17's quantisation of one pose entry: one float32 product (this unit is built with -ffp-contract=off), the range
+// test, one round-to-nearest-even (the default rounding mode)
+static bool estimate_quantise(const float *pose, float xy_scale, int32_t q[4]) {
+  const float t[4] = {pose[2] * xy_scale, pose[3] * xy_scale, pose[0] * 1048576.0f, pose[1] * 1048576.0f};
+  for (int k = 0; k < 4; ++k) {
+    if (!(std::fabs(t[k]) < 8388608.0f)) return false;
+  }
+  for (int k = 0; k < 4; ++k) q[k] = (int32_t)std::rint(t[k]);  // X, Y, C, S
+  return true;
+}
+
+int32_t rplgpu_estimate_host(const float *poses, uint32_t P, const uint32_t *weights,
+                             const rplgpu_pose_estimate_t *s, uint32_t center, uint32_t result[72]) {
+  if (!poses || !result || rplgpu_pose_estimate_check(s) != RPLGPU_OK || P == 0 || P > RPLGPU_MAX_POSES)
+    return RPLGPU_ERR_INVALID_ARG;
+  const uint32_t qc = std::min(center, P - 1u);
+  int32_t c[4] = {0, 0, 0, 0};
+  const bool c_in = estimate_quantise(poses + 4u * (size_t)qc, s->xy_scale, c);
+  __int128 sum[2][8] = {};
+  uint32_t count[2][2] = {{0, 0}, {0, 0}};
+  for (uint32_t i = 0; i < P; ++i) {
+    int32_t q[4];
+    if (!estimate_quantise(poses + 4u * (size_t)i, s->xy_scale, q)) continue;
+    const int64_t X = q[0], Y = q[1], C = q[2], S = q[3];
+    const int64_t dX = X - c[0], dY = Y - c[1];
+    const bool gate = c_in && (uint64_t)(dX * dX + dY * dY) <= s->gate_r2 && C * c[2] + S * c[3] >= s->gate_dot;
+    const __int128 w = weights ? weights[i] : 1u;
+    const __int128 term[8] = {w, w * X, w * Y, w * C, w * S, w * (X * X), w * (X * Y), w * (Y * Y)};
+    for (int k = 0; k < (gate ? 2 : 1); ++k) {
+      for (int m = 0; m < 8; ++m) sum[k][m] += term[m];
+      count[k][0] += 1u;
+      count[k][1] += w != 0 ? 1u : 0u;
+    }
+  }
+  result[0] = (c_in ? 0u : 1u) | (count[0][0] != P ? 2u : 0u) | (sum[0][0] == 0 ? 4u : 0u) | (sum[1][0] == 0 ? 8u : 0u);
+  result[1] = qc;
+  result[2] = count[0][0];
+  result[3] = count[0][1];
+  result[4] = count[1][0];
+  result[5] = count[1][1];
+  result[6] = result[7] = 0u;
+  for (int k = 0; k < 2; ++k) {
+    for (int m = 0; m < 8; ++m) {
+      const unsigned __int128 v = (unsigned __int128)sum[k][m];
+      for (int j = 0; j < 4; ++j) result[8 + 32 * k + 4 * m + j] = (uint32_t)(v >> (32 * j));
+    }
+  }
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_estimate_pose(const uint32_t result[72], float xy_scale, uint32_t set, double out[8]) {
+  if (!result || !out || set > 1u || !std::isfinite(xy_scale) || !(xy_scale > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  double v[8];  // each sum rounded to fp64 once
+  for (int m = 0; m < 8; ++m) {
+    unsigned __int128 u = 0;
+    for (int j = 3; j >= 0; --j) u = (u << 32) | result[8 + 32 * set + 4 * m + j];
+    v[m] = (double)(__int128)u;
+  }
+  if (v[0] == 0.0) return RPLGPU_ERR_INVALID_ARG;  // (W < 2^52 is exact, so this is W == 0)
+  const double scale = (double)xy_scale, scale2 = scale * scale;  // (24 x 24 bits: exact)
+  const double mx = v[1] / v[0] / scale, my = v[2] / v[0] / scale;
+  out[0] = mx;
+  out[1] = my;
+  out[2] = std::atan2(v[4], v[3]);
+  out[3] = v[5] / v[0] / scale2 - mx * mx;
+  out[4] = v[6] / v[0] / scale2 - mx * my;
+  out[5] = v[7] / v[0] / scale2 - my * my;
+  out[6] = std::hypot(v[3], v[4]) / (v[0] * 1048576.0);
+  out[7] = v[0];
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_estimate_poses_dev(rplgpu_handle_t h, const float *d_poses, uint64_t pose_stride,
+                                  uint32_t poses_per_group, const uint32_t *d_weights, uint64_t weight_stride,
+                                  uint32_t G, uint32_t P, const rplgpu_pose_estimate_t *s, const uint32_t *d_center,
+                                  uint64_t center_stride, uint32_t *d_result, uint32_t *d_scratch) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_estimate_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_estimate_poses_dev: invalid rplgpu_pose_estimate_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_estimate_poses_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_estimate_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_poses || !d_result || !d_scratch || misaligned(d_poses, 15) || misaligned(d_result, 3) || misaligned(d_scratch, 7) ||
+      misaligned(d_weights, 3) || misaligned(d_center, 3)) {
+    h->err = "rplgpu_estimate_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for the "
+             "pose list, 8 for d_scratch, 4 otherwise)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (pose_stride < 4ull * P || (pose_stride & 3u) || (d_weights && weight_stride < P)) {
+    h->err = "rplgpu_estimate_poses_dev: pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_center && center_stride == 0 && G > 1u) {
+    h->err = "rplgpu_estimate_poses_dev: center_stride must not be 0 with more than one group";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, {{d_poses, "d_poses", true}, {d_result, "d_result", true}, {d_scratch, "d_scratch", true},
+                           {d_weights, "d_weights", false}, {d_center, "d_center", false}}))
+    return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_estimate(h->stream, d_poses, pose_stride, poses_per_group, d_weights, weight_stride, G, P,
+                                  s->xy_scale, s->gate_r2, s->gate_dot, d_center, center_stride, d_result,
+                                  d_scratch));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_estimate_poses(rplgpu_handle_t h, const float *poses, uint32_t P, const uint32_t *weights,
+                              const rplgpu_pose_estimate_t *s, uint32_t center, uint32_t result[72]) {
+  if (!h || !poses || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_estimate_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_estimate_poses: invalid rplgpu_pose_estimate_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_estimate_poses: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // poses | weights | scratch | centre + result
+  DoorBuffer buf(h, "rplgpu_estimate_poses");
+  const size_t o_in = buf.part(16u * (size_t)P), o_wt = buf.part_if(weights, 4u * (size_t)P),
+               o_scr = buf.part(4u * (size_t)rplgpu_estimate_scratch_words(1, P)),
+               o_small = buf.part(16u + 4u * RPLGPU_ESTIMATE_WORDS);
+  uint32_t words[RPLGPU_ESTIMATE_WORDS];
+  const int32_t rc = buf.run([&]() -> int32_t {
+    uint32_t *d_small = buf.at<uint32_t>(o_small);  // the centre word, then the result at + 4 words
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_in), poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    if (weights) RPL_HIP(h, hipMemcpyAsync(buf.at(o_wt), weights, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(d_small, &center, 4, hipMemcpyHostToDevice, h->stream));
+    const int32_t irc = rplgpu_estimate_poses_dev(h, buf.at<const float>(o_in), 4ull * P, 0,
+                                                  buf.at<const uint32_t>(o_wt), P, 1, P, s, d_small, 0, d_small + 4,
+                                                  buf.at<uint32_t>(o_scr));
+    if (irc) return irc;
+    RPL_HIP(h, hipMemcpyAsync(words, d_small + 4, sizeof(words), hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  });
+  if (rc) return rc;
+  std::memcpy(result, words, sizeof(words));
+  return RPLGPU_OK;
+}
+
+// ---- E18: a pose list's motion noise drawn on the device (include/rplgpu_msg.h) --------------------------------------
+
+void rplgpu_default_motion_noise(rplgpu_motion_noise_t *s) {
+  if (!s) return;
+  s->seed = 0;
+  s->step = 0;
+  s->first = 0;
+  s->reserved = 0;
+}
+
+static void philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  uint32_t c[4] = {ctr[0], ctr[1], ctr[2], ctr[3]}, k0 = key[0], k1 = key[1];
+  for (int r = 0; r < 10; ++r) {
+    if (r) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const uint64_t p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = (uint32_t)p1;
+    c[2] = n2;
+    c[3] = (uint32_t)p0;
+  }
+  std::memcpy(out, c, 16);
+}
+
+int32_t rplgpu_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  if (!ctr || !key || !out) return RPLGPU_ERR_INVALID_ARG;
+  philox4x32(ctr, key, out);
+  return RPLGPU_OK;
+}
+
+// E18's integer normal of one draw: the eight 16-bit halves of the block, minus their mean
+static int32_t motion_draw(const rplgpu_motion_noise_t *s, uint32_t g, uint32_t j, uint32_t i) {
+  const uint32_t ctr[4] = {s->first + j, (g << 2) | i, (uint32_t)s->step, (uint32_t)(s->step >> 32)};
+  const uint32_t key[2] = {(uint32_t)s->seed, (uint32_t)(s->seed >> 32)};
+  uint32_t w[4];
+  philox4x32(ctr, key, w);
+  int32_t z = -262140;
+  for (int k = 0; k < 4; ++k) z += (int32_t)(w[k] & 0xFFFFu) + (int32_t)(w[k] >> 16);
+  return z;
+}
+
+// E18's noise rotation by 2 atan(Z k) and the composition r o n: float32, every operation rounded once (this unit is
+// built with -ffp-contract=off)
+static void motion_noise(int32_t z, float k, float n[2]) {
+  const float t = (float)z * k, q = t * t, den = 1.0f + q;
+  n[0] = (1.0f - q) / den;
+  n[1] = (t + t) / den;
+}
+static void motion_compose(const float r[2], const float n[2], float a[2]) {
+  const float p0 = r[0] * n[0], p1 = r[1] * n[1], p2 = r[1] * n[0], p3 = r[0] * n[1];
+  a[0] = p0 - p1;
+  a[1] = p2 + p3;
+}
+
+int32_t rplgpu_sample_motion_host(const float odom[8], uint32_t group, uint32_t M, const rplgpu_motion_noise_t *s,
+                                  float *delta_out, uint32_t result[8]) {
+  if (!odom || !s || !delta_out || !result || group > 65534u || M == 0 || M > RPLGPU_MAX_POSES)
+    return RPLGPU_ERR_INVALID_ARG;
+  const float r1[2] = {odom[0], odom[1]}, r2[2] = {odom[3], odom[4]};
+  const float trans = odom[2], k1 = odom[5], kt = odom[6], k2 = odom[7];
+  uint32_t nans = 0, zmax = 0;
+  int64_t sum = 0;
+  uint64_t squares = 0;
+  for (uint32_t j = 0; j < M; ++j) {
+    int32_t z[3];
+    for (uint32_t i = 0; i < 3; ++i) {
+      z[i] = motion_draw(s, group, j, i);
+      zmax = std::max(zmax, (uint32_t)std::abs(z[i]));
+      sum += z[i];
+      squares += (uint64_t)((int64_t)z[i] * z[i]);
+    }
+    float n1[2], n2[2], a[2], b[2], d[2];
+    motion_noise(z[0], k1, n1);
+    motion_noise(z[2], k2, n2);
+    motion_compose(r1, n1, a);
+    motion_compose(r2, n2, b);
+    motion_compose(a, b, d);
+    const float noise = (float)z[1] * kt;
+    const float tr = trans + noise;
+    float v[4] = {d[0], d[1], a[0] * tr, a[1] * tr};
+    const uint32_t qnan = 0x7FC00000u;
+    bool any = false;
+    for (int k = 0; k < 4; ++k) {
+      if (v[k] != v[k]) {
+        std::memcpy(&v[k], &qnan, 4);
+        any = true;
+      }
+    }
+    nans += any ? 1u : 0u;
+    std::memcpy(delta_out + 4u * (size_t)j, v, 16);
+  }
+  result[0] = nans;
+  result[1] = zmax;
+  result[2] = (uint32_t)(uint64_t)sum;
+  result[3] = (uint32_t)((uint64_t)sum >> 32);
+  result[4] = (uint32_t)squares;
+  result[5] = (uint32_t)(squares >> 32);
+  result[6] = 0u;
+  result[7] = nans ? 1u : 0u;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_motion_odometry(double dx, double dy, double dtheta, const double alpha[4], float out[8]) {
+  if (!alpha || !out) return RPLGPU_ERR_INVALID_ARG;
+  const double pi = 3.14159265358979323846;
+  const double trans = std::sqrt(dx * dx + dy * dy);
+  const double rot1 = trans >= 0.01 ? std::atan2(dy, dx) : 0.0;
+  const double d = dtheta - rot1;
+  const double rot2 = std::atan2(std::sin(d), std::cos(d));
+  const double f1 = std::min(std::fabs(rot1), pi - std::fabs(rot1));
+  const double f2 = std::min(std::fabs(rot2), pi - std::fabs(rot2));
+  const double v1 = alpha[0] * f1 * f1 + alpha[1] * trans * trans;
+  const double vt = alpha[2] * trans * trans + alpha[3] * (f1 * f1 + f2 * f2);
+  const double v2 = alpha[0] * f2 * f2 + alpha[1] * trans * trans;
+  const double sigma_z = std::sqrt(2863311530.0);
+  out[0] = (float)std::cos(rot1);
+  out[1] = (float)std::sin(rot1);
+  out[2] = (float)trans;
+  out[3] = (float)std::cos(rot2);
+  out[4] = (float)std::sin(rot2);
+  out[5] = (float)(std::sqrt(v1) / (2.0 * sigma_z));
+  out[6] = (float)(std::sqrt(vt) / sigma_z);
+  out[7] = (float)(std::sqrt(v2) / (2.0 * sigma_z));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_sample_motion_dev(rplgpu_handle_t h, const float *d_odom, uint32_t odom_per_group, uint32_t G,
+                                 uint32_t M, const rplgpu_motion_noise_t *s, float *d_delta, uint64_t delta_stride,
+                                 uint32_t *d_result) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  if (!s) {
+    h->err = "rplgpu_sample_motion_dev: the rplgpu_motion_noise_t is missing";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_sample_motion_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (M == 0 || M > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_sample_motion_dev: M must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_odom || !d_delta || !d_result || misaligned(d_odom, 15) || misaligned(d_delta, 15) || misaligned(d_result, 3)) {
+    h->err = "rplgpu_sample_motion_dev: a required pointer is missing or a pointer is misaligned (16 bytes for d_odom "
+             "and d_delta, 4 for d_result)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (delta_stride < 4ull * M || (delta_stride & 3u)) {
+    h->err = "rplgpu_sample_motion_dev: delta_stride >= 4 M and a multiple of 4 is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, {{d_odom, "d_odom", true}, {d_delta, "d_delta", true}, {d_result, "d_result", true}}))
+    return RPLGPU_ERR_INVALID_ARG;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_motion(h->stream, d_odom, odom_per_group, G, M, s->seed, s->step, s->first, d_delta,
+                                delta_stride, d_result));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_sample_motion(rplgpu_handle_t h, const float odom[8], uint32_t M, const rplgpu_motion_noise_t *s,
+                             float *delta_out, uint32_t result[8]) {
+  if (!h || !odom || !s || !delta_out || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (M == 0 || M > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_sample_motion: M must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  DoorBuffer buf(h, "rplgpu_sample_motion");
+  const size_t o_odom = buf.part(32), o_res = buf.part(32), o_dl = buf.part(16u * (size_t)M);
+  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int32_t rc = buf.run([&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_odom), odom, 32, hipMemcpyHostToDevice, h->stream));
+    const int32_t irc = rplgpu_sample_motion_dev(h, buf.at<const float>(o_odom), 0, 1, M, s, buf.at<float>(o_dl),
+                                                 4ull * M, buf.at<uint32_t>(o_res));
+    if (irc) return irc;
+    RPL_HIP(h, hipMemcpyAsync(delta_out, buf.at(o_dl), 16u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, buf.at(o_res), 32, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  });
+  if (rc) return rc;
+  std::memcpy(result, small, 32);
+  return RPLGPU_OK;
+}
+
+// ---- E19: a pose list seeded over a grid's free cells on the device (include/rplgpu_msg.h) ---------------------------
+
+void rplgpu_default_pose_seed(rplgpu_pose_seed_t *s) {
+  if (!s) return;
+  s->origin_x = -25.6f;
+  s->origin_y = -25.6f;
+  s->resolution = 0.05f;
+  s->width = 1024;
+  s->height = 1024;
+  s->free_lo = 0;
+  s->free_hi = 0;
+  s->flags = 0;
+}
+
+int32_t rplgpu_pose_seed_check(const rplgpu_pose_seed_t *s) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(s->origin_x) || !std::isfinite(s->origin_y) || !std::isfinite(s->resolution))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!(s->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  if (s->width == 0 || s->width > RPLGPU_MAX_OCC_DIM || s->height == 0 || s->height > RPLGPU_MAX_OCC_DIM)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (s->free_lo < -128 || s->free_lo > 127 || s->free_hi < -128 || s->free_hi > 127 || s->free_lo > s->free_hi)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (s->flags > 1u) return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+uint64_t rplgpu_seed_scratch_words(uint32_t G_f, uint32_t width, uint32_t height) {
+  return rpl::seed_scratch_words(G_f, width, height);
+}
+
+int32_t rplgpu_seed_headings(uint32_t H, float *cs) {
+  if (!cs || H == 0 || H > 65536u) return RPLGPU_ERR_INVALID_ARG;
+  const double two_pi = 6.283185307179586476925286766559;
+  for (uint32_t k = 0; k < H; ++k) {
+    const double a = two_pi * (double)k / (double)H;
+    cs[2u * k] = k == 0 ? 1.0f : (float)std::cos(a);
+    cs[2u * k + 1u] = k == 0 ? 0.0f : (float)std::sin(a);
+  }
+  return RPLGPU_OK;
+}
+
+// the E11 cell rule on the host: float32, every operation rounded once (this unit is built with -ffp-contract=off)
+static bool seed_cell(float x, float y, const rplgpu_pose_seed_t *s, int32_t *cx, int32_t *cy) {
+  const float du = x - s->origin_x, dv = y - s->origin_y;
+  const float u = du / s->resolution, v = dv / s->resolution;
+  const float fu = std::floor(u), fv = std::floor(v);
+  if (!(std::fabs(fu) < 1048576.0f && std::fabs(fv) < 1048576.0f)) return false;
+  *cx = (int32_t)fu;
+  *cy = (int32_t)fv;
+  return true;
+}
+
+int32_t rplgpu_seed_poses_host(const rplgpu_pose_seed_t *s, const int8_t *grid, const float *headings, uint32_t H,
+                               uint32_t group, uint32_t M, const rplgpu_motion_noise_t *noise, float *poses_out,
+                               uint32_t *cells_out, uint32_t result[8]) {
+  if (rplgpu_pose_seed_check(s) != RPLGPU_OK || !grid || !headings || !noise || !poses_out || !result ||
+      group > 65534u || H == 0 || H > 65536u || M == 0 || M > RPLGPU_MAX_POSES)
+    return RPLGPU_ERR_INVALID_ARG;
+  const uint32_t cells = s->width * s->height;
+  auto is_free = [&](uint32_t i) { return grid[i] >= s->free_lo && grid[i] <= s->free_hi; };
+  uint32_t F = 0;
+  for (uint32_t i = 0; i < cells; ++i) F += is_free(i) ? 1u : 0u;
+  const bool none = F == 0;
+  if (none) F = cells;
+  // the draws first, then ONE walk over the cells in index order hands every draw its cell: the outputs sorted by r
+  std::vector<uint32_t> words(4u * (size_t)M), order(M), cell(M);
+  const uint32_t key[2] = {(uint32_t)noise->seed, (uint32_t)(noise->seed >> 32)};
+  for (uint32_t j = 0; j < M; ++j) {
+    const uint32_t ctr[4] = {noise->first + j, (group << 2) | 3u, (uint32_t)noise->step,
+                             (uint32_t)(noise->step >> 32)};
+    philox4x32(ctr, key, &words[4u * (size_t)j]);
+    order[j] = j;
+  }
+  auto rank = [&](uint32_t j) { return (uint32_t)(((uint64_t)words[4u * (size_t)j] * F) >> 32); };
+  if (none) {
+    for (uint32_t j = 0; j < M; ++j) cell[j] = rank(j);
+  } else {
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rank(a) < rank(b); });
+    uint32_t seen = 0, q = 0;  // free cells in front of cell i; outputs served
+    for (uint32_t i = 0; i < cells && q < M; ++i) {
+      if (!is_free(i)) continue;
+      while (q < M && rank(order[q]) == seen) cell[order[q++]] = i;
+      ++seen;
+    }
+  }
+  uint32_t off = 0, lo = 0xFFFFFFFFu, hi = 0;
+  const bool centres = (s->flags & 1u) != 0;
+  for (uint32_t j = 0; j < M; ++j) {
+    const uint32_t *p = &words[4u * (size_t)j];
+    const uint32_t k = (uint32_t)(((uint64_t)p[1] * H) >> 32);
+    const uint32_t cy = cell[j] / s->width, cx = cell[j] - cy * s->width;
+    const float fx = centres ? 0.5f : ((float)(p[2] >> 24) + 0.5f) * (1.0f / 256.0f);
+    const float fy = centres ? 0.5f : ((float)(p[3] >> 24) + 0.5f) * (1.0f / 256.0f);
+    const float ux = (float)cx + fx, uy = (float)cy + fy;
+    const float mx = ux * s->resolution, my = uy * s->resolution;
+    const float x = s->origin_x + mx, y = s->origin_y + my;
+    int32_t bx = 0, by = 0;
+    if (!(seed_cell(x, y, s, &bx, &by) && bx == (int32_t)cx && by == (int32_t)cy)) ++off;
+    lo = std::min(lo, cell[j]);
+    hi = std::max(hi, cell[j]);
+    std::memcpy(poses_out + 4u * (size_t)j, headings + 2u * (size_t)k, 8);  // bit for bit
+    poses_out[4u * (size_t)j + 2u] = x;
+    poses_out[4u * (size_t)j + 3u] = y;
+    if (cells_out) cells_out[j] = cell[j];
+  }
+  result[0] = F;
+  result[1] = off;
+  result[2] = lo;
+  result[3] = hi;
+  result[4] = result[5] = result[6] = 0u;
+  result[7] = (none ? 1u : 0u) | (off ? 2u : 0u);
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_seed_poses_dev(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, const int8_t *d_grid,
+                              uint64_t grid_stride, uint32_t grid_per_group, const float *d_headings, uint32_t H,
+                              uint32_t G, uint32_t M, const rplgpu_motion_noise_t *noise, float *d_poses_out,
+                              uint64_t out_stride, uint32_t *d_cells_out, uint64_t cell_stride, uint32_t *d_result,
+                              uint32_t *d_scratch) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_seed_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_seed_poses_dev: the rplgpu_pose_seed_t is missing or rplgpu_pose_seed_check refuses it";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!noise) {
+    h->err = "rplgpu_seed_poses_dev: the rplgpu_motion_noise_t is missing";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_seed_poses_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (M == 0 || M > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_seed_poses_dev: M must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (H == 0 || H > 65536u) {
+    h->err = "rplgpu_seed_poses_dev: H must be in 1 .. 65536";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_grid || !d_headings || !d_poses_out || !d_result || !d_scratch || misaligned(d_grid, 3) || misaligned(d_headings, 7) ||
+      misaligned(d_poses_out, 15) || misaligned(d_cells_out, 3) || misaligned(d_result, 3) || misaligned(d_scratch, 7)) {
+    h->err = "rplgpu_seed_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for "
+             "d_poses_out, 8 for d_headings and d_scratch, 4 for d_grid, d_cells_out and d_result)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint64_t cells = (uint64_t)s->width * s->height;
+  if (grid_stride < cells || (grid_stride & 3u)) {
+    h->err = "rplgpu_seed_poses_dev: grid_stride >= width * height and a multiple of 4 is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (out_stride < 4ull * M || (out_stride & 3u)) {
+    h->err = "rplgpu_seed_poses_dev: out_stride >= 4 M and a multiple of 4 is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_cells_out && cell_stride < M) {
+    h->err = "rplgpu_seed_poses_dev: cell_stride >= M is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, {{d_grid, "d_grid", true}, {d_headings, "d_headings", true},
+                           {d_poses_out, "d_poses_out", true}, {d_result, "d_result", true},
+                           {d_scratch, "d_scratch", true}, {d_cells_out, "d_cells_out", false}}))
+    return RPLGPU_ERR_INVALID_ARG;
+  rpl::SeedK k;
+  k.origin_x = s->origin_x;
+  k.origin_y = s->origin_y;
+  k.resolution = s->resolution;
+  k.width = s->width;
+  k.height = s->height;
+  k.free_lo = s->free_lo;
+  k.free_hi = s->free_hi;
+  k.centres = s->flags & 1u;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_seed(h->stream, k, d_grid, grid_stride, grid_per_group, d_headings, H, G, M, noise->seed,
+                              noise->step, noise->first, d_poses_out, out_stride, d_cells_out, cell_stride, d_result,
+                              d_scratch));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_seed_poses(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, const int8_t *grid, const float *headings,
+                          uint32_t H, uint32_t M, const rplgpu_motion_noise_t *noise, float *poses_out,
+                          uint32_t *cells_out, uint32_t result[8]) {
+  if (!h || !grid || !headings || !noise || !poses_out || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_seed_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_seed_poses: the rplgpu_pose_seed_t is missing or rplgpu_pose_seed_check refuses it";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (M == 0 || M > RPLGPU_MAX_POSES || H == 0 || H > 65536u) {
+    h->err = "rplgpu_seed_poses: M must be in 1 .. RPLGPU_MAX_POSES and H in 1 .. 65536";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // result | headings | grid | scratch | cells | poses
+  const size_t cells = (size_t)s->width * s->height, gstride = (cells + 3u) & ~(size_t)3u;
+  DoorBuffer buf(h, "rplgpu_seed_poses");
+  const size_t o_res = buf.part(32), o_head = buf.part(8u * (size_t)H), o_grid = buf.part(gstride),
+               o_scr = buf.part(4u * (size_t)rplgpu_seed_scratch_words(1, s->width, s->height)),
+               o_cells = buf.part(4u * (size_t)M), o_poses = buf.part(16u * (size_t)M);
+  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int32_t rc = buf.run([&]() -> int32_t {
+    RPL_HIP(h, hipMemsetAsync(buf.at(o_grid), 0, up16(gstride), h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_head), headings, 8u * (size_t)H, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_grid), grid, cells, hipMemcpyHostToDevice, h->stream));
+    const int32_t irc = rplgpu_seed_poses_dev(h, s, buf.at<const int8_t>(o_grid), gstride, 0,
+                                              buf.at<const float>(o_head), H, 1, M, noise, buf.at<float>(o_poses),
+                                              4ull * M, buf.at<uint32_t>(o_cells), M, buf.at<uint32_t>(o_res),
+                                              buf.at<uint32_t>(o_scr));
+    if (irc) return irc;
+    RPL_HIP(h, hipMemcpyAsync(poses_out, buf.at(o_poses), 16u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    if (cells_out)
+      RPL_HIP(h, hipMemcpyAsync(cells_out, buf.at(o_cells), 4u * (size_t)M, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, buf.at(o_res), 32, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  });
+  if (rc) return rc;
+  std::memcpy(result, small, 32);
+  return RPLGPU_OK;
+}
+
+// ---- E20: a pose list's occupied bins counted on the device (include/rplgpu_msg.h) -----------------------------------
+
+void rplgpu_default_pose_bins(rplgpu_pose_bins_t *s) {
+  if (!s) return;
+  s->origin_x = -25.6f;
+  s->origin_y = -25.6f;
+  s->inv_size = 2.0f;
+  s->nx = 103;
+  s->ny = 103;
+  s->flags = 0;
+}
+
+int32_t rplgpu_pose_bins_check(const rplgpu_pose_bins_t *s, uint32_t T) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(s->origin_x) || !std::isfinite(s->origin_y) || !std::isfinite(s->inv_size))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!(s->inv_size > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  if (s->nx == 0 || s->nx > 65536u || s->ny == 0 || s->ny > 65536u) return RPLGPU_ERR_INVALID_ARG;
+  if (T == 0 || T > RPLGPU_MAX_HEADING_BINS) return RPLGPU_ERR_INVALID_ARG;
+  if ((uint64_t)s->nx * s->ny * T > (uint64_t)RPLGPU_MAX_POSE_BINS) return RPLGPU_ERR_INVALID_ARG;
+  if (s->flags > 1u) return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+uint64_t rplgpu_bin_map_words(uint32_t nx, uint32_t ny, uint32_t T) {
+  rplgpu_pose_bins_t s;
+  rplgpu_default_pose_bins(&s);
+  s.nx = nx;
+  s.ny = ny;
+  if (rplgpu_pose_bins_check(&s, T) != RPLGPU_OK) return 0;
+  const uint64_t words = ((uint64_t)nx * ny * T + 31u) >> 5;
+  return (words + 1u) & ~(uint64_t)1u;
+}
+
+// E20's quantisation of (c, s), E17's rule: one float32 product, the range test, one round-to-nearest-even; false for
+// an entry that is out of range or quantises to (0, 0)
+static bool bins_quantise(const float *cs, int32_t q[2]) {
+  const float tc = cs[0] * 1048576.0f, ts = cs[1] * 1048576.0f;
+  q[0] = q[1] = 0;
+  if (!(std::fabs(tc) < 8388608.0f && std::fabs(ts) < 8388608.0f)) return false;
+  q[0] = (int32_t)std::rint(tc);
+  q[1] = (int32_t)std::rint(ts);
+  return q[0] != 0 || q[1] != 0;
+}
+static uint32_t bins_half(const int32_t a[2]) { return (a[1] > 0 || (a[1] == 0 && a[0] > 0)) ? 0u : 1u; }
+// a <= b in the angular order, both in range and not (0, 0)
+static bool bins_le(const int32_t a[2], const int32_t b[2]) {
+  const uint32_t ha = bins_half(a), hb = bins_half(b);
+  if (ha != hb) return ha < hb;
+  return (int64_t)a[0] * b[1] - (int64_t)a[1] * b[0] >= 0;
+}
+
+int32_t rplgpu_heading_edges_check(const float *cs, uint32_t T) {
+  if (!cs || T == 0 || T > RPLGPU_MAX_HEADING_BINS) return RPLGPU_ERR_INVALID_ARG;
+  int32_t prev[2], cur[2];
+  if (!bins_quantise(cs, prev) || prev[0] != 1048576 || prev[1] != 0) return RPLGPU_ERR_INVALID_ARG;
+  for (uint32_t k = 1; k < T; ++k) {
+    if (!bins_quantise(cs + 2u * (size_t)k, cur)) return RPLGPU_ERR_INVALID_ARG;
+    if (bins_le(cur, prev)) return RPLGPU_ERR_INVALID_ARG;  // not strictly behind its predecessor
+    prev[0] = cur[0];
+    prev[1] = cur[1];
+  }
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_bin_poses_host(const rplgpu_pose_bins_t *s, const float *poses, uint32_t P, const uint32_t *weights,
+                              const float *edges, uint32_t T, uint32_t *map, uint32_t *bins_out,
+                              uint32_t result[8]) {
+  if (rplgpu_pose_bins_check(s, T) != RPLGPU_OK || !poses || !edges || !map || !result || P == 0 ||
+      P > RPLGPU_MAX_POSES)
+    return RPLGPU_ERR_INVALID_ARG;
+  const uint32_t nb = s->nx * s->ny * T, words = (nb + 31u) >> 5;
+  const bool keep = (s->flags & 1u) != 0;
+  if (!keep) std::memset(map, 0, 4u * (size_t)words);
+  std::vector<int32_t> eq(2u * (size_t)T);
+  std::vector<unsigned char> e_ok(T);
+  for (uint32_t k = 0; k < T; ++k) e_ok[k] = bins_quantise(edges + 2u * (size_t)k, &eq[2u * (size_t)k]) ? 1 : 0;
+  uint32_t K = 0, counted = 0, outside = 0, skipped = 0, lo_bin = 0xFFFFFFFFu, hi_bin = 0;
+  for (uint32_t i = 0; i < P; ++i) {
+    const float *p = poses + 4u * (size_t)i;
+    uint32_t b = 0xFFFFFFFFu;
+    if (weights && weights[i] == 0u) {
+      ++skipped;  // (whether or not it is in range)
+    } else {
+      const float dx = p[2] - s->origin_x, dy = p[3] - s->origin_y;
+      const float fx = dx * s->inv_size, fy = dy * s->inv_size;  // (-ffp-contract=off: the difference rounded first)
+      const bool x_in = fx >= 0.0f && fx < (float)s->nx;
+      const bool y_in = fy >= 0.0f && fy < (float)s->ny;
+      int32_t h[2];
+      const bool h_in = bins_quantise(p, h);
+      if (x_in && y_in && h_in) {
+        const uint32_t bx = (uint32_t)std::floor(fx), by = (uint32_t)std::floor(fy);
+        uint32_t lo = 0, hi = T;
+        while (hi - lo > 1u) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (e_ok[mid] && bins_le(&eq[2u * (size_t)mid], h))
+            lo = mid;
+          else
+            hi = mid;
+        }
+        b = (lo * s->ny + by) * s->nx + bx;
+        ++counted;
+        lo_bin = std::min(lo_bin, b);
+        hi_bin = std::max(hi_bin, b);
+        const uint32_t bit = 1u << (b & 31u);
+        if (!(map[b >> 5] & bit)) ++K;  // a bit this call turns from 0 to 1
+        map[b >> 5] |= bit;
+      } else {
+        ++outside;
+      }
+    }
+    if (bins_out) bins_out[i] = b;
+  }
+  result[0] = K;
+  result[1] = counted;
+  result[2] = outside;
+  result[3] = skipped;
+  result[4] = lo_bin;
+  result[5] = hi_bin;
+  result[6] = 0u;
+  result[7] = (counted == 0 ? 1u : 0u) | (outside != 0 ? 2u : 0u) | (keep ? 4u : 0u);
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_bin_poses_dev(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, const float *d_poses,
+                             uint64_t pose_stride, uint32_t poses_per_group, const uint32_t *d_weights,
+                             uint64_t weight_stride, uint32_t G, uint32_t P, const float *d_edges, uint32_t T,
+                             uint32_t *d_map, uint64_t map_stride, uint32_t *d_bins_out, uint64_t bin_stride,
+                             uint32_t *d_result) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_bins_check(s, T) != RPLGPU_OK) {
+    h->err = "rplgpu_bin_poses_dev: the rplgpu_pose_bins_t is missing or rplgpu_pose_bins_check refuses it or T";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_bin_poses_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_bin_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_poses || !d_edges || !d_map || !d_result || misaligned(d_poses, 15) || misaligned(d_edges, 7) || misaligned(d_map, 7) ||
+      misaligned(d_weights, 3) || misaligned(d_bins_out, 3) || misaligned(d_result, 3)) {
+    h->err = "rplgpu_bin_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for d_poses, "
+             "8 for d_edges and d_map, 4 for d_weights, d_bins_out and d_result)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (pose_stride < 4ull * P || (pose_stride & 3u) || (d_weights && weight_stride < P)) {
+    h->err = "rplgpu_bin_poses_dev: pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint64_t words = ((uint64_t)s->nx * s->ny * T + 31u) >> 5;
+  if (map_stride < words || (map_stride & 1u)) {
+    h->err = "rplgpu_bin_poses_dev: map_stride >= ceil(nx * ny * T / 32) and even is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_bins_out && bin_stride < P) {
+    h->err = "rplgpu_bin_poses_dev: bin_stride >= P is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, {{d_poses, "d_poses", true}, {d_edges, "d_edges", true}, {d_map, "d_map", true},
+                           {d_result, "d_result", true}, {d_weights, "d_weights", false},
+                           {d_bins_out, "d_bins_out", false}}))
+    return RPLGPU_ERR_INVALID_ARG;
+  rpl::BinsK k;
+  k.origin_x = s->origin_x;
+  k.origin_y = s->origin_y;
+  k.inv_size = s->inv_size;
+  k.nx = s->nx;
+  k.ny = s->ny;
+  k.keep = s->flags & 1u;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_bins(h->stream, k, d_poses, pose_stride, poses_per_group, d_weights, weight_stride, G, P,
+                              d_edges, T, d_map, map_stride, d_bins_out, bin_stride, d_result));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_bin_poses(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, const float *poses, uint32_t P,
+                         const uint32_t *weights, const float *edges, uint32_t T, uint32_t *map, uint32_t *bins_out,
+                         uint32_t result[8]) {
+  if (!h || !poses || !edges || !map || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_bins_check(s, T) != RPLGPU_OK) {
+    h->err = "rplgpu_bin_poses: the rplgpu_pose_bins_t is missing or rplgpu_pose_bins_check refuses it or T";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_bin_poses: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // result | edges | map | weights | bins | poses
+  const size_t words = ((size_t)s->nx * s->ny * T + 31u) >> 5, stride = (size_t)rplgpu_bin_map_words(s->nx, s->ny, T);
+  DoorBuffer buf(h, "rplgpu_bin_poses");
+  const size_t o_res = buf.part(32), o_edge = buf.part(8u * (size_t)T), o_map = buf.part(4u * stride),
+               o_wt = buf.part_if(weights, 4u * (size_t)P), o_bins = buf.part_if(bins_out, 4u * (size_t)P),
+               o_poses = buf.part(16u * (size_t)P);
+  uint32_t small[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<uint32_t> map_back(words), bins_back(bins_out ? P : 0u);
+  const int32_t rc = buf.run([&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_poses), poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_edge), edges, 8u * (size_t)T, hipMemcpyHostToDevice, h->stream));
+    if (weights) RPL_HIP(h, hipMemcpyAsync(buf.at(o_wt), weights, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    if (s->flags & 1u) RPL_HIP(h, hipMemcpyAsync(buf.at(o_map), map, 4u * words, hipMemcpyHostToDevice, h->stream));
+    const int32_t irc = rplgpu_bin_poses_dev(h, s, buf.at<const float>(o_poses), 4ull * P, 0,
+                                             buf.at<const uint32_t>(o_wt), P, 1, P, buf.at<const float>(o_edge), T,
+                                             buf.at<uint32_t>(o_map), stride, buf.at<uint32_t>(o_bins), P,
+                                             buf.at<uint32_t>(o_res));
+    if (irc) return irc;
+    RPL_HIP(h, hipMemcpyAsync(map_back.data(), buf.at(o_map), 4u * words, hipMemcpyDeviceToHost, h->stream));
+    if (bins_out)
+      RPL_HIP(h, hipMemcpyAsync(bins_back.data(), buf.at(o_bins), 4u * (size_t)P, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, buf.at(o_res), 32, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  });
+  if (rc) return rc;  // (no output changed)
+  std::memcpy(map, map_back.data(), 4u * words);
+  if (bins_out) std::memcpy(bins_out, bins_back.data(), 4u * (size_t)P);
+  std::memcpy(result, small, 32);
+  return RPLGPU_OK;
+}
+
+uint32_t rplgpu_kld_samples(uint32_t k, double epsilon, double z, uint32_t m_min, uint32_t m_max) {
+  if (k <= 1u) return m_max;
+  const double b = 2.0 / (9.0 * ((double)k - 1.0));
+  const double x = 1.0 - b + std::sqrt(b) * z;
+  const double n = std::ceil(((double)k - 1.0) / (2.0 * epsilon) * x * x * x);
+  if (!(n >= (double)m_min)) return m_min;  // (NaN too)
+  if (n > (double)m_max) return m_max;
+  return (uint32_t)n;
+}
+
+}  // extern "C"
