@@ -1216,6 +1216,102 @@ int32_t rplgpu_bin_poses(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, const f
  * byte-exact contract. */
 uint32_t rplgpu_kld_samples(uint32_t k, double epsilon, double z, uint32_t m_min, uint32_t m_max);
 
+/* ---- E21: a binned pose list clustered on the device, the heaviest cluster summed (row 4; the pose AMCL publishes) ----
+ * The pose AMCL publishes is the mean of the HEAVIEST CLUSTER of its samples (pf_kdtree_cluster + pf_cluster_stats),
+ * not a mean over the list; E17's gate around E15's best pose stood in for it.  E20 leaves what clustering needs on
+ * the device — the bit map of occupied bins and one bin id per pose — so this call labels the connected components
+ * of that map, weighs each one and reduces the heaviest to E17's exact integer sums: rplgpu_estimate_pose reads the
+ * result unchanged, and bin -> cluster -> resample queues on one stream without a read of the map.  Nothing in the
+ * reference clusters poses, so these rules ARE the definition (parity unpinned, as E5-E20).  After E17's quantisation
+ * everything is integers: the result depends on no order of execution.
+ *
+ * BINS: bin b = (ktheta * ny + by) * nx + bx and NB = nx * ny * T, exactly as E20; bin b is OCCUPIED iff bit b & 31
+ * of word b >> 5 of the group's map (d_map + g * map_stride, E20's layout and rules) is set.  Bits at and beyond NB
+ * are not looked at.  K is the number of occupied bins.
+ * NEIGHBOURS: two DIFFERENT occupied bins are neighbours iff |dbx| <= 1 and |dby| <= 1 and dktheta is 0, +1 or -1 —
+ * taken modulo T when flags bit 0 (WRAP) is set, so that bin T - 1 is next to bin 0, and plainly otherwise.  There
+ * is no wrap in x or y: bin (nx - 1, by) and bin (0, by + 1) have adjacent ids and are NOT neighbours.
+ * CLUSTERS: a cluster is a connected component of the occupied bins under that relation; its LABEL is its smallest
+ * bin id; N_c is the number of clusters.  A map made under KEEP may hold bits that no pose of this list has: such
+ * bins still connect clusters, and a cluster may hold no pose.
+ * POSES: pose i takes its bin from d_bins[g * bin_stride + i] (E20's d_bins_out; bin_stride >= P).  0xFFFFFFFF is
+ * UNLABELLED; an id >= NB, or an id whose bit is not set in the map, is STRAY: counted, flagged (bit 4), and it
+ * contributes to nothing; any other pose is LABELLED with its bin's cluster.
+ * SUMS: a labelled pose is quantised by E17's rule (xy_scale for x and y, 2^20 for (c, s), in range iff
+ * fabsf(t) < 8388608.0f for all four, rintf).  Out of range it sets flag bit 1 and contributes to no sum, count or
+ * W (its label is still written).  Weights are read as in E17; d_weights NULL means w = 1.
+ * CLUSTER WEIGHT: a cluster's W = sum w and its pose count are taken over its labelled in-range poses.  BEST is the
+ * cluster with the largest W, ties going to the smaller label; it is defined whenever N_c >= 1.  SECOND is the same
+ * choice among the other clusters, or none when N_c < 2.
+ * RESULT: RPLGPU_CLUSTER_WORDS words per group at d_result + 80 g.  Words 0 - 71 are in E17's layout, so
+ * rplgpu_estimate_pose works on them: set 0 covers every labelled in-range pose, set 1 the poses of BEST, the same
+ * eight 128-bit sums in the same order.
+ *   0        flags: bit 0 = N_c is 0; bit 1 = a labelled pose is out of E17's range; bit 2 = set 0 has W = 0;
+ *            bit 3 = set 1 has W = 0; bit 4 = a stray entry; bit 5 = a bound was hit (below)
+ *   1        BEST's label (0xFFFFFFFF: none)
+ *   2, 3     the labelled in-range poses;  those among them with w != 0
+ *   4, 5     the poses of BEST;  those among them with w != 0
+ *   6, 7     N_c;  K
+ *   8 .. 71  the sums, as E17
+ *   72, 73   SECOND's label (0xFFFFFFFF: none);  its poses
+ *   74, 75   SECOND's W, low and high word
+ *   76, 77   the stray entries;  the unlabelled entries
+ *   78, 79   0
+ * BOUND: the call holds at most RPLGPU_MAX_POSES occupied bins (no list makes more; a KEEP map ORed over several
+ * lists can).  With K above it the result is word 0 = 32, words 1 and 72 = 0xFFFFFFFF, word 7 = K and every other
+ * word 0, every label written is 0xFFFFFFFF and no table row is written.  Bit 5 is also what a kernel sets when one
+ * of its loops reaches its stated bound (rpl_clusters.hip); a correct build never does.  Word 7 tells the two apart:
+ * bit 5 with word 7 above RPLGPU_MAX_POSES is this rule and the caller's map, bit 5 with word 7 at or below it is a
+ * defect of the build.
+ * OPTIONAL OUTPUTS: d_labels_out[g * label_stride + i] (label_stride >= P) receives pose i's label, or 0xFFFFFFFF
+ * for an unlabelled or stray pose; words at and beyond P are never changed.  d_clusters + g * cluster_stride
+ * receives 4-word rows {label, poses, W low, W high}: the first min(N_c, cluster_cap) clusters in ASCENDING LABEL
+ * order; rows beyond that are never changed; cluster_stride >= 4 * cluster_cap.
+ * d_map, d_bins, d_poses and d_weights are only read.  SCRATCH is the caller's, as E17's:
+ * rplgpu_cluster_scratch_words(G, P, nx, ny, T) uint32 words at d_scratch, 8-byte aligned (its layout: the head of
+ * rpl_clusters.hip); the function is host only and returns 0 for arguments the call refuses.
+ * RPLGPU_ERR_INVALID_ARG, no output changed and nothing queued, for a spec the check refuses, G = 0 or above 65535,
+ * P = 0 or above RPLGPU_MAX_POSES, a missing d_poses / d_map / d_bins / d_result / d_scratch, a misaligned pointer
+ * (16 bytes: d_poses; 8: d_map, d_scratch; 4: the others), a pose_stride below 4 P or no multiple of 4, a
+ * weight_stride below P with d_weights set, a map_stride below ceil(NB / 32) or odd, a bin_stride below P, a
+ * label_stride below P with d_labels_out set, a cluster_stride below 4 cluster_cap with d_clusters set and
+ * cluster_cap not 0, and an output (d_labels_out, d_clusters, d_result, d_scratch) that overlaps an input or another
+ * output.  Asynchronous on the handle's stream. */
+#define RPLGPU_CLUSTER_WORDS 80u
+typedef struct rplgpu_pose_clusters {
+  uint32_t nx, ny;     /* E20's nx, ny: the map's geometry */
+  float    xy_scale;   /* E17's quantum for the sums (1024) */
+  uint32_t flags;      /* bit 0: the heading axis WRAPS (bin T - 1 is next to bin 0); other bits 0 */
+} rplgpu_pose_clusters_t;
+/* 103 x 103 bins, xy_scale 1024, WRAP on: E20's default map and E17's default quantum */
+void rplgpu_default_pose_clusters(rplgpu_pose_clusters_t *s);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL, E20's limits on nx, ny, T and nx * ny * T, an
+ * xy_scale that is not finite or not > 0, or flags above 1.  The device path uses this function. */
+int32_t rplgpu_pose_clusters_check(const rplgpu_pose_clusters_t *s, uint32_t T);
+uint64_t rplgpu_cluster_scratch_words(uint32_t G, uint32_t P, uint32_t nx, uint32_t ny, uint32_t T);
+int32_t rplgpu_cluster_poses_dev(rplgpu_handle_t h, const rplgpu_pose_clusters_t *s, const float *d_poses,
+                                 uint64_t pose_stride, uint32_t poses_per_group, const uint32_t *d_weights,
+                                 uint64_t weight_stride, uint32_t G, uint32_t P, uint32_t T, const uint32_t *d_map,
+                                 uint64_t map_stride, const uint32_t *d_bins, uint64_t bin_stride,
+                                 uint32_t *d_labels_out, uint64_t label_stride, uint32_t *d_clusters,
+                                 uint64_t cluster_stride, uint32_t cluster_cap, uint32_t *d_result,
+                                 uint32_t *d_scratch);
+/* Host only (no handle, no device): the same rule in plain C++ for ONE group — the definition a reader can run (a
+ * flood fill over the occupied bins in ascending id, sums in __int128).  poses: 4 P floats; weights (optional): P
+ * words; map: ceil(NB / 32) words; bins: P words; labels_out (optional): P words; clusters_out (optional): 4 *
+ * cluster_cap words; result: 80 words.  RPLGPU_ERR_INVALID_ARG and nothing written for a spec the check refuses, a
+ * NULL poses / map / bins / result and P = 0 or above RPLGPU_MAX_POSES. */
+int32_t rplgpu_cluster_poses_host(const rplgpu_pose_clusters_t *s, const float *poses, uint32_t P,
+                                  const uint32_t *weights, uint32_t T, const uint32_t *map, const uint32_t *bins,
+                                  uint32_t *labels_out, uint32_t *clusters_out, uint32_t cluster_cap,
+                                  uint32_t result[80]);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp), arguments as rplgpu_cluster_poses_host.  Allocates
+ * its device buffers and scratch per call and returns when the results are in place: a door, not a hot path. */
+int32_t rplgpu_cluster_poses(rplgpu_handle_t h, const rplgpu_pose_clusters_t *s, const float *poses, uint32_t P,
+                             const uint32_t *weights, uint32_t T, const uint32_t *map, const uint32_t *bins,
+                             uint32_t *labels_out, uint32_t *clusters_out, uint32_t cluster_cap,
+                             uint32_t result[80]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@ MAX_OCC_STEPS = 8192     # RPLGPU_MAX_OCC_STEPS (include/rplgpu_msg.h)
 MAX_INFLATION_CELLS = 64  # RPLGPU_MAX_INFLATION_CELLS (include/rplgpu_msg.h)
 MAX_POSES = 1048576       # RPLGPU_MAX_POSES (include/rplgpu_msg.h)
 ESTIMATE_WORDS = 72       # RPLGPU_ESTIMATE_WORDS
+CLUSTER_WORDS = 80        # RPLGPU_CLUSTER_WORDS
 MAX_POSE_BINS = 67108864  # RPLGPU_MAX_POSE_BINS (include/rplgpu_msg.h)
 MAX_HEADING_BINS = 1024   # RPLGPU_MAX_HEADING_BINS (include/rplgpu_msg.h)
 
@@ -171,6 +172,12 @@ ABI_SYMBOLS = [
     "rplgpu_bin_poses_host",
     "rplgpu_bin_poses",
     "rplgpu_kld_samples",
+    "rplgpu_default_pose_clusters",
+    "rplgpu_pose_clusters_check",
+    "rplgpu_cluster_scratch_words",
+    "rplgpu_cluster_poses_dev",
+    "rplgpu_cluster_poses_host",
+    "rplgpu_cluster_poses",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -533,6 +540,32 @@ class PoseBins(C.Structure):
         return int(load_library().rplgpu_pose_bins_check(C.byref(self), T))
 
 
+class PoseClusters(C.Structure):
+    """Mirror of ``rplgpu_pose_clusters_t`` (E21: a binned pose list clustered on the device)."""
+
+    _fields_ = [
+        ("nx", C.c_uint32),
+        ("ny", C.c_uint32),
+        ("xy_scale", C.c_float),
+        ("flags", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "PoseClusters":
+        """The library's own defaults (``rplgpu_default_pose_clusters``), then the overrides."""
+        s = cls()
+        load_library().rplgpu_default_pose_clusters(C.byref(s))
+        for k, v in kw.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s
+
+    def check(self, T: int) -> int:
+        """``rplgpu_pose_clusters_check`` with T heading bins: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_pose_clusters_check(C.byref(self), T))
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -768,6 +801,15 @@ def load_library() -> C.CDLL:
     lib.rplgpu_bin_poses.argtypes = [vp, C.POINTER(PoseBins), vp, u32, vp, vp, u32, vp, vp, vp]
     lib.rplgpu_kld_samples.argtypes = [u32, C.c_double, C.c_double, u32, u32]
     lib.rplgpu_kld_samples.restype = C.c_uint32
+    lib.rplgpu_default_pose_clusters.argtypes = [C.POINTER(PoseClusters)]
+    lib.rplgpu_default_pose_clusters.restype = None
+    lib.rplgpu_pose_clusters_check.argtypes = [C.POINTER(PoseClusters), u32]
+    lib.rplgpu_cluster_scratch_words.argtypes = [u32, u32, u32, u32, u32]
+    lib.rplgpu_cluster_scratch_words.restype = C.c_uint64
+    lib.rplgpu_cluster_poses_dev.argtypes = [vp, C.POINTER(PoseClusters), vp, u64, u32, vp, u64, u32, u32, u32, vp, u64,
+                                             vp, u64, vp, u64, vp, u64, u32, vp, vp]
+    lib.rplgpu_cluster_poses_host.argtypes = [C.POINTER(PoseClusters), vp, u32, vp, u32, vp, vp, vp, vp, u32, vp]
+    lib.rplgpu_cluster_poses.argtypes = [vp, C.POINTER(PoseClusters), vp, u32, vp, u32, vp, vp, vp, vp, u32, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1318,6 +1360,34 @@ class RplGpu:
             self._h, C.byref(spec), poses.ctypes.data, len(poses), weights.ctypes.data if weights is not None else None,
             edges.ctypes.data, len(edges), bmap.ctypes.data, bins.ctypes.data, result.ctypes.data))
         return bmap, bins, result
+
+    def cluster_poses_dev(self, spec: "PoseClusters", d_poses: int, pose_stride: int, poses_per_group: int,
+                          d_weights: int, weight_stride: int, G: int, P: int, T: int, d_map: int, map_stride: int,
+                          d_bins: int, bin_stride: int, d_labels_out: int, label_stride: int, d_clusters: int,
+                          cluster_stride: int, cluster_cap: int, d_result: int, d_scratch: int):
+        """E21: per group the occupied bins of E20's bit map at d_map labelled by connected component, the P poses
+        (bin ids at d_bins, E20's ``d_bins_out``) given their cluster's label (d_labels_out, optional), the clusters
+        weighed (4-word rows at d_clusters, optional) and the heaviest reduced to E17's sums: 80 result words at
+        d_result + 80 g.  d_scratch: ``cluster_scratch_words(G, P, nx, ny, T)`` uint32 words."""
+        self._check(self._lib.rplgpu_cluster_poses_dev(
+            self._h, C.byref(spec), d_poses, pose_stride, poses_per_group, d_weights, weight_stride, G, P, T, d_map,
+            map_stride, d_bins, bin_stride, d_labels_out, label_stride, d_clusters, cluster_stride, cluster_cap,
+            d_result, d_scratch))
+
+    def cluster_poses(self, poses: np.ndarray, bmap: np.ndarray, bins: np.ndarray, T: int, weights: np.ndarray = None,
+                      spec: "PoseClusters" = None, cluster_cap: int = 0, clusters_in: np.ndarray = None):
+        """E21, one group, host buffers: poses (P, 4) float32, the map (ceil(NB / 32),) uint32, bins (P,) uint32,
+        weights (P,) uint32 or None -> ``(labels (P,) uint32, clusters (cluster_cap, 4) uint32, result (80,)
+        uint32)``; ``clusters_in`` is what the rows beyond N_c keep."""
+        poses, bmap, bins, weights, spec, table = _cluster_args(poses, bmap, bins, T, weights, spec, cluster_cap,
+                                                                clusters_in)
+        labels = np.zeros(len(poses), np.uint32)
+        result = np.zeros(CLUSTER_WORDS, np.uint32)
+        self._check(self._lib.rplgpu_cluster_poses(
+            self._h, C.byref(spec), poses.ctypes.data, len(poses), weights.ctypes.data if weights is not None else None,
+            T, bmap.ctypes.data, bins.ctypes.data, labels.ctypes.data, table.ctypes.data if cluster_cap else None,
+            cluster_cap, result.ctypes.data))
+        return labels, table, result
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -2025,3 +2095,48 @@ def bin_poses_host(poses, edges, weights=None, spec: PoseBins = None, map_in=Non
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_bin_poses_host")
     return bmap, bins[:len(poses)], result
+
+
+def _cluster_args(poses, bmap, bins, T, weights, spec, cluster_cap, clusters_in):
+    spec = PoseClusters.defaults() if spec is None else spec
+    poses = np.ascontiguousarray(poses, np.float32)
+    bins = np.ascontiguousarray(bins, np.uint32)
+    bmap = np.ascontiguousarray(bmap, np.uint32)
+    if poses.ndim != 2 or poses.shape[1] != 4:
+        raise TypeError("poses must be (P, 4) float32")
+    if bins.shape != (len(poses),):
+        raise TypeError("bins must be (P,) uint32")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.uint32)
+        if weights.shape != (len(poses),):
+            raise TypeError("weights must be (P,) uint32")
+    if spec.check(T) != OK:
+        raise RplGpuError(ERR_INVALID_ARG, "rplgpu_pose_clusters_check")
+    if bmap.shape != ((spec.nx * spec.ny * T + 31) // 32,):
+        raise TypeError("the map must hold ceil(nx * ny * T / 32) words")
+    table = np.zeros((cluster_cap, 4), np.uint32) if clusters_in is None else np.array(clusters_in, np.uint32)
+    if table.shape != (cluster_cap, 4):
+        raise TypeError("clusters_in must be (cluster_cap, 4) uint32")
+    return poses, bmap, bins, weights, spec, table
+
+
+def cluster_scratch_words(G: int, P: int, nx: int, ny: int, T: int) -> int:
+    """Host only: the uint32 words of scratch cluster_poses_dev needs; 0 for arguments the call refuses."""
+    return int(load_library().rplgpu_cluster_scratch_words(G, P, nx, ny, T))
+
+
+def cluster_poses_host(poses, bmap, bins, T: int, weights=None, spec: PoseClusters = None, cluster_cap: int = 0,
+                       clusters_in=None):
+    """Host only: E21's rule for one group by the library's own rplgpu_cluster_poses_host (no handle, no device);
+    arguments and results as ``RplGpu.cluster_poses``."""
+    poses, bmap, bins, weights, spec, table = _cluster_args(poses, bmap, bins, T, weights, spec, cluster_cap,
+                                                            clusters_in)
+    labels = np.zeros(max(len(poses), 1), np.uint32)
+    result = np.zeros(CLUSTER_WORDS, np.uint32)
+    rc = load_library().rplgpu_cluster_poses_host(
+        C.byref(spec), poses.ctypes.data, len(poses), weights.ctypes.data if weights is not None else None, T,
+        bmap.ctypes.data, bins.ctypes.data, labels.ctypes.data, table.ctypes.data if cluster_cap else None,
+        cluster_cap, result.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_cluster_poses_host")
+    return labels[:len(poses)], table, result

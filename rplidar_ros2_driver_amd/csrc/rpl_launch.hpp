@@ -417,4 +417,24 @@ hipError_t launch_bins(hipStream_t s, const BinsK &k, const float *poses, unsign
                        unsigned long long map_stride, uint32_t *bins_out, unsigned long long bin_stride,
                        uint32_t *result);
 
+// E21: a binned pose list clustered (rpl_clusters.hip, include/rplgpu_msg.h).  Nine launches on the stream: the map's
+// words indexed (popcounts and running counts), the block counts scanned, a thread per bin to start and then to link
+// the occupied bins' ranks in a parent array (agent-scope atomics only, the larger root hooked under the smaller), the
+// roots flattened and counted, a thread per pose for its label and its cluster's weight, one workgroup per group for
+// BEST, SECOND and the table rows, then E17's tile reduction and finish over the poses of BEST.  labels and clusters
+// may be null.  The scratch holds clusters_scratch_words(G, P, nx, ny, T) uint32 words (0 for arguments the call
+// refuses) and is 8-byte aligned.
+struct ClustersK {
+  uint32_t nx, ny;
+  float xy_scale;
+  uint32_t wrap;  // flags bit 0: heading bin T - 1 is next to bin 0
+};
+unsigned long long clusters_scratch_words(uint32_t G, uint32_t P, uint32_t nx, uint32_t ny, uint32_t T);
+hipError_t launch_clusters(hipStream_t s, const ClustersK &k, const float *poses, unsigned long long pose_stride,
+                           uint32_t poses_per_group, const uint32_t *weights, unsigned long long weight_stride,
+                           uint32_t G, uint32_t P, uint32_t T, const uint32_t *map, unsigned long long map_stride,
+                           const uint32_t *bins, unsigned long long bin_stride, uint32_t *labels,
+                           unsigned long long label_stride, uint32_t *clusters, unsigned long long cluster_stride,
+                           uint32_t cluster_cap, uint32_t *result, uint32_t *scratch);
+
 }  // namespace rpl

@@ -1,11 +1,11 @@
 // rplgpu_pose_stages.hip — the extern "C" entry points of the stages that work on pose lists
 // (include/rplgpu_msg.h): E15 scoring, E16 resampling, E17 the pose estimate, E18 motion noise, E19 seeding,
-// E20 occupied bins and the KLD sample count.
+// E20 occupied bins and the KLD sample count, E21 clusters of those bins.
 //
 // Host side only: argument checks, the launches, the host-buffer doors and the host twins of the integer and
 // float32 rules (this unit is built with -ffp-contract=off -fno-fast-math like every other: the twins' comments rely
-// on it); the kernels are in rpl_pose.hip, rpl_resample.hip, rpl_estimate.hip, rpl_motion.hip, rpl_seed.hip and
-// rpl_bins.hip.  The handle, the helpers of rplgpu_api.hip, the scan-stage prologue and the doors' per-call buffer
+// on it); the kernels are in rpl_pose.hip, rpl_resample.hip, rpl_estimate.hip, rpl_motion.hip, rpl_seed.hip,
+// rpl_bins.hip and rpl_clusters.hip.  The handle, the helpers of rplgpu_api.hip, the scan-stage prologue and the doors' per-call buffer
 // come from rpl_host.hpp.
 #include <hip/hip_runtime.h>
 
@@ -1151,6 +1151,299 @@ uint32_t rplgpu_kld_samples(uint32_t k, double epsilon, double z, uint32_t m_min
   if (!(n >= (double)m_min)) return m_min;  // (NaN too)
   if (n > (double)m_max) return m_max;
   return (uint32_t)n;
+}
+
+// ---- E21: a binned pose list clustered, the heaviest cluster summed (include/rplgpu_msg.h) ----------------------------
+
+void rplgpu_default_pose_clusters(rplgpu_pose_clusters_t *s) {
+  if (!s) return;
+  s->nx = 103;
+  s->ny = 103;
+  s->xy_scale = 1024.0f;
+  s->flags = 1;
+}
+
+int32_t rplgpu_pose_clusters_check(const rplgpu_pose_clusters_t *s, uint32_t T) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  if (s->nx == 0 || s->nx > 65536u || s->ny == 0 || s->ny > 65536u) return RPLGPU_ERR_INVALID_ARG;
+  if (T == 0 || T > RPLGPU_MAX_HEADING_BINS) return RPLGPU_ERR_INVALID_ARG;
+  if ((uint64_t)s->nx * s->ny * T > (uint64_t)RPLGPU_MAX_POSE_BINS) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(s->xy_scale) || !(s->xy_scale > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  if (s->flags > 1u) return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+uint64_t rplgpu_cluster_scratch_words(uint32_t G, uint32_t P, uint32_t nx, uint32_t ny, uint32_t T) {
+  return rpl::clusters_scratch_words(G, P, nx, ny, T);
+}
+
+int32_t rplgpu_cluster_poses_host(const rplgpu_pose_clusters_t *s, const float *poses, uint32_t P,
+                                  const uint32_t *weights, uint32_t T, const uint32_t *map, const uint32_t *bins,
+                                  uint32_t *labels_out, uint32_t *clusters_out, uint32_t cluster_cap,
+                                  uint32_t result[80]) {
+  if (rplgpu_pose_clusters_check(s, T) != RPLGPU_OK || !poses || !map || !bins || !result || P == 0 ||
+      P > RPLGPU_MAX_POSES)
+    return RPLGPU_ERR_INVALID_ARG;
+  const uint32_t nx = s->nx, ny = s->ny, nb = nx * ny * T, none = 0xFFFFFFFFu;
+  const bool wrap = (s->flags & 1u) != 0;
+  auto occupied = [&](uint32_t b) { return b < nb && ((map[b >> 5] >> (b & 31u)) & 1u) != 0; };
+  // the occupied bins in ascending id; a bin's place in that list is found by bisection
+  std::vector<uint32_t> ids;
+  for (uint32_t b = 0; b < nb; ++b)
+    if (occupied(b)) ids.push_back(b);
+  const uint32_t K = (uint32_t)ids.size();
+  std::memset(result, 0, 4u * RPLGPU_CLUSTER_WORDS);
+  result[1] = result[72] = none;
+  result[7] = K;
+  if (K > RPLGPU_MAX_POSES) {  // the BOUND rule
+    result[0] = 32u;
+    if (labels_out)
+      for (uint32_t i = 0; i < P; ++i) labels_out[i] = none;
+    return RPLGPU_OK;
+  }
+  auto place = [&](uint32_t b) { return (uint32_t)(std::lower_bound(ids.begin(), ids.end(), b) - ids.begin()); };
+  // a flood fill from every occupied bin not yet reached, in ascending id: the bin it starts from is the label, and
+  // the clusters are met in ascending label order
+  std::vector<uint32_t> cluster_of(K, none), label, stack;
+  for (uint32_t k0 = 0; k0 < K; ++k0) {
+    if (cluster_of[k0] != none) continue;
+    const uint32_t c = (uint32_t)label.size();
+    label.push_back(ids[k0]);
+    cluster_of[k0] = c;
+    stack.push_back(ids[k0]);
+    while (!stack.empty()) {
+      const uint32_t b = stack.back();
+      stack.pop_back();
+      const int64_t bx = b % nx, by = (b / nx) % ny, kt = b / nx / ny;
+      for (int dk = -1; dk <= 1; ++dk) {
+        int64_t k = kt + dk;
+        if (wrap) k = (k + T) % T;
+        if (k < 0 || k >= (int64_t)T) continue;
+        for (int dy = -1; dy <= 1; ++dy) {
+          for (int dx = -1; dx <= 1; ++dx) {
+            const int64_t x = bx + dx, y = by + dy;
+            if (x < 0 || x >= (int64_t)nx || y < 0 || y >= (int64_t)ny) continue;  // no wrap in x or y
+            const uint32_t q = (uint32_t)((k * ny + y) * nx + x);
+            if (q == b || !occupied(q)) continue;
+            const uint32_t at = place(q);
+            if (cluster_of[at] != none) continue;
+            cluster_of[at] = c;
+            stack.push_back(q);
+          }
+        }
+      }
+    }
+  }
+  const uint32_t nc = (uint32_t)label.size();
+  // the poses: labels, the clusters' weights and counts
+  std::vector<uint64_t> W(nc, 0);
+  std::vector<uint32_t> count(nc, 0), pose_cluster(P, none);
+  uint32_t stray = 0, unlabelled = 0, flags = 0;
+  for (uint32_t i = 0; i < P; ++i) {
+    uint32_t lab = none;
+    if (bins[i] == none) {
+      ++unlabelled;
+    } else if (!occupied(bins[i])) {
+      ++stray;
+      flags |= 16u;
+    } else {
+      const uint32_t c = cluster_of[place(bins[i])];
+      lab = label[c];
+      int32_t q[4];
+      if (estimate_quantise(poses + 4u * (size_t)i, s->xy_scale, q)) {
+        pose_cluster[i] = c;
+        W[c] += weights ? weights[i] : 1u;
+        count[c] += 1u;
+      } else {
+        flags |= 2u;
+      }
+    }
+    if (labels_out) labels_out[i] = lab;
+  }
+  // BEST and SECOND: the largest W, ties to the smaller label (the clusters are in ascending label order)
+  uint32_t best = none, second = none;
+  for (uint32_t c = 0; c < nc; ++c)
+    if (best == none || W[c] > W[best]) best = c;
+  for (uint32_t c = 0; c < nc; ++c)
+    if (c != best && (second == none || W[c] > W[second])) second = c;
+  if (clusters_out) {
+    for (uint32_t c = 0; c < nc && c < cluster_cap; ++c) {
+      clusters_out[4u * c] = label[c];
+      clusters_out[4u * c + 1u] = count[c];
+      clusters_out[4u * c + 2u] = (uint32_t)W[c];
+      clusters_out[4u * c + 3u] = (uint32_t)(W[c] >> 32);
+    }
+  }
+  __int128 sum[2][8] = {};
+  uint32_t n[2][2] = {{0, 0}, {0, 0}};
+  for (uint32_t i = 0; i < P; ++i) {
+    if (pose_cluster[i] == none) continue;
+    int32_t q[4];
+    estimate_quantise(poses + 4u * (size_t)i, s->xy_scale, q);
+    const int64_t X = q[0], Y = q[1], C = q[2], S = q[3];
+    const __int128 w = weights ? weights[i] : 1u;
+    const __int128 term[8] = {w, w * X, w * Y, w * C, w * S, w * (X * X), w * (X * Y), w * (Y * Y)};
+    for (int k = 0; k < (pose_cluster[i] == best ? 2 : 1); ++k) {
+      for (int m = 0; m < 8; ++m) sum[k][m] += term[m];
+      n[k][0] += 1u;
+      n[k][1] += w != 0 ? 1u : 0u;
+    }
+  }
+  result[0] = (nc == 0 ? 1u : 0u) | flags | (sum[0][0] == 0 ? 4u : 0u) | (sum[1][0] == 0 ? 8u : 0u);
+  result[1] = best != none ? label[best] : none;
+  result[2] = n[0][0];
+  result[3] = n[0][1];
+  result[4] = n[1][0];
+  result[5] = n[1][1];
+  result[6] = nc;
+  for (int k = 0; k < 2; ++k) {
+    for (int m = 0; m < 8; ++m) {
+      const unsigned __int128 v = (unsigned __int128)sum[k][m];
+      for (int j = 0; j < 4; ++j) result[8 + 32 * k + 4 * m + j] = (uint32_t)(v >> (32 * j));
+    }
+  }
+  if (second != none) {
+    result[72] = label[second];
+    result[73] = count[second];
+    result[74] = (uint32_t)W[second];
+    result[75] = (uint32_t)(W[second] >> 32);
+  }
+  result[76] = stray;
+  result[77] = unlabelled;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_cluster_poses_dev(rplgpu_handle_t h, const rplgpu_pose_clusters_t *s, const float *d_poses,
+                                 uint64_t pose_stride, uint32_t poses_per_group, const uint32_t *d_weights,
+                                 uint64_t weight_stride, uint32_t G, uint32_t P, uint32_t T, const uint32_t *d_map,
+                                 uint64_t map_stride, const uint32_t *d_bins, uint64_t bin_stride,
+                                 uint32_t *d_labels_out, uint64_t label_stride, uint32_t *d_clusters,
+                                 uint64_t cluster_stride, uint32_t cluster_cap, uint32_t *d_result,
+                                 uint32_t *d_scratch) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_clusters_check(s, T) != RPLGPU_OK) {
+    h->err = "rplgpu_cluster_poses_dev: the rplgpu_pose_clusters_t is missing or rplgpu_pose_clusters_check refuses it or T";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_cluster_poses_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_cluster_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_poses || !d_map || !d_bins || !d_result || !d_scratch || misaligned(d_poses, 15) || misaligned(d_map, 7) ||
+      misaligned(d_scratch, 7) || misaligned(d_weights, 3) || misaligned(d_bins, 3) || misaligned(d_labels_out, 3) ||
+      misaligned(d_clusters, 3) || misaligned(d_result, 3)) {
+    h->err = "rplgpu_cluster_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for d_poses, "
+             "8 for d_map and d_scratch, 4 otherwise)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (pose_stride < 4ull * P || (pose_stride & 3u) || (d_weights && weight_stride < P)) {
+    h->err = "rplgpu_cluster_poses_dev: pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint64_t words = ((uint64_t)s->nx * s->ny * T + 31u) >> 5;
+  if (map_stride < words || (map_stride & 1u)) {
+    h->err = "rplgpu_cluster_poses_dev: map_stride >= ceil(nx * ny * T / 32) and even is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const bool table = d_clusters && cluster_cap != 0;
+  if (bin_stride < P || (d_labels_out && label_stride < P) || (table && cluster_stride < 4ull * cluster_cap)) {
+    h->err = "rplgpu_cluster_poses_dev: bin_stride >= P, label_stride >= P and cluster_stride >= 4 cluster_cap are "
+             "required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  // no output may share a byte with an input or with another output
+  const uint64_t scratch_words = rplgpu_cluster_scratch_words(G, P, s->nx, s->ny, T);
+  struct Range {
+    const void *p;
+    uint64_t bytes;
+    bool out;
+  };
+  const Range ranges[] = {
+      {d_poses, 4ull * ((poses_per_group ? (uint64_t)(G - 1u) * pose_stride : 0ull) + 4ull * P), false},
+      {d_weights, d_weights ? 4ull * ((uint64_t)(G - 1u) * weight_stride + P) : 0ull, false},
+      {d_map, 4ull * ((uint64_t)(G - 1u) * map_stride + words), false},
+      {d_bins, 4ull * ((uint64_t)(G - 1u) * bin_stride + P), false},
+      {d_labels_out, d_labels_out ? 4ull * ((uint64_t)(G - 1u) * label_stride + P) : 0ull, true},
+      {d_clusters, table ? 4ull * ((uint64_t)(G - 1u) * cluster_stride + 4ull * cluster_cap) : 0ull, true},
+      {d_result, 4ull * RPLGPU_CLUSTER_WORDS * G, true},
+      {d_scratch, 4ull * scratch_words, true}};
+  for (const Range &a : ranges) {
+    for (const Range &b : ranges) {
+      if (&a < &b && (a.out || b.out) && a.bytes && b.bytes && ranges_overlap(a.p, a.bytes, b.p, b.bytes)) {
+        h->err = "rplgpu_cluster_poses_dev: an output overlaps an input or another output";
+        return RPLGPU_ERR_INVALID_ARG;
+      }
+    }
+  }
+  if (!device_readable(h, {{d_poses, "d_poses", true}, {d_map, "d_map", true}, {d_bins, "d_bins", true},
+                           {d_result, "d_result", true}, {d_scratch, "d_scratch", true},
+                           {d_weights, "d_weights", false}, {d_labels_out, "d_labels_out", false},
+                           {d_clusters, "d_clusters", false}}))
+    return RPLGPU_ERR_INVALID_ARG;
+  const rpl::ClustersK k{s->nx, s->ny, s->xy_scale, s->flags & 1u};
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_clusters(h->stream, k, d_poses, pose_stride, poses_per_group, d_weights, weight_stride, G, P,
+                                  T, d_map, map_stride, d_bins, bin_stride, d_labels_out, label_stride,
+                                  table ? d_clusters : nullptr, cluster_stride, table ? cluster_cap : 0u, d_result,
+                                  d_scratch));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_cluster_poses(rplgpu_handle_t h, const rplgpu_pose_clusters_t *s, const float *poses, uint32_t P,
+                             const uint32_t *weights, uint32_t T, const uint32_t *map, const uint32_t *bins,
+                             uint32_t *labels_out, uint32_t *clusters_out, uint32_t cluster_cap,
+                             uint32_t result[80]) {
+  if (!h || !poses || !map || !bins || !result) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_pose_clusters_check(s, T) != RPLGPU_OK) {
+    h->err = "rplgpu_cluster_poses: the rplgpu_pose_clusters_t is missing or rplgpu_pose_clusters_check refuses it or T";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES) {
+    h->err = "rplgpu_cluster_poses: P must be in 1 .. RPLGPU_MAX_POSES";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // result | map | weights | bins | labels | table | scratch | poses
+  const size_t words = ((size_t)s->nx * s->ny * T + 31u) >> 5, stride = (size_t)rplgpu_bin_map_words(s->nx, s->ny, T);
+  const bool table = clusters_out && cluster_cap != 0;
+  DoorBuffer buf(h, "rplgpu_cluster_poses");
+  const size_t o_res = buf.part(4u * RPLGPU_CLUSTER_WORDS), o_map = buf.part(4u * stride),
+               o_wt = buf.part_if(weights, 4u * (size_t)P), o_bins = buf.part(4u * (size_t)P),
+               o_lab = buf.part_if(labels_out, 4u * (size_t)P), o_tab = buf.part_if(table, 16u * (size_t)cluster_cap),
+               o_scr = buf.part(4u * (size_t)rplgpu_cluster_scratch_words(1, P, s->nx, s->ny, T)),
+               o_poses = buf.part(16u * (size_t)P);
+  uint32_t small[RPLGPU_CLUSTER_WORDS];
+  std::vector<uint32_t> lab_back(labels_out ? P : 0u), tab_back(table ? 4u * (size_t)cluster_cap : 0u);
+  const int32_t rc = buf.run([&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_poses), poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_map), map, 4u * words, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_bins), bins, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    if (weights) RPL_HIP(h, hipMemcpyAsync(buf.at(o_wt), weights, 4u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    if (table)  // the rows beyond N_c keep what the caller has there
+      RPL_HIP(h, hipMemcpyAsync(buf.at(o_tab), clusters_out, 16u * (size_t)cluster_cap, hipMemcpyHostToDevice, h->stream));
+    const int32_t irc = rplgpu_cluster_poses_dev(
+        h, s, buf.at<const float>(o_poses), 4ull * P, 0, buf.at<const uint32_t>(o_wt), P, 1, P, T,
+        buf.at<const uint32_t>(o_map), stride, buf.at<const uint32_t>(o_bins), P, buf.at<uint32_t>(o_lab), P,
+        buf.at<uint32_t>(o_tab), 4ull * cluster_cap, table ? cluster_cap : 0u, buf.at<uint32_t>(o_res),
+        buf.at<uint32_t>(o_scr));
+    if (irc) return irc;
+    if (labels_out)
+      RPL_HIP(h, hipMemcpyAsync(lab_back.data(), buf.at(o_lab), 4u * (size_t)P, hipMemcpyDeviceToHost, h->stream));
+    if (table)
+      RPL_HIP(h, hipMemcpyAsync(tab_back.data(), buf.at(o_tab), 16u * (size_t)cluster_cap, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, buf.at(o_res), sizeof(small), hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  });
+  if (rc) return rc;  // (no output changed)
+  if (labels_out) std::memcpy(labels_out, lab_back.data(), 4u * (size_t)P);
+  if (table) std::memcpy(clusters_out, tab_back.data(), 16u * (size_t)cluster_cap);
+  std::memcpy(result, small, sizeof(small));
+  return RPLGPU_OK;
 }
 
 }  // extern "C"

@@ -471,6 +471,44 @@ int main(int argc, char **argv) {
     }
     std::printf("bin poses: 64 poses in %u bins (%u .. %u), map %08x, next list %u poses\n", br.new_bins, br.min_bin,
                 br.max_bin, bmap[0], br.samples());
+    // E21: six poses in two bins of a 6 x 1 x 4 map that do not touch — four of weight 1 in bin 0, two of weight 5 in
+    // bin 4: two clusters, the heavier one (W = 10, label 4) has fewer poses and its mean is (2.25, 0.25, 0); against
+    // the library's own host-only twin word for word.
+    rplgpu_pose_clusters_t cspec;
+    rplgpu_default_pose_clusters(&cspec);
+    cspec.nx = 6;
+    cspec.ny = 1;
+    std::vector<float> cposes;
+    for (int k = 0; k < 6; ++k) {
+      const float pose[4] = {1.0f, 0.0f, k < 4 ? 0.25f : 2.25f, 0.25f};
+      cposes.insert(cposes.end(), pose, pose + 4);
+    }
+    const std::vector<uint32_t> cweights = {1, 1, 1, 1, 5, 5}, cmap = {0x11u}, cbins = {0, 0, 0, 0, 4, 4};
+    std::vector<rplgpu_host::ScanPath::Cluster> rows;
+    rplgpu_host::ScanPath::ClusterResult cr;
+    uint32_t cluster_twin[RPLGPU_CLUSTER_WORDS], rows_twin[8];
+    if (!path.cluster_poses(cspec, cposes, cweights, 4, cmap, cbins, 2, rows, cr)) {
+      std::fprintf(stderr, "cluster poses failed: %s\n", path.last_error().c_str());
+      return 29;
+    }
+    if (rplgpu_cluster_poses_host(&cspec, cposes.data(), 6, cweights.data(), 4, cmap.data(), cbins.data(), nullptr,
+                                  rows_twin, 2, cluster_twin) != RPLGPU_OK)
+      return 30;
+    const bool cluster_ok =
+        cr.clusters == 2 && cr.occupied_bins == 2 && cr.best_label == 4 && cr.best_poses == 2 && cr.second_label == 0 &&
+        cr.second_poses == 4 && cr.second_weight == 4 && cr.stray == 0 && cr.unlabelled == 0 && cr.flags == 0 &&
+        cr.flags == cluster_twin[0] && cr.best_label == cluster_twin[1] && cr.clusters == cluster_twin[6] &&
+        cr.best_valid && cr.whole_valid && cr.best[0] == 2.25 && cr.best[1] == 0.25 && cr.best[2] == 0.0 &&
+        cr.best[7] == 10.0 && cr.whole[7] == 14.0 && rows.size() == 2 && rows[0].label == rows_twin[0] &&
+        rows[0].label == 0 && rows[0].poses == 4 && rows[0].weight == 4 && rows[1].label == rows_twin[4] &&
+        rows[1].label == 4 && rows[1].poses == 2 && rows[1].weight == 10;
+    if (!cluster_ok) {
+      std::fprintf(stderr, "cluster poses: wrong answer (N_c %u, best %u with %u poses at (%.4f, %.4f), flags %u)\n",
+                   cr.clusters, cr.best_label, cr.best_poses, cr.best[0], cr.best[1], cr.flags);
+      return 30;
+    }
+    std::printf("cluster poses: %u clusters, the heaviest (label %u, %u poses, W %.0f) at (%.4f, %.4f, %.4f)\n",
+                cr.clusters, cr.best_label, cr.best_poses, cr.best[7], cr.best[0], cr.best[1], cr.best[2]);
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

@@ -38,6 +38,8 @@
 //         -> rplgpu_host::ScanPath::seed_poses(spec, grid, headings, noise, count, poses, result)  (E19)
 //         and the size of the next list from the bins the list occupies (AMCL's KLD sampling):
 //         -> rplgpu_host::ScanPath::bin_poses(spec, poses, weights, headings, map, result)  (E20)
+//         and the pose AMCL publishes, the mean of the heaviest cluster of those bins (pf_cluster_stats):
+//         -> rplgpu_host::ScanPath::cluster_poses(spec, poses, weights, headings, map, bins, max, clusters, result)  (E21)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -717,6 +719,73 @@ class ScanPath {
     result.min_bin = out[4];
     result.max_bin = out[5];
     result.none_counted = (out[7] & 1u) != 0;
+    return true;
+  }
+
+  // ext E21 (include/rplgpu_msg.h): the occupied bins of bin_poses' `map` clustered (26 neighbours, the heading axis
+  // wrapping with spec.flags bit 0), each pose given the cluster of its bin (`bins`: rplgpu_bin_poses' bin ids, one
+  // per pose) and the HEAVIEST cluster reduced to a pose — what AMCL publishes (pf_cluster_stats).  best is the mean
+  // over the heaviest cluster, whole the mean over every clustered pose; `clusters` receives up to max_clusters rows
+  // in ascending label order.
+  struct Cluster {
+    uint32_t label = 0;         // the cluster's smallest bin id
+    uint32_t poses = 0;
+    uint64_t weight = 0;
+  };
+  struct ClusterResult {
+    uint32_t clusters = 0;      // N_c
+    uint32_t occupied_bins = 0;  // K
+    uint32_t best_label = 0xFFFFFFFFu, second_label = 0xFFFFFFFFu;
+    uint32_t best_poses = 0, second_poses = 0;
+    uint64_t second_weight = 0;
+    uint32_t stray = 0, unlabelled = 0;
+    uint32_t flags = 0;         // result word 0
+    bool best_valid = false, whole_valid = false;  // W of the set is not 0
+    double best[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // rplgpu_estimate_pose's eight values for set 1
+    double whole[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // ... and for set 0
+  };
+  bool cluster_poses(const rplgpu_pose_clusters_t &spec, const std::vector<float> &poses,
+                     const std::vector<uint32_t> &weights, uint32_t headings, const std::vector<uint32_t> &map,
+                     const std::vector<uint32_t> &bins, uint32_t max_clusters, std::vector<Cluster> &clusters,
+                     ClusterResult &result) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    if (rplgpu_pose_clusters_check(&spec, headings) != RPLGPU_OK)
+      return fail("cluster_poses: rplgpu_pose_clusters_check refuses the spec or the number of heading bins");
+    const size_t count = poses.size() / 4;
+    if (count == 0 || count > RPLGPU_MAX_POSES || poses.size() != 4 * count)
+      return fail("cluster_poses: poses must hold 1 .. RPLGPU_MAX_POSES entries of four floats");
+    if (!weights.empty() && weights.size() != count) return fail("cluster_poses: one weight per pose, or none");
+    if (bins.size() != count) return fail("cluster_poses: one bin id per pose");
+    if (map.size() != (static_cast<size_t>(spec.nx) * spec.ny * headings + 31) / 32)
+      return fail("cluster_poses: the map must hold ceil(nx * ny * headings / 32) words");
+    std::vector<uint32_t> rows(4 * static_cast<size_t>(max_clusters), 0u);
+    uint32_t out[RPLGPU_CLUSTER_WORDS];
+    if (rplgpu_cluster_poses(h_, &spec, poses.data(), static_cast<uint32_t>(count),
+                             weights.empty() ? nullptr : weights.data(), headings, map.data(), bins.data(), nullptr,
+                             max_clusters ? rows.data() : nullptr, max_clusters, out) != RPLGPU_OK)
+      return note_error();
+    result = ClusterResult();
+    result.flags = out[0];
+    result.best_label = out[1];
+    result.best_poses = out[4];
+    result.clusters = out[6];
+    result.occupied_bins = out[7];
+    result.second_label = out[72];
+    result.second_poses = out[73];
+    result.second_weight = static_cast<uint64_t>(out[74]) | (static_cast<uint64_t>(out[75]) << 32);
+    result.stray = out[76];
+    result.unlabelled = out[77];
+    result.whole_valid = rplgpu_estimate_pose(out, spec.xy_scale, 0, result.whole) == RPLGPU_OK;
+    result.best_valid = rplgpu_estimate_pose(out, spec.xy_scale, 1, result.best) == RPLGPU_OK;
+    clusters.clear();
+    for (uint32_t c = 0; c < max_clusters && c < result.clusters; ++c) {
+      Cluster row;
+      row.label = rows[4 * c];
+      row.poses = rows[4 * c + 1];
+      row.weight = static_cast<uint64_t>(rows[4 * c + 2]) | (static_cast<uint64_t>(rows[4 * c + 3]) << 32);
+      clusters.push_back(row);
+    }
     return true;
   }
 
