@@ -1312,6 +1312,138 @@ int32_t rplgpu_cluster_poses(rplgpu_handle_t h, const rplgpu_pose_clusters_t *s,
                              uint32_t *labels_out, uint32_t *clusters_out, uint32_t cluster_cap,
                              uint32_t result[80]);
 
+/* ---- E22: a beam fan cast from every pose of a list into a grid (row 4; the beam model's expected ranges) ----
+ * E15 weighs a pose by the field bytes under the scan's end points and never asks what lies between the pose and a
+ * return.  The second sensor model of the localisation readers (AMCL's beam model, map_calc_range) does: from every
+ * pose a ray runs along every beam through the map to the first obstacle, the EXPECTED range, which is then compared
+ * with the measured one.  The same cast makes a simulated LaserScan from E14's map and checks a pose hypothesis for
+ * visibility.  The grid is E11 / E12 / E14's int8 grid, the walk is E11's, the list is E15 / E16 / E19's, the
+ * measured scan is E9's (or E10's) merged LaserScan in the base frame, and the weights and result words come out in
+ * E15's layout, so E16, E17, E20 and E21 take them unchanged and seed -> cast -> estimate -> resample -> cast queues
+ * on one stream without a read.  Nothing in the reference casts rays, so these rules ARE the definition (parity
+ * unpinned, as E5-E21).  After two fixed float32 compositions per ray everything is integers: the result depends on
+ * no order.
+ *
+ * BEAM TABLE: A entries (cb, sb), 2 floats each, at d_beams (8-byte aligned), 1 <= A <= RPLGPU_MAX_MERGE_BEAMS,
+ * shared by all groups, only read; the device evaluates no trigonometric function.  P * A <= 2^28 (every count of a
+ * group fits 32 bits).
+ * RAY (q, a) of group g, q in [0, P), a in [0, A): pose (c, s, tx, ty) by E15's addressing (d_poses, pose_stride in
+ * floats, >= 4 P and a multiple of 4, poses_per_group, 16-byte aligned).  Float32, no FMA, each product rounded, then
+ * the difference or sum:
+ *   dc = c*cb - s*sb;   ds = s*cb + c*sb                                               (E16's composition)
+ *   Rm = (float)N * resolution;   ex = tx + dc*Rm;   ey = ty + ds*Rm                   (N = max_steps)
+ *   (x0, y0) = the E11 CELL of (tx, ty);  (x1, y1) = the E11 CELL of (ex, ey): same rule, same IEEE divides.
+ *   A ray whose start or end has no cell is DROPPED: its range word is 0xFFFFFFFF.
+ * Any (c, s) is defined (a scale, the zero matrix, NaN: dropped).
+ * THE WALK is E11's Bresenham, verbatim: ax = |x1 - x0|, ay = |y1 - y0|, stepx = sign(x1 - x0), stepy =
+ * sign(y1 - y0), err = ax - ay; visit n = 0 is the cell (x0, y0).  AT EVERY VISIT of a cell (x, y), in this order:
+ *   1. (x, y) outside [0, width) x [0, height):                    stop, kind LEFT (2)
+ *   2. (int8)byte >= hit_lo:                                        stop, kind HIT (0)
+ *   3. byte < 0 and unknown_stops:                                  stop, kind UNKNOWN (1)
+ *   4. (x, y) == (x1, y1) or n == N:                                stop, kind NONE (3)
+ *   5. otherwise e2 = 2 err, and with this one e2
+ *        if (e2 > -ay) { err -= ay; x += stepx; }   if (e2 < ax) { err += ax; y += stepy; }   and n + 1.
+ * N bounds every walk.  byte = d_grid[g_f * grid_stride + y * width + x], g_f = g when grid_per_group is not 0, else
+ * 0; grid_stride >= width * height and a multiple of 4, d_grid 4-byte aligned (E15's field rules); only read.
+ * RANGE WORD = D2 | kind << 28 with D2 = (x - x0)^2 + (y - y0)^2 of the stopping cell (<= 2^27: |x - x0| <= n <= N
+ * <= 8192); bits 30 and 31 are 0, so no range word equals the dropped ray's.  It goes to
+ * d_ranges_out[g * range_stride + q * A + a] (optional; range_stride in words, >= P * A); words at and beyond P * A
+ * of a group are never changed.
+ * WEIGHT, only with d_measured set: the measured range of beam a is
+ *   z = d_measured[g * meas_stride + meas_first + a * meas_step]                       (E9's ranges; +inf: no return)
+ * with meas_first + (A - 1) * meas_step < meas_stride.  z NaN (a beam E10 removed): the beam is SKIPPED for every
+ * pose.  A dropped ray is skipped for its pose.  Otherwise, float32:
+ *   mz = z / resolution (IEEE divide; +inf stays +inf)
+ *   de = sqrtf((float)D2), correctly rounded, for kinds 0 - 2;  +inf for NONE
+ *   both +inf:  t = d_table[2K + 1]                                                    (K = table_half)
+ *   otherwise   d = mz - de;   t = d_table[K + (int)max(-K, min(K, floorf(d)))]
+ * d_table: 2K + 2 bytes, uint8, the caller's, shared by all groups, only read: entry K + j is the term of a return
+ * j cells (rounded down) behind the expected one, entries 0 and 2K take everything beyond, entry 2K + 1 is "no
+ * return expected, none measured".  Gaussian hit, short, max and random are mixed by the caller, in cells.
+ *   d_weights[g * weight_stride + q] = the sum of t over the pose's beams, uint32 (255 * 16384 < 2^32);
+ *   weight_stride >= P; words at and beyond P of a group are never changed.
+ * RESULT, only with d_measured set: eight words per group at d_result + 8 g, E15's exactly (largest weight, the
+ * smallest q that has it, how many have it, the weights of 0, word 4, the weight of pose 0, the sum low and high);
+ * word 4 = the beams whose z is not NaN.  Without d_measured, d_weights and d_result are ignored and never written.
+ * CAST COUNTS: eight words per group at d_cast + 8 g (required, 4-byte aligned):
+ *   0 - 3   the rays of kind HIT / UNKNOWN / LEFT / NONE
+ *   4       the dropped rays                                       (words 0 + 1 + 2 + 3 + 4 = P * A)
+ *   5       the largest D2 among the HIT rays (0 if none)
+ *   6, 7    the sum over all rays of n at the stop (the cell steps walked), low and high word
+ * At least one of d_ranges_out / d_measured must be set.
+ * IDENTITIES that follow from the rules:
+ *   (1) pose (c, s, tx, ty) with beam (1, 0) has the range word of pose (1, 0, tx, ty) with beam (c, s): c*1 - s*0
+ *       and 1*c - 0*s both round to c (for finite c, s);
+ *   (2) the weights recomputed on the host from the returned range words, the measured ranges and the table by the
+ *       WEIGHT rule equal the device's;
+ *   (3) a list cast in two pieces (pointer offsets into d_poses, d_ranges_out, d_weights) has the words and weights
+ *       of the list cast at once, and the counts of the pieces add up (word 5: the larger);
+ *   (4) the result words are what E15's RESULT rule gives on the returned weights.
+ * RPLGPU_ERR_INVALID_ARG, no output changed and nothing queued, for a spec the check refuses, G = 0 or above 65535,
+ * P = 0 or above RPLGPU_MAX_POSES, A = 0 or above RPLGPU_MAX_MERGE_BEAMS, P * A above 2^28, a missing d_poses /
+ * d_beams / d_grid / d_cast, neither d_ranges_out nor d_measured, d_measured without d_table / d_weights / d_result,
+ * a misaligned pointer (16 bytes: d_poses; 8: d_beams; 4: d_grid, d_measured, d_ranges_out, d_weights, d_result,
+ * d_cast), a pose_stride below 4 P or no multiple of 4, a grid_stride below width * height or no multiple of 4, a
+ * range_stride below P * A with d_ranges_out set, and with d_measured set a weight_stride below P or
+ * meas_first + (A - 1) * meas_step >= meas_stride.  Asynchronous on the handle's stream; no scratch. */
+#define RPLGPU_CAST_HIT     0u
+#define RPLGPU_CAST_UNKNOWN 1u
+#define RPLGPU_CAST_LEFT    2u
+#define RPLGPU_CAST_NONE    3u
+#define RPLGPU_CAST_DROPPED 0xFFFFFFFFu
+#define RPLGPU_MAX_CAST_TABLE_HALF 4096u
+#define RPLGPU_MAX_CAST_RAYS 268435456u
+typedef struct rplgpu_range_cast {
+  float    origin_x, origin_y, resolution;  /* the grid: as rplgpu_pose_score_t */
+  uint32_t width, height;                   /* 1 .. RPLGPU_MAX_OCC_DIM */
+  uint32_t max_steps;                       /* N, 1 .. RPLGPU_MAX_OCC_STEPS */
+  int32_t  hit_lo;                          /* 1 .. 127: a cell stops a ray as HIT iff (int8)byte >= hit_lo */
+  uint32_t unknown_stops;                   /* 0 / 1: a negative byte stops a ray as UNKNOWN */
+  uint32_t table_half;                      /* K, 0 .. RPLGPU_MAX_CAST_TABLE_HALF */
+} rplgpu_range_cast_t;
+/* E11's default grid (0.05 m, 1024 x 1024 cells, origin (-25.6, -25.6)), N = 240 (12 m), hit_lo 100,
+ * unknown_stops 1 (AMCL's rule), K = 40 */
+void rplgpu_default_range_cast(rplgpu_range_cast_t *s);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL, a value that is not finite, resolution <= 0, a
+ * dimension of 0 or above RPLGPU_MAX_OCC_DIM, max_steps of 0 or above RPLGPU_MAX_OCC_STEPS, hit_lo outside
+ * [1, 127], unknown_stops above 1 or table_half above RPLGPU_MAX_CAST_TABLE_HALF.  The device path uses this
+ * function. */
+int32_t rplgpu_range_cast_check(const rplgpu_range_cast_t *s);
+/* Host only: the centre directions of E9's beams k = first + a * step, a in [0, A), as cs[2a], cs[2a + 1] =
+ * ((float)cos(phi), (float)sin(phi)), phi = (double)angle_min + ((double)k + 0.5) * (double)inc with inc from
+ * rplgpu_scan_merge_edges, taken in fp64 and rounded once.  With first and step as meas_first and meas_step the
+ * table lines up with the merged scan's ranges.  RPLGPU_ERR_INVALID_ARG and nothing written for a NULL cs, a spec
+ * rplgpu_scan_merge_edges refuses, A = 0 or above RPLGPU_MAX_MERGE_BEAMS, or first + (A - 1) * step >= m->count.  A
+ * convenience, NOT part of the byte-exact contract, like rplgpu_seed_headings. */
+int32_t rplgpu_cast_beams(const rplgpu_scan_merge_t *m, uint32_t first, uint32_t step, uint32_t A, float *cs);
+/* Host only: a range word in metres, sqrt((double)D2) * (double)resolution for kinds 0 - 2, +inf for NONE, NaN for
+ * a dropped ray. */
+double rplgpu_cast_range_m(uint32_t word, float resolution);
+int32_t rplgpu_cast_ranges_dev(rplgpu_handle_t h, const rplgpu_range_cast_t *s, const float *d_poses,
+                               uint64_t pose_stride, uint32_t poses_per_group, uint32_t G, uint32_t P,
+                               const float *d_beams, uint32_t A, const int8_t *d_grid, uint64_t grid_stride,
+                               uint32_t grid_per_group, const float *d_measured, uint64_t meas_stride,
+                               uint32_t meas_first, uint32_t meas_step, const uint8_t *d_table,
+                               uint32_t *d_ranges_out, uint64_t range_stride, uint32_t *d_weights,
+                               uint64_t weight_stride, uint32_t *d_result, uint32_t *d_cast);
+/* Host only (no handle, no device): the same rule in plain C++ for ONE group — the definition a reader can run.
+ * poses: 4 P floats; beams: 2 A floats; grid: width * height bytes; measured (optional): meas_count floats, which
+ * stand for meas_stride; table: 2K + 2 bytes, weights_out: P words and result: 8 words, all three required with
+ * measured and ignored without it; ranges_out (optional): P * A words; cast: 8 words.  RPLGPU_ERR_INVALID_ARG and
+ * nothing written for a spec the check refuses, a NULL poses / beams / grid / cast, neither ranges_out nor
+ * measured, P = 0 or above RPLGPU_MAX_POSES, A = 0 or above RPLGPU_MAX_MERGE_BEAMS, P * A above 2^28 and
+ * meas_first + (A - 1) * meas_step >= meas_count. */
+int32_t rplgpu_cast_ranges_host(const rplgpu_range_cast_t *s, const float *poses, uint32_t P, const float *beams,
+                                uint32_t A, const int8_t *grid, const float *measured, uint32_t meas_count,
+                                uint32_t meas_first, uint32_t meas_step, const uint8_t *table, uint32_t *ranges_out,
+                                uint32_t *weights_out, uint32_t result[8], uint32_t cast[8]);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp), arguments as rplgpu_cast_ranges_host.  Allocates
+ * its device buffers per call and returns when the results are in place: a door, not a hot path. */
+int32_t rplgpu_cast_ranges(rplgpu_handle_t h, const rplgpu_range_cast_t *s, const float *poses, uint32_t P,
+                           const float *beams, uint32_t A, const int8_t *grid, const float *measured,
+                           uint32_t meas_count, uint32_t meas_first, uint32_t meas_step, const uint8_t *table,
+                           uint32_t *ranges_out, uint32_t *weights_out, uint32_t result[8], uint32_t cast[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,13 @@ ABI_SYMBOLS = [
     "rplgpu_cluster_poses_dev",
     "rplgpu_cluster_poses_host",
     "rplgpu_cluster_poses",
+    "rplgpu_default_range_cast",
+    "rplgpu_range_cast_check",
+    "rplgpu_cast_beams",
+    "rplgpu_cast_range_m",
+    "rplgpu_cast_ranges_dev",
+    "rplgpu_cast_ranges_host",
+    "rplgpu_cast_ranges",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -566,6 +573,37 @@ class PoseClusters(C.Structure):
         return int(load_library().rplgpu_pose_clusters_check(C.byref(self), T))
 
 
+class RangeCast(C.Structure):
+    """Mirror of ``rplgpu_range_cast_t`` (E22: a beam fan cast from every pose of a list into a grid)."""
+
+    _fields_ = [
+        ("origin_x", C.c_float),
+        ("origin_y", C.c_float),
+        ("resolution", C.c_float),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("max_steps", C.c_uint32),
+        ("hit_lo", C.c_int32),
+        ("unknown_stops", C.c_uint32),
+        ("table_half", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "RangeCast":
+        """The library's own defaults (``rplgpu_default_range_cast``), then the overrides."""
+        s = cls()
+        load_library().rplgpu_default_range_cast(C.byref(s))
+        for k, v in kw.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s
+
+    def check(self) -> int:
+        """``rplgpu_range_cast_check``: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_range_cast_check(C.byref(self)))
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -810,6 +848,18 @@ def load_library() -> C.CDLL:
                                              vp, u64, vp, u64, vp, u64, u32, vp, vp]
     lib.rplgpu_cluster_poses_host.argtypes = [C.POINTER(PoseClusters), vp, u32, vp, u32, vp, vp, vp, vp, u32, vp]
     lib.rplgpu_cluster_poses.argtypes = [vp, C.POINTER(PoseClusters), vp, u32, vp, u32, vp, vp, vp, vp, u32, vp]
+    lib.rplgpu_default_range_cast.argtypes = [C.POINTER(RangeCast)]
+    lib.rplgpu_default_range_cast.restype = None
+    lib.rplgpu_range_cast_check.argtypes = [C.POINTER(RangeCast)]
+    lib.rplgpu_cast_beams.argtypes = [C.POINTER(ScanMerge), u32, u32, u32, vp]
+    lib.rplgpu_cast_range_m.argtypes = [u32, C.c_float]
+    lib.rplgpu_cast_range_m.restype = C.c_double
+    lib.rplgpu_cast_ranges_dev.argtypes = [vp, C.POINTER(RangeCast), vp, u64, u32, u32, u32, vp, u32, vp, u64, u32, vp,
+                                           u64, u32, u32, vp, vp, u64, vp, u64, vp, vp]
+    lib.rplgpu_cast_ranges_host.argtypes = [C.POINTER(RangeCast), vp, u32, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp,
+                                            vp, vp]
+    lib.rplgpu_cast_ranges.argtypes = [vp, C.POINTER(RangeCast), vp, u32, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp,
+                                       vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1388,6 +1438,40 @@ class RplGpu:
             T, bmap.ctypes.data, bins.ctypes.data, labels.ctypes.data, table.ctypes.data if cluster_cap else None,
             cluster_cap, result.ctypes.data))
         return labels, table, result
+
+    def cast_ranges_dev(self, spec: "RangeCast", d_poses: int, pose_stride: int, poses_per_group: int, G: int, P: int,
+                        d_beams: int, A: int, d_grid: int, grid_stride: int, grid_per_group: int, d_measured: int,
+                        meas_stride: int, meas_first: int, meas_step: int, d_table: int, d_ranges_out: int,
+                        range_stride: int, d_weights: int, weight_stride: int, d_result: int, d_cast: int):
+        """E22: per group a ray from each of the P poses at d_poses (E15 / E16 / E19's layout) along each of the A
+        beams (cb, sb) at d_beams through the int8 grid at d_grid + g * grid_stride by E11's walk; the range words
+        ``D2 | kind << 28`` at d_ranges_out + g * range_stride + q * A + a (optional), eight cast counts at d_cast +
+        8 g.  With d_measured (the merged scan's ranges, beam a at meas_first + a * meas_step) every ray is compared
+        through the 2K + 2 bytes at d_table and summed into E15's weights at d_weights and result words at d_result."""
+        self._check(self._lib.rplgpu_cast_ranges_dev(
+            self._h, C.byref(spec), d_poses, pose_stride, poses_per_group, G, P, d_beams, A, d_grid, grid_stride,
+            grid_per_group, d_measured, meas_stride, meas_first, meas_step, d_table, d_ranges_out, range_stride,
+            d_weights, weight_stride, d_result, d_cast))
+
+    def cast_ranges(self, poses: np.ndarray, beams: np.ndarray, grid: np.ndarray, spec: "RangeCast" = None,
+                    measured: np.ndarray = None, table: np.ndarray = None, meas_first: int = 0, meas_step: int = 1,
+                    want_ranges: bool = True):
+        """E22, one group, host buffers: poses (P, 4) float32, beams (A, 2) float32, grid (height, width) int8,
+        measured (n,) float32 and table (2K + 2,) uint8 or both None -> ``(ranges (P, A) uint32 or None, weights (P,)
+        uint32 or None, result (8,) uint32 or None, cast (8,) uint32)``."""
+        poses, beams, grid, spec, measured, table = _cast_args(poses, beams, grid, spec, measured, table)
+        P, A = len(poses), len(beams)
+        ranges = np.zeros((P, A), np.uint32) if want_ranges else None
+        weights = np.zeros(P, np.uint32) if measured is not None else None
+        result = np.zeros(8, np.uint32) if measured is not None else None
+        cast = np.zeros(8, np.uint32)
+        self._check(self._lib.rplgpu_cast_ranges(
+            self._h, C.byref(spec), poses.ctypes.data, P, beams.ctypes.data, A, grid.ctypes.data,
+            measured.ctypes.data if measured is not None else None, len(measured) if measured is not None else 0,
+            meas_first, meas_step, table.ctypes.data if table is not None else None,
+            ranges.ctypes.data if want_ranges else None, weights.ctypes.data if weights is not None else None,
+            result.ctypes.data if result is not None else None, cast.ctypes.data))
+        return ranges, weights, result, cast
 
     def filter_laserscan_batch_dev(self, d_ranges: int, d_intens: int, n_stride: int, d_beam_count: int,
                                    B: int, params: Params, flt: ScanFilter, d_ranges_out: int,
@@ -2140,3 +2224,68 @@ def cluster_poses_host(poses, bmap, bins, T: int, weights=None, spec: PoseCluste
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_cluster_poses_host")
     return labels[:len(poses)], table, result
+
+
+CAST_HIT, CAST_UNKNOWN, CAST_LEFT, CAST_NONE = 0, 1, 2, 3
+CAST_DROPPED = 0xFFFFFFFF
+MAX_CAST_RAYS = 1 << 28
+
+
+def _cast_args(poses, beams, grid, spec, measured, table):
+    spec = RangeCast.defaults() if spec is None else spec
+    poses = np.ascontiguousarray(poses, np.float32)
+    beams = np.ascontiguousarray(beams, np.float32)
+    grid = np.ascontiguousarray(grid, np.int8)
+    if poses.ndim != 2 or poses.shape[1] != 4:
+        raise TypeError("poses must be (P, 4) float32")
+    if beams.ndim != 2 or beams.shape[1] != 2:
+        raise TypeError("beams must be (A, 2) float32")
+    if spec.check() != OK:
+        raise RplGpuError(ERR_INVALID_ARG, "rplgpu_range_cast_check")
+    if grid.shape != (spec.height, spec.width):
+        raise TypeError("grid must be (height, width) int8")
+    if (measured is None) != (table is None):
+        raise TypeError("measured and table come together")
+    if measured is not None:
+        measured = np.ascontiguousarray(measured, np.float32)
+        table = np.ascontiguousarray(table, np.uint8)
+        if measured.ndim != 1 or table.shape != (2 * spec.table_half + 2,):
+            raise TypeError("measured must be (n,) float32 and table (2 * table_half + 2,) uint8")
+    return poses, beams, grid, spec, measured, table
+
+
+def cast_beams(merge: ScanMerge, first: int, step: int, A: int) -> np.ndarray:
+    """Host only: the centre directions (cos, sin) of E9's beams first + a * step as (A, 2) float32, by the library's
+    own rplgpu_cast_beams."""
+    out = np.zeros((max(A, 1), 2), np.float32)
+    rc = load_library().rplgpu_cast_beams(C.byref(merge), first, step, A, out.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_cast_beams")
+    return out[:A]
+
+
+def cast_range_m(word: int, resolution: float) -> float:
+    """Host only: a range word in metres (+inf for NONE, NaN for a dropped ray), rplgpu_cast_range_m."""
+    return float(load_library().rplgpu_cast_range_m(int(word) & 0xFFFFFFFF, resolution))
+
+
+def cast_ranges_host(poses, beams, grid, spec: RangeCast = None, measured=None, table=None, meas_first: int = 0,
+                     meas_step: int = 1, want_ranges: bool = True):
+    """Host only: E22's rule for one group by the library's own rplgpu_cast_ranges_host (no handle, no device);
+    arguments and results as ``RplGpu.cast_ranges``."""
+    poses, beams, grid, spec, measured, table = _cast_args(poses, beams, grid, spec, measured, table)
+    P, A = len(poses), len(beams)
+    ok = 0 < P and 0 < A and P * A <= MAX_CAST_RAYS
+    ranges = np.zeros((P, A) if ok else (1, 1), np.uint32) if want_ranges else None
+    weights = np.zeros(max(P, 1), np.uint32) if measured is not None else None
+    result = np.zeros(8, np.uint32) if measured is not None else None
+    cast = np.zeros(8, np.uint32)
+    rc = load_library().rplgpu_cast_ranges_host(
+        C.byref(spec), poses.ctypes.data, P, beams.ctypes.data, A, grid.ctypes.data,
+        measured.ctypes.data if measured is not None else None, len(measured) if measured is not None else 0,
+        meas_first, meas_step, table.ctypes.data if table is not None else None,
+        ranges.ctypes.data if want_ranges else None, weights.ctypes.data if weights is not None else None,
+        result.ctypes.data if result is not None else None, cast.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_cast_ranges_host")
+    return ranges, (weights[:P] if weights is not None else None), result, cast

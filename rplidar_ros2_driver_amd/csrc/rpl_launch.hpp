@@ -437,4 +437,25 @@ hipError_t launch_clusters(hipStream_t s, const ClustersK &k, const float *poses
                            unsigned long long label_stride, uint32_t *clusters, unsigned long long cluster_stride,
                            uint32_t cluster_cap, uint32_t *result, uint32_t *scratch);
 
+// E22: a beam fan cast from every pose of a list into a grid (rpl_cast.hip, include/rplgpu_msg.h).  Two launches on
+// the stream — the cast words of every group started (and result word 4, the measured beams that are not NaN), then
+// one thread per ray: the float32 set-up of the header, E11's walk with one grid byte per visit, the range word, the
+// beam's table term added to its pose's weight in LDS, the tile's counts by ballots and integer atomics — between
+// E15's launch_pose_prepare and launch_pose_best when `measured` is set.  ranges may be null, or measured (with it
+// table, weights and result), not both.  No scratch.
+struct CastK {  // a checked rplgpu_range_cast_t
+  float origin_x, origin_y, resolution;
+  uint32_t width, height;
+  uint32_t max_steps;
+  int32_t hit_lo;
+  uint32_t unknown_stops;
+  uint32_t table_half;
+};
+hipError_t launch_cast(hipStream_t s, const CastK &k, const float *poses, unsigned long long pose_stride,
+                       uint32_t poses_per_group, uint32_t G, uint32_t P, const float *beams, uint32_t A,
+                       const int8_t *grid, unsigned long long grid_stride, uint32_t grid_per_group,
+                       const float *measured, unsigned long long meas_stride, uint32_t meas_first, uint32_t meas_step,
+                       const uint8_t *table, uint32_t *ranges, unsigned long long range_stride, uint32_t *weights,
+                       unsigned long long weight_stride, uint32_t *result, uint32_t *cast);
+
 }  // namespace rpl

@@ -1,11 +1,11 @@
 // rplgpu_pose_stages.hip — the extern "C" entry points of the stages that work on pose lists
 // (include/rplgpu_msg.h): E15 scoring, E16 resampling, E17 the pose estimate, E18 motion noise, E19 seeding,
-// E20 occupied bins and the KLD sample count, E21 clusters of those bins.
+// E20 occupied bins and the KLD sample count, E21 clusters of those bins, E22 the beam fan cast into a grid.
 //
 // Host side only: argument checks, the launches, the host-buffer doors and the host twins of the integer and
 // float32 rules (this unit is built with -ffp-contract=off -fno-fast-math like every other: the twins' comments rely
 // on it); the kernels are in rpl_pose.hip, rpl_resample.hip, rpl_estimate.hip, rpl_motion.hip, rpl_seed.hip,
-// rpl_bins.hip and rpl_clusters.hip.  The handle, the helpers of rplgpu_api.hip, the scan-stage prologue and the doors' per-call buffer
+// rpl_bins.hip, rpl_clusters.hip and rpl_cast.hip.  The handle, the helpers of rplgpu_api.hip, the scan-stage prologue and the doors' per-call buffer
 // come from rpl_host.hpp.
 #include <hip/hip_runtime.h>
 
@@ -1443,6 +1443,331 @@ int32_t rplgpu_cluster_poses(rplgpu_handle_t h, const rplgpu_pose_clusters_t *s,
   if (labels_out) std::memcpy(labels_out, lab_back.data(), 4u * (size_t)P);
   if (table) std::memcpy(clusters_out, tab_back.data(), 16u * (size_t)cluster_cap);
   std::memcpy(result, small, sizeof(small));
+  return RPLGPU_OK;
+}
+
+// ---- E22: a beam fan cast from every pose of a list into a grid (include/rplgpu_msg.h) --------------------------------
+
+void rplgpu_default_range_cast(rplgpu_range_cast_t *s) {
+  if (!s) return;
+  s->origin_x = -25.6f;
+  s->origin_y = -25.6f;
+  s->resolution = 0.05f;
+  s->width = 1024;
+  s->height = 1024;
+  s->max_steps = 240;
+  s->hit_lo = 100;
+  s->unknown_stops = 1;
+  s->table_half = 40;
+}
+
+int32_t rplgpu_range_cast_check(const rplgpu_range_cast_t *s) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  if (!std::isfinite(s->origin_x) || !std::isfinite(s->origin_y) || !std::isfinite(s->resolution))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (!(s->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
+  if (s->width == 0 || s->width > RPLGPU_MAX_OCC_DIM || s->height == 0 || s->height > RPLGPU_MAX_OCC_DIM)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (s->max_steps == 0 || s->max_steps > RPLGPU_MAX_OCC_STEPS) return RPLGPU_ERR_INVALID_ARG;
+  if (s->hit_lo < 1 || s->hit_lo > 127 || s->unknown_stops > 1u || s->table_half > RPLGPU_MAX_CAST_TABLE_HALF)
+    return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_cast_beams(const rplgpu_scan_merge_t *m, uint32_t first, uint32_t step, uint32_t A, float *cs) {
+  float inc = 0.0f;
+  if (!cs || !m || A == 0 || A > RPLGPU_MAX_MERGE_BEAMS || rplgpu_scan_merge_edges(m, nullptr, &inc) != RPLGPU_OK ||
+      (uint64_t)first + (uint64_t)(A - 1u) * step >= m->count)
+    return RPLGPU_ERR_INVALID_ARG;
+  for (uint32_t a = 0; a < A; ++a) {
+    const double k = (double)(first + a * step);
+    const double phi = (double)m->angle_min + (k + 0.5) * (double)inc;
+    cs[2u * a] = (float)std::cos(phi);
+    cs[2u * a + 1u] = (float)std::sin(phi);
+  }
+  return RPLGPU_OK;
+}
+
+double rplgpu_cast_range_m(uint32_t word, float resolution) {
+  if (word == RPLGPU_CAST_DROPPED) return std::nan("");
+  if ((word >> 28) == RPLGPU_CAST_NONE) return HUGE_VAL;
+  return std::sqrt((double)(word & 0x0FFFFFFFu)) * (double)resolution;
+}
+
+// the E11 cell rule on the host (seed_cell with this stage's spec)
+static bool cast_cell(float x, float y, const rplgpu_range_cast_t *s, int32_t *cx, int32_t *cy) {
+  const float du = x - s->origin_x, dv = y - s->origin_y;
+  const float u = du / s->resolution, v = dv / s->resolution;
+  const float fu = std::floor(u), fv = std::floor(v);
+  if (!(std::fabs(fu) < 1048576.0f && std::fabs(fv) < 1048576.0f)) return false;
+  *cx = (int32_t)fu;
+  *cy = (int32_t)fv;
+  return true;
+}
+
+// one ray by the header's rule; *n_out: the visit at which it stopped (0 for a dropped ray)
+static uint32_t cast_ray(const rplgpu_range_cast_t *s, const float *pose, const float *beam, const int8_t *grid,
+                         uint32_t *n_out) {
+  const float c = pose[0], sn = pose[1], tx = pose[2], ty = pose[3], cb = beam[0], sb = beam[1];
+  const float p0 = c * cb, p1 = sn * sb, p2 = sn * cb, p3 = c * sb;  // (-ffp-contract=off: every product rounded)
+  const float dc = p0 - p1, ds = p2 + p3;
+  const float rm = (float)s->max_steps * s->resolution;
+  const float mx = dc * rm, my = ds * rm;
+  const float ex = tx + mx, ey = ty + my;
+  int32_t x0, y0, x1, y1;
+  *n_out = 0;
+  if (!cast_cell(tx, ty, s, &x0, &y0) || !cast_cell(ex, ey, s, &x1, &y1)) return RPLGPU_CAST_DROPPED;
+  const int32_t ax = std::abs(x1 - x0), ay = std::abs(y1 - y0);
+  const int32_t stepx = (x1 > x0) - (x1 < x0), stepy = (y1 > y0) - (y1 < y0);
+  int32_t err = ax - ay, x = x0, y = y0;
+  uint32_t n = 0, kind;
+  for (;;) {
+    if (x < 0 || y < 0 || x >= (int32_t)s->width || y >= (int32_t)s->height) {
+      kind = RPLGPU_CAST_LEFT;
+      break;
+    }
+    const int32_t v = grid[(size_t)y * s->width + (size_t)x];
+    if (v >= s->hit_lo) {
+      kind = RPLGPU_CAST_HIT;
+      break;
+    }
+    if (v < 0 && s->unknown_stops) {
+      kind = RPLGPU_CAST_UNKNOWN;
+      break;
+    }
+    if ((x == x1 && y == y1) || n == s->max_steps) {
+      kind = RPLGPU_CAST_NONE;
+      break;
+    }
+    const int32_t e2 = 2 * err;
+    if (e2 > -ay) {
+      err -= ay;
+      x += stepx;
+    }
+    if (e2 < ax) {
+      err += ax;
+      y += stepy;
+    }
+    ++n;
+  }
+  *n_out = n;
+  const int32_t dx = x - x0, dy = y - y0;
+  return (uint32_t)(dx * dx + dy * dy) | (kind << 28);
+}
+
+// the table term of one range word against the measured range z (not NaN), the header's WEIGHT rule
+static uint32_t cast_term(const rplgpu_range_cast_t *s, uint32_t word, float z, const uint8_t *table) {
+  const int32_t K = (int32_t)s->table_half;
+  const float mz = z / s->resolution;
+  const float de = (word >> 28) == RPLGPU_CAST_NONE ? HUGE_VALF : std::sqrt((float)(word & 0x0FFFFFFFu));
+  if (mz == HUGE_VALF && de == HUGE_VALF) return table[2 * K + 1];
+  const float d = mz - de;
+  const float cl = std::max(-(float)K, std::min((float)K, std::floor(d)));
+  return table[K + (int32_t)cl];
+}
+
+int32_t rplgpu_cast_ranges_host(const rplgpu_range_cast_t *s, const float *poses, uint32_t P, const float *beams,
+                                uint32_t A, const int8_t *grid, const float *measured, uint32_t meas_count,
+                                uint32_t meas_first, uint32_t meas_step, const uint8_t *table, uint32_t *ranges_out,
+                                uint32_t *weights_out, uint32_t result[8], uint32_t cast[8]) {
+  if (rplgpu_range_cast_check(s) != RPLGPU_OK || !poses || !beams || !grid || !cast || (!ranges_out && !measured) ||
+      P == 0 || P > RPLGPU_MAX_POSES || A == 0 || A > RPLGPU_MAX_MERGE_BEAMS ||
+      (uint64_t)P * A > RPLGPU_MAX_CAST_RAYS)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (measured && (!table || !weights_out || !result ||
+                   (uint64_t)meas_first + (uint64_t)(A - 1u) * meas_step >= meas_count))
+    return RPLGPU_ERR_INVALID_ARG;
+  uint32_t counts[5] = {0, 0, 0, 0, 0}, far_hit = 0, beams_in = 0;
+  uint64_t steps = 0;
+  for (uint32_t q = 0; q < P; ++q) {
+    uint32_t w = 0;
+    for (uint32_t a = 0; a < A; ++a) {
+      uint32_t n = 0;
+      const uint32_t word = cast_ray(s, poses + 4u * (size_t)q, beams + 2u * (size_t)a, grid, &n);
+      steps += n;
+      if (word == RPLGPU_CAST_DROPPED) {
+        ++counts[4];
+      } else {
+        ++counts[word >> 28];
+        if ((word >> 28) == RPLGPU_CAST_HIT) far_hit = std::max(far_hit, word & 0x0FFFFFFFu);
+      }
+      if (ranges_out) ranges_out[(size_t)q * A + a] = word;
+      if (measured && word != RPLGPU_CAST_DROPPED) {
+        const float z = measured[meas_first + (size_t)a * meas_step];
+        if (!std::isnan(z)) w += cast_term(s, word, z, table);
+      }
+    }
+    if (measured) weights_out[q] = w;
+  }
+  if (measured) {
+    for (uint32_t a = 0; a < A; ++a) beams_in += std::isnan(measured[meas_first + (size_t)a * meas_step]) ? 0u : 1u;
+    uint32_t top = 0, at = 0, same = 0, dead = 0;  // E15's RESULT rule on the weights
+    uint64_t sum = 0;
+    for (uint32_t q = 0; q < P; ++q) {
+      const uint32_t w = weights_out[q];
+      if (w > top) {
+        top = w;
+        at = q;
+      }
+      dead += w == 0u ? 1u : 0u;
+      sum += w;
+    }
+    for (uint32_t q = 0; q < P; ++q) same += weights_out[q] == top ? 1u : 0u;
+    result[0] = top;
+    result[1] = at;
+    result[2] = same;
+    result[3] = dead;
+    result[4] = beams_in;
+    result[5] = weights_out[0];
+    result[6] = (uint32_t)sum;
+    result[7] = (uint32_t)(sum >> 32);
+  }
+  for (uint32_t i = 0; i < 5; ++i) cast[i] = counts[i];
+  cast[5] = far_hit;
+  cast[6] = (uint32_t)steps;
+  cast[7] = (uint32_t)(steps >> 32);
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_cast_ranges_dev(rplgpu_handle_t h, const rplgpu_range_cast_t *s, const float *d_poses,
+                               uint64_t pose_stride, uint32_t poses_per_group, uint32_t G, uint32_t P,
+                               const float *d_beams, uint32_t A, const int8_t *d_grid, uint64_t grid_stride,
+                               uint32_t grid_per_group, const float *d_measured, uint64_t meas_stride,
+                               uint32_t meas_first, uint32_t meas_step, const uint8_t *d_table,
+                               uint32_t *d_ranges_out, uint64_t range_stride, uint32_t *d_weights,
+                               uint64_t weight_stride, uint32_t *d_result, uint32_t *d_cast) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_range_cast_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_cast_ranges_dev: the rplgpu_range_cast_t is missing or rplgpu_range_cast_check refuses it";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
+    h->err = "rplgpu_cast_ranges_dev: G must be in 1 .. 65535";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES || A == 0 || A > RPLGPU_MAX_MERGE_BEAMS ||
+      (uint64_t)P * A > RPLGPU_MAX_CAST_RAYS) {
+    h->err = "rplgpu_cast_ranges_dev: P must be in 1 .. RPLGPU_MAX_POSES, A in 1 .. RPLGPU_MAX_MERGE_BEAMS and "
+             "P * A at most 2^28";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_ranges_out && !d_measured) {
+    h->err = "rplgpu_cast_ranges_dev: at least one of d_ranges_out and d_measured is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!d_poses || !d_beams || !d_grid || !d_cast || (d_measured && (!d_table || !d_weights || !d_result)) ||
+      misaligned(d_poses, 15) || misaligned(d_beams, 7) || misaligned(d_grid, 3) || misaligned(d_measured, 3) ||
+      misaligned(d_ranges_out, 3) || misaligned(d_cast, 3) ||
+      (d_measured && (misaligned(d_weights, 3) || misaligned(d_result, 3)))) {
+    h->err = "rplgpu_cast_ranges_dev: a required pointer is missing (d_table, d_weights and d_result with d_measured) "
+             "or a pointer is misaligned (16 bytes for d_poses, 8 for d_beams, 4 for d_grid, d_measured, "
+             "d_ranges_out, d_weights, d_result and d_cast)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (pose_stride < 4ull * P || (pose_stride & 3u)) {
+    h->err = "rplgpu_cast_ranges_dev: pose_stride >= 4 P and a multiple of 4 is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (grid_stride < (uint64_t)s->width * s->height || (grid_stride & 3u)) {
+    h->err = "rplgpu_cast_ranges_dev: grid_stride >= width * height and a multiple of 4 is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_ranges_out && range_stride < (uint64_t)P * A) {
+    h->err = "rplgpu_cast_ranges_dev: range_stride >= P * A is required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (d_measured &&
+      (weight_stride < P || (uint64_t)meas_first + (uint64_t)(A - 1u) * meas_step >= meas_stride)) {
+    h->err = "rplgpu_cast_ranges_dev: weight_stride >= P and meas_first + (A - 1) * meas_step < meas_stride are "
+             "required";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!device_readable(h, {{d_poses, "d_poses", true}, {d_beams, "d_beams", true}, {d_grid, "d_grid", true},
+                           {d_cast, "d_cast", true}, {d_measured, "d_measured", false},
+                           {d_ranges_out, "d_ranges_out", false}}))
+    return RPLGPU_ERR_INVALID_ARG;
+  if (d_measured && !device_readable(h, {{d_table, "d_table", true}, {d_weights, "d_weights", true},
+                                         {d_result, "d_result", true}}))
+    return RPLGPU_ERR_INVALID_ARG;
+  rpl::CastK k;
+  k.origin_x = s->origin_x;
+  k.origin_y = s->origin_y;
+  k.resolution = s->resolution;
+  k.width = s->width;
+  k.height = s->height;
+  k.max_steps = s->max_steps;
+  k.hit_lo = s->hit_lo;
+  k.unknown_stops = s->unknown_stops;
+  k.table_half = s->table_half;
+  RPL_HIP(h, hipSetDevice(h->device));
+  RPL_HIP(h, rpl::launch_cast(h->stream, k, d_poses, pose_stride, poses_per_group, G, P, d_beams, A, d_grid,
+                              grid_stride, grid_per_group, d_measured, meas_stride, meas_first, meas_step,
+                              d_measured ? d_table : nullptr, d_ranges_out, range_stride,
+                              d_measured ? d_weights : nullptr, weight_stride, d_measured ? d_result : nullptr,
+                              d_cast));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_cast_ranges(rplgpu_handle_t h, const rplgpu_range_cast_t *s, const float *poses, uint32_t P,
+                           const float *beams, uint32_t A, const int8_t *grid, const float *measured,
+                           uint32_t meas_count, uint32_t meas_first, uint32_t meas_step, const uint8_t *table,
+                           uint32_t *ranges_out, uint32_t *weights_out, uint32_t result[8], uint32_t cast[8]) {
+  if (!h || !poses || !beams || !grid || !cast) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_range_cast_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_cast_ranges: the rplgpu_range_cast_t is missing or rplgpu_range_cast_check refuses it";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (P == 0 || P > RPLGPU_MAX_POSES || A == 0 || A > RPLGPU_MAX_MERGE_BEAMS ||
+      (uint64_t)P * A > RPLGPU_MAX_CAST_RAYS) {
+    h->err = "rplgpu_cast_ranges: P must be in 1 .. RPLGPU_MAX_POSES, A in 1 .. RPLGPU_MAX_MERGE_BEAMS and P * A at "
+             "most 2^28";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if ((!ranges_out && !measured) || (measured && (!table || !weights_out || !result || meas_count == 0))) {
+    h->err = "rplgpu_cast_ranges: ranges_out or measured is required, and table, weights_out and result with measured";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  RPL_HIP(h, hipSetDevice(h->device));
+  // result | cast | beams | table | measured | grid | weights | ranges | poses
+  const size_t cells = (size_t)s->width * s->height, gstride = (cells + 3u) & ~(size_t)3u;
+  const size_t rays = (size_t)P * A, tbytes = 2u * (size_t)s->table_half + 2u;
+  DoorBuffer buf(h, "rplgpu_cast_ranges");
+  const size_t o_res = buf.part(32), o_cast = buf.part(32), o_beams = buf.part(8u * (size_t)A),
+               o_tab = buf.part_if(measured, tbytes), o_meas = buf.part_if(measured, 4u * (size_t)meas_count),
+               o_grid = buf.part(gstride), o_wt = buf.part_if(measured, 4u * (size_t)P),
+               o_rng = buf.part_if(ranges_out, 4u * rays), o_poses = buf.part(16u * (size_t)P);
+  uint32_t small[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<uint32_t> wt_back(measured ? P : 0u);
+  const int32_t rc = buf.run([&]() -> int32_t {
+    RPL_HIP(h, hipMemsetAsync(buf.at(o_grid), 0, up16(gstride), h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_poses), poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_beams), beams, 8u * (size_t)A, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_grid), grid, cells, hipMemcpyHostToDevice, h->stream));
+    if (measured) {
+      RPL_HIP(h, hipMemcpyAsync(buf.at(o_tab), table, tbytes, hipMemcpyHostToDevice, h->stream));
+      RPL_HIP(h, hipMemcpyAsync(buf.at(o_meas), measured, 4u * (size_t)meas_count, hipMemcpyHostToDevice, h->stream));
+    }
+    const int32_t irc = rplgpu_cast_ranges_dev(
+        h, s, buf.at<const float>(o_poses), 4ull * P, 0, 1, P, buf.at<const float>(o_beams), A,
+        buf.at<const int8_t>(o_grid), gstride, 0, buf.at<const float>(o_meas), meas_count, meas_first, meas_step,
+        buf.at<const uint8_t>(o_tab), buf.at<uint32_t>(o_rng), rays, buf.at<uint32_t>(o_wt), P,
+        measured ? buf.at<uint32_t>(o_res) : nullptr, buf.at<uint32_t>(o_cast));
+    if (irc) return irc;
+    // (the range words may be a gigabyte: straight into the caller's buffer, which a refused call never reaches)
+    if (ranges_out)
+      RPL_HIP(h, hipMemcpyAsync(ranges_out, buf.at(o_rng), 4u * rays, hipMemcpyDeviceToHost, h->stream));
+    if (measured)
+      RPL_HIP(h, hipMemcpyAsync(wt_back.data(), buf.at(o_wt), 4u * (size_t)P, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, buf.at(o_res), 64, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  });
+  if (rc) return rc;
+  if (measured) {
+    std::memcpy(weights_out, wt_back.data(), 4u * (size_t)P);
+    std::memcpy(result, small, 32);
+  }
+  std::memcpy(cast, small + 8, 32);
   return RPLGPU_OK;
 }
 

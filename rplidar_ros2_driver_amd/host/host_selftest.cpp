@@ -509,6 +509,46 @@ int main(int argc, char **argv) {
     }
     std::printf("cluster poses: %u clusters, the heaviest (label %u, %u poses, W %.0f) at (%.4f, %.4f, %.4f)\n",
                 cr.clusters, cr.best_label, cr.best_poses, cr.best[7], cr.best[0], cr.best[1], cr.best[2]);
+    // E22: one pose in the middle of a 9 x 9 room of 1 m cells with a wall around it, four beams along the axes: every
+    // ray hits the wall after 4 cells (D2 16).  Measured 4 m, 4.6 m, no return and a removed beam: terms table[K],
+    // table[K] (floorf(0.6) = 0), table[2K] and nothing; against the library's own host-only twin word for word.
+    rplgpu_range_cast_t rspec;
+    rplgpu_default_range_cast(&rspec);
+    rspec.origin_x = rspec.origin_y = 0.0f;
+    rspec.resolution = 1.0f;
+    rspec.width = rspec.height = 9;
+    rspec.max_steps = 20;
+    rspec.table_half = 3;
+    std::vector<int8_t> room(81, 0);
+    for (int k = 0; k < 9; ++k) room[k] = room[72 + k] = room[9 * k] = room[9 * k + 8] = 100;
+    const std::vector<float> rposes = {1.0f, 0.0f, 4.5f, 4.5f}, rbeams = {1, 0, 0, 1, -1, 0, 0, -1};
+    const std::vector<float> rscan = {4.0f, 4.6f, HUGE_VALF, std::nanf("")};
+    const std::vector<uint8_t> rtable = {10, 11, 12, 13, 14, 15, 16, 99};
+    std::vector<uint32_t> rwords, rweights;
+    rplgpu_host::ScanPath::CastResult cres;
+    uint32_t words_twin[4], weight_twin[1], result_twin[8], cast_twin[8];
+    if (!path.cast_ranges(rspec, rposes, rbeams, room, rscan, 0, 1, rtable, &rwords, rweights, cres)) {
+      std::fprintf(stderr, "cast ranges failed: %s\n", path.last_error().c_str());
+      return 31;
+    }
+    if (rplgpu_cast_ranges_host(&rspec, rposes.data(), 1, rbeams.data(), 4, room.data(), rscan.data(), 4, 0, 1,
+                                rtable.data(), words_twin, weight_twin, result_twin, cast_twin) != RPLGPU_OK)
+      return 32;
+    bool cast_ok = rwords.size() == 4 && rweights.size() == 1 && rweights[0] == 13 + 13 + 16 &&
+                   rweights[0] == weight_twin[0] && cres.hit == 4 && cres.hit == cast_twin[0] && cres.unknown == 0 &&
+                   cres.left == 0 && cres.none == 0 && cres.dropped == 0 && cres.max_hit_d2 == 16 && cres.steps == 16 &&
+                   cres.steps == cast_twin[6] && cres.beams_used == 3 && cres.beams_used == result_twin[4] &&
+                   cres.best_weight == rweights[0] && cres.best_index == 0 && cres.best_count == 1 && cres.zero_weights == 0 &&
+                   cres.weight_sum == rweights[0] && rplgpu_cast_range_m(rwords.empty() ? 0u : rwords[0], 1.0f) == 4.0;
+    for (size_t k = 0; cast_ok && k < 4; ++k) cast_ok = rwords[k] == 16u && rwords[k] == words_twin[k];
+    if (!cast_ok) {
+      std::fprintf(stderr, "cast ranges: wrong answer (weight %u / %u, hits %u, steps %llu, word %08x)\n",
+                   rweights.empty() ? 0u : rweights[0], weight_twin[0], cres.hit, (unsigned long long)cres.steps,
+                   rwords.empty() ? 0u : rwords[0]);
+      return 32;
+    }
+    std::printf("cast ranges: 4 rays hit after %.1f m, weight %u from %u beams, %llu cell steps\n",
+                rplgpu_cast_range_m(rwords[0], 1.0f), rweights[0], cres.beams_used, (unsigned long long)cres.steps);
     return 0;
   }
   std::FILE *f = std::fopen(argv[1], "rb");

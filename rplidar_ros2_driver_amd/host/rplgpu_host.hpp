@@ -40,6 +40,8 @@
 //         -> rplgpu_host::ScanPath::bin_poses(spec, poses, weights, headings, map, result)  (E20)
 //         and the pose AMCL publishes, the mean of the heaviest cluster of those bins (pf_cluster_stats):
 //         -> rplgpu_host::ScanPath::cluster_poses(spec, poses, weights, headings, map, bins, max, clusters, result)  (E21)
+//         and the filter's other sensor model, the beam model (a ray from every pose along every beam, map_calc_range):
+//         -> rplgpu_host::ScanPath::cast_ranges(spec, poses, beams, grid, measured, first, step, table, ranges, weights, result)  (E22)
 //
 // Header only, no ROS dependency: the message types are template parameters, so the same
 // code compiles against sensor_msgs::msg::LaserScan / PointCloud2 in the node and against
@@ -786,6 +788,65 @@ class ScanPath {
       row.weight = static_cast<uint64_t>(rows[4 * c + 2]) | (static_cast<uint64_t>(rows[4 * c + 3]) << 32);
       clusters.push_back(row);
     }
+    return true;
+  }
+
+  // ext E22 (include/rplgpu_msg.h): a ray from every pose (c, s, x, y) along every beam (cb, sb) of `beams` through the
+  // int8 grid to the first cell that stops it (AMCL's map_calc_range) — the beam model's expected ranges.  `ranges`
+  // (optional) receives poses x beams range words (rplgpu_cast_range_m turns one into metres).  With `measured` not
+  // empty (a merged LaserScan's ranges; beam a is entry meas_first + a * meas_step) each ray is compared with its
+  // beam's measured range through `table` (2 * spec.table_half + 2 bytes) and the terms are summed into `weights`, one
+  // per pose, in score_poses' layout: resample_poses, estimate_pose and bin_poses take them unchanged.
+  struct CastResult {
+    uint32_t hit = 0, unknown = 0, left = 0, none = 0, dropped = 0;  // rays by how they ended
+    uint32_t max_hit_d2 = 0;    // the largest squared distance (cells) among the rays that hit
+    uint64_t steps = 0;         // cell steps walked
+    uint32_t best_weight = 0, best_index = 0, best_count = 0, zero_weights = 0, beams_used = 0;
+    uint64_t weight_sum = 0;
+  };
+  bool cast_ranges(const rplgpu_range_cast_t &spec, const std::vector<float> &poses, const std::vector<float> &beams,
+                   const std::vector<int8_t> &grid, const std::vector<float> &measured, uint32_t meas_first,
+                   uint32_t meas_step, const std::vector<uint8_t> &table, std::vector<uint32_t> *ranges,
+                   std::vector<uint32_t> &weights, CastResult &result) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    if (rplgpu_range_cast_check(&spec) != RPLGPU_OK) return fail("cast_ranges: rplgpu_range_cast_check refuses the spec");
+    const size_t count = poses.size() / 4, n_beams = beams.size() / 2;
+    if (count == 0 || count > RPLGPU_MAX_POSES || poses.size() != 4 * count)
+      return fail("cast_ranges: poses must hold 1 .. RPLGPU_MAX_POSES entries of four floats");
+    if (n_beams == 0 || n_beams > RPLGPU_MAX_MERGE_BEAMS || beams.size() != 2 * n_beams ||
+        count * n_beams > RPLGPU_MAX_CAST_RAYS)
+      return fail("cast_ranges: beams must hold 1 .. RPLGPU_MAX_MERGE_BEAMS entries of two floats, poses x beams <= 2^28");
+    if (grid.size() != static_cast<size_t>(spec.width) * spec.height) return fail("cast_ranges: grid is not width x height");
+    const bool weigh = !measured.empty();
+    if (!weigh && !ranges) return fail("cast_ranges: neither ranges nor a measured scan");
+    if (weigh && table.size() != 2 * static_cast<size_t>(spec.table_half) + 2)
+      return fail("cast_ranges: table must hold 2 * table_half + 2 bytes");
+    std::vector<uint32_t> r_out(ranges ? count * n_beams : 0), w_out(weigh ? count : 0);
+    uint32_t out[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cast[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_cast_ranges(h_, &spec, poses.data(), static_cast<uint32_t>(count), beams.data(),
+                           static_cast<uint32_t>(n_beams), grid.data(), weigh ? measured.data() : nullptr,
+                           static_cast<uint32_t>(measured.size()), meas_first, meas_step, weigh ? table.data() : nullptr,
+                           ranges ? r_out.data() : nullptr, weigh ? w_out.data() : nullptr, out, cast) != RPLGPU_OK)
+      return note_error();
+    result = CastResult();
+    result.hit = cast[0];
+    result.unknown = cast[1];
+    result.left = cast[2];
+    result.none = cast[3];
+    result.dropped = cast[4];
+    result.max_hit_d2 = cast[5];
+    result.steps = static_cast<uint64_t>(cast[6]) | (static_cast<uint64_t>(cast[7]) << 32);
+    if (weigh) {
+      result.best_weight = out[0];
+      result.best_index = out[1];
+      result.best_count = out[2];
+      result.zero_weights = out[3];
+      result.beams_used = out[4];
+      result.weight_sum = static_cast<uint64_t>(out[6]) | (static_cast<uint64_t>(out[7]) << 32);
+      weights.swap(w_out);
+    }
+    if (ranges) ranges->swap(r_out);
     return true;
   }
 
