@@ -26,37 +26,27 @@
 //                        goes 0 -> 1 exactly once and exactly one atomic sees it, in any order, and a bit that KEEP
 //                        found set is nobody's.
 //                  A tile's statistics are wave reductions through LDS and thread 0's integer atomics, as E18 / E19.
-// The quantisation is E17's (rpl_estimate.hip, es_quantise), its three lines copied: moving them into a header would
-// touch an existing kernel's source.  This unit is built with -ffp-contract=off: every float32 operation rounds once.
+// The quantisation of (c, s) is E17's (rpl_moments.hpp, es_quantise_cs).  This unit is built with -ffp-contract=off:
+// every float32 operation rounds once.
 #include <hip/hip_runtime.h>
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
+#include "rpl_moments.hpp"
 #include "rplgpu_msg.h"
 
 namespace rpl {
 namespace {
 
-typedef unsigned long long u64;
-typedef long long i64;
-typedef float bn_f32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kBnTile = kBlock;          // poses per tile: one per thread
 constexpr uint32_t kBnClearWords = 8192u;     // map words per block of k_bins_start: four pairs per thread
 constexpr uint32_t kBnMergeRounds = 8u;       // merge rounds per wave; a lane still pending after them marks alone
-constexpr float kBnCsScale = 1048576.0f;
-constexpr float kBnLimit = 8388608.0f;
 static_assert(RPLGPU_MAX_HEADING_BINS == (uint32_t)kBlock, "one edge per thread");
 static_assert(kBnClearWords == 8u * kBlock, "four 8-byte stores per thread");
 
-__host__ __device__ inline uint32_t bn_map_words(uint32_t nb) { return (nb + 31u) >> 5; }
-
-// E17's rule for one entry of (c, s): one product, the range test (false for NaN), one round-to-nearest-even
+// E17's rule for one entry of (c, s); false as well for an entry that quantises to (0, 0)
 __device__ __forceinline__ bool bn_quantise(float c, float s, int32_t *C, int32_t *S) {
-  const float tc = c * kBnCsScale, ts = s * kBnCsScale;
-  const bool in = fabsf(tc) < kBnLimit && fabsf(ts) < kBnLimit;
-  *C = in ? (int32_t)rintf(tc) : 0;
-  *S = in ? (int32_t)rintf(ts) : 0;
-  return in && (*C != 0 || *S != 0);
+  return es_quantise_cs(c, s, C, S) && (*C != 0 || *S != 0);
 }
 
 __device__ __forceinline__ uint32_t bn_half(int32_t C, int32_t S) { return (S > 0 || (S == 0 && C > 0)) ? 0u : 1u; }
@@ -117,9 +107,9 @@ __global__ __launch_bounds__(kBlock) void k_bins_mark(
     bn_quantise(e.x, e.y, &q.x, &q.y);  // (0, 0) when out of range
     s_edge[threadIdx.x] = q;
   }
-  const bn_f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-  const bn_f32x4 v =
-      live ? reinterpret_cast<const bn_f32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride)[i] : zero;
+  const es_f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+  const es_f32x4 v =
+      live ? reinterpret_cast<const es_f32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride)[i] : zero;
   const uint32_t w = live ? (weights ? weights[(size_t)g * weight_stride + i] : 1u) : 0u;
   __syncthreads();
   // the position bin
@@ -141,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void k_bins_mark(
         hi = mid;
     }
   }
-  const uint32_t nb = nx * ny * T, words = bn_map_words(nb);
+  const uint32_t nb = nx * ny * T, words = bin_map_words(nb);
   const bool skipped = live && w == 0u;
   const bool counted = live && !skipped && pos_in && head_in;
   const bool outside = live && !skipped && !counted;
@@ -219,7 +209,7 @@ hipError_t launch_bins(hipStream_t s, const BinsK &k, const float *poses, unsign
       k.nx == 0 || k.nx > 65536u || k.ny == 0 || k.ny > 65536u ||
       (u64)k.nx * k.ny * T > (u64)RPLGPU_MAX_POSE_BINS)
     return hipErrorInvalidValue;
-  const uint32_t words = bn_map_words(k.nx * k.ny * T);
+  const uint32_t words = bin_map_words(k.nx * k.ny * T);
   if (pose_stride < 4ull * P || (pose_stride & 3u) || (weights && weight_stride < P) || map_stride < words ||
       (map_stride & 1u) || (bins_out && bin_stride < P))
     return hipErrorInvalidValue;

@@ -18,11 +18,12 @@
 //                  reductions into LDS, then seven integer atomics per workgroup: order-free sums and one max; the
 //                  64-bit sum of n is a 32-bit add whose returned value tells the one adder that wrapped the low word
 //                  to carry into the high word.
-// This unit is built with -ffp-contract=off: every float32 operation rounds once.  The cell rule is rpl_ray.hpp's
-// occ_cell with this stage's spec (its four lines copied: it takes E11's OccK).
+// This unit is built with -ffp-contract=off: every float32 operation rounds once.  The cell rule is E11's, rpl_grid.hpp's
+// grid_cell with this stage's spec.
 #include <hip/hip_runtime.h>
 
 #include "rpl_device.hpp"
+#include "rpl_grid.hpp"
 #include "rpl_launch.hpp"
 #include "rplgpu_msg.h"
 
@@ -32,19 +33,8 @@ namespace {
 typedef float ca_f32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kCaBlock = 256u;  // rays per tile: one per thread
 constexpr uint32_t kCaWaves = kCaBlock / 64u;
-constexpr float kCaCellLimit = 1048576.0f;
 static_assert((uint64_t)kCaBlock * RPLGPU_MAX_OCC_STEPS < (1ull << 32), "a tile's sum of n fits one word");
 static_assert(255ull * RPLGPU_MAX_MERGE_BEAMS < (1ull << 32), "a weight fits one word");
-
-// the E11 cell rule; false: the position has no cell (NaN fails the compares too)
-__device__ __forceinline__ bool ca_cell(float x, float y, const CastK &k, int *cx, int *cy) {
-  const float fu = floorf((x - k.origin_x) / k.resolution);
-  const float fv = floorf((y - k.origin_y) / k.resolution);
-  if (!(fabsf(fu) < kCaCellLimit && fabsf(fv) < kCaCellLimit)) return false;
-  *cx = (int)fu;
-  *cy = (int)fv;
-  return true;
-}
 
 __global__ __launch_bounds__(kCaBlock) void k_cast_start(const float *__restrict__ measured,
                                                          unsigned long long meas_stride, uint32_t meas_first,
@@ -99,7 +89,8 @@ __global__ __launch_bounds__(kCaBlock) void k_cast(
     const float rm = (float)k.max_steps * k.resolution;
     const float ex = tx + dc * rm, ey = ty + ds * rm;
     int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
-    if (ca_cell(tx, ty, k, &x0, &y0) && ca_cell(ex, ey, k, &x1, &y1)) {
+    if (grid_cell(tx, ty, k.origin_x, k.origin_y, k.resolution, &x0, &y0) &&
+        grid_cell(ex, ey, k.origin_x, k.origin_y, k.resolution, &x1, &y1)) {
       const int8_t *gr = grid + (grid_per_group ? (size_t)g * grid_stride : (size_t)0);
       const int ax = abs(x1 - x0), ay = abs(y1 - y0);
       const int stepx = (x1 > x0) - (x1 < x0), stepy = (y1 > y0) - (y1 < y0);

@@ -36,9 +36,9 @@
 //   k_cl_best     grid (G): rbase scanned (<= 1024 totals, one per thread) -> N_c; one sweep over the rank blocks that
 //                 hold a root writes the table rows of the roots of ordinal < cap and finds BEST by (W descending,
 //                 rank ascending), a second sweep finds SECOND among the others.
-//   k_cl_tiles, k_cl_finish   E17's tile reduction and finish (rpl_estimate.hip, its limbs and its 128-bit adds copied:
-//                 moving them into a header would touch an existing kernel's source) with "pord[i] is BEST's root" in
-//                 place of the gate; the finish kernel writes the 80 result words.
+//   k_cl_tiles, k_cl_finish   E17's tile reduction and finish (rpl_moments.hpp's es_tile_sums and es_finish_sums, the
+//                 bodies rpl_estimate.hip runs) with "pord[i] is BEST's root" in place of the gate; the finish kernel
+//                 adds its own words 0 - 7 and 72 - 79.
 // With K above kClMaxBins (a KEEP map ORed over several lists) k_cl_scan says so in the header and every later kernel
 // does nothing but write the header's rule: labels 0xFFFFFFFF, word 0 = 32.
 //
@@ -53,22 +53,16 @@
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
+#include "rpl_moments.hpp"
 #include "rplgpu_msg.h"
 
 namespace rpl {
 namespace {
 
-typedef unsigned long long u64;
-typedef long long i64;
-typedef __int128 i128;
-typedef float cl_f32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kClBlock = kBlock;            // map words per index block, bins per link block, poses per tile
 constexpr uint32_t kClMaxBins = RPLGPU_MAX_POSES;  // occupied bins a call holds
 constexpr uint32_t kClNone = 0xFFFFFFFFu;
 constexpr uint32_t kClMergeRounds = 8u;
-constexpr uint32_t kClSums = 16u, kClPlanes = 17u, kClLimbs = 11u;  // E17's
-constexpr float kClCsScale = 1048576.0f;
-constexpr float kClLimit = 8388608.0f;
 static_assert(RPLGPU_MAX_POSE_BINS / 32u / kClBlock <= 2u * kClBlock, "k_cl_scan takes two block totals per thread");
 static_assert(kClMaxBins / kClBlock <= kClBlock, "k_cl_best takes one block total per thread");
 static_assert(RPLGPU_CLUSTER_WORDS == RPLGPU_ESTIMATE_WORDS + 8u, "the result's layout");
@@ -77,8 +71,6 @@ enum { H_K = 0, H_NC, H_FLAGS, H_STRAY, H_UNLAB, H_BEST, H_BESTLABEL, H_SECLABEL
        H_WORDS = 16 };
 
 __host__ __device__ inline u64 cl_even(u64 v) { return (v + 1ull) & ~1ull; }
-__host__ __device__ inline uint32_t cl_map_words(uint32_t nb) { return (nb + 31u) >> 5; }
-__host__ __device__ inline uint32_t cl_tiles(uint32_t P) { return (P + kClBlock - 1u) / kClBlock; }
 
 struct ClLayout {
   u64 bbase, rbase, wpre, parent, root, binid, ordpre, tabn, tabw, pord, est, total;
@@ -86,7 +78,7 @@ struct ClLayout {
 };
 __host__ __device__ inline ClLayout cl_layout(uint32_t nb, uint32_t P) {
   ClLayout l;
-  const uint32_t words = cl_map_words(nb);
+  const uint32_t words = bin_map_words(nb);
   l.kc = nb < kClMaxBins ? nb : kClMaxBins;
   const u64 kc = cl_even(l.kc);
   l.bbase = H_WORDS;
@@ -100,7 +92,7 @@ __host__ __device__ inline ClLayout cl_layout(uint32_t nb, uint32_t P) {
   l.tabw = l.tabn + kc;
   l.pord = l.tabw + 2ull * kc;
   l.est = l.pord + cl_even(P);
-  l.total = l.est + 4ull * kClPlanes * cl_tiles(P);
+  l.total = l.est + es_group_words(es_tiles(P));
   return l;
 }
 
@@ -137,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_index(ClArgs a) {
   const ClLayout l = cl_layout(a.nb, a.P);
   uint32_t *grp = a.scratch + (size_t)g * l.total;
   const uint32_t *map = a.map + (size_t)g * a.map_stride;
-  const uint32_t words = cl_map_words(a.nb);
+  const uint32_t words = bin_map_words(a.nb);
   const uint32_t w = blockIdx.x * kClBlock + threadIdx.x;
   const uint32_t pc = w < words ? (uint32_t)__popc(cl_word(map, w, a.nb)) : 0u;
   uint32_t total;
@@ -151,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_scan(ClArgs a) {
   const uint32_t g = blockIdx.x;
   const ClLayout l = cl_layout(a.nb, a.P);
   uint32_t *grp = a.scratch + (size_t)g * l.total;
-  const uint32_t nblk = (cl_map_words(a.nb) + kClBlock - 1u) / kClBlock;  // <= 2048
+  const uint32_t nblk = (bin_map_words(a.nb) + kClBlock - 1u) / kClBlock;  // <= 2048
   const uint32_t i0 = 2u * threadIdx.x, i1 = i0 + 1u;
   const uint32_t v0 = i0 < nblk ? grp[l.bbase + i0] : 0u, v1 = i1 < nblk ? grp[l.bbase + i1] : 0u;
   uint32_t K;
@@ -270,22 +262,6 @@ __global__ __launch_bounds__(kBlock) void k_cl_flatten(ClArgs a) {
   if (threadIdx.x == 0) grp[l.rbase + blockIdx.x] = total;
 }
 
-// E17's rule for one pose (rpl_estimate.hip, es_quantise)
-struct ClPose {
-  int32_t X, Y, C, S;
-  bool in;
-};
-__device__ __forceinline__ ClPose cl_quantise(cl_f32x4 v, float xy_scale) {
-  const float tc = v.x * kClCsScale, ts = v.y * kClCsScale, tx = v.z * xy_scale, ty = v.w * xy_scale;
-  ClPose q;
-  q.in = fabsf(tx) < kClLimit && fabsf(ty) < kClLimit && fabsf(tc) < kClLimit && fabsf(ts) < kClLimit;  // NaN: false
-  q.X = q.in ? (int32_t)rintf(tx) : 0;
-  q.Y = q.in ? (int32_t)rintf(ty) : 0;
-  q.C = q.in ? (int32_t)rintf(tc) : 0;
-  q.S = q.in ? (int32_t)rintf(ts) : 0;
-  return q;
-}
-
 __global__ __launch_bounds__(kBlock) void k_cl_weigh(ClArgs a, const float *__restrict__ poses, u64 pose_stride,
                                                      uint32_t poses_per_group, const uint32_t *__restrict__ weights,
                                                      u64 weight_stride, float xy_scale,
@@ -314,10 +290,10 @@ __global__ __launch_bounds__(kBlock) void k_cl_weigh(ClArgs a, const float *__re
     label = grp[l.binid + root];
   }
   if (live && labels) labels[(size_t)g * label_stride + i] = label;  // i < P <= label_stride
-  const cl_f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-  const cl_f32x4 v =
-      labelled ? reinterpret_cast<const cl_f32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride)[i] : zero;
-  const bool in = labelled && cl_quantise(v, xy_scale).in;
+  const es_f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+  const es_f32x4 v =
+      labelled ? reinterpret_cast<const es_f32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride)[i] : zero;
+  const bool in = labelled && es_quantise(v, xy_scale).in;
   const uint32_t w = in ? (weights ? weights[(size_t)g * weight_stride + i] : 1u) : 0u;
   if (live) grp[l.pord + i] = in ? root : kClNone;
   // the lanes of the wave that hit the same root hand their weight and count to the first of them; what the FIRST
@@ -492,36 +468,12 @@ __global__ __launch_bounds__(kBlock) void k_cl_best(ClArgs a, uint32_t *__restri
   }
 }
 
-// ---- E17's tile reduction and finish (rpl_estimate.hip) ---------------------------------------------------------------
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ i64 cl_dpp_add(i64 v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u64)v, CTRL, ROWMASK, 0xF, false);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)((u64)v >> 32), CTRL, ROWMASK, 0xF, false);
-  return (i64)((u64)v + (((u64)hi << 32) | lo));
-}
-__device__ __forceinline__ i64 cl_wave_sum_lane63(i64 v) {
-  v = cl_dpp_add<0x111, 0xF>(v);  // row_shr:1
-  v = cl_dpp_add<0x112, 0xF>(v);  // row_shr:2
-  v = cl_dpp_add<0x114, 0xF>(v);  // row_shr:4
-  v = cl_dpp_add<0x118, 0xF>(v);  // row_shr:8
-  v = cl_dpp_add<0x142, 0xA>(v);  // row_bcast:15 -> rows 1,3
-  v = cl_dpp_add<0x143, 0xC>(v);  // row_bcast:31 -> rows 2,3
-  return v;
-}
-
-__device__ __forceinline__ void cl_store128(uint32_t *at, i128 v) {
-  u64 *p = reinterpret_cast<u64 *>(at);  // (the part is 8-byte aligned and an entry has 16 bytes)
-  p[0] = (u64)v;
-  p[1] = (u64)((unsigned __int128)v >> 64);
-}
-
+// ---- E17's tile reduction and finish (rpl_moments.hpp) ----------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_cl_tiles(ClArgs a, const float *__restrict__ poses, u64 pose_stride,
                                                      uint32_t poses_per_group, const uint32_t *__restrict__ weights,
                                                      u64 weight_stride, float xy_scale) {
-  __shared__ i64 s_limb[2u * kClLimbs][kWaves];
-  __shared__ uint32_t s_cnt[kWaves];
   const uint32_t tile = blockIdx.x, g = blockIdx.y;
-  const uint32_t TL = cl_tiles(a.P);
+  const uint32_t TL = es_tiles(a.P);
   const ClLayout l = cl_layout(a.nb, a.P);
   uint32_t *grp = a.scratch + (size_t)g * l.total;
   const uint32_t best = grp[H_BEST];
@@ -530,115 +482,22 @@ __global__ __launch_bounds__(kBlock) void k_cl_tiles(ClArgs a, const float *__re
   const uint32_t ord = live ? grp[l.pord + i] : kClNone;
   const bool in0 = ord != kClNone;  // labelled and in range (k_cl_weigh)
   const bool in1 = in0 && ord == best;
-  const cl_f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-  const cl_f32x4 v =
-      in0 ? reinterpret_cast<const cl_f32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride)[i] : zero;
-  const ClPose q = cl_quantise(v, xy_scale);
+  const es_f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+  const es_f32x4 v =
+      in0 ? reinterpret_cast<const es_f32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride)[i] : zero;
+  const EsPose q = es_quantise(v, xy_scale);
   const uint32_t w = in0 ? (weights ? weights[(size_t)g * weight_stride + i] : 1u) : 0u;
-  const i64 w0 = in0 ? (i64)w : 0ll;
-  const i64 xx = (i64)q.X * q.X, xy = (i64)q.X * q.Y, yy = (i64)q.Y * q.Y;
-  i64 m[2u * kClLimbs];
-  m[0] = w0;
-  m[1] = w0 * q.X;
-  m[2] = w0 * q.Y;
-  m[3] = w0 * q.C;
-  m[4] = w0 * q.S;
-  m[5] = w0 * (xx & 0x7FFFFFll);
-  m[6] = w0 * (xx >> 23);
-  m[7] = w0 * (xy & 0x7FFFFFll);
-  m[8] = w0 * (xy >> 23);  // (an arithmetic shift: floor, so that low + 2^23 * high is xy for either sign)
-  m[9] = w0 * (yy & 0x7FFFFFll);
-  m[10] = w0 * (yy >> 23);
-#pragma unroll
-  for (uint32_t k = 0; k < kClLimbs; ++k) m[kClLimbs + k] = in1 ? m[k] : 0ll;
-#pragma unroll
-  for (uint32_t k = 0; k < 2u * kClLimbs; ++k) {
-    const i64 sum = cl_wave_sum_lane63(m[k]);
-    if (lane_id() == 63u) s_limb[k][wave_id()] = sum;
-  }
-  const uint32_t alive = w != 0u ? 1u : 0u;
-  const uint32_t cnt = wave_incl_scan_fast((in0 ? 1u | alive << 8 : 0u) | (in1 ? 1u << 16 | alive << 24 : 0u));
-  if (lane_id() == 63u) s_cnt[wave_id()] = cnt;
-  __syncthreads();
-  uint32_t *est = grp + l.est;
-  if (threadIdx.x < kClSums) {
-    const uint32_t set = threadIdx.x >> 3, j = threadIdx.x & 7u;
-    const uint32_t at = set * kClLimbs + (j < 5u ? j : 5u + 2u * (j - 5u));
-    i128 low = 0, high = 0;
-    for (int k = 0; k < kWaves; ++k) {
-      low += s_limb[at][k];
-      if (j >= 5u) high += s_limb[at + 1u][k];
-    }
-    cl_store128(est + 4u * ((size_t)threadIdx.x * TL + tile), low + high * (i128)8388608);
-  } else if (threadIdx.x == kClSums) {
-    uint32_t n[4] = {0u, 0u, 0u, 0u};
-    for (int k = 0; k < kWaves; ++k) {
-      const uint32_t c = s_cnt[k];
-      n[0] += c & 0xFFu;
-      n[1] += (c >> 8) & 0xFFu;
-      n[2] += (c >> 16) & 0xFFu;
-      n[3] += c >> 24;
-    }
-    u64 *rec = reinterpret_cast<u64 *>(est + 4u * ((size_t)kClSums * TL + tile));
-    rec[0] = (u64)n[0] | (u64)n[1] << 32;
-    rec[1] = (u64)n[2] | (u64)n[3] << 32;
-  }
+  es_tile_sums(q, w, in0, in1, tile, TL, grp + l.est);
 }
 
 __global__ __launch_bounds__(kBlock) void k_cl_finish(ClArgs a, uint32_t *__restrict__ result) {
   __shared__ uint32_t s_cnt[4];
   __shared__ uint32_t s_empty[2];
-  const uint32_t g = blockIdx.x, m = wave_id();
-  const uint32_t TL = cl_tiles(a.P);
+  const uint32_t g = blockIdx.x;
   const ClLayout l = cl_layout(a.nb, a.P);
   const uint32_t *grp = a.scratch + (size_t)g * l.total;
-  const uint32_t *est = grp + l.est;
   uint32_t *res = result + (size_t)RPLGPU_CLUSTER_WORDS * g;
-  u64 lo = 0ull, hi = 0ull;
-  for (uint32_t t = lane_id(); t < TL; t += 64u) {  // at most 16 rounds: TL <= 1024
-    const u64 *rec = reinterpret_cast<const u64 *>(est + 4u * ((size_t)m * TL + t));
-    const u64 v = rec[0];
-    lo += v;
-    hi += rec[1] + (lo < v ? 1ull : 0ull);
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const u64 olo = __shfl_xor(lo, d, 64), ohi = __shfl_xor(hi, d, 64);
-    lo += olo;
-    hi += ohi + (lo < olo ? 1ull : 0ull);  // (both lanes of a pair see the same carry)
-  }
-  if (lane_id() == 0u) {
-    uint32_t *out = res + 8u + 4u * m;
-    out[0] = (uint32_t)lo;
-    out[1] = (uint32_t)(lo >> 32);
-    out[2] = (uint32_t)hi;
-    out[3] = (uint32_t)(hi >> 32);
-    if ((m & 7u) == 0u) s_empty[m >> 3] = (lo | hi) == 0ull ? 1u : 0u;  // W of set 0 and of set 1
-  }
-  if (m == 0u) {  // (wave-uniform) the counts: at most 2^20 each
-    uint32_t n0 = 0u, n1 = 0u, n2 = 0u, n3 = 0u;
-    for (uint32_t t = lane_id(); t < TL; t += 64u) {
-      const uint32_t *rec = est + 4u * ((size_t)kClSums * TL + t);
-      n0 += rec[0];
-      n1 += rec[1];
-      n2 += rec[2];
-      n3 += rec[3];
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-      n0 += __shfl_xor(n0, d, 64);
-      n1 += __shfl_xor(n1, d, 64);
-      n2 += __shfl_xor(n2, d, 64);
-      n3 += __shfl_xor(n3, d, 64);
-    }
-    if (lane_id() == 0u) {
-      s_cnt[0] = n0;
-      s_cnt[1] = n1;
-      s_cnt[2] = n2;
-      s_cnt[3] = n3;
-    }
-  }
-  __syncthreads();
+  es_finish_sums(grp + l.est, es_tiles(a.P), res, s_cnt, s_empty);
   if (threadIdx.x == 0) {
     const bool over = grp[H_OVER] != 0u;
     const uint32_t nc = grp[H_NC];
@@ -681,14 +540,14 @@ hipError_t launch_clusters(hipStream_t s, const ClustersK &k, const float *poses
                            unsigned long long label_stride, uint32_t *clusters, unsigned long long cluster_stride,
                            uint32_t cluster_cap, uint32_t *result, uint32_t *scratch) {
   if (cl_refused(G, P, k.nx, k.ny, T)) return hipErrorInvalidValue;
-  const uint32_t nb = k.nx * k.ny * T, words = cl_map_words(nb);
+  const uint32_t nb = k.nx * k.ny * T, words = bin_map_words(nb);
   if (pose_stride < 4ull * P || (pose_stride & 3u) || (weights && weight_stride < P) || map_stride < words ||
       bin_stride < P || (labels && label_stride < P) || (clusters && cluster_stride < 4ull * cluster_cap))
     return hipErrorInvalidValue;
   const ClLayout l = cl_layout(nb, P);
   const ClArgs a{k.nx, k.ny, T, nb, k.wrap, P, map, map_stride, scratch};
   const uint32_t word_blocks = (words + kClBlock - 1u) / kClBlock, bin_blocks = (nb + kClBlock - 1u) / kClBlock;
-  const uint32_t rank_blocks = (l.kc + kClBlock - 1u) / kClBlock, tiles = cl_tiles(P);
+  const uint32_t rank_blocks = (l.kc + kClBlock - 1u) / kClBlock, tiles = es_tiles(P);
   hipError_t e;
 #define RPL_CL_LAUNCH(kernel, grid, ...)                                        \
   hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, __VA_ARGS__);            \

@@ -1,5 +1,5 @@
 // rpl_host.hpp — what the host translation units share: rplgpu_api.hip (handle, single scans, batches, clouds,
-// decode, messages, exchange), rplgpu_scan_stages.hip (E9 - E14) and rplgpu_pose_stages.hip (E15 - E21).
+// decode, messages, exchange), rplgpu_scan_stages.hip (E9 - E14) and rplgpu_pose_stages.hip (E15 - E22).
 //
 // Host code only, internal to the library: everything in rpl::host has hidden visibility, so nothing declared here
 // is an exported symbol.  rplgpu_api.hip defines the handle's helpers, rplgpu_scan_stages.hip the scan-stage
@@ -160,6 +160,27 @@ inline bool device_readable(rplgpu_ctx *c, std::initializer_list<PtrCheck> list)
     if ((e.required || e.p) && !device_readable(c, e.p, e.name)) return false;
   return true;
 }
+
+// ---- the pose-list doors ----------------------------------------------------------------------------------------------
+// What the doors of the pose-list stages refuse alike, in parts, because a door tests its pointers between the counts
+// and the strides and the order of its tests is part of what a caller sees.  false: c->err is "<fn>: <what>".
+struct PoseListDoor {
+  rplgpu_ctx *c;
+  const char *fn;
+  bool refuse(const char *what) const {
+    c->err = std::string(fn) + ": " + what;
+    return false;
+  }
+  // (the tiles of a group by the groups: a grid's second dimension)
+  bool groups(uint32_t G) const { return (G != 0 && G <= 65535u) || refuse("G must be in 1 .. 65535"); }
+  bool poses(uint32_t P) const {
+    return (P != 0 && P <= RPLGPU_MAX_POSES) || refuse("P must be in 1 .. RPLGPU_MAX_POSES");
+  }
+  bool strides(uint32_t P, uint64_t pose_stride, const void *weights, uint64_t weight_stride) const {
+    return (pose_stride >= 4ull * P && !(pose_stride & 3u) && (!weights || weight_stride >= P)) ||
+           refuse("pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required");
+  }
+};
 
 // ---- the scan-stage prologue (rplgpu_scan_stages.hip) -----------------------------------------------------------------
 // What E11, E13, E14 and E15 run between their own argument checks and their launches (E9: admit() only).  A stage's

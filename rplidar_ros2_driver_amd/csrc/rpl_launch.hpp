@@ -406,6 +406,8 @@ hipError_t launch_seed(hipStream_t s, const SeedK &k, const int8_t *grid, unsign
 // position bin, a bounded bisection over the quantised edge table in LDS, the wave's marks merged per map word, a
 // device-scope read and a returning atomic OR only where a bit is missing — and the tile's statistics added to the
 // words with integer atomics.  No scratch.
+// the words of a bit map of nb bins (nb <= RPLGPU_MAX_POSE_BINS), on the device and on the host, for E20 and E21
+__host__ __device__ inline uint32_t bin_map_words(uint32_t nb) { return (nb + 31u) >> 5; }
 struct BinsK {
   float origin_x, origin_y, inv_size;
   uint32_t nx, ny;

@@ -27,7 +27,7 @@
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
-#include "rpl_ray.hpp"  // run_behind, shared with rpl_map.hip
+#include "rpl_ray.hpp"  // run_behind, shared with rpl_map.hip; the cell rule (rpl_grid.hpp)
 #include "rpl_xf.hpp"
 
 namespace rpl {
@@ -35,7 +35,6 @@ namespace {
 
 typedef uint32_t mt_u32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kList = 2u * kBlock;  // entries per pass: two samples per thread
-constexpr float kCellLimit = 1048576.0f;
 constexpr int kCellBias = 64;            // cell + kCellBias >= 32 for every listed cell: an entry is never 0
 constexpr uint32_t kCellBits = 13;       // -32 .. 4096 + 31, biased, per axis
 constexpr uint32_t kCellMask = (1u << kCellBits) - 1u;
@@ -44,16 +43,6 @@ static_assert((2u * RPLGPU_MAX_MATCH_SHIFT + 1u) * (2u * RPLGPU_MAX_MATCH_SHIFT 
               "the window does not fit the registers of a workgroup");
 static_assert(RPLGPU_MAX_OCC_DIM + RPLGPU_MAX_MATCH_SHIFT + kCellBias <= (1u << kCellBits), "cell bits");
 static_assert(RPLGPU_MAX_MATCH_SHIFT <= (uint32_t)kCellBias / 2u, "cell bias");
-
-// the E11 cell rule; false: the position has no cell (NaN fails the compares too)
-__device__ __forceinline__ bool match_cell(float x, float y, const MatchK &k, int *cx, int *cy) {
-  const float fu = floorf((x - k.origin_x) / k.resolution);
-  const float fv = floorf((y - k.origin_y) / k.resolution);
-  if (!(fabsf(fu) < kCellLimit && fabsf(fv) < kCellLimit)) return false;
-  *cx = (int)fu;
-  *cy = (int)fv;
-  return true;
-}
 
 // One sample to its list word (biased cell, weight field 0), or 0: not kept, not finite, without a cell, or
 // out of every candidate's reach.
@@ -70,7 +59,7 @@ __device__ __forceinline__ uint32_t match_word(uint32_t lo, uint32_t hi, uint32_
   const float rx = (c * qx - s * qy) + px;
   const float ry = (s * qx + c * qy) + py;
   int cx, cy;
-  if (!match_cell(rx, ry, k, &cx, &cy)) {
+  if (!grid_cell(rx, ry, k.origin_x, k.origin_y, k.resolution, &cx, &cy)) {
     *cell_range = true;
     return 0u;
   }

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(kBlock) void k_occ_walk(
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc((void *)scan, 0, (int)(n * 8u), 0x00020000);
   int x0 = 0, y0 = 0;
-  const bool sensor_ok = occ_cell(sd.xf.tx, sd.xf.ty, k, &x0, &y0);
+  const bool sensor_ok = grid_cell(sd.xf.tx, sd.xf.ty, k.origin_x, k.origin_y, k.resolution, &x0, &y0);
   OccWalk o;
   o.s_win = s_win;
   o.words = reinterpret_cast<uint32_t *>(grid + (size_t)g * grid_stride);

@@ -23,7 +23,7 @@
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
-#include "rpl_ray.hpp"  // occ_cell
+#include "rpl_grid.hpp"
 #include "rpl_xf.hpp"
 
 namespace rpl {
@@ -42,7 +42,7 @@ __device__ __forceinline__ uint32_t pose_look(float x, float y, float c, float s
   const float rx = (c * x - s * y) + tx;
   const float ry = (s * x + c * y) + ty;
   int cx, cy;
-  if (!occ_cell(rx, ry, k, &cx, &cy)) {
+  if (!grid_cell(rx, ry, k.origin_x, k.origin_y, k.resolution, &cx, &cy)) {
     *cell_range = true;
     return 0u;
   }

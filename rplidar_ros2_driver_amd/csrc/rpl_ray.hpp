@@ -5,24 +5,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rpl_grid.hpp"
 #include "rpl_launch.hpp"
 #include "rpl_xf.hpp"
 
 namespace rpl {
 
-constexpr float kRayCellLimit = 1048576.0f;
 constexpr int kRayBias = 16384;              // |end cell - sensor cell| < kRayBias (host-checked spec: <= 8195)
 constexpr uint32_t kRayCut = 1u << 30, kRayMark = 1u << 31;
-
-// the cell rule of the spec; false: the position has no cell (NaN fails the compares too)
-__device__ __forceinline__ bool occ_cell(float x, float y, const OccK &k, int *cx, int *cy) {
-  const float fu = floorf((x - k.origin_x) / k.resolution);
-  const float fv = floorf((y - k.origin_y) / k.resolution);
-  if (!(fabsf(fu) < kRayCellLimit && fabsf(fv) < kRayCellLimit)) return false;
-  *cx = (int)fu;
-  *cy = (int)fv;
-  return true;
-}
 
 // One sample to its ray word, or 0: no ray (not kept, ignored by the range rules, or dropped).
 template <bool FAST>
@@ -44,7 +34,7 @@ __device__ __forceinline__ uint32_t occ_ray(uint32_t lo, uint32_t hi, uint32_t i
     bits = kRayCut;
   }
   int x1, y1;
-  if (!sensor_ok || !occ_cell(ex, ey, k, &x1, &y1)) {
+  if (!sensor_ok || !grid_cell(ex, ey, k.origin_x, k.origin_y, k.resolution, &x1, &y1)) {
     *cell_range = true;
     return 0u;
   }

@@ -24,11 +24,12 @@
 //                  n-th set bit by popcounts of halves (6 steps) — an empty block or word has the prefix of its
 //                  successor and is never the LARGEST such index while r < F; with F substituted the cell is r and
 //                  nothing is read.  Then the float32 steps of the header, each rounded once (this unit is built
-//                  with -ffp-contract=off; `/` is the IEEE divide), the E11 cell rule on the result, one 16-byte
+//                  with -ffp-contract=off; `/` is the IEEE divide), the E11 cell rule (rpl_grid.hpp) on the result, one 16-byte
 //                  store.  A tile's statistics are wave reductions through LDS and thread 0's integer atomics.
 #include <hip/hip_runtime.h>
 
 #include "rpl_device.hpp"
+#include "rpl_grid.hpp"
 #include "rpl_launch.hpp"
 #include "rpl_philox.hpp"
 #include "rplgpu_msg.h"
@@ -42,7 +43,6 @@ constexpr uint32_t kSdTile = kBlock;          // outputs per tile: one per threa
 constexpr uint32_t kSdBlockCells = 4096u;     // cells per index block: four per thread
 constexpr uint32_t kSdBlockWords = 64u;       // mask words per index block
 constexpr uint32_t kSdMaxBlocks = RPLGPU_MAX_OCC_DIM * RPLGPU_MAX_OCC_DIM / kSdBlockCells;
-constexpr float kSdCellLimit = 1048576.0f;
 static_assert(kSdBlockCells == 4u * kBlock && kSdMaxBlocks == 4u * kBlock, "four cells and four blocks per thread");
 
 struct SeedScratch {
@@ -127,16 +127,6 @@ __global__ __launch_bounds__(kBlock) void k_seed_scan(uint32_t cells, uint32_t b
   }
 }
 
-// the E11 cell rule; false: the position has no cell (NaN fails the compares too)
-__device__ __forceinline__ bool sd_cell(float x, float y, float ox, float oy, float res, int *cx, int *cy) {
-  const float fu = floorf((x - ox) / res);
-  const float fv = floorf((y - oy) / res);
-  if (!(fabsf(fu) < kSdCellLimit && fabsf(fv) < kSdCellLimit)) return false;
-  *cx = (int)fu;
-  *cy = (int)fv;
-  return true;
-}
-
 __global__ __launch_bounds__(kBlock) void k_seed_emit(
     float origin_x, float origin_y, float resolution, uint32_t width, uint32_t cells, uint32_t blocks,
     uint32_t centres, uint32_t grid_per_group, const uint2 *__restrict__ headings, uint32_t H, uint32_t M,
@@ -190,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void k_seed_emit(
   const float mx = ux * resolution, my = uy * resolution;
   const float x = origin_x + mx, y = origin_y + my;
   int bx = 0, by = 0;
-  const bool has = sd_cell(x, y, origin_x, origin_y, resolution, &bx, &by);
+  const bool has = grid_cell(x, y, origin_x, origin_y, resolution, &bx, &by);
   const bool off = !(has && bx == (int)cx && by == (int)cy);
   if (live) {
     sd_u32x4 out;

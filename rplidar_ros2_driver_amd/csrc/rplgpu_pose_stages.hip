@@ -73,10 +73,7 @@ static int32_t pose_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32
     h->err = "rplgpu_score_poses_dev: invalid rplgpu_pose_score_t (see include/rplgpu_msg.h)";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_score_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!PoseListDoor{h, "rplgpu_score_poses_dev"}.poses(P)) return RPLGPU_ERR_INVALID_ARG;
   if (pose_stride < 4ull * P || (pose_stride & 3u) || (reinterpret_cast<uintptr_t>(d_poses) & 15u)) {
     h->err = "rplgpu_score_poses_dev: pose_stride must be >= 4 P floats and a multiple of 4, d_poses 16-byte aligned";
     return RPLGPU_ERR_INVALID_ARG;
@@ -141,10 +138,7 @@ int32_t rplgpu_score_poses(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32
     h->err = "rplgpu_score_poses: invalid rplgpu_pose_score_t (see include/rplgpu_msg.h)";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_score_poses: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!PoseListDoor{h, "rplgpu_score_poses"}.poses(P)) return RPLGPU_ERR_INVALID_ARG;
   if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
   RPL_HIP(h, hipSetDevice(h->device));
   const size_t cells_n = (size_t)s->width * s->height, stride = (cells_n + 3u) & ~(size_t)3u;
@@ -255,10 +249,7 @@ int32_t rplgpu_resample_poses_dev(rplgpu_handle_t h, const uint32_t *d_weights, 
                                   float *d_poses_out, uint64_t out_stride, uint32_t *d_ancestors,
                                   uint64_t anc_stride, uint32_t *d_result, uint32_t *d_scratch) {
   if (!h) return RPLGPU_ERR_INVALID_ARG;
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_resample_poses_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!PoseListDoor{h, "rplgpu_resample_poses_dev"}.groups(G)) return RPLGPU_ERR_INVALID_ARG;
   if (P == 0 || P > RPLGPU_MAX_POSES || M == 0 || M > RPLGPU_MAX_POSES) {
     h->err = "rplgpu_resample_poses_dev: P and M must be in 1 .. RPLGPU_MAX_POSES";
     return RPLGPU_ERR_INVALID_ARG;
@@ -373,6 +364,38 @@ static bool estimate_quantise(const float *pose, float xy_scale, int32_t q[4]) {
   return true;
 }
 
+// E17's sums on the host, for E17 and E21: two sets of eight 128-bit sums and two counts (set 0: every pose added, set
+// 1: those the caller says)
+namespace {
+struct EstimateSums {
+  __int128 sum[2][8] = {};
+  uint32_t count[2][2] = {{0, 0}, {0, 0}};
+  // q: the X, Y, C, S of a pose that estimate_quantise admits
+  void add(const int32_t q[4], uint32_t weight, bool in_set1) {
+    const int64_t X = q[0], Y = q[1], C = q[2], S = q[3];
+    const __int128 w = weight;
+    const __int128 term[8] = {w, w * X, w * Y, w * C, w * S, w * (X * X), w * (X * Y), w * (Y * Y)};
+    for (int k = 0; k < (in_set1 ? 2 : 1); ++k) {
+      for (int m = 0; m < 8; ++m) sum[k][m] += term[m];
+      count[k][0] += 1u;
+      count[k][1] += weight != 0 ? 1u : 0u;
+    }
+  }
+  // result words 2 - 5 and 8 - 71; bit k of what it returns: W of set k is zero
+  uint32_t write(uint32_t *result) const {
+    for (int k = 0; k < 2; ++k) {
+      result[2 + 2 * k] = count[k][0];
+      result[3 + 2 * k] = count[k][1];
+      for (int m = 0; m < 8; ++m) {
+        const unsigned __int128 v = (unsigned __int128)sum[k][m];
+        for (int j = 0; j < 4; ++j) result[8 + 32 * k + 4 * m + j] = (uint32_t)(v >> (32 * j));
+      }
+    }
+    return (sum[0][0] == 0 ? 1u : 0u) | (sum[1][0] == 0 ? 2u : 0u);
+  }
+};
+}  // namespace
+
 int32_t rplgpu_estimate_host(const float *poses, uint32_t P, const uint32_t *weights,
                              const rplgpu_pose_estimate_t *s, uint32_t center, uint32_t result[72]) {
   if (!poses || !result || rplgpu_pose_estimate_check(s) != RPLGPU_OK || P == 0 || P > RPLGPU_MAX_POSES)
@@ -380,35 +403,19 @@ int32_t rplgpu_estimate_host(const float *poses, uint32_t P, const uint32_t *wei
   const uint32_t qc = std::min(center, P - 1u);
   int32_t c[4] = {0, 0, 0, 0};
   const bool c_in = estimate_quantise(poses + 4u * (size_t)qc, s->xy_scale, c);
-  __int128 sum[2][8] = {};
-  uint32_t count[2][2] = {{0, 0}, {0, 0}};
+  EstimateSums sums;
   for (uint32_t i = 0; i < P; ++i) {
     int32_t q[4];
     if (!estimate_quantise(poses + 4u * (size_t)i, s->xy_scale, q)) continue;
-    const int64_t X = q[0], Y = q[1], C = q[2], S = q[3];
-    const int64_t dX = X - c[0], dY = Y - c[1];
-    const bool gate = c_in && (uint64_t)(dX * dX + dY * dY) <= s->gate_r2 && C * c[2] + S * c[3] >= s->gate_dot;
-    const __int128 w = weights ? weights[i] : 1u;
-    const __int128 term[8] = {w, w * X, w * Y, w * C, w * S, w * (X * X), w * (X * Y), w * (Y * Y)};
-    for (int k = 0; k < (gate ? 2 : 1); ++k) {
-      for (int m = 0; m < 8; ++m) sum[k][m] += term[m];
-      count[k][0] += 1u;
-      count[k][1] += w != 0 ? 1u : 0u;
-    }
+    const int64_t dX = (int64_t)q[0] - c[0], dY = (int64_t)q[1] - c[1];
+    const bool gate = c_in && (uint64_t)(dX * dX + dY * dY) <= s->gate_r2 &&
+                      (int64_t)q[2] * c[2] + (int64_t)q[3] * c[3] >= s->gate_dot;
+    sums.add(q, weights ? weights[i] : 1u, gate);
   }
-  result[0] = (c_in ? 0u : 1u) | (count[0][0] != P ? 2u : 0u) | (sum[0][0] == 0 ? 4u : 0u) | (sum[1][0] == 0 ? 8u : 0u);
+  const uint32_t empty = sums.write(result);
+  result[0] = (c_in ? 0u : 1u) | (result[2] != P ? 2u : 0u) | empty << 2;
   result[1] = qc;
-  result[2] = count[0][0];
-  result[3] = count[0][1];
-  result[4] = count[1][0];
-  result[5] = count[1][1];
   result[6] = result[7] = 0u;
-  for (int k = 0; k < 2; ++k) {
-    for (int m = 0; m < 8; ++m) {
-      const unsigned __int128 v = (unsigned __int128)sum[k][m];
-      for (int j = 0; j < 4; ++j) result[8 + 32 * k + 4 * m + j] = (uint32_t)(v >> (32 * j));
-    }
-  }
   return RPLGPU_OK;
 }
 
@@ -443,24 +450,15 @@ int32_t rplgpu_estimate_poses_dev(rplgpu_handle_t h, const float *d_poses, uint6
     h->err = "rplgpu_estimate_poses_dev: invalid rplgpu_pose_estimate_t (see include/rplgpu_msg.h)";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_estimate_poses_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_estimate_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  const PoseListDoor door{h, "rplgpu_estimate_poses_dev"};
+  if (!door.groups(G) || !door.poses(P)) return RPLGPU_ERR_INVALID_ARG;
   if (!d_poses || !d_result || !d_scratch || misaligned(d_poses, 15) || misaligned(d_result, 3) || misaligned(d_scratch, 7) ||
       misaligned(d_weights, 3) || misaligned(d_center, 3)) {
     h->err = "rplgpu_estimate_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for the "
              "pose list, 8 for d_scratch, 4 otherwise)";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (pose_stride < 4ull * P || (pose_stride & 3u) || (d_weights && weight_stride < P)) {
-    h->err = "rplgpu_estimate_poses_dev: pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!door.strides(P, pose_stride, d_weights, weight_stride)) return RPLGPU_ERR_INVALID_ARG;
   if (d_center && center_stride == 0 && G > 1u) {
     h->err = "rplgpu_estimate_poses_dev: center_stride must not be 0 with more than one group";
     return RPLGPU_ERR_INVALID_ARG;
@@ -482,10 +480,7 @@ int32_t rplgpu_estimate_poses(rplgpu_handle_t h, const float *poses, uint32_t P,
     h->err = "rplgpu_estimate_poses: invalid rplgpu_pose_estimate_t (see include/rplgpu_msg.h)";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_estimate_poses: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!PoseListDoor{h, "rplgpu_estimate_poses"}.poses(P)) return RPLGPU_ERR_INVALID_ARG;
   RPL_HIP(h, hipSetDevice(h->device));
   // poses | weights | scratch | centre + result
   DoorBuffer buf(h, "rplgpu_estimate_poses");
@@ -648,10 +643,7 @@ int32_t rplgpu_sample_motion_dev(rplgpu_handle_t h, const float *d_odom, uint32_
     h->err = "rplgpu_sample_motion_dev: the rplgpu_motion_noise_t is missing";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_sample_motion_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!PoseListDoor{h, "rplgpu_sample_motion_dev"}.groups(G)) return RPLGPU_ERR_INVALID_ARG;
   if (M == 0 || M > RPLGPU_MAX_POSES) {
     h->err = "rplgpu_sample_motion_dev: M must be in 1 .. RPLGPU_MAX_POSES";
     return RPLGPU_ERR_INVALID_ARG;
@@ -741,10 +733,11 @@ int32_t rplgpu_seed_headings(uint32_t H, float *cs) {
   return RPLGPU_OK;
 }
 
-// the E11 cell rule on the host: float32, every operation rounded once (this unit is built with -ffp-contract=off)
-static bool seed_cell(float x, float y, const rplgpu_pose_seed_t *s, int32_t *cx, int32_t *cy) {
-  const float du = x - s->origin_x, dv = y - s->origin_y;
-  const float u = du / s->resolution, v = dv / s->resolution;
+// the E11 cell rule on the host, for E19 and E22: float32, every operation rounded once (this unit is built with
+// -ffp-contract=off)
+static bool host_cell(float x, float y, float origin_x, float origin_y, float resolution, int32_t *cx, int32_t *cy) {
+  const float du = x - origin_x, dv = y - origin_y;
+  const float u = du / resolution, v = dv / resolution;
   const float fu = std::floor(u), fv = std::floor(v);
   if (!(std::fabs(fu) < 1048576.0f && std::fabs(fv) < 1048576.0f)) return false;
   *cx = (int32_t)fu;
@@ -797,7 +790,8 @@ int32_t rplgpu_seed_poses_host(const rplgpu_pose_seed_t *s, const int8_t *grid, 
     const float mx = ux * s->resolution, my = uy * s->resolution;
     const float x = s->origin_x + mx, y = s->origin_y + my;
     int32_t bx = 0, by = 0;
-    if (!(seed_cell(x, y, s, &bx, &by) && bx == (int32_t)cx && by == (int32_t)cy)) ++off;
+    if (!(host_cell(x, y, s->origin_x, s->origin_y, s->resolution, &bx, &by) && bx == (int32_t)cx && by == (int32_t)cy))
+      ++off;
     lo = std::min(lo, cell[j]);
     hi = std::max(hi, cell[j]);
     std::memcpy(poses_out + 4u * (size_t)j, headings + 2u * (size_t)k, 8);  // bit for bit
@@ -828,10 +822,7 @@ int32_t rplgpu_seed_poses_dev(rplgpu_handle_t h, const rplgpu_pose_seed_t *s, co
     h->err = "rplgpu_seed_poses_dev: the rplgpu_motion_noise_t is missing";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_seed_poses_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!PoseListDoor{h, "rplgpu_seed_poses_dev"}.groups(G)) return RPLGPU_ERR_INVALID_ARG;
   if (M == 0 || M > RPLGPU_MAX_POSES) {
     h->err = "rplgpu_seed_poses_dev: M must be in 1 .. RPLGPU_MAX_POSES";
     return RPLGPU_ERR_INVALID_ARG;
@@ -950,7 +941,7 @@ uint64_t rplgpu_bin_map_words(uint32_t nx, uint32_t ny, uint32_t T) {
   s.nx = nx;
   s.ny = ny;
   if (rplgpu_pose_bins_check(&s, T) != RPLGPU_OK) return 0;
-  const uint64_t words = ((uint64_t)nx * ny * T + 31u) >> 5;
+  const uint64_t words = rpl::bin_map_words(nx * ny * T);  // (checked: at most RPLGPU_MAX_POSE_BINS bins)
   return (words + 1u) & ~(uint64_t)1u;
 }
 
@@ -991,7 +982,7 @@ int32_t rplgpu_bin_poses_host(const rplgpu_pose_bins_t *s, const float *poses, u
   if (rplgpu_pose_bins_check(s, T) != RPLGPU_OK || !poses || !edges || !map || !result || P == 0 ||
       P > RPLGPU_MAX_POSES)
     return RPLGPU_ERR_INVALID_ARG;
-  const uint32_t nb = s->nx * s->ny * T, words = (nb + 31u) >> 5;
+  const uint32_t nb = s->nx * s->ny * T, words = rpl::bin_map_words(nb);
   const bool keep = (s->flags & 1u) != 0;
   if (!keep) std::memset(map, 0, 4u * (size_t)words);
   std::vector<int32_t> eq(2u * (size_t)T);
@@ -1054,25 +1045,16 @@ int32_t rplgpu_bin_poses_dev(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, con
     h->err = "rplgpu_bin_poses_dev: the rplgpu_pose_bins_t is missing or rplgpu_pose_bins_check refuses it or T";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_bin_poses_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_bin_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  const PoseListDoor door{h, "rplgpu_bin_poses_dev"};
+  if (!door.groups(G) || !door.poses(P)) return RPLGPU_ERR_INVALID_ARG;
   if (!d_poses || !d_edges || !d_map || !d_result || misaligned(d_poses, 15) || misaligned(d_edges, 7) || misaligned(d_map, 7) ||
       misaligned(d_weights, 3) || misaligned(d_bins_out, 3) || misaligned(d_result, 3)) {
     h->err = "rplgpu_bin_poses_dev: a required pointer is missing or a pointer is misaligned (16 bytes for d_poses, "
              "8 for d_edges and d_map, 4 for d_weights, d_bins_out and d_result)";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (pose_stride < 4ull * P || (pose_stride & 3u) || (d_weights && weight_stride < P)) {
-    h->err = "rplgpu_bin_poses_dev: pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const uint64_t words = ((uint64_t)s->nx * s->ny * T + 31u) >> 5;
+  if (!door.strides(P, pose_stride, d_weights, weight_stride)) return RPLGPU_ERR_INVALID_ARG;
+  const uint64_t words = rpl::bin_map_words(s->nx * s->ny * T);
   if (map_stride < words || (map_stride & 1u)) {
     h->err = "rplgpu_bin_poses_dev: map_stride >= ceil(nx * ny * T / 32) and even is required";
     return RPLGPU_ERR_INVALID_ARG;
@@ -1106,13 +1088,10 @@ int32_t rplgpu_bin_poses(rplgpu_handle_t h, const rplgpu_pose_bins_t *s, const f
     h->err = "rplgpu_bin_poses: the rplgpu_pose_bins_t is missing or rplgpu_pose_bins_check refuses it or T";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_bin_poses: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!PoseListDoor{h, "rplgpu_bin_poses"}.poses(P)) return RPLGPU_ERR_INVALID_ARG;
   RPL_HIP(h, hipSetDevice(h->device));
   // result | edges | map | weights | bins | poses
-  const size_t words = ((size_t)s->nx * s->ny * T + 31u) >> 5, stride = (size_t)rplgpu_bin_map_words(s->nx, s->ny, T);
+  const size_t words = rpl::bin_map_words(s->nx * s->ny * T), stride = (size_t)rplgpu_bin_map_words(s->nx, s->ny, T);
   DoorBuffer buf(h, "rplgpu_bin_poses");
   const size_t o_res = buf.part(32), o_edge = buf.part(8u * (size_t)T), o_map = buf.part(4u * stride),
                o_wt = buf.part_if(weights, 4u * (size_t)P), o_bins = buf.part_if(bins_out, 4u * (size_t)P),
@@ -1274,34 +1253,16 @@ int32_t rplgpu_cluster_poses_host(const rplgpu_pose_clusters_t *s, const float *
       clusters_out[4u * c + 3u] = (uint32_t)(W[c] >> 32);
     }
   }
-  __int128 sum[2][8] = {};
-  uint32_t n[2][2] = {{0, 0}, {0, 0}};
+  EstimateSums sums;
   for (uint32_t i = 0; i < P; ++i) {
     if (pose_cluster[i] == none) continue;
     int32_t q[4];
     estimate_quantise(poses + 4u * (size_t)i, s->xy_scale, q);
-    const int64_t X = q[0], Y = q[1], C = q[2], S = q[3];
-    const __int128 w = weights ? weights[i] : 1u;
-    const __int128 term[8] = {w, w * X, w * Y, w * C, w * S, w * (X * X), w * (X * Y), w * (Y * Y)};
-    for (int k = 0; k < (pose_cluster[i] == best ? 2 : 1); ++k) {
-      for (int m = 0; m < 8; ++m) sum[k][m] += term[m];
-      n[k][0] += 1u;
-      n[k][1] += w != 0 ? 1u : 0u;
-    }
+    sums.add(q, weights ? weights[i] : 1u, pose_cluster[i] == best);
   }
-  result[0] = (nc == 0 ? 1u : 0u) | flags | (sum[0][0] == 0 ? 4u : 0u) | (sum[1][0] == 0 ? 8u : 0u);
+  result[0] = (nc == 0 ? 1u : 0u) | flags | sums.write(result) << 2;
   result[1] = best != none ? label[best] : none;
-  result[2] = n[0][0];
-  result[3] = n[0][1];
-  result[4] = n[1][0];
-  result[5] = n[1][1];
   result[6] = nc;
-  for (int k = 0; k < 2; ++k) {
-    for (int m = 0; m < 8; ++m) {
-      const unsigned __int128 v = (unsigned __int128)sum[k][m];
-      for (int j = 0; j < 4; ++j) result[8 + 32 * k + 4 * m + j] = (uint32_t)(v >> (32 * j));
-    }
-  }
   if (second != none) {
     result[72] = label[second];
     result[73] = count[second];
@@ -1325,14 +1286,8 @@ int32_t rplgpu_cluster_poses_dev(rplgpu_handle_t h, const rplgpu_pose_clusters_t
     h->err = "rplgpu_cluster_poses_dev: the rplgpu_pose_clusters_t is missing or rplgpu_pose_clusters_check refuses it or T";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_cluster_poses_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_cluster_poses_dev: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  const PoseListDoor door{h, "rplgpu_cluster_poses_dev"};
+  if (!door.groups(G) || !door.poses(P)) return RPLGPU_ERR_INVALID_ARG;
   if (!d_poses || !d_map || !d_bins || !d_result || !d_scratch || misaligned(d_poses, 15) || misaligned(d_map, 7) ||
       misaligned(d_scratch, 7) || misaligned(d_weights, 3) || misaligned(d_bins, 3) || misaligned(d_labels_out, 3) ||
       misaligned(d_clusters, 3) || misaligned(d_result, 3)) {
@@ -1340,11 +1295,8 @@ int32_t rplgpu_cluster_poses_dev(rplgpu_handle_t h, const rplgpu_pose_clusters_t
              "8 for d_map and d_scratch, 4 otherwise)";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (pose_stride < 4ull * P || (pose_stride & 3u) || (d_weights && weight_stride < P)) {
-    h->err = "rplgpu_cluster_poses_dev: pose_stride >= 4 P and a multiple of 4 and weight_stride >= P are required";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  const uint64_t words = ((uint64_t)s->nx * s->ny * T + 31u) >> 5;
+  if (!door.strides(P, pose_stride, d_weights, weight_stride)) return RPLGPU_ERR_INVALID_ARG;
+  const uint64_t words = rpl::bin_map_words(s->nx * s->ny * T);
   if (map_stride < words || (map_stride & 1u)) {
     h->err = "rplgpu_cluster_poses_dev: map_stride >= ceil(nx * ny * T / 32) and even is required";
     return RPLGPU_ERR_INVALID_ARG;
@@ -1402,13 +1354,10 @@ int32_t rplgpu_cluster_poses(rplgpu_handle_t h, const rplgpu_pose_clusters_t *s,
     h->err = "rplgpu_cluster_poses: the rplgpu_pose_clusters_t is missing or rplgpu_pose_clusters_check refuses it or T";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (P == 0 || P > RPLGPU_MAX_POSES) {
-    h->err = "rplgpu_cluster_poses: P must be in 1 .. RPLGPU_MAX_POSES";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!PoseListDoor{h, "rplgpu_cluster_poses"}.poses(P)) return RPLGPU_ERR_INVALID_ARG;
   RPL_HIP(h, hipSetDevice(h->device));
   // result | map | weights | bins | labels | table | scratch | poses
-  const size_t words = ((size_t)s->nx * s->ny * T + 31u) >> 5, stride = (size_t)rplgpu_bin_map_words(s->nx, s->ny, T);
+  const size_t words = rpl::bin_map_words(s->nx * s->ny * T), stride = (size_t)rplgpu_bin_map_words(s->nx, s->ny, T);
   const bool table = clusters_out && cluster_cap != 0;
   DoorBuffer buf(h, "rplgpu_cluster_poses");
   const size_t o_res = buf.part(4u * RPLGPU_CLUSTER_WORDS), o_map = buf.part(4u * stride),
@@ -1494,17 +1443,6 @@ double rplgpu_cast_range_m(uint32_t word, float resolution) {
   return std::sqrt((double)(word & 0x0FFFFFFFu)) * (double)resolution;
 }
 
-// the E11 cell rule on the host (seed_cell with this stage's spec)
-static bool cast_cell(float x, float y, const rplgpu_range_cast_t *s, int32_t *cx, int32_t *cy) {
-  const float du = x - s->origin_x, dv = y - s->origin_y;
-  const float u = du / s->resolution, v = dv / s->resolution;
-  const float fu = std::floor(u), fv = std::floor(v);
-  if (!(std::fabs(fu) < 1048576.0f && std::fabs(fv) < 1048576.0f)) return false;
-  *cx = (int32_t)fu;
-  *cy = (int32_t)fv;
-  return true;
-}
-
 // one ray by the header's rule; *n_out: the visit at which it stopped (0 for a dropped ray)
 static uint32_t cast_ray(const rplgpu_range_cast_t *s, const float *pose, const float *beam, const int8_t *grid,
                          uint32_t *n_out) {
@@ -1516,7 +1454,9 @@ static uint32_t cast_ray(const rplgpu_range_cast_t *s, const float *pose, const 
   const float ex = tx + mx, ey = ty + my;
   int32_t x0, y0, x1, y1;
   *n_out = 0;
-  if (!cast_cell(tx, ty, s, &x0, &y0) || !cast_cell(ex, ey, s, &x1, &y1)) return RPLGPU_CAST_DROPPED;
+  if (!host_cell(tx, ty, s->origin_x, s->origin_y, s->resolution, &x0, &y0) ||
+      !host_cell(ex, ey, s->origin_x, s->origin_y, s->resolution, &x1, &y1))
+    return RPLGPU_CAST_DROPPED;
   const int32_t ax = std::abs(x1 - x0), ay = std::abs(y1 - y0);
   const int32_t stepx = (x1 > x0) - (x1 < x0), stepy = (y1 > y0) - (y1 < y0);
   int32_t err = ax - ay, x = x0, y = y0;
@@ -1641,10 +1581,7 @@ int32_t rplgpu_cast_ranges_dev(rplgpu_handle_t h, const rplgpu_range_cast_t *s, 
     h->err = "rplgpu_cast_ranges_dev: the rplgpu_range_cast_t is missing or rplgpu_range_cast_check refuses it";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (G == 0 || G > 65535u) {  // (the tiles of a group by the groups: a grid's second dimension)
-    h->err = "rplgpu_cast_ranges_dev: G must be in 1 .. 65535";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!PoseListDoor{h, "rplgpu_cast_ranges_dev"}.groups(G)) return RPLGPU_ERR_INVALID_ARG;
   if (P == 0 || P > RPLGPU_MAX_POSES || A == 0 || A > RPLGPU_MAX_MERGE_BEAMS ||
       (uint64_t)P * A > RPLGPU_MAX_CAST_RAYS) {
     h->err = "rplgpu_cast_ranges_dev: P must be in 1 .. RPLGPU_MAX_POSES, A in 1 .. RPLGPU_MAX_MERGE_BEAMS and "
