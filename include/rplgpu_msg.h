@@ -1444,6 +1444,111 @@ int32_t rplgpu_cast_ranges(rplgpu_handle_t h, const rplgpu_range_cast_t *s, cons
                            uint32_t meas_count, uint32_t meas_first, uint32_t meas_step, const uint8_t *table,
                            uint32_t *ranges_out, uint32_t *weights_out, uint32_t result[8], uint32_t cast[8]);
 
+/* ---- E23: the beams a pose list disagrees with are left out of the weights (row 4; AMCL's beam skip) ----
+ * E15 adds every point's field value into every pose's weight.  A return from something the map does not hold (a
+ * person, a trolley) lands far from every obstacle at almost every pose of the list: it lowers every weight by the
+ * same amount and the list loses contrast exactly when the room is busy.  AMCL's likelihood_field_prob model counts,
+ * per beam, at how many particles the beam lands near an obstacle, leaves out the beams too few particles agree
+ * with, and falls back to all beams when too many would go (the filter has then probably converged on a wrong
+ * pose).  The per-beam count is a reduction ACROSS the pose list of all poses x points look-ups, which only the
+ * device ever sees, so it cannot be done from outside E15.  The mask that comes out is worth having on its own: the
+ * returns the map does not explain, that is, the moving obstacles.  Nothing in the reference does this, so these
+ * rules ARE the definition (parity unpinned, as E5-E22).  All integers behind E15's float32 pose transform:
+ * byte-exact, order-free, chainable.
+ *
+ * f(q, i): E15's field value of sample i at pose q, exactly — the same points (E1, E5, E2, E6, the mount pose), the
+ * same transform without FMA, the E11 cell rule, 0 outside the grid, 0 for an unknown (negative) byte, 0 (and
+ * RPLGPU_SCAN_CELL_RANGE) for a position without a cell.  P is the whole list of the group, whatever its poses are.
+ *   AGREE   a look-up of sample i at pose q agrees iff f(q, i) >= agree_lo (1 .. 127).  A pose at which the sample
+ *           has no cell simply does not agree, and stays in P.
+ *   COUNT   count[i] = the number of poses q in [0, P) that agree; 0 for a sample that E1 or E5 drops, that is not
+ *           finite, or that lies at or beyond the scan's clamped length min(n, n_stride).
+ *   KEEP    a finite sample is kept by the rule iff (uint64)count[i] * keep_den > (uint64)keep_num * P: strict, as
+ *           AMCL's obs_count / total > beam_skip_threshold.  1 <= keep_den <= 2^20, keep_num <= keep_den.
+ *   FALL BACK  with F the group's finite points and K those kept by the rule, the group falls back iff F > 0 and
+ *           (uint64)(F - K) * err_den >= (uint64)err_num * F: AMCL's skipped >= beams * beam_skip_error_threshold.
+ *           1 <= err_den <= 2^20, err_num <= 2^20.  err_num == 0: every group with a finite point falls back, the
+ *           stage is off.  err_num > err_den: no group ever does.
+ *   WEIGHT  d_weights[g * weight_stride + q] = the sum of f(q, i) over the samples that ENTERED the weights: all F
+ *           finite ones when the group fell back, else the K kept ones.  E15's layout, bound (group * n_stride <=
+ *           2^24) and result words: d_result + 8 g holds E15's eight words computed from these weights, word 4 stays
+ *           the number of finite points.  E16, E17, E20 and E21 take both unchanged.
+ * OUTPUTS besides d_weights, d_result and d_status (E15's rules and refusals for all of them and for the points,
+ * groups, pose list and field):
+ *   d_counts[sc * count_stride + i], uint32, count_stride >= n_stride: count[i] of scan sc.  Every word [0, n_stride)
+ *           of every scan of the call is written; words beyond are never changed.
+ *   d_mask[sc * mask_stride + (i >> 5)] bit (i & 31): E5's keep-mask layout, mask_stride >= ceil(n_stride / 32).  1 iff
+ *           the sample is finite and kept by the rule — the RULE's mask whether or not the group falls back, so it
+ *           stays usable as the detection of what the map does not explain.  Every word [0, ceil(n_stride / 32)) of
+ *           every scan is written; bits at and beyond n_stride are 0.
+ *   d_agree + 8 g, eight words per group:
+ *     0      F, the group's finite points
+ *     1      K, those kept by the rule
+ *     2      1 iff the group fell back
+ *     3      the samples that entered the weights (F on a fallback, else K)
+ *     4      the largest count
+ *     5      the smallest count over the finite samples (0 when F = 0)
+ *     6, 7   the sum of all counts, low and high word (up to 2^44)
+ * FOUR IDENTITIES follow from the rules and hold the kernels of this stage to E15's:
+ *   (1) with err_num = 0 the weights and d_result equal rplgpu_score_poses_dev's on the same inputs, byte for byte;
+ *   (2) with a field of bytes 0 and 1 only and agree_lo = 1, words 6 and 7 of d_agree equal words 6 and 7 of E15's
+ *       result (every agreeing look-up adds exactly 1 to one weight);
+ *   (3) with P = 1, agree_lo = 1, keep_num = 0 and err_num > err_den the weight equals E15's, and the mask is exactly
+ *       the set of samples with f >= 1;
+ *   (4) with E5 off, for a group that did not fall back, the weights equal E15's on a copy of the batch in which every
+ *       skipped sample (finite, mask bit 0) is replaced by a node E1 drops (distance 0).
+ * d_counts, d_mask and d_agree are required, 4-byte aligned device memory.  RPLGPU_ERR_INVALID_ARG for everything
+ * rplgpu_score_poses_dev refuses, a spec the check refuses, count_stride below n_stride and mask_stride below
+ * ceil(n_stride / 32).  A refused call changes no output.  Asynchronous on the handle's stream; nothing is stored
+ * on the handle, the call's scratch is its outputs. */
+typedef struct rplgpu_beam_agree {
+  float    origin_x, origin_y;   /* the field's grid: as rplgpu_pose_score_t */
+  float    resolution;
+  uint32_t width, height;        /* 1 .. RPLGPU_MAX_OCC_DIM */
+  int32_t  agree_lo;             /* 1 .. 127 */
+  uint32_t keep_num, keep_den;   /* 1 <= keep_den <= 2^20, keep_num <= keep_den */
+  uint32_t err_num, err_den;     /* 1 <= err_den <= 2^20, err_num <= 2^20 */
+} rplgpu_beam_agree_t;
+#define RPLGPU_AGREE_MAX_DEN 1048576u
+/* E11's default grid, agree_lo 1, keep 3 / 10 and err 9 / 10 (AMCL's beam_skip_threshold 0.3 and
+ * beam_skip_error_threshold 0.9) */
+void rplgpu_default_beam_agree(rplgpu_beam_agree_t *s);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL, a grid rplgpu_pose_score_check refuses,
+ * agree_lo outside [1, 127], keep_den or err_den of 0 or above 2^20, keep_num above keep_den, err_num above 2^20.
+ * The device path uses this function. */
+int32_t rplgpu_beam_agree_check(const rplgpu_beam_agree_t *s);
+int32_t rplgpu_score_poses_agree_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                                     const uint32_t *d_n_per_scan, uint32_t B, uint32_t group,
+                                     const rplgpu_params_t *p, const float *d_motion, const float *d_pose2d,
+                                     const rplgpu_beam_agree_t *s, const float *d_poses, uint32_t P,
+                                     uint64_t pose_stride, uint32_t poses_per_group, const int8_t *d_field,
+                                     uint64_t field_stride, uint32_t field_per_group, uint32_t *d_weights,
+                                     uint64_t weight_stride, uint32_t *d_result, uint32_t *d_status,
+                                     uint32_t *d_counts, uint64_t count_stride, uint32_t *d_mask,
+                                     uint64_t mask_stride, uint32_t *d_agree);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp), shaped as rplgpu_score_poses: counts_out
+ * (optional): n_scans * n_stride words; mask_out (optional): n_scans * ceil(n_stride / 32) words; agree: 8 words.
+ * Allocates its device buffers per call and returns when the results are in place. */
+int32_t rplgpu_score_poses_agree(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                                 const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                                 const float *motion, const float *pose2d, const float *t0,
+                                 const rplgpu_beam_agree_t *s, const float *poses, uint32_t P, const int8_t *field,
+                                 uint32_t *weights_out, uint32_t result[8], uint32_t *status, uint32_t *counts_out,
+                                 uint32_t *mask_out, uint32_t agree[8]);
+/* Host only (no handle, no device): the same rule in plain C++ for ONE group, over POINTS — the definition a reader
+ * can run, and a node's fallback without a device.  Point k is (x[k], y[k]) in the base frame (what E15's front end
+ * makes of a sample that E1 and E5 keep; it may be not finite) and belongs to sample index[k] of scan slot[k]; each
+ * (slot, index) appears at most once.  poses: 4 P floats; field: width * height bytes.  counts_out: n_scans *
+ * n_stride words, mask_out: n_scans * ceil(n_stride / 32) words, weights_out: P words, result: 8, agree: 8, all
+ * required and written whole; status (optional): RPLGPU_SCAN_CELL_RANGE or 0.  RPLGPU_ERR_INVALID_ARG and nothing
+ * written for a spec the check refuses, a NULL pointer (x, y, slot, index only with n_points > 0), P = 0 or above
+ * RPLGPU_MAX_POSES, n_scans = 0, n_stride = 0, n_scans * n_stride above 2^24, or a slot / index out of range. */
+int32_t rplgpu_beam_agree_points_host(const float *x, const float *y, const uint32_t *slot, const uint32_t *index,
+                                      uint32_t n_points, uint32_t n_scans, uint32_t n_stride, const float *poses,
+                                      uint32_t P, const int8_t *field, const rplgpu_beam_agree_t *s,
+                                      uint32_t *counts_out, uint32_t *mask_out, uint32_t *weights_out,
+                                      uint32_t result[8], uint32_t agree[8], uint32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,11 @@ ABI_SYMBOLS = [
     "rplgpu_cast_ranges_dev",
     "rplgpu_cast_ranges_host",
     "rplgpu_cast_ranges",
+    "rplgpu_default_beam_agree",
+    "rplgpu_beam_agree_check",
+    "rplgpu_score_poses_agree_dev",
+    "rplgpu_score_poses_agree",
+    "rplgpu_beam_agree_points_host",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -604,6 +609,38 @@ class RangeCast(C.Structure):
         return int(load_library().rplgpu_range_cast_check(C.byref(self)))
 
 
+class BeamAgree(C.Structure):
+    """Mirror of ``rplgpu_beam_agree_t`` (E23: the beams a pose list disagrees with are left out of the weights)."""
+
+    _fields_ = [
+        ("origin_x", C.c_float),
+        ("origin_y", C.c_float),
+        ("resolution", C.c_float),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("agree_lo", C.c_int32),
+        ("keep_num", C.c_uint32),
+        ("keep_den", C.c_uint32),
+        ("err_num", C.c_uint32),
+        ("err_den", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "BeamAgree":
+        """The library's own defaults (``rplgpu_default_beam_agree``), then the overrides."""
+        s = cls()
+        load_library().rplgpu_default_beam_agree(C.byref(s))
+        for k, v in kw.items():
+            if not hasattr(s, k):
+                raise AttributeError(k)
+            setattr(s, k, v)
+        return s
+
+    def check(self) -> int:
+        """``rplgpu_beam_agree_check``: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_beam_agree_check(C.byref(self)))
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -860,6 +897,16 @@ def load_library() -> C.CDLL:
                                             vp, vp]
     lib.rplgpu_cast_ranges.argtypes = [vp, C.POINTER(RangeCast), vp, u32, vp, u32, vp, vp, u32, u32, u32, vp, vp, vp,
                                        vp, vp]
+    lib.rplgpu_default_beam_agree.argtypes = [C.POINTER(BeamAgree)]
+    lib.rplgpu_default_beam_agree.restype = None
+    lib.rplgpu_beam_agree_check.argtypes = [C.POINTER(BeamAgree)]
+    lib.rplgpu_score_poses_agree_dev.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp,
+                                                 C.POINTER(BeamAgree), vp, u32, u64, u32, vp, u64, u32, vp, u64, vp,
+                                                 vp, vp, u64, vp, u64, vp]
+    lib.rplgpu_score_poses_agree.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp,
+                                             C.POINTER(BeamAgree), vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.rplgpu_beam_agree_points_host.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u32, vp, C.POINTER(BeamAgree),
+                                                  vp, vp, vp, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1299,6 +1346,50 @@ class RplGpu:
             C.byref(spec), poses.ctypes.data, P, field.ctypes.data, ptr(weights), result.ctypes.data,
             status.ctypes.data))
         return weights, result, int(status[0])
+
+    def score_poses_agree_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int,
+                              params: Params, d_motion: int, d_pose2d: int, spec: "BeamAgree", d_poses: int, P: int,
+                              pose_stride: int, poses_per_group: int, d_field: int, field_stride: int,
+                              field_per_group: int, d_weights: int, weight_stride: int, d_result: int, d_status: int,
+                              d_counts: int, count_stride: int, d_mask: int, mask_stride: int, d_agree: int):
+        """E23: ``score_poses_dev`` without the samples the pose list disagrees with (AMCL's beam skip): besides the
+        weights and result words, per scan the counts (uint32, n_stride words, count_stride apart) and the keep mask
+        (ceil(n_stride / 32) words, mask_stride apart), and eight agree words at d_agree + 8 g."""
+        self._check(self._lib.rplgpu_score_poses_agree_dev(
+            self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d, C.byref(spec),
+            d_poses, P, pose_stride, poses_per_group, d_field, field_stride, field_per_group, d_weights,
+            weight_stride, d_result, d_status, d_counts, count_stride, d_mask, mask_stride, d_agree))
+
+    def score_poses_agree(self, scans: np.ndarray, lens, params: Params, spec: "BeamAgree", poses: np.ndarray,
+                          field: np.ndarray, motion=None, pose2d=None, t0=None):
+        """E23, one group, host buffers, arguments as ``score_poses`` -> ``(weights (P,) uint32, result (8,) uint32,
+        status, counts (S, n) uint32, mask (S, ceil(n / 32)) uint32, agree (8,) uint32)``."""
+        scans = np.ascontiguousarray(scans)
+        if scans.dtype != NODE_DTYPE or scans.ndim != 2:
+            raise TypeError("scans must be a 2-D array of abi.NODE_DTYPE")
+        field = np.ascontiguousarray(field, np.int8)
+        if field.shape != (spec.height, spec.width):
+            raise TypeError("field must be a (height, width) int8 array")
+        poses = np.ascontiguousarray(poses, np.float32)
+        if poses.ndim != 2 or poses.shape[1] != 4:
+            raise TypeError("poses must be a (P, 4) float32 array")
+        S, n = scans.shape
+        P = len(poses)
+        lens = np.ascontiguousarray(lens, np.uint32)
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
+        motion, pose2d, t0 = f32(motion), f32(pose2d), f32(t0)
+        weights = np.zeros(P, np.uint32)
+        result = np.zeros(8, np.uint32)
+        status = np.zeros(1, np.uint32)
+        counts = np.zeros((S, n), np.uint32)
+        mask = np.zeros((S, (n + 31) // 32), np.uint32)
+        agree = np.zeros(8, np.uint32)
+        ptr = lambda a: 0 if a is None else a.ctypes.data  # noqa: E731
+        self._check(self._lib.rplgpu_score_poses_agree(
+            self._h, scans.ctypes.data, n, lens.ctypes.data, S, C.byref(params), ptr(motion), ptr(pose2d), ptr(t0),
+            C.byref(spec), poses.ctypes.data, P, field.ctypes.data, weights.ctypes.data, result.ctypes.data,
+            status.ctypes.data, counts.ctypes.data, mask.ctypes.data, agree.ctypes.data))
+        return weights, result, int(status[0]), counts, mask, agree
 
     def resample_poses_dev(self, d_weights: int, weight_stride: int, d_poses: int, pose_stride: int,
                            poses_per_group: int, G: int, P: int, M: int, d_u: int, d_delta: int, n_delta: int,
@@ -2289,3 +2380,37 @@ def cast_ranges_host(poses, beams, grid, spec: RangeCast = None, measured=None, 
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_cast_ranges_host")
     return ranges, (weights[:P] if weights is not None else None), result, cast
+
+
+def beam_agree_points_host(x, y, slot, index, n_scans: int, n_stride: int, poses, field, spec: BeamAgree):
+    """Host only: E23's rule for one group over points, by the library's own rplgpu_beam_agree_points_host (no
+    handle, no device).  x, y: the points in the base frame, slot / index: their scan and sample; poses (P, 4)
+    float32; field (height, width) int8 -> ``(counts (n_scans, n_stride) uint32, mask (n_scans, ceil(n_stride / 32))
+    uint32, weights (P,) uint32, result (8,) uint32, agree (8,) uint32, status)``."""
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.ascontiguousarray(y, np.float32)
+    slot = np.ascontiguousarray(slot, np.uint32)
+    index = np.ascontiguousarray(index, np.uint32)
+    if not (x.ndim == 1 and x.shape == y.shape == slot.shape == index.shape):
+        raise TypeError("x, y, slot and index must be 1-D arrays of one length")
+    poses = np.ascontiguousarray(poses, np.float32)
+    if poses.ndim != 2 or poses.shape[1] != 4:
+        raise TypeError("poses must be a (P, 4) float32 array")
+    field = np.ascontiguousarray(field, np.int8)
+    if field.shape != (spec.height, spec.width):
+        raise TypeError("field must be a (height, width) int8 array")
+    P = len(poses)
+    ok = 0 < n_scans and 0 < n_stride and n_scans * n_stride <= 1 << 24
+    counts = np.zeros((n_scans, n_stride) if ok else (1, 1), np.uint32)
+    mask = np.zeros((n_scans, (n_stride + 31) // 32) if ok else (1, 1), np.uint32)
+    weights = np.zeros(max(P, 1), np.uint32)
+    result = np.zeros(8, np.uint32)
+    agree = np.zeros(8, np.uint32)
+    status = np.zeros(1, np.uint32)
+    rc = load_library().rplgpu_beam_agree_points_host(
+        x.ctypes.data, y.ctypes.data, slot.ctypes.data, index.ctypes.data, len(x), n_scans, n_stride,
+        poses.ctypes.data, P, field.ctypes.data, C.byref(spec), counts.ctypes.data, mask.ctypes.data,
+        weights.ctypes.data, result.ctypes.data, agree.ctypes.data, status.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_beam_agree_points_host")
+    return counts, mask, weights[:P], result, agree, int(status[0])

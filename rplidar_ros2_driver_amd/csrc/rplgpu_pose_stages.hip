@@ -1,11 +1,12 @@
 // rplgpu_pose_stages.hip — the extern "C" entry points of the stages that work on pose lists
 // (include/rplgpu_msg.h): E15 scoring, E16 resampling, E17 the pose estimate, E18 motion noise, E19 seeding,
-// E20 occupied bins and the KLD sample count, E21 clusters of those bins, E22 the beam fan cast into a grid.
+// E20 occupied bins and the KLD sample count, E21 clusters of those bins, E22 the beam fan cast into a grid, E23
+// scoring without the beams the list disagrees with.
 //
 // Host side only: argument checks, the launches, the host-buffer doors and the host twins of the integer and
 // float32 rules (this unit is built with -ffp-contract=off -fno-fast-math like every other: the twins' comments rely
 // on it); the kernels are in rpl_pose.hip, rpl_resample.hip, rpl_estimate.hip, rpl_motion.hip, rpl_seed.hip,
-// rpl_bins.hip, rpl_clusters.hip and rpl_cast.hip.  The handle, the helpers of rplgpu_api.hip, the scan-stage prologue and the doors' per-call buffer
+// rpl_bins.hip, rpl_clusters.hip, rpl_cast.hip and rpl_agree.hip.  The handle, the helpers of rplgpu_api.hip, the scan-stage prologue and the doors' per-call buffer
 // come from rpl_host.hpp.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,7 @@
 #include "rplgpu_msg.h"
 #include "rpl_launch.hpp"
 #include "rpl_host.hpp"
+#include "rpl_agree.hpp"
 
 using namespace rpl::host;
 
@@ -58,6 +60,35 @@ int32_t rplgpu_pose_list(const double *xyt, uint32_t n, float *poses_out) {
   return RPLGPU_OK;
 }
 
+// The argument checks E15 and E23 share behind check_batch, in E15's order; fn names the entry point in the texts.
+// spec_ok: the stage's own spec check passed; cells: width * height of that spec (read only when spec_ok).
+static int32_t score_args_check(rplgpu_handle_t h, const char *fn, const char *spec_name, bool spec_ok, uint64_t cells,
+                                uint32_t group, const float *d_poses, uint32_t P, uint64_t pose_stride,
+                                const int8_t *d_field, uint64_t field_stride, const uint32_t *d_weights,
+                                uint64_t weight_stride, const uint32_t *d_result, const uint32_t *d_status) {
+  const std::string at = std::string(fn) + ": ";
+  if (!d_poses || !d_field || !d_weights || !d_result || group == 0) return RPLGPU_ERR_INVALID_ARG;
+  if (!spec_ok) {
+    h->err = at + "invalid " + spec_name + " (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!PoseListDoor{h, fn}.poses(P)) return RPLGPU_ERR_INVALID_ARG;
+  if (pose_stride < 4ull * P || (pose_stride & 3u) || (reinterpret_cast<uintptr_t>(d_poses) & 15u)) {
+    h->err = at + "pose_stride must be >= 4 P floats and a multiple of 4, d_poses 16-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (field_stride < cells || (field_stride & 3u) || (reinterpret_cast<uintptr_t>(d_field) & 3u)) {
+    h->err = at + "field_stride must be >= width * height and a multiple of 4, d_field 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (weight_stride < P || (reinterpret_cast<uintptr_t>(d_weights) & 3u) ||
+      (reinterpret_cast<uintptr_t>(d_result) & 3u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
+    h->err = at + "weight_stride must be >= P, d_weights / d_result / d_status 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  return RPLGPU_OK;
+}
+
 // d_t0: the per-scan time offsets of E6 for this call (the handle's, or the host door's own), or NULL
 static int32_t pose_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
                          const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
@@ -68,26 +99,11 @@ static int32_t pose_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32
                          uint32_t *d_status) {
   int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
   if (rc) return rc;
-  if (!p || !s || !d_poses || !d_field || !d_weights || !d_result || group == 0) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_pose_score_check(s) != RPLGPU_OK) {
-    h->err = "rplgpu_score_poses_dev: invalid rplgpu_pose_score_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!PoseListDoor{h, "rplgpu_score_poses_dev"}.poses(P)) return RPLGPU_ERR_INVALID_ARG;
-  if (pose_stride < 4ull * P || (pose_stride & 3u) || (reinterpret_cast<uintptr_t>(d_poses) & 15u)) {
-    h->err = "rplgpu_score_poses_dev: pose_stride must be >= 4 P floats and a multiple of 4, d_poses 16-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (field_stride < (uint64_t)s->width * s->height || (field_stride & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_field) & 3u)) {
-    h->err = "rplgpu_score_poses_dev: field_stride must be >= width * height and a multiple of 4, d_field 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (weight_stride < P || (reinterpret_cast<uintptr_t>(d_weights) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_result) & 3u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) {
-    h->err = "rplgpu_score_poses_dev: weight_stride must be >= P, d_weights / d_result / d_status 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!p || !s) return RPLGPU_ERR_INVALID_ARG;
+  if ((rc = score_args_check(h, "rplgpu_score_poses_dev", "rplgpu_pose_score_t", rplgpu_pose_score_check(s) == RPLGPU_OK,
+                             (uint64_t)s->width * s->height, group, d_poses, P, pose_stride, d_field, field_stride,
+                             d_weights, weight_stride, d_result, d_status)))
+    return rc;
   if (B == 0) return RPLGPU_OK;
   if (!device_readable(h, {{d_motion, "d_motion", false}, {d_pose2d, "d_pose2d", false}, {d_poses, "d_poses", true},
                            {d_field, "d_field", true}, {d_weights, "d_weights", true}, {d_result, "d_result", true},
@@ -1705,6 +1721,249 @@ int32_t rplgpu_cast_ranges(rplgpu_handle_t h, const rplgpu_range_cast_t *s, cons
     std::memcpy(result, small, 32);
   }
   std::memcpy(cast, small + 8, 32);
+  return RPLGPU_OK;
+}
+
+// ---- E23: the beams a pose list disagrees with are left out of the weights (include/rplgpu_msg.h) -------------------
+
+void rplgpu_default_beam_agree(rplgpu_beam_agree_t *s) {
+  if (!s) return;
+  s->origin_x = -25.6f;
+  s->origin_y = -25.6f;
+  s->resolution = 0.05f;
+  s->width = 1024;
+  s->height = 1024;
+  s->agree_lo = 1;
+  s->keep_num = 3;
+  s->keep_den = 10;
+  s->err_num = 9;
+  s->err_den = 10;
+}
+
+int32_t rplgpu_beam_agree_check(const rplgpu_beam_agree_t *s) {
+  if (!s) return RPLGPU_ERR_INVALID_ARG;
+  const rplgpu_pose_score_t grid = {s->origin_x, s->origin_y, s->resolution, s->width, s->height};
+  if (rplgpu_pose_score_check(&grid) != RPLGPU_OK) return RPLGPU_ERR_INVALID_ARG;
+  if (s->agree_lo < 1 || s->agree_lo > 127) return RPLGPU_ERR_INVALID_ARG;
+  if (s->keep_den == 0 || s->keep_den > RPLGPU_AGREE_MAX_DEN || s->keep_num > s->keep_den) return RPLGPU_ERR_INVALID_ARG;
+  if (s->err_den == 0 || s->err_den > RPLGPU_AGREE_MAX_DEN || s->err_num > RPLGPU_AGREE_MAX_DEN)
+    return RPLGPU_ERR_INVALID_ARG;
+  return RPLGPU_OK;
+}
+
+// E23's three comparisons, for the host twin (the kernels of rpl_agree.hip spell the same expressions)
+static bool agree_kept(const rplgpu_beam_agree_t *s, uint32_t count, uint32_t P) {
+  return (uint64_t)count * s->keep_den > (uint64_t)s->keep_num * P;
+}
+static bool agree_falls_back(const rplgpu_beam_agree_t *s, uint32_t F, uint32_t K) {
+  return F > 0 && (uint64_t)(F - K) * s->err_den >= (uint64_t)s->err_num * F;
+}
+
+// E15's field value of the point (x, y) at one pose: float32, each product rounded, then the difference or sum, then
+// the translation (this unit is built with -ffp-contract=off); *no_cell is set for a position without a cell
+static uint32_t agree_look_host(const rplgpu_beam_agree_t *s, const int8_t *field, const float *pose, float x, float y,
+                                bool *no_cell) {
+  const float c = pose[0], sn = pose[1], tx = pose[2], ty = pose[3];
+  const float p0 = c * x, p1 = sn * y, p2 = sn * x, p3 = c * y;
+  const float rx = (p0 - p1) + tx, ry = (p2 + p3) + ty;
+  int32_t cx = 0, cy = 0;
+  if (!host_cell(rx, ry, s->origin_x, s->origin_y, s->resolution, &cx, &cy)) {
+    *no_cell = true;
+    return 0u;
+  }
+  if (cx < 0 || cy < 0 || (uint32_t)cx >= s->width || (uint32_t)cy >= s->height) return 0u;
+  const int v = field[(size_t)cy * s->width + (size_t)cx];
+  return (uint32_t)std::max(v, 0);
+}
+
+int32_t rplgpu_beam_agree_points_host(const float *x, const float *y, const uint32_t *slot, const uint32_t *index,
+                                      uint32_t n_points, uint32_t n_scans, uint32_t n_stride, const float *poses,
+                                      uint32_t P, const int8_t *field, const rplgpu_beam_agree_t *s,
+                                      uint32_t *counts_out, uint32_t *mask_out, uint32_t *weights_out,
+                                      uint32_t result[8], uint32_t agree[8], uint32_t *status) {
+  if (rplgpu_beam_agree_check(s) != RPLGPU_OK || !poses || !field || !counts_out || !mask_out || !weights_out ||
+      !result || !agree || (n_points && (!x || !y || !slot || !index)) || P == 0 || P > RPLGPU_MAX_POSES ||
+      n_scans == 0 || n_stride == 0 || (uint64_t)n_scans * n_stride > (1ull << 24))
+    return RPLGPU_ERR_INVALID_ARG;
+  for (uint32_t k = 0; k < n_points; ++k) {
+    if (slot[k] >= n_scans || index[k] >= n_stride) return RPLGPU_ERR_INVALID_ARG;
+  }
+  const uint32_t mask_words = (n_stride + 31u) / 32u;
+  std::fill(counts_out, counts_out + (size_t)n_scans * n_stride, 0u);
+  std::fill(mask_out, mask_out + (size_t)n_scans * mask_words, 0u);
+  std::vector<uint64_t> w(P, 0u);
+  std::vector<uint32_t> finite;  // the points that are finite
+  bool no_cell = false;
+  // first all look-ups: E15's sums and the counts
+  uint32_t hi = 0, lo = 0xFFFFFFFFu;
+  uint64_t total = 0;
+  for (uint32_t k = 0; k < n_points; ++k) {
+    if (!(std::fabs(x[k]) < HUGE_VALF && std::fabs(y[k]) < HUGE_VALF)) continue;
+    finite.push_back(k);
+    uint32_t count = 0;
+    for (uint32_t q = 0; q < P; ++q) {
+      const uint32_t f = agree_look_host(s, field, poses + 4u * (size_t)q, x[k], y[k], &no_cell);
+      w[q] += f;
+      count += f >= (uint32_t)s->agree_lo ? 1u : 0u;
+    }
+    counts_out[(size_t)slot[k] * n_stride + index[k]] = count;
+    hi = std::max(hi, count);
+    lo = std::min(lo, count);
+    total += count;
+  }
+  // the rule's mask, whether or not the group falls back
+  const uint32_t F = (uint32_t)finite.size();
+  uint32_t K = 0;
+  for (uint32_t k : finite) {
+    if (!agree_kept(s, counts_out[(size_t)slot[k] * n_stride + index[k]], P)) continue;
+    mask_out[(size_t)slot[k] * mask_words + (index[k] >> 5)] |= 1u << (index[k] & 31u);
+    ++K;
+  }
+  const bool back = agree_falls_back(s, F, K);
+  if (!back) {  // the skipped samples leave the weights again
+    for (uint32_t k : finite) {
+      if ((mask_out[(size_t)slot[k] * mask_words + (index[k] >> 5)] >> (index[k] & 31u)) & 1u) continue;
+      for (uint32_t q = 0; q < P; ++q) w[q] -= agree_look_host(s, field, poses + 4u * (size_t)q, x[k], y[k], &no_cell);
+    }
+  }
+  // E15's result words from the final weights
+  uint64_t sum = 0;
+  uint32_t top = 0, top_at = 0, n_top = 0, n_zero = 0;
+  for (uint32_t q = 0; q < P; ++q) {
+    const uint32_t v = (uint32_t)w[q];  // (n_scans * n_stride <= 2^24: no sum wraps)
+    weights_out[q] = v;
+    sum += v;
+    n_zero += v == 0 ? 1u : 0u;
+    if (v > top) {
+      top = v;
+      top_at = q;
+    }
+  }
+  for (uint32_t q = 0; q < P; ++q) n_top += weights_out[q] == top ? 1u : 0u;
+  const uint32_t res[8] = {top, top_at, n_top, n_zero, F, weights_out[0], (uint32_t)sum, (uint32_t)(sum >> 32)};
+  const uint32_t agr[8] = {F, K, back ? 1u : 0u, back ? F : K, hi, F ? lo : 0u, (uint32_t)total, (uint32_t)(total >> 32)};
+  std::memcpy(result, res, 32);
+  std::memcpy(agree, agr, 32);
+  if (status) *status = no_cell ? RPLGPU_SCAN_CELL_RANGE : 0u;
+  return RPLGPU_OK;
+}
+
+// d_t0: as pose_impl
+static int32_t agree_impl(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                          const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                          const float *d_motion, const float *d_pose2d, const float *d_t0,
+                          const rplgpu_beam_agree_t *s, const float *d_poses, uint32_t P, uint64_t pose_stride,
+                          uint32_t poses_per_group, const int8_t *d_field, uint64_t field_stride,
+                          uint32_t field_per_group, uint32_t *d_weights, uint64_t weight_stride, uint32_t *d_result,
+                          uint32_t *d_status, uint32_t *d_counts, uint64_t count_stride, uint32_t *d_mask,
+                          uint64_t mask_stride, uint32_t *d_agree) {
+  const char *fn = "rplgpu_score_poses_agree_dev";
+  int32_t rc = check_batch(h, d_nodes, n_stride, d_n_per_scan, B);
+  if (rc) return rc;
+  if (!p || !s) return RPLGPU_ERR_INVALID_ARG;
+  if ((rc = score_args_check(h, fn, "rplgpu_beam_agree_t", rplgpu_beam_agree_check(s) == RPLGPU_OK,
+                             (uint64_t)s->width * s->height, group, d_poses, P, pose_stride, d_field, field_stride,
+                             d_weights, weight_stride, d_result, d_status)))
+    return rc;
+  if (!d_counts || !d_mask || !d_agree || misaligned(d_counts, 3) || misaligned(d_mask, 3) || misaligned(d_agree, 3)) {
+    h->err = std::string(fn) + ": d_counts, d_mask and d_agree are required and 4-byte aligned";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (count_stride < n_stride || mask_stride < (n_stride + 31u) / 32u) {
+    h->err = std::string(fn) + ": count_stride must be >= n_stride and mask_stride >= ceil(n_stride / 32)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (B == 0) return RPLGPU_OK;
+  if (!device_readable(h, {{d_motion, "d_motion", false}, {d_pose2d, "d_pose2d", false}, {d_poses, "d_poses", true},
+                           {d_field, "d_field", true}, {d_weights, "d_weights", true}, {d_result, "d_result", true},
+                           {d_status, "d_status", false}, {d_counts, "d_counts", true}, {d_mask, "d_mask", true},
+                           {d_agree, "d_agree", true}}))
+    return RPLGPU_ERR_INVALID_ARG;
+  ScanPrologue pro;
+  if ((rc = pro.admit(h, fn, p, d_motion, d_t0, B, group))) return rc;
+  if ((uint64_t)pro.group * n_stride > (1ull << 24)) {  // 127 x points stays below 2^32: no weight wraps
+    h->err = std::string(fn) + ": group x n_stride above 2^24 samples";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if ((uint64_t)pro.G * ((P + 255u) / 256u) > 0x7FFFFFFFull) {  // (E15's limit, kept: the calls take the same lists)
+    h->err = std::string(fn) + ": groups x P too large for one call";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  const rpl::AgreeK k{s->origin_x, s->origin_y, s->resolution, s->width,   s->height,
+                      (uint32_t)s->agree_lo, s->keep_num, s->keep_den,   s->err_num, s->err_den};
+  if ((rc = pro.begin(h, d_nodes, n_stride, d_n_per_scan, B, p, d_t0, d_status))) return rc;
+  RPL_HIP(h, rpl::launch_agree(h->stream, d_nodes, n_stride, d_n_per_scan, B, pro.group, pro.G, pro.kp, pro.T, pro.mask,
+                               kMaskStride, d_motion, d_pose2d, k, d_poses, P, pose_stride, poses_per_group, d_field,
+                               field_stride, field_per_group, d_weights, weight_stride, d_result, d_status, d_counts,
+                               count_stride, d_mask, mask_stride, d_agree));
+  RPL_HIP(h, rpl::launch_pose_best(h->stream, d_weights, weight_stride, pro.G, P, d_result));
+  return RPLGPU_OK;
+}
+
+int32_t rplgpu_score_poses_agree_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                                     const uint32_t *d_n_per_scan, uint32_t B, uint32_t group,
+                                     const rplgpu_params_t *p, const float *d_motion, const float *d_pose2d,
+                                     const rplgpu_beam_agree_t *s, const float *d_poses, uint32_t P,
+                                     uint64_t pose_stride, uint32_t poses_per_group, const int8_t *d_field,
+                                     uint64_t field_stride, uint32_t field_per_group, uint32_t *d_weights,
+                                     uint64_t weight_stride, uint32_t *d_result, uint32_t *d_status,
+                                     uint32_t *d_counts, uint64_t count_stride, uint32_t *d_mask,
+                                     uint64_t mask_stride, uint32_t *d_agree) {
+  if (!h) return RPLGPU_ERR_INVALID_ARG;
+  return agree_impl(h, d_nodes, n_stride, d_n_per_scan, B, group, p, d_motion, d_pose2d, h->scan_t0, s, d_poses, P,
+                    pose_stride, poses_per_group, d_field, field_stride, field_per_group, d_weights, weight_stride,
+                    d_result, d_status, d_counts, count_stride, d_mask, mask_stride, d_agree);
+}
+
+int32_t rplgpu_score_poses_agree(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                                 const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                                 const float *motion, const float *pose2d, const float *t0,
+                                 const rplgpu_beam_agree_t *s, const float *poses, uint32_t P, const int8_t *field,
+                                 uint32_t *weights_out, uint32_t result[8], uint32_t *status, uint32_t *counts_out,
+                                 uint32_t *mask_out, uint32_t agree[8]) {
+  if (!h || !nodes || !n_per_scan || !p || !s || !poses || !field || !result || !agree || n_scans == 0 ||
+      n_stride == 0)
+    return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_beam_agree_check(s) != RPLGPU_OK) {
+    h->err = "rplgpu_score_poses_agree: invalid rplgpu_beam_agree_t (see include/rplgpu_msg.h)";
+    return RPLGPU_ERR_INVALID_ARG;
+  }
+  if (!PoseListDoor{h, "rplgpu_score_poses_agree"}.poses(P)) return RPLGPU_ERR_INVALID_ARG;
+  if (n_scans > h->max_b || n_stride > h->max_n) return RPLGPU_ERR_CAPACITY;
+  RPL_HIP(h, hipSetDevice(h->device));
+  const size_t cells_n = (size_t)s->width * s->height, stride = (cells_n + 3u) & ~(size_t)3u;
+  const size_t mask_words = (n_stride + 31u) / 32u;
+  const size_t cnt_bytes = 4u * (size_t)n_scans * n_stride, mask_bytes = 4u * (size_t)n_scans * mask_words;
+  // field | poses | weights | counts | mask | the scans | result + agree + status
+  DoorBuffer buf(h, "rplgpu_score_poses_agree");
+  const size_t o_field = buf.part(stride), o_ps = buf.part(16u * (size_t)P), o_wt = buf.part(4u * (size_t)P),
+               o_cnt = buf.part(cnt_bytes), o_mask = buf.part(mask_bytes);
+  DoorScans scans(buf, nodes, n_stride, n_per_scan, n_scans, motion, pose2d, t0);
+  const size_t o_small = buf.part(80);
+  uint32_t small[17] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int32_t rc = buf.run([&]() -> int32_t {
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_field), field, cells_n, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(buf.at(o_ps), poses, 16u * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    if (int32_t urc = scans.upload(h, buf)) return urc;
+    uint32_t *d_small = buf.at<uint32_t>(o_small);  // result, agree, status
+    const int32_t irc = agree_impl(h, scans.d_nodes, n_stride, scans.d_n_per_scan, n_scans, n_scans, p, scans.d_motion,
+                                   scans.d_pose2d, scans.d_t0, s, buf.at<const float>(o_ps), P, 4ull * P, 0,
+                                   buf.at<const int8_t>(o_field), stride, 0, buf.at<uint32_t>(o_wt), P, d_small,
+                                   d_small + 16, buf.at<uint32_t>(o_cnt), n_stride, buf.at<uint32_t>(o_mask),
+                                   mask_words, d_small + 8);
+    if (irc) return irc;
+    if (weights_out)
+      RPL_HIP(h, hipMemcpyAsync(weights_out, buf.at(o_wt), 4u * (size_t)P, hipMemcpyDeviceToHost, h->stream));
+    if (counts_out) RPL_HIP(h, hipMemcpyAsync(counts_out, buf.at(o_cnt), cnt_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (mask_out) RPL_HIP(h, hipMemcpyAsync(mask_out, buf.at(o_mask), mask_bytes, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipMemcpyAsync(small, d_small, 68, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, hipStreamSynchronize(h->stream));
+    return RPLGPU_OK;
+  });
+  if (rc) return rc;
+  std::memcpy(result, small, 32);
+  std::memcpy(agree, small + 8, 32);
+  if (status) *status = small[16];
   return RPLGPU_OK;
 }
 

@@ -313,6 +313,56 @@ int main(int argc, char **argv) {
     }
     std::printf("pose score: best %u at pose %u of 4, sum %llu\n", pr.best, pr.best_index,
                 static_cast<unsigned long long>(pr.sum));
+    // E23 on the same poses with agree_lo 99, keep 1 / 4, err 9 / 10.  The look-ups of the return at 2 m are 100, 99,
+    // 36, 0 at the four poses, of the one at 4 m 36, 99, 100, 0: two poses agree with each, 2 * 4 > 1 * 4 keeps them.
+    // The return at 7 m agrees nowhere (unknown cells, a free one) and is skipped; 1 of 3 is no fallback.  It added
+    // nothing, so the weights are E15's.  The door against the library's host-only twin over the same three points.
+    rplgpu_beam_agree_t arule;
+    rplgpu_default_beam_agree(&arule);
+    arule.agree_lo = 99;
+    arule.keep_num = 1;
+    arule.keep_den = 4;
+    std::vector<uint32_t> aweights, acounts, amask;
+    rplgpu_host::ScanPath::PoseResult apr;
+    rplgpu_host::ScanPath::AgreeResult ar;
+    uint32_t astatus = 99;
+    if (!path.score_poses_agree(step, rplgpu_host::ScanConfig(), nullptr, nullptr, nullptr, cost_msg, arule, xyt,
+                                aweights, apr, acounts, amask, ar, &astatus)) {
+      std::fprintf(stderr, "pose score (agree) failed: %s\n", path.last_error().c_str());
+      return 90;
+    }
+    {
+      rplgpu_beam_agree_t spec = arule;
+      spec.origin_x = og.origin_x;
+      spec.origin_y = og.origin_y;
+      spec.resolution = og.resolution;
+      spec.width = og.width;
+      spec.height = og.height;
+      const float px[3] = {2.0f, 4.0f, 7.0f}, py[3] = {0.0f, 0.0f, 0.0f};
+      const uint32_t slot[3] = {0, 0, 0}, index[3] = {0, 1, 2};
+      std::vector<float> list(16);
+      uint32_t tc[3], tm[1], tw[4], tres[8], tagr[8], tstatus = 99;
+      if (rplgpu_pose_list(xyt.data(), 4, list.data()) != RPLGPU_OK ||
+          rplgpu_beam_agree_points_host(px, py, slot, index, 3, 1, 3, list.data(), 4, cost_msg.data.data(), &spec, tc,
+                                        tm, tw, tres, tagr, &tstatus) != RPLGPU_OK) {
+        std::fprintf(stderr, "pose score (agree): the host twin refused\n");
+        return 91;
+      }
+      if (aweights.size() != 4 || std::memcmp(aweights.data(), tw, 16) != 0 || acounts.size() != 3 ||
+          std::memcmp(acounts.data(), tc, 12) != 0 || amask.size() != 1 || amask[0] != tm[0] || astatus != tstatus ||
+          ar.finite != tagr[0] || ar.kept != tagr[1] || ar.fell_back != tagr[2] || ar.entered != tagr[3] ||
+          ar.count_max != tagr[4] || ar.count_min != tagr[5] || ar.count_sum != tagr[6] || apr.best != tres[0] ||
+          apr.best_index != tres[1] || apr.sum != tres[6] || aweights != weights || acounts[0] != 2 ||
+          acounts[1] != 2 || acounts[2] != 0 || amask[0] != 3 || ar.finite != 3 || ar.kept != 2 || ar.fell_back != 0) {
+        std::fprintf(stderr, "pose score (agree): wrong answer (counts %u %u %u, mask %u, F %u K %u back %u)\n",
+                     acounts.size() > 2 ? acounts[0] : 0, acounts.size() > 2 ? acounts[1] : 0,
+                     acounts.size() > 2 ? acounts[2] : 0, amask.empty() ? 0 : amask[0], ar.finite, ar.kept,
+                     ar.fell_back);
+        return 92;
+      }
+    }
+    std::printf("pose score (agree): %u of %u samples kept, counts %u %u %u, equal to the host twin\n", ar.kept,
+                ar.finite, acounts[0], acounts[1], acounts[2]);
     // E16 on those weights (136, 198, 136, 0; S = 470), four outputs, u = 0: t = (0, 117, 235, 352) against
     // C = (136, 334, 470, 470) gives the ancestors (0, 0, 1, 2): the dead pose is gone and pose 0 is there twice.
     // The device call against the library's own host-only twin, byte for byte, with one metre ahead as the delta.

@@ -513,6 +513,77 @@ class ScanPath {
     return true;
   }
 
+  // ext E23 (include/rplgpu_msg.h): score_poses without the samples the pose list disagrees with (AMCL's beam skip).
+  // rule: agree_lo and the keep and err ratios (its grid fields are taken from field_msg.info).  counts and mask come
+  // back per scan at `stride` (the longest scan) and ceil(stride / 32) words: mask bit i of scan b is 0 for a finite
+  // sample the map does not explain.  agree: the header's d_agree table.
+  struct AgreeResult {
+    uint32_t finite = 0, kept = 0, fell_back = 0, entered = 0, count_max = 0, count_min = 0;
+    uint64_t count_sum = 0;
+    uint32_t stride = 0;  // samples per scan in counts; (stride + 31) / 32 words per scan in mask
+  };
+  template <class NodeT, class OccupancyGridT>
+  bool score_poses_agree(const std::vector<std::vector<NodeT>> &scans, const ScanConfig &cfg, const float *pose2d,
+                         const float *motion, const float *t0, const OccupancyGridT &field_msg,
+                         const rplgpu_beam_agree_t &rule, const std::vector<double> &xyt,
+                         std::vector<uint32_t> &weights, PoseResult &result, std::vector<uint32_t> &counts,
+                         std::vector<uint32_t> &mask, AgreeResult &agree, uint32_t *status = nullptr) {
+    if (scans.empty()) return false;
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    rplgpu_beam_agree_t spec = rule;
+    spec.origin_x = static_cast<float>(field_msg.info.origin.position.x);
+    spec.origin_y = static_cast<float>(field_msg.info.origin.position.y);
+    spec.resolution = field_msg.info.resolution;
+    spec.width = field_msg.info.width;
+    spec.height = field_msg.info.height;
+    const size_t n_cells = static_cast<size_t>(spec.width) * spec.height;
+    if (n_cells == 0 || field_msg.data.size() != n_cells)
+      return fail("score_poses_agree: data is not width x height");
+    const size_t n_poses = xyt.size() / 3;
+    if (n_poses == 0 || xyt.size() != 3 * n_poses || n_poses > RPLGPU_MAX_POSES)
+      return fail("score_poses_agree: xyt must hold 1 .. RPLGPU_MAX_POSES poses of 3 values");
+    size_t stride = 1;
+    for (const auto &s : scans) stride = s.size() > stride ? s.size() : stride;
+    if (stride > max_n_) return fail("scan larger than the configured capacity");
+    occ_nodes_.assign(scans.size() * stride, rplgpu_node_t{});
+    occ_len_.resize(scans.size());
+    for (size_t b = 0; b < scans.size(); ++b) {
+      if (!scans[b].empty()) std::memcpy(&occ_nodes_[b * stride], scans[b].data(), scans[b].size() * 8);
+      occ_len_[b] = static_cast<uint32_t>(scans[b].size());
+    }
+    occ_prev_.assign(field_msg.data.begin(), field_msg.data.end());
+    pose_list_.resize(4 * n_poses);
+    if (rplgpu_pose_list(xyt.data(), static_cast<uint32_t>(n_poses), pose_list_.data()) != RPLGPU_OK)
+      return fail("score_poses_agree: rplgpu_pose_list refused the list");
+    weights.assign(n_poses, 0u);
+    counts.assign(scans.size() * stride, 0u);
+    mask.assign(scans.size() * ((stride + 31) / 32), 0u);
+    const rplgpu_params_t p = cfg.to_params();
+    uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0}, aw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_score_poses_agree(h_, occ_nodes_.data(), static_cast<uint32_t>(stride), occ_len_.data(),
+                                 static_cast<uint32_t>(scans.size()), &p, motion, pose2d, t0, &spec,
+                                 pose_list_.data(), static_cast<uint32_t>(n_poses), occ_prev_.data(), weights.data(),
+                                 words, status, counts.data(), mask.data(), aw) != RPLGPU_OK)
+      return note_error();
+    result.best = words[0];
+    result.best_index = words[1];
+    result.ties = words[2];
+    result.zeros = words[3];
+    result.points = words[4];
+    result.weight_of_first = words[5];
+    result.sum = static_cast<uint64_t>(words[6]) | (static_cast<uint64_t>(words[7]) << 32);
+    agree.finite = aw[0];
+    agree.kept = aw[1];
+    agree.fell_back = aw[2];
+    agree.entered = aw[3];
+    agree.count_max = aw[4];
+    agree.count_min = aw[5];
+    agree.count_sum = static_cast<uint64_t>(aw[6]) | (static_cast<uint64_t>(aw[7]) << 32);
+    agree.stride = static_cast<uint32_t>(stride);
+    return true;
+  }
+
   // ext E16 (include/rplgpu_msg.h): the list `poses` (four floats per pose, as rplgpu_pose_list writes them)
   // redrawn by `weights` (what score_poses returned) into `count` poses — systematic resampling from the caller's
   // one random word u — and moved by `delta` (dc, ds, dx, dy): empty for a plain copy, 4 floats for one odometry
