@@ -8,6 +8,7 @@
 #include "rplgpu_comm.h"
 #include "rpl_device.hpp"
 #include "rpl_msg.hpp"
+#include "rpl_rules.hpp"
 
 namespace rplmsg {
 struct Prefix;
@@ -405,9 +406,7 @@ hipError_t launch_seed(hipStream_t s, const SeedK &k, const int8_t *grid, unsign
 // cleared (not under KEEP) and the result words started, then one thread per pose — one 16-byte load, the float32
 // position bin, a bounded bisection over the quantised edge table in LDS, the wave's marks merged per map word, a
 // device-scope read and a returning atomic OR only where a bit is missing — and the tile's statistics added to the
-// words with integer atomics.  No scratch.
-// the words of a bit map of nb bins (nb <= RPLGPU_MAX_POSE_BINS), on the device and on the host, for E20 and E21
-__host__ __device__ inline uint32_t bin_map_words(uint32_t nb) { return (nb + 31u) >> 5; }
+// words with integer atomics.  No scratch.  (bin_map_words(nb), the words of a map, is in rpl_rules.hpp.)
 struct BinsK {
   float origin_x, origin_y, inv_size;
   uint32_t nx, ny;

@@ -70,6 +70,23 @@ def test_host_header_compiles_against_ros_shaped_messages(tmp_path):
     assert r.returncode == 0, r.stderr
 
 
+def test_pose_rules_unit_is_plain_cpp(tmp_path):
+    """csrc/rplgpu_pose_rules.cpp (the host twins, checks and tables of E15 - E23) and the stand-alone program that
+    drives it build with the system g++ from those two files alone, warning-free, and the program accepts every
+    call it should (no sanitizer here: tools/dev/pose_rules_asan.cpp's header has that recipe)."""
+    rules = ROOT / "rplidar_ros2_driver_amd" / "csrc" / "rplgpu_pose_rules.cpp"
+    text = rules.read_text()
+    assert "hip/hip_runtime" not in text and "rpl_launch.hpp" not in text
+    exe = tmp_path / "pose_rules"
+    cmd = ["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
+           f"-I{ROOT / 'include'}", f"-I{rules.parent}", str(rules),
+           str(ROOT / "tools" / "dev" / "pose_rules_asan.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
 def _build_selftest():
     r = subprocess.run(["make", "-C", str(HOST)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
