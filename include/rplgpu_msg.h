@@ -1549,6 +1549,111 @@ int32_t rplgpu_beam_agree_points_host(const float *x, const float *y, const uint
                                       uint32_t *counts_out, uint32_t *mask_out, uint32_t *weights_out,
                                       uint32_t result[8], uint32_t agree[8], uint32_t *status);
 
+/* ---- E24: scans matched over a wide window by bound and refine (row 4; the mapping side's loop closer) ----
+ * E13 scores every pose of its window, so the window ends at 32 cells (1.6 m at 0.05 m): enough to track a pose
+ * between two time steps, not to close a loop after drift, relocalise against a stored map or start E14's chain from
+ * a poor prior.  Here the window reaches 256 cells a side and the answer is still E13's, by the branch and bound of
+ * Cartographer's FastCorrelativeScanMatcher2D with ONE coarse level: a sliding maximum P of the field, an upper
+ * bound U per BLOCK of s x s shifts read from P, E13 scores only for the blocks whose bound can still win.  Nothing
+ * in the reference matches scans, so these rules ARE the definition (parity unpinned, as E5-E23).  After the float32
+ * rotation everything is sums and maxima of bytes: the result depends on no order.
+ *
+ * POINTS, the pivot, CANDIDATE (k, j, i), the rotated cell (cx, cy), f = max(byte, 0) with 0 outside the grid
+ * (written F(x, y) below), RPLGPU_SCAN_OUT_TRUNCATED / RPLGPU_SCAN_CELL_RANGE in d_status[g] and the bound group *
+ * n_stride <= 2^24 are those of the E13 block above, word for word, with i in [-Tx, Tx], j in [-Ty, Ty] and Tx, Ty
+ * up to RPLGPU_MAX_WIDE_SHIFT.  The ROTATION TABLE is exactly rplgpu_scan_match_rotations of an E13 spec with the
+ * same rot_steps and rot_step.  score(k, j, i) below is E13's score of that candidate.
+ * POOLED FIELD, s = RPLGPU_WIDE_MATCH_BLOCK: for x in [-(s-1), width) and y in [-(s-1), height)
+ *   P(x, y) = max over a, b in [0, s) of F(x + a, y + b),
+ * int8 (0 .. 127) in a grid of Wp = width + s - 1 by Hp = height + s - 1: P(x, y) sits at (y + s-1) * Wp + (x + s-1).
+ * BLOCKS: nbx = ceil((2Tx + 1) / s), nby = ceil((2Ty + 1) / s).  Block (k, bj, bi) holds the candidates of rotation
+ * k with i in [-Tx + bi*s, -Tx + bi*s + s-1] and at most Tx, j likewise (2T + 1 is odd: the last block of an axis is
+ * always partial).  Its flat index is ((k + K) * nby + bj) * nbx + bi.
+ * BOUND: U[g][k][bj][bi] = the sum over the group's points of P(cx - Tx + bi*s, cy - Ty + bj*s), 0 where P is not
+ * defined; uint32 at d_bounds + g * bounds_stride + the block's flat index.  U is at least the score of every
+ * candidate of its block.  The bounds volume is the call's own result, as E13's score volume is; words at and beyond
+ * a group's rplgpu_wide_match_blocks words are never changed.
+ * SEEDS: A is the block of the greatest U, among equals the lowest flat index; B is the block that holds (0, 0, 0).
+ * b0 = the greatest score over the (in-window) candidates of both seeds.
+ * LIST: every block with U >= b0; n is their number.
+ *   PROVEN, n <= max_blocks: every candidate of every listed block is scored, and words 0 - 3 and 6 of d_best + 8 g
+ *     are E13's words of the exhaustive volume over the wide window, tie rule included (largest score, then the
+ *     smallest i*i + j*j, |k|, k, j, i).  A candidate of score >= b0 lies in a block of U >= b0, so the best, every
+ *     candidate that ties with it and their number are all inside the list.
+ *   UNPROVEN, n > max_blocks: nothing beyond the seeds is scored; words 0 - 3 and 6 are taken over the candidates
+ *     of the two seeds alone (each once when A is B) and word 7 is RPLGPU_WIDE_MATCH_UNPROVEN.  The caller repeats
+ *     with max_blocks >= word 4 of the work words, or accepts the result.
+ *   Word 4 is always the group's finite points, word 5 always the score of (0, 0, 0), word 7 otherwise 0.
+ * A group without points has U 0 everywhere and b0 0, so every block is listed: it is proven iff the volume has at
+ * most max_blocks blocks, and then best is 0 at (0, 0, 0) with word 6 the number of candidates, as E13; unproven it
+ * is 0 at (0, 0, 0) with word 6 the candidates of block 0 and of seed B.
+ * WORK WORDS, eight per group at d_work + 8 g: 0 the blocks in the volume, 1 the greatest U, 2 seed A's flat index,
+ * 3 b0, 4 n, 5 max_blocks, 6 and 7 zero.
+ * APPLYING IT: d_best goes into rplgpu_apply_match_dev unchanged; that call reads k against K and takes any i, j,
+ * and the caller hands it an E13 spec (rplgpu_scan_match_t) with the same grid, rot_steps and rot_step, any shifts. */
+#define RPLGPU_WIDE_MATCH_BLOCK    8u      /* s: a block is 8 x 8 shifts, one wave of candidates */
+#define RPLGPU_MAX_WIDE_SHIFT      256u    /* cells, per axis */
+#define RPLGPU_MAX_WIDE_BLOCKS     65536u  /* the largest max_blocks */
+#define RPLGPU_WIDE_MATCH_UNPROVEN 0x1u    /* word 7 of d_best */
+typedef struct rplgpu_wide_match {
+  float    origin_x, origin_y;   /* the field's grid: as rplgpu_scan_match_t */
+  float    resolution;
+  uint32_t width, height;        /* 1 .. RPLGPU_MAX_OCC_DIM */
+  uint32_t shift_x, shift_y;     /* Tx, Ty: 0 .. RPLGPU_MAX_WIDE_SHIFT */
+  uint32_t rot_steps;            /* K: 0 .. RPLGPU_MAX_MATCH_ROT */
+  float    rot_step;             /* rad, E13's rules */
+  uint32_t max_blocks;           /* the cap of the list, 1 .. RPLGPU_MAX_WIDE_BLOCKS */
+} rplgpu_wide_match_t;
+/* E11's default grid, Tx = Ty = 64, K = 10, rot_step = (float)(0.25 * pi / 180), max_blocks = 1024 */
+void rplgpu_default_wide_match(rplgpu_wide_match_t *m);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for everything rplgpu_scan_match_check refuses with
+ * RPLGPU_MAX_WIDE_SHIFT in place of RPLGPU_MAX_MATCH_SHIFT, and for max_blocks of 0 or above RPLGPU_MAX_WIDE_BLOCKS.
+ * The device path uses this function. */
+int32_t rplgpu_wide_match_check(const rplgpu_wide_match_t *m);
+/* Host only.  (2K + 1) * nby * nbx, the words of one group's bounds volume; 0 for a spec the check refuses. */
+uint32_t rplgpu_wide_match_blocks(const rplgpu_wide_match_t *m);
+/* Host only.  The uint32 words of scratch a call over G groups takes: G * (272 + 65 * max_blocks), the cap's 64
+ * score words a listed block, the list, the seeds and the counters; not decreasing in G and in max_blocks, and 0
+ * for a spec the check refuses or G = 0. */
+uint64_t rplgpu_wide_match_scratch_words(const rplgpu_wide_match_t *m, uint32_t G);
+/* Host only: P of ONE field in plain C++, the definition a reader can run.  field: width * height bytes; pooled:
+ * (width + s-1) * (height + s-1) bytes, written whole.  RPLGPU_ERR_INVALID_ARG and nothing written for a NULL
+ * pointer or a dimension of 0 or above RPLGPU_MAX_OCC_DIM. */
+int32_t rplgpu_pool_field_host(const int8_t *field, uint32_t width, uint32_t height, int8_t *pooled);
+/* P of F fields on the handle's stream, an entry of its own so that a caller with a static map pools it once.
+ * Field f is read at d_field + f * field_stride (E13's rules: 4-byte aligned, field_stride >= width * height and a
+ * multiple of 4, only read) and its P written at d_pooled + f * pooled_stride (4-byte aligned, pooled_stride >=
+ * Wp * Hp and a multiple of 4, which must not overlap the fields); bytes at and beyond Wp * Hp of a pooled field are
+ * never changed.  Only the grid of `m` is used, but the whole spec is checked.  RPLGPU_ERR_INVALID_ARG for a spec
+ * the check refuses, a missing or misaligned pointer, the stride rules, F above 65535; F = 0 does nothing.  A refused
+ * call changes no output. */
+int32_t rplgpu_pool_field_dev(rplgpu_handle_t h, const rplgpu_wide_match_t *m, const int8_t *d_field,
+                              uint64_t field_stride, uint32_t F, int8_t *d_pooled, uint64_t pooled_stride);
+/* The match.  E13's arguments with the new spec; d_pooled holds P of the very fields at d_field (pooled field g_f
+ * beside field g_f; both are only read), d_bounds / bounds_stride (>= rplgpu_wide_match_blocks) the bounds volumes,
+ * d_best and d_work eight words a group, d_status optional.  SCRATCH is the caller's: rplgpu_wide_match_scratch_words
+ * (m, G) uint32 words at d_scratch, 8-byte aligned, G the number of groups; it holds nothing a second call may rely
+ * on, and words beyond it are never touched, whatever n is.  Nothing is stored on the handle, nothing is copied from
+ * pageable memory, and there is no host round trip between bound, select and refine: the list's length stays on the
+ * device.  RPLGPU_ERR_INVALID_ARG for everything rplgpu_match_scans_dev refuses (the spec by rplgpu_wide_match_check,
+ * bounds for scores), a missing or misaligned d_pooled / d_work (4 bytes) / d_scratch (8 bytes) and the pooled
+ * stride rules above.  A refused call changes no output.  Asynchronous on the handle's stream. */
+int32_t rplgpu_match_wide_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                              const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                              const float *d_motion, const float *d_pose2d, const float *d_pivot,
+                              const rplgpu_wide_match_t *m, const int8_t *d_field, uint64_t field_stride,
+                              uint32_t field_per_group, const int8_t *d_pooled, uint64_t pooled_stride,
+                              uint32_t *d_bounds, uint64_t bounds_stride, uint32_t *d_scratch, uint32_t *d_best,
+                              uint32_t *d_work, uint32_t *d_status);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp), shaped as rplgpu_match_scans: pools the field
+ * itself; bounds_out (optional): rplgpu_wide_match_blocks words; best: 8 words; work: 8 words; status (optional).
+ * Allocates its device buffers per call and returns when the results are in place: a door, not a hot path. */
+int32_t rplgpu_match_wide(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                          const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                          const float *motion, const float *pose2d, const float *t0, const float *pivot,
+                          const rplgpu_wide_match_t *m, const int8_t *field, uint32_t *bounds_out, uint32_t best[8],
+                          uint32_t work[8], uint32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,10 @@ ERR_SCAN_OVERFLOW = -6
 
 SCAN_ALL_INVALID = 0x1
 SCAN_CELL_RANGE = 0x2
+WIDE_MATCH_BLOCK = 8          # RPLGPU_WIDE_MATCH_BLOCK (E24)
+MAX_WIDE_SHIFT = 256          # RPLGPU_MAX_WIDE_SHIFT
+MAX_WIDE_BLOCKS = 65536       # RPLGPU_MAX_WIDE_BLOCKS
+WIDE_MATCH_UNPROVEN = 0x1     # word 7 of E24's result words
 SCAN_TABLE_FULL = 0x4
 SCAN_OUT_TRUNCATED = 0x8
 
@@ -190,6 +194,14 @@ ABI_SYMBOLS = [
     "rplgpu_score_poses_agree_dev",
     "rplgpu_score_poses_agree",
     "rplgpu_beam_agree_points_host",
+    "rplgpu_default_wide_match",
+    "rplgpu_wide_match_check",
+    "rplgpu_wide_match_blocks",
+    "rplgpu_wide_match_scratch_words",
+    "rplgpu_pool_field_host",
+    "rplgpu_pool_field_dev",
+    "rplgpu_match_wide_dev",
+    "rplgpu_match_wide",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -641,6 +653,44 @@ class BeamAgree(C.Structure):
         return int(load_library().rplgpu_beam_agree_check(C.byref(self)))
 
 
+class WideMatch(C.Structure):
+    """Mirror of ``rplgpu_wide_match_t`` (E24: scans matched over a wide window by bound and refine)."""
+
+    _fields_ = [
+        ("origin_x", C.c_float),
+        ("origin_y", C.c_float),
+        ("resolution", C.c_float),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("shift_x", C.c_uint32),
+        ("shift_y", C.c_uint32),
+        ("rot_steps", C.c_uint32),
+        ("rot_step", C.c_float),
+        ("max_blocks", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "WideMatch":
+        """The library's own defaults (``rplgpu_default_wide_match``), then the overrides."""
+        m = cls()
+        load_library().rplgpu_default_wide_match(C.byref(m))
+        for k, v in kw.items():
+            if not hasattr(m, k):
+                raise AttributeError(k)
+            setattr(m, k, v)
+        return m
+
+    def check(self) -> int:
+        """``rplgpu_wide_match_check``: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_wide_match_check(C.byref(self)))
+
+    def scan_match(self, shift_x: int = 0, shift_y: int = 0) -> "ScanMatch":
+        """The E13 spec with the same grid, rot_steps and rot_step: what ``apply_match_dev`` takes beside E24's
+        result words, and the spec whose ``scan_match_rotations`` is E24's rotation table."""
+        return ScanMatch(self.origin_x, self.origin_y, self.resolution, self.width, self.height, shift_x, shift_y,
+                         self.rot_steps, self.rot_step)
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -907,6 +957,19 @@ def load_library() -> C.CDLL:
                                              C.POINTER(BeamAgree), vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.rplgpu_beam_agree_points_host.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, u32, vp, C.POINTER(BeamAgree),
                                                   vp, vp, vp, vp, vp, vp]
+    lib.rplgpu_default_wide_match.argtypes = [C.POINTER(WideMatch)]
+    lib.rplgpu_default_wide_match.restype = None
+    lib.rplgpu_wide_match_check.argtypes = [C.POINTER(WideMatch)]
+    lib.rplgpu_wide_match_blocks.argtypes = [C.POINTER(WideMatch)]
+    lib.rplgpu_wide_match_blocks.restype = u32
+    lib.rplgpu_wide_match_scratch_words.argtypes = [C.POINTER(WideMatch), u32]
+    lib.rplgpu_wide_match_scratch_words.restype = u64
+    lib.rplgpu_pool_field_host.argtypes = [vp, u32, u32, vp]
+    lib.rplgpu_pool_field_dev.argtypes = [vp, C.POINTER(WideMatch), vp, u64, u32, vp, u64]
+    lib.rplgpu_match_wide_dev.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp, vp,
+                                          C.POINTER(WideMatch), vp, u64, u32, vp, u64, vp, u64, vp, vp, vp, vp]
+    lib.rplgpu_match_wide.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp, vp,
+                                      C.POINTER(WideMatch), vp, vp, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1390,6 +1453,54 @@ class RplGpu:
             C.byref(spec), poses.ctypes.data, P, field.ctypes.data, weights.ctypes.data, result.ctypes.data,
             status.ctypes.data, counts.ctypes.data, mask.ctypes.data, agree.ctypes.data))
         return weights, result, int(status[0]), counts, mask, agree
+
+    def pool_field_dev(self, match: "WideMatch", d_field: int, field_stride: int, F: int, d_pooled: int,
+                       pooled_stride: int):
+        """E24: the pooled field P (the 8 x 8 sliding maximum of max(byte, 0), (height + 7) x (width + 7) int8) of
+        each of the F fields at d_field, at d_pooled + f * pooled_stride."""
+        self._check(self._lib.rplgpu_pool_field_dev(
+            self._h, C.byref(match), d_field, field_stride, F, d_pooled, pooled_stride))
+
+    def match_wide_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int, params: Params,
+                       d_motion: int, d_pose2d: int, d_pivot: int, match: "WideMatch", d_field: int,
+                       field_stride: int, field_per_group: int, d_pooled: int, pooled_stride: int, d_bounds: int,
+                       bounds_stride: int, d_scratch: int, d_best: int, d_work: int, d_status: int = 0):
+        """E24: per group of scans E13's best over a window of up to 256 cells a side, by bound and refine: the
+        bounds volume (uint32, ``wide_match_blocks`` words, bounds_stride apart), eight result words at d_best + 8 g
+        and eight work words at d_work + 8 g.  d_scratch: ``wide_match_scratch_words(match, G)`` uint32 words."""
+        self._check(self._lib.rplgpu_match_wide_dev(
+            self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d, d_pivot,
+            C.byref(match), d_field, field_stride, field_per_group, d_pooled, pooled_stride, d_bounds, bounds_stride,
+            d_scratch, d_best, d_work, d_status))
+
+    def match_wide(self, scans: np.ndarray, lens, params: Params, match: "WideMatch", field: np.ndarray,
+                   motion=None, pose2d=None, t0=None, pivot=None, want_bounds: bool = True):
+        """E24, one group, host buffers: scans (S, n) NODE_DTYPE and a (height, width) int8 field ->
+        ``(bounds (2K+1, nby, nbx) uint32 or None, best (8,) uint32, work (8,) uint32, status)``."""
+        scans = np.ascontiguousarray(scans)
+        if scans.dtype != NODE_DTYPE or scans.ndim != 2:
+            raise TypeError("scans must be a 2-D array of abi.NODE_DTYPE")
+        field = np.ascontiguousarray(field, np.int8)
+        if field.shape != (match.height, match.width):
+            raise TypeError("field must be a (height, width) int8 array")
+        S, n = scans.shape
+        lens = np.ascontiguousarray(lens, np.uint32)
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
+        motion, pose2d, t0, pivot = f32(motion), f32(pose2d), f32(t0), f32(pivot)
+        bounds = None
+        if want_bounds:
+            s = WIDE_MATCH_BLOCK
+            bounds = np.zeros((2 * match.rot_steps + 1, (2 * match.shift_y + s) // s, (2 * match.shift_x + s) // s),
+                              np.uint32)
+        best = np.zeros(8, np.uint32)
+        work = np.zeros(8, np.uint32)
+        status = np.zeros(1, np.uint32)
+        ptr = lambda a: 0 if a is None else a.ctypes.data  # noqa: E731
+        self._check(self._lib.rplgpu_match_wide(
+            self._h, scans.ctypes.data, n, lens.ctypes.data, S, C.byref(params), ptr(motion), ptr(pose2d), ptr(t0),
+            ptr(pivot), C.byref(match), field.ctypes.data, ptr(bounds), best.ctypes.data, work.ctypes.data,
+            status.ctypes.data))
+        return bounds, best, work, int(status[0])
 
     def resample_poses_dev(self, d_weights: int, weight_stride: int, d_poses: int, pose_stride: int,
                            poses_per_group: int, G: int, P: int, M: int, d_u: int, d_delta: int, n_delta: int,
@@ -2414,3 +2525,34 @@ def beam_agree_points_host(x, y, slot, index, n_scans: int, n_stride: int, poses
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_beam_agree_points_host")
     return counts, mask, weights[:P], result, agree, int(status[0])
+
+
+def wide_match_check(match: WideMatch) -> None:
+    """Host only: validates an E24 spec by the library's own rplgpu_wide_match_check; raises RplGpuError."""
+    rc = load_library().rplgpu_wide_match_check(C.byref(match))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_wide_match_check")
+
+
+def wide_match_blocks(match: WideMatch) -> int:
+    """Host only: the words of one group's bounds volume, (2K + 1) * nby * nbx; 0 for a spec the check refuses."""
+    return int(load_library().rplgpu_wide_match_blocks(C.byref(match)))
+
+
+def wide_match_scratch_words(match: WideMatch, G: int) -> int:
+    """Host only: the uint32 words of scratch ``match_wide_dev`` takes for G groups; 0 for a refused spec."""
+    return int(load_library().rplgpu_wide_match_scratch_words(C.byref(match), G))
+
+
+def pool_field_host(field) -> np.ndarray:
+    """Host only: E24's pooled field of a (height, width) int8 field, (height + 7, width + 7) int8, by the library's
+    own rplgpu_pool_field_host."""
+    field = np.ascontiguousarray(field, np.int8)
+    if field.ndim != 2:
+        raise TypeError("field must be a (height, width) int8 array")
+    H, W = field.shape
+    out = np.zeros((H + WIDE_MATCH_BLOCK - 1, W + WIDE_MATCH_BLOCK - 1), np.int8)
+    rc = load_library().rplgpu_pool_field_host(field.ctypes.data, W, H, out.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_pool_field_host")
+    return out

@@ -1,5 +1,5 @@
 // rpl_host.hpp — what the host translation units share: rplgpu_api.hip (handle, single scans, batches, clouds,
-// decode, messages, exchange), rplgpu_scan_stages.hip (E9 - E14) and rplgpu_pose_stages.hip (E15 - E22).
+// decode, messages, exchange), rplgpu_scan_stages.hip (E9 - E14), rplgpu_pose_stages.hip (E15 - E23) and rplgpu_wide_stages.hip (E24).
 //
 // Host code only, internal to the library: everything in rpl::host has hidden visibility, so nothing declared here
 // is an exported symbol.  rplgpu_api.hip defines the handle's helpers, rplgpu_scan_stages.hip the scan-stage

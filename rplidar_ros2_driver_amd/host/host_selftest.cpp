@@ -264,6 +264,31 @@ int main(int argc, char **argv) {
     }
     std::printf("scan match: best %u at (k, j, i) = (%d, %d, %d), %u at the prior\n", mr.score, mr.k, mr.j, mr.i,
                 mr.score_at_prior);
+    // E24 on the same return and costmap with a window of 12 x 9 cells (4 x 3 blocks of 8 x 8 shifts): only the
+    // block of shifts i in [-4, 3], j in [-1, 6] has the lethal cell under its pooled look-up, it is both seeds, its
+    // best score 100 is the floor and no other bound reaches it: one block listed, E13's answer, proven.
+    rplgpu_wide_match_t wide;
+    rplgpu_default_wide_match(&wide);
+    wide.shift_x = 12;
+    wide.shift_y = 9;
+    wide.rot_steps = 0;
+    rplgpu_host::ScanPath::WideMatchResult wr;
+    uint32_t wstatus = 99;
+    if (!path.match_wide(one, rplgpu_host::ScanConfig(), prior, nullptr, nullptr, nullptr, cost_msg, wide, wr,
+                         &wstatus)) {
+      std::fprintf(stderr, "wide scan match failed: %s\n", path.last_error().c_str());
+      return 11;
+    }
+    if (wr.score != 100 || wr.k != 0 || wr.j != 0 || wr.i != 1 || wr.points != 1 || wr.score_at_prior != 99 ||
+        wr.ties != 1 || !wr.proven || wr.blocks != 12 || wr.greatest_bound != 100 || wr.floor != 100 ||
+        wr.listed != 1 || wstatus != 0) {
+      std::fprintf(stderr, "wide scan match: wrong answer (%u at %d %d %d, %u ties, proven %d, %u of %u blocks, bound %u, floor %u)\n",
+                   wr.score, wr.k, wr.j, wr.i, wr.ties, (int)wr.proven, wr.listed, wr.blocks, wr.greatest_bound,
+                   wr.floor);
+      return 12;
+    }
+    std::printf("wide scan match: best %u at (k, j, i) = (%d, %d, %d), %u of %u blocks scored\n", wr.score, wr.k, wr.j,
+                wr.i, wr.listed, wr.blocks);
     // E14: the three rays of the E11 leg added twice into a count map.  Per call the row of the sensor gets
     // misses 3 3 2 2 1 1 (the whole ray beyond obstacle_max leaves its end cell 4 alone, the cut one counts its
     // end cell 5) and one hit in cell 2; after two calls the default rule (2 observations, 10 %) gives the E11 row.

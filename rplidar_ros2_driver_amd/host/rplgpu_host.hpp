@@ -24,6 +24,7 @@
 //         -> rplgpu_host::ScanPath::inflate_grid(grid_msg, inflation, costmap_msg)  (E12)
 //   mat the localisation side's loop (a correlative scan matcher's search window over a likelihood field):
 //         -> rplgpu_host::ScanPath::match_scans(scans, ..., field_msg, window, result)  (E13)
+//         -> rplgpu_host::ScanPath::match_wide(scans, ..., field_msg, window, result)   (E24: up to 256 cells a side)
 //   map the mapping side's loop (a map that many time steps vote on, each at its matched pose):
 //         -> rplgpu_host::ScanPath::update_map(scans, ..., counts) and fill_map_grid(counts, ..., grid_msg)  (E14)
 //   pf  the localisation side's other loop (a particle filter's sensor update over a list of arbitrary poses):
@@ -451,6 +452,61 @@ class ScanPath {
     result.points = best[4];
     result.score_at_prior = best[5];
     result.ties = best[6];
+    return true;
+  }
+
+  // ext E24 (include/rplgpu_msg.h): match_scans over a window of up to 256 cells a side, by bound and refine — what
+  // a loop closer or a relocaliser asks of a stored map.  Arguments as match_scans; shift_x / shift_y / rot_steps /
+  // rot_step / max_blocks of `window` are used.  result.proven false: the list was longer than max_blocks, the
+  // answer is the best of the two seed blocks only, and result.listed says which max_blocks proves it.  The result
+  // goes into rplgpu_apply_match_dev with an E13 spec of the same grid, rot_steps and rot_step.
+  struct WideMatchResult : MatchResult {
+    bool proven = false;
+    uint32_t blocks = 0, greatest_bound = 0, floor = 0, listed = 0;  // work words 0, 1, 3, 4
+  };
+  template <class NodeT, class OccupancyGridT>
+  bool match_wide(const std::vector<std::vector<NodeT>> &scans, const ScanConfig &cfg, const float *pose2d,
+                  const float *motion, const float *t0, const float *pivot, const OccupancyGridT &field_msg,
+                  const rplgpu_wide_match_t &window, WideMatchResult &result, uint32_t *status = nullptr) {
+    if (scans.empty()) return false;
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    rplgpu_wide_match_t m = window;
+    m.origin_x = static_cast<float>(field_msg.info.origin.position.x);
+    m.origin_y = static_cast<float>(field_msg.info.origin.position.y);
+    m.resolution = field_msg.info.resolution;
+    m.width = field_msg.info.width;
+    m.height = field_msg.info.height;
+    const size_t n_cells = static_cast<size_t>(m.width) * m.height;
+    if (n_cells == 0 || field_msg.data.size() != n_cells) return fail("match_wide: data is not width x height");
+    size_t stride = 1;
+    for (const auto &s : scans) stride = s.size() > stride ? s.size() : stride;
+    if (stride > max_n_) return fail("scan larger than the configured capacity");
+    occ_nodes_.assign(scans.size() * stride, rplgpu_node_t{});
+    occ_len_.resize(scans.size());
+    for (size_t b = 0; b < scans.size(); ++b) {
+      if (!scans[b].empty()) std::memcpy(&occ_nodes_[b * stride], scans[b].data(), scans[b].size() * 8);
+      occ_len_[b] = static_cast<uint32_t>(scans[b].size());
+    }
+    occ_prev_.assign(field_msg.data.begin(), field_msg.data.end());
+    const rplgpu_params_t p = cfg.to_params();
+    uint32_t best[8] = {0, 0, 0, 0, 0, 0, 0, 0}, work[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_match_wide(h_, occ_nodes_.data(), static_cast<uint32_t>(stride), occ_len_.data(),
+                          static_cast<uint32_t>(scans.size()), &p, motion, pose2d, t0, pivot, &m, occ_prev_.data(),
+                          nullptr, best, work, status) != RPLGPU_OK)
+      return note_error();
+    result.score = best[0];
+    result.k = static_cast<int32_t>(best[1]);
+    result.j = static_cast<int32_t>(best[2]);
+    result.i = static_cast<int32_t>(best[3]);
+    result.points = best[4];
+    result.score_at_prior = best[5];
+    result.ties = best[6];
+    result.proven = (best[7] & RPLGPU_WIDE_MATCH_UNPROVEN) == 0;
+    result.blocks = work[0];
+    result.greatest_bound = work[1];
+    result.floor = work[3];
+    result.listed = work[4];
     return true;
   }
 
