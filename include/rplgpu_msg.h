@@ -1654,6 +1654,191 @@ int32_t rplgpu_match_wide(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_
                           const rplgpu_wide_match_t *m, const int8_t *field, uint32_t *bounds_out, uint32_t best[8],
                           uint32_t work[8], uint32_t *status);
 
+/* ---- E25: poses refined below a cell by Gauss-Newton on the interpolated field (row 4; the matcher's last stage) ----
+ * E13 / E24 answer on a lattice of whole cells and rotation steps, E15 scores a pose by the byte under each point.
+ * Every 2-D matcher among E11's readers then refines below the cell: Hector's Gauss-Newton on the bilinearly
+ * interpolated map, Cartographer's Ceres matcher behind its correlative one.  Here that stage runs on the device:
+ * for every pose of a list the normal equations of ONE Gauss-Newton step of the group's points against the bilinear
+ * field, a tiny kernel that takes the step, n rounds queued on one stream, and two joining kernels to E13 / E24 on
+ * one side and E11 / E14 on the other.  Nothing in the reference refines a pose, so these rules ARE the definition
+ * (parity unpinned, as E5-E24).  After a fixed float32 front everything is integers: the sums have one answer and
+ * depend on no order; the step is a fixed sequence of correctly rounded fp64 operations with a host twin.
+ *
+ * POINTS: those of rplgpu_score_poses_dev, word for word (E1, E5 with p->ror_enable, E2, E6, d_pose2d as each
+ * sensor's MOUNT pose in the base frame, groups clamped to B, a point that is not finite ignored, group * n_stride
+ * <= 2^24).  POSES: E15's as well, (c, s, tx, ty) at d_poses + g_p * pose_stride + 4 q, the same alignment, stride
+ * and poses_per_group rules; no trigonometric function runs on the device.
+ * PER POINT (x, y) AND POSE, float32, no FMA, every operation rounded once, `/` the IEEE divide:
+ *   ax = c*x - s*y;  ay = s*x + c*y;  rx = ax + tx;  ry = ay + ty                       (E15's positions)
+ *   hu = ((rx - origin_x) / resolution) * 256.0f - 128.0f;  hv likewise from ry and origin_y
+ *   lx = ax / resolution;  ly = ay / resolution                                       (the lever about the base, cells)
+ * The point is DROPPED for this pose unless |hu| < 2^28, |hv| < 2^28, |lx| < 8192 and |ly| < 8192 (a NaN fails all
+ * four): it contributes nothing, counts in word 28 and sets RPLGPU_SCAN_CELL_RANGE in d_status[g].  From here on
+ * integers:
+ *   U = (int)floorf(hu);  i0 = U >> 8 (arithmetic);  a = U & 255;   V_, j0, b likewise from hv
+ *   Lx = (int)rintf(lx * 16.0f);  Ly likewise                      (ties to even; |L| <= 2^17)
+ *   m(ix, iy) = max((int8)field[iy * width + ix], 0), 0 outside [0, width) x [0, height)   (field g_f as E15)
+ *   m00 = m(i0, j0), m10 = m(i0+1, j0), m01 = m(i0, j0+1), m11 = m(i0+1, j0+1)
+ *   V  = (256-a)(256-b) m00 + a (256-b) m10 + (256-a) b m01 + a b m11           (Q16, 0 .. 127 * 65536)
+ *   Gx = (256-b)(m10 - m00) + b (m11 - m01);  Gy = (256-a)(m01 - m00) + a (m11 - m10)   (Q8 per cell, |G| < 2^15)
+ *   Gt = Gy * Lx - Gx * Ly                                                      (Q12 per radian, |Gt| < 2^33)
+ *   E  = target * 65536 - V                                                     (|E| < 2^23)
+ * Cell centres are the interpolation nodes (the -128): a point on a cell centre has a = b = 0 and V = 65536 m00.
+ * SUMS: RPLGPU_REFINE_WORDS = 32 uint32 per pose at d_sums + g * sums_stride + 32 q (sums_stride in words, >= 32 P
+ * and a multiple of 4, d_sums 16-byte aligned), little-endian two's complement; with the 2^24 points a group can have:
+ *   words   value    width  bound        words   value    width  bound
+ *   0 - 1   S Gx^2   u64    2^54         12 - 14 S Gx Gt  i96    2^72
+ *   2 - 3   S Gx Gy  i64    2^54         15 - 17 S Gy Gt  i96    2^72
+ *   4 - 5   S Gy^2   u64    2^54         18 - 20 S Gt^2   u96    2^90
+ *   6 - 7   S Gx E   i64    2^62         21 - 23 S Gt E   i96    2^80
+ *   8 - 9   S Gy E   i64    2^62         24 - 26 S E^2    u96    2^70
+ *   10 - 11 S V      u64    2^47         27 n, the points that contributed;  28 the dropped points;  29 - 31 zero
+ * One point can push S Gt^2 past 2^64.  A group without points has 32 zero words per pose; words at and beyond 32 P
+ * of a group are never changed.
+ * STEP, fp64, every operation below rounded once, none fused.  d64(v) is the IEEE conversion of a 64-bit value (signed
+ * or unsigned as the table says); d96(w0, w1, w2) = ((double)w2 * 2^32 + (double)w1) * 2^32 + (double)w0 with w2 read
+ * as int32 for i96 and uint32 for u96, w1 and w0 as uint32.  Scalings by powers of two (exact):
+ *   a11 = d(S Gx^2) 2^-16;  a12 = d(S Gx Gy) 2^-16;  a22 = d(S Gy^2) 2^-16;  a13 = d(S Gx Gt) 2^-20;
+ *   a23 = d(S Gy Gt) 2^-20;  a33 = d(S Gt^2) 2^-24;  g1 = d(S Gx E) 2^-24;  g2 = d(S Gy E) 2^-24;  g3 = d(S Gt E) 2^-28
+ *   aii = aii + (double)damping * aii                                            (i = 1, 2, 3)
+ *   c11 = a22*a33 - a23*a23;  c12 = a13*a23 - a12*a33;  c13 = a12*a23 - a13*a22;
+ *   c22 = a11*a33 - a13*a13;  c23 = a12*a13 - a11*a23;  c33 = a11*a22 - a12*a12;
+ *   det = (a11*c11 + a12*c12) + a13*c13
+ *   dx = ((c11*g1 + c12*g2) + c13*g3) / det;  dy = ((c12*g1 + c22*g2) + c23*g3) / det;
+ *   dt = ((c13*g1 + c23*g2) + c33*g3) / det                                      (dx, dy in cells, dt in rad)
+ * NO STEP, the pose copied bit for bit and the step words 0: n < min_points (RPLGPU_REFINE_FEW), else det not > 0 or
+ * not finite, or one of dx, dy, dt not finite (RPLGPU_REFINE_SINGULAR).  Otherwise RPLGPU_REFINE_STEPPED, and dx, dy
+ * are clamped to +-(double)max_step_cells (RPLGPU_REFINE_CLAMP_X / _Y), dt to +-(double)max_rot (RPLGPU_REFINE_CLAMP_T);
+ *   h = 0.5*dt;  hh = h*h;  den = 1.0 + hh;  dc = (1.0 - hh) / den;  ds = (h + h) / den
+ * is the exact rotation by 2 atan h, (1, 0) for dt = 0.  Then in float32, no FMA, as E16's move, with fc = (float)dc,
+ * fs = (float)ds, mx = (float)(dx * (double)resolution), my likewise:
+ *   c' = c*fc - s*fs;  s' = s*fc + c*fs;  tx' = tx + mx;  ty' = ty + my;   a NaN is stored as 0x7FC00000.
+ * STEP WORDS (optional), four per pose at d_step + g * step_stride + 4 q: the bits of mx, my, (float)dt, and the flags.
+ * RESULT, eight words per group at d_result + 8 g: 0 the poses stepped, 1 not stepped for too few points, 2 not
+ * stepped for singular or not finite, 3 the poses with a clamp (the step's words; 0 after rplgpu_refine_sums_dev
+ * alone); 4 the smallest q with the greatest S V, 5 and 6 that S V low and high, 7 the group's finite points (the
+ * sums' words; rplgpu_refine_step_dev leaves them alone). */
+#define RPLGPU_REFINE_WORDS    32u
+#define RPLGPU_REFINE_PLANES   29u   /* the 64-bit scratch planes per pose: one per live word of the sums */
+#define RPLGPU_REFINE_MAX_ITERS 16u
+#define RPLGPU_REFINE_STEPPED  0x01u
+#define RPLGPU_REFINE_FEW      0x02u
+#define RPLGPU_REFINE_SINGULAR 0x04u
+#define RPLGPU_REFINE_CLAMP_X  0x08u
+#define RPLGPU_REFINE_CLAMP_Y  0x10u
+#define RPLGPU_REFINE_CLAMP_T  0x20u
+typedef struct rplgpu_pose_refine {
+  float    origin_x, origin_y;   /* the field's grid: as rplgpu_pose_score_t */
+  float    resolution;
+  uint32_t width, height;        /* 1 .. RPLGPU_MAX_OCC_DIM */
+  uint32_t target;               /* 1 .. 127: the field value a perfectly placed point has */
+  float    damping;              /* >= 0: aii += damping * aii (Levenberg-Marquardt's diagonal) */
+  float    max_step_cells;       /* > 0: the clamp of dx and dy */
+  float    max_rot;              /* rad, > 0: the clamp of dt */
+  uint32_t min_points;           /* >= 3 */
+} rplgpu_pose_refine_t;
+/* E11's default grid, target 127, damping 0, max_step_cells 2, max_rot 0.1, min_points 16 */
+void rplgpu_default_pose_refine(rplgpu_pose_refine_t *r);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL, everything rplgpu_pose_score_check refuses in
+ * the grid, a target of 0 or above 127, a damping that is negative or not finite, a max_step_cells or max_rot that is
+ * not > 0 or not finite, min_points below 3.  The device path uses this function. */
+int32_t rplgpu_pose_refine_check(const rplgpu_pose_refine_t *r);
+/* Host only.  The uint32 words of scratch a call over G groups of P poses takes: 2 * RPLGPU_REFINE_PLANES * G * P
+ * (one 64-bit word per pose and live word of the sums: the kernel adds 32-bit limbs into 64-bit planes, so no carry
+ * crosses an atomic); 0 for G = 0, P = 0 or P above RPLGPU_MAX_POSES. */
+uint64_t rplgpu_refine_scratch_words(uint32_t G, uint32_t P);
+/* Host only: the SUMS of ONE group in plain C++ over n points already in the base frame (a point that is not finite
+ * is ignored), for P poses of four floats; sums_out: 32 P words, written whole; result (optional): the eight words
+ * with 0 - 3 zero; status (optional): RPLGPU_SCAN_CELL_RANGE or 0.  RPLGPU_ERR_INVALID_ARG and nothing written for a
+ * spec the check refuses, a NULL pointer, P = 0 or above RPLGPU_MAX_POSES, n above 2^24. */
+int32_t rplgpu_refine_sums_host(const float *x, const float *y, uint32_t n, const float *poses, uint32_t P,
+                                const int8_t *field, const rplgpu_pose_refine_t *r, uint32_t *sums_out,
+                                uint32_t result[8], uint32_t *status);
+/* Host only: the STEP of ONE pose in plain C++, the sequence above operation for operation (the device runs the same
+ * sequence through __dmul_rn / __dadd_rn / __ddiv_rn).  sums: 32 words; pose_out may be pose; step (optional): the
+ * four step words.  Returns the flags, or RPLGPU_ERR_INVALID_ARG (negative) and nothing written for a spec the check
+ * refuses or a NULL pointer. */
+int32_t rplgpu_refine_step_host(const uint32_t sums[32], const rplgpu_pose_refine_t *r, const float pose[4],
+                                float pose_out[4], uint32_t step[4]);
+/* Host only: the covariance Hector and Karto publish with a match.  A = the matrix of STEP without the damping;
+ * cov9 = S A^-1 S row-major over (x, y, theta) with S = diag(resolution, resolution, 1): metres and radians.  fp64,
+ * the cofactors and det of STEP.  RPLGPU_ERR_INVALID_ARG and nine zeros for a det that is not > 0 or not finite;
+ * RPLGPU_ERR_INVALID_ARG and nothing written for a spec the check refuses or a NULL pointer. */
+int32_t rplgpu_refine_covariance(const uint32_t sums[32], const rplgpu_pose_refine_t *r, double cov9[9]);
+/* The SUMS on the handle's stream: E15's arguments with the new spec, d_sums / sums_stride as above, d_result eight
+ * words a group (words 0 - 3 zeroed), d_status optional (RPLGPU_SCAN_OUT_TRUNCATED and RPLGPU_SCAN_CELL_RANGE, cleared
+ * on the stream by the call).  SCRATCH is the caller's: rplgpu_refine_scratch_words(G, P) uint32 words at d_scratch,
+ * 8-byte aligned, cleared by the call's own prepare launch; words beyond it are never touched.  The field and the
+ * poses are only read.  RPLGPU_ERR_INVALID_ARG for everything rplgpu_score_poses_dev refuses (the spec by
+ * rplgpu_pose_refine_check, sums for weights), a missing d_scratch or one not 8-byte aligned, a d_sums not 16-byte
+ * aligned.  A refused call changes no output.  Asynchronous on the handle's stream. */
+int32_t rplgpu_refine_sums_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                               const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                               const float *d_motion, const float *d_pose2d, const rplgpu_pose_refine_t *r,
+                               const float *d_poses, uint32_t P, uint64_t pose_stride, uint32_t poses_per_group,
+                               const int8_t *d_field, uint64_t field_stride, uint32_t field_per_group,
+                               uint32_t *d_sums, uint64_t sums_stride, uint32_t *d_scratch, uint32_t *d_result,
+                               uint32_t *d_status);
+/* The STEP of G groups of P poses: pose q of group g is read as above, its sums at d_sums + g * sums_stride + 32 q,
+ * and the stepped pose goes to d_poses_out + g * out_stride + 4 q (out_stride in floats, >= 4 P and a multiple of 4,
+ * 16-byte aligned), the step words (optional) to d_step + g * step_stride + 4 q (step_stride >= 4 P words), result
+ * words 0 - 3 to d_result + 8 g.  d_poses_out == d_poses is allowed, element-wise, when out_stride == pose_stride
+ * and every group reads its own list (poses_per_group not 0, or G = 1); any other overlap of the two is refused.
+ * RPLGPU_ERR_INVALID_ARG also for a spec the check refuses, G = 0 or above 65535, P = 0 or above RPLGPU_MAX_POSES, a
+ * missing or misaligned pointer and the stride rules.  A refused call changes no output.  Asynchronous. */
+int32_t rplgpu_refine_step_dev(rplgpu_handle_t h, const uint32_t *d_sums, uint64_t sums_stride,
+                               const rplgpu_pose_refine_t *r, const float *d_poses, uint64_t pose_stride,
+                               uint32_t poses_per_group, uint32_t G, uint32_t P, float *d_poses_out,
+                               uint64_t out_stride, uint32_t *d_step, uint64_t step_stride, uint32_t *d_result);
+/* `iters` rounds (1 .. RPLGPU_REFINE_MAX_ITERS) of SUMS + STEP queued on the stream with no read in between: round
+ * 0 reads d_poses, every later round the list the round before left in d_poses_out (every group its own).  Behind
+ * the call d_sums, d_step and d_result are the LAST round's (so the sums are those of the list BEFORE the last step)
+ * and d_poses_out is the final list; d_status collects every round.  iters = 1 is exactly rplgpu_refine_sums_dev
+ * followed by rplgpu_refine_step_dev.  The refusals of both; a refused call changes no output. */
+int32_t rplgpu_refine_poses_dev(rplgpu_handle_t h, const rplgpu_node_t *d_nodes, uint32_t n_stride,
+                                const uint32_t *d_n_per_scan, uint32_t B, uint32_t group, const rplgpu_params_t *p,
+                                const float *d_motion, const float *d_pose2d, const rplgpu_pose_refine_t *r,
+                                const float *d_poses, uint32_t P, uint64_t pose_stride, uint32_t poses_per_group,
+                                const int8_t *d_field, uint64_t field_stride, uint32_t field_per_group,
+                                uint32_t iters, float *d_poses_out, uint64_t out_stride, uint32_t *d_sums,
+                                uint64_t sums_stride, uint32_t *d_step, uint64_t step_stride, uint32_t *d_scratch,
+                                uint32_t *d_result, uint32_t *d_status);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp), shaped as rplgpu_score_poses: poses 4 P floats;
+ * poses_out: 4 P floats; sums_out (optional): 32 P words; step_out (optional): 4 P words; result: 8 words; status
+ * (optional).  Allocates its device buffers per call and returns when the results are in place. */
+int32_t rplgpu_refine_poses(rplgpu_handle_t h, const rplgpu_node_t *nodes, uint32_t n_stride,
+                            const uint32_t *n_per_scan, uint32_t n_scans, const rplgpu_params_t *p,
+                            const float *motion, const float *pose2d, const float *t0,
+                            const rplgpu_pose_refine_t *r, const float *poses, uint32_t P, const int8_t *field,
+                            uint32_t iters, float *poses_out, uint32_t *sums_out, uint32_t *step_out,
+                            uint32_t result[8], uint32_t *status);
+/* JOINING E13 / E24: the eight result words of group g at d_best + 8 g become ONE pose (c', s', x', y') at
+ * d_poses_out + g * out_stride (out_stride in floats, >= 4 and a multiple of 4, 16-byte aligned): a list of P = 1 with
+ * poses_per_group = 1.  `m` is a checked rplgpu_scan_match_t: its resolution, K and the table
+ * of rplgpu_scan_match_rotations are used.  The base prior (c0, s0, x0, y0) = the four floats at d_prior + 4 g, or
+ * (1, 0, px, py) when d_prior is NULL; (px, py) = d_pivot[2g], d_pivot[2g + 1], (0, 0) when NULL; (k, j, i) words
+ * 1 - 3, (c, s) the table's entry k.  E13's APPLYING IT in float32, no FMA, in this order:
+ *   c' = c*c0 - s*s0;  s' = s*c0 + c*s0;  qx = x0 - px;  qy = y0 - py;
+ *   x' = ((c*qx - s*qy) + px) + (float)i * resolution;  y' = ((s*qx + c*qy) + py) + (float)j * resolution
+ * A k outside [-K, K] keeps the prior, bit for bit.  RPLGPU_ERR_INVALID_ARG for a spec the check refuses, G = 0 or
+ * above 65535, a missing d_best / d_poses_out, a misaligned pointer, the stride rule.  A refused call changes nothing. */
+int32_t rplgpu_match_poses_dev(rplgpu_handle_t h, const uint32_t *d_best, const rplgpu_scan_match_t *m,
+                               const float *d_pivot, const float *d_prior, uint32_t G, float *d_poses_out,
+                               uint64_t out_stride);
+/* JOINING E11 / E14: pose q_g of group g's list, (c, s, x, y) at d_poses + g_p * pose_stride + 4 q_g, composed in
+ * front of every mount pose of the group.  q_g = q when d_result is NULL, else word 4 of d_result + 8 g (E25's best
+ * pose); a q_g >= P copies the mount poses unchanged.  For scan sc of group g (group clamped to B) with the mount
+ * (r00 r01 tx r10 r11 ty) = d_pose2d_in + 6 sc (NULL: identity), float32, no FMA:
+ *   r00' = c*r00 - s*r10;  r01' = c*r01 - s*r11;  r10' = s*r00 + c*r10;  r11' = s*r01 + c*r11;
+ *   tx' = (c*tx - s*ty) + x;  ty' = (s*tx + c*ty) + y
+ * go to d_pose2d_out + 6 sc, the poses rplgpu_map_update_dev and rplgpu_occupancy_grid_dev take.  d_pose2d_out ==
+ * d_pose2d_in is allowed (element-wise).  RPLGPU_ERR_INVALID_ARG for group = 0, P = 0 or above RPLGPU_MAX_POSES, a
+ * missing d_poses / d_pose2d_out, a misaligned pointer, the E15 stride rules; RPLGPU_ERR_CAPACITY for B above the
+ * handle's max_batch.  A refused call changes nothing.  Asynchronous on the handle's stream. */
+int32_t rplgpu_compose_poses_dev(rplgpu_handle_t h, const float *d_poses, uint64_t pose_stride,
+                                 uint32_t poses_per_group, uint32_t P, const uint32_t *d_result, uint32_t q,
+                                 const float *d_pose2d_in, uint32_t B, uint32_t group, float *d_pose2d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,15 @@ WIDE_MATCH_BLOCK = 8          # RPLGPU_WIDE_MATCH_BLOCK (E24)
 MAX_WIDE_SHIFT = 256          # RPLGPU_MAX_WIDE_SHIFT
 MAX_WIDE_BLOCKS = 65536       # RPLGPU_MAX_WIDE_BLOCKS
 WIDE_MATCH_UNPROVEN = 0x1     # word 7 of E24's result words
+REFINE_WORDS = 32             # RPLGPU_REFINE_WORDS (E25): uint32 words of sums per pose
+REFINE_PLANES = 29            # RPLGPU_REFINE_PLANES
+REFINE_MAX_ITERS = 16         # RPLGPU_REFINE_MAX_ITERS
+REFINE_STEPPED = 0x01         # E25's step flags
+REFINE_FEW = 0x02
+REFINE_SINGULAR = 0x04
+REFINE_CLAMP_X = 0x08
+REFINE_CLAMP_Y = 0x10
+REFINE_CLAMP_T = 0x20
 SCAN_TABLE_FULL = 0x4
 SCAN_OUT_TRUNCATED = 0x8
 
@@ -202,6 +211,18 @@ ABI_SYMBOLS = [
     "rplgpu_pool_field_dev",
     "rplgpu_match_wide_dev",
     "rplgpu_match_wide",
+    "rplgpu_default_pose_refine",
+    "rplgpu_pose_refine_check",
+    "rplgpu_refine_scratch_words",
+    "rplgpu_refine_sums_host",
+    "rplgpu_refine_step_host",
+    "rplgpu_refine_covariance",
+    "rplgpu_refine_sums_dev",
+    "rplgpu_refine_step_dev",
+    "rplgpu_refine_poses_dev",
+    "rplgpu_refine_poses",
+    "rplgpu_match_poses_dev",
+    "rplgpu_compose_poses_dev",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -691,6 +712,38 @@ class WideMatch(C.Structure):
                          self.rot_steps, self.rot_step)
 
 
+class PoseRefine(C.Structure):
+    """Mirror of ``rplgpu_pose_refine_t`` (E25: poses refined below a cell by Gauss-Newton on the field)."""
+
+    _fields_ = [
+        ("origin_x", C.c_float),
+        ("origin_y", C.c_float),
+        ("resolution", C.c_float),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("target", C.c_uint32),
+        ("damping", C.c_float),
+        ("max_step_cells", C.c_float),
+        ("max_rot", C.c_float),
+        ("min_points", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **kw) -> "PoseRefine":
+        """The library's own defaults (``rplgpu_default_pose_refine``), then the overrides."""
+        r = cls()
+        load_library().rplgpu_default_pose_refine(C.byref(r))
+        for k, v in kw.items():
+            if not hasattr(r, k):
+                raise AttributeError(k)
+            setattr(r, k, v)
+        return r
+
+    def check(self) -> int:
+        """``rplgpu_pose_refine_check``: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_pose_refine_check(C.byref(self)))
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -970,6 +1023,26 @@ def load_library() -> C.CDLL:
                                           C.POINTER(WideMatch), vp, u64, u32, vp, u64, vp, u64, vp, vp, vp, vp]
     lib.rplgpu_match_wide.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp, vp,
                                       C.POINTER(WideMatch), vp, vp, vp, vp, vp]
+    lib.rplgpu_default_pose_refine.argtypes = [C.POINTER(PoseRefine)]
+    lib.rplgpu_default_pose_refine.restype = None
+    lib.rplgpu_pose_refine_check.argtypes = [C.POINTER(PoseRefine)]
+    lib.rplgpu_refine_scratch_words.argtypes = [u32, u32]
+    lib.rplgpu_refine_scratch_words.restype = u64
+    lib.rplgpu_refine_sums_host.argtypes = [vp, vp, u32, vp, u32, vp, C.POINTER(PoseRefine), vp, vp, vp]
+    lib.rplgpu_refine_step_host.argtypes = [vp, C.POINTER(PoseRefine), vp, vp, vp]
+    lib.rplgpu_refine_covariance.argtypes = [vp, C.POINTER(PoseRefine), vp]
+    lib.rplgpu_refine_sums_dev.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp,
+                                           C.POINTER(PoseRefine), vp, u32, u64, u32, vp, u64, u32, vp, u64, vp, vp,
+                                           vp]
+    lib.rplgpu_refine_step_dev.argtypes = [vp, vp, u64, C.POINTER(PoseRefine), vp, u64, u32, u32, u32, vp, u64, vp,
+                                           u64, vp]
+    lib.rplgpu_refine_poses_dev.argtypes = [vp, vp, u32, vp, u32, u32, C.POINTER(Params), vp, vp,
+                                            C.POINTER(PoseRefine), vp, u32, u64, u32, vp, u64, u32, u32, vp, u64, vp,
+                                            u64, vp, u64, vp, vp, vp]
+    lib.rplgpu_refine_poses.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, vp, vp, C.POINTER(PoseRefine),
+                                        vp, u32, vp, u32, vp, vp, vp, vp, vp]
+    lib.rplgpu_match_poses_dev.argtypes = [vp, vp, C.POINTER(ScanMatch), vp, vp, u32, vp, u64]
+    lib.rplgpu_compose_poses_dev.argtypes = [vp, vp, u64, u32, u32, vp, u32, vp, u32, u32, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1501,6 +1574,82 @@ class RplGpu:
             ptr(pivot), C.byref(match), field.ctypes.data, ptr(bounds), best.ctypes.data, work.ctypes.data,
             status.ctypes.data))
         return bounds, best, work, int(status[0])
+
+    def refine_sums_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int, params: Params,
+                        d_motion: int, d_pose2d: int, spec: "PoseRefine", d_poses: int, P: int, pose_stride: int,
+                        poses_per_group: int, d_field: int, field_stride: int, field_per_group: int, d_sums: int,
+                        sums_stride: int, d_scratch: int, d_result: int, d_status: int = 0):
+        """E25: per group of scans and pose of the list the 32 words of the Gauss-Newton sums against the bilinear
+        field at d_sums + g * sums_stride + 32 q, eight result words at d_result + 8 g.  d_scratch:
+        ``refine_scratch_words(G, P)`` uint32 words."""
+        self._check(self._lib.rplgpu_refine_sums_dev(
+            self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d, C.byref(spec),
+            d_poses, P, pose_stride, poses_per_group, d_field, field_stride, field_per_group, d_sums, sums_stride,
+            d_scratch, d_result, d_status))
+
+    def refine_step_dev(self, d_sums: int, sums_stride: int, spec: "PoseRefine", d_poses: int, pose_stride: int,
+                        poses_per_group: int, G: int, P: int, d_poses_out: int, out_stride: int, d_step: int,
+                        step_stride: int, d_result: int):
+        """E25: one Gauss-Newton step of every pose from its sums: the stepped list at d_poses_out, the step words
+        (optional) at d_step, result words 0 - 3 at d_result + 8 g."""
+        self._check(self._lib.rplgpu_refine_step_dev(
+            self._h, d_sums, sums_stride, C.byref(spec), d_poses, pose_stride, poses_per_group, G, P, d_poses_out,
+            out_stride, d_step, step_stride, d_result))
+
+    def refine_poses_dev(self, d_nodes: int, n_stride: int, d_n_per_scan: int, B: int, group: int, params: Params,
+                         d_motion: int, d_pose2d: int, spec: "PoseRefine", d_poses: int, P: int, pose_stride: int,
+                         poses_per_group: int, d_field: int, field_stride: int, field_per_group: int, iters: int,
+                         d_poses_out: int, out_stride: int, d_sums: int, sums_stride: int, d_step: int,
+                         step_stride: int, d_scratch: int, d_result: int, d_status: int = 0):
+        """E25: ``iters`` rounds of sums + step queued on the stream; the final list at d_poses_out, the last
+        round's sums, step words and result words."""
+        self._check(self._lib.rplgpu_refine_poses_dev(
+            self._h, d_nodes, n_stride, d_n_per_scan, B, group, C.byref(params), d_motion, d_pose2d, C.byref(spec),
+            d_poses, P, pose_stride, poses_per_group, d_field, field_stride, field_per_group, iters, d_poses_out,
+            out_stride, d_sums, sums_stride, d_step, step_stride, d_scratch, d_result, d_status))
+
+    def refine_poses(self, scans: np.ndarray, lens, params: Params, spec: "PoseRefine", poses: np.ndarray,
+                     field: np.ndarray, iters: int = 1, motion=None, pose2d=None, t0=None):
+        """E25, one group, host buffers: scans (S, n) NODE_DTYPE, poses (P, 4) float32 and a (height, width) int8
+        field -> ``(poses_out (P, 4) float32, sums (P, 32) uint32, step (P, 4) uint32, result (8,) uint32,
+        status)``."""
+        scans = np.ascontiguousarray(scans)
+        if scans.dtype != NODE_DTYPE or scans.ndim != 2:
+            raise TypeError("scans must be a 2-D array of abi.NODE_DTYPE")
+        field = np.ascontiguousarray(field, np.int8)
+        if field.shape != (spec.height, spec.width):
+            raise TypeError("field must be a (height, width) int8 array")
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 4)
+        S, n = scans.shape
+        P = len(poses)
+        lens = np.ascontiguousarray(lens, np.uint32)
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
+        motion, pose2d, t0 = f32(motion), f32(pose2d), f32(t0)
+        out = np.zeros((P, 4), np.float32)
+        sums = np.zeros((P, REFINE_WORDS), np.uint32)
+        step = np.zeros((P, 4), np.uint32)
+        result = np.zeros(8, np.uint32)
+        status = np.zeros(1, np.uint32)
+        ptr = lambda a: 0 if a is None else a.ctypes.data  # noqa: E731
+        self._check(self._lib.rplgpu_refine_poses(
+            self._h, scans.ctypes.data, n, lens.ctypes.data, S, C.byref(params), ptr(motion), ptr(pose2d), ptr(t0),
+            C.byref(spec), poses.ctypes.data, P, field.ctypes.data, iters, out.ctypes.data, sums.ctypes.data,
+            step.ctypes.data, result.ctypes.data, status.ctypes.data))
+        return out, sums, step, result, int(status[0])
+
+    def match_poses_dev(self, d_best: int, match: "ScanMatch", d_pivot: int, d_prior: int, G: int, d_poses_out: int,
+                        out_stride: int):
+        """E25's joint to E13 / E24: the eight result words of every group applied to its base prior (0: the
+        identity at the pivot), one pose (c, s, x, y) per group at d_poses_out + g * out_stride."""
+        self._check(self._lib.rplgpu_match_poses_dev(
+            self._h, d_best, C.byref(match), d_pivot, d_prior, G, d_poses_out, out_stride))
+
+    def compose_poses_dev(self, d_poses: int, pose_stride: int, poses_per_group: int, P: int, d_result: int, q: int,
+                          d_pose2d_in: int, B: int, group: int, d_pose2d_out: int):
+        """E25's joint to E11 / E14: pose q (d_result 0) or word 4 of d_result + 8 g of every group's list composed
+        in front of the group's mount poses, six floats per scan at d_pose2d_out."""
+        self._check(self._lib.rplgpu_compose_poses_dev(
+            self._h, d_poses, pose_stride, poses_per_group, P, d_result, q, d_pose2d_in, B, group, d_pose2d_out))
 
     def resample_poses_dev(self, d_weights: int, weight_stride: int, d_poses: int, pose_stride: int,
                            poses_per_group: int, G: int, P: int, M: int, d_u: int, d_delta: int, n_delta: int,
@@ -2556,3 +2705,62 @@ def pool_field_host(field) -> np.ndarray:
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_pool_field_host")
     return out
+
+
+def pose_refine_check(spec: PoseRefine) -> None:
+    """Host only: validates an E25 spec by the library's own rplgpu_pose_refine_check; raises RplGpuError."""
+    rc = load_library().rplgpu_pose_refine_check(C.byref(spec))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_pose_refine_check")
+
+
+def refine_scratch_words(G: int, P: int) -> int:
+    """Host only: the uint32 words of scratch ``refine_sums_dev`` / ``refine_poses_dev`` take; 0 when refused."""
+    return int(load_library().rplgpu_refine_scratch_words(G, P))
+
+
+def refine_sums_host(x, y, poses, field, spec: PoseRefine):
+    """Host only: E25's sums of one group's points (already in the base frame) by the library's plain C++ twin ->
+    ``(sums (P, 32) uint32, result (8,) uint32, status)``."""
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.ascontiguousarray(y, np.float32)
+    poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 4)
+    field = np.ascontiguousarray(field, np.int8)
+    if field.shape != (spec.height, spec.width) or x.shape != y.shape or x.ndim != 1:
+        raise TypeError("field must be (height, width) int8, x and y equally long 1-D arrays")
+    sums = np.zeros((len(poses), REFINE_WORDS), np.uint32)
+    result = np.zeros(8, np.uint32)
+    status = np.zeros(1, np.uint32)
+    rc = load_library().rplgpu_refine_sums_host(x.ctypes.data, y.ctypes.data, len(x), poses.ctypes.data, len(poses),
+                                                field.ctypes.data, C.byref(spec), sums.ctypes.data,
+                                                result.ctypes.data, status.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_refine_sums_host")
+    return sums, result, int(status[0])
+
+
+def refine_step_host(sums, spec: PoseRefine, pose):
+    """Host only: E25's step of one pose from its 32 words of sums by the library's plain C++ twin ->
+    ``(pose_out (4,) float32, step (4,) uint32)``; step[3] holds the flags."""
+    sums = np.ascontiguousarray(sums, np.uint32)
+    pose = np.ascontiguousarray(pose, np.float32)
+    if sums.shape != (REFINE_WORDS,) or pose.shape != (4,):
+        raise TypeError("sums must be 32 uint32 words, pose 4 floats")
+    out = np.zeros(4, np.float32)
+    step = np.zeros(4, np.uint32)
+    rc = load_library().rplgpu_refine_step_host(sums.ctypes.data, C.byref(spec), pose.ctypes.data, out.ctypes.data,
+                                                step.ctypes.data)
+    if rc < 0:
+        raise RplGpuError(rc, "rplgpu_refine_step_host")
+    return out, step
+
+
+def refine_covariance(sums, spec: PoseRefine):
+    """Host only: (x, y, theta) covariance in metres and radians from a pose's sums, (3, 3) float64, or None when
+    the matrix is singular."""
+    sums = np.ascontiguousarray(sums, np.uint32)
+    if sums.shape != (REFINE_WORDS,) or spec.check() != OK:
+        raise TypeError("sums must be 32 uint32 words and the spec a checked one")
+    cov = np.zeros(9, np.float64)
+    rc = load_library().rplgpu_refine_covariance(sums.ctypes.data, C.byref(spec), cov.ctypes.data)
+    return cov.reshape(3, 3) if rc == OK else None

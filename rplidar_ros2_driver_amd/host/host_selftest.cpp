@@ -289,6 +289,29 @@ int main(int argc, char **argv) {
     }
     std::printf("wide scan match: best %u at (k, j, i) = (%d, %d, %d), %u of %u blocks scored\n", wr.score, wr.k, wr.j,
                 wr.i, wr.listed, wr.blocks);
+    // E25 on the same return and costmap: one point is fewer than min_points, so the one pose is not stepped and
+    // comes back bit for bit; the sums still count the point.
+    rplgpu_pose_refine_t refine;
+    rplgpu_default_pose_refine(&refine);
+    refine.target = 100;
+    std::vector<float> fposes = {1.0f, 0.0f, 0.25f, -0.5f};
+    std::vector<uint32_t> fsums;
+    rplgpu_host::ScanPath::RefineResult fr;
+    uint32_t fstatus = 99;
+    if (!path.refine_poses(one, rplgpu_host::ScanConfig(), prior, nullptr, nullptr, cost_msg, refine, 2, fposes, fr,
+                           &fsums, &fstatus)) {
+      std::fprintf(stderr, "pose refinement failed: %s\n", path.last_error().c_str());
+      return 11;
+    }
+    if (fr.stepped != 0 || fr.too_few != 1 || fr.singular != 0 || fr.clamped != 0 || fr.best_index != 0 ||
+        fr.points != 1 || fsums.size() != 32 || fsums[27] + fsums[28] != 1 || fposes[0] != 1.0f ||
+        fposes[1] != 0.0f || fposes[2] != 0.25f || fposes[3] != -0.5f || fstatus != 0) {
+      std::fprintf(stderr, "pose refinement: wrong answer (%u stepped, %u too few, %u points)\n", fr.stepped,
+                   fr.too_few, fr.points);
+      return 12;
+    }
+    std::printf("pose refinement: %u of 1 poses stepped on %u point(s), %u too few\n", fr.stepped, fr.points,
+                fr.too_few);
     // E14: the three rays of the E11 leg added twice into a count map.  Per call the row of the sensor gets
     // misses 3 3 2 2 1 1 (the whole ray beyond obstacle_max leaves its end cell 4 alone, the cut one counts its
     // end cell 5) and one hit in cell 2; after two calls the default rule (2 observations, 10 %) gives the E11 row.

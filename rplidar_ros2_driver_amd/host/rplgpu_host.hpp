@@ -25,6 +25,7 @@
 //   mat the localisation side's loop (a correlative scan matcher's search window over a likelihood field):
 //         -> rplgpu_host::ScanPath::match_scans(scans, ..., field_msg, window, result)  (E13)
 //         -> rplgpu_host::ScanPath::match_wide(scans, ..., field_msg, window, result)   (E24: up to 256 cells a side)
+//         -> rplgpu_host::ScanPath::refine_poses(scans, ..., field_msg, rule, iters, poses, result)   (E25: below a cell)
 //   map the mapping side's loop (a map that many time steps vote on, each at its matched pose):
 //         -> rplgpu_host::ScanPath::update_map(scans, ..., counts) and fill_map_grid(counts, ..., grid_msg)  (E14)
 //   pf  the localisation side's other loop (a particle filter's sensor update over a list of arbitrary poses):
@@ -507,6 +508,64 @@ class ScanPath {
     result.greatest_bound = work[1];
     result.floor = work[3];
     result.listed = work[4];
+    return true;
+  }
+
+  // ext E25 (include/rplgpu_msg.h): a list of poses of the BASE, four floats (cos, sin, x, y) each in the field's
+  // frame, refined below a cell by `iters` Gauss-Newton steps against the bilinearly interpolated `field_msg` — what
+  // Hector's matcher does, and Cartographer's last stage behind its correlative matcher.  pose2d: every sensor's MOUNT
+  // pose in the base frame (null: identity); target / damping / max_step_cells / max_rot / min_points of `rule` are
+  // used, its grid comes from field_msg.info (origin orientation must be the identity).  poses is stepped in place;
+  // sums (optional): the last round's 32 words per pose, what rplgpu_refine_covariance takes.
+  struct RefineResult {
+    uint32_t stepped = 0, too_few = 0, singular = 0, clamped = 0, best_index = 0, points = 0;
+    uint64_t best_sum = 0;  // the greatest S V of the last round's sums
+  };
+  template <class NodeT, class OccupancyGridT>
+  bool refine_poses(const std::vector<std::vector<NodeT>> &scans, const ScanConfig &cfg, const float *pose2d,
+                    const float *motion, const float *t0, const OccupancyGridT &field_msg,
+                    const rplgpu_pose_refine_t &rule, uint32_t iters, std::vector<float> &poses, RefineResult &result,
+                    std::vector<uint32_t> *sums = nullptr, uint32_t *status = nullptr) {
+    if (scans.empty()) return false;
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    if (poses.empty() || poses.size() % 4 != 0) return fail("refine_poses: poses must hold four floats a pose");
+    rplgpu_pose_refine_t r = rule;
+    r.origin_x = static_cast<float>(field_msg.info.origin.position.x);
+    r.origin_y = static_cast<float>(field_msg.info.origin.position.y);
+    r.resolution = field_msg.info.resolution;
+    r.width = field_msg.info.width;
+    r.height = field_msg.info.height;
+    const size_t n_cells = static_cast<size_t>(r.width) * r.height;
+    if (n_cells == 0 || field_msg.data.size() != n_cells) return fail("refine_poses: data is not width x height");
+    size_t stride = 1;
+    for (const auto &s : scans) stride = s.size() > stride ? s.size() : stride;
+    if (stride > max_n_) return fail("scan larger than the configured capacity");
+    occ_nodes_.assign(scans.size() * stride, rplgpu_node_t{});
+    occ_len_.resize(scans.size());
+    for (size_t b = 0; b < scans.size(); ++b) {
+      if (!scans[b].empty()) std::memcpy(&occ_nodes_[b * stride], scans[b].data(), scans[b].size() * 8);
+      occ_len_[b] = static_cast<uint32_t>(scans[b].size());
+    }
+    occ_prev_.assign(field_msg.data.begin(), field_msg.data.end());
+    const rplgpu_params_t p = cfg.to_params();
+    const uint32_t P = static_cast<uint32_t>(poses.size() / 4);
+    std::vector<float> out(poses.size());
+    if (sums) sums->assign(static_cast<size_t>(RPLGPU_REFINE_WORDS) * P, 0u);
+    uint32_t res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_refine_poses(h_, occ_nodes_.data(), static_cast<uint32_t>(stride), occ_len_.data(),
+                            static_cast<uint32_t>(scans.size()), &p, motion, pose2d, t0, &r, poses.data(), P,
+                            occ_prev_.data(), iters, out.data(), sums ? sums->data() : nullptr, nullptr, res,
+                            status) != RPLGPU_OK)
+      return note_error();
+    poses.swap(out);
+    result.stepped = res[0];
+    result.too_few = res[1];
+    result.singular = res[2];
+    result.clamped = res[3];
+    result.best_index = res[4];
+    result.best_sum = (static_cast<uint64_t>(res[6]) << 32) | res[5];
+    result.points = res[7];
     return true;
   }
 
