@@ -187,6 +187,24 @@ __device__ __forceinline__ void glb_store128(void *p, u32x4 v) {
   asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
+// A device-scope fetch-and-add by ONE thread whose round trip to L2 is to run under the instructions behind
+// it: atomic_issue_* only issues it, atomic_wait() makes the result usable.  Left to the compiler an
+// atomicAdd goes through its atomic optimiser, which reads the result back with a v_readfirstlane right
+// behind the instruction, i.e. waits for the whole round trip at once (as for the queue atomic in
+// voxel_block_pass).  The compiler does not count this instruction: its own vmcnt waits only get longer by
+// it, never shorter (an older load / atomic returns first).  Between the two calls nothing may touch the
+// result: it is passed by reference and bound to one register by both asm statements.
+__device__ __forceinline__ void atomic_issue_u32(uint32_t &r, uint32_t *p, uint32_t v) {
+  asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=&v"(r) : "v"(p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void atomic_issue_u64(unsigned long long &r, unsigned long long *p, unsigned long long v) {
+  asm volatile("global_atomic_add_x2 %0, %1, %2, off sc0" : "=&v"(r) : "v"(p), "v"(v) : "memory");
+}
+template <class T>
+__device__ __forceinline__ void atomic_wait(T &r) {
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(r)::"memory");
+}
+
 // What E5 needs of a sample when it runs inside the streaming pass (see voxel_stream, HASROR)
 struct RorPre {
   f2 xy;    // E2 point in the sensor frame (in front of any E6 / E8 transform)
@@ -687,9 +705,19 @@ __device__ __forceinline__ uint32_t voxel_reduce(VoxelLds &L, const KParams &p,
     pc.lap(6);
     // position of every cell's first record (16-bit entries; the row arrays are free again)
     uint16_t *heads = reinterpret_cast<uint16_t *>(L.rows);
+    // the only band of this scan: its cells are reserved as soon as their number is known; the round trip
+    // of the atomic runs under the head stores, and their barrier publishes the reservation
+    const bool reserves = mode == kEmitArenaFirst && threadIdx.x == 0;
+    unsigned long long reserved = 0ull;
+    if (reserves) atomic_issue_u64(reserved, arena.cursor, (unsigned long long)ncell);
 #pragma unroll
     for (int k = 0; k < (int)kRecPerThread; ++k)
       if ((headbits >> k) & 1u) heads[cell++] = (uint16_t)(r_lo + k);
+    if (reserves) {
+      atomic_wait(reserved);
+      L.tmp[28] = (uint32_t)reserved;
+      L.tmp[29] = (uint32_t)(reserved >> 32);
+    }
     __syncthreads();
     // one cell per thread, coalesced 16-byte output rows.  All sums are exact in fp64
     // (integers below 2^53); the quotient by the count uses the host-built correctly
@@ -698,13 +726,7 @@ __device__ __forceinline__ uint32_t voxel_reduce(VoxelLds &L, const KParams &p,
     const double inv_scale = 1.0 / p.vox_scale;  // exact power of two
     const double dL = (double)p.vox_L, dbias = (double)vbias;
     uint32_t nemit = min(ncell, out_stride > out_base ? out_stride - out_base : 0u);
-    if (mode == kEmitArenaFirst) {  // the only band of this scan: reserve its cells now
-      if (threadIdx.x == 0) {
-        const unsigned long long at = atomicAdd(arena.cursor, (unsigned long long)ncell);
-        L.tmp[28] = (uint32_t)at;
-        L.tmp[29] = (uint32_t)(at >> 32);
-      }
-      __syncthreads();
+    if (mode == kEmitArenaFirst) {  // (reserved above)
       const unsigned long long at = ((unsigned long long)L.tmp[29] << 32) | L.tmp[28];
       out = arena.base + at;
       if (cell_keys) cell_keys = p.cell_keys + at;
@@ -779,6 +801,38 @@ __device__ __forceinline__ uint32_t voxel_reduce(VoxelLds &L, const KParams &p,
   return 0u;
 }
 
+// Byte offset of a lane's sample pair in block `blk` of its scan (see voxel_stream: HASROR blocks overlap
+// by a pair either side, and lane 0 of block 0 reads past the resource — `oob_off` — for its zeros)
+template <bool HASROR>
+__device__ __forceinline__ uint32_t voxel_blk_off(uint32_t blk, uint32_t oob_off, uint32_t lane) {
+  const uint32_t o = blk * (HASROR ? 992u : 1024u) + (HASROR ? lane * 16u - 16u : lane * 16u);
+  return (HASROR && blk == 0u && lane == 0u) ? oob_off : o;
+}
+// (the lane index behind an optimisation barrier: what the once-per-scan code derives from it is computed
+// there, not hoisted out of the persistent item loop into registers that stay live through phase R:
+// this kernel's spills come from such hoisting)
+__device__ __forceinline__ uint32_t lane_id_here() {
+  uint32_t lane = lane_id();
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+// The wave's first AHEAD raw pairs, loaded SPECULATIVELY: `slot_rsrc` covers the scan's whole slot (n_stride
+// nodes, known without a load), so these loads are issued before the scan's length has arrived and travel
+// with the load of the length instead of behind it.  voxel_stream zeroes what lies at or beyond the
+// length once it is known — exactly what the length-bounded resource returns there.  No byte outside
+// the caller's slot is read, and a full-length scan reads what it always read.
+template <bool HASROR, int AHEAD>
+__device__ __forceinline__ void voxel_prologue_loads(const __amdgpu_buffer_rsrc_t slot_rsrc, uint32_t blk0,
+                                                     uint32_t oob_off, uint4 (&pro)[AHEAD]) {
+  const uint32_t lane = lane_id_here();
+#pragma unroll
+  for (int j = 0; j < AHEAD; ++j) {
+    const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(
+        slot_rsrc, (int)voxel_blk_off<HASROR>(blk0 + (uint32_t)(j * kVW), oob_off, lane), 0, RPL_RAW_AUX);
+    pro[j] = make_uint4(t.x, t.y, t.z, t.w);
+  }
+}
+
 // ------------------------------------------------------------------------------
 // Phase S over the blocks blk0, blk0 + kVW, ... < blk_end of ONE scan (`scan_rsrc`: a bounds-checked
 // buffer resource over the bytes this caller may read; beyond it a load returns zeros = dropped
@@ -804,14 +858,15 @@ template <bool FAST_DIV, bool SAFE, bool SPLIT, bool DBG, bool HASQ, bool HASMAS
           bool HASROR = false>
 __device__ __forceinline__ void voxel_stream(QueueSink &sink, const KParams &p,
                                              const float2 *__restrict__ cs,
-                                             const __amdgpu_buffer_rsrc_t scan_rsrc, uint32_t blk0,
+                                             const __amdgpu_buffer_rsrc_t scan_rsrc, uint32_t n,
+                                             const uint4 (&pro)[AHEAD], uint32_t blk0,
                                              uint32_t blk_end, const uint32_t *__restrict__ ror_bits,
                                              uint32_t mask_stride, const ScanXf &xf, uint32_t q_min16,
                                              uint32_t ibfe_off, uint32_t ibfe_w, uint32_t &flags,
                                              unsigned long long *dbg_slot, RorSide *rs = nullptr,
                                              uint32_t oob_off = 0u) {
   static_assert(!HASROR || !HASMASK, "the ROR instance: no mask word");
-  constexpr uint32_t kBlkBytes = HASROR ? 992u : 1024u, kBlkSamples = HASROR ? 124u : 128u;
+  constexpr uint32_t kBlkSamples = HASROR ? 124u : 128u;  // (a block's bytes: voxel_blk_off)
   // raw pairs run AHEAD blocks in front of the block being aggregated, the table entries GA blocks (their
   // addresses come out of the raw pair: GA < AHEAD); both live in register rings of N slots, the loop is
   // unrolled N times so that the rings cost no moves
@@ -823,18 +878,22 @@ __device__ __forceinline__ void voxel_stream(QueueSink &sink, const KParams &p,
     return make_uint4(t.x, t.y, t.z, t.w);
   };
   // (HASROR: lane 0 of block 0 would read the 16 bytes in front of the scan: it reads past the
-  // resource instead — `oob_off`, a multiple of 16 >= the scan's bytes — and gets zeros)
-  const uint32_t lane_off = HASROR ? lane_id() * 16u - 16u : lane_id() * 16u;
-  const bool first_lane = HASROR && lane_id() == 0u;
-  auto blk_off = [&](uint32_t blk) -> uint32_t {
-    const uint32_t o = blk * kBlkBytes + lane_off;
-    return (HASROR && blk == 0u) ? (first_lane ? oob_off : o) : o;
-  };
+  // resource instead — `oob_off`, a multiple of 16 >= the slot's bytes — and gets zeros)
+  auto blk_off = [&](uint32_t blk) -> uint32_t { return voxel_blk_off<HASROR>(blk, oob_off, lane_id()); };
   const bool owned = !HASROR || (lane_id() - 1u) < 62u;
   uint4 w[N];
   float2 cA[N], cB[N];
+  // the first AHEAD pairs came through the slot's resource (voxel_prologue_loads): a node at or beyond
+  // the scan's length reads as zero, as it does through `scan_rsrc` (lane 0 of HASROR's block 0: the
+  // index wraps, both nodes are zero, which is what it loaded)
+  const uint32_t lane_pro = lane_id_here();
 #pragma unroll
-  for (int j = 0; j < AHEAD; ++j) w[j] = load_pair(blk_off(blk0 + (uint32_t)(j * kVW)));
+  for (int j = 0; j < AHEAD; ++j) {
+    const uint32_t blk = blk0 + (uint32_t)(j * kVW);
+    const uint32_t i0 = HASROR ? blk * kBlkSamples + lane_pro * 2u - 2u : blk * 128u + lane_pro * 2u;
+    const bool in0 = i0 < n, in1 = i0 + 1u < n;
+    w[j] = make_uint4(in0 ? pro[j].x : 0u, in0 ? pro[j].y : 0u, in1 ? pro[j].z : 0u, in1 ? pro[j].w : 0u);
+  }
   auto gat = [&](uint32_t word) -> float2 { return cs[word & 0xFFFFu]; };
 #pragma unroll
   for (int j = 0; j < GA; ++j) {
@@ -1121,7 +1180,8 @@ __device__ __forceinline__ bool ror_resolve(QueueSink &S, RorSide &R, const KPar
 template <bool FAST_DIV, bool SAFE, bool SPLIT, bool DBG, int AHEAD, int RORM = 0>
 __device__ __forceinline__ void voxel_stream_dispatch(QueueSink &sink, const KParams &p,
                                                       const float2 *__restrict__ cs,
-                                                      const __amdgpu_buffer_rsrc_t rsrc, uint32_t blk0,
+                                                      const __amdgpu_buffer_rsrc_t rsrc, uint32_t n,
+                                                      const uint4 (&pro)[AHEAD], uint32_t blk0,
                                                       uint32_t blk_end, const ScanSide &sd,
                                                       uint32_t mask_stride, bool use_xf,
                                                       uint32_t q_min16, uint32_t ibfe_off,
@@ -1131,17 +1191,17 @@ __device__ __forceinline__ void voxel_stream_dispatch(QueueSink &sink, const KPa
   if constexpr (RORM == 1) {  // E5 inside the pass: transform (quality test always on) / quality filter / neither
     if (use_xf)
       voxel_stream<FAST_DIV, SAFE, SPLIT, false, true, false, true, AHEAD, true>(
-          sink, p, cs, rsrc, blk0, blk_end, nullptr, 0u, sd.xf, q_min16, ibfe_off, ibfe_w, flags, nullptr, rs, oob_off);
+          sink, p, cs, rsrc, n, pro, blk0, blk_end, nullptr, 0u, sd.xf, q_min16, ibfe_off, ibfe_w, flags, nullptr, rs, oob_off);
     else if (q_min16)
       voxel_stream<FAST_DIV, SAFE, SPLIT, false, true, false, false, AHEAD, true>(
-          sink, p, cs, rsrc, blk0, blk_end, nullptr, 0u, sd.xf, q_min16, ibfe_off, ibfe_w, flags, nullptr, rs, oob_off);
+          sink, p, cs, rsrc, n, pro, blk0, blk_end, nullptr, 0u, sd.xf, q_min16, ibfe_off, ibfe_w, flags, nullptr, rs, oob_off);
     else
       voxel_stream<FAST_DIV, SAFE, SPLIT, false, false, false, false, AHEAD, true>(
-          sink, p, cs, rsrc, blk0, blk_end, nullptr, 0u, sd.xf, q_min16, ibfe_off, ibfe_w, flags, nullptr, rs, oob_off);
+          sink, p, cs, rsrc, n, pro, blk0, blk_end, nullptr, 0u, sd.xf, q_min16, ibfe_off, ibfe_w, flags, nullptr, rs, oob_off);
     return;
   }
 #define RPL_VS(HQ, HM, XFB)                                                                         \
-  voxel_stream<FAST_DIV, SAFE, SPLIT, DBG, HQ, HM, XFB, AHEAD>(sink, p, cs, rsrc, blk0, blk_end, \
+  voxel_stream<FAST_DIV, SAFE, SPLIT, DBG, HQ, HM, XFB, AHEAD>(sink, p, cs, rsrc, n, pro, blk0, blk_end, \
                                                                      sd.ror_bits, mask_stride, sd.xf, \
                                                                      q_min16, ibfe_off, ibfe_w, flags, \
                                                                      dbg_slot)
@@ -1188,14 +1248,21 @@ __device__ __forceinline__ void voxel_work_loop(VoxelLds &L, const KParams &p, c
   int emit_mode = arena.base ? kEmitArenaFirst : kEmitLegacy;
   unsigned long long arena_at = 0ull;  // first point of this scan in the arena
 
-  if (threadIdx.x < 16) L.misc[threadIdx.x] = 0u;
+  // Item setup and the pop of the item's first band in one step behind one barrier: that band is always
+  // the whole key range (0, 0xFFFFFFFE) at stack pointer 0, so L.misc is written as the pop leaves it
+  // (words 4 and 8: the empty minima; the stack, word 3, is empty) and the band stack itself is not
+  // touched — whoever pushes bands (bisect, the histogram bands, the second go of kEmitCountOnly)
+  // writes the entries it pushes.
+  {
+    uint32_t t = threadIdx.x;
+    asm volatile("" : "+v"(t));  // (the word's value is made here, not kept in a register from item to item)
+    if (t < 16) L.misc[t] = 0u - ((0x0110u >> t) & 1u);
+  }
   if (threadIdx.x == 0) {
-    L.band_lo[0] = 0u;
-    L.band_hi[0] = 0xFFFFFFFEu;
-    L.misc[3] = 1u;  // stack pointer
     L.tmp[28] = 0u;  // arena reservation of this scan (stays 0 for a scan without cells)
     L.tmp[29] = 0u;
   }
+  for (uint32_t t = threadIdx.x; t < kRowCap; t += kVB) L.rows[t] = 0u;  // (see the pop below)
   __syncthreads();
 
   uint32_t flags = 0;
@@ -1207,24 +1274,28 @@ __device__ __forceinline__ void voxel_work_loop(VoxelLds &L, const KParams &p, c
   bool from_store = false;  // block-uniform: the scan's records are (all) in the record store
   uint32_t n_all = 0;       // records of the whole scan (valid once the scan was streamed)
   while (true) {
-    // ---- pop a key band -----------------------------------------------------------
-    const uint32_t sp = L.misc[3];
-    if (sp == 0) break;
-    const uint32_t klo = L.band_lo[sp - 1], khi = L.band_hi[sp - 1];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      L.misc[0] = 0u;
-      L.misc[2] = 0u;
-      L.misc[3] = sp - 1;
-      L.misc[4] = 0xFFFFFFFFu;
-      L.misc[5] = 0u;
-      L.misc[8] = 0xFFFFFFFFu;  // occupied key range of the band (known after a failed selection)
-      L.misc[9] = 0u;
+    // ---- pop a key band (the first one came with the item setup) ----------------------
+    uint32_t klo = 0u, khi = 0xFFFFFFFEu;
+    if (!first) {  // block-uniform
+      const uint32_t sp = L.misc[3];
+      if (sp == 0) break;
+      klo = L.band_lo[sp - 1];
+      khi = L.band_hi[sp - 1];
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        L.misc[0] = 0u;
+        L.misc[2] = 0u;
+        L.misc[3] = sp - 1;
+        L.misc[4] = 0xFFFFFFFFu;
+        L.misc[5] = 0u;
+        L.misc[8] = 0xFFFFFFFFu;  // occupied key range of the band (known after a failed selection)
+        L.misc[9] = 0u;
+      }
+      // the row histogram of this band is filled while the records are loaded in phase R (rows
+      // are addressed modulo kRowCap, so the first row need not be known yet)
+      for (uint32_t t = threadIdx.x; t < kRowCap; t += kVB) L.rows[t] = 0u;
+      __syncthreads();
     }
-    // the row histogram of this band is filled while the records are loaded in phase R (rows
-    // are addressed modulo kRowCap, so the first row need not be known yet)
-    for (uint32_t t = threadIdx.x; t < kRowCap; t += kVB) L.rows[t] = 0u;
-    __syncthreads();
 
     if (first) {
       abandoned = first_band(b, bl, flags);
@@ -1556,24 +1627,35 @@ __device__ __forceinline__ void voxel_work_loop(VoxelLds &L, const KParams &p, c
 
   if (flags) atomicOr(&L.misc[1], flags);
   __syncthreads();
-  if (threadIdx.x == 0 && !abandoned) {
-    const uint32_t total = L.misc[7];
-    if (arena.base) {
-      const unsigned long long room = arena_at >= arena.capacity ? 0ull : arena.capacity - arena_at;
-      const uint32_t kept = (uint32_t)min((unsigned long long)total, room);
-      arena.scan_start[b] = arena_at;
-      n_points[b] = kept;
-      if (status) status[b] = L.misc[1] | (kept < total ? RPLGPU_SCAN_OUT_TRUNCATED : 0u);
-    } else {
-      n_points[b] = min(total, out_stride);
-      if (status) status[b] = L.misc[1] | ((total > out_stride) ? RPLGPU_SCAN_OUT_TRUNCATED : 0u);
+  const bool draw = RORM == 2 || B > gridDim.x;  // (else a workgroup per item — single scans, small batches: no queue)
+  if (threadIdx.x == 0) {
+    // the draw is issued in front of the item's result words: its round trip to L2 runs while they are stored
+    uint32_t drawn = 0u;
+    if (draw) atomic_issue_u32(drawn, &T.work_ctr[0], 1u);  // (block-uniform)
+    if (!abandoned) {
+      const uint32_t total = L.misc[7];
+      if (arena.base) {
+        const unsigned long long room = arena_at >= arena.capacity ? 0ull : arena.capacity - arena_at;
+        const uint32_t kept = (uint32_t)min((unsigned long long)total, room);
+        arena.scan_start[b] = arena_at;
+        n_points[b] = kept;
+        if (status) status[b] = L.misc[1] | (kept < total ? RPLGPU_SCAN_OUT_TRUNCATED : 0u);
+      } else {
+        n_points[b] = min(total, out_stride);
+        if (status) status[b] = L.misc[1] | ((total > out_stride) ? RPLGPU_SCAN_OUT_TRUNCATED : 0u);
+      }
+    }
+    if (draw) {
+      atomic_wait(drawn);
+      L.tmp[31] = gridDim.x + drawn;
     }
   }
-  if (RORM != 2 && B <= gridDim.x) return;  // a workgroup per item (single scans, small batches): no queue
-  if (threadIdx.x == 0) L.tmp[31] = gridDim.x + atomicAdd(&T.work_ctr[0], 1u);
+  if (!draw) return;
   __syncthreads();  // LDS is reused by the next scan
+  // (no barrier behind this read: L.tmp[31] is not written again before the end of the next item, which
+  // lies behind that item's barriers, and what the next item's setup overwrites — L.misc, L.rows,
+  // L.tmp[28..29] — nobody reads any more: thread 0 read L.misc in front of the barrier above)
   bl = L.tmp[31];
-  __syncthreads();
   }
 }
 
@@ -1610,24 +1692,33 @@ __global__ __launch_bounds__(kVB) __attribute__((amdgpu_waves_per_eu(kVB * kVWG 
     QueueSink sink{L, G};
     const uint32_t s_lo = b * group, s_hi = min(n_scans, s_lo + group);
     for (uint32_t sc = s_lo; sc < s_hi; ++sc) {
+      // The length is loaded first and used last: the wave's first raw pairs go out behind it through a
+      // resource over the scan's slot, whose size needs no load (voxel_prologue_loads), so the length,
+      // the scan_side words and those pairs are in flight together.
+      const uint32_t n_given = n_per_scan[sc];
+      const uint2 *scan = nodes + (size_t)sc * n_stride;
+      const uint32_t slot_n = min(n_stride, kMaxN);
+      const __amdgpu_buffer_rsrc_t slot_rsrc =
+          __builtin_amdgcn_make_buffer_rsrc((void *)scan, 0, (int)(slot_n * 8u), 0x00020000);
+      const uint32_t blk0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_id());
+      const uint32_t oob_off = (slot_n * 8u + 15u) & ~15u;  // (past the slot, hence past the scan)
+      uint4 pro[RPL_VOXEL_AHEAD];
+      voxel_prologue_loads<RORM == 1, RPL_VOXEL_AHEAD>(slot_rsrc, blk0, oob_off, pro);
+      const ScanSide sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
       // (readfirstlane: the value is wave-uniform, and must live in scalar registers for the
       // buffer resource below — a min3 in vector registers makes every load a waterfall loop)
-      const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane(
-          (int)min(n_per_scan[sc], min(n_stride, kMaxN)));  // never past the slot
-      const uint2 *scan = nodes + (size_t)sc * n_stride;
+      const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(n_given, slot_n));  // never past the slot
       // Bounds-checked buffer resource over this scan's n*8 bytes: a node beyond the scan reads
       // as zero, i.e. dist 0, which the keep test drops.  Every lane always issues the load, so
       // the compiler's vmcnt bookkeeping is exact.
       const __amdgpu_buffer_rsrc_t scan_rsrc =
           __builtin_amdgcn_make_buffer_rsrc((void *)scan, 0, (int)(n * 8u), 0x00020000);
-      const ScanSide sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
-      const uint32_t blk0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_id());
       if constexpr (RORM == 1) {
         if (threadIdx.x == 0) { Rs.n_todo = 0u; Rs.n_todo2 = 0u; }
         __syncthreads();
         voxel_stream_dispatch<FAST_DIV, SAFE, SPLIT, false, RPL_VOXEL_AHEAD, 1>(
-            sink, p, cs, scan_rsrc, blk0, (n + 123u) / 124u, sd, 0u, use_xf, q_min16, ibfe_off, ibfe_w, flags,
-            nullptr, &Rs, (n * 8u + 15u) & ~15u);
+            sink, p, cs, scan_rsrc, n, pro, blk0, (n + 123u) / 124u, sd, 0u, use_xf, q_min16, ibfe_off, ibfe_w,
+            flags, nullptr, &Rs, oob_off);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // (the pass's hand-written record stores)
         __syncthreads();
         bool clutter;
@@ -1639,7 +1730,7 @@ __global__ __launch_bounds__(kVB) __attribute__((amdgpu_waves_per_eu(kVB * kVWG 
         __syncthreads();           // (the lists are reused by the group's next scan)
       } else {
         voxel_stream_dispatch<FAST_DIV, SAFE, SPLIT, DBG, RPL_VOXEL_AHEAD, RORM>(
-            sink, p, cs, scan_rsrc, blk0, (n + 127u) >> 7, sd, mask_stride, use_xf, q_min16, ibfe_off,
+            sink, p, cs, scan_rsrc, n, pro, blk0, (n + 127u) >> 7, sd, mask_stride, use_xf, q_min16, ibfe_off,
             ibfe_w, flags, (DBG && p.dbg) ? p.dbg + 16 * b : nullptr);
       }
     }
