@@ -6,11 +6,11 @@
 // field load, the second takes off only what the skipped samples added (usually a few percent of the points).  The
 // weights are unsigned and no final value is negative, so the subtraction is exact in any order.
 //   k_agree_prepare  zeroes weights, result, counts, mask and agree words (the smallest count starts at ~0);
-//   k_agree_count    E15's grid and walk (one workgroup per scan x tile of 1024 poses x slice of passes, a thread owns
-//                    one pose and walks the LDS point list by broadcast): per point acc += f, one ballot of
-//                    f >= agree_lo per wave popcounted into an LDS counter of the list entry; at the end of a pass
-//                    the non-zero counters leave with one no-return atomic add each; the first tile's workgroups
-//                    store the finite bits and add result word 4;
+//   k_agree_count    E15's grid and walk (one workgroup per scan x tile of 1024 poses x slice of passes, the front end
+//                    of rpl_front.hpp, a thread owns one pose and walks the LDS point list by broadcast): per point
+//                    acc += f, one ballot of f >= agree_lo per wave popcounted into an LDS counter of the list entry;
+//                    at the end of a pass the non-zero counters leave with one no-return atomic add each; the first
+//                    tile's workgroups store the finite bits and add result word 4;
 //   k_agree_decide   a thread per sample: the rule bit from count and P, a ballot makes the mask words (finite AND
 //                    kept), wave reductions and integer atomics make F, K, the largest, smallest and summed count;
 //   k_agree_flag     a thread per group: agree words 2, 3 and 5;
@@ -22,53 +22,12 @@
 #include <algorithm>
 
 #include "rpl_agree.hpp"
+#include "rpl_front.hpp"
 
 namespace rpl {
 namespace {
 
-static_assert(kAgList * sizeof(float2) == 16384, "the point list is 16 KiB");
-
-// the scan's part of both walking kernels, as k_pose_score sets it up
-struct AgreeScan {
-  ScanSide sd;
-  const float2 *cs;
-  uint32_t q_min16;
-  __amdgpu_buffer_rsrc_t rsrc;
-};
-__device__ __forceinline__ AgreeScan agree_scan(const uint2 *__restrict__ nodes, uint32_t n_stride, uint32_t sc,
-                                                uint32_t n, const KParams &p, const Tables &T,
-                                                const uint32_t *__restrict__ keepmask, uint32_t mask_stride,
-                                                const float *__restrict__ motion, const float *__restrict__ pose2d) {
-  AgreeScan a;
-  a.sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
-  a.cs = p.inverted ? T.cs_inv : T.cs;
-  a.q_min16 = p.clip_enable ? (min(p.q_min, 256u) << 16) : 0u;
-  const uint2 *scan = nodes + (size_t)sc * n_stride;
-  // bounds-checked over the scan's n * 8 bytes: a node beyond it reads as zero (and i < n drops it)
-  a.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)scan, 0, (int)(n * 8u), 0x00020000);
-  return a;
-}
-
-// the pose of a thread: entry q0 of the tile, copy `slice` of `slices` (k_pose_score's layout, the same formula)
-struct AgreeLane {
-  uint32_t per, slices, slice, q;
-  bool own;
-  float c, s, tx, ty;
-};
-__device__ __forceinline__ AgreeLane agree_lane(uint32_t tile, uint32_t P, const float *__restrict__ list) {
-  AgreeLane l;
-  l.per = min((P + 63u) & ~63u, (uint32_t)kAgTile);  // threads of one copy of the list
-  l.slices = P <= (uint32_t)kAgTile ? (uint32_t)kAgTile / l.per : 1u;
-  l.slice = threadIdx.x / l.per;  // (wave-uniform: per is whole waves)
-  l.q = tile * kAgTile + (threadIdx.x - l.slice * l.per);
-  l.own = l.slice < l.slices && l.q < P;
-  l.c = l.s = l.tx = l.ty = 0.0f;
-  if (l.own) {  // a thread without a pose loads nothing, adds nothing and agrees with nothing
-    const ag_f32x4 v = *reinterpret_cast<const ag_f32x4 *>(list + 4u * (size_t)l.q);
-    l.c = v.x; l.s = v.y; l.tx = v.z; l.ty = v.w;
-  }
-  return l;
-}
+static_assert(kFrontList * sizeof(float2) == 16384, "the point list is 16 KiB");
 
 constexpr uint32_t kPrepThreads = 256;
 constexpr uint32_t kPrepBlocks = 2048;
@@ -110,23 +69,23 @@ __global__ __launch_bounds__(kBlock) void k_agree_count(
     unsigned long long weight_stride, uint32_t *__restrict__ result, uint32_t *__restrict__ status,
     uint32_t *__restrict__ counts, unsigned long long count_stride, uint32_t *__restrict__ mask,
     unsigned long long mask_words_stride) {
-  __shared__ ag_f32x4 s_pts[kAgList / 2u];  // two points (x0, y0, x1, y1) per element
-  __shared__ uint32_t s_idx[kAgList];       // the sample index of every list entry
-  __shared__ uint32_t s_agree[kAgList];     // the poses of this tile that agree with it
+  __shared__ f32x4 s_pts[kFrontList / 2u];  // two points (x0, y0, x1, y1) per element
+  __shared__ uint32_t s_idx[kFrontList];       // the sample index of every list entry
+  __shared__ uint32_t s_agree[kFrontList];     // the poses of this tile that agree with it
   __shared__ uint32_t s_sum[kBlock];
   __shared__ uint32_t s_cnt[2];  // the list's length, by the pass's parity: a reset never meets a late reader
   const uint32_t sc = blockIdx.x;
   const uint32_t tile = blockIdx.y;
   const uint32_t g = sc / group;
   const uint32_t n_in = n_per_scan[sc];
-  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(n_in, min(n_stride, kMaxN)));
+  const uint32_t n = scan_len(n_in, n_stride);
   const bool first_of_scan = tile == 0u && blockIdx.z == 0u;
   if (threadIdx.x == 0 && status && first_of_scan && n_in > n) atomicOr(&status[g], RPLGPU_SCAN_OUT_TRUNCATED);
-  if (blockIdx.z * kAgList >= n) return;  // (block-uniform)
-  const AgreeScan a = agree_scan(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
+  if (blockIdx.z * kFrontList >= n) return;  // (block-uniform)
+  const ScanFront f = scan_front(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
   const OccK ck{k.origin_x, k.origin_y, k.resolution, k.width, k.height, 0.0f, 0.0f, 0.0f};  // (the cell rule's part)
   const int8_t *fld = field + (size_t)(field_per_group ? g : 0u) * field_stride;
-  const AgreeLane l = agree_lane(tile, P, poses + (size_t)(poses_per_group ? g : 0u) * pose_stride);
+  const PoseLane l = pose_lane(tile, P, poses + (size_t)(poses_per_group ? g : 0u) * pose_stride);
   uint32_t *cnt_row = counts + (size_t)sc * count_stride;
   uint32_t *fin_row = tile == 0u ? mask + (size_t)sc * mask_words_stride : nullptr;
   uint32_t acc = 0u;
@@ -137,22 +96,22 @@ __global__ __launch_bounds__(kBlock) void k_agree_count(
   // a thread zeroes and flushes the same two counters, t and t + kBlock: no barrier between a flush and the reset
   s_agree[threadIdx.x] = 0u;
   s_agree[threadIdx.x + kBlock] = 0u;
-  for (uint32_t base = blockIdx.z * kAgList; base < n; base += gridDim.z * kAgList) {
+  for (uint32_t base = blockIdx.z * kFrontList; base < n; base += gridDim.z * kFrontList) {
     uint32_t *cnt_at = &s_cnt[pass++ & 1u];
     if (threadIdx.x == 0) *cnt_at = 0u;
     __syncthreads();  // (also: the last pass's readers are done with the list, its flush with the indices)
-    agree_front_pass<FAST>(a.rsrc, n, base, p, a.q_min16, a.cs, a.sd, cnt_at, pts, s_idx, fin_row, nullptr, &finite);
+    front_point_pass<FAST>(f, base, p, cnt_at, pts, s_idx, fin_row, nullptr, &finite);
     __syncthreads();
-    const uint32_t cnt = *cnt_at;  // <= kAgList
+    const uint32_t cnt = *cnt_at;  // <= kFrontList
     if (l.slice < l.slices) {      // (wave-uniform: the ballots below see whole waves)
-      // copy `slice` walks the point pairs slice, slice + slices, ...: pair e holds points 2e and 2e + 1 < kAgList
+      // copy `slice` walks the point pairs slice, slice + slices, ...: pair e holds points 2e and 2e + 1 < kFrontList
       // (not unrolled: the ballots are convergent operations)
       for (uint32_t e = l.slice; 2u * e < cnt; e += l.slices) {
-        const ag_f32x4 v = s_pts[e];
+        const f32x4 v = s_pts[e];
         uint32_t f0 = 0u, f1 = 0u;
         if (l.own) {
-          f0 = agree_look(v.x, v.y, l.c, l.s, l.tx, l.ty, ck, fld, &cell_range);
-          if (2u * e + 1u < cnt) f1 = agree_look(v.z, v.w, l.c, l.s, l.tx, l.ty, ck, fld, &cell_range);
+          f0 = pose_look(v.x, v.y, l.c, l.s, l.tx, l.ty, ck, fld, &cell_range);
+          if (2u * e + 1u < cnt) f1 = pose_look(v.z, v.w, l.c, l.s, l.tx, l.ty, ck, fld, &cell_range);
         }
         acc += f0 + f1;
         // a lane without a pose has f = 0 < agree_lo; so has the missing second point of the last pair
@@ -165,9 +124,9 @@ __global__ __launch_bounds__(kBlock) void k_agree_count(
       }
     }
     __syncthreads();
-    // the pass's counters leave: entry j < cnt <= kAgList has sample s_idx[j] < n <= n_stride <= count_stride
+    // the pass's counters leave: entry j < cnt <= kFrontList has sample s_idx[j] < n <= n_stride <= count_stride
 #pragma unroll
-    for (uint32_t j = threadIdx.x; j < kAgList; j += kBlock) {
+    for (uint32_t j = threadIdx.x; j < kFrontList; j += kBlock) {
       const uint32_t c = s_agree[j];
       if (j < cnt && c) {
         atomicAdd(&cnt_row[s_idx[j]], c);
@@ -184,10 +143,10 @@ __global__ __launch_bounds__(kBlock) void k_agree_count(
   __syncthreads();
   s_sum[threadIdx.x] = acc;  // copy `slice` at [slice * per, slice * per + per); 0 where a thread owns no pose
   __syncthreads();
-  if (threadIdx.x < l.per && tile * kAgTile + threadIdx.x < P) {
+  if (threadIdx.x < l.per && tile * kPoseTile + threadIdx.x < P) {
     uint32_t sum = 0u;
     for (uint32_t s = 0; s < l.slices; ++s) sum += s_sum[s * l.per + threadIdx.x];  // slices * per <= kBlock
-    if (sum) atomicAdd(&weights[(size_t)g * weight_stride + tile * kAgTile + threadIdx.x], sum);
+    if (sum) atomicAdd(&weights[(size_t)g * weight_stride + tile * kPoseTile + threadIdx.x], sum);
   }
 }
 
@@ -257,50 +216,49 @@ __global__ __launch_bounds__(kBlock) void k_agree_apply(
     unsigned long long field_stride, uint32_t field_per_group, uint32_t *__restrict__ weights,
     unsigned long long weight_stride, const uint32_t *__restrict__ mask, unsigned long long mask_words_stride,
     const uint32_t *__restrict__ agree) {
-  __shared__ ag_f32x4 s_pts[kAgList / 2u];
+  __shared__ f32x4 s_pts[kFrontList / 2u];
   __shared__ uint32_t s_sum[kBlock];
   __shared__ uint32_t s_cnt[2];
   const uint32_t sc = blockIdx.x;
   const uint32_t tile = blockIdx.y;
   const uint32_t g = sc / group;
   if (agree[8u * (size_t)g + 2u]) return;  // (block-uniform) the group fell back: every finite sample stays in
-  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(n_per_scan[sc], min(n_stride, kMaxN)));
-  if (blockIdx.z * kAgList >= n) return;  // (block-uniform)
-  const AgreeScan a = agree_scan(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
+  const uint32_t n = scan_len(n_per_scan[sc], n_stride);
+  if (blockIdx.z * kFrontList >= n) return;  // (block-uniform)
+  const ScanFront f = scan_front(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
   const OccK ck{k.origin_x, k.origin_y, k.resolution, k.width, k.height, 0.0f, 0.0f, 0.0f};
   const int8_t *fld = field + (size_t)(field_per_group ? g : 0u) * field_stride;
-  const AgreeLane l = agree_lane(tile, P, poses + (size_t)(poses_per_group ? g : 0u) * pose_stride);
+  const PoseLane l = pose_lane(tile, P, poses + (size_t)(poses_per_group ? g : 0u) * pose_stride);
   const uint32_t *rule_row = mask + (size_t)sc * mask_words_stride;
   uint32_t acc = 0u;
   uint32_t finite = 0u;
   bool cell_range = false;  // (the count pass has reported it)
   uint32_t pass = 0u;
   float2 *pts = reinterpret_cast<float2 *>(s_pts);
-  for (uint32_t base = blockIdx.z * kAgList; base < n; base += gridDim.z * kAgList) {
+  for (uint32_t base = blockIdx.z * kFrontList; base < n; base += gridDim.z * kFrontList) {
     uint32_t *cnt_at = &s_cnt[pass++ & 1u];
     if (threadIdx.x == 0) *cnt_at = 0u;
     __syncthreads();
-    agree_front_pass<FAST>(a.rsrc, n, base, p, a.q_min16, a.cs, a.sd, cnt_at, pts, nullptr, nullptr, rule_row,
-                           &finite);
+    front_point_pass<FAST>(f, base, p, cnt_at, pts, nullptr, nullptr, rule_row, &finite);
     __syncthreads();
     const uint32_t cnt = *cnt_at;  // the skipped samples of the pass: usually none
     if (l.own) {
 #pragma unroll 2
       for (uint32_t e = l.slice; 2u * e < cnt; e += l.slices) {
-        const ag_f32x4 v = s_pts[e];
-        acc += agree_look(v.x, v.y, l.c, l.s, l.tx, l.ty, ck, fld, &cell_range);
-        if (2u * e + 1u < cnt) acc += agree_look(v.z, v.w, l.c, l.s, l.tx, l.ty, ck, fld, &cell_range);
+        const f32x4 v = s_pts[e];
+        acc += pose_look(v.x, v.y, l.c, l.s, l.tx, l.ty, ck, fld, &cell_range);
+        if (2u * e + 1u < cnt) acc += pose_look(v.z, v.w, l.c, l.s, l.tx, l.ty, ck, fld, &cell_range);
       }
     }
   }
   if (!__syncthreads_or(acc != 0u)) return;  // nothing to take off
   s_sum[threadIdx.x] = acc;
   __syncthreads();
-  if (threadIdx.x < l.per && tile * kAgTile + threadIdx.x < P) {
+  if (threadIdx.x < l.per && tile * kPoseTile + threadIdx.x < P) {
     uint32_t sum = 0u;
     for (uint32_t s = 0; s < l.slices; ++s) sum += s_sum[s * l.per + threadIdx.x];
     // what the count pass added for these samples at this pose: the weight holds at least that
-    if (sum) atomicSub(&weights[(size_t)g * weight_stride + tile * kAgTile + threadIdx.x], sum);
+    if (sum) atomicSub(&weights[(size_t)g * weight_stride + tile * kPoseTile + threadIdx.x], sum);
   }
 }
 
@@ -333,8 +291,8 @@ hipError_t launch_agree(hipStream_t s, const void *nodes, uint32_t n_stride, con
   hipLaunchKernelGGL(k_agree_prepare, dim3(prep), dim3(kPrepThreads), 0, s, weights, weight_stride, G, P, result,
                      counts, count_stride, B, n_stride, mask, mask_words_stride, mask_words, agree);
   // slices of a scan's passes, as launch_pose_score
-  const uint32_t passes = (n_stride + kAgList - 1u) / kAgList;
-  const dim3 grid(B, (P + kAgTile - 1u) / kAgTile, std::min(passes, 8u));
+  const uint32_t passes = (n_stride + kFrontList - 1u) / kFrontList;
+  const dim3 grid(B, (P + kPoseTile - 1u) / kPoseTile, std::min(passes, 8u));
   if (p.fast_d4000)
     hipLaunchKernelGGL(k_agree_count<true>, grid, dim3(kBlock), 0, s, (const uint2 *)nodes, n_stride, n_per_scan,
                        group, p, T, keepmask, mask_stride, motion, pose2d, k, poses, P, pose_stride, poses_per_group,

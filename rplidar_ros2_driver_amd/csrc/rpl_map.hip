@@ -7,8 +7,9 @@
 //   k_apply_match  one thread per scan: the group's (k, j, i) composed in front of the scan's pose.
 //
 // k_map_walk is k_occ_walk (rpl_occ.hip) with counts in the place of bits: one 1024-thread workgroup per scan,
-// the same front end and ray word (rpl_ray.hpp), 2048 samples per pass, the same one-step-per-iteration
-// Bresenham over an LDS ray queue.  What differs, because a count cannot "test the bit and skip":
+// the same scan set-up and pair load (rpl_front.hpp's scan_front, scan_pair) and ray word (rpl_ray.hpp), 2048 samples
+// per pass, the same one-step-per-iteration Bresenham over an LDS ray queue.  The wave compaction alone is written out
+// here (see the pass).  What differs, because a count cannot "test the bit and skip":
 //   * equal consecutive rays are not dropped but become ONE queue entry with a weight of up to 64 (the two
 //     ballots of rpl_match.hip); the ray word is full, so the weights have a byte queue of their own;
 //   * the window around the sensor holds 16-bit counters, two per LDS word (a scan has at most 32768 samples
@@ -21,16 +22,15 @@
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
+#include "rpl_front.hpp"
 #include "rpl_ray.hpp"
-#include "rpl_xf.hpp"
 
 namespace rpl {
 namespace {
 
-typedef uint32_t mp_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kMapWin = 176;                  // window side in cells: 176 * 176 * 2 B = 61952 B of counters
 constexpr int kMapWinWords = kMapWin / 2;     // words per window row
-constexpr uint32_t kQueue = 2u * kBlock;      // rays per pass: two samples per thread
+constexpr uint32_t kQueue = kFrontList;       // rays per pass: two samples per thread
 static_assert(kMapWin % 2 == 0, "two counters per word");
 static_assert(kMaxN <= 32768u, "a 16-bit window counter holds a scan's samples");
 
@@ -72,17 +72,11 @@ __global__ __launch_bounds__(kBlock) void k_map_walk(
   for (uint32_t j = threadIdx.x; j < (uint32_t)(kMapWin * kMapWinWords); j += kBlock) s_win[j] = 0u;
   if (threadIdx.x == 0) s_sensor = 0u;
   const uint32_t n_in = n_per_scan[sc];
-  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(n_in, min(n_stride, kMaxN)));
+  const uint32_t n = scan_len(n_in, n_stride);
   if (threadIdx.x == 0 && status && n_in > n) atomicOr(&status[g], RPLGPU_SCAN_OUT_TRUNCATED);
-  const ScanSide sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
-  const float2 *cs = p.inverted ? T.cs_inv : T.cs;
-  const uint32_t q_min16 = p.clip_enable ? (min(p.q_min, 256u) << 16) : 0u;
-  const uint2 *scan = nodes + (size_t)sc * n_stride;
-  // bounds-checked over the scan's n * 8 bytes: a node beyond it reads as zero (and i < n drops it)
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void *)scan, 0, (int)(n * 8u), 0x00020000);
+  const ScanFront f = scan_front(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
   int x0 = 0, y0 = 0;
-  const bool sensor_ok = grid_cell(sd.xf.tx, sd.xf.ty, k.origin_x, k.origin_y, k.resolution, &x0, &y0);
+  const bool sensor_ok = grid_cell(f.sd.xf.tx, f.sd.xf.ty, k.origin_x, k.origin_y, k.resolution, &x0, &y0);
   MapWalk o;
   o.s_win = s_win;
   o.counts = counts;
@@ -104,19 +98,9 @@ __global__ __launch_bounds__(kBlock) void k_map_walk(
     uint32_t r0 = 0u, r1 = 0u, wt0 = 0u, wt1 = 0u;
     unsigned long long m0 = 0ull, m1 = 0ull;
     if (2u * pr < n) {  // (the active lanes of a wave are its first ones: a lane's predecessor is active)
-      const mp_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(pr * 16u), 0, 0);
-      const uint32_t i0 = 2u * pr, i1 = i0 + 1u;
-      bool k0 = i0 < n && (__builtin_amdgcn_alignbit(t.y, t.x, 16) - p.d_lo) <= p.d_span &&
-                (t.y & 0x00FF0000u) >= q_min16;  // E1
-      bool k1 = i1 < n && (__builtin_amdgcn_alignbit(t.w, t.z, 16) - p.d_lo) <= p.d_span &&
-                (t.w & 0x00FF0000u) >= q_min16;
-      if (sd.ror_bits) {  // E1 AND E5 (launch_ror_mask); both samples sit in one word (i0 is even)
-        const uint32_t w = sd.ror_bits[i0 >> 5];
-        k0 = k0 && ((w >> (i0 & 31u)) & 1u);
-        k1 = k1 && ((w >> (i1 & 31u)) & 1u);
-      }
-      r0 = occ_ray<FAST>(t.x, t.y, i0, k0, cs, sd.xf, k, sensor_ok, x0, y0, &cell_range);
-      r1 = occ_ray<FAST>(t.z, t.w, i1, k1, cs, sd.xf, k, sensor_ok, x0, y0, &cell_range);
+      const ScanPair s = scan_pair(f, p, pr);
+      r0 = occ_ray<FAST>(s.t.x, s.t.y, s.i0, s.k0, f.cs, f.sd.xf, k, sensor_ok, x0, y0, &cell_range);
+      r1 = occ_ray<FAST>(s.t.z, s.t.w, s.i1, s.k1, f.cs, f.sd.xf, k, sensor_ok, x0, y0, &cell_range);
       // A sample continues a run when it has the ray of the sample before it; sample 0 of lanes 0 and 32 never
       // does, so a run holds at most 64 samples.  Every sample with a ray is in exactly one run: the weights of a
       // pass add up to its rays.
@@ -137,7 +121,9 @@ __global__ __launch_bounds__(kBlock) void k_map_walk(
     // (outside the branch: a shuffle must not read a lane that is switched off)
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) own += __shfl_xor(own, d, 64);
-    // one LDS atomic per wave: the wave's rays stay together in the queue, in sample order
+    // one LDS atomic per wave: the wave's rays stay together in the queue, in sample order (rpl_front.hpp's wave_slot
+    // written out: its two ballots stand in the branch above, in front of the reduction, and lane 0's two atomics go
+    // together; with wave_slot here the clean-rings walk measured 0.5 % slower)
     if (2u * pr < n) {  // (the same lanes as above: lane 0 is one of them)
       const unsigned long long below = (1ull << lane_id()) - 1ull;
       if (lane_id() == 0) {

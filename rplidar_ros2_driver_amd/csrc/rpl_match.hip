@@ -9,9 +9,9 @@
 //   k_match_best     reduces a group's volume to its eight result words.
 //
 // k_match_score: one 1024-thread workgroup per (scan, rotation, slice of the scan's 2048-sample passes), the
-// front end of k_occ_walk as it stands (two nodes per bounds-checked buffer_load_dwordx4, E1 / E5 keep bits, the
-// (cos, sin) table, rpl_xf.hpp's sample_xy), so a point lands where E8, E9 and E11 put it, bit for bit.  Behind
-// it, per 2048 samples:
+// front end of rpl_front.hpp (scan_front, front_cell_pass: two nodes per bounds-checked buffer_load_dwordx4, E1 / E5
+// keep bits, the (cos, sin) table, rpl_xf.hpp's sample_xy), so a point lands where E8, E9 and E11 put it, bit for
+// bit.  Per 2048 samples (the first two steps are front_cell_pass, the look-up is rpl_grid.hpp's field_look):
 //   * a sample becomes a CELL: the E11 cell of its rotated position.  A cell farther than the window from the
 //     grid scores nothing at any shift and is dropped; the others fit 13 bits per axis.
 //   * consecutive samples of a wave half that land in one cell (a wall's neighbours) become ONE list entry with
@@ -27,53 +27,18 @@
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
-#include "rpl_ray.hpp"  // run_behind, shared with rpl_map.hip; the cell rule (rpl_grid.hpp)
-#include "rpl_xf.hpp"
+#include "rpl_front.hpp"
 
 namespace rpl {
 namespace {
 
-typedef uint32_t mt_u32x4 __attribute__((ext_vector_type(4)));
-constexpr uint32_t kList = 2u * kBlock;  // entries per pass: two samples per thread
-constexpr int kCellBias = 64;            // cell + kCellBias >= 32 for every listed cell: an entry is never 0
-constexpr uint32_t kCellBits = 13;       // -32 .. 4096 + 31, biased, per axis
-constexpr uint32_t kCellMask = (1u << kCellBits) - 1u;
-constexpr int kMaxOwn = 5;               // candidates a thread owns when the window is above kBlock (65 * 65 / 1024)
+constexpr int kCellBias = 64;  // cell + kCellBias >= 32 for every listed cell: an entry is never 0
+constexpr int kMaxOwn = 5;     // candidates a thread owns when the window is above kBlock (65 * 65 / 1024)
 static_assert((2u * RPLGPU_MAX_MATCH_SHIFT + 1u) * (2u * RPLGPU_MAX_MATCH_SHIFT + 1u) <= (uint32_t)kMaxOwn * kBlock,
               "the window does not fit the registers of a workgroup");
+// -32 .. 4096 + 31, biased, per axis
 static_assert(RPLGPU_MAX_OCC_DIM + RPLGPU_MAX_MATCH_SHIFT + kCellBias <= (1u << kCellBits), "cell bits");
 static_assert(RPLGPU_MAX_MATCH_SHIFT <= (uint32_t)kCellBias / 2u, "cell bias");
-
-// One sample to its list word (biased cell, weight field 0), or 0: not kept, not finite, without a cell, or
-// out of every candidate's reach.
-template <bool FAST>
-__device__ __forceinline__ uint32_t match_word(uint32_t lo, uint32_t hi, uint32_t i, bool kept,
-                                               const float2 *__restrict__ cs, const ScanXf &xf, const MatchK &k,
-                                               float c, float s, float px, float py, uint32_t *finite,
-                                               bool *cell_range) {
-  if (!kept) return 0u;
-  const f2 xy = sample_xy<FAST>(lo, hi, i, cs, xf);
-  if (!(fabsf(xy.x) < __builtin_huge_valf() && fabsf(xy.y) < __builtin_huge_valf())) return 0u;
-  *finite += 1u;
-  const float qx = xy.x - px, qy = xy.y - py;
-  const float rx = (c * qx - s * qy) + px;
-  const float ry = (s * qx + c * qy) + py;
-  int cx, cy;
-  if (!grid_cell(rx, ry, k.origin_x, k.origin_y, k.resolution, &cx, &cy)) {
-    *cell_range = true;
-    return 0u;
-  }
-  if (cx < -(int)k.tx || cx >= (int)(k.width + k.tx) || cy < -(int)k.ty || cy >= (int)(k.height + k.ty)) return 0u;
-  return ((uint32_t)(cy + kCellBias) << kCellBits) | (uint32_t)(cx + kCellBias);
-}
-
-// field value under (cx + di, cy + dj): 0 outside the grid and for an unknown (negative) byte
-__device__ __forceinline__ uint32_t match_look(const int8_t *__restrict__ field, int cx, int cy, uint32_t W,
-                                               uint32_t H) {
-  if ((uint32_t)cx >= W || (uint32_t)cy >= H) return 0u;
-  const int v = field[(uint32_t)cy * W + (uint32_t)cx];
-  return (uint32_t)max(v, 0);
-}
 
 template <bool FAST>
 __global__ __launch_bounds__(kBlock) void k_match_score(
@@ -83,26 +48,19 @@ __global__ __launch_bounds__(kBlock) void k_match_score(
     MatchRot rot, const int8_t *__restrict__ field, unsigned long long field_stride, uint32_t field_per_group,
     uint32_t *__restrict__ scores, unsigned long long score_stride, uint32_t *__restrict__ best,
     uint32_t *__restrict__ status) {
-  __shared__ uint32_t s_list[kList];
+  __shared__ uint32_t s_list[kFrontList];
   __shared__ uint32_t s_sum[kBlock];
   __shared__ uint32_t s_cnt[2];  // the list's length, by the pass's parity: a reset never meets a late reader
   const uint32_t sc = blockIdx.x;
   const uint32_t kk = blockIdx.y;  // k + K
   const uint32_t g = sc / group;
   const uint32_t n_in = n_per_scan[sc];
-  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(n_in, min(n_stride, kMaxN)));
+  const uint32_t n = scan_len(n_in, n_stride);
   const bool first_of_scan = kk == 0u && blockIdx.z == 0u;
   if (threadIdx.x == 0 && status && first_of_scan && n_in > n) atomicOr(&status[g], RPLGPU_SCAN_OUT_TRUNCATED);
-  if (blockIdx.z * kList >= n) return;  // (block-uniform)
-  const ScanSide sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
-  const float2 *cs = p.inverted ? T.cs_inv : T.cs;
-  const uint32_t q_min16 = p.clip_enable ? (min(p.q_min, 256u) << 16) : 0u;
-  const uint2 *scan = nodes + (size_t)sc * n_stride;
-  // bounds-checked over the scan's n * 8 bytes: a node beyond it reads as zero (and i < n drops it)
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void *)scan, 0, (int)(n * 8u), 0x00020000);
-  const float rc = rot.cs[2u * kk], rs = rot.cs[2u * kk + 1u];
-  const float px = pivot ? pivot[2u * g] : 0.0f, py = pivot ? pivot[2u * g + 1u] : 0.0f;
+  if (blockIdx.z * kFrontList >= n) return;  // (block-uniform)
+  const ScanFront f = scan_front(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
+  const CellRot cr = cell_rot(rot, kk, pivot, g);
   const int8_t *fld = field + (size_t)(field_per_group ? g : 0u) * field_stride;
   const uint32_t W = k.width, H = k.height;
   // the candidates of this thread: window position c = (j + Ty) * nx + (i + Tx), copy `slice` of `slices`
@@ -125,51 +83,17 @@ __global__ __launch_bounds__(kBlock) void k_match_score(
   uint32_t finite = 0u;
   bool cell_range = false;
   uint32_t pass = 0u;
-  for (uint32_t base = blockIdx.z * kList; base < n; base += gridDim.z * kList) {
+  for (uint32_t base = blockIdx.z * kFrontList; base < n; base += gridDim.z * kFrontList) {
     uint32_t *cnt_at = &s_cnt[pass++ & 1u];
-    if (threadIdx.x == 0) *cnt_at = 0u;
-    __syncthreads();  // (also: the last pass's readers are done with the list)
-    const uint32_t pr = base / 2u + threadIdx.x;
-    if (2u * pr < n) {  // (the active lanes of a wave are its first ones: a lane's predecessor is active)
-      const mt_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(pr * 16u), 0, 0);
-      const uint32_t i0 = 2u * pr, i1 = i0 + 1u;
-      bool k0 = i0 < n && (__builtin_amdgcn_alignbit(t.y, t.x, 16) - p.d_lo) <= p.d_span &&
-                (t.y & 0x00FF0000u) >= q_min16;  // E1
-      bool k1 = i1 < n && (__builtin_amdgcn_alignbit(t.w, t.z, 16) - p.d_lo) <= p.d_span &&
-                (t.w & 0x00FF0000u) >= q_min16;
-      if (sd.ror_bits) {  // E1 AND E5 (launch_ror_mask); both samples sit in one word (i0 is even)
-        const uint32_t w = sd.ror_bits[i0 >> 5];
-        k0 = k0 && ((w >> (i0 & 31u)) & 1u);
-        k1 = k1 && ((w >> (i1 & 31u)) & 1u);
-      }
-      const uint32_t w0 = match_word<FAST>(t.x, t.y, i0, k0, cs, sd.xf, k, rc, rs, px, py, &finite, &cell_range);
-      const uint32_t w1 = match_word<FAST>(t.z, t.w, i1, k1, cs, sd.xf, k, rc, rs, px, py, &finite, &cell_range);
-      // A sample continues a run when it has the cell of the sample before it; sample 0 of lanes 0 and 32 never
-      // does, so a run holds at most 64 samples and its weight - 1 fits the six bits above the cell.
-      const uint32_t before = __shfl_up(w1, 1, 64);  // the word of sample i0 - 1
-      const bool e0 = w0 && (lane_id() & 31u) != 0u && w0 == before, e1 = w1 && w1 == w0;
-      const bool h0 = w0 && !e0, h1 = w1 && !e1;
-      const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1);
-      const unsigned long long c_first = __ballot(e0), c_both = c_first & __ballot(e1);
-      const uint32_t behind = run_behind(lane_id(), c_both, c_first);
-      const uint32_t wt0 = e1 ? 2u + behind : 1u, wt1 = 1u + behind;
-      // one LDS atomic per wave: the wave's entries stay together in the list, in sample order
-      const unsigned long long below = (1ull << lane_id()) - 1ull;
-      uint32_t at = 0u;
-      if (lane_id() == 0) at = atomicAdd(cnt_at, (uint32_t)(__popcll(m0) + __popcll(m1)));
-      at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at) + (uint32_t)(__popcll(m0 & below) + __popcll(m1 & below));
-      if (h0) s_list[at] = w0 | ((wt0 - 1u) << (2u * kCellBits));
-      if (h1) s_list[at + (h0 ? 1u : 0u)] = w1 | ((wt1 - 1u) << (2u * kCellBits));
-    }
-    __syncthreads();
-    const uint32_t cnt = *cnt_at;  // <= kList
+    front_cell_pass<FAST, kCellBias, 0>(f, base, p, k, cr, s_list, cnt_at, &finite, &cell_range);
+    const uint32_t cnt = *cnt_at;  // <= kFrontList
     if (!wide) {
       if (own[0]) {
 #pragma unroll 4
         for (uint32_t e = slice; e < cnt; e += slices) {
           const uint32_t w = s_list[e];
           const int cx = (int)(w & kCellMask) - kCellBias, cy = (int)((w >> kCellBits) & kCellMask) - kCellBias;
-          acc[0] += ((w >> (2u * kCellBits)) + 1u) * match_look(fld, cx + di[0], cy + dj[0], W, H);
+          acc[0] += ((w >> (2u * kCellBits)) + 1u) * field_look(fld, cx + di[0], cy + dj[0], W, H);
         }
       }
     } else {
@@ -179,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_match_score(
         const uint32_t wt = (w >> (2u * kCellBits)) + 1u;
 #pragma unroll
         for (int r = 0; r < kMaxOwn; ++r)
-          if (own[r]) acc[r] += wt * match_look(fld, cx + di[r], cy + dj[r], W, H);
+          if (own[r]) acc[r] += wt * field_look(fld, cx + di[r], cy + dj[r], W, H);
       }
     }
   }
@@ -318,7 +242,7 @@ hipError_t launch_match_score(hipStream_t s, const void *nodes, uint32_t n_strid
       score_stride < match_volume(k))
     return hipErrorInvalidValue;
   // slices of a scan's passes: enough workgroups for a time step of a few scans, and at most 8 x the atomics
-  const uint32_t passes = (min(n_stride, kMaxN) + kList - 1u) / kList;
+  const uint32_t passes = (min(n_stride, kMaxN) + kFrontList - 1u) / kFrontList;
   const dim3 grid(B, 2u * k.rot + 1u, min(passes, 8u));
   if (p.fast_d4000)
     hipLaunchKernelGGL(k_match_score<true>, grid, dim3(kBlock), 0, s, (const uint2 *)nodes, n_stride, n_per_scan,

@@ -1,10 +1,10 @@
 // rpl_merge.hip — E9: the scans of a group (the sensors of one time step) merged into ONE LaserScan in
 // the common frame (include/rplgpu_msg.h, rplgpu_merge_scans_dev).
 //
-// k_merge_scans: one 1024-thread workgroup per scan.  A lane takes two consecutive samples per
-// buffer_load_dwordx4 of the packed 8-byte nodes, keeps what E1 (and the E5 keep bits) keep, and runs
-// E2 with the (cos, sin) table, then E6 + the planar pose through rpl_xf.hpp's apply_xf — the front end
-// of E8, so a point lands where rplgpu_cloud_fused_voxel_dev puts it, bit for bit.  The beam comes from
+// k_merge_scans: one 1024-thread workgroup per scan.  The scan is opened by rpl_front.hpp (scan_front, scan_pair:
+// two consecutive samples per buffer_load_dwordx4, the E1 / E5 keep bits), a kept sample runs E2 with the
+// (cos, sin) table, then E6 + the planar pose through rpl_xf.hpp's sample_xy — the front end of E8, so a
+// point lands where rplgpu_cloud_fused_voxel_dev puts it, bit for bit.  The beam comes from
 // the exact side tests of the spec (merge_bin), the reduction is a 64-bit min over
 //   key = r2 bits << 32 | slot in group << 15 | sample index
 // in LDS (ds_min_u64: r2 >= 0, so its bits order like the value; ties go to the first point in
@@ -15,13 +15,12 @@
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
+#include "rpl_front.hpp"
 #include "rpl_msg.hpp"
-#include "rpl_xf.hpp"
 
 namespace rpl {
 namespace {
 
-typedef uint32_t mg_u32x4 __attribute__((ext_vector_type(4)));
 constexpr unsigned long long kEmptyBeam = ~0ull;
 
 // cross_k(p) >= 0: the products of two float32 values are exact in fp64 and the difference is rounded
@@ -107,31 +106,15 @@ __global__ __launch_bounds__(kBlock) void k_merge_scans(
   const uint32_t g = sc / group, slot = sc - g * group;
   for (uint32_t j = threadIdx.x; j < mk.count; j += kBlock) s_key[j] = kEmptyBeam;
   const uint32_t n_in = n_per_scan[sc];
-  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(n_in, min(n_stride, kMaxN)));
+  const uint32_t n = scan_len(n_in, n_stride);
   if (threadIdx.x == 0 && status && n_in > n) atomicOr(&status[g], RPLGPU_SCAN_OUT_TRUNCATED);
-  const ScanSide sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
-  const float2 *cs = p.inverted ? T.cs_inv : T.cs;
-  const uint32_t q_min16 = p.clip_enable ? (min(p.q_min, 256u) << 16) : 0u;
+  const ScanFront f = scan_front(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
   const unsigned long long slot_bits = (unsigned long long)slot << 15;
-  const uint2 *scan = nodes + (size_t)sc * n_stride;
-  // bounds-checked over the scan's n * 8 bytes: a node beyond it reads as zero (and i < n drops it)
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void *)scan, 0, (int)(n * 8u), 0x00020000);
   __syncthreads();
   for (uint32_t pr = threadIdx.x; 2u * pr < n; pr += kBlock) {
-    const mg_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(pr * 16u), 0, 0);
-    const uint32_t i0 = 2u * pr, i1 = i0 + 1u;
-    bool k0 = i0 < n && (__builtin_amdgcn_alignbit(t.y, t.x, 16) - p.d_lo) <= p.d_span &&
-              (t.y & 0x00FF0000u) >= q_min16;  // E1
-    bool k1 = i1 < n && (__builtin_amdgcn_alignbit(t.w, t.z, 16) - p.d_lo) <= p.d_span &&
-              (t.w & 0x00FF0000u) >= q_min16;
-    if (sd.ror_bits) {  // E1 AND E5 (launch_ror_mask); both samples sit in one word (i0 is even)
-      const uint32_t w = sd.ror_bits[i0 >> 5];
-      k0 = k0 && ((w >> (i0 & 31u)) & 1u);
-      k1 = k1 && ((w >> (i1 & 31u)) & 1u);
-    }
-    merge_sample<FAST>(t.x, t.y, i0, k0, cs, sd.xf, mk, slot_bits, s_key);
-    merge_sample<FAST>(t.z, t.w, i1, k1, cs, sd.xf, mk, slot_bits, s_key);
+    const ScanPair s = scan_pair(f, p, pr);
+    merge_sample<FAST>(s.t.x, s.t.y, s.i0, s.k0, f.cs, f.sd.xf, mk, slot_bits, s_key);
+    merge_sample<FAST>(s.t.z, s.t.w, s.i1, s.k1, f.cs, f.sd.xf, mk, slot_bits, s_key);
   }
   __syncthreads();
   unsigned long long *row = keys + (size_t)g * mk.count;

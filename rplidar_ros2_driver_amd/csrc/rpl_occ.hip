@@ -7,9 +7,14 @@
 //   k_occ_walk     ORs 0x01 (cleared) / 0x02 (marked) into the cells' bytes;
 //   k_occ_finish   maps a byte with 0x02 to 100, one with 0x01 to 0, any other to d_prev or -1, and counts.
 //
-// k_occ_walk: one 1024-thread workgroup per scan, the front end of k_merge_scans as it stands (two nodes
-// per bounds-checked buffer_load_dwordx4, E1 / E5 keep bits, the (cos, sin) table, rpl_xf.hpp's sample_xy),
-// so a point lands where E8 and E9 put it, bit for bit.  Behind it, per 2048 samples:
+// k_occ_walk: one 1024-thread workgroup per scan, the front end of rpl_front.hpp WRITTEN OUT (two nodes per
+// bounds-checked buffer_load_dwordx4, E1 / E5 keep bits, the (cos, sin) table, rpl_xf.hpp's sample_xy), so a
+// point lands where E8 and E9 put it, bit for bit.  It is the one kernel of E9 - E25 that does not call that
+// header: through scan_len / scan_front / scan_pair / wave_slot the compiler's code had the same instruction
+// count and resources but another order of a few scalar instructions, and the clean-rings walk of
+// tools/dev/occbench.py measured 0.1 - 0.2 % above this form after five more alternating pairs
+// (profiles/r31/scan_front_r31.txt).  A change to the front end in rpl_front.hpp has
+// to be repeated here; tests/test_gpu_occ.py holds this copy to the oracle.  Behind it, per 2048 samples:
 //   * a sample becomes a RAY: one word, the end cell relative to the sensor cell (the sensor cell is the
 //     scan's; the spec bounds |delta| by raytrace_max / resolution <= 8192) and the whole / cut / mark bits.
 //     A ray equal to its predecessor's is dropped (consecutive samples of a wall end in the same cell; the

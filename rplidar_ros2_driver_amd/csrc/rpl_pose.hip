@@ -10,10 +10,10 @@
 //   k_pose_best     reduces a group's weights to its eight result words.
 //
 // k_pose_score: one 1024-thread workgroup per (scan, tile of 1024 poses, slice of the scan's 2048-sample passes),
-// the front end of k_match_score as it stands (two nodes per bounds-checked buffer_load_dwordx4, E1 / E5 keep bits,
-// the (cos, sin) table, rpl_xf.hpp's sample_xy), so a point lands where E8, E9, E11 and E13 put it, bit for bit.
-// Behind it, per 2048 samples:
-//   * the finite points are compacted into an LDS list of float2 (one atomic per wave);
+// the front end of rpl_front.hpp (scan_front, front_point_pass: two nodes per bounds-checked buffer_load_dwordx4,
+// E1 / E5 keep bits, the (cos, sin) table, rpl_xf.hpp's sample_xy), so a point lands where E8, E9, E11 and E13 put
+// it, bit for bit.  Per 2048 samples:
+//   * the finite points are compacted into an LDS list of float2 (front_point_pass: one atomic per wave);
 //   * then a thread owns ONE pose in registers and walks the list: every lane of a wave reads the same LDS
 //     address, a broadcast, two points per 128-bit read.  A list of up to 1024 poses is rounded up to whole waves
 //     and repeated over the workgroup as often as it fits; each copy walks its share of the point pairs;
@@ -23,33 +23,12 @@
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
-#include "rpl_grid.hpp"
-#include "rpl_xf.hpp"
+#include "rpl_front.hpp"
 
 namespace rpl {
 namespace {
 
-typedef uint32_t ps_u32x4 __attribute__((ext_vector_type(4)));
-typedef float ps_f32x4 __attribute__((ext_vector_type(4)));
-constexpr uint32_t kList = 2u * kBlock;  // points per pass: two samples per thread
-constexpr uint32_t kTile = kBlock;       // poses per workgroup: one per thread
-static_assert(kList * sizeof(float2) == 16384, "the point list is 16 KiB");
-
-// field value under the cell of (c*x - s*y + tx, s*x + c*y + ty): 0 without a cell (and *cell_range), outside the
-// grid and for an unknown (negative) byte
-__device__ __forceinline__ uint32_t pose_look(float x, float y, float c, float s, float tx, float ty,
-                                              const OccK &k, const int8_t *__restrict__ field, bool *cell_range) {
-  const float rx = (c * x - s * y) + tx;
-  const float ry = (s * x + c * y) + ty;
-  int cx, cy;
-  if (!grid_cell(rx, ry, k.origin_x, k.origin_y, k.resolution, &cx, &cy)) {
-    *cell_range = true;
-    return 0u;
-  }
-  if ((uint32_t)cx >= k.width || (uint32_t)cy >= k.height) return 0u;
-  const int v = field[(uint32_t)cy * k.width + (uint32_t)cx];
-  return (uint32_t)max(v, 0);
-}
+static_assert(kFrontList * sizeof(float2) == 16384, "the point list is 16 KiB");
 
 template <bool FAST>
 __global__ __launch_bounds__(kBlock) void k_pose_score(
@@ -59,88 +38,40 @@ __global__ __launch_bounds__(kBlock) void k_pose_score(
     uint32_t P, unsigned long long pose_stride, uint32_t poses_per_group, const int8_t *__restrict__ field,
     unsigned long long field_stride, uint32_t field_per_group, uint32_t *__restrict__ weights,
     unsigned long long weight_stride, uint32_t *__restrict__ result, uint32_t *__restrict__ status) {
-  __shared__ ps_f32x4 s_pts[kList / 2u];  // two points (x0, y0, x1, y1) per element
+  __shared__ f32x4 s_pts[kFrontList / 2u];  // two points (x0, y0, x1, y1) per element
   __shared__ uint32_t s_sum[kBlock];
   __shared__ uint32_t s_cnt[2];  // the list's length, by the pass's parity: a reset never meets a late reader
   const uint32_t sc = blockIdx.x;
   const uint32_t tile = blockIdx.y;
   const uint32_t g = sc / group;
   const uint32_t n_in = n_per_scan[sc];
-  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(n_in, min(n_stride, kMaxN)));
+  const uint32_t n = scan_len(n_in, n_stride);
   const bool first_of_scan = tile == 0u && blockIdx.z == 0u;
   if (threadIdx.x == 0 && status && first_of_scan && n_in > n) atomicOr(&status[g], RPLGPU_SCAN_OUT_TRUNCATED);
-  if (blockIdx.z * kList >= n) return;  // (block-uniform)
-  const ScanSide sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
-  const float2 *cs = p.inverted ? T.cs_inv : T.cs;
-  const uint32_t q_min16 = p.clip_enable ? (min(p.q_min, 256u) << 16) : 0u;
-  const uint2 *scan = nodes + (size_t)sc * n_stride;
-  // bounds-checked over the scan's n * 8 bytes: a node beyond it reads as zero (and i < n drops it)
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void *)scan, 0, (int)(n * 8u), 0x00020000);
+  if (blockIdx.z * kFrontList >= n) return;  // (block-uniform)
+  const ScanFront f = scan_front(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
   const OccK ck{k.origin_x, k.origin_y, k.resolution, k.width, k.height, 0.0f, 0.0f, 0.0f};  // (the cell rule's part)
   const int8_t *fld = field + (size_t)(field_per_group ? g : 0u) * field_stride;
-  // the pose of this thread: entry q0 of the tile, copy `slice` of `slices` (pose_layout below, the same formula)
-  const uint32_t per = min((P + 63u) & ~63u, (uint32_t)kTile);  // threads of one copy of the list
-  const uint32_t slices = P <= (uint32_t)kTile ? (uint32_t)kTile / per : 1u;
-  const uint32_t slice = threadIdx.x / per, q0 = threadIdx.x - slice * per;  // (slice: wave-uniform, per is whole waves)
-  const uint32_t q = tile * kTile + q0;
-  const bool own = slice < slices && q < P;
-  float pc = 0.0f, psn = 0.0f, ptx = 0.0f, pty = 0.0f;
-  if (own) {  // a thread without a pose loads nothing and adds nothing
-    const ps_f32x4 v =
-        *reinterpret_cast<const ps_f32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride + 4u * (size_t)q);
-    pc = v.x; psn = v.y; ptx = v.z; pty = v.w;
-  }
+  const PoseLane l = pose_lane(tile, P, poses + (size_t)(poses_per_group ? g : 0u) * pose_stride);
   uint32_t acc = 0u;
   uint32_t finite = 0u;
   bool cell_range = false;
   uint32_t pass = 0u;
   float2 *pts = reinterpret_cast<float2 *>(s_pts);
-  for (uint32_t base = blockIdx.z * kList; base < n; base += gridDim.z * kList) {
+  for (uint32_t base = blockIdx.z * kFrontList; base < n; base += gridDim.z * kFrontList) {
     uint32_t *cnt_at = &s_cnt[pass++ & 1u];
     if (threadIdx.x == 0) *cnt_at = 0u;
     __syncthreads();  // (also: the last pass's readers are done with the list)
-    const uint32_t pr = base / 2u + threadIdx.x;
-    if (2u * pr < n) {  // (the active lanes of a wave are its first ones)
-      const ps_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(pr * 16u), 0, 0);
-      const uint32_t i0 = 2u * pr, i1 = i0 + 1u;
-      bool k0 = i0 < n && (__builtin_amdgcn_alignbit(t.y, t.x, 16) - p.d_lo) <= p.d_span &&
-                (t.y & 0x00FF0000u) >= q_min16;  // E1
-      bool k1 = i1 < n && (__builtin_amdgcn_alignbit(t.w, t.z, 16) - p.d_lo) <= p.d_span &&
-                (t.w & 0x00FF0000u) >= q_min16;
-      if (sd.ror_bits) {  // E1 AND E5 (launch_ror_mask); both samples sit in one word (i0 is even)
-        const uint32_t w = sd.ror_bits[i0 >> 5];
-        k0 = k0 && ((w >> (i0 & 31u)) & 1u);
-        k1 = k1 && ((w >> (i1 & 31u)) & 1u);
-      }
-      f2 a = {0.0f, 0.0f}, b = {0.0f, 0.0f};
-      if (k0) {
-        a = sample_xy<FAST>(t.x, t.y, i0, cs, sd.xf);
-        k0 = fabsf(a.x) < __builtin_huge_valf() && fabsf(a.y) < __builtin_huge_valf();
-      }
-      if (k1) {
-        b = sample_xy<FAST>(t.z, t.w, i1, cs, sd.xf);
-        k1 = fabsf(b.x) < __builtin_huge_valf() && fabsf(b.y) < __builtin_huge_valf();
-      }
-      finite += (k0 ? 1u : 0u) + (k1 ? 1u : 0u);
-      // one LDS atomic per wave: the wave's points stay together in the list, in sample order
-      const unsigned long long m0 = __ballot(k0), m1 = __ballot(k1);
-      const unsigned long long below = (1ull << lane_id()) - 1ull;
-      uint32_t at = 0u;
-      if (lane_id() == 0) at = atomicAdd(cnt_at, (uint32_t)(__popcll(m0) + __popcll(m1)));
-      at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at) + (uint32_t)(__popcll(m0 & below) + __popcll(m1 & below));
-      if (k0) pts[at] = make_float2(a.x, a.y);                    // at + 1 <= the wave's share: < kList
-      if (k1) pts[at + (k0 ? 1u : 0u)] = make_float2(b.x, b.y);
-    }
+    front_point_pass<FAST>(f, base, p, cnt_at, pts, nullptr, nullptr, nullptr, &finite);
     __syncthreads();
-    const uint32_t cnt = *cnt_at;  // <= kList
-    if (own) {
-      // copy `slice` walks the point pairs slice, slice + slices, ...: pair e holds points 2e and 2e + 1 < kList
+    const uint32_t cnt = *cnt_at;  // <= kFrontList
+    if (l.own) {
+      // copy `slice` walks the point pairs slice, slice + slices, ...: pair e holds points 2e and 2e + 1 < kFrontList
 #pragma unroll 2
-      for (uint32_t e = slice; 2u * e < cnt; e += slices) {
-        const ps_f32x4 v = s_pts[e];
-        acc += pose_look(v.x, v.y, pc, psn, ptx, pty, ck, fld, &cell_range);
-        if (2u * e + 1u < cnt) acc += pose_look(v.z, v.w, pc, psn, ptx, pty, ck, fld, &cell_range);
+      for (uint32_t e = l.slice; 2u * e < cnt; e += l.slices) {
+        const f32x4 v = s_pts[e];
+        acc += pose_look(v.x, v.y, l.c, l.s, l.tx, l.ty, ck, fld, &cell_range);
+        if (2u * e + 1u < cnt) acc += pose_look(v.z, v.w, l.c, l.s, l.tx, l.ty, ck, fld, &cell_range);
       }
     }
   }
@@ -153,10 +84,10 @@ __global__ __launch_bounds__(kBlock) void k_pose_score(
   __syncthreads();
   s_sum[threadIdx.x] = acc;  // copy `slice` at [slice * per, slice * per + per); 0 where a thread owns no pose
   __syncthreads();
-  if (threadIdx.x < per && tile * kTile + threadIdx.x < P) {
+  if (threadIdx.x < l.per && tile * kPoseTile + threadIdx.x < P) {
     uint32_t sum = 0u;
-    for (uint32_t s = 0; s < slices; ++s) sum += s_sum[s * per + threadIdx.x];  // slices * per <= kBlock
-    if (sum) atomicAdd(&weights[(size_t)g * weight_stride + tile * kTile + threadIdx.x], sum);
+    for (uint32_t s = 0; s < l.slices; ++s) sum += s_sum[s * l.per + threadIdx.x];  // slices * per <= kBlock
+    if (sum) atomicAdd(&weights[(size_t)g * weight_stride + tile * kPoseTile + threadIdx.x], sum);
   }
 }
 
@@ -269,8 +200,8 @@ hipError_t launch_pose_score(hipStream_t s, const void *nodes, uint32_t n_stride
       pose_stride < 4ull * P || (pose_stride & 3u) || weight_stride < P)
     return hipErrorInvalidValue;
   // slices of a scan's passes: enough workgroups for a time step of a few scans, and at most 8 x the atomics
-  const uint32_t passes = (min(n_stride, kMaxN) + kList - 1u) / kList;
-  const dim3 grid(B, (P + kTile - 1u) / kTile, min(passes, 8u));
+  const uint32_t passes = (min(n_stride, kMaxN) + kFrontList - 1u) / kFrontList;
+  const dim3 grid(B, (P + kPoseTile - 1u) / kPoseTile, min(passes, 8u));
   if (p.fast_d4000)
     hipLaunchKernelGGL(k_pose_score<true>, grid, dim3(kBlock), 0, s, (const uint2 *)nodes, n_stride, n_per_scan,
                        group, p, T, keepmask, mask_stride, motion, pose2d, k, poses, P, pose_stride,

@@ -3,8 +3,8 @@
 //
 //   k_refine_prepare  zeroes the scratch planes and the eight result words of every group;
 //   k_refine_sums     E23's grid and walk (one workgroup per scan x tile of 1024 poses x slice of passes; the front
-//                     end is agree_front_pass of rpl_agree.hpp, not a copy; a thread owns one pose and walks the LDS
-//                     point list by broadcast): per point four field bytes, V, Gx, Gy, Gt, E and the eleven sums in
+//                     end is scan_front, front_point_pass and pose_lane of rpl_front.hpp; a thread owns one pose and
+//                     walks the LDS point list by broadcast): per point four field bytes, V, Gx, Gy, Gt, E and the eleven sums in
 //                     registers; at the end the copies of a short list are added in LDS, limb by limb, and every
 //                     32-bit limb leaves with one 64-bit no-return atomic add onto its own plane of the scratch, so
 //                     no carry crosses an atomic and the planes depend on no order;
@@ -19,7 +19,7 @@
 
 #include <algorithm>
 
-#include "rpl_agree.hpp"
+#include "rpl_front.hpp"
 #include "rpl_refine.hpp"
 
 namespace rpl {
@@ -27,33 +27,12 @@ namespace {
 
 typedef unsigned long long u64;
 typedef long long i64;
-typedef uint32_t rf_u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t kPlanes = RPLGPU_REFINE_PLANES;
 constexpr uint32_t kMaxZ = 8u;  // slices of a scan's passes
-static_assert((kMaxN + kAgList - 1u) / kAgList <= 2u * kMaxZ, "a workgroup walks at most two passes: 4096 points");
+static_assert((kMaxN + kFrontList - 1u) / kFrontList <= 2u * kMaxZ,
+              "a workgroup walks at most two passes: 4096 points");
 static_assert(RPLGPU_REFINE_WORDS == 32u && kPlanes == 29u, "the layout of the header's table");
-
-// the pose of a thread: entry q0 of the tile, copy `slice` of `slices` (k_pose_score's layout, the same formula)
-struct RefineLane {
-  uint32_t per, slices, slice, q;
-  bool own;
-  float c, s, tx, ty;
-};
-__device__ __forceinline__ RefineLane refine_lane(uint32_t tile, uint32_t P, const float *__restrict__ list) {
-  RefineLane l;
-  l.per = min((P + 63u) & ~63u, (uint32_t)kAgTile);
-  l.slices = P <= (uint32_t)kAgTile ? (uint32_t)kAgTile / l.per : 1u;
-  l.slice = threadIdx.x / l.per;
-  l.q = tile * kAgTile + (threadIdx.x - l.slice * l.per);
-  l.own = l.slice < l.slices && l.q < P;
-  l.c = l.s = l.tx = l.ty = 0.0f;
-  if (l.own) {
-    const ag_f32x4 v = *reinterpret_cast<const ag_f32x4 *>(list + 4u * (size_t)l.q);
-    l.c = v.x; l.s = v.y; l.tx = v.z; l.ty = v.w;
-  }
-  return l;
-}
 
 // a thread's sums (the header's table; the limbs are made at the end)
 struct RefineAcc {
@@ -65,14 +44,8 @@ struct RefineAcc {
   uint32_t n, dropped;
 };
 
-// m(ix, iy): 0 outside the grid and for a negative byte
-__device__ __forceinline__ int refine_m(const int8_t *__restrict__ field, const RefineK &k, int ix, int iy) {
-  if ((uint32_t)ix >= k.width || (uint32_t)iy >= k.height) return 0;
-  return max((int)field[(uint32_t)iy * k.width + (uint32_t)ix], 0);  // < width * height <= field_stride
-}
-
 // one point at one pose, the header's PER POINT rule
-__device__ __forceinline__ void refine_point(float x, float y, const RefineLane &l, const RefineK &k,
+__device__ __forceinline__ void refine_point(float x, float y, const PoseLane &l, const RefineK &k,
                                              const int8_t *__restrict__ field, RefineAcc &a) {
   const float ax = l.c * x - l.s * y;
   const float ay = l.s * x + l.c * y;
@@ -87,8 +60,10 @@ __device__ __forceinline__ void refine_point(float x, float y, const RefineLane 
   const int U = (int)floorf(hu), V_ = (int)floorf(hv);
   const int i0 = U >> 8, j0 = V_ >> 8, fa = U & 255, fb = V_ & 255;  // |i0|, |j0| <= 2^20: i0 + 1 does not wrap
   const int Lx = (int)rintf(lx * 16.0f), Ly = (int)rintf(ly * 16.0f);
-  const int m00 = refine_m(field, k, i0, j0), m10 = refine_m(field, k, i0 + 1, j0);
-  const int m01 = refine_m(field, k, i0, j0 + 1), m11 = refine_m(field, k, i0 + 1, j0 + 1);
+  // m(ix, iy): 0 outside the grid and for a negative byte
+  const uint32_t W = k.width, H = k.height;
+  const int m00 = (int)field_look(field, i0, j0, W, H), m10 = (int)field_look(field, i0 + 1, j0, W, H);
+  const int m01 = (int)field_look(field, i0, j0 + 1, W, H), m11 = (int)field_look(field, i0 + 1, j0 + 1, W, H);
   const int na = 256 - fa, nb = 256 - fb;
   const int V = na * nb * m00 + fa * nb * m10 + na * fb * m01 + fa * fb * m11;  // <= 127 * 65536
   const int Gx = nb * (m10 - m00) + fb * (m11 - m01);
@@ -133,41 +108,35 @@ __global__ __launch_bounds__(kBlock) void k_refine_sums(
     uint32_t P, unsigned long long pose_stride, uint32_t poses_per_group, const int8_t *__restrict__ field,
     unsigned long long field_stride, uint32_t field_per_group, u64 *__restrict__ scratch,
     uint32_t *__restrict__ result, uint32_t *__restrict__ status) {
-  __shared__ ag_f32x4 s_pts[kAgList / 2u];  // two points (x0, y0, x1, y1) per element
+  __shared__ f32x4 s_pts[kFrontList / 2u];  // two points (x0, y0, x1, y1) per element
   __shared__ uint32_t s_sum[kBlock];
   __shared__ uint32_t s_cnt[2];  // the list's length, by the pass's parity: a reset never meets a late reader
   const uint32_t sc = blockIdx.x;
   const uint32_t tile = blockIdx.y;
   const uint32_t g = sc / group;
   const uint32_t n_in = n_per_scan[sc];
-  const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(n_in, min(n_stride, kMaxN)));
+  const uint32_t n = scan_len(n_in, n_stride);
   const bool first_of_scan = tile == 0u && blockIdx.z == 0u;
   if (threadIdx.x == 0 && status && first_of_scan && n_in > n) atomicOr(&status[g], RPLGPU_SCAN_OUT_TRUNCATED);
-  if (blockIdx.z * kAgList >= n) return;  // (block-uniform)
-  // the scan's side, as k_agree_count sets it up
-  const ScanSide sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
-  const float2 *cs = p.inverted ? T.cs_inv : T.cs;
-  const uint32_t q_min16 = p.clip_enable ? (min(p.q_min, 256u) << 16) : 0u;
-  // bounds-checked over the scan's n * 8 bytes: a node beyond it reads as zero (and i < n drops it)
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void *)(nodes + (size_t)sc * n_stride), 0, (int)(n * 8u), 0x00020000);
+  if (blockIdx.z * kFrontList >= n) return;  // (block-uniform)
+  const ScanFront f = scan_front(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
   const int8_t *fld = field + (size_t)(field_per_group ? g : 0u) * field_stride;
-  const RefineLane l = refine_lane(tile, P, poses + (size_t)(poses_per_group ? g : 0u) * pose_stride);
+  const PoseLane l = pose_lane(tile, P, poses + (size_t)(poses_per_group ? g : 0u) * pose_stride);
   RefineAcc a = {};
   uint32_t finite = 0u;
   uint32_t pass = 0u;
   float2 *pts = reinterpret_cast<float2 *>(s_pts);
-  for (uint32_t base = blockIdx.z * kAgList; base < n; base += gridDim.z * kAgList) {
+  for (uint32_t base = blockIdx.z * kFrontList; base < n; base += gridDim.z * kFrontList) {
     uint32_t *cnt_at = &s_cnt[pass++ & 1u];
     if (threadIdx.x == 0) *cnt_at = 0u;
     __syncthreads();  // (also: the last pass's readers are done with the list)
-    agree_front_pass<FAST>(rsrc, n, base, p, q_min16, cs, sd, cnt_at, pts, nullptr, nullptr, nullptr, &finite);
+    front_point_pass<FAST>(f, base, p, cnt_at, pts, nullptr, nullptr, nullptr, &finite);
     __syncthreads();
-    const uint32_t cnt = *cnt_at;  // <= kAgList
+    const uint32_t cnt = *cnt_at;  // <= kFrontList
     if (l.own) {
-      // copy `slice` walks the point pairs slice, slice + slices, ...: pair e holds points 2e and 2e + 1 < kAgList
+      // copy `slice` walks the point pairs slice, slice + slices, ...: pair e holds points 2e and 2e + 1 < kFrontList
       for (uint32_t e = l.slice; 2u * e < cnt; e += l.slices) {
-        const ag_f32x4 v = s_pts[e];
+        const f32x4 v = s_pts[e];
         refine_point(v.x, v.y, l, k, fld, a);
         if (2u * e + 1u < cnt) refine_point(v.z, v.w, l, k, fld, a);
       }
@@ -193,7 +162,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_sums(
       a.n, a.dropped};
   // plane j of the group: P 64-bit words; the copies of a short list are added here first, one limb at a time
   u64 *plane = scratch + (size_t)g * kPlanes * P;
-  const bool writer = threadIdx.x < l.per && tile * kAgTile + threadIdx.x < P;
+  const bool writer = threadIdx.x < l.per && tile * kPoseTile + threadIdx.x < P;
 #pragma unroll
   for (uint32_t j = 0; j < kPlanes; ++j) {
     __syncthreads();
@@ -202,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void k_refine_sums(
     if (writer) {
       u64 sum = 0ull;
       for (uint32_t s = 0; s < l.slices; ++s) sum += s_sum[s * l.per + threadIdx.x];  // slices * per <= kBlock
-      if (sum) atomicAdd(&plane[(size_t)j * P + tile * kAgTile + threadIdx.x], sum);  // q < P: inside the plane
+      if (sum) atomicAdd(&plane[(size_t)j * P + tile * kPoseTile + threadIdx.x], sum);  // q < P: inside the plane
     }
   }
 }
@@ -233,9 +202,9 @@ __global__ __launch_bounds__(kPoseThreads) void k_refine_finish(uint32_t P, cons
     }
   }
   w[29] = w[30] = w[31] = 0u;
-  rf_u32x4 *out = reinterpret_cast<rf_u32x4 *>(sums + (size_t)g * sums_stride + 32u * (size_t)q);
+  u32x4 *out = reinterpret_cast<u32x4 *>(sums + (size_t)g * sums_stride + 32u * (size_t)q);
 #pragma unroll
-  for (uint32_t i = 0; i < 8u; ++i) out[i] = rf_u32x4{w[4u * i], w[4u * i + 1u], w[4u * i + 2u], w[4u * i + 3u]};
+  for (uint32_t i = 0; i < 8u; ++i) out[i] = u32x4{w[4u * i], w[4u * i + 1u], w[4u * i + 2u], w[4u * i + 3u]};
 }
 
 // grid G: the smallest q with the greatest S V (words 10 - 11 of a pose's sums)
@@ -303,15 +272,15 @@ __global__ __launch_bounds__(kPoseThreads) void k_refine_step(
   const uint32_t g = blockIdx.y;
   uint32_t flags = 0u;
   if (q < P) {
-    const rf_u32x4 *in = reinterpret_cast<const rf_u32x4 *>(sums + (size_t)g * sums_stride + 32u * (size_t)q);
+    const u32x4 *in = reinterpret_cast<const u32x4 *>(sums + (size_t)g * sums_stride + 32u * (size_t)q);
     uint32_t w[28];
 #pragma unroll
     for (uint32_t i = 0; i < 7u; ++i) {
-      const rf_u32x4 v = in[i];
+      const u32x4 v = in[i];
       w[4u * i] = v.x; w[4u * i + 1u] = v.y; w[4u * i + 2u] = v.z; w[4u * i + 3u] = v.w;
     }
-    const rf_u32x4 pose =
-        *reinterpret_cast<const rf_u32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride + 4u * (size_t)q);
+    const u32x4 pose =
+        *reinterpret_cast<const u32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride + 4u * (size_t)q);
     double dx = 0.0, dy = 0.0, dt = 0.0;
     if (w[27] < k.min_points) {
       flags = RPLGPU_REFINE_FEW;
@@ -346,7 +315,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_refine_step(
         flags = rf_finite(dx) && rf_finite(dy) && rf_finite(dt) ? RPLGPU_REFINE_STEPPED : RPLGPU_REFINE_SINGULAR;
       }
     }
-    rf_u32x4 out = pose;
+    u32x4 out = pose;
     float mx = 0.0f, my = 0.0f, mt = 0.0f;
     if (flags & RPLGPU_REFINE_STEPPED) {
       const double ms = (double)k.max_step_cells, mr = (double)k.max_rot;
@@ -372,10 +341,10 @@ __global__ __launch_bounds__(kPoseThreads) void k_refine_step(
       out.w = rf_canon(__fadd_rn(__uint_as_float(pose.w), my));
     }
     // q < P: inside the group's 4 P floats of out_stride, 4 P words of step_stride
-    *reinterpret_cast<rf_u32x4 *>(poses_out + (size_t)g * out_stride + 4u * (size_t)q) = out;
+    *reinterpret_cast<u32x4 *>(poses_out + (size_t)g * out_stride + 4u * (size_t)q) = out;
     if (step)
-      *reinterpret_cast<rf_u32x4 *>(step + (size_t)g * step_stride + 4u * (size_t)q) =
-          rf_u32x4{__float_as_uint(mx), __float_as_uint(my), __float_as_uint(mt), flags};
+      *reinterpret_cast<u32x4 *>(step + (size_t)g * step_stride + 4u * (size_t)q) =
+          u32x4{__float_as_uint(mx), __float_as_uint(my), __float_as_uint(mt), flags};
   }
   // result words 0 - 3: one popcount per wave (a thread without a pose has no flag)
   const u64 b0 = __ballot(flags & RPLGPU_REFINE_STEPPED), b1 = __ballot(flags & RPLGPU_REFINE_FEW);
@@ -402,8 +371,8 @@ __global__ __launch_bounds__(kPoseThreads) void k_match_poses(const uint32_t *__
   const int kr = (int)bw[1], j = (int)bw[2], i = (int)bw[3];
   const int K = (int)k.rot;
   const float px = pivot ? pivot[2u * (size_t)g] : 0.0f, py = pivot ? pivot[2u * (size_t)g + 1u] : 0.0f;
-  rf_u32x4 out = {__float_as_uint(1.0f), 0u, __float_as_uint(px), __float_as_uint(py)};
-  if (prior) out = *reinterpret_cast<const rf_u32x4 *>(prior + 4u * (size_t)g);
+  u32x4 out = {__float_as_uint(1.0f), 0u, __float_as_uint(px), __float_as_uint(py)};
+  if (prior) out = *reinterpret_cast<const u32x4 *>(prior + 4u * (size_t)g);
   if (kr >= -K && kr <= K) {  // (else a caller's error: the prior is kept, no table index leaves the table)
     const uint32_t kk = (uint32_t)(kr + K);
     const float c = rot.cs[2u * kk], s = rot.cs[2u * kk + 1u];
@@ -414,7 +383,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_match_poses(const uint32_t *__
     out.z = __float_as_uint(((c * qx - s * qy) + px) + (float)i * k.resolution);
     out.w = __float_as_uint(((s * qx + c * qy) + py) + (float)j * k.resolution);
   }
-  *reinterpret_cast<rf_u32x4 *>(poses_out + (size_t)g * out_stride) = out;
+  *reinterpret_cast<u32x4 *>(poses_out + (size_t)g * out_stride) = out;
 }
 
 // a thread per scan: pose q_g of the group's list composed in front of the scan's mount pose
@@ -434,8 +403,8 @@ __global__ __launch_bounds__(kPoseThreads) void k_compose_poses(const float *__r
     r00 = m[0]; r01 = m[1]; tx = m[2]; r10 = m[3]; r11 = m[4]; ty = m[5];
   }
   if (qg < P) {  // (else the mount pose is copied: no index leaves the list)
-    const ag_f32x4 v =
-        *reinterpret_cast<const ag_f32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride + 4u * (size_t)qg);
+    const f32x4 v =
+        *reinterpret_cast<const f32x4 *>(poses + (size_t)(poses_per_group ? g : 0u) * pose_stride + 4u * (size_t)qg);
     const float c = v.x, s = v.y;
     const float n00 = c * r00 - s * r10, n01 = c * r01 - s * r11;
     const float n10 = s * r00 + c * r10, n11 = s * r01 + c * r11;
@@ -473,8 +442,8 @@ hipError_t launch_refine_sums(hipStream_t s, const void *nodes, uint32_t n_strid
       pose_stride < 4ull * P || (pose_stride & 3u) || n_stride == 0 || n_stride > kMaxN || !scratch || !result)
     return hipErrorInvalidValue;
   // slices of a scan's passes, as launch_pose_score: at most two passes a workgroup
-  const uint32_t passes = (n_stride + kAgList - 1u) / kAgList;
-  const dim3 grid(B, (P + kAgTile - 1u) / kAgTile, std::min(passes, kMaxZ));
+  const uint32_t passes = (n_stride + kFrontList - 1u) / kFrontList;
+  const dim3 grid(B, (P + kPoseTile - 1u) / kPoseTile, std::min(passes, kMaxZ));
   if (p.fast_d4000)
     hipLaunchKernelGGL(k_refine_sums<true>, grid, dim3(kBlock), 0, s, (const uint2 *)nodes, n_stride, n_per_scan,
                        group, p, T, keepmask, mask_stride, motion, pose2d, k, poses, P, pose_stride, poses_per_group,

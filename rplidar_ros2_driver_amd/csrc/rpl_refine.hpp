@@ -1,6 +1,6 @@
 // rpl_refine.hpp — E25 (include/rplgpu_msg.h, rplgpu_refine_poses_dev): what rpl_refine.hip (the kernels) and
 // rplgpu_refine_stages.hip (the doors) share.  A round of sums is four launches on the stream and nothing on the
-// handle: prepare zeroes the scratch planes and the result words, sums walks the points (E23's front end, rpl_agree.hpp)
+// handle: prepare zeroes the scratch planes and the result words, sums walks the points (the shared front end, rpl_front.hpp)
 // and leaves through 64-bit integer atomics onto the planes, finish normalises the carries into the 32 words of a
 // pose, best makes result words 4 - 6.  The step is one launch more; the two joining kernels are one launch each.
 #pragma once

@@ -12,8 +12,8 @@
 //   k_wide_best     E13's tie rule over the listed blocks' candidates (the seeds' when the list is above the cap).
 //
 // k_wide_refine runs twice with the same fixed grid, over the seeds and over the list: the list's length stays on the
-// device.  The front end (a sample to its cell, runs of equal cells to one weighted list entry) is k_match_score's,
-// copied: rpl_match.hip keeps its own in an anonymous namespace.
+// device.  The front end (a sample to its cell, runs of equal cells to one weighted list entry) is k_match_score's:
+// rpl_front.hpp's scan_front and front_cell_pass, here with the wide bias and the reach of a block below the window.
 //
 // A group's scratch, in words (rplgpu_wide_match_scratch_words): [0, 8) counters, [8, 144) the list's first entry per
 // rotation, [144, 272) the seeds' 2 x 64 scores, [272, 272 + cap) the list, then 64 score words per list entry.
@@ -21,23 +21,19 @@
 
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
-#include "rpl_ray.hpp"  // run_behind; the cell rule (rpl_grid.hpp)
+#include "rpl_front.hpp"
 #include "rpl_wide.hpp"
-#include "rpl_xf.hpp"
 
 namespace rpl {
 namespace {
 
-typedef uint32_t wd_u32x4 __attribute__((ext_vector_type(4)));
-constexpr uint32_t kList = 2u * kBlock;  // entries per pass: two samples per thread
 constexpr int kS = (int)RPLGPU_WIDE_MATCH_BLOCK;
-constexpr int kCellBias = 320;           // cell + kCellBias > 0 for every listed cell: an entry is never 0
-constexpr uint32_t kCellBits = 13;       // -(256 + 7) .. 4096 + 255, biased, per axis
-constexpr uint32_t kCellMask = (1u << kCellBits) - 1u;
-constexpr int kMaxOwn = 5;               // blocks a thread owns when a rotation has more than kBlock (65 * 65 / 1024)
+constexpr int kCellBias = 320;  // cell + kCellBias > 0 for every listed cell: an entry is never 0
+constexpr int kMaxOwn = 5;      // blocks a thread owns when a rotation has more than kBlock (65 * 65 / 1024)
 static_assert(kS == 8, "a block is one wave of candidates: lane = 8 * (j in the block) + (i in the block)");
 static_assert(((2u * RPLGPU_MAX_WIDE_SHIFT + kS) / kS) * ((2u * RPLGPU_MAX_WIDE_SHIFT + kS) / kS) <=
                   (uint32_t)kMaxOwn * kBlock, "a rotation's blocks do not fit the registers of a workgroup");
+// -(256 + 7) .. 4096 + 255, biased, per axis
 static_assert(RPLGPU_MAX_OCC_DIM + RPLGPU_MAX_WIDE_SHIFT + kCellBias <= (1u << kCellBits), "cell bits");
 static_assert(RPLGPU_MAX_WIDE_SHIFT + kS - 1 < (uint32_t)kCellBias, "cell bias");
 
@@ -45,91 +41,6 @@ static_assert(RPLGPU_MAX_WIDE_SHIFT + kS - 1 < (uint32_t)kCellBias, "cell bias")
 constexpr uint32_t kHdrListed = 0, kHdrSeeds = 1, kHdrSeedAt = 2, kHdrUnproven = 4;
 constexpr uint32_t kRotAt = 8, kSeedScoresAt = 144, kListAt = 272;
 static_assert(kRotAt + 2u * RPLGPU_MAX_MATCH_ROT + 2u <= kSeedScoresAt, "the first entry per rotation, and the end");
-
-// One sample to its list word (biased cell, weight field 0), or 0: not kept, not finite, without a cell, or out of
-// the reach of every block's look-up into P (which covers every candidate's look-up into the field).
-template <bool FAST>
-__device__ __forceinline__ uint32_t wide_word(uint32_t lo, uint32_t hi, uint32_t i, bool kept,
-                                              const float2 *__restrict__ cs, const ScanXf &xf, const MatchK &k,
-                                              float c, float s, float px, float py, uint32_t *finite,
-                                              bool *cell_range) {
-  if (!kept) return 0u;
-  const f2 xy = sample_xy<FAST>(lo, hi, i, cs, xf);
-  if (!(fabsf(xy.x) < __builtin_huge_valf() && fabsf(xy.y) < __builtin_huge_valf())) return 0u;
-  *finite += 1u;
-  const float qx = xy.x - px, qy = xy.y - py;
-  const float rx = (c * qx - s * qy) + px;
-  const float ry = (s * qx + c * qy) + py;
-  int cx, cy;
-  if (!grid_cell(rx, ry, k.origin_x, k.origin_y, k.resolution, &cx, &cy)) {
-    *cell_range = true;
-    return 0u;
-  }
-  if (cx < -(int)k.tx - (kS - 1) || cx >= (int)(k.width + k.tx) || cy < -(int)k.ty - (kS - 1) ||
-      cy >= (int)(k.height + k.ty))
-    return 0u;
-  return ((uint32_t)(cy + kCellBias) << kCellBits) | (uint32_t)(cx + kCellBias);
-}
-
-// what a workgroup of the bound and of the refine kernel knows about its scan and rotation
-struct WideScan {
-  __amdgpu_buffer_rsrc_t rsrc;  // bounds-checked over the scan's n * 8 bytes
-  uint32_t n, q_min16;
-  ScanSide sd;
-  const float2 *cs;
-  float rc, rs, px, py;
-};
-
-// One pass of 2048 samples into the LDS list (k_match_score's, as it stands); every thread of the workgroup calls it.
-template <bool FAST>
-__device__ __forceinline__ void wide_list_pass(const WideScan &w, uint32_t base, const KParams &p, const MatchK &k,
-                                               uint32_t *s_list, uint32_t *cnt_at, uint32_t *finite,
-                                               bool *cell_range) {
-  if (threadIdx.x == 0) *cnt_at = 0u;
-  __syncthreads();  // (also: the last pass's readers are done with the list)
-  const uint32_t n = w.n;
-  const uint32_t pr = base / 2u + threadIdx.x;
-  if (2u * pr < n) {  // (the active lanes of a wave are its first ones: a lane's predecessor is active)
-    const wd_u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(w.rsrc, (int)(pr * 16u), 0, 0);
-    const uint32_t i0 = 2u * pr, i1 = i0 + 1u;
-    bool k0 = i0 < n && (__builtin_amdgcn_alignbit(t.y, t.x, 16) - p.d_lo) <= p.d_span &&
-              (t.y & 0x00FF0000u) >= w.q_min16;  // E1
-    bool k1 = i1 < n && (__builtin_amdgcn_alignbit(t.w, t.z, 16) - p.d_lo) <= p.d_span &&
-              (t.w & 0x00FF0000u) >= w.q_min16;
-    if (w.sd.ror_bits) {  // E1 AND E5 (launch_ror_mask); both samples sit in one word (i0 is even)
-      const uint32_t m = w.sd.ror_bits[i0 >> 5];
-      k0 = k0 && ((m >> (i0 & 31u)) & 1u);
-      k1 = k1 && ((m >> (i1 & 31u)) & 1u);
-    }
-    const uint32_t w0 =
-        wide_word<FAST>(t.x, t.y, i0, k0, w.cs, w.sd.xf, k, w.rc, w.rs, w.px, w.py, finite, cell_range);
-    const uint32_t w1 =
-        wide_word<FAST>(t.z, t.w, i1, k1, w.cs, w.sd.xf, k, w.rc, w.rs, w.px, w.py, finite, cell_range);
-    // A sample continues a run when it has the cell of the sample before it; sample 0 of lanes 0 and 32 never
-    // does, so a run holds at most 64 samples and its weight - 1 fits the six bits above the cell.
-    const uint32_t before = __shfl_up(w1, 1, 64);  // the word of sample i0 - 1
-    const bool e0 = w0 && (lane_id() & 31u) != 0u && w0 == before, e1 = w1 && w1 == w0;
-    const bool h0 = w0 && !e0, h1 = w1 && !e1;
-    const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1);
-    const unsigned long long c_first = __ballot(e0), c_both = c_first & __ballot(e1);
-    const uint32_t behind = run_behind(lane_id(), c_both, c_first);
-    const uint32_t wt0 = e1 ? 2u + behind : 1u, wt1 = 1u + behind;
-    const unsigned long long below = (1ull << lane_id()) - 1ull;
-    uint32_t at = 0u;
-    if (lane_id() == 0) at = atomicAdd(cnt_at, (uint32_t)(__popcll(m0) + __popcll(m1)));
-    at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at) + (uint32_t)(__popcll(m0 & below) + __popcll(m1 & below));
-    if (h0) s_list[at] = w0 | ((wt0 - 1u) << (2u * kCellBits));
-    if (h1) s_list[at + (h0 ? 1u : 0u)] = w1 | ((wt1 - 1u) << (2u * kCellBits));
-  }
-  __syncthreads();
-}
-
-// F(x, y): 0 outside the grid and for an unknown (negative) byte
-__device__ __forceinline__ uint32_t field_look(const int8_t *__restrict__ field, int x, int y, uint32_t W, uint32_t H) {
-  if ((uint32_t)x >= W || (uint32_t)y >= H) return 0u;
-  const int v = field[(uint32_t)y * W + (uint32_t)x];
-  return (uint32_t)max(v, 0);
-}
 
 // P(x, y): 0 where P is not defined
 __device__ __forceinline__ uint32_t pooled_look(const int8_t *__restrict__ pooled, int x, int y, uint32_t Wp,
@@ -139,14 +50,6 @@ __device__ __forceinline__ uint32_t pooled_look(const int8_t *__restrict__ poole
   const int v = pooled[(uint32_t)ay * Wp + (uint32_t)ax];
   return (uint32_t)max(v, 0);
 }
-
-#define WIDE_SCAN_SETUP()                                                                                      \
-  const uint32_t sc = blockIdx.x;                                                                              \
-  const uint32_t kk = blockIdx.y; /* k + K */                                                                  \
-  const uint32_t g = sc / group;                                                                               \
-  const uint32_t n_in = n_per_scan[sc];                                                                        \
-  WideScan ws;                                                                                                 \
-  ws.n = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(n_in, min(n_stride, kMaxN)));
 
 // ---- the pooled field -------------------------------------------------------------------------------------------------
 constexpr int kPoolTile = 32, kPoolIn = kPoolTile + kS - 1, kPoolThreads = 256;
@@ -213,23 +116,20 @@ __global__ __launch_bounds__(kBlock) void k_wide_bound(
     MatchRot rot, const int8_t *__restrict__ pooled, unsigned long long pooled_stride, uint32_t field_per_group,
     uint32_t *__restrict__ bounds, unsigned long long bounds_stride, uint32_t *__restrict__ best,
     uint32_t *__restrict__ status) {
-  __shared__ uint32_t s_list[kList];
+  __shared__ uint32_t s_list[kFrontList];
   __shared__ uint32_t s_sum[kBlock];
   __shared__ uint32_t s_cnt[2];  // the list's length, by the pass's parity: a reset never meets a late reader
   const MatchK &k = wk.k;
-  WIDE_SCAN_SETUP();
-  const uint32_t n = ws.n;
+  const uint32_t sc = blockIdx.x;
+  const uint32_t kk = blockIdx.y;  // k + K
+  const uint32_t g = sc / group;
+  const uint32_t n_in = n_per_scan[sc];
+  const uint32_t n = scan_len(n_in, n_stride);
   const bool first_of_scan = kk == 0u && blockIdx.z == 0u;
   if (threadIdx.x == 0 && status && first_of_scan && n_in > n) atomicOr(&status[g], RPLGPU_SCAN_OUT_TRUNCATED);
-  if (blockIdx.z * kList >= n) return;  // (block-uniform)
-  ws.sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
-  ws.cs = p.inverted ? T.cs_inv : T.cs;
-  ws.q_min16 = p.clip_enable ? (min(p.q_min, 256u) << 16) : 0u;
-  ws.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(nodes + (size_t)sc * n_stride), 0, (int)(n * 8u), 0x00020000);
-  ws.rc = rot.cs[2u * kk];
-  ws.rs = rot.cs[2u * kk + 1u];
-  ws.px = pivot ? pivot[2u * g] : 0.0f;
-  ws.py = pivot ? pivot[2u * g + 1u] : 0.0f;
+  if (blockIdx.z * kFrontList >= n) return;  // (block-uniform)
+  const ScanFront f = scan_front(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
+  const CellRot cr = cell_rot(rot, kk, pivot, g);
   const int8_t *pl = pooled + (size_t)(field_per_group ? g : 0u) * pooled_stride;
   const uint32_t Wp = k.width + (uint32_t)kS - 1u, Hp = k.height + (uint32_t)kS - 1u;
   // the blocks of this thread: position c = bj * nbx + bi in the rotation, copy `slice` of `slices`
@@ -252,10 +152,12 @@ __global__ __launch_bounds__(kBlock) void k_wide_bound(
   uint32_t finite = 0u;
   bool cell_range = false;
   uint32_t pass = 0u;
-  for (uint32_t base = blockIdx.z * kList; base < n; base += gridDim.z * kList) {
+  for (uint32_t base = blockIdx.z * kFrontList; base < n; base += gridDim.z * kFrontList) {
     uint32_t *cnt_at = &s_cnt[pass++ & 1u];
-    wide_list_pass<FAST>(ws, base, p, k, s_list, cnt_at, &finite, &cell_range);
-    const uint32_t cnt = *cnt_at;  // <= kList
+    // (a cell up to kS - 1 below the window is still in the reach of a block's look-up into P, and that look-up
+    // covers the look-ups of the block's candidates into the field)
+    front_cell_pass<FAST, kCellBias, kS - 1>(f, base, p, k, cr, s_list, cnt_at, &finite, &cell_range);
+    const uint32_t cnt = *cnt_at;  // <= kFrontList
     if (!wide) {
       if (own[0]) {
 #pragma unroll 4
@@ -375,12 +277,14 @@ __global__ __launch_bounds__(kBlock) void k_wide_refine(
     const float *__restrict__ motion, const float *__restrict__ pose2d, const float *__restrict__ pivot, WideK wk,
     MatchRot rot, const int8_t *__restrict__ field, unsigned long long field_stride, uint32_t field_per_group,
     uint32_t *__restrict__ scratch, unsigned long long scratch_stride, uint32_t seeds) {
-  __shared__ uint32_t s_list[kList];
+  __shared__ uint32_t s_list[kFrontList];
   __shared__ uint32_t s_cnt[2];
   const MatchK &k = wk.k;
-  WIDE_SCAN_SETUP();
-  const uint32_t n = ws.n;
-  if (blockIdx.z * kList >= n) return;  // (block-uniform)
+  const uint32_t sc = blockIdx.x;
+  const uint32_t kk = blockIdx.y;  // k + K
+  const uint32_t g = sc / group;
+  const uint32_t n = scan_len(n_per_scan[sc], n_stride);
+  if (blockIdx.z * kFrontList >= n) return;  // (block-uniform)
   uint32_t *sg = scratch + (size_t)g * scratch_stride;
   const uint32_t nb = wk.nbx * wk.nby;
   // the entries [e0, e1) of this workgroup's rotation (block-uniform)
@@ -404,23 +308,19 @@ __global__ __launch_bounds__(kBlock) void k_wide_refine(
     e1 = min(sg[kRotAt + kk + 1u], listed);
     if (e0 >= e1) return;
   }
-  ws.sd = scan_side(sc, keepmask, mask_stride, motion, pose2d, T.scan_t0);
-  ws.cs = p.inverted ? T.cs_inv : T.cs;
-  ws.q_min16 = p.clip_enable ? (min(p.q_min, 256u) << 16) : 0u;
-  ws.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(nodes + (size_t)sc * n_stride), 0, (int)(n * 8u), 0x00020000);
-  ws.rc = rot.cs[2u * kk];
-  ws.rs = rot.cs[2u * kk + 1u];
-  ws.px = pivot ? pivot[2u * g] : 0.0f;
-  ws.py = pivot ? pivot[2u * g + 1u] : 0.0f;
+  const ScanFront f = scan_front(nodes, n_stride, sc, n, p, T, keepmask, mask_stride, motion, pose2d);
+  const CellRot cr = cell_rot(rot, kk, pivot, g);
   const int8_t *fld = field + (size_t)(field_per_group ? g : 0u) * field_stride;
   const uint32_t W = k.width, H = k.height;
   uint32_t finite = 0u;  // (the bound kernel has counted them)
   bool cell_range = false;
   uint32_t pass = 0u;
-  for (uint32_t base = blockIdx.z * kList; base < n; base += gridDim.z * kList) {
+  for (uint32_t base = blockIdx.z * kFrontList; base < n; base += gridDim.z * kFrontList) {
     uint32_t *cnt_at = &s_cnt[pass++ & 1u];
-    wide_list_pass<FAST>(ws, base, p, k, s_list, cnt_at, &finite, &cell_range);
-    const uint32_t cnt = *cnt_at;  // <= kList
+    // (a cell up to kS - 1 below the window is still in the reach of a block's look-up into P, and that look-up
+    // covers the look-ups of the block's candidates into the field)
+    front_cell_pass<FAST, kCellBias, kS - 1>(f, base, p, k, cr, s_list, cnt_at, &finite, &cell_range);
+    const uint32_t cnt = *cnt_at;  // <= kFrontList
     for (uint32_t e = e0 + wave_id(); e < e1; e += (uint32_t)kWaves) {  // one wave per block of 64 candidates
       const uint32_t v = list[e];
       if (v / nb != kk) continue;  // (a seed of another rotation; wave-uniform)
@@ -599,7 +499,7 @@ hipError_t launch_wide_prepare(hipStream_t s, uint32_t *bounds, unsigned long lo
 namespace {
 dim3 wide_scan_grid(uint32_t B, uint32_t n_stride, const WideK &wk) {
   // slices of a scan's passes, as launch_match_score
-  const uint32_t passes = (min(n_stride, kMaxN) + kList - 1u) / kList;
+  const uint32_t passes = (min(n_stride, kMaxN) + kFrontList - 1u) / kFrontList;
   return dim3(B, 2u * wk.k.rot + 1u, min(passes, 8u));
 }
 }  // namespace

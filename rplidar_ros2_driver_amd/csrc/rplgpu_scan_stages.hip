@@ -714,19 +714,7 @@ void rplgpu_default_scan_match(rplgpu_scan_match_t *m) {
 }
 
 int32_t rplgpu_scan_match_check(const rplgpu_scan_match_t *m) {
-  if (!m) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(m->origin_x) || !std::isfinite(m->origin_y) || !std::isfinite(m->resolution) ||
-      !std::isfinite(m->rot_step))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (!(m->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
-  if (m->width == 0 || m->width > RPLGPU_MAX_OCC_DIM || m->height == 0 || m->height > RPLGPU_MAX_OCC_DIM)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (m->shift_x > RPLGPU_MAX_MATCH_SHIFT || m->shift_y > RPLGPU_MAX_MATCH_SHIFT ||
-      m->rot_steps > RPLGPU_MAX_MATCH_ROT)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (m->rot_steps > 0 && (!(m->rot_step > 0.0f) || (double)m->rot_steps * (double)m->rot_step > M_PI / 2.0))
-    return RPLGPU_ERR_INVALID_ARG;
-  return RPLGPU_OK;
+  return rpl::match_spec_check(m, RPLGPU_MAX_MATCH_SHIFT);
 }
 
 int32_t rplgpu_scan_match_rotations(const rplgpu_scan_match_t *m, float *cs) {

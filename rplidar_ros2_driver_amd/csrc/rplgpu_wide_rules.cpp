@@ -10,6 +10,7 @@
 
 #include "rplgpu.h"
 #include "rplgpu_msg.h"
+#include "rpl_rules.hpp"
 
 extern "C" {
 
@@ -27,19 +28,10 @@ void rplgpu_default_wide_match(rplgpu_wide_match_t *m) {
   m->max_blocks = 1024;
 }
 
-// E13's check (rplgpu_scan_match_check) with the wide limits; written out, because that one lives in a HIP unit
+// E13's check (rpl_rules.hpp's match_spec_check) with the wide shift limit, and the cap of the list
 int32_t rplgpu_wide_match_check(const rplgpu_wide_match_t *m) {
-  if (!m) return RPLGPU_ERR_INVALID_ARG;
-  if (!std::isfinite(m->origin_x) || !std::isfinite(m->origin_y) || !std::isfinite(m->resolution) ||
-      !std::isfinite(m->rot_step))
-    return RPLGPU_ERR_INVALID_ARG;
-  if (!(m->resolution > 0.0f)) return RPLGPU_ERR_INVALID_ARG;
-  if (m->width == 0 || m->width > RPLGPU_MAX_OCC_DIM || m->height == 0 || m->height > RPLGPU_MAX_OCC_DIM)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (m->shift_x > RPLGPU_MAX_WIDE_SHIFT || m->shift_y > RPLGPU_MAX_WIDE_SHIFT || m->rot_steps > RPLGPU_MAX_MATCH_ROT)
-    return RPLGPU_ERR_INVALID_ARG;
-  if (m->rot_steps > 0 && (!(m->rot_step > 0.0f) || (double)m->rot_steps * (double)m->rot_step > M_PI / 2.0))
-    return RPLGPU_ERR_INVALID_ARG;
+  const int32_t rc = rpl::match_spec_check(m, RPLGPU_MAX_WIDE_SHIFT);
+  if (rc != RPLGPU_OK) return rc;
   if (m->max_blocks == 0 || m->max_blocks > RPLGPU_MAX_WIDE_BLOCKS) return RPLGPU_ERR_INVALID_ARG;
   return RPLGPU_OK;
 }

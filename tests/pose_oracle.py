@@ -18,7 +18,7 @@ F32 = np.float32
 MAX_DIM = 4096
 MAX_POSES = 1 << 20
 SCAN_CELL_RANGE = 0x2
-TILE = 1024  # poses per workgroup, threads per workgroup (csrc/rpl_pose.hip: kTile = kBlock)
+TILE = 1024  # poses per workgroup, threads per workgroup (csrc/rpl_front.hpp: kPoseTile = kBlock)
 DEFAULT = dict(origin_x=-25.6, origin_y=-25.6, resolution=0.05, width=1024, height=1024)
 
 

@@ -79,13 +79,16 @@ def test_pose_list():
 
 
 def test_layout_formula_is_the_kernels():
-    """A tripwire and no more: tests/pose_oracle.layout restates two lines of csrc/rpl_pose.hip, and this test only
-    notices when those lines are edited, so that the restatement is looked at again.  It proves nothing about the
-    compiled kernel; tests/test_gpu_pose.py::test_layouts over every P of LAYOUT_P is what holds the formula."""
-    src = (Path(__file__).resolve().parent.parent / "rplidar_ros2_driver_amd" / "csrc" / "rpl_pose.hip").read_text()
-    assert "const uint32_t per = min((P + 63u) & ~63u, (uint32_t)kTile);" in src
-    assert "const uint32_t slices = P <= (uint32_t)kTile ? (uint32_t)kTile / per : 1u;" in src
-    assert re.search(r"constexpr uint32_t kTile = kBlock;", src)
+    """A tripwire and no more: tests/pose_oracle.layout restates two lines of pose_lane in csrc/rpl_front.hpp (the one
+    copy E15, E23 and E25 call), and this test only notices when those lines are edited, so that the restatement is
+    looked at again.  It proves nothing about the compiled kernel; tests/test_gpu_pose.py::test_layouts over every P
+    of LAYOUT_P is what holds the formula."""
+    csrc = Path(__file__).resolve().parent.parent / "rplidar_ros2_driver_amd" / "csrc"
+    src = (csrc / "rpl_front.hpp").read_text()
+    assert "l.per = min((P + 63u) & ~63u, kPoseTile);" in src
+    assert "l.slices = P <= kPoseTile ? kPoseTile / l.per : 1u;" in src
+    assert re.search(r"constexpr uint32_t kPoseTile = kBlock;", src)
+    assert "pose_lane(tile, P, " in (csrc / "rpl_pose.hip").read_text()
     dev = (Path(__file__).resolve().parent.parent / "rplidar_ros2_driver_amd" / "csrc" / "rpl_device.hpp").read_text()
     assert int(re.search(r"constexpr int kBlock = (\d+);", dev).group(1)) == po.TILE
 
