@@ -26,6 +26,14 @@
 //     exactly (phase P5).
 // Timestamps are not produced: the reference stamps nodes with the wall clock of the decoding
 // host (dataunpacker.cpp:164-166), not with anything in the stream.
+//
+// How the unit is laid out:
+//   DecCfg<ANS>, dec_is_capsule / dec_is_filtered   sizes and the answer-type predicates, stated once
+//   DecSrc<STG>, DecodeLds<ANS, STG>, DecFuse        where a workgroup reads from, its LDS, the fused outputs
+//   capsule_step, capsule_angle_inc, raw_sync,
+//   with_sync_flag, store_node_pair                  capsule rules shared by the kernel's phases
+//   k_decode                                         one body, phases P1 .. P5 as blocks and lambdas
+//   dispatch_ans, DecodeLaunch -> dec_launch_kernel  one switch over the answer type, one expansion of the parameters
 #include <type_traits>
 
 #include <mutex>
@@ -45,10 +53,22 @@ constexpr uint32_t kDecMaxFrames = RPL_DEC_MAXFRAMES;     // frames of one strea
 constexpr uint32_t kUdMaxFrames = 512;       // ultra-dense: 64 nodes each -> 32768 LDS slots
 // LDS is sized per answer type so that several streams share a CU (a 32 000-sample DenseBoost
 // scan is 800 frames): dense 25 KiB, express / ultra 16 KiB, HQ 34 KiB, ultra-dense 24 KiB
+// The answer-type predicates, stated once for host and device.  Capsule types: a node needs the
+// start angles of two neighbouring frames; their sync bits follow from the capsule headers alone,
+// so they are also the types the fused and the LDS-staged instances exist for.  Filtered types:
+// the raw sync bits go through s_i = r_i & ~s_{i-1}.
+__host__ __device__ constexpr bool dec_is_capsule(int ans) {
+  return ans == RPLGPU_ANS_CAPSULED || ans == RPLGPU_ANS_CAPSULED_ULTRA ||
+         ans == RPLGPU_ANS_DENSE_CAPSULED || ans == RPLGPU_ANS_ULTRA_DENSE_CAPSULED;
+}
+__host__ __device__ constexpr bool dec_is_filtered(int ans) {
+  return ans == RPLGPU_ANS_DENSE_CAPSULED || ans == RPLGPU_ANS_ULTRA_DENSE_CAPSULED;
+}
+
 template <int ANS>
 struct DecCfg {
-  static constexpr bool kFiltered =
-      ANS == RPLGPU_ANS_DENSE_CAPSULED || ANS == RPLGPU_ANS_ULTRA_DENSE_CAPSULED;
+  static constexpr bool kCaps = dec_is_capsule(ANS);
+  static constexpr bool kFiltered = dec_is_filtered(ANS);
   // legacy 5-byte nodes carry no inter-frame state and always publish: no frame table at all
   static constexpr bool kTable = ANS != RPLGPU_ANS_MEASUREMENT;
   static constexpr uint32_t kMaxFrames = !kTable ? 0x7FFFFFFFu
@@ -75,9 +95,7 @@ struct DecCfg {
   // scan boundaries are known before the payload is decoded and the nodes of completed scans
   // can be written straight into batch slots (k_decode<..., FUSE = true>); up to kFuseSyn sync
   // nodes and kFuseRst reset requests per stream and call, else the unfused path takes over
-  static constexpr bool kFusable = ANS == RPLGPU_ANS_CAPSULED || ANS == RPLGPU_ANS_CAPSULED_ULTRA ||
-                                   ANS == RPLGPU_ANS_DENSE_CAPSULED ||
-                                   ANS == RPLGPU_ANS_ULTRA_DENSE_CAPSULED;
+  static constexpr bool kFusable = kCaps;
   static constexpr uint32_t kFuseSyn = kFusable ? 256u : 1u, kFuseRst = kFusable ? 64u : 1u;
   static constexpr uint32_t kStageWords = ANS == RPLGPU_ANS_HQ ? (kDecBlock / 64) * 64 * 17 : 1u;
 };
@@ -161,8 +179,7 @@ __host__ __device__ inline DecStageLayout dec_stage_layout(int ans, uint32_t mf)
   DecStageLayout l;
   // (+16: the re-aligning reads of the last bytes look a dword or two further)
   l.raw_at = ((mf * dec_frame_size(ans) + 15u) & ~15u) + 16u;
-  const bool filtered = ans == RPLGPU_ANS_DENSE_CAPSULED || ans == RPLGPU_ANS_ULTRA_DENSE_CAPSULED;
-  l.raw_words = filtered ? (mf * dec_nodes_per_frame(ans) + 63u) / 64u : 0u;
+  l.raw_words = dec_is_filtered(ans) ? (mf * dec_nodes_per_frame(ans) + 63u) / 64u : 0u;
   l.frame_at = l.raw_at + 8u * l.raw_words;
   l.emit_at = l.frame_at + 4u * mf;
   l.total = (l.emit_at + 2u * mf + 15u) & ~15u;
@@ -320,6 +337,120 @@ struct DecFuse {
   uint32_t *stage_todo;
 };
 
+// ---- developer aids: compiled out unless the unit is built with -DRPL_DEC_DBG / -DRPL_DEC_NOSTORE ----
+#ifdef RPL_DEC_DBG
+constexpr bool kDecDbg = true;
+#else
+constexpr bool kDecDbg = false;
+#endif
+#ifdef RPL_DEC_NOSTORE
+constexpr bool kDecNoStore = true;
+#else
+constexpr bool kDecNoStore = false;
+#endif
+
+// Phase cycle counters (tools/dev/decbench.py with DEC_DBG=1 reads them out of the reset_at slots 2..11);
+// empty unless DBG.  A stamp / lap is taken behind a barrier of its own, so that a phase's slowest wave counts.
+template <bool DBG>
+struct DecClock {
+  unsigned long long begin = 0, t[7] = {0, 0, 0, 0, 0, 0, 0}, mark = 0, p3 = 0, p5 = 0;
+  unsigned long long ud[4] = {0, 0, 0, 0}, u0 = 0;  // ultra-dense: walk, map scan, second walk, final decode
+  __device__ __forceinline__ void start() {
+    if (DBG) begin = __builtin_amdgcn_s_memtime();
+  }
+  __device__ __forceinline__ void stamp(int i, bool barrier = true) {
+    if (DBG) {
+      if (barrier) __syncthreads();
+      t[i] = mark = __builtin_amdgcn_s_memtime();
+    }
+  }
+  // (ultra-dense: P3 / P5 alternate chunk by chunk; the clocks accumulate each)
+  __device__ __forceinline__ void lap(unsigned long long &acc) {
+    if (DBG) {
+      __syncthreads();
+      const unsigned long long now = __builtin_amdgcn_s_memtime();
+      acc += now - mark;
+      mark = now;
+    }
+  }
+  __device__ __forceinline__ void ud_start() {
+    if (DBG) u0 = __builtin_amdgcn_s_memtime();
+  }
+  __device__ __forceinline__ void ud_lap(int i, bool barrier = true) {
+    if (DBG) {
+      if (barrier) __syncthreads();
+      const unsigned long long now = __builtin_amdgcn_s_memtime();
+      ud[i] += now - u0;
+      u0 = now;
+    }
+  }
+  // (slot "P4" = 0, slot "P5" = the smoothing passes; the sync filter goes uncounted)
+  __device__ __forceinline__ void report(uint32_t *row, uint32_t reset_stride) {
+    if (DBG && row && reset_stride >= 8) {
+      t[3] = t[2] + p3;
+      t[4] = t[3];
+      t[5] = t[4] + p5;
+      for (int d = 0; d < 5; ++d) row[3 + d] = (uint32_t)(t[d + 1] - t[d]);
+      row[2] = (uint32_t)(t[0] - begin);
+      if (reset_stride >= 16)
+        for (int d = 0; d < 4; ++d) row[8 + d] = (uint32_t)ud[d];
+    }
+  }
+};
+
+// RPL_DEC_NOSTORE: the kernel without its node stores (the nodes still have to be computed)
+template <uint32_t G>
+__device__ __forceinline__ bool dec_nostore_skip(const uint2 (&nd)[G], uint32_t rs) {
+  if (!kDecNoStore) return false;
+  uint32_t hsh = rs;
+#pragma unroll
+  for (uint32_t j = 0; j < G; ++j) hsh = hsh * 31u + nd[j].x + nd[j].y;
+  return hsh != 0xDEADBEEFu;
+}
+
+// ---- capsule rules that have to agree bit for bit with the reference, kept as functions of values ----
+// (a helper that takes the kernel's locals or arrays by reference changes the code of every instance:
+// profiles/r32/decode_phases_r32.txt; what that ruled out is listed there)
+// The angle step between two neighbouring capsules, from their frame-table words (start angle Q6 in
+// bits 0..14), in Q8.  Signed arithmetic throughout, as in the reference: a corrupted-but-checksummed
+// start angle above 360 deg makes the step (and everything derived from it) negative.
+struct CapsuleStep {
+  int prev_q8, diff_q8;
+};
+__device__ __forceinline__ CapsuleStep capsule_step(uint32_t rec_prev, uint32_t rec_cur) {
+  const int cur_q8 = (int)(rec_cur & 0x7FFFu) << 2, prev_q8 = (int)(rec_prev & 0x7FFFu) << 2;
+  int diff = cur_q8 - prev_q8;
+  if (prev_q8 > cur_q8) diff += (360 << 8);
+  return {prev_q8, diff};
+}
+// the angle between two nodes of a capsule (Q16) from the step between two capsules, per answer type
+template <int ANS>
+__device__ __forceinline__ int capsule_angle_inc(int diff_q8) {
+  return ANS == RPLGPU_ANS_CAPSULED         ? diff_q8 << 3
+         : ANS == RPLGPU_ANS_CAPSULED_ULTRA ? (diff_q8 << 3) / 3
+         : ANS == RPLGPU_ANS_DENSE_CAPSULED ? (diff_q8 << 8) / 40
+                                            : (diff_q8 << 8) / 64;
+}
+// a node's raw sync bit: ((angle + step) mod 360 deg) < step (dense types: 2 x step), :246-257 and siblings
+template <int ANS>
+__device__ __forceinline__ uint32_t raw_sync(int ang, int inc) {
+  return (((ang + inc) % (360 << 16)) < (dec_is_filtered(ANS) ? inc * 2 : inc)) ? 1u : 0u;
+}
+// two nodes as one 16-byte store.  STREAM: non-temporal (the node stream is written once and read by a
+// later kernel; -5 % dense, -13 % express, -6 % HQ).  Not for ultra: its 48 bytes per lane complete a
+// cache line over three instructions, and streaming stores that leave lines half written cost it +46 %.
+template <bool STREAM>
+__device__ __forceinline__ void store_node_pair(uint2 *dst, uint2 a, uint2 b) {
+  typedef uint32_t nt_u32x4 __attribute__((ext_vector_type(4), aligned(8)));
+  const nt_u32x4 v = {a.x, a.y, b.x, b.y};
+  if (STREAM) __builtin_nontemporal_store(v, reinterpret_cast<nt_u32x4 *>(dst));
+  else *reinterpret_cast<nt_u32x4 *>(dst) = v;
+}
+// flag byte of a node whose filtered sync bit is set: sync | (!sync << 1) : 2 -> 1
+__device__ __forceinline__ uint32_t with_sync_flag(uint32_t node_y) {
+  return (node_y & 0x00FFFFFFu) | (1u << 24);
+}
+
 // FRAMED: frame offsets (and gaps) given; else back to back.  STG: the workgroup (NT threads) copies
 // its stream into LDS first and decodes from there (see the head of the kernel).
 template <int ANS, bool FRAMED, bool FUSE, bool STG = false, int NT = kDecBlock>
@@ -334,9 +465,7 @@ __global__ __launch_bounds__(NT) void k_decode(
   static_assert(!FUSE || DecCfg<ANS>::kFusable, "FUSE: the four capsule types only");
   constexpr uint32_t S = dec_frame_size(ANS);
   constexpr uint32_t NPF = dec_nodes_per_frame(ANS);
-  constexpr bool CAPS = ANS == RPLGPU_ANS_CAPSULED || ANS == RPLGPU_ANS_CAPSULED_ULTRA ||
-                        ANS == RPLGPU_ANS_DENSE_CAPSULED || ANS == RPLGPU_ANS_ULTRA_DENSE_CAPSULED;
-  constexpr bool FILTERED = ANS == RPLGPU_ANS_DENSE_CAPSULED || ANS == RPLGPU_ANS_ULTRA_DENSE_CAPSULED;
+  constexpr bool CAPS = DecCfg<ANS>::kCaps, FILTERED = DecCfg<ANS>::kFiltered;
   constexpr uint32_t SA_OFF = ANS == RPLGPU_ANS_ULTRA_DENSE_CAPSULED ? 8u : 2u;
   __shared__ DecodeLds<ANS, STG> L;
 
@@ -361,9 +490,8 @@ __global__ __launch_bounds__(NT) void k_decode(
     if (STG && FRAMED) return k * S + ((Lframe_[k] >> 16) & 0x3FFFu);
     return FRAMED ? foff[k] : k * S;
   };
-#ifdef RPL_DEC_DBG
-  const unsigned long long dbg_start = __builtin_amdgcn_s_memtime();
-#endif
+  DecClock<kDecDbg> clk;
+  clk.start();
   // STG: the dynamic part of the workgroup's LDS = [the stream's bytes | raw sync bits | frame table |
   // emit list], the three tables sized by the call's max_frames (dec_stage_layout, shared with the
   // launcher).  While other workgroups of the CU have node stores in flight every global load of
@@ -447,10 +575,7 @@ __global__ __launch_bounds__(NT) void k_decode(
   if (n_frames[b] > nf && tid == 0) L.misc[0] = RPLGPU_STREAM_FRAMES_TRUNCATED;
   __syncthreads();
 
-#ifdef RPL_DEC_DBG
-  unsigned long long dbg_t[7];
-  dbg_t[0] = __builtin_amdgcn_s_memtime();
-#endif
+  clk.stamp(0, false);
   // ---- P1: per frame: framing check (unframed input only), checksum, header word ---------
   uint32_t my_err = 0, unframed = 0;
   if (ANS == RPLGPU_ANS_HQ) {  // handler_hqnode.cpp:99-172, a wave per 64 frames
@@ -576,10 +701,7 @@ __global__ __launch_bounds__(NT) void k_decode(
   }
   const bool bad_framing = (L.misc[0] & RPLGPU_STREAM_UNFRAMED) != 0u;
 
-#ifdef RPL_DEC_DBG
-  __syncthreads();
-  dbg_t[1] = __builtin_amdgcn_s_memtime();
-#endif
+  clk.stamp(1);
   // ---- P2: which frames publish, node offsets, reset requests ------------------------------
   // (loop over chunks of 256 frames with a running carry)
   uint32_t carry_nodes = 0, carry_emit = 0, carry_reset = 0;
@@ -601,12 +723,8 @@ __global__ __launch_bounds__(NT) void k_decode(
         const bool prev_ok = k > 0 && (Lframe[k - 1] >> 31) && !gap_k;
         if (prev_ok && !resets) {
           emits = 1;
-          if (FILTERED) {  // :750-754 / :971-975: too large an angle step -> discard
-            const int cur_q8 = (int)(rec & 0x7FFFu) << 2, prev_q8 = (int)(Lframe[k - 1] & 0x7FFFu) << 2;
-            int diff = cur_q8 - prev_q8;
-            if (prev_q8 > cur_q8) diff += (360 << 8);
-            if (diff > thr_q8) emits = 0;
-          }
+          // :750-754 / :971-975: too large an angle step -> discard
+          if (FILTERED && capsule_step(Lframe[k - 1], rec).diff_q8 > thr_q8) emits = 0;
         }
       }
     }
@@ -676,7 +794,6 @@ __global__ __launch_bounds__(NT) void k_decode(
                       : ANS == RPLGPU_ANS_CAPSULED_ULTRA ? (diff_q8 << 3) / 3
                       : ANS == RPLGPU_ANS_DENSE_CAPSULED ? (diff_q8 << 8) / 40
                                                          : (diff_q8 << 8) / 64;
-      const int lim = FILTERED ? inc * 2 : inc;
       auto mark = [&](uint32_t pos) {
         const uint32_t i = e * NPF + pos;
         if (FILTERED) {
@@ -702,8 +819,7 @@ __global__ __launch_bounds__(NT) void k_decode(
         if (FILTERED && j0 + 1u <= NPF) mark(j0);
       } else {
         for (uint32_t pos = 0; pos < NPF; ++pos) {
-          const int ang = A + (int)pos * inc;
-          if (((ang + inc) % kTurn) < lim) mark(pos);
+          if (raw_sync<ANS>(A + (int)pos * inc, inc)) mark(pos);
         }
       }
     }
@@ -757,12 +873,7 @@ __global__ __launch_bounds__(NT) void k_decode(
     __syncthreads();
   }
 
-#ifdef RPL_DEC_DBG
-  __syncthreads();
-  dbg_t[2] = __builtin_amdgcn_s_memtime();
-  unsigned long long dbg_p3 = 0, dbg_p5 = 0, dbg_mark = dbg_t[2];
-  unsigned long long dbg_ud[4] = {0, 0, 0, 0}, dbg_u0 = 0;  // ultra-dense: walk, map scan, second walk, final decode
-#endif
+  clk.stamp(2);
   // ---- P3: the nodes ----------------------------------------------------------------------
   // A lane decodes G consecutive nodes of ONE frame: the per-frame arithmetic (table look-ups,
   // angle step, the divisions) is paid once per group, the payload arrives in one or two wide
@@ -822,10 +933,9 @@ __global__ __launch_bounds__(NT) void k_decode(
     if (CAPS) {
       // signed arithmetic throughout, as in the reference: a corrupted-but-checksummed start
       // angle above 360 deg makes the step (and everything derived from it) negative
-      const int cur_q8 = (int)(Lframe[k] & 0x7FFFu) << 2;
-      g.prev_q8 = (int)(Lframe[k - 1] & 0x7FFFu) << 2;
-      g.diff_q8 = cur_q8 - g.prev_q8;
-      if (g.prev_q8 > cur_q8) g.diff_q8 += (360 << 8);
+      const CapsuleStep cs = capsule_step(Lframe[k - 1], Lframe[k]);
+      g.prev_q8 = cs.prev_q8;
+      g.diff_q8 = cs.diff_q8;
     }
   };
   auto fetch = [&](GroupIn &g) {  // the payload loads (nothing here waits for another load)
@@ -880,7 +990,7 @@ __global__ __launch_bounds__(NT) void k_decode(
 #pragma unroll
       for (uint32_t j = 0; j < G; ++j) rs |= ((nd[j].y >> 24) & 1u) << j;
     } else if (ANS == RPLGPU_ANS_CAPSULED) {  // :206-260 — two cabins of 5 bytes = 4 nodes
-      const int inc = diff_q8 << 3;
+      const int inc = capsule_angle_inc<ANS>(diff_q8);
       const uint64_t cab[2] = {g.w & 0xFFFFFFFFFFull, (g.w >> 40) | ((uint64_t)g.w2 << 24)};
 #pragma unroll
       for (uint32_t j = 0; j < G; ++j) {
@@ -891,12 +1001,12 @@ __global__ __launch_bounds__(NT) void k_decode(
         const int dist = (int)(da & 0xFFFCu);
         const int aoff = (int)(((j & 1u) ? (offs >> 4) : (offs & 0xFu)) | ((da & 0x3u) << 4));
         const int angle_q6 = (ang - (aoff << 13)) >> 10;
-        const uint32_t sync = (((ang + inc) % (360 << 16)) < inc) ? 1u : 0u;
+        const uint32_t sync = raw_sync<ANS>(ang, inc);
         nd[j] = make_node(angle_q6, (uint32_t)dist, dist ? (0x2Fu << 2) : 0u, sync);
         rs |= sync << j;
       }
     } else if (ANS == RPLGPU_ANS_CAPSULED_ULTRA) {  // :460-577 — two cabins of 4 bytes = 6 nodes
-      const int inc = (diff_q8 << 3) / 3;
+      const int inc = capsule_angle_inc<ANS>(diff_q8);
       const uint32_t cw[3] = {(uint32_t)g.w, (uint32_t)(g.w >> 32), g.w2};
       uint32_t lvl[3];
       int major[3];
@@ -927,7 +1037,7 @@ __global__ __launch_bounds__(NT) void k_decode(
             dist = (int)((uint32_t)(pred + mj2) << 2);
           }
         }
-        const uint32_t sync = (((ang + inc) % (360 << 16)) < inc) ? 1u : 0u;
+        const uint32_t sync = raw_sync<ANS>(ang, inc);
         // triangulation angle correction :547-556, from the table (see the kernel's head);
         // k2 = 98361 / dist exactly: dist < 2^24, so the float quotient is off by at most one
         uint32_t slot = 492u;
@@ -943,16 +1053,16 @@ __global__ __launch_bounds__(NT) void k_decode(
         rs |= sync << j;
       }
     } else if (ANS == RPLGPU_ANS_DENSE_CAPSULED) {  // :756-784 — four 16-bit distances
-      const int inc = (diff_q8 << 8) / 40;
+      const int inc = capsule_angle_inc<ANS>(diff_q8);
 #pragma unroll
       for (uint32_t j = 0; j < G; ++j) {
         const int ang = (prev_q8 << 8) + (int)(pos0 + j) * inc;
         const int dist = (int)((uint32_t)(g.w >> (16u * j)) & 0xFFFFu) << 2;
-        rs |= ((((ang + inc) % (360 << 16)) < (inc * 2)) ? 1u : 0u) << j;
+        rs |= raw_sync<ANS>(ang, inc) << j;
         nd[j] = make_node(ang >> 10, (uint32_t)dist, dist ? (0x2Fu << 2) : 0u, 0u);
       }
     } else {  // ultra dense :979-1045 — two cabins of 5 bytes = 4 nodes
-      const int inc = (diff_q8 << 8) / 64;
+      const int inc = capsule_angle_inc<ANS>(diff_q8);
       const uint64_t cab[2] = {g.w & 0xFFFFFFFFFFull, (g.w >> 40) | ((uint64_t)g.w2 << 24)};
       uint32_t sm[G];
 #pragma unroll
@@ -973,7 +1083,7 @@ __global__ __launch_bounds__(NT) void k_decode(
         // |d - last| <= 8 can hold only if last <= 8192: store min(dist, 0x3FFF)
         sm[j] = scale == 0u ? (0x8000u | dist) : min(dist, 0x3FFFu);
         if (MODE == 2) dist = (uint32_t)((int)dist + (int)L.fin[i - chunk0 + j] - 4);  // (state 4 unless scale 0)
-        rs |= ((((ang + inc) % (360 << 16)) < (inc * 2)) ? 1u : 0u) << j;
+        rs |= raw_sync<ANS>(ang, inc) << j;
         nd[j] = make_node(ang >> 10, dist, quality, 0u);
       }
       if (MODE != 2) {
@@ -983,14 +1093,7 @@ __global__ __launch_bounds__(NT) void k_decode(
         if (MODE == 1) return;
       }
     }
-#ifdef RPL_DEC_NOSTORE
-    {
-      uint32_t hsh = rs;
-#pragma unroll
-      for (uint32_t j = 0; j < G; ++j) hsh = hsh * 31u + nd[j].x + nd[j].y;
-      if (hsh != 0xDEADBEEFu) return;
-    }
-#endif
+    if (dec_nostore_skip(nd, rs)) return;
     if (FUSE) {
       // where the nodes go: scan j = the last sync node at or before the node; a node in front
       // of the first sync node, in the scan still open at the end, in a scan a reset broke or
@@ -1005,19 +1108,10 @@ __global__ __launch_bounds__(NT) void k_decode(
         if (off + G < len) {  // (strictly below the last slot)
           uint2 *dst = fz.batch + ((size_t)b * fz.scan_cap + L.sslot[j]) * fz.n_stride + off;
           uint2 n0 = nd[0];
-          if (FILTERED && off == 0u) n0.y = (n0.y & 0x00FFFFFFu) | (1u << 24);  // flag byte 2 -> 1
-          typedef uint32_t nt_u32x4 __attribute__((ext_vector_type(4), aligned(8)));
-          const nt_u32x4 va = {n0.x, n0.y, nd[G > 1 ? 1 : 0].x, nd[G > 1 ? 1 : 0].y};
-          const nt_u32x4 vb = {nd[G > 2 ? 2 : 0].x, nd[G > 2 ? 2 : 0].y, nd[G > 3 ? 3 : 0].x, nd[G > 3 ? 3 : 0].y};
-          if (G == 4u) {
-            __builtin_nontemporal_store(va, reinterpret_cast<nt_u32x4 *>(dst));
-            __builtin_nontemporal_store(vb, reinterpret_cast<nt_u32x4 *>(dst + 2));
-          } else {  // ultra: 48 bytes per lane (plain stores, see the unfused path)
-            const nt_u32x4 vc = {nd[G > 4 ? 4 : 0].x, nd[G > 4 ? 4 : 0].y, nd[G > 5 ? 5 : 0].x, nd[G > 5 ? 5 : 0].y};
-            *reinterpret_cast<nt_u32x4 *>(dst) = va;
-            *reinterpret_cast<nt_u32x4 *>(dst + 2) = vb;
-            *reinterpret_cast<nt_u32x4 *>(dst + 4) = vc;
-          }
+          if (FILTERED && off == 0u) n0.y = with_sync_flag(n0.y);  // flag byte 2 -> 1
+          store_node_pair<G == 4u>(dst, n0, nd[G > 1 ? 1 : 0]);
+          store_node_pair<G == 4u>(dst + 2, nd[G > 2 ? 2 : 0], nd[G > 3 ? 3 : 0]);
+          if (G > 4u) store_node_pair<false>(dst + 4, nd[G > 4 ? 4 : 0], nd[G > 5 ? 5 : 0]);  // ultra: 48 bytes per lane
           return;
         }
       }
@@ -1039,7 +1133,7 @@ __global__ __launch_bounds__(NT) void k_decode(
           pos = len - 1u;
         }
         uint2 v = nd[jn];
-        if (FILTERED && off == 0u) v.y = (v.y & 0x00FFFFFFu) | (1u << 24);  // flag byte 2 -> 1
+        if (FILTERED && off == 0u) v.y = with_sync_flag(v.y);
         fz.batch[((size_t)b * fz.scan_cap + slot) * fz.n_stride + pos] = v;
       }
       return;
@@ -1050,18 +1144,7 @@ __global__ __launch_bounds__(NT) void k_decode(
       } else {
 #pragma unroll
         for (uint32_t j = 0; j + 1u < G; j += 2u) {
-          // 32 bytes per lane as two streaming stores (non-temporal: the node stream is written
-          // once and read by a later kernel; -5 % dense, -13 % express, -6 % HQ).  Not for ultra:
-          // its 48 bytes per lane complete a cache line over three instructions, and streaming
-          // stores that leave lines half written cost it +46 %.
-          if (G == 4u) {
-            typedef uint32_t nt_u32x4 __attribute__((ext_vector_type(4), aligned(8)));
-            const nt_u32x4 v = {nd[j].x, nd[j].y, nd[j + 1u].x, nd[j + 1u].y};
-            __builtin_nontemporal_store(v, reinterpret_cast<nt_u32x4 *>(out + i + j));
-          } else {
-            const uint4 v = make_uint4(nd[j].x, nd[j].y, nd[j + 1u].x, nd[j + 1u].y);
-            __builtin_memcpy(out + i + j, &v, 16);
-          }
+          store_node_pair<G == 4u>(out + i + j, nd[j], nd[j + 1u]);
         }
       }
     } else {
@@ -1141,14 +1224,7 @@ __global__ __launch_bounds__(NT) void k_decode(
     emit(t0, g1, mode0{});
   }
 
-#ifdef RPL_DEC_DBG
-  __syncthreads();
-  {  // (ultra-dense: P3 / P5 alternate chunk by chunk; the clocks accumulate each)
-    const unsigned long long now = __builtin_amdgcn_s_memtime();
-    dbg_p3 += now - dbg_mark;
-    dbg_mark = now;
-  }
-#endif
+  clk.lap(clk.p3);
   // ---- P5 (ultra-dense): distance smoothing (:997-1003, :1020) -------------------------------
   // out_i = smooth(d_i, out_{i-1}) is a recurrence, but a smoothed value stays within +-4 of its
   // raw value, so "out_{i-1} - d_{i-1} + 4" is one of 9 states and every node is a map from
@@ -1158,9 +1234,7 @@ __global__ __launch_bounds__(NT) void k_decode(
   // writes the smoothed distances.  Exact for any input, O(n / 256) steps per thread.
   if (UD && carry_nodes) {  // (indices below are relative to the chunk)
     __syncthreads();
-#ifdef RPL_DEC_DBG
-    dbg_u0 = __builtin_amdgcn_s_memtime();
-#endif
+    clk.ud_start();
     auto rawd = [&](uint32_t i) -> int { return (int)(L.smooth[i] & 0x3FFFu); };
     auto is_s0 = [&](uint32_t i) -> bool { return (L.smooth[i] & 0x8000u) != 0u; };
     // state of node i given the value `last` its predecessor left behind (:997-1003):
@@ -1282,10 +1356,7 @@ __global__ __launch_bounds__(NT) void k_decode(
 #pragma unroll
       for (int c = 0; c < 9; ++c) M |= (unsigned long long)(uint32_t)cur[c] << (4 * c);
     }
-#ifdef RPL_DEC_DBG
-    __syncthreads();
-    { const unsigned long long now = __builtin_amdgcn_s_memtime(); dbg_ud[0] += now - dbg_u0; dbg_u0 = now; }
-#endif
+    clk.ud_lap(0);
     // pass B: exclusive scan of the maps over the block (composition, earlier segment first).
     // A segment whose states merged has a CONSTANT map, and "anything, then a constant" is that
     // constant: when every segment of the wave is constant — distances that vary merge within a
@@ -1325,10 +1396,7 @@ __global__ __launch_bounds__(NT) void k_decode(
     // every map in front of a non-empty segment starts with node 0's constant map, so any
     // entry state (take 4) gives the state its predecessor node really has
     int sp = (int)((excl >> (4 * 4)) & 15ull);
-#ifdef RPL_DEC_DBG
-    __syncthreads();
-    { const unsigned long long now = __builtin_amdgcn_s_memtime(); dbg_ud[1] += now - dbg_u0; dbg_u0 = now; }
-#endif
+    clk.ud_lap(1);
     // pass C: the (usually empty) head of the segment again, if its true entry state is not the
     // guessed one
     if (sp != 4) {
@@ -1343,9 +1411,7 @@ __global__ __launch_bounds__(NT) void k_decode(
       }
     }
     __syncthreads();
-#ifdef RPL_DEC_DBG
-    { const unsigned long long now = __builtin_amdgcn_s_memtime(); dbg_ud[2] += now - dbg_u0; dbg_u0 = now; }
-#endif
+    clk.ud_lap(2, false);
     chunk_last = (int)L.misc[7];
     if (!last_chunk) {
     } else if (L.misc[4] & 0x80000000u) {
@@ -1375,21 +1441,8 @@ __global__ __launch_bounds__(NT) void k_decode(
     }
   }
 
-#ifdef RPL_DEC_DBG
-  __syncthreads();
-  {
-    const unsigned long long now = __builtin_amdgcn_s_memtime();
-    dbg_p5 += now - dbg_mark;
-    dbg_mark = now;
-    (void)dbg_u0;
-  }
-#endif
+  clk.lap(clk.p5);
   }  // chunks
-#ifdef RPL_DEC_DBG
-  dbg_t[3] = dbg_t[2] + dbg_p3;
-  dbg_t[4] = dbg_t[3];
-  dbg_t[5] = dbg_t[4] + dbg_p5;  // (slot "P4" = 0, slot "P5" = the smoothing passes; the sync filter goes uncounted)
-#endif
 
   // ---- P4 (dense / ultra-dense): the sync-bit filter, s_i = r_i & ~s_{i-1} -------------------
   if (FILTERED) {
@@ -1398,7 +1451,7 @@ __global__ __launch_bounds__(NT) void k_decode(
       sync_filter([&](uint32_t i) {
         if (i < n_out) {  // flag byte: sync | (!sync << 1) : 2 -> 1
           uint2 v = out[i];
-          v.y = (v.y & 0x00FFFFFFu) | (1u << 24);
+          v.y = with_sync_flag(v.y);
           out[i] = v;
           report_sync(i);
         }
@@ -1419,15 +1472,7 @@ __global__ __launch_bounds__(NT) void k_decode(
     if (FILTERED && carry_nodes > raw_words * 64u) st |= RPLGPU_STREAM_FRAMES_TRUNCATED;
     if (n_nodes) n_nodes[b] = bad_framing ? 0u : n_out;
     if (n_reset) n_reset[b] = bad_framing ? 0u : min(carry_reset, reset_at ? reset_stride : carry_reset);
-#ifdef RPL_DEC_DBG
-    if (reset_at && reset_stride >= 8)
-    {
-      for (int d = 0; d < 5; ++d) reset_at[(size_t)b * reset_stride + 3 + d] = (uint32_t)(dbg_t[d + 1] - dbg_t[d]);
-      reset_at[(size_t)b * reset_stride + 2] = (uint32_t)(dbg_t[0] - dbg_start);
-      if (reset_stride >= 16)
-        for (int d = 0; d < 4; ++d) reset_at[(size_t)b * reset_stride + 8 + d] = (uint32_t)dbg_ud[d];
-    }
-#endif
+    clk.report(reset_at ? reset_at + (size_t)b * reset_stride : nullptr, reset_stride);
     if (n_errors) n_errors[b] = L.misc[5];
     if (n_sync) n_sync[b] = bad_framing ? 0u : min(L.misc[6], sync_stride);
     if (my_sync && L.misc[6] > sync_stride) st |= RPLGPU_STREAM_FRAMES_TRUNCATED;
@@ -1779,6 +1824,32 @@ __global__ __launch_bounds__(kDecBlock) void k_scans_to_batch(
 }
 
 // ---- launchers ------------------------------------------------------------------------------
+// The one switch over the answer type: f(std::integral_constant<int, ANS>{}), or `other` for a type
+// that is none.  Which kernels exist is decided by what f instantiates under `if constexpr`.
+template <class R, class F>
+static R dispatch_ans(int ans, R other, F &&f) {
+  switch (ans) {
+    case RPLGPU_ANS_MEASUREMENT: return f(std::integral_constant<int, RPLGPU_ANS_MEASUREMENT>{});
+    case RPLGPU_ANS_CAPSULED: return f(std::integral_constant<int, RPLGPU_ANS_CAPSULED>{});
+    case RPLGPU_ANS_HQ: return f(std::integral_constant<int, RPLGPU_ANS_HQ>{});
+    case RPLGPU_ANS_CAPSULED_ULTRA: return f(std::integral_constant<int, RPLGPU_ANS_CAPSULED_ULTRA>{});
+    case RPLGPU_ANS_DENSE_CAPSULED: return f(std::integral_constant<int, RPLGPU_ANS_DENSE_CAPSULED>{});
+    case RPLGPU_ANS_ULTRA_DENSE_CAPSULED: return f(std::integral_constant<int, RPLGPU_ANS_ULTRA_DENSE_CAPSULED>{});
+    default: return other;
+  }
+}
+
+// the kernel's parameter list, expanded from the descriptor (here and nowhere else)
+template <class K>
+static hipError_t dec_launch_kernel(K kfn, uint32_t nt, uint32_t lds_bytes, hipStream_t s,
+                                    const DecodeLaunch &d, const DecFuse &fz) {
+  hipLaunchKernelGGL(kfn, dim3(d.B), dim3(nt), lds_bytes, s, d.bytes, d.stream_stride, d.frame_off,
+                     d.gap, d.n_frames, d.max_frames, d.sample_duration_us, d.state_in, d.state_out,
+                     (uint2 *)d.nodes, d.node_stride, d.n_nodes, d.reset_at, d.reset_stride, d.n_reset,
+                     d.n_errors, d.status, d.sync_at, d.sync_stride, d.n_sync, fz);
+  return hipGetLastError();
+}
+
 // The LDS-staged instances (capsule streams, nodes out; back to back or with frame offsets):
 // 512-thread workgroups, two per CU — for calls whose streams fit half the CU's LDS together with their tables (max_frames up to
 // decode_staged_frames(ans): 830 DenseBoost frames, 876 express, 557 ultra, 339 ultra-dense).  *done stays false
@@ -1791,196 +1862,136 @@ static bool dec_stage_fits(uint32_t mf) {  // two workgroups of the staged insta
   const uint32_t need = (uint32_t)sizeof(DecodeLds<ANS, true>) + dec_stage_layout(ANS, mf).total;
   return 2u * ((need + kLdsGranule - 1u) / kLdsGranule * kLdsGranule) <= kLdsPerCu;
 }
-template <int ANS>
-static uint32_t dec_staged_frames() {  // the largest max_frames the staged instance takes
-  uint32_t lo = 0, hi = DecCfg<ANS>::kMaxFrames;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1u) >> 1;
-    if (dec_stage_fits<ANS>(mid)) lo = mid; else hi = mid - 1u;
-  }
-  return lo;
-}
-uint32_t decode_staged_frames(int ans) {
-  switch (ans) {
-    case RPLGPU_ANS_CAPSULED: return dec_staged_frames<RPLGPU_ANS_CAPSULED>();
-    case RPLGPU_ANS_CAPSULED_ULTRA: return dec_staged_frames<RPLGPU_ANS_CAPSULED_ULTRA>();
-    case RPLGPU_ANS_DENSE_CAPSULED: return dec_staged_frames<RPLGPU_ANS_DENSE_CAPSULED>();
-    case RPLGPU_ANS_ULTRA_DENSE_CAPSULED: return dec_staged_frames<RPLGPU_ANS_ULTRA_DENSE_CAPSULED>();
-    default: return 0u;
-  }
-}
-template <bool FRAMED, bool FUSE = false>
-static hipError_t launch_decode_staged(hipStream_t s, int ans, const uint8_t *bytes, uint64_t stream_stride,
-                                       const uint32_t *frame_off, const uint8_t *gap,
-                                       const uint32_t *n_frames, uint32_t max_frames, uint32_t B,
-                                       uint32_t sample_duration_us, const int32_t *state_in,
-                                       int32_t *state_out, uint2 *nodes, uint32_t node_stride,
-                                       uint32_t *n_nodes, uint32_t *reset_at, uint32_t reset_stride,
-                                       uint32_t *n_reset, uint32_t *n_errors, uint32_t *status,
-                                       uint32_t *sync_at, uint32_t sync_stride, uint32_t *n_sync,
-                                       const DecFuse &fz, bool *done) {
-  *done = false;
-  if (max_frames == 0u) return hipSuccess;
-  auto go = [&](auto kfn, uint32_t nt, bool fits, uint32_t mf_cap) -> hipError_t {
-    if (!fits) return hipSuccess;
-    const DecStageLayout lay = dec_stage_layout(ans, max_frames < mf_cap ? max_frames : mf_cap);
-    // The attribute is per kernel FUNCTION and process-wide: set with a call's own size, two handles
-    // decoding on two host threads could interleave set(large) set(small) launch(large), and the
-    // launch would fail.  It is set ONCE per instance and device, to the most any call of the
-    // instance can ask for (the staged frame count of the answer type); a launch passes its own size.
-    {
-      static std::mutex mu;
-      static std::set<std::pair<const void *, int>> done_for;
-      // (the attribute lands on the CURRENT device: it must be the one the launch goes to — the
-      // stream's.  ADVICE r5: the result of hipGetDevice was ignored and a caller that had not made
-      // the handle's device current would have had the attribute recorded for the wrong device.)
-      int dev = -1;
-      if (const hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-      if (s) {
-        hipDevice_t sdev;
-        if (hipStreamGetDevice(s, &sdev) == hipSuccess) {
-          if ((int)sdev != dev) return hipErrorInvalidDevice;
-        } else {
-          (void)hipGetLastError();
-        }
-      }
-      std::lock_guard<std::mutex> lk(mu);
-      const auto key = std::make_pair(reinterpret_cast<const void *>(kfn), dev);
-      if (!done_for.count(key)) {
-        const DecStageLayout most = dec_stage_layout(ans, decode_staged_frames(ans));
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kfn),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)(most.total > lay.total ? most.total : lay.total));
-        if (e != hipSuccess) return e;
-        done_for.insert(key);
-      }
+uint32_t decode_staged_frames(int ans) {  // the largest max_frames the staged instance takes
+  return dispatch_ans(ans, 0u, [](auto a) -> uint32_t {
+    constexpr int A = decltype(a)::value;
+    if (!DecCfg<A>::kCaps) return 0u;
+    uint32_t lo = 0, hi = DecCfg<A>::kMaxFrames;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi + 1u) >> 1;
+      if (dec_stage_fits<A>(mid)) lo = mid; else hi = mid - 1u;
     }
-    hipLaunchKernelGGL(kfn, dim3(B), dim3(nt), lay.total, s, bytes, stream_stride,
-                       frame_off, gap, n_frames, max_frames,
-                       sample_duration_us, state_in, state_out, nodes, node_stride, n_nodes, reset_at,
-                       reset_stride, n_reset, n_errors, status, sync_at, sync_stride, n_sync, fz);
-    *done = true;
-    return hipGetLastError();
-  };
-#define RPL_STAGED(A)                                                                           \
-  case A:                                                                                       \
-    return go(k_decode<A, FRAMED, FUSE, true, 512>, 512u,                                       \
-              dec_stage_fits<A>(max_frames < DecCfg<A>::kMaxFrames ? max_frames : DecCfg<A>::kMaxFrames), \
-              DecCfg<A>::kMaxFrames);
-  switch (ans) {
-    RPL_STAGED(RPLGPU_ANS_CAPSULED)
-    RPL_STAGED(RPLGPU_ANS_CAPSULED_ULTRA)
-    RPL_STAGED(RPLGPU_ANS_DENSE_CAPSULED)
-    RPL_STAGED(RPLGPU_ANS_ULTRA_DENSE_CAPSULED)
-    default: return hipSuccess;
-  }
-#undef RPL_STAGED
+    return lo;
+  });
 }
 
-hipError_t launch_decode(hipStream_t s, int ans, const uint8_t *bytes, uint64_t stream_stride,
-                         const uint32_t *frame_off, const uint8_t *gap, const uint32_t *n_frames,
-                         uint32_t max_frames, uint32_t B, uint32_t sample_duration_us,
-                         const int32_t *state_in, int32_t *state_out, void *nodes,
-                         uint32_t node_stride, uint32_t *n_nodes, uint32_t *reset_at,
-                         uint32_t reset_stride, uint32_t *n_reset, uint32_t *n_errors,
-                         uint32_t *status, uint32_t *sync_at, uint32_t sync_stride,
-                         uint32_t *n_sync, const uint32_t *only, bool staged_ok, uint32_t *stage_todo) {
-  if (B == 0) return hipSuccess;
+// The dynamic-LDS attribute is per kernel FUNCTION and process-wide: set with a call's own size, two
+// handles decoding on two host threads could interleave set(large) set(small) launch(large), and the
+// launch would fail.  It is set ONCE per instance and device, to the most any call of the
+// instance can ask for (the staged frame count of the answer type); a launch passes its own size.
+static hipError_t dec_reserve_stage_lds(const void *kfn, hipStream_t s, int ans, uint32_t this_call) {
+  static std::mutex mu;
+  static std::set<std::pair<const void *, int>> done_for;
+  // (the attribute lands on the CURRENT device: it must be the one the launch goes to — the
+  // stream's.  ADVICE r5: the result of hipGetDevice was ignored and a caller that had not made
+  // the handle's device current would have had the attribute recorded for the wrong device.)
+  int dev = -1;
+  if (const hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+  if (s) {
+    hipDevice_t sdev;
+    if (hipStreamGetDevice(s, &sdev) == hipSuccess) {
+      if ((int)sdev != dev) return hipErrorInvalidDevice;
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+  std::lock_guard<std::mutex> lk(mu);
+  const auto key = std::make_pair(kfn, dev);
+  if (!done_for.count(key)) {
+    const uint32_t most = dec_stage_layout(ans, decode_staged_frames(ans)).total;
+    const hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)(most > this_call ? most : this_call));
+    if (e != hipSuccess) return e;
+    done_for.insert(key);
+  }
+  return hipSuccess;
+}
+
+template <bool FRAMED, bool FUSE = false>
+static hipError_t launch_decode_staged(hipStream_t s, const DecodeLaunch &d, const DecFuse &fz, bool *done) {
+  *done = false;
+  if (d.max_frames == 0u) return hipSuccess;
+  return dispatch_ans(d.ans, hipSuccess, [&](auto a) -> hipError_t {
+    constexpr int A = decltype(a)::value;
+    if constexpr (DecCfg<A>::kCaps) {
+      const uint32_t mf = d.max_frames < DecCfg<A>::kMaxFrames ? d.max_frames : DecCfg<A>::kMaxFrames;
+      if (!dec_stage_fits<A>(mf)) return hipSuccess;
+      const auto kfn = k_decode<A, FRAMED, FUSE, true, 512>;
+      const uint32_t lds = dec_stage_layout(A, mf).total;
+      if (const hipError_t e = dec_reserve_stage_lds(reinterpret_cast<const void *>(kfn), s, A, lds);
+          e != hipSuccess)
+        return e;
+      *done = true;
+      return dec_launch_kernel(kfn, 512u, lds, s, d, fz);
+    } else {
+      return hipSuccess;
+    }
+  });
+}
+
+template <bool FUSE>
+static hipError_t launch_decode_plain(hipStream_t s, const DecodeLaunch &d, const DecFuse &fz) {
+  return dispatch_ans(d.ans, hipErrorInvalidValue, [&](auto a) -> hipError_t {
+    constexpr int A = decltype(a)::value;
+    if constexpr (!FUSE || DecCfg<A>::kFusable) {
+      if (d.frame_off) return dec_launch_kernel(k_decode<A, true, FUSE>, kDecBlock, 0u, s, d, fz);
+      return dec_launch_kernel(k_decode<A, false, FUSE>, kDecBlock, 0u, s, d, fz);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
+}
+
+hipError_t launch_decode(hipStream_t s, const DecodeLaunch &d) {
+  if (d.B == 0) return hipSuccess;
   DecFuse fz{};
-  fz.only = only;
-  fz.stage_todo = stage_todo;
-#define RPL_LAUNCH_DEC3(A, F, Z)                                                                 \
-  hipLaunchKernelGGL((k_decode<A, F, Z>), dim3(B), dim3(kDecBlock), 0, s, bytes, stream_stride, \
-                     frame_off, gap, n_frames, max_frames, sample_duration_us, state_in,         \
-                     state_out, (uint2 *)nodes, node_stride, n_nodes, reset_at, reset_stride,    \
-                     n_reset, n_errors, status, sync_at, sync_stride, n_sync, fz)
-#define RPL_LAUNCH_DEC(A)                          \
-  do {                                             \
-    if (frame_off) RPL_LAUNCH_DEC3(A, true, false); \
-    else RPL_LAUNCH_DEC3(A, false, false);         \
-  } while (0)
-  if (staged_ok && !frame_off) {
+  fz.only = d.only;
+  fz.stage_todo = d.stage_todo;
+  if (d.staged_ok && !d.frame_off) {
     bool done = false;
-    const hipError_t e = launch_decode_staged<false>(s, ans, bytes, stream_stride, nullptr, nullptr, n_frames,
-        max_frames, B, sample_duration_us, state_in, state_out, (uint2 *)nodes, node_stride, n_nodes,
-        reset_at, reset_stride, n_reset, n_errors, status, sync_at, sync_stride, n_sync, fz, &done);
+    const hipError_t e = launch_decode_staged<false>(s, d, fz, &done);
     if (done) return e;
-  } else if (staged_ok && stage_todo) {
+  } else if (d.staged_ok && d.stage_todo) {
     // frame offsets given: the staged kernel takes every stream whose frames lie the way it needs
     // them and lists the others in stage_todo; the plain kernel below then runs over that list
     bool done = false;
-    const hipError_t e = launch_decode_staged<true>(s, ans, bytes, stream_stride, frame_off, gap, n_frames,
-        max_frames, B, sample_duration_us, state_in, state_out, (uint2 *)nodes, node_stride, n_nodes,
-        reset_at, reset_stride, n_reset, n_errors, status, sync_at, sync_stride, n_sync, fz, &done);
+    const hipError_t e = launch_decode_staged<true>(s, d, fz, &done);
     if (e != hipSuccess) return e;
-    if (done) fz.only = stage_todo;  // (0 where `only` was 0: those streams were someone else's)
+    if (done) fz.only = d.stage_todo;  // (0 where `only` was 0: those streams were someone else's)
   }
-  switch (ans) {
-    case RPLGPU_ANS_MEASUREMENT: RPL_LAUNCH_DEC(RPLGPU_ANS_MEASUREMENT); break;
-    case RPLGPU_ANS_CAPSULED: RPL_LAUNCH_DEC(RPLGPU_ANS_CAPSULED); break;
-    case RPLGPU_ANS_HQ: RPL_LAUNCH_DEC(RPLGPU_ANS_HQ); break;
-    case RPLGPU_ANS_CAPSULED_ULTRA: RPL_LAUNCH_DEC(RPLGPU_ANS_CAPSULED_ULTRA); break;
-    case RPLGPU_ANS_DENSE_CAPSULED: RPL_LAUNCH_DEC(RPLGPU_ANS_DENSE_CAPSULED); break;
-    case RPLGPU_ANS_ULTRA_DENSE_CAPSULED: RPL_LAUNCH_DEC(RPLGPU_ANS_ULTRA_DENSE_CAPSULED); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef RPL_LAUNCH_DEC
-  return hipGetLastError();
+  return launch_decode_plain<false>(s, d, fz);
 }
 
-bool decode_fusable(int ans) {
-  return ans == RPLGPU_ANS_CAPSULED || ans == RPLGPU_ANS_CAPSULED_ULTRA ||
-         ans == RPLGPU_ANS_DENSE_CAPSULED || ans == RPLGPU_ANS_ULTRA_DENSE_CAPSULED;
-}
+bool decode_fusable(int ans) { return dec_is_capsule(ans); }
 
-// The fused decoder (express / ultra / dense): completed scans straight into batch slots; d_todo[b]
+// The fused decoder (express / ultra / dense): completed scans straight into batch slots; todo[b]
 // = 1 for a stream it could not take (more sync nodes or reset requests than its tables hold).
-hipError_t launch_decode_fused(hipStream_t s, int ans, const uint8_t *bytes, uint64_t stream_stride,
-                               const uint32_t *frame_off, const uint8_t *gap,
-                               const uint32_t *n_frames, uint32_t max_frames, uint32_t B,
-                               uint32_t sample_duration_us, const int32_t *state_in,
-                               int32_t *state_out, uint32_t *n_errors, uint32_t *status,
-                               uint32_t max_count, void *batch, uint32_t n_stride,
-                               uint32_t scan_cap, uint32_t *n_per_scan, uint32_t *n_scans,
-                               uint32_t *todo, bool staged_ok) {
-  if (B == 0) return hipSuccess;
+hipError_t launch_decode_fused(hipStream_t s, const DecodeLaunch &d) {
+  if (d.B == 0) return hipSuccess;
   DecFuse fz{};
-  fz.batch = (uint2 *)batch;
-  fz.n_per_scan = n_per_scan;
-  fz.n_scans = n_scans;
-  fz.todo = todo;
-  fz.n_stride = n_stride;
-  fz.scan_cap = scan_cap;
-  fz.max_count = max_count;
-  uint2 *nodes = nullptr;
-  const uint32_t node_stride = 0xFFFFFFFFu, reset_stride = 0, sync_stride = 0;
-  uint32_t *n_nodes = nullptr, *reset_at = nullptr, *n_reset = nullptr, *sync_at = nullptr, *n_sync = nullptr;
-  if (frame_off && staged_ok) {
+  fz.batch = (uint2 *)d.batch;
+  fz.n_per_scan = d.n_per_scan;
+  fz.n_scans = d.n_scans;
+  fz.todo = d.todo;
+  fz.n_stride = d.n_stride;
+  fz.scan_cap = d.scan_cap;
+  fz.max_count = d.max_count;
+  DecodeLaunch f = d;  // no node stream, no lists
+  f.nodes = nullptr;
+  f.node_stride = 0xFFFFFFFFu;
+  f.n_nodes = f.reset_at = f.n_reset = f.sync_at = f.n_sync = nullptr;
+  f.reset_stride = f.sync_stride = 0;
+  if (f.frame_off && f.staged_ok) {
     // with frame offsets the staged form wins (the plain kernel's per-group offset loads queue
     // behind the node stores: 0.33 against 0.24 ms without offsets); a stream whose frames do
     // not lie the way it needs them raises todo[b] like one with too many sync nodes
     bool done = false;
-    const hipError_t e = launch_decode_staged<true, true>(s, ans, bytes, stream_stride, frame_off, gap,
-        n_frames, max_frames, B, sample_duration_us, state_in, state_out, nodes, node_stride, n_nodes,
-        reset_at, reset_stride, n_reset, n_errors, status, sync_at, sync_stride, n_sync, fz, &done);
+    const hipError_t e = launch_decode_staged<true, true>(s, f, fz, &done);
     if (done || e != hipSuccess) return e;
   }
-#define RPL_LAUNCH_FUSED(A)                         \
-  do {                                              \
-    if (frame_off) RPL_LAUNCH_DEC3(A, true, true);  \
-    else RPL_LAUNCH_DEC3(A, false, true);           \
-  } while (0)
-  switch (ans) {
-    case RPLGPU_ANS_CAPSULED: RPL_LAUNCH_FUSED(RPLGPU_ANS_CAPSULED); break;
-    case RPLGPU_ANS_CAPSULED_ULTRA: RPL_LAUNCH_FUSED(RPLGPU_ANS_CAPSULED_ULTRA); break;
-    case RPLGPU_ANS_DENSE_CAPSULED: RPL_LAUNCH_FUSED(RPLGPU_ANS_DENSE_CAPSULED); break;
-    case RPLGPU_ANS_ULTRA_DENSE_CAPSULED: RPL_LAUNCH_FUSED(RPLGPU_ANS_ULTRA_DENSE_CAPSULED); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef RPL_LAUNCH_FUSED
-#undef RPL_LAUNCH_DEC3
-  return hipGetLastError();
+  return launch_decode_plain<true>(s, f, fz);
 }
+
 
 hipError_t launch_segment(hipStream_t s, const void *nodes, uint32_t node_stride,
                           const uint32_t *n_nodes, const uint32_t *reset_at, uint32_t reset_stride,

@@ -152,26 +152,50 @@ hipError_t launch_pack_xyi(hipStream_t s, const float *arena, const unsigned lon
                            unsigned long long slot_points, float *slot, uint32_t n_cu);
 
 // decode stage (rpl_decode.hip)
-hipError_t launch_decode(hipStream_t s, int ans, const uint8_t *bytes, uint64_t stream_stride,
-                         const uint32_t *frame_off, const uint8_t *gap, const uint32_t *n_frames,
-                         uint32_t max_frames, uint32_t B, uint32_t sample_duration_us,
-                         const int32_t *state_in, int32_t *state_out, void *nodes,
-                         uint32_t node_stride, uint32_t *n_nodes, uint32_t *reset_at,
-                         uint32_t reset_stride, uint32_t *n_reset, uint32_t *n_errors,
-                         uint32_t *status, uint32_t *sync_at = nullptr, uint32_t sync_stride = 0,
-                         uint32_t *n_sync = nullptr, const uint32_t *only = nullptr,
-                         // capsule streams that fit: the LDS-staged instance (rpl_decode.hip); with frame
-                         // offsets it needs B words of scratch for the streams it leaves to the plain kernel
-                         bool staged_ok = true, uint32_t *stage_todo = nullptr);
+// One decode call (k_decode): B recorded answer streams of one answer type.
+struct DecodeLaunch {
+  int ans = 0;
+  // input: stream b at bytes + b * stream_stride, n_frames[b] <= max_frames frames; back to back, or
+  // (frame_off given) at frame_off[b * max_frames + k], gap[..] != 0 where bytes were rejected in front
+  const uint8_t *bytes = nullptr;
+  uint64_t stream_stride = 0;
+  const uint32_t *frame_off = nullptr;
+  const uint8_t *gap = nullptr;
+  const uint32_t *n_frames = nullptr;
+  uint32_t max_frames = 0, B = 0, sample_duration_us = 0;
+  // decoder state carried from call to call, four words per stream (optional)
+  const int32_t *state_in = nullptr;
+  int32_t *state_out = nullptr;
+  // launch_decode: the node streams, node_stride apart, with the reset-request list and (optional)
+  // the sync-node list of each
+  void *nodes = nullptr;
+  uint32_t node_stride = 0;
+  uint32_t *n_nodes = nullptr;
+  uint32_t *reset_at = nullptr;
+  uint32_t reset_stride = 0;
+  uint32_t *n_reset = nullptr;
+  uint32_t *sync_at = nullptr;
+  uint32_t sync_stride = 0;
+  uint32_t *n_sync = nullptr;
+  // per stream (optional)
+  uint32_t *n_errors = nullptr, *status = nullptr;
+  // launch_decode_fused: completed scans of at most max_count nodes straight into the batch (scan s of
+  // stream b at slot b * scan_cap + s, n_stride nodes apart); todo[b] = 1 for a stream it could not
+  // take (more sync nodes or reset requests than its tables hold)
+  uint32_t max_count = 0;
+  void *batch = nullptr;
+  uint32_t n_stride = 0, scan_cap = 0;
+  uint32_t *n_per_scan = nullptr, *n_scans = nullptr, *todo = nullptr;
+  // launch_decode: streams with only[b] == 0 are skipped (null: all)
+  const uint32_t *only = nullptr;
+  // capsule streams that fit: the LDS-staged instance (rpl_decode.hip); with frame offsets
+  // launch_decode needs B words of scratch for the streams it leaves to the plain kernel
+  bool staged_ok = true;
+  uint32_t *stage_todo = nullptr;
+};
+hipError_t launch_decode(hipStream_t s, const DecodeLaunch &d);
 bool decode_fusable(int ans);
-hipError_t launch_decode_fused(hipStream_t s, int ans, const uint8_t *bytes, uint64_t stream_stride,
-                               const uint32_t *frame_off, const uint8_t *gap,
-                               const uint32_t *n_frames, uint32_t max_frames, uint32_t B,
-                               uint32_t sample_duration_us, const int32_t *state_in,
-                               int32_t *state_out, uint32_t *n_errors, uint32_t *status,
-                               uint32_t max_count, void *batch, uint32_t n_stride,
-                               uint32_t scan_cap, uint32_t *n_per_scan, uint32_t *n_scans,
-                               uint32_t *todo, bool staged_ok = true);
+hipError_t launch_decode_fused(hipStream_t s, const DecodeLaunch &d);
 hipError_t launch_segment(hipStream_t s, const void *nodes, uint32_t node_stride,
                           const uint32_t *n_nodes, const uint32_t *reset_at, uint32_t reset_stride,
                           const uint32_t *n_reset, uint32_t B, uint32_t max_count, void *out_nodes,

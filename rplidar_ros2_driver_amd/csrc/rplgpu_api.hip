@@ -1255,6 +1255,26 @@ size_t rplgpu_frame_stream(uint8_t ans_type, const uint8_t *bytes, size_t nbytes
   return found;
 }
 
+// the part of a decode call every decode door takes from its caller as it is: the streams and the carried state
+static rpl::DecodeLaunch decode_input(uint8_t ans_type, uint32_t sample_duration_us, const uint8_t *d_bytes,
+                                      uint64_t stream_stride, const uint32_t *d_frame_off,
+                                      const uint8_t *d_gap, const uint32_t *d_n_frames, uint32_t max_frames,
+                                      uint32_t B, const int32_t *d_state_in, int32_t *d_state_out) {
+  rpl::DecodeLaunch d;
+  d.ans = ans_type;
+  d.bytes = d_bytes;
+  d.stream_stride = stream_stride;
+  d.frame_off = d_frame_off;
+  d.gap = d_gap;
+  d.n_frames = d_n_frames;
+  d.max_frames = max_frames;
+  d.B = B;
+  d.sample_duration_us = sample_duration_us;
+  d.state_in = d_state_in;
+  d.state_out = d_state_out;
+  return d;
+}
+
 int32_t rplgpu_decode_batch_dev(rplgpu_handle_t h, uint8_t ans_type, uint32_t sample_duration_us,
                                 const uint8_t *d_bytes, uint64_t stream_stride,
                                 const uint32_t *d_frame_off, const uint8_t *d_gap,
@@ -1287,11 +1307,19 @@ int32_t rplgpu_decode_batch_dev(rplgpu_handle_t h, uint8_t ans_type, uint32_t sa
     }
     stage_todo = h->d_dec_todo;
   }
-  RPL_HIP(h, rpl::launch_decode(h->stream, ans_type, d_bytes, stream_stride, d_frame_off, d_gap,
-                                d_n_frames, max_frames, B, sample_duration_us, d_state_in,
-                                d_state_out, d_nodes, node_stride, d_n_nodes, d_reset_at,
-                                reset_stride, d_n_reset, d_n_errors, d_status, nullptr, 0, nullptr,
-                                nullptr, h->dec_stage, stage_todo));
+  rpl::DecodeLaunch d = decode_input(ans_type, sample_duration_us, d_bytes, stream_stride, d_frame_off,
+                                     d_gap, d_n_frames, max_frames, B, d_state_in, d_state_out);
+  d.nodes = d_nodes;
+  d.node_stride = node_stride;
+  d.n_nodes = d_n_nodes;
+  d.reset_at = d_reset_at;
+  d.reset_stride = reset_stride;
+  d.n_reset = d_n_reset;
+  d.n_errors = d_n_errors;
+  d.status = d_status;
+  d.staged_ok = h->dec_stage;
+  d.stage_todo = stage_todo;
+  RPL_HIP(h, rpl::launch_decode(h->stream, d));
   return RPLGPU_OK;
 }
 
@@ -1361,22 +1389,36 @@ static int32_t decode_scans_impl(rplgpu_handle_t h, uint8_t ans_type, uint32_t s
   // and writes the nodes of completed scans straight into their batch slots; a stream with more
   // sync nodes / reset requests than its tables hold raises t_todo[b] and takes the general path
   // below (decode to the node stream, then assemble), which skips every stream already done.
-  const uint32_t *only = nullptr;
+  rpl::DecodeLaunch d = decode_input(ans_type, sample_duration_us, d_bytes, stream_stride, d_frame_off,
+                                     d_gap, d_n_frames, max_frames, B, d_state_in, d_state_out);
+  d.nodes = t_nodes;
+  d.node_stride = node_stride;
+  d.n_nodes = t_nn;
+  d.reset_at = t_rst;
+  d.reset_stride = reset_stride;
+  d.n_reset = t_nr;
+  d.sync_at = t_sync;
+  d.sync_stride = sync_stride;
+  d.n_sync = t_ns;
+  d.n_errors = d_n_errors;
+  d.status = d_status;
+  d.max_count = max_count;
+  d.batch = d_batch;
+  d.n_stride = n_stride;
+  d.scan_cap = scan_cap;
+  d.n_per_scan = d_n_per_scan;
+  d.n_scans = d_n_scans;
+  d.todo = t_todo;
+  d.staged_ok = h->dec_stage;
+  d.stage_todo = d_frame_off ? t_stage_todo : nullptr;
   // (with a carried scan every stream takes the general path: the fused decoder neither decodes
   // the nodes in front of a call's first sync node nor those behind its last)
   if (!carry && rpl::decode_fusable(ans_type)) {
-    RPL_HIP(h, rpl::launch_decode_fused(h->stream, ans_type, d_bytes, stream_stride, d_frame_off,
-                                        d_gap, d_n_frames, max_frames, B, sample_duration_us,
-                                        d_state_in, d_state_out, d_n_errors, d_status, max_count,
-                                        d_batch, n_stride, scan_cap, d_n_per_scan, d_n_scans, t_todo,
-                                        h->dec_stage));
-    only = t_todo;
+    RPL_HIP(h, rpl::launch_decode_fused(h->stream, d));
+    d.only = t_todo;
   }
-  RPL_HIP(h, rpl::launch_decode(h->stream, ans_type, d_bytes, stream_stride, d_frame_off, d_gap,
-                                d_n_frames, max_frames, B, sample_duration_us, d_state_in,
-                                d_state_out, t_nodes, node_stride, t_nn, t_rst, reset_stride, t_nr,
-                                d_n_errors, d_status, t_sync, sync_stride, t_ns, only, h->dec_stage,
-                                d_frame_off ? t_stage_todo : nullptr));
+  RPL_HIP(h, rpl::launch_decode(h->stream, d));
+  const uint32_t *only = d.only;
   RPL_HIP(h, rpl::launch_assemble(h->stream, t_nodes, node_stride, t_nn, t_sync, sync_stride, t_ns,
                                   t_rst, reset_stride, t_nr, B, max_count, d_batch, n_stride,
                                   scan_cap, d_n_per_scan, d_n_scans, d_status, only, d_carry_in,

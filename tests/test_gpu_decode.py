@@ -870,3 +870,141 @@ def test_staged_decoder_with_frame_offsets(gpu, gpu_plain_decoder, oracle, ans):
         assert got["nodes"][b].view(NODE_DTYPE)[:n].tobytes() == want.tobytes(), (hex(ans), b)
         assert list(got["rst"][b, : got["nr"][b]]) == list(w_rst) and int(got["ne"][b]) == w_err
         assert tuple(int(v) for v in got["sout"][b, :2]) == w_st
+
+
+# One recording, every route, one answer.  The frame counts follow from the decode kernel's own
+# constants (rpl_decode.hip: DecCfg<ANS>::kGroup = G, the trip depth U, the workgroup size NT), not
+# from any workload.  P3 hands out groups of G nodes, U x NT per full trip, the rest in a tail loop:
+# a stream runs BOTH loops of an instance when it publishes at least U x NT groups and not a whole
+# number of trips.  NT is 512 for the LDS-staged instances and 256 for the plain ones, so the staged
+# size decides (the plain instances then make two full trips and a tail).  Frames that publish =
+# frames - 1 (a capsule is decoded with its successor's start angle) - the frames the test breaks;
+# `spare` covers those.
+#   type         NPF  G  groups/frame  U  U x 512   frames that must publish      frames
+#   express       32  4       8        4   2048     256                           256 + 1 + spare = 270
+#   ultra         96  6      16        4   2048     128                           128 + 1 + spare = 140
+#   dense         40  4      10        4   2048     205 (2050 groups)             205 + 1 + spare = 216
+#   ultra-dense   64  4      16        -   (no trips: one 8 192-node chunk = 128 frames, and one more
+#                                           chunk has to start)                   128 + 1 + spare = 140
+#   HQ            96  4      24        2   512 (NT = 256 only)  22 (528 groups)    22 + spare     = 30
+#   legacy         1  1       1        4   1024 (NT = 256 only) 1025               1025 + spare   = 1100
+# All of them lie below rplgpu_decode_staged_frames (830 dense, 876 express, 557 ultra, 339
+# ultra-dense), which the test asserts.  Three and a half revolutions per stream close at least two.
+_ROUTE_FRAMES = {0x82: 270, 0x84: 140, 0x85: 216, 0x86: 140, 0x83: 30, 0x81: 1100}
+
+
+@pytest.mark.parametrize("ans", ALL_ANS)
+def test_one_recording_every_route_one_answer(gpu, gpu_plain_decoder, oracle, ans):
+    """A small batch of streams through every route the library has for its answer type:
+    decode_batch_dev -> segment_batch_dev -> scans_to_batch_dev, and decode_scans_dev, each back to
+    back and with frame offsets, each on the `gpu` handle (LDS-staged instances where they exist) and
+    on a handle that never stages — eight routes for a capsule type, the same calls for HQ and legacy
+    nodes (whose two handles run the same instances).  Nodes, counts, reset positions, error counts,
+    status words, carried state and the scans of every route equal the oracle's, byte for byte, and
+    so each other's.  The batch: a clean stream, one with a flipped payload byte, one whose gap flag
+    is raised on a frame (offset routes only: its answer differs from the back-to-back one, and both
+    are checked against the oracle given the same input), one with carried-in state, one too short
+    for a full trip, and one whose frame 0 is flagged as the previous call's last frame (state word 2:
+    the oracle has no such call, so that stream is held to the first route's answer, which
+    test_staged_decoder_matches_plain_and_oracle ties to the plain kernel).  Frame counts: see
+    _ROUTE_FRAMES."""
+    torch = _torch()
+    dev = torch.device("cuda:0")
+    lib = abi.load_library()
+    S, npf = cp.FRAME_SIZE[ans], cp.NODES_PER_FRAME[ans]
+    nf = _ROUTE_FRAMES[ans]
+    capsule = ans in (0x82, 0x84, 0x85, 0x86)
+    if capsule:
+        assert nf <= int(lib.rplgpu_decode_staged_frames(ans))
+    B, handed_over = 6, 5
+    nfs = np.array([nf, nf, nf, nf, max(nf // 5, 3), nf], np.int32)
+    streams = [cp.make_stream(ans, int(nfs[b]), 7100 + b, payload=("ring_noisy", "random", "ring", "ring_near", "ring", "ring_noisy")[b],
+                              frames_per_rev=float(nfs[b]) / 3.5).copy() for b in range(B)]
+    streams[1][(nf // 2) * S + S - 1] ^= 0x5A  # a payload byte: checksum / CRC failure (legacy: another distance)
+    buf = np.stack([np.pad(s, (0, nf * S - len(s))) for s in streams])
+    offs = np.tile(np.arange(nf, dtype=np.uint32) * S, (B, 1))
+    gaps = np.zeros((B, nf), np.uint8)
+    gaps[2, nf // 3] = 1
+    state_in = np.zeros((B, 4), np.int32)
+    state_in[3, :2] = (1, 1234 * 4)
+    state_in[handed_over, 2] = 1
+    d_bytes, d_nf = torch.from_numpy(buf).to(dev), torch.from_numpy(nfs).to(dev)
+    d_off, d_gap = torch.from_numpy(offs.view(np.int32)).to(dev), torch.from_numpy(gaps).to(dev)
+    d_sin = torch.from_numpy(state_in).to(dev)
+    node_stride, reset_stride, max_count = nf * npf, 32, 8192
+    # (HQ's random payload sets the sync flag on every other node: many short scans)
+    scan_cap, n_stride = (2048, 64) if ans == 0x83 else (64, 4096)
+
+    def want_for(framed):
+        out = []
+        for b in range(B):
+            st = (int(state_in[b, 0]), int(state_in[b, 1]))
+            k = int(nfs[b])
+            if framed:
+                nodes, rst, err, st_out = oracle.unpack_frames(ans, buf[b], offs[b, :k], gaps[b, :k], 125, state=st)
+            else:
+                nodes, rst, err, st_out = oracle.unpack(ans, buf[b, : k * S], 125, state=st)
+            scans, w_off = oracle.segment(nodes, rst, max_count)
+            out.append(dict(nodes=nodes.tobytes(), rst=[int(v) for v in rst], err=int(err), state=tuple(st_out),
+                            scans=[scans[w_off[s]: w_off[s + 1]].tobytes() for s in range(len(w_off) - 1)]))
+        return out
+
+    want = {False: want_for(False), True: want_for(True)}
+    for b in range(B):  # one recording: without a raised gap flag the offsets change nothing
+        if not gaps[b].any():
+            assert want[True][b] == want[False][b], (hex(ans), b)
+    assert want[True][2] != want[False][2] or not capsule
+    assert any(len(w["scans"]) >= 1 for w in want[False])
+    assert all(len(w["scans"]) <= scan_cap and all(len(s) <= n_stride * 8 for s in w["scans"]) for f in want for w in want[f])
+
+    def new(shape, dt, fill=0x55):
+        return torch.full(shape, fill, dtype=dt, device=dev)
+
+    def route_batch(h, framed):
+        nodes, seg = new((B, node_stride * 8), torch.uint8, 0), new((B, node_stride * 8), torch.uint8, 0)
+        nn, nr, ne, st, ns = (new((B,), torch.int32) for _ in range(5))
+        rst, sout = new((B, reset_stride), torch.int32), new((B, 4), torch.int32)
+        s_off, base = new((B, scan_cap + 1), torch.int32, 0), new((B + 1,), torch.int32, 0)
+        batch, lens = new((B * scan_cap, n_stride * 8), torch.uint8, 0), new((B * scan_cap,), torch.int32, 0)
+        h.decode_batch_dev(ans, 125, d_bytes.data_ptr(), nf * S, d_off.data_ptr() if framed else 0,
+                           d_gap.data_ptr() if framed else 0, d_nf.data_ptr(), nf, B, d_sin.data_ptr(),
+                           sout.data_ptr(), nodes.data_ptr(), node_stride, nn.data_ptr(), rst.data_ptr(),
+                           reset_stride, nr.data_ptr(), ne.data_ptr(), st.data_ptr())
+        h.segment_batch_dev(nodes.data_ptr(), node_stride, nn.data_ptr(), rst.data_ptr(), reset_stride,
+                            nr.data_ptr(), B, max_count, seg.data_ptr(), node_stride, s_off.data_ptr(),
+                            scan_cap, ns.data_ptr())
+        h.scans_to_batch_dev(seg.data_ptr(), node_stride, s_off.data_ptr(), scan_cap, ns.data_ptr(), B,
+                             base.data_ptr(), batch.data_ptr(), n_stride, B * scan_cap, lens.data_ptr())
+        h.synchronize()
+        nodes, nn, nr, ne, st, ns, rst, sout, base, batch, lens = (
+            t.cpu().numpy() for t in (nodes, nn, nr, ne, st, ns, rst, sout, base, batch, lens))
+        return [dict(nodes=nodes[b, : int(nn[b]) * 8].tobytes(), rst=[int(v) for v in rst[b, : int(nr[b])]],
+                     err=int(ne[b]), status=int(st[b]), state=(int(sout[b, 0]), int(sout[b, 1])),
+                     scans=[batch[int(base[b]) + s, : int(lens[int(base[b]) + s]) * 8].tobytes()
+                            for s in range(int(ns[b]))]) for b in range(B)]
+
+    def route_scans(h, framed):
+        ns, ne, st = (new((B,), torch.int32) for _ in range(3))
+        sout = new((B, 4), torch.int32)
+        batch, lens = new((B * scan_cap, n_stride * 8), torch.uint8, 0), new((B * scan_cap,), torch.int32)
+        h.decode_scans_dev(ans, 125, d_bytes.data_ptr(), nf * S, d_off.data_ptr() if framed else 0,
+                           d_gap.data_ptr() if framed else 0, d_nf.data_ptr(), nf, B, d_sin.data_ptr(),
+                           sout.data_ptr(), max_count, batch.data_ptr(), n_stride, scan_cap, lens.data_ptr(),
+                           ns.data_ptr(), ne.data_ptr(), st.data_ptr())
+        h.synchronize()
+        ns, ne, st, sout, batch, lens = (t.cpu().numpy() for t in (ns, ne, st, sout, batch, lens))
+        return [dict(err=int(ne[b]), status=int(st[b]), state=(int(sout[b, 0]), int(sout[b, 1])),
+                     scans=[batch[b * scan_cap + s, : int(lens[b * scan_cap + s]) * 8].tobytes()
+                            for s in range(int(ns[b]))]) for b in range(B)]
+
+    first = {}  # the handed-over stream: the first route's answer, per kind of route
+    for framed in (False, True):
+        for hname, h in (("staged", gpu), ("plain", gpu_plain_decoder)):
+            for rname, got in (("batch", route_batch(h, framed)), ("scans", route_scans(h, framed))):
+                for b in range(B):
+                    key = (hex(ans), "offsets" if framed else "back to back", hname, rname, b)
+                    w = first.setdefault(rname, got[b]) if b == handed_over else want[framed][b]
+                    for field in ("nodes", "rst", "err", "state", "scans"):
+                        if field in got[b]:
+                            assert got[b][field] == w[field], key + (field,)
+                    assert got[b]["status"] == 0, key  # (nothing unframed, nothing truncated)

@@ -65,7 +65,7 @@ for ans, nf in ((0x85, 801), (0x82, 1001), (0x84, 334), (0x86, 501), (0x83, 334)
             print("   ultra-dense smoothing: [walk, map scan, second walk, -] (mean cycles):", d_rst.cpu().numpy()[:, 8:12].astype(np.float64).mean(0).round(0))
         print("   P1 p10/p50/p90:", np.percentile(ph[:, 0], [10, 50, 90]).round(0), " first 1792 WGs mean", ph[:1792, 0].mean().round(0), "rest", ph[1792:, 0].mean().round(0),
               " P3 p10/p50/p90:", np.percentile(ph[:, 2], [10, 50, 90]).round(0))
-    print(f"ans {ans:#x}: {nodes/1e6:.1f} Mnodes in {t:.3f} ms -> {nodes/t/1e6:.1f} Gnodes/s, "
+    print(f"ans {ans:#x}: {nodes/1e6:.1f} Mnodes in {t:.3f} ms (median {sorted(ts)[2]:.3f}, max {max(ts):.3f}) -> {nodes/t/1e6:.1f} Gnodes/s, "
           f"in {B*nf*S/1e6:.0f} MB out {nodes*8/1e6:.0f} MB -> {(B*nf*S+nodes*8)/t/1e6:.0f} GB/s")
     if True:
         scan_cap, n_stride = 4, min(node_stride, 32768)
@@ -88,7 +88,7 @@ for ans, nf in ((0x85, 801), (0x82, 1001), (0x84, 334), (0x86, 501), (0x83, 334)
             k = (torch.arange(w.shape[1], device=dev) % 1021 + 1)
             extra = f", checksum {int(w.sum().item())} {int((w * k).sum().item())}"
             del w
-        print(f"  segment-fused decode_scans_dev: {min(ts):.3f} ms, scans {int(d_ns2.sum().item())}, nodes in scans {int(d_len.sum().item())}, status {int(d_st2.max().item())}" + extra)
+        print(f"  segment-fused decode_scans_dev: {min(ts):.3f} ms (median {sorted(ts)[2]:.3f}, max {max(ts):.3f}), scans {int(d_ns2.sum().item())}, nodes in scans {int(d_len.sum().item())}, status {int(d_st2.max().item())}" + extra)
         del d_batch
     if ans == 0x85:
         d_seg = torch.empty_like(d_nodes)
