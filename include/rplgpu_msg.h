@@ -1839,6 +1839,134 @@ int32_t rplgpu_compose_poses_dev(rplgpu_handle_t h, const float *d_poses, uint64
                                  uint32_t poses_per_group, uint32_t P, const uint32_t *d_result, uint32_t q,
                                  const float *d_pose2d_in, uint32_t B, uint32_t group, float *d_pose2d_out);
 
+/* ---- E26: a cost-to-goal field over a costmap, and the paths down it (row 4; the first reader of E12 as a costmap) ----
+ * E12 makes the costmap every planner starts from; E13 - E25 read an int8 grid only as a likelihood field.  This is
+ * the step a costmap's user takes next: the navigation function of NavFn / global_planner — the least cost from every
+ * cell to a goal, Dijkstra over the costmap — and the path that follows it downhill.  Nothing in the reference plans,
+ * so these rules ARE the definition (parity unpinned, as E5-E25).  Everything is integers: the field is the one
+ * solution of a min-plus fixed-point equation, depends on no order and is held to its oracle byte for byte.
+ *
+ * CELL WEIGHT of input byte v (int8, E11's layout, cell (cx, cy) at cy * width + cx):
+ *   v >= lethal: impassable;   0 <= v < lethal: w = neutral + factor * v;
+ *   v < 0: w = unknown_cost, impassable when that is 0.          Every passable w is in 1 .. RPLGPU_NAV_MAX_COST.
+ * STEPS, numbered 0 .. 7 as (dx, dy) with the factor k:
+ *   0 (+1, 0)  1 (-1, 0)  2 (0, +1)  3 (0, -1)   k = 5;      4 (+1, +1)  5 (-1, +1)  6 (+1, -1)  7 (-1, -1)   k = 7
+ * A step from c to its neighbour n inside the grid is ALLOWED when c is passable; a diagonal one also needs both
+ * cells it passes between, (cx + dx, cy) and (cx, cy + dy), passable by their bytes (no corner cutting).  n's own
+ * byte does not matter.
+ * FIELD D, one uint32 per cell, RPLGPU_NAV_UNREACHED = 0xFFFFFFFF:
+ *   D = 0 at every goal cell, whatever its byte;
+ *   otherwise D(c) = min over the allowed steps c -> n with D(n) reached of D(n) + k * w(c) if that is <= cap, else
+ *   UNREACHED (so an impassable cell that is no goal is UNREACHED).
+ * Every w >= 1, so there is exactly one solution: the least path cost to a goal, cut at cap (consistently: every
+ * cell further along a least path has a smaller value).  Nothing overflows: cap + 7 * 2047 < 2^32.
+ * GOALS per grid g: d_n_goals[g] cell indices (cy * width + cx) at d_goals + g * goal_stride, in device memory; of
+ * these the first RPLGPU_NAV_MAX_GOALS = 1024 are read.  An index >= width * height, and every index beyond the
+ * first 1024, is IGNORED and counted; an index in range is TAKEN and counted, duplicates each time.  No goal taken:
+ * everything UNREACHED.
+ * PATH from a start cell c0: while D(c) != 0, step to the allowed neighbour n of LOWEST step number with D(n) reached
+ * and D(n) + k * w(c) == D(c).  D falls strictly, so the walk ends, and the cells written cost exactly D(c0).  The
+ * cells' indices go to the path's words, c0 first.  Four INFO words a path: 0 the cells written (start and goal
+ * included), 1 the flags, 2 D(c0) (UNREACHED under NO_START), 3 the last cell written (the start index as given when
+ * none was).  Flags, one of:
+ *   RPLGPU_NAV_PATH_REACHED    the last cell written has D = 0
+ *   RPLGPU_NAV_PATH_NO_START   the index is >= width * height; nothing written
+ *   RPLGPU_NAV_PATH_UNREACHED  D(c0) is UNREACHED; nothing written
+ *   RPLGPU_NAV_PATH_TRUNCATED  max_len cells written and the last has D != 0
+ *   RPLGPU_NAV_PATH_BROKEN     no neighbour satisfies the equality at the last cell written: only when the potential
+ *                              is not the finished field of this grid and spec
+ * Words of a path at and beyond its length are never changed.
+ * TILES: RPLGPU_NAV_TILE = 64 cells a side, ntx = ceil(width / 64), nty = ceil(height / 64); tile (tx, ty) of a grid
+ * is tile ty * ntx + tx.  The device relaxes tile by tile, one launch a ROUND; a tile is DIRTY when a word it reads
+ * may have changed since it last ran. */
+#define RPLGPU_NAV_TILE        64u
+#define RPLGPU_NAV_MAX_COST    2047u
+#define RPLGPU_NAV_MAX_CAP     0xFFFF0000u
+#define RPLGPU_NAV_MAX_ROUNDS  4096u
+#define RPLGPU_NAV_MAX_GOALS   1024u
+#define RPLGPU_NAV_MAX_STARTS  65536u
+#define RPLGPU_NAV_MAX_TILES   0x800000u   /* G * ntx * nty of one call: a round's launch stays below 2^32 threads */
+#define RPLGPU_NAV_UNREACHED   0xFFFFFFFFu
+#define RPLGPU_NAV_UNFINISHED  0x01u   /* result word 1: dirty tiles are left, the field is not the answer yet */
+#define RPLGPU_NAV_PATH_REACHED    0x01u
+#define RPLGPU_NAV_PATH_NO_START   0x02u
+#define RPLGPU_NAV_PATH_UNREACHED  0x04u
+#define RPLGPU_NAV_PATH_TRUNCATED  0x08u
+#define RPLGPU_NAV_PATH_BROKEN     0x10u
+typedef struct rplgpu_nav_field {
+  uint32_t width, height;   /* 1 .. RPLGPU_MAX_OCC_DIM */
+  uint32_t lethal;          /* 1 .. 100: bytes at and above it are impassable */
+  uint32_t neutral;         /* 1 .. 255: the weight of a free cell */
+  uint32_t factor;          /* 0 .. 16: the weight added per cost unit */
+  uint32_t unknown_cost;    /* 0: unknown is impassable; else 1 .. RPLGPU_NAV_MAX_COST */
+  uint32_t cap;             /* 0 .. RPLGPU_NAV_MAX_CAP: values above it are UNREACHED */
+  uint32_t rounds;          /* 1 .. RPLGPU_NAV_MAX_ROUNDS: the launches one call queues */
+} rplgpu_nav_field_t;
+/* 1024 x 1024, lethal 99, neutral 50, factor 2, unknown_cost 0, cap RPLGPU_NAV_MAX_CAP, rounds
+ * rplgpu_nav_field_default_rounds(1024, 1024) */
+void rplgpu_default_nav_field(rplgpu_nav_field_t *f);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL, a value outside the ranges above, and
+ * neutral + factor * (lethal - 1) > RPLGPU_NAV_MAX_COST.  The device path uses this function. */
+int32_t rplgpu_nav_field_check(const rplgpu_nav_field_t *f);
+/* Host only: 2 * (ntx + nty) + 2, enough for a field whose least paths cross every tile border once in each
+ * direction; 0 for a width or height outside 1 .. RPLGPU_MAX_OCC_DIM.  A maze needs more: resume. */
+uint32_t rplgpu_nav_field_default_rounds(uint32_t width, uint32_t height);
+/* Host only: the uint32 words of scratch rplgpu_nav_field_dev takes for G grids, 2 * ntx * nty * G (two planes of
+ * one dirty word per tile); 0 for a spec the check refuses, G = 0 or G * ntx * nty above RPLGPU_NAV_MAX_TILES. */
+uint64_t rplgpu_nav_field_scratch_words(const rplgpu_nav_field_t *f, uint32_t G);
+/* Host only: the FIELD of ONE grid by a binary-heap Dijkstra from the goals, the definition a reader can run.
+ * goals: n_goals indices (NULL with 0); potential: width * height words, written whole; result (optional): the
+ * eight words below with 0, 1, 6 and 7 zero.  `rounds` is not used.  RPLGPU_ERR_INVALID_ARG and nothing written for
+ * a spec the check refuses or a NULL pointer. */
+int32_t rplgpu_nav_field_host(const rplgpu_nav_field_t *f, const int8_t *grid, const uint32_t *goals,
+                              uint32_t n_goals, uint32_t *potential, uint32_t result[8]);
+/* Host only: ONE PATH down `potential` in plain C++; path: max_len words (>= 1), info: the four words.  Returns the
+ * flags, or RPLGPU_ERR_INVALID_ARG (negative) and nothing written for a spec the check refuses, a NULL pointer or
+ * max_len = 0. */
+int32_t rplgpu_nav_path_host(const rplgpu_nav_field_t *f, const int8_t *grid, const uint32_t *potential,
+                             uint32_t start, uint32_t *path, uint32_t max_len, uint32_t info[4]);
+/* The FIELD of G grids on the handle's stream: grid g at d_grid + g * grid_stride (E12's rules: the stride >= width
+ * * height and a multiple of 4, the pointer 4-byte aligned; only read), its field at d_potential + g *
+ * potential_stride (words; >= width * height; 4-byte aligned; words at and beyond width * height of a grid are never
+ * changed), its goals as above (goal_stride in words, >= 1), d_n_goals G words.  The call queues an init launch, the
+ * goals (which mark dirty every tile that reads a goal cell, its neighbours across a tile border too), `rounds` rounds
+ * and two closing launches with no host round trip; no workgroup ever waits for another, and
+ * a round's tile that is not dirty leaves at once.  resume = 0 starts afresh.  resume = 1 continues from d_potential
+ * and from the dirty words a previous call with the SAME arguments left in d_scratch — THE ONE STAGE WHOSE SCRATCH
+ * HOLDS SOMETHING A SECOND CALL RELIES ON: between such calls the caller leaves d_scratch, d_potential, the grid and
+ * the goals alone.  A finished field resumed stays byte-identical.
+ * RESULT, eight words per grid at d_result + 8 g: 0 the dirty tiles left (0 = finished), 1 the flags
+ * (RPLGPU_NAV_UNFINISHED), 2 the goals taken, 3 the goals ignored, 4 the reached cells, 5 the greatest reached D
+ * (0 when none), 6 the tile visits of this call, 7 the rounds of this call that had a dirty tile.  4 and 5 describe
+ * d_potential as the call left it.  While a field is unfinished, words 4 - 7 and the field itself are not defined
+ * byte for byte; only this is: every word is UNREACHED or >= the answer.  6 and 7 depend on the schedule even for a
+ * finished field.
+ * RPLGPU_ERR_INVALID_ARG for a spec the check refuses, G = 0 or above 65535, a missing or misaligned pointer, the
+ * stride rules, resume above 1; RPLGPU_ERR_CAPACITY for G * ntx * nty above RPLGPU_NAV_MAX_TILES
+ * = 2^23, before anything is queued.  A refused call changes no output.
+ * Asynchronous on the handle's stream; nothing is stored on the handle. */
+int32_t rplgpu_nav_field_dev(rplgpu_handle_t h, const rplgpu_nav_field_t *f, const int8_t *d_grid,
+                             uint64_t grid_stride, uint32_t G, const uint32_t *d_goals, uint64_t goal_stride,
+                             const uint32_t *d_n_goals, uint32_t *d_potential, uint64_t potential_stride,
+                             uint32_t *d_scratch, uint32_t resume, uint32_t *d_result);
+/* S PATHS per grid (1 .. RPLGPU_NAV_MAX_STARTS), one thread a path (a dependent chain of neighbour reads: not the
+ * hot path): the start of path s of grid g at d_starts[g * S + s], its cells at d_paths + (g * S + s) * max_len,
+ * its info at d_info + 4 (g * S + s).  The grid and the potential are only read.  RPLGPU_ERR_INVALID_ARG for a spec
+ * the check refuses, G = 0 or above 65535, S out of range, max_len = 0, a missing or misaligned (4-byte) pointer,
+ * the stride rules of rplgpu_nav_field_dev.  A refused call changes no output.  Asynchronous. */
+int32_t rplgpu_nav_paths_dev(rplgpu_handle_t h, const rplgpu_nav_field_t *f, const int8_t *d_grid,
+                             uint64_t grid_stride, const uint32_t *d_potential, uint64_t potential_stride,
+                             uint32_t G, const uint32_t *d_starts, uint32_t S, uint32_t *d_paths, uint32_t max_len,
+                             uint32_t *d_info);
+/* ONE grid, HOST buffers (the node-side door, rplgpu_host.hpp): allocates its device buffers per call, calls
+ * rplgpu_nav_field_dev with resume until the field is finished or 64 calls have passed, and returns when the results
+ * are in place.  potential: width * height words; result: 8 words, 6 and 7 summed over the calls.  starts (optional,
+ * S of them): with them paths (S * max_len words, copied in first so that words beyond a path stay) and info (4 S
+ * words) are required. */
+int32_t rplgpu_nav_field(rplgpu_handle_t h, const rplgpu_nav_field_t *f, const int8_t *grid, const uint32_t *goals,
+                         uint32_t n_goals, uint32_t *potential, uint32_t result[8], const uint32_t *starts,
+                         uint32_t S, uint32_t *paths, uint32_t max_len, uint32_t *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,16 @@ MAX_WIDE_SHIFT = 256          # RPLGPU_MAX_WIDE_SHIFT
 MAX_WIDE_BLOCKS = 65536       # RPLGPU_MAX_WIDE_BLOCKS
 WIDE_MATCH_UNPROVEN = 0x1     # word 7 of E24's result words
 REFINE_WORDS = 32             # RPLGPU_REFINE_WORDS (E25): uint32 words of sums per pose
+NAV_TILE = 64                 # RPLGPU_NAV_TILE (E26): cells a side of a tile of the field
+NAV_MAX_COST = 2047           # RPLGPU_NAV_MAX_COST
+NAV_MAX_CAP = 0xFFFF0000      # RPLGPU_NAV_MAX_CAP
+NAV_MAX_ROUNDS = 4096         # RPLGPU_NAV_MAX_ROUNDS
+NAV_MAX_GOALS = 1024          # RPLGPU_NAV_MAX_GOALS
+NAV_MAX_STARTS = 65536        # RPLGPU_NAV_MAX_STARTS
+NAV_MAX_TILES = 1 << 23       # RPLGPU_NAV_MAX_TILES: G x tiles of one call
+NAV_UNREACHED = 0xFFFFFFFF    # RPLGPU_NAV_UNREACHED
+NAV_UNFINISHED = 0x01         # RPLGPU_NAV_UNFINISHED (result word 1)
+NAV_PATH_REACHED, NAV_PATH_NO_START, NAV_PATH_UNREACHED, NAV_PATH_TRUNCATED, NAV_PATH_BROKEN = 1, 2, 4, 8, 16
 REFINE_PLANES = 29            # RPLGPU_REFINE_PLANES
 REFINE_MAX_ITERS = 16         # RPLGPU_REFINE_MAX_ITERS
 REFINE_STEPPED = 0x01         # E25's step flags
@@ -223,6 +233,15 @@ ABI_SYMBOLS = [
     "rplgpu_refine_poses",
     "rplgpu_match_poses_dev",
     "rplgpu_compose_poses_dev",
+    "rplgpu_default_nav_field",
+    "rplgpu_nav_field_check",
+    "rplgpu_nav_field_default_rounds",
+    "rplgpu_nav_field_scratch_words",
+    "rplgpu_nav_field_host",
+    "rplgpu_nav_path_host",
+    "rplgpu_nav_field_dev",
+    "rplgpu_nav_paths_dev",
+    "rplgpu_nav_field",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -744,6 +763,32 @@ class PoseRefine(C.Structure):
         return int(load_library().rplgpu_pose_refine_check(C.byref(self)))
 
 
+class NavField(C.Structure):
+    """Mirror of ``rplgpu_nav_field_t`` (E26: a cost-to-goal field over a costmap, and the paths down it)."""
+
+    _fields_ = [(k, C.c_uint32) for k in (
+        "width", "height", "lethal", "neutral", "factor", "unknown_cost", "cap", "rounds")]
+
+    @classmethod
+    def defaults(cls, **kw) -> "NavField":
+        """The library's own defaults (``rplgpu_default_nav_field``), then the overrides; a width or height given
+        without ``rounds`` takes ``rplgpu_nav_field_default_rounds`` of the new size."""
+        f = cls()
+        lib = load_library()
+        lib.rplgpu_default_nav_field(C.byref(f))
+        for k, v in kw.items():
+            if not hasattr(f, k):
+                raise AttributeError(k)
+            setattr(f, k, v)
+        if "rounds" not in kw and ("width" in kw or "height" in kw):
+            f.rounds = int(lib.rplgpu_nav_field_default_rounds(f.width, f.height)) or f.rounds
+        return f
+
+    def check(self) -> int:
+        """``rplgpu_nav_field_check``: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_nav_field_check(C.byref(self)))
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -1043,6 +1088,18 @@ def load_library() -> C.CDLL:
                                         vp, u32, vp, u32, vp, vp, vp, vp, vp]
     lib.rplgpu_match_poses_dev.argtypes = [vp, vp, C.POINTER(ScanMatch), vp, vp, u32, vp, u64]
     lib.rplgpu_compose_poses_dev.argtypes = [vp, vp, u64, u32, u32, vp, u32, vp, u32, u32, vp]
+    lib.rplgpu_default_nav_field.argtypes = [C.POINTER(NavField)]
+    lib.rplgpu_default_nav_field.restype = None
+    lib.rplgpu_nav_field_check.argtypes = [C.POINTER(NavField)]
+    lib.rplgpu_nav_field_default_rounds.argtypes = [u32, u32]
+    lib.rplgpu_nav_field_default_rounds.restype = u32
+    lib.rplgpu_nav_field_scratch_words.argtypes = [C.POINTER(NavField), u32]
+    lib.rplgpu_nav_field_scratch_words.restype = u64
+    lib.rplgpu_nav_field_host.argtypes = [C.POINTER(NavField), vp, vp, u32, vp, vp]
+    lib.rplgpu_nav_path_host.argtypes = [C.POINTER(NavField), vp, vp, u32, vp, u32, vp]
+    lib.rplgpu_nav_field_dev.argtypes = [vp, C.POINTER(NavField), vp, u64, u32, vp, u64, vp, vp, u64, vp, u32, vp]
+    lib.rplgpu_nav_paths_dev.argtypes = [vp, C.POINTER(NavField), vp, u64, vp, u64, u32, vp, u32, vp, u32, vp]
+    lib.rplgpu_nav_field.argtypes = [vp, C.POINTER(NavField), vp, vp, u32, vp, vp, vp, u32, vp, u32, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1650,6 +1707,48 @@ class RplGpu:
         in front of the group's mount poses, six floats per scan at d_pose2d_out."""
         self._check(self._lib.rplgpu_compose_poses_dev(
             self._h, d_poses, pose_stride, poses_per_group, P, d_result, q, d_pose2d_in, B, group, d_pose2d_out))
+
+    def nav_field_dev(self, spec: "NavField", d_grid: int, grid_stride: int, G: int, d_goals: int, goal_stride: int,
+                      d_n_goals: int, d_potential: int, potential_stride: int, d_scratch: int, resume: int,
+                      d_result: int):
+        """E26: the cost-to-goal field of G costmaps, ``spec.rounds`` rounds queued on the stream; eight result words
+        at d_result + 8 g (word 0: the dirty tiles left, 0 = finished).  d_scratch: ``nav_field_scratch_words(spec,
+        G)`` uint32 words, which a call with ``resume`` = 1 continues from."""
+        self._check(self._lib.rplgpu_nav_field_dev(
+            self._h, C.byref(spec), d_grid, grid_stride, G, d_goals, goal_stride, d_n_goals, d_potential,
+            potential_stride, d_scratch, resume, d_result))
+
+    def nav_paths_dev(self, spec: "NavField", d_grid: int, grid_stride: int, d_potential: int, potential_stride: int,
+                      G: int, d_starts: int, S: int, d_paths: int, max_len: int, d_info: int):
+        """E26: S paths per grid down the field, path s of grid g at d_paths + (g S + s) max_len, four info words
+        at d_info + 4 (g S + s)."""
+        self._check(self._lib.rplgpu_nav_paths_dev(
+            self._h, C.byref(spec), d_grid, grid_stride, d_potential, potential_stride, G, d_starts, S, d_paths,
+            max_len, d_info))
+
+    def nav_field(self, spec: "NavField", grid: np.ndarray, goals, starts=None, max_len: int = 0, path_fill: int = 0):
+        """E26, one grid, host buffers: a (height, width) int8 costmap and goal cell indices -> ``(potential
+        (height, width) uint32, result (8,) uint32)``, with ``starts`` also ``paths (S, max_len) uint32`` (words
+        beyond a path keep ``path_fill``) and ``info (S, 4) uint32``."""
+        grid = np.ascontiguousarray(grid, np.int8)
+        if grid.shape != (spec.height, spec.width):
+            raise TypeError("grid must be a (height, width) int8 array")
+        goals = np.ascontiguousarray(goals, np.uint32).reshape(-1)
+        pot = np.zeros((spec.height, spec.width), np.uint32)
+        result = np.zeros(8, np.uint32)
+        if starts is None:
+            self._check(self._lib.rplgpu_nav_field(
+                self._h, C.byref(spec), grid.ctypes.data, goals.ctypes.data if len(goals) else 0, len(goals),
+                pot.ctypes.data, result.ctypes.data, 0, 0, 0, 0, 0))
+            return pot, result
+        starts = np.ascontiguousarray(starts, np.uint32).reshape(-1)
+        paths = np.full((len(starts), max_len), path_fill, np.uint32)
+        info = np.zeros((len(starts), 4), np.uint32)
+        self._check(self._lib.rplgpu_nav_field(
+            self._h, C.byref(spec), grid.ctypes.data, goals.ctypes.data if len(goals) else 0, len(goals),
+            pot.ctypes.data, result.ctypes.data, starts.ctypes.data, len(starts), paths.ctypes.data, max_len,
+            info.ctypes.data))
+        return pot, result, paths, info
 
     def resample_poses_dev(self, d_weights: int, weight_stride: int, d_poses: int, pose_stride: int,
                            poses_per_group: int, G: int, P: int, M: int, d_u: int, d_delta: int, n_delta: int,
@@ -2764,3 +2863,51 @@ def refine_covariance(sums, spec: PoseRefine):
     cov = np.zeros(9, np.float64)
     rc = load_library().rplgpu_refine_covariance(sums.ctypes.data, C.byref(spec), cov.ctypes.data)
     return cov.reshape(3, 3) if rc == OK else None
+
+
+def nav_field_check(spec: NavField) -> None:
+    """Host only: validates an E26 spec by the library's own rplgpu_nav_field_check; raises RplGpuError."""
+    rc = load_library().rplgpu_nav_field_check(C.byref(spec))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_nav_field_check")
+
+
+def nav_field_default_rounds(width: int, height: int) -> int:
+    """Host only: 2 (ntx + nty) + 2; 0 for a size the check refuses."""
+    return int(load_library().rplgpu_nav_field_default_rounds(width, height))
+
+
+def nav_field_scratch_words(spec: NavField, G: int) -> int:
+    """Host only: the uint32 words of scratch ``nav_field_dev`` takes; 0 when refused."""
+    return int(load_library().rplgpu_nav_field_scratch_words(C.byref(spec), G))
+
+
+def nav_field_host(spec: NavField, grid, goals):
+    """Host only: rplgpu_nav_field_host, the binary-heap Dijkstra -> ``(potential (height, width) uint32, result
+    (8,) uint32)``."""
+    grid = np.ascontiguousarray(grid, np.int8)
+    if spec.check() != OK or grid.shape != (spec.height, spec.width):
+        raise RplGpuError(ERR_INVALID_ARG, "nav_field_host: a checked spec and a (height, width) int8 grid")
+    goals = np.ascontiguousarray(goals, np.uint32).reshape(-1)
+    pot = np.zeros((spec.height, spec.width), np.uint32)
+    result = np.zeros(8, np.uint32)
+    rc = load_library().rplgpu_nav_field_host(C.byref(spec), grid.ctypes.data, goals.ctypes.data if len(goals) else 0,
+                                              len(goals), pot.ctypes.data, result.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_nav_field_host")
+    return pot, result
+
+
+def nav_path_host(spec: NavField, grid, potential, start: int, max_len: int, path_fill: int = 0):
+    """Host only: rplgpu_nav_path_host -> ``(path (max_len,) uint32, info (4,) uint32)``."""
+    grid = np.ascontiguousarray(grid, np.int8)
+    potential = np.ascontiguousarray(potential, np.uint32)
+    if spec.check() != OK or grid.shape != (spec.height, spec.width) or potential.shape != grid.shape or max_len < 1:
+        raise RplGpuError(ERR_INVALID_ARG, "nav_path_host: a checked spec, a grid and a potential of its shape")
+    path = np.full(max_len, path_fill, np.uint32)
+    info = np.zeros(4, np.uint32)
+    rc = load_library().rplgpu_nav_path_host(C.byref(spec), grid.ctypes.data, potential.ctypes.data, start,
+                                             path.ctypes.data, max_len, info.ctypes.data)
+    if rc < 0:
+        raise RplGpuError(rc, "rplgpu_nav_path_host")
+    return path, info

@@ -312,6 +312,34 @@ int main(int argc, char **argv) {
     }
     std::printf("pose refinement: %u of 1 poses stepped on %u point(s), %u too few\n", fr.stepped, fr.points,
                 fr.too_few);
+    // E26 over that costmap with lethal 100 and unknown cells at 60: the goal in the free cell (5, 1).  Cell (0, 1)
+    // (byte 36, weight 122) cannot pass the lethal cell (2, 1) along its row; steps 4 (+1, +1) and 6 (+1, -1) both cost
+    // 2260 + 7 * 122 = 3114 and the lower number wins, so its path runs below the row: cells 8 17 18 19 20 13.
+    rplgpu_nav_field_t nav;
+    rplgpu_default_nav_field(&nav);
+    nav.lethal = 100;
+    nav.unknown_cost = 60;
+    nav.rounds = 1;  // one tile: the door's second call finds nothing dirty
+    std::vector<uint32_t> potential, ninfo;
+    std::vector<std::vector<uint32_t>> npaths;
+    const std::vector<uint32_t> ngoals = {13u, 24u}, nstarts = {8u, 10u};
+    rplgpu_host::ScanPath::NavResult nr;
+    if (!path.nav_field(cost_msg, nav, ngoals, potential, nr, &nstarts, 16, &npaths, &ninfo)) {
+      std::fprintf(stderr, "cost-to-goal field failed: %s\n", path.last_error().c_str());
+      return 11;
+    }
+    static const uint32_t path_want[6] = {8, 17, 18, 19, 20, 13};
+    if (!nr.finished || nr.goals_taken != 1 || nr.goals_ignored != 1 || nr.reached != 23 || nr.greatest != 3500 ||
+        potential.size() != 24 || potential[8] != 3114 || potential[10] != RPLGPU_NAV_UNREACHED || potential[13] != 0 ||
+        npaths.size() != 2 || npaths[0].size() != 6 || std::memcmp(npaths[0].data(), path_want, 24) != 0 ||
+        ninfo[1] != RPLGPU_NAV_PATH_REACHED || ninfo[2] != 3114 || !npaths[1].empty() ||
+        ninfo[5] != RPLGPU_NAV_PATH_UNREACHED) {
+      std::fprintf(stderr, "cost-to-goal field: wrong answer (%u reached, greatest %u, %u from cell 8)\n", nr.reached,
+                   nr.greatest, potential.size() == 24 ? potential[8] : 0u);
+      return 12;
+    }
+    std::printf("cost-to-goal field: %u cells reached, %u from cell 8 over %zu cells, %u tile visit(s)\n", nr.reached,
+                potential[8], npaths[0].size(), nr.tile_visits);
     // E14: the three rays of the E11 leg added twice into a count map.  Per call the row of the sensor gets
     // misses 3 3 2 2 1 1 (the whole ray beyond obstacle_max leaves its end cell 4 alone, the cut one counts its
     // end cell 5) and one hit in cell 2; after two calls the default rule (2 observations, 10 %) gives the E11 row.

@@ -22,6 +22,8 @@
 //         -> rplgpu_host::ScanPath::fill_occupancy_grid(scans, ..., grid_msg)   (E11)
 //   inf the consumer's second loop (a costmap inflation layer over that grid):
 //         -> rplgpu_host::ScanPath::inflate_grid(grid_msg, inflation, costmap_msg)  (E12)
+//   nav the planning side's first loop (a navigation function over that costmap, and the paths down it):
+//         -> rplgpu_host::ScanPath::nav_field(costmap_msg, rule, goals, potential, result, starts, ...)  (E26)
 //   mat the localisation side's loop (a correlative scan matcher's search window over a likelihood field):
 //         -> rplgpu_host::ScanPath::match_scans(scans, ..., field_msg, window, result)  (E13)
 //         -> rplgpu_host::ScanPath::match_wide(scans, ..., field_msg, window, result)   (E24: up to 256 cells a side)
@@ -566,6 +568,57 @@ class ScanPath {
     result.best_index = res[4];
     result.best_sum = (static_cast<uint64_t>(res[6]) << 32) | res[5];
     result.points = res[7];
+    return true;
+  }
+
+  // ext E26 (include/rplgpu_msg.h): the cost-to-goal field over `costmap_msg` (E12's output, or any OccupancyGrid) —
+  // NavFn's potential — and, with `starts`, the paths down it.  goals and starts are cell indices (y * width + x);
+  // lethal / neutral / factor / unknown_cost / cap / rounds of `rule` are used, its size comes from costmap_msg.info.
+  // potential: width x height words, RPLGPU_NAV_UNREACHED where no goal is in reach.  paths (with starts): one list of
+  // cells per start, the start first; info: the four words per path.  The door resumes until the field is finished.
+  struct NavResult {
+    uint32_t dirty_tiles = 0, goals_taken = 0, goals_ignored = 0, reached = 0, greatest = 0, tile_visits = 0, rounds = 0;
+    bool finished = false;
+  };
+  template <class OccupancyGridT>
+  bool nav_field(const OccupancyGridT &costmap_msg, const rplgpu_nav_field_t &rule, const std::vector<uint32_t> &goals,
+                 std::vector<uint32_t> &potential, NavResult &result, const std::vector<uint32_t> *starts = nullptr,
+                 uint32_t max_len = 0, std::vector<std::vector<uint32_t>> *paths = nullptr,
+                 std::vector<uint32_t> *info = nullptr) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    rplgpu_nav_field_t f = rule;
+    f.width = costmap_msg.info.width;
+    f.height = costmap_msg.info.height;
+    const size_t n_cells = static_cast<size_t>(f.width) * f.height;
+    if (n_cells == 0 || costmap_msg.data.size() != n_cells) return fail("nav_field: data is not width x height");
+    const bool with_paths = starts && !starts->empty();
+    if (with_paths && (!paths || !info || max_len == 0)) return fail("nav_field: starts need paths, info and max_len");
+    occ_prev_.assign(costmap_msg.data.begin(), costmap_msg.data.end());
+    potential.assign(n_cells, RPLGPU_NAV_UNREACHED);
+    const uint32_t S = with_paths ? static_cast<uint32_t>(starts->size()) : 0u;
+    std::vector<uint32_t> flat(static_cast<size_t>(S) * max_len, RPLGPU_NAV_UNREACHED);
+    if (with_paths) info->assign(4u * static_cast<size_t>(S), 0u);
+    uint32_t res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_nav_field(h_, &f, occ_prev_.data(), goals.empty() ? nullptr : goals.data(),
+                         static_cast<uint32_t>(goals.size()), potential.data(), res,
+                         with_paths ? starts->data() : nullptr, S, with_paths ? flat.data() : nullptr, max_len,
+                         with_paths ? info->data() : nullptr) != RPLGPU_OK)
+      return note_error();
+    if (with_paths) {
+      paths->assign(S, std::vector<uint32_t>());
+      for (uint32_t s = 0; s < S; ++s)
+        (*paths)[s].assign(flat.begin() + static_cast<size_t>(s) * max_len,
+                           flat.begin() + static_cast<size_t>(s) * max_len + (*info)[4u * s]);
+    }
+    result.dirty_tiles = res[0];
+    result.finished = res[0] == 0;
+    result.goals_taken = res[2];
+    result.goals_ignored = res[3];
+    result.reached = res[4];
+    result.greatest = res[5];
+    result.tile_visits = res[6];
+    result.rounds = res[7];
     return true;
   }
 
