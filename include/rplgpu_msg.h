@@ -1967,6 +1967,129 @@ int32_t rplgpu_nav_field(rplgpu_handle_t h, const rplgpu_nav_field_t *f, const i
                          uint32_t n_goals, uint32_t *potential, uint32_t result[8], const uint32_t *starts,
                          uint32_t S, uint32_t *paths, uint32_t max_len, uint32_t *info);
 
+/* ---- E27: candidate motions rolled out of a pose and scored (row 4; the first reader of E26's field) ----
+ * E11 -> E12 -> E26 end in a costmap and a cost-to-goal field D; the local planner is what reads both.  DWB / DWA rolls
+ * constant-velocity arcs out of the current pose and scores them by the worst cost under the footprint along the arc
+ * (ObstacleFootprint) and by look-ups into the field (GoalDist / PathDist); MPPI does the same with noisy control
+ * sequences, which E18 already writes on the device.  The roll's step is E16's MOVE, the look-up E15's transform and
+ * E11's CELL.  Nothing in the reference plans or controls, so these rules ARE the definition (parity unpinned, as
+ * E5-E26).  float32 operations, each rounded once, no FMA, IEEE divides; after the cell rule everything is integers:
+ * the result depends on no order.
+ *
+ * START of group g: four floats (c, s, x, y) at d_start + 4 g_s, E15's pose form; g_s = g when start_per_group is
+ * not 0, else 0; 16-byte aligned.  Any values are defined: the device evaluates no trigonometric function and does
+ * not renormalise.
+ * DELTAS: four floats (dc, ds, dx, dy) each, E16 / E18's layout, at d_delta + g_d * delta_stride (g_d = g when
+ * delta_per_group is not 0, else 0; 16-byte aligned; delta_stride in floats and a multiple of 4).
+ *   delta_per_step = 0: candidate k has the ONE delta at 4 k and applies it T times (an arc); delta_stride >= 4 K.
+ *   delta_per_step = 1: step t (1-based) of candidate k uses the delta at 4 (k T + t - 1) (a control sequence);
+ *   delta_stride >= 4 K T.  This is the output of rplgpu_sample_motion_dev with M = K T.
+ * ROLL: pose_0 is the start; pose_t = pose_(t-1) composed with the delta on the right by E16's MOVE, operation for
+ * operation:  c' = c*dc - s*ds;  s' = s*dc + c*ds;  x' = (c*dx - s*dy) + x;  y' = (s*dx + c*dy) + y;  a NaN result
+ * is 0x7FC00000.  The composition is sequential by definition (float rounding is not associative).
+ * FOOTPRINT: F points (fx, fy), 1 <= F <= RPLGPU_ROLLOUT_MAX_FOOTPRINT, two floats each at d_footprint (8-byte
+ * aligned), one list for the whole call, in the base frame; (0, 0) alone is "the centre".  At pose t a point is at
+ *   rx = (c*fx - s*fy) + x;   ry = (s*fx + c*fy) + y
+ * and its cell is E11's CELL in the spec's grid.  Its VALUE p:
+ *   no cell (NaN, Inf, a magnitude >= 1048576 cells): BLOCKED, and the point is OFF RANGE;
+ *   a cell outside [0, width) x [0, height): BLOCKED;
+ *   else v = (int8)d_grid[g_c * grid_stride + cy * width + cx] (E12's output layout, E26's stride rules; g_c = g
+ *   when grid_per_group is not 0, else 0);  p = v for v >= 0, else unknown_value;  p >= lethal is BLOCKED.
+ * Pose t is BLOCKED when any of its points is; else m_t = the max of p over its points.
+ * CANDIDATE: n = the number of poses before the first blocked one among t = 1 .. T (T when none); poses behind n
+ * contribute nothing.  cost_sum = the sum of m_t over t = 1 .. n, cost_max their max (0 when n = 0).  The CENTRE of
+ * pose t is the cell of (x_t, y_t) itself; D_t = the word of d_potential (E26's layout: d_potential + g_c *
+ * potential_stride) at that cell, RPLGPU_NAV_UNREACHED without a cell or outside the grid.  D_end = D_n, D_min = the
+ * min of D_t over t = 1 .. n, both UNREACHED when n = 0; with d_potential NULL both are 0 whatever n.
+ *   FLAGS: RPLGPU_ROLLOUT_BLOCKED n < T;  RPLGPU_ROLLOUT_CELL_RANGE n < T and a point of pose n + 1, the first
+ *   blocked one, is off range;  RPLGPU_ROLLOUT_END_UNREACHED d_potential given and D_end UNREACHED;
+ *   RPLGPU_ROLLOUT_ADMISSIBLE n >= min_steps and not END_UNREACHED.
+ *   SCORE, uint64: a_end*D_end + a_min*D_min + a_sum*cost_sum + a_max*cost_max (below 2^50) when admissible (D_min
+ *   is then reached, because D_n is among its terms), else 2^64 - 1.
+ * OUTPUT, eight words per candidate at d_out + g * out_stride + 8 k (out_stride in words, >= 8 K and a multiple of
+ * 4; 16-byte aligned): 0 n, 1 the flags, 2 cost_sum, 3 cost_max, 4 D_end, 5 D_min, 6 and 7 the score, low and high.
+ * pose_n (the start's 16 bytes bit for bit when n = 0) goes to d_end_poses + g * end_stride + 4 k when that is given
+ * (E15's list form, so that it chains: end_stride in floats, >= 4 K and a multiple of 4; 16-byte aligned).  Words at
+ * and beyond K of a group are never changed.
+ * RESULT, eight words per group at d_result + 8 g: 0 the admissible candidates, 1 the smallest k with the lowest
+ * score among them (RPLGPU_ROLLOUT_NONE when none), 2 and 3 that score (all ones when none), 4 how many admissible
+ * candidates have it (0 when none), 5 the candidates with BLOCKED, 6 those with CELL_RANGE, 7 flags (bit 0: none is
+ * admissible).
+ * AN IDENTITY that holds independent code to each other: with a footprint that is never blocked, d_end_poses of
+ * (T, delta_per_step = 0) equals T chained calls of E16's move (rplgpu_resample_poses_dev with P = 1, weight 1,
+ * M = K, n_delta = M; likewise rplgpu_resample_host), byte for byte. */
+#define RPLGPU_ROLLOUT_MAX_STEPS      256u
+#define RPLGPU_ROLLOUT_MAX_FOOTPRINT   64u
+#define RPLGPU_ROLLOUT_MAX_WEIGHT   65535u
+#define RPLGPU_ROLLOUT_NONE    0xFFFFFFFFu
+#define RPLGPU_ROLLOUT_TILE            32u   /* candidates a workgroup takes: one scratch record each */
+#define RPLGPU_ROLLOUT_MAX_TILES 0x800000u   /* G * ceil(K / tile) of one call: the launch stays below 2^32 threads */
+#define RPLGPU_ROLLOUT_BLOCKED        0x1u
+#define RPLGPU_ROLLOUT_CELL_RANGE     0x2u
+#define RPLGPU_ROLLOUT_END_UNREACHED  0x4u
+#define RPLGPU_ROLLOUT_ADMISSIBLE     0x8u
+typedef struct rplgpu_rollout {
+  float    origin_x, origin_y, resolution;  /* the costmap's grid, as rplgpu_pose_score_t */
+  uint32_t width, height;                   /* 1 .. RPLGPU_MAX_OCC_DIM */
+  uint32_t lethal;         /* 1 .. 100: a value at or above it blocks (E26's meaning) */
+  uint32_t unknown_value;  /* 0 .. 100: what a negative byte counts as; at or above lethal it blocks */
+  uint32_t steps;          /* T, 1 .. RPLGPU_ROLLOUT_MAX_STEPS */
+  uint32_t min_steps;      /* 1 .. T: unblocked poses a candidate needs to be admissible (T = DWB's rule) */
+  uint32_t a_end, a_min, a_sum, a_max;  /* 0 .. RPLGPU_ROLLOUT_MAX_WEIGHT: the four critics' scales */
+} rplgpu_rollout_t;
+/* E11's grid (0.05 m, 1024 x 1024, origin (-25.6, -25.6)), lethal 99, unknown_value 100, steps 32, min_steps 32,
+ * a_end 1, a_min 0, a_sum 1, a_max 0 */
+void rplgpu_default_rollout(rplgpu_rollout_t *r);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL, a grid value that is not finite,
+ * resolution <= 0, a value outside the ranges above, min_steps > steps.  The device path uses this function. */
+int32_t rplgpu_rollout_check(const rplgpu_rollout_t *r);
+/* Host only: the uint32 words of scratch the device call takes, 8 * ceil(K / RPLGPU_ROLLOUT_TILE) * G (a record of
+ * eight words per workgroup); 0 for G = 0 or above 65535, a K outside 1 .. RPLGPU_MAX_POSES or G * ceil(K /
+ * RPLGPU_ROLLOUT_TILE) above RPLGPU_ROLLOUT_MAX_TILES. */
+uint64_t rplgpu_rollout_scratch_words(uint32_t G, uint32_t K);
+/* Host only, a convenience that is NOT part of the byte-exact contract (as rplgpu_motion_odometry is not): K body
+ * velocities (vx, vy, w), three doubles each, held for dt seconds become K deltas of four floats.  In fp64:
+ * th = w dt, dc = cos th, ds = sin th; for |th| < 1e-9 dx = vx dt, dy = vy dt, else the exact arc
+ * dx = (vx sin th - vy (1 - cos th)) / w, dy = (vx (1 - cos th) + vy sin th) / w; each value rounded once to float.
+ * w = 0 gives exactly (1, 0, vx dt, vy dt).  RPLGPU_ERR_INVALID_ARG for a NULL pointer, K = 0 or above
+ * RPLGPU_MAX_POSES. */
+int32_t rplgpu_rollout_deltas(const double *vxyw, uint32_t K, double dt, float *delta_out);
+/* Host only: the rules above in plain C++ for ONE group, the definition a reader can run.  start: 4 floats; delta:
+ * 4 K floats, or 4 K T with delta_per_step = 1; footprint: 2 F floats; grid: width * height bytes; potential: NULL
+ * or width * height words; out: 8 K words; end_poses (optional): 4 K floats; result: 8 words.
+ * RPLGPU_ERR_INVALID_ARG and nothing written for a spec the check refuses, a NULL start / delta / footprint / grid /
+ * out / result, K = 0 or above RPLGPU_MAX_POSES, K * T above 2^24, F outside 1 .. RPLGPU_ROLLOUT_MAX_FOOTPRINT,
+ * delta_per_step above 1. */
+int32_t rplgpu_rollout_host(const rplgpu_rollout_t *r, const float *start, const float *delta,
+                            uint32_t delta_per_step, const float *footprint, uint32_t F, const int8_t *grid,
+                            const uint32_t *potential, uint32_t K, uint32_t *out, float *end_poses,
+                            uint32_t result[8]);
+/* K candidates for each of G groups on the handle's stream: two launches (a workgroup per tile of
+ * RPLGPU_ROLLOUT_TILE candidates of one group, then one workgroup per group that folds the tiles' records), no
+ * workgroup waits for another, nothing is stored on the handle.  d_scratch: rplgpu_rollout_scratch_words of (G, K)
+ * words, 16-byte aligned, the caller's; it holds nothing a later call relies on.  d_grid 4-byte aligned, grid_stride
+ * >= width * height and a multiple of 4; d_potential NULL or 4-byte aligned with potential_stride >= width * height;
+ * both only read, as the start, the deltas and the footprint are.
+ * RPLGPU_ERR_INVALID_ARG, no output changed and nothing queued, for a spec the check refuses, G = 0 or above 65535,
+ * K = 0 or above RPLGPU_MAX_POSES, K * T above 2^24, F outside 1 .. RPLGPU_ROLLOUT_MAX_FOOTPRINT, delta_per_step
+ * above 1, a missing d_start / d_delta / d_footprint / d_grid / d_out / d_result / d_scratch, a misaligned pointer
+ * (16 bytes: d_start, d_delta, d_out, d_end_poses, d_scratch; 8: d_footprint; 4: the others), the stride rules
+ * above, and an output (d_out, d_end_poses, d_result, d_scratch) that overlaps an input or another output over the
+ * ranges used; RPLGPU_ERR_CAPACITY for G * ceil(K / RPLGPU_ROLLOUT_TILE) above RPLGPU_ROLLOUT_MAX_TILES = 2^23.
+ * Asynchronous on the handle's stream. */
+int32_t rplgpu_rollout_dev(rplgpu_handle_t h, const rplgpu_rollout_t *r, const float *d_start,
+                           uint32_t start_per_group, const float *d_delta, uint64_t delta_stride,
+                           uint32_t delta_per_group, uint32_t delta_per_step, const float *d_footprint, uint32_t F,
+                           const int8_t *d_grid, uint64_t grid_stride, const uint32_t *d_potential,
+                           uint64_t potential_stride, uint32_t grid_per_group, uint32_t G, uint32_t K,
+                           uint32_t *d_out, uint64_t out_stride, float *d_end_poses, uint64_t end_stride,
+                           uint32_t *d_result, uint32_t *d_scratch);
+/* ONE group, HOST buffers (the node-side door, rplgpu_host.hpp), arguments as rplgpu_rollout_host.  Allocates its
+ * device buffers and scratch per call and returns when the results are in place: a door, not a hot path. */
+int32_t rplgpu_rollout(rplgpu_handle_t h, const rplgpu_rollout_t *r, const float *start, const float *delta,
+                       uint32_t delta_per_step, const float *footprint, uint32_t F, const int8_t *grid,
+                       const uint32_t *potential, uint32_t K, uint32_t *out, float *end_poses, uint32_t result[8]);
+
 #ifdef __cplusplus
 }
 #endif

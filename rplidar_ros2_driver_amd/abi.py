@@ -50,6 +50,13 @@ NAV_MAX_TILES = 1 << 23       # RPLGPU_NAV_MAX_TILES: G x tiles of one call
 NAV_UNREACHED = 0xFFFFFFFF    # RPLGPU_NAV_UNREACHED
 NAV_UNFINISHED = 0x01         # RPLGPU_NAV_UNFINISHED (result word 1)
 NAV_PATH_REACHED, NAV_PATH_NO_START, NAV_PATH_UNREACHED, NAV_PATH_TRUNCATED, NAV_PATH_BROKEN = 1, 2, 4, 8, 16
+ROLLOUT_MAX_STEPS = 256       # RPLGPU_ROLLOUT_MAX_STEPS (E27)
+ROLLOUT_MAX_FOOTPRINT = 64    # RPLGPU_ROLLOUT_MAX_FOOTPRINT
+ROLLOUT_MAX_WEIGHT = 65535    # RPLGPU_ROLLOUT_MAX_WEIGHT
+ROLLOUT_NONE = 0xFFFFFFFF     # RPLGPU_ROLLOUT_NONE (result word 1)
+ROLLOUT_TILE = 32             # RPLGPU_ROLLOUT_TILE: candidates a workgroup takes
+ROLLOUT_MAX_TILES = 1 << 23   # RPLGPU_ROLLOUT_MAX_TILES: G x tiles of one call
+ROLLOUT_BLOCKED, ROLLOUT_CELL_RANGE, ROLLOUT_END_UNREACHED, ROLLOUT_ADMISSIBLE = 1, 2, 4, 8
 REFINE_PLANES = 29            # RPLGPU_REFINE_PLANES
 REFINE_MAX_ITERS = 16         # RPLGPU_REFINE_MAX_ITERS
 REFINE_STEPPED = 0x01         # E25's step flags
@@ -242,6 +249,13 @@ ABI_SYMBOLS = [
     "rplgpu_nav_field_dev",
     "rplgpu_nav_paths_dev",
     "rplgpu_nav_field",
+    "rplgpu_default_rollout",
+    "rplgpu_rollout_check",
+    "rplgpu_rollout_scratch_words",
+    "rplgpu_rollout_deltas",
+    "rplgpu_rollout_host",
+    "rplgpu_rollout_dev",
+    "rplgpu_rollout",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -789,6 +803,31 @@ class NavField(C.Structure):
         return int(load_library().rplgpu_nav_field_check(C.byref(self)))
 
 
+class Rollout(C.Structure):
+    """Mirror of ``rplgpu_rollout_t`` (E27: candidate motions rolled out of a pose and scored)."""
+
+    _fields_ = [(k, C.c_float) for k in ("origin_x", "origin_y", "resolution")] + [(k, C.c_uint32) for k in (
+        "width", "height", "lethal", "unknown_value", "steps", "min_steps", "a_end", "a_min", "a_sum", "a_max")]
+
+    @classmethod
+    def defaults(cls, **kw) -> "Rollout":
+        """The library's own defaults (``rplgpu_default_rollout``), then the overrides; ``steps`` given without
+        ``min_steps`` takes ``min_steps = steps`` (DWB's rule)."""
+        r = cls()
+        load_library().rplgpu_default_rollout(C.byref(r))
+        for k, v in kw.items():
+            if not hasattr(r, k):
+                raise AttributeError(k)
+            setattr(r, k, v)
+        if "steps" in kw and "min_steps" not in kw:
+            r.min_steps = r.steps
+        return r
+
+    def check(self) -> int:
+        """``rplgpu_rollout_check``: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_rollout_check(C.byref(self)))
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -1100,6 +1139,16 @@ def load_library() -> C.CDLL:
     lib.rplgpu_nav_field_dev.argtypes = [vp, C.POINTER(NavField), vp, u64, u32, vp, u64, vp, vp, u64, vp, u32, vp]
     lib.rplgpu_nav_paths_dev.argtypes = [vp, C.POINTER(NavField), vp, u64, vp, u64, u32, vp, u32, vp, u32, vp]
     lib.rplgpu_nav_field.argtypes = [vp, C.POINTER(NavField), vp, vp, u32, vp, vp, vp, u32, vp, u32, vp]
+    lib.rplgpu_default_rollout.argtypes = [C.POINTER(Rollout)]
+    lib.rplgpu_default_rollout.restype = None
+    lib.rplgpu_rollout_check.argtypes = [C.POINTER(Rollout)]
+    lib.rplgpu_rollout_scratch_words.argtypes = [u32, u32]
+    lib.rplgpu_rollout_scratch_words.restype = u64
+    lib.rplgpu_rollout_deltas.argtypes = [vp, u32, C.c_double, vp]
+    lib.rplgpu_rollout_host.argtypes = [C.POINTER(Rollout), vp, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp]
+    lib.rplgpu_rollout_dev.argtypes = [vp, C.POINTER(Rollout), vp, u32, vp, u64, u32, u32, vp, u32, vp, u64, vp, u64,
+                                       u32, u32, u32, vp, u64, vp, u64, vp, vp]
+    lib.rplgpu_rollout.argtypes = [vp, C.POINTER(Rollout), vp, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1749,6 +1798,28 @@ class RplGpu:
             pot.ctypes.data, result.ctypes.data, starts.ctypes.data, len(starts), paths.ctypes.data, max_len,
             info.ctypes.data))
         return pot, result, paths, info
+
+    def rollout_dev(self, spec: "Rollout", d_start: int, start_per_group: int, d_delta: int, delta_stride: int,
+                    delta_per_group: int, delta_per_step: int, d_footprint: int, F: int, d_grid: int,
+                    grid_stride: int, d_potential: int, potential_stride: int, grid_per_group: int, G: int, K: int,
+                    d_out: int, out_stride: int, d_end_poses: int, end_stride: int, d_result: int, d_scratch: int):
+        """E27: K candidates per group rolled ``spec.steps`` steps out of the group's start pose by their deltas (one
+        each, or one per step with ``delta_per_step``), the F footprint points looked up in the costmap at d_grid and
+        the centre in E26's field at d_potential (0: none); eight words per candidate at d_out + g out_stride + 8 k,
+        the end poses (optional) and eight result words at d_result + 8 g.  d_scratch:
+        ``rollout_scratch_words(G, K)`` uint32 words."""
+        self._check(self._lib.rplgpu_rollout_dev(
+            self._h, C.byref(spec), d_start, start_per_group, d_delta, delta_stride, delta_per_group, delta_per_step,
+            d_footprint, F, d_grid, grid_stride, d_potential, potential_stride, grid_per_group, G, K, d_out,
+            out_stride, d_end_poses, end_stride, d_result, d_scratch))
+
+    def rollout(self, spec: "Rollout", start, delta, footprint, grid, potential=None):
+        """E27, one group, host buffers: start (4,) float32, delta (K, 4) or (K, steps, 4) float32, footprint (F, 2)
+        float32, a (height, width) int8 costmap and optionally E26's field of the same shape -> ``(out (K, 8) uint32,
+        end_poses (K, 4) float32, result (8,) uint32)``."""
+        a = _rollout_args(spec, start, delta, footprint, grid, potential)
+        self._check(self._lib.rplgpu_rollout(self._h, C.byref(spec), *a[0]))
+        return a[1]
 
     def resample_poses_dev(self, d_weights: int, weight_stride: int, d_poses: int, pose_stride: int,
                            poses_per_group: int, G: int, P: int, M: int, d_u: int, d_delta: int, n_delta: int,
@@ -2911,3 +2982,61 @@ def nav_path_host(spec: NavField, grid, potential, start: int, max_len: int, pat
     if rc < 0:
         raise RplGpuError(rc, "rplgpu_nav_path_host")
     return path, info
+
+
+def rollout_check(spec: Rollout) -> None:
+    """Host only: validates an E27 spec by the library's own rplgpu_rollout_check; raises RplGpuError."""
+    rc = load_library().rplgpu_rollout_check(C.byref(spec))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_rollout_check")
+
+
+def rollout_scratch_words(G: int, K: int) -> int:
+    """Host only: the uint32 words of scratch ``rollout_dev`` takes; 0 when refused."""
+    return int(load_library().rplgpu_rollout_scratch_words(G, K))
+
+
+def rollout_deltas(vxyw, dt: float) -> np.ndarray:
+    """Host only: K body velocities (vx, vy, w) held for dt seconds -> the (K, 4) float32 deltas of E27's arcs, by
+    the library's own rplgpu_rollout_deltas."""
+    vxyw = np.ascontiguousarray(vxyw, np.float64).reshape(-1, 3)
+    out = np.zeros((max(len(vxyw), 1), 4), np.float32)
+    rc = load_library().rplgpu_rollout_deltas(vxyw.ctypes.data, len(vxyw), dt, out.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_rollout_deltas")
+    return out
+
+
+def _rollout_args(spec, start, delta, footprint, grid, potential):
+    """-> (the arguments behind the spec, (out, end_poses, result)); the arrays stay alive in the first tuple."""
+    start = np.ascontiguousarray(start, np.float32).reshape(-1)
+    delta = np.ascontiguousarray(delta, np.float32)
+    footprint = np.ascontiguousarray(footprint, np.float32).reshape(-1, 2)
+    grid = np.ascontiguousarray(grid, np.int8)
+    per_step = 1 if delta.ndim == 3 else 0
+    if start.shape != (4,) or delta.ndim not in (2, 3) or delta.shape[-1] != 4 or len(delta) == 0 or \
+            (per_step and delta.shape[1] != spec.steps) or grid.shape != (spec.height, spec.width):
+        raise TypeError("start (4,), delta (K, 4) or (K, steps, 4), footprint (F, 2), grid (height, width) int8")
+    if potential is not None:
+        potential = np.ascontiguousarray(potential, np.uint32)
+        if potential.shape != grid.shape:
+            raise TypeError("potential must have the grid's shape")
+    K = len(delta)
+    out = np.zeros((K, 8), np.uint32)
+    end = np.zeros((K, 4), np.float32)
+    result = np.zeros(8, np.uint32)
+    keep = (start, delta, footprint, grid, potential)
+    args = (start.ctypes.data, delta.ctypes.data, per_step, footprint.ctypes.data, len(footprint), grid.ctypes.data,
+            0 if potential is None else potential.ctypes.data, K, out.ctypes.data, end.ctypes.data,
+            result.ctypes.data)
+    return args, (out, end, result), keep
+
+
+def rollout_host(spec: Rollout, start, delta, footprint, grid, potential=None):
+    """Host only: E27's rules for one group by the library's own rplgpu_rollout_host (no handle, no device);
+    arguments and results as ``RplGpu.rollout``."""
+    a = _rollout_args(spec, start, delta, footprint, grid, potential)
+    rc = load_library().rplgpu_rollout_host(C.byref(spec), *a[0])
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_rollout_host")
+    return a[1]

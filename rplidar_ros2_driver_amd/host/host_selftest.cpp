@@ -340,6 +340,35 @@ int main(int argc, char **argv) {
     }
     std::printf("cost-to-goal field: %u cells reached, %u from cell 8 over %zu cells, %u tile visit(s)\n", nr.reached,
                 potential[8], npaths[0].size(), nr.tile_visits);
+    // E27 over that costmap and field: from the goal cell (5, 1) heading west, candidate 0 moves a cell a step — cell 4
+    // (36), cell 3 (99, below lethal 100), then the lethal cell 2: D_end is the field at cell 11, D_min at cell 12 —
+    // and candidate 1 stays where D = 0 and the cost is 0.
+    rplgpu_rollout_t roll;
+    rplgpu_default_rollout(&roll);
+    roll.lethal = 100;
+    roll.unknown_value = 60;
+    roll.steps = 4;
+    roll.min_steps = 2;
+    const double roll_start[3] = {5.0, 0.0, 3.14159265358979323846};
+    const std::vector<float> roll_deltas = {1.0f, 0.0f, 1.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f}, roll_fp = {0.0f, 0.0f};
+    std::vector<uint32_t> roll_out;
+    std::vector<float> roll_ends;
+    rplgpu_host::ScanPath::RolloutResult ro_res;
+    if (!path.rollout(cost_msg, roll, roll_start, roll_deltas, false, roll_fp, &potential, roll_out, ro_res, &roll_ends)) {
+      std::fprintf(stderr, "rollout failed: %s\n", path.last_error().c_str());
+      return 11;
+    }
+    if (roll_out.size() != 16 || roll_out[0] != 2 || roll_out[1] != (RPLGPU_ROLLOUT_BLOCKED | RPLGPU_ROLLOUT_ADMISSIBLE) ||
+        roll_out[2] != 135 || roll_out[3] != 99 || roll_out[4] != potential[11] || roll_out[5] != potential[12] ||
+        roll_out[6] != potential[11] + 135 || roll_out[8] != 4 || roll_out[9] != RPLGPU_ROLLOUT_ADMISSIBLE ||
+        roll_out[14] != 0 || ro_res.admissible != 2 || ro_res.best_index != 1 || ro_res.best_score != 0 || ro_res.ties != 1 ||
+        ro_res.blocked != 1 || ro_res.cell_range != 0 || ro_res.none || roll_ends[2] != 3.0f || roll_ends[6] != 5.0f) {
+      std::fprintf(stderr, "rollout: wrong answer (n %u, cost %u, D %u, best %u)\n", roll_out.empty() ? 0u : roll_out[0],
+                   roll_out.empty() ? 0u : roll_out[2], roll_out.empty() ? 0u : roll_out[4], ro_res.best_index);
+      return 12;
+    }
+    std::printf("rollout: candidate 0 blocked after %u poses (cost %u, D %u), candidate %u wins of %u admissible\n",
+                roll_out[0], roll_out[2], roll_out[4], ro_res.best_index, ro_res.admissible);
     // E14: the three rays of the E11 leg added twice into a count map.  Per call the row of the sensor gets
     // misses 3 3 2 2 1 1 (the whole ray beyond obstacle_max leaves its end cell 4 alone, the cut one counts its
     // end cell 5) and one hit in cell 2; after two calls the default rule (2 observations, 10 %) gives the E11 row.

@@ -24,6 +24,7 @@
 //         -> rplgpu_host::ScanPath::inflate_grid(grid_msg, inflation, costmap_msg)  (E12)
 //   nav the planning side's first loop (a navigation function over that costmap, and the paths down it):
 //         -> rplgpu_host::ScanPath::nav_field(costmap_msg, rule, goals, potential, result, starts, ...)  (E26)
+//         -> rplgpu_host::ScanPath::rollout(costmap_msg, rule, start, deltas, per_step, footprint, potential, ...)  (E27)
 //   mat the localisation side's loop (a correlative scan matcher's search window over a likelihood field):
 //         -> rplgpu_host::ScanPath::match_scans(scans, ..., field_msg, window, result)  (E13)
 //         -> rplgpu_host::ScanPath::match_wide(scans, ..., field_msg, window, result)   (E24: up to 256 cells a side)
@@ -619,6 +620,59 @@ class ScanPath {
     result.greatest = res[5];
     result.tile_visits = res[6];
     result.rounds = res[7];
+    return true;
+  }
+
+  // ext E27 (include/rplgpu_msg.h): candidate motions rolled out of the pose `start_xyt` (x, y, theta in the costmap's
+  // frame; it goes through rplgpu_pose_list) and scored — DWB's / MPPI's inner loop.  deltas: four floats per
+  // candidate (rplgpu_rollout_deltas makes them from body velocities), or per candidate and step with per_step;
+  // footprint: (x, y) pairs in the base frame; potential: E26's field over the same grid (nav_field's output), or null.
+  // lethal / unknown_value / steps / min_steps and the four scales of `rule` are used, its grid comes from
+  // costmap_msg.info (origin orientation must be the identity).  out: the eight words per candidate; end_poses
+  // (optional): four floats per candidate.
+  struct RolloutResult {
+    uint32_t admissible = 0, best_index = RPLGPU_ROLLOUT_NONE, ties = 0, blocked = 0, cell_range = 0;
+    uint64_t best_score = ~0ull;
+    bool none = true;
+  };
+  template <class OccupancyGridT>
+  bool rollout(const OccupancyGridT &costmap_msg, const rplgpu_rollout_t &rule, const double start_xyt[3],
+               const std::vector<float> &deltas, bool per_step, const std::vector<float> &footprint,
+               const std::vector<uint32_t> *potential, std::vector<uint32_t> &out, RolloutResult &result,
+               std::vector<float> *end_poses = nullptr) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    rplgpu_rollout_t r = rule;
+    r.origin_x = static_cast<float>(costmap_msg.info.origin.position.x);
+    r.origin_y = static_cast<float>(costmap_msg.info.origin.position.y);
+    r.resolution = costmap_msg.info.resolution;
+    r.width = costmap_msg.info.width;
+    r.height = costmap_msg.info.height;
+    const size_t n_cells = static_cast<size_t>(r.width) * r.height;
+    if (n_cells == 0 || costmap_msg.data.size() != n_cells) return fail("rollout: data is not width x height");
+    if (potential && potential->size() != n_cells) return fail("rollout: the potential is not width x height");
+    const size_t per = 4u * (per_step ? static_cast<size_t>(r.steps) : 1u);
+    if (per == 0 || deltas.empty() || deltas.size() % per != 0) return fail("rollout: deltas must be 4 floats per candidate (and step)");
+    if (footprint.empty() || footprint.size() % 2 != 0) return fail("rollout: footprint must be (x, y) pairs");
+    const uint32_t K = static_cast<uint32_t>(deltas.size() / per);
+    float start[4];
+    if (rplgpu_pose_list(start_xyt, 1, start) != RPLGPU_OK) return fail("rollout: start pose");
+    occ_prev_.assign(costmap_msg.data.begin(), costmap_msg.data.end());
+    out.assign(8u * static_cast<size_t>(K), 0u);
+    if (end_poses) end_poses->assign(4u * static_cast<size_t>(K), 0.0f);
+    uint32_t res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_rollout(h_, &r, start, deltas.data(), per_step ? 1u : 0u, footprint.data(),
+                       static_cast<uint32_t>(footprint.size() / 2), occ_prev_.data(),
+                       potential ? potential->data() : nullptr, K, out.data(), end_poses ? end_poses->data() : nullptr,
+                       res) != RPLGPU_OK)
+      return note_error();
+    result.admissible = res[0];
+    result.best_index = res[1];
+    result.best_score = (static_cast<uint64_t>(res[3]) << 32) | res[2];
+    result.ties = res[4];
+    result.blocked = res[5];
+    result.cell_range = res[6];
+    result.none = (res[7] & 1u) != 0;
     return true;
   }
 
