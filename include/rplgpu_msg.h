@@ -2090,6 +2090,138 @@ int32_t rplgpu_rollout(rplgpu_handle_t h, const rplgpu_rollout_t *r, const float
                        uint32_t delta_per_step, const float *footprint, uint32_t F, const int8_t *grid,
                        const uint32_t *potential, uint32_t K, uint32_t *out, float *end_poses, uint32_t result[8]);
 
+/* ---- E28: rolled-out candidates weighed and blended into new controls (row 4; MPPI's update behind E27) ----
+ * E18 draws noisy per-step deltas, E27 rolls K candidates of T steps and leaves eight words per candidate.  What MPPI
+ * does next is a softmax-weighted mean of the candidates' controls, then new candidates around that mean.  E28 is
+ * both on the device, so that spread -> E27 -> update -> spread runs on one stream with no read of a candidate.
+ * Nothing in the reference plans or controls, so these rules ARE the definition (parity unpinned, as E5-E27).
+ *
+ * A. THE UPDATE (rplgpu_mppi_update_dev).  Inputs per group g: E27's d_out (eight words a candidate at d_out +
+ * g * out_stride + 8 k, E27's stride rules), E27's eight result words at d_rollout_result + 8 g, the deltas E27 rolled
+ * (d_delta / delta_stride / delta_per_group and the spec's delta_per_step exactly as E27 reads them; T_e = steps when
+ * delta_per_step is 1, else 1; the entry of candidate k at step t, 0-based, is at 4 (k T_e + t)), a table of
+ * table_len = N uint16 entries at d_table (2-byte aligned, one for all groups) and optionally a nominal sequence of
+ * T_e deltas at d_nominal + g_n * nominal_stride (g_n = g when nominal_per_group is not 0, else 0; 16-byte aligned;
+ * the stride in floats, >= 4 T_e and a multiple of 4).
+ * WEIGHT of candidate k: w = 0 unless word 1 of the candidate has RPLGPU_ROLLOUT_ADMISSIBLE and bit 0 of word 7 of the
+ * group's result is clear.  Otherwise s = the candidate's words 6, 7 and m = the result's words 2, 3, both uint64;
+ * d = s - m, or 0 when s < m (any input is defined);  i = d >> shift;  the index is CLAMPED when i > N - 1;
+ * w = table[min(i, N - 1)].  Nothing is exponentiated on the device: the temperature lives in the table
+ * (rplgpu_mppi_table makes one), as E22's byte table carries its sensor model.
+ * QUANTISATION of a delta (dc, ds, dx, dy): float32, every operation rounded once, no FMA, IEEE divide.
+ *   h = ds / (1.0f + dc)  (the tangent of half the angle: E18's and E25's parametrisation, no trigonometric function)
+ *   th = h * 1048576.0f;  tx = dx * xy_scale;  ty = dy * xy_scale
+ * IN RANGE iff fabsf(t) < 8388608.0f for all three (NaN and +-Inf are not, nor is the half turn dc = -1);
+ * H, X, Y = (int32) rintf(t), ties to even.
+ * SUMS: per step t of T_e, over the candidates with w != 0 whose delta at t is in range, four exact integers
+ * W_t = sum w, sum w H, sum w X, sum w Y (each below 2^59), int64 two's complement, low word first: eight words a
+ * step at d_sums + g * sums_stride + 8 t (sums_stride in words, >= 8 T_e and a multiple of 4; 16-byte aligned).
+ * FINISH per step, in fp64 with every operation rounded once ((double) of an int64 is one round to nearest even):
+ *   W_t > 0:  hb = (sum w H / W_t) * 2^-20;  hh = hb * hb;  den = 1 + hh;
+ *             dc = (float)((1 - hh) / den);  ds = (float)((hb + hb) / den)      (a unit vector without a square root)
+ *             dx = (float)((sum w X / W_t) / (double)xy_scale);  dy likewise
+ *   W_t = 0:  step t of d_nominal bit for bit, or (1, 0, 0, 0) when d_nominal is NULL.
+ * T_e deltas go to d_nominal_out + g * nominal_out_stride + 4 t (E16's layout; 16-byte aligned; the stride in floats,
+ * >= 4 T_e and a multiple of 4).  d_nominal_out may equal d_nominal with equal strides and nominal_per_group not 0 (or
+ * G = 1): the finish reads step t before it writes step t.
+ * d_weights (required): w of candidate k at d_weights + g * weight_stride + k, E15's layout (weight_stride >= K), so
+ * that E16 can resample the candidates and E17 reduce their end poses with these weights.
+ * RESULT, eight words per group at d_result + 8 g: 0 the candidates with w != 0;  1 the candidates that pass the
+ * weight's gate and whose index was clamped;  2, 3 sum w;  4, 5 sum w^2 (below 2^52; N_eff = (sum w)^2 / sum w^2);
+ * 6 the (candidate, step) entries not in range among candidates with w != 0;  7 flags: RPLGPU_MPPI_NO_WEIGHT word 0
+ * is 0, RPLGPU_MPPI_OFF_RANGE word 6 is not 0, RPLGPU_MPPI_EMPTY_STEP some step had W_t = 0.
+ * Words beyond K, 8 T_e and 4 T_e of a group are never changed.
+ *
+ * B. THE SPREAD (rplgpu_mppi_spread_dev): the next iteration's candidates.  T_n nominal deltas a group (A's output;
+ * d_nominal + g_n * nominal_stride) and K x T noise deltas in E27's per-step layout (d_noise + g_z * noise_stride, the
+ * output of rplgpu_sample_motion_dev with M = K T around the identity odometry (1, 0, 0, 1, 0, k1, kt, k2)):
+ *   out[k][t] = nominal[min(t + shift, T_n - 1)] composed with noise[k][t]     (t 0-based; shift: the receding horizon)
+ * by E16's MOVE operation for operation with the nominal delta as the pose; a NaN is stored as 0x7FC00000.  With
+ * keep_first not 0, candidate 0 is the (shifted) nominal bit for bit.  The output (d_out + g * out_stride) is E27's
+ * delta_per_step = 1 input.  d_out may equal d_noise with equal strides and noise_per_group not 0 (or G = 1).
+ * AN IDENTITY that holds independent code to each other: without keep_first, step t of all candidates equals
+ * rplgpu_resample_host with P = 1, the nominal step as the pose, weight 1, M = K, n_delta = M, byte for byte. */
+#define RPLGPU_MPPI_MAX_SHIFT          49u
+#define RPLGPU_MPPI_MAX_TABLE       65536u
+#define RPLGPU_MPPI_MAX_SPREAD_SHIFT  256u
+#define RPLGPU_MPPI_PER_LANE            8u   /* candidates a lane of the sums launch folds in registers */
+#define RPLGPU_MPPI_MAX_BLOCKS   0x800000u   /* workgroups of one launch: it stays below 2^32 threads */
+#define RPLGPU_MPPI_NO_WEIGHT         0x1u
+#define RPLGPU_MPPI_OFF_RANGE         0x2u
+#define RPLGPU_MPPI_EMPTY_STEP        0x4u
+typedef struct rplgpu_mppi {
+  float    xy_scale;        /* finite, > 0: quanta per metre of dx, dy (1024 = E17's quantum) */
+  uint32_t shift;           /* 0 .. RPLGPU_MPPI_MAX_SHIFT: score units per table entry, as a power of two */
+  uint32_t table_len;       /* N, 1 .. RPLGPU_MPPI_MAX_TABLE */
+  uint32_t steps;           /* T, 1 .. RPLGPU_ROLLOUT_MAX_STEPS: E27's */
+  uint32_t delta_per_step;  /* 0 or 1: E27's */
+} rplgpu_mppi_t;
+/* xy_scale 1024, shift 0, table_len 1024, steps 32, delta_per_step 1 */
+void rplgpu_default_mppi(rplgpu_mppi_t *m);
+/* Host only.  RPLGPU_ERR_INVALID_ARG for NULL, an xy_scale that is not finite or not > 0, a value outside the ranges
+ * above.  The device path uses this function. */
+int32_t rplgpu_mppi_check(const rplgpu_mppi_t *m);
+/* Host only: the uint32 words of scratch the update takes for G groups of K candidates and T_e steps:
+ * 8 ceil(K / 256) G (a record per workgroup of the weights launch) + 12 C T_e G (a record per workgroup and step of
+ * the sums launch), C = ceil(K / (RPLGPU_MPPI_PER_LANE * 256 / TW)), TW = the power of two at or above T_e.  0 for
+ * G = 0 or above 65535, a K outside 1 .. RPLGPU_MAX_POSES, a T_e outside 1 .. RPLGPU_ROLLOUT_MAX_STEPS, K T_e above
+ * 2^24, or a launch above RPLGPU_MPPI_MAX_BLOCKS workgroups. */
+uint64_t rplgpu_mppi_scratch_words(uint32_t G, uint32_t K, uint32_t T_e);
+/* Host only, fp64, NOT part of the byte-exact contract (as rplgpu_rollout_deltas is not): the softmax table of
+ * temperature lambda (in score units), out[i] = floor(65535 exp(-(i 2^shift) / lambda) + 0.5); out[0] is always 65535.
+ * RPLGPU_ERR_INVALID_ARG for a NULL out, a lambda that is not finite or not > 0, shift above RPLGPU_MPPI_MAX_SHIFT,
+ * N outside 1 .. RPLGPU_MPPI_MAX_TABLE. */
+int32_t rplgpu_mppi_table(double lambda, uint32_t shift, uint32_t N, uint16_t *out);
+/* Host only: A's rules in plain C++ for ONE group.  out: 8 K words; rollout_result: 8 words; delta: 4 K T_e floats;
+ * table: N entries; nominal: NULL or 4 T_e floats; weights: K words; sums: 8 T_e words; nominal_out: 4 T_e floats
+ * (it may be nominal itself); result: 8 words.  RPLGPU_ERR_INVALID_ARG and nothing written for a spec the check
+ * refuses, a NULL pointer other than nominal, K = 0 or above RPLGPU_MAX_POSES, K * T above 2^24. */
+int32_t rplgpu_mppi_update_host(const rplgpu_mppi_t *m, const uint32_t *out, const uint32_t rollout_result[8],
+                                const float *delta, const uint16_t *table, const float *nominal, uint32_t K,
+                                uint32_t *weights, uint32_t *sums, float *nominal_out, uint32_t result[8]);
+/* A for each of G groups on the handle's stream: three launches (the weights with a record per workgroup, the sums
+ * with a record per workgroup and step, then one workgroup per group that folds both kinds of record and does the
+ * finish), no workgroup waits for another, nothing is stored on the handle.  d_scratch: rplgpu_mppi_scratch_words of
+ * (G, K, T_e) words, 16-byte aligned, the caller's; it holds nothing a later call relies on.
+ * RPLGPU_ERR_INVALID_ARG, no output changed and nothing queued, for a spec the check refuses, G = 0 or above 65535,
+ * K = 0 or above RPLGPU_MAX_POSES, K * T above 2^24, a missing d_out / d_rollout_result / d_delta / d_table /
+ * d_weights / d_sums / d_nominal_out / d_result / d_scratch, a misaligned pointer (16 bytes: d_out, d_delta,
+ * d_nominal, d_sums, d_nominal_out, d_scratch; 2: d_table; 4: the others), the stride rules above, and an output
+ * (d_weights, d_sums, d_nominal_out, d_result, d_scratch) that overlaps an input or another output over the ranges
+ * used, but for d_nominal_out on d_nominal as above; RPLGPU_ERR_CAPACITY where a launch would pass
+ * RPLGPU_MPPI_MAX_BLOCKS workgroups.  Asynchronous on the handle's stream. */
+int32_t rplgpu_mppi_update_dev(rplgpu_handle_t h, const rplgpu_mppi_t *m, const uint32_t *d_out, uint64_t out_stride,
+                               const uint32_t *d_rollout_result, const float *d_delta, uint64_t delta_stride,
+                               uint32_t delta_per_group, const uint16_t *d_table, const float *d_nominal,
+                               uint64_t nominal_stride, uint32_t nominal_per_group, uint32_t G, uint32_t K,
+                               uint32_t *d_weights, uint64_t weight_stride, uint32_t *d_sums, uint64_t sums_stride,
+                               float *d_nominal_out, uint64_t nominal_out_stride, uint32_t *d_result,
+                               uint32_t *d_scratch);
+/* ONE group, HOST buffers, arguments as rplgpu_mppi_update_host.  Allocates its device buffers and scratch per call
+ * and returns when the results are in place: a door, not a hot path. */
+int32_t rplgpu_mppi_update(rplgpu_handle_t h, const rplgpu_mppi_t *m, const uint32_t *out,
+                           const uint32_t rollout_result[8], const float *delta, const uint16_t *table,
+                           const float *nominal, uint32_t K, uint32_t *weights, uint32_t *sums, float *nominal_out,
+                           uint32_t result[8]);
+/* Host only: B's rule in plain C++ for ONE group.  nominal: 4 T_n floats; noise: 4 K T floats; out: 4 K T floats (it
+ * may be noise itself).  RPLGPU_ERR_INVALID_ARG and nothing written for a NULL pointer, K = 0 or above
+ * RPLGPU_MAX_POSES, T or T_n outside 1 .. RPLGPU_ROLLOUT_MAX_STEPS, K * T above 2^24, shift above
+ * RPLGPU_MPPI_MAX_SPREAD_SHIFT. */
+int32_t rplgpu_mppi_spread_host(const float *nominal, uint32_t T_n, const float *noise, uint32_t K, uint32_t T,
+                                uint32_t shift, uint32_t keep_first, float *out);
+/* B for each of G groups on the handle's stream: one launch, a thread per (candidate, step).  All three pointers
+ * 16-byte aligned; nominal_stride >= 4 T_n, noise_stride and out_stride >= 4 K T, all in floats and multiples of 4.
+ * RPLGPU_ERR_INVALID_ARG, no output changed and nothing queued, for the host twin's refusals, G = 0 or above 65535, a
+ * misaligned pointer, the stride rules and a d_out that overlaps an input other than d_noise as above;
+ * RPLGPU_ERR_CAPACITY where the launch would pass RPLGPU_MPPI_MAX_BLOCKS workgroups.  Asynchronous. */
+int32_t rplgpu_mppi_spread_dev(rplgpu_handle_t h, const float *d_nominal, uint64_t nominal_stride,
+                               uint32_t nominal_per_group, uint32_t T_n, const float *d_noise, uint64_t noise_stride,
+                               uint32_t noise_per_group, uint32_t G, uint32_t K, uint32_t T, uint32_t shift,
+                               uint32_t keep_first, float *d_out, uint64_t out_stride);
+/* ONE group, HOST buffers, arguments as rplgpu_mppi_spread_host: a door, not a hot path. */
+int32_t rplgpu_mppi_spread(rplgpu_handle_t h, const float *nominal, uint32_t T_n, const float *noise, uint32_t K,
+                           uint32_t T, uint32_t shift, uint32_t keep_first, float *out);
+
 #ifdef __cplusplus
 }
 #endif

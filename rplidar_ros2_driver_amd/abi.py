@@ -57,6 +57,12 @@ ROLLOUT_NONE = 0xFFFFFFFF     # RPLGPU_ROLLOUT_NONE (result word 1)
 ROLLOUT_TILE = 32             # RPLGPU_ROLLOUT_TILE: candidates a workgroup takes
 ROLLOUT_MAX_TILES = 1 << 23   # RPLGPU_ROLLOUT_MAX_TILES: G x tiles of one call
 ROLLOUT_BLOCKED, ROLLOUT_CELL_RANGE, ROLLOUT_END_UNREACHED, ROLLOUT_ADMISSIBLE = 1, 2, 4, 8
+MPPI_MAX_SHIFT = 49           # RPLGPU_MPPI_MAX_SHIFT (E28)
+MPPI_MAX_TABLE = 65536        # RPLGPU_MPPI_MAX_TABLE
+MPPI_MAX_SPREAD_SHIFT = 256   # RPLGPU_MPPI_MAX_SPREAD_SHIFT
+MPPI_PER_LANE = 8             # RPLGPU_MPPI_PER_LANE: candidates a lane of the sums launch folds
+MPPI_MAX_BLOCKS = 1 << 23     # RPLGPU_MPPI_MAX_BLOCKS: workgroups of one launch
+MPPI_NO_WEIGHT, MPPI_OFF_RANGE, MPPI_EMPTY_STEP = 1, 2, 4
 REFINE_PLANES = 29            # RPLGPU_REFINE_PLANES
 REFINE_MAX_ITERS = 16         # RPLGPU_REFINE_MAX_ITERS
 REFINE_STEPPED = 0x01         # E25's step flags
@@ -256,6 +262,16 @@ ABI_SYMBOLS = [
     "rplgpu_rollout_host",
     "rplgpu_rollout_dev",
     "rplgpu_rollout",
+    "rplgpu_default_mppi",
+    "rplgpu_mppi_check",
+    "rplgpu_mppi_scratch_words",
+    "rplgpu_mppi_table",
+    "rplgpu_mppi_update_host",
+    "rplgpu_mppi_update_dev",
+    "rplgpu_mppi_update",
+    "rplgpu_mppi_spread_host",
+    "rplgpu_mppi_spread_dev",
+    "rplgpu_mppi_spread",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -828,6 +844,33 @@ class Rollout(C.Structure):
         return int(load_library().rplgpu_rollout_check(C.byref(self)))
 
 
+class Mppi(C.Structure):
+    """Mirror of ``rplgpu_mppi_t`` (E28: rolled-out candidates weighed and blended into new controls)."""
+
+    _fields_ = [("xy_scale", C.c_float)] + [(k, C.c_uint32) for k in (
+        "shift", "table_len", "steps", "delta_per_step")]
+
+    @classmethod
+    def defaults(cls, **kw) -> "Mppi":
+        """The library's own defaults (``rplgpu_default_mppi``), then the overrides."""
+        m = cls()
+        load_library().rplgpu_default_mppi(C.byref(m))
+        for k, v in kw.items():
+            if not hasattr(m, k):
+                raise AttributeError(k)
+            setattr(m, k, v)
+        return m
+
+    def check(self) -> int:
+        """``rplgpu_mppi_check``: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_mppi_check(C.byref(self)))
+
+    @property
+    def steps_e(self) -> int:
+        """T_e: the steps that carry a delta of their own."""
+        return self.steps if self.delta_per_step else 1
+
+
 class OccupancyLayout(C.Structure):
     """Mirror of ``rplgpu_occupancy_layout_t``."""
 
@@ -1149,6 +1192,19 @@ def load_library() -> C.CDLL:
     lib.rplgpu_rollout_dev.argtypes = [vp, C.POINTER(Rollout), vp, u32, vp, u64, u32, u32, vp, u32, vp, u64, vp, u64,
                                        u32, u32, u32, vp, u64, vp, u64, vp, vp]
     lib.rplgpu_rollout.argtypes = [vp, C.POINTER(Rollout), vp, vp, u32, vp, u32, vp, vp, u32, vp, vp, vp]
+    lib.rplgpu_default_mppi.argtypes = [C.POINTER(Mppi)]
+    lib.rplgpu_default_mppi.restype = None
+    lib.rplgpu_mppi_check.argtypes = [C.POINTER(Mppi)]
+    lib.rplgpu_mppi_scratch_words.argtypes = [u32, u32, u32]
+    lib.rplgpu_mppi_scratch_words.restype = u64
+    lib.rplgpu_mppi_table.argtypes = [C.c_double, u32, u32, vp]
+    lib.rplgpu_mppi_update_host.argtypes = [C.POINTER(Mppi), vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    lib.rplgpu_mppi_update_dev.argtypes = [vp, C.POINTER(Mppi), vp, u64, vp, vp, u64, u32, vp, vp, u64, u32, u32, u32,
+                                           vp, u64, vp, u64, vp, u64, vp, vp]
+    lib.rplgpu_mppi_update.argtypes = [vp, C.POINTER(Mppi), vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    lib.rplgpu_mppi_spread_host.argtypes = [vp, u32, vp, u32, u32, u32, u32, vp]
+    lib.rplgpu_mppi_spread_dev.argtypes = [vp, vp, u64, u32, u32, vp, u64, u32, u32, u32, u32, u32, u32, vp, u64]
+    lib.rplgpu_mppi_spread.argtypes = [vp, vp, u32, vp, u32, u32, u32, u32, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1819,6 +1875,42 @@ class RplGpu:
         end_poses (K, 4) float32, result (8,) uint32)``."""
         a = _rollout_args(spec, start, delta, footprint, grid, potential)
         self._check(self._lib.rplgpu_rollout(self._h, C.byref(spec), *a[0]))
+        return a[1]
+
+    def mppi_update_dev(self, spec: "Mppi", d_out: int, out_stride: int, d_rollout_result: int, d_delta: int,
+                        delta_stride: int, delta_per_group: int, d_table: int, d_nominal: int, nominal_stride: int,
+                        nominal_per_group: int, G: int, K: int, d_weights: int, weight_stride: int, d_sums: int,
+                        sums_stride: int, d_nominal_out: int, nominal_out_stride: int, d_result: int, d_scratch: int):
+        """E28 A: per group the K candidates E27 scored (d_out, d_rollout_result) weighed through the uint16 table at
+        d_table, the deltas E27 rolled summed per step under those weights (eight words a step at d_sums) and blended
+        into ``spec.steps_e`` new deltas at d_nominal_out; the weights at d_weights (E15's layout), eight result words
+        at d_result + 8 g.  d_scratch: ``mppi_scratch_words(G, K, spec.steps_e)`` uint32 words."""
+        self._check(self._lib.rplgpu_mppi_update_dev(
+            self._h, C.byref(spec), d_out, out_stride, d_rollout_result, d_delta, delta_stride, delta_per_group,
+            d_table, d_nominal, nominal_stride, nominal_per_group, G, K, d_weights, weight_stride, d_sums, sums_stride,
+            d_nominal_out, nominal_out_stride, d_result, d_scratch))
+
+    def mppi_update(self, spec: "Mppi", out, rollout_result, delta, table, nominal=None):
+        """E28 A, one group, host buffers: out (K, 8) uint32 and rollout_result (8,) uint32 from E27, delta (K, 4) or
+        (K, steps, 4) float32, table (N,) uint16, nominal None or (steps_e, 4) float32 -> ``(weights (K,) uint32, sums
+        (steps_e, 8) uint32, nominal_out (steps_e, 4) float32, result (8,) uint32)``."""
+        a = _mppi_update_args(spec, out, rollout_result, delta, table, nominal)
+        self._check(self._lib.rplgpu_mppi_update(self._h, C.byref(spec), *a[0]))
+        return a[1]
+
+    def mppi_spread_dev(self, d_nominal: int, nominal_stride: int, nominal_per_group: int, T_n: int, d_noise: int,
+                        noise_stride: int, noise_per_group: int, G: int, K: int, T: int, shift: int, keep_first: int,
+                        d_out: int, out_stride: int):
+        """E28 B: per group out[k][t] = nominal[min(t + shift, T_n - 1)] composed with noise[k][t] (E16's move), the
+        per-step deltas ``rollout_dev`` reads; candidate 0 is the nominal itself with keep_first."""
+        self._check(self._lib.rplgpu_mppi_spread_dev(
+            self._h, d_nominal, nominal_stride, nominal_per_group, T_n, d_noise, noise_stride, noise_per_group, G, K,
+            T, shift, keep_first, d_out, out_stride))
+
+    def mppi_spread(self, nominal, noise, shift: int = 0, keep_first: int = 0) -> np.ndarray:
+        """E28 B, one group, host buffers: nominal (T_n, 4) and noise (K, T, 4) float32 -> (K, T, 4) float32."""
+        a = _mppi_spread_args(nominal, noise, shift, keep_first)
+        self._check(self._lib.rplgpu_mppi_spread(self._h, *a[0]))
         return a[1]
 
     def resample_poses_dev(self, d_weights: int, weight_stride: int, d_poses: int, pose_stride: int,
@@ -3039,4 +3131,82 @@ def rollout_host(spec: Rollout, start, delta, footprint, grid, potential=None):
     rc = load_library().rplgpu_rollout_host(C.byref(spec), *a[0])
     if rc != OK:
         raise RplGpuError(rc, "rplgpu_rollout_host")
+    return a[1]
+
+
+def mppi_check(spec: Mppi) -> None:
+    """Host only: validates an E28 spec by the library's own rplgpu_mppi_check; raises RplGpuError."""
+    rc = load_library().rplgpu_mppi_check(C.byref(spec))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_mppi_check")
+
+
+def mppi_scratch_words(G: int, K: int, T_e: int) -> int:
+    """Host only: the uint32 words of scratch ``mppi_update_dev`` takes; 0 when refused."""
+    return int(load_library().rplgpu_mppi_scratch_words(G, K, T_e))
+
+
+def mppi_table(lam: float, shift: int, N: int) -> np.ndarray:
+    """Host only: the (N,) uint16 softmax table of temperature ``lam`` (score units), by the library's own
+    rplgpu_mppi_table."""
+    out = np.zeros(max(min(N, MPPI_MAX_TABLE), 1), np.uint16)
+    rc = load_library().rplgpu_mppi_table(lam, shift, N, out.ctypes.data)
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_mppi_table")
+    return out
+
+
+def _mppi_update_args(spec, out, rollout_result, delta, table, nominal):
+    """-> (the arguments behind the spec, (weights, sums, nominal_out, result), the arrays kept alive)"""
+    out = np.ascontiguousarray(out, np.uint32)
+    rres = np.ascontiguousarray(rollout_result, np.uint32).reshape(-1)
+    delta = np.ascontiguousarray(delta, np.float32)
+    table = np.ascontiguousarray(table, np.uint16).reshape(-1)
+    T_e = spec.steps_e
+    K = len(out)
+    if out.ndim != 2 or out.shape[1] != 8 or K == 0 or rres.shape != (8,) or delta.size != 4 * K * T_e or \
+            len(table) != spec.table_len:
+        raise TypeError("out (K, 8), rollout_result (8,), delta (K, 4) or (K, steps, 4), table (table_len,) uint16")
+    if nominal is not None:
+        nominal = np.ascontiguousarray(nominal, np.float32)
+        if nominal.size != 4 * T_e:
+            raise TypeError("nominal must be (steps_e, 4) float32")
+    weights = np.zeros(K, np.uint32)
+    sums = np.zeros((T_e, 8), np.uint32)
+    nout = np.zeros((T_e, 4), np.float32)
+    result = np.zeros(8, np.uint32)
+    args = (out.ctypes.data, rres.ctypes.data, delta.ctypes.data, table.ctypes.data,
+            0 if nominal is None else nominal.ctypes.data, K, weights.ctypes.data, sums.ctypes.data, nout.ctypes.data,
+            result.ctypes.data)
+    return args, (weights, sums, nout, result), (out, rres, delta, table, nominal)
+
+
+def mppi_update_host(spec: Mppi, out, rollout_result, delta, table, nominal=None):
+    """Host only: E28 A's rules for one group by the library's own rplgpu_mppi_update_host (no handle, no device);
+    arguments and results as ``RplGpu.mppi_update``."""
+    a = _mppi_update_args(spec, out, rollout_result, delta, table, nominal)
+    rc = load_library().rplgpu_mppi_update_host(C.byref(spec), *a[0])
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_mppi_update_host")
+    return a[1]
+
+
+def _mppi_spread_args(nominal, noise, shift, keep_first):
+    nominal = np.ascontiguousarray(nominal, np.float32).reshape(-1, 4)
+    noise = np.ascontiguousarray(noise, np.float32)
+    if noise.ndim != 3 or noise.shape[2] != 4 or noise.size == 0 or len(nominal) == 0:
+        raise TypeError("nominal (T_n, 4) and noise (K, T, 4) float32")
+    K, T = noise.shape[:2]
+    out = np.zeros((K, T, 4), np.float32)
+    return (nominal.ctypes.data, len(nominal), noise.ctypes.data, K, T, shift, keep_first, out.ctypes.data), out, \
+        (nominal, noise)
+
+
+def mppi_spread_host(nominal, noise, shift: int = 0, keep_first: int = 0) -> np.ndarray:
+    """Host only: E28 B's rule for one group by the library's own rplgpu_mppi_spread_host; arguments and result as
+    ``RplGpu.mppi_spread``."""
+    a = _mppi_spread_args(nominal, noise, shift, keep_first)
+    rc = load_library().rplgpu_mppi_spread_host(*a[0])
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_mppi_spread_host")
     return a[1]

@@ -369,6 +369,37 @@ int main(int argc, char **argv) {
     }
     std::printf("rollout: candidate 0 blocked after %u poses (cost %u, D %u), candidate %u wins of %u admissible\n",
                 roll_out[0], roll_out[2], roll_out[4], ro_res.best_index, ro_res.admissible);
+    // E28 behind it: both candidates are admissible; with shift 0 and a table of two the winner (candidate 1, score 0)
+    // has index 0 and candidate 0 (a score far above 1) is clamped to index 1.  The table (1, 3) gives them the
+    // weights 1 and 3, so the deltas (1, 0, 1, 0) and (1, 0, 0, 0) blend into dx = 0.75.
+    rplgpu_mppi_t mp;
+    rplgpu_default_mppi(&mp);
+    mp.steps = roll.steps;
+    mp.delta_per_step = 0;
+    mp.table_len = 2;
+    const uint32_t roll_words[8] = {ro_res.admissible, ro_res.best_index, 0, 0, ro_res.ties, ro_res.blocked, ro_res.cell_range, 0};
+    const std::vector<uint16_t> mp_table = {1, 3};
+    std::vector<uint32_t> mp_weights;
+    std::vector<float> mp_nominal, mp_next;
+    rplgpu_host::ScanPath::MppiResult mp_res;
+    if (!path.mppi_update(mp, roll_out, roll_words, roll_deltas, mp_table, nullptr, mp_weights, mp_nominal, mp_res)) {
+      std::fprintf(stderr, "mppi_update failed: %s\n", path.last_error().c_str());
+      return 11;
+    }
+    if (mp_weights.size() != 2 || mp_weights[0] != 3 || mp_weights[1] != 1 || mp_res.weighted != 2 || mp_res.clamped != 1 ||
+        mp_res.sum_w != 4 || mp_res.sum_w2 != 10 || mp_res.no_weight || mp_res.empty_step || mp_nominal.size() != 4 ||
+        mp_nominal[0] != 1.0f || mp_nominal[1] != 0.0f || mp_nominal[2] != 0.75f || mp_nominal[3] != 0.0f) {
+      std::fprintf(stderr, "mppi_update: wrong answer (weights %u %u, dx %g)\n", mp_weights.empty() ? 0u : mp_weights[0],
+                   mp_weights.size() < 2 ? 0u : mp_weights[1], mp_nominal.size() < 3 ? 0.0 : (double)mp_nominal[2]);
+      return 12;
+    }
+    if (!path.mppi_spread(mp_nominal, roll_deltas, 2, 0, true, mp_next) || mp_next.size() != 8 || mp_next[2] != 0.75f ||
+        mp_next[6] != 0.75f) {
+      std::fprintf(stderr, "mppi_spread: wrong answer: %s\n", path.last_error().c_str());
+      return 12;
+    }
+    std::printf("mppi: weights %u and %u, the blended step moves %g, spread around it %g and %g\n", mp_weights[0],
+                mp_weights[1], (double)mp_nominal[2], (double)mp_next[2], (double)mp_next[6]);
     // E14: the three rays of the E11 leg added twice into a count map.  Per call the row of the sensor gets
     // misses 3 3 2 2 1 1 (the whole ray beyond obstacle_max leaves its end cell 4 alone, the cut one counts its
     // end cell 5) and one hit in cell 2; after two calls the default rule (2 observations, 10 %) gives the E11 row.

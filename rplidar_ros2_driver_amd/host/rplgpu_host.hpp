@@ -25,6 +25,8 @@
 //   nav the planning side's first loop (a navigation function over that costmap, and the paths down it):
 //         -> rplgpu_host::ScanPath::nav_field(costmap_msg, rule, goals, potential, result, starts, ...)  (E26)
 //         -> rplgpu_host::ScanPath::rollout(costmap_msg, rule, start, deltas, per_step, footprint, potential, ...)  (E27)
+//         -> rplgpu_host::ScanPath::mppi_update(rule, rollout_out, rollout_words, deltas, table, nominal, ...)  (E28)
+//         -> rplgpu_host::ScanPath::mppi_spread(nominal, noise, K, shift, keep_first, candidates)  (E28)
 //   mat the localisation side's loop (a correlative scan matcher's search window over a likelihood field):
 //         -> rplgpu_host::ScanPath::match_scans(scans, ..., field_msg, window, result)  (E13)
 //         -> rplgpu_host::ScanPath::match_wide(scans, ..., field_msg, window, result)   (E24: up to 256 cells a side)
@@ -673,6 +675,65 @@ class ScanPath {
     result.blocked = res[5];
     result.cell_range = res[6];
     result.none = (res[7] & 1u) != 0;
+    return true;
+  }
+
+  // ext E28 (include/rplgpu_msg.h): MPPI's update behind rollout().  rollout_out: the eight words per candidate and
+  // rollout_words: the eight result words rplgpu_rollout left (RolloutResult is made from them); deltas: what was
+  // rolled (four floats per candidate, or per candidate and step with rule.delta_per_step); table: rule.table_len
+  // entries (rplgpu_mppi_table); nominal: the sequence kept where no candidate has weight at a step, or null.
+  // weights: one word per candidate; nominal_out: four floats per step (it may be *nominal).
+  struct MppiResult {
+    uint32_t weighted = 0, clamped = 0, off_range = 0;
+    uint64_t sum_w = 0, sum_w2 = 0;
+    bool no_weight = true, empty_step = false;
+  };
+  bool mppi_update(const rplgpu_mppi_t &rule, const std::vector<uint32_t> &rollout_out, const uint32_t rollout_words[8],
+                   const std::vector<float> &deltas, const std::vector<uint16_t> &table,
+                   const std::vector<float> *nominal, std::vector<uint32_t> &weights, std::vector<float> &nominal_out,
+                   MppiResult &result, std::vector<uint32_t> *sums = nullptr) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    const size_t T_e = rule.delta_per_step ? rule.steps : 1u;
+    if (rollout_out.empty() || rollout_out.size() % 8 != 0) return fail("mppi_update: rollout_out must be 8 words per candidate");
+    const uint32_t K = static_cast<uint32_t>(rollout_out.size() / 8);
+    if (T_e == 0 || deltas.size() != 4u * K * T_e) return fail("mppi_update: deltas must be 4 floats per candidate (and step)");
+    if (table.size() != rule.table_len) return fail("mppi_update: the table is not table_len entries");
+    if (nominal && nominal->size() != 4u * T_e) return fail("mppi_update: nominal must be 4 floats per step");
+    std::vector<float> nout(4u * T_e, 0.0f);
+    std::vector<uint32_t> s(8u * T_e, 0u);
+    weights.assign(K, 0u);
+    uint32_t res[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (rplgpu_mppi_update(h_, &rule, rollout_out.data(), rollout_words, deltas.data(), table.data(),
+                           nominal ? nominal->data() : nullptr, K, weights.data(), s.data(), nout.data(), res) != RPLGPU_OK)
+      return note_error();
+    nominal_out = nout;
+    if (sums) *sums = s;
+    result.weighted = res[0];
+    result.clamped = res[1];
+    result.sum_w = (static_cast<uint64_t>(res[3]) << 32) | res[2];
+    result.sum_w2 = (static_cast<uint64_t>(res[5]) << 32) | res[4];
+    result.off_range = res[6];
+    result.no_weight = (res[7] & RPLGPU_MPPI_NO_WEIGHT) != 0;
+    result.empty_step = (res[7] & RPLGPU_MPPI_EMPTY_STEP) != 0;
+    return true;
+  }
+
+  // ext E28: the next candidates, K sequences of noise.size() / (4 K) steps around the nominal sequence moved `shift`
+  // steps on (the receding horizon); candidates is rollout()'s per-step `deltas`.
+  bool mppi_spread(const std::vector<float> &nominal, const std::vector<float> &noise, uint32_t K, uint32_t shift,
+                   bool keep_first, std::vector<float> &candidates) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    if (nominal.empty() || nominal.size() % 4 != 0) return fail("mppi_spread: nominal must be 4 floats per step");
+    if (K == 0 || noise.empty() || noise.size() % (4u * static_cast<size_t>(K)) != 0)
+      return fail("mppi_spread: noise must be 4 floats per candidate and step");
+    std::vector<float> out(noise.size(), 0.0f);
+    if (rplgpu_mppi_spread(h_, nominal.data(), static_cast<uint32_t>(nominal.size() / 4), noise.data(), K,
+                           static_cast<uint32_t>(noise.size() / (4u * static_cast<size_t>(K))), shift, keep_first ? 1u : 0u,
+                           out.data()) != RPLGPU_OK)
+      return note_error();
+    candidates.swap(out);
     return true;
   }
 
