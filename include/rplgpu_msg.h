@@ -2222,6 +2222,95 @@ int32_t rplgpu_mppi_spread_dev(rplgpu_handle_t h, const float *d_nominal, uint64
 int32_t rplgpu_mppi_spread(rplgpu_handle_t h, const float *nominal, uint32_t T_n, const float *noise, uint32_t K,
                            uint32_t T, uint32_t shift, uint32_t keep_first, float *out);
 
+/* ---- E29: a map's frontiers found, grouped and the next goal picked (row 4; what hands E26 its goal) ----
+ * Every stage from E26 on starts from a goal cell; a robot that builds E14's map has to decide where to drive next.
+ * Yamauchi's frontiers (explore_lite, frontier_exploration) work on the two arrays already in device memory: the int8
+ * grid of rplgpu_map_grid_dev / rplgpu_inflate_grids_dev and E26's field D taken with the robot's own cell as the
+ * goal, the cost of reaching every cell from the robot.  E29 writes its choice in E26's goal layout, so map_grid ->
+ * inflate -> field (from the robot) -> frontiers -> field (to the frontier) -> rollout -> update queues with no
+ * read-back.  Nothing in the reference explores: these rules are the definition (parity unpinned, as E5-E28).
+ * Everything is integers and depends on no order of execution.
+ *
+ * Per grid g of G: the int8 grid at d_grid + g * grid_stride (E11's layout, cell (cx, cy) at cy * width + cx; E12's
+ * stride and alignment rules) and optionally E26's field at d_potential + g * potential_stride.  Both are only read.
+ *   FREE      0 <= v < lethal (E26's meaning)             UNKNOWN   v < 0
+ *   D(c)      the field's word; with d_potential = NULL it is 0 for every cell
+ *   FRONTIER  c is FREE, D(c) != RPLGPU_NAV_UNREACHED and at least one of its four edge neighbours INSIDE the grid is
+ *             UNKNOWN (outside the grid is not unknown).  F: the frontier cells of a grid.
+ *   COMPONENTS  of the frontier cells under 8-adjacency, no wrap ((width - 1, cy) and (0, cy + 1) are no neighbours).
+ *             A component's LABEL is its smallest cell index.  N: the components of a grid.
+ *   per component, exact integers: n, its cells; sum cx and sum cy (two words each); the least of D(c) * 2^32 + c
+ *             over its cells, which gives Dmin and, on ties, the smallest cell that holds it ("its cell").
+ *   KEPT      n >= min_size.     COST of a kept component: dist_weight * Dmin - size_weight * n as an int64
+ *             (explore_lite's potential_scale / gain_scale).
+ *   BEST      the kept component of least cost, ties to the smaller label.
+ *   BOUND     a call holds at most comp_cap components (1 .. RPLGPU_FRONTIER_MAX_COMPS, it sizes the scratch).  With
+ *             N above it: flag bit 2; F, N and the labels are still exact and whole; words 3 - 14 are as if no
+ *             component existed (5 = 0xFFFFFFFF, the others 0), bit 1 is set, no row is written, the goal count is 0.
+ * RESULT, RPLGPU_FRONTIER_WORDS = 16 words per grid at d_result + 16 g: 0 the flags (RPLGPU_FRONTIER_NONE: F = 0;
+ * _NO_KEPT: no BEST, so with F = 0 and under BOUND too; _BOUND; _LOOP: a kernel loop reached its stated bound, which a
+ * correct build never does), 1 F, 2 N, 3 the kept components, 4 the cells of dropped components, 5 BEST's label
+ * (0xFFFFFFFF: none), 6 its n, 7 its Dmin, 8 its cell, 9, 10 its sum cx (low, high), 11, 12 its sum cy, 13 the
+ * greatest n of any component, 14 the rows written, 15 0.
+ * ROW, RPLGPU_FRONTIER_ROW_WORDS = 8 words: {label, n, sum cx low, high, sum cy low, high, Dmin, cell}. */
+#define RPLGPU_FRONTIER_WORDS      16u
+#define RPLGPU_FRONTIER_ROW_WORDS  8u
+#define RPLGPU_FRONTIER_MAX_COMPS  0x100000u
+#define RPLGPU_FRONTIER_NONE       0x01u
+#define RPLGPU_FRONTIER_NO_KEPT    0x02u
+#define RPLGPU_FRONTIER_BOUND      0x04u
+#define RPLGPU_FRONTIER_LOOP       0x08u
+#define RPLGPU_FRONTIER_NO_LABEL   0xFFFFFFFFu
+typedef struct rplgpu_frontiers {
+  uint32_t width, height;   /* 1 .. RPLGPU_MAX_OCC_DIM */
+  uint32_t lethal;          /* 1 .. 100: bytes in 0 .. lethal - 1 are FREE */
+  uint32_t min_size;        /* >= 1: a component of fewer cells is dropped */
+  uint32_t dist_weight;     /* 0 .. 65535 */
+  uint32_t size_weight;     /* 0 .. 65535 */
+} rplgpu_frontiers_t;
+/* 1024 x 1024, lethal 99, min_size 8, dist_weight 1, size_weight 0 */
+void rplgpu_default_frontiers(rplgpu_frontiers_t *f);
+/* Host only (no handle, no device).  RPLGPU_ERR_INVALID_ARG for NULL and a value outside the ranges above.  The
+ * device path uses this function. */
+int32_t rplgpu_frontiers_check(const rplgpu_frontiers_t *f);
+/* Host only: the uint32 words of scratch rplgpu_frontiers_dev takes, G times
+ * 16 + up4(ceil(cells / 1024)) + 2 up4(cells) + 8 comp_cap with cells = width * height and up4 the next multiple of
+ * four (a header, a count per 1024 cells, the parent plane, the rank plane, a table row per component); 0 for a spec the check refuses, G = 0 or above
+ * 65535, comp_cap outside 1 .. RPLGPU_FRONTIER_MAX_COMPS and G * ntx * nty above RPLGPU_NAV_MAX_TILES. */
+uint64_t rplgpu_frontiers_scratch_words(const rplgpu_frontiers_t *f, uint32_t G, uint32_t comp_cap);
+/* Host only: ONE grid in plain C++, a flood fill over the frontier cells in ascending cell index.  potential,
+ * labels_out (width * height words, written whole), rows (row_cap rows; the first min(kept, row_cap) are written),
+ * goal_out and n_goal_out (one word each; both or neither) are optional; result: 16 words.
+ * RPLGPU_ERR_INVALID_ARG and nothing written for a spec the check refuses, comp_cap out of range, a NULL grid or
+ * result, rows = NULL with row_cap != 0, one of goal_out and n_goal_out without the other. */
+int32_t rplgpu_frontiers_host(const rplgpu_frontiers_t *f, const int8_t *grid, const uint32_t *potential,
+                              uint32_t comp_cap, uint32_t *labels_out, uint32_t *rows, uint32_t row_cap,
+                              uint32_t *goal_out, uint32_t *n_goal_out, uint32_t result[16]);
+/* G grids on the handle's stream, seven launches and no host round trip; no workgroup ever waits for another.
+ * d_labels_out + g * label_stride (optional; label_stride >= width * height words): one word per cell, the label of a
+ * frontier cell, RPLGPU_FRONTIER_NO_LABEL otherwise; words at and beyond width * height are never changed.
+ * d_rows + g * row_stride (optional, required with row_cap != 0; row_stride >= 8 row_cap words): the rows of the
+ * first min(kept, row_cap) kept components in ascending label order; rows beyond are never changed.
+ * d_goal_out + g * goal_stride and d_n_goal_out[g] (optional, both or neither; goal_stride >= 1), in
+ * rplgpu_nav_field_dev's d_goals / d_n_goals layout: BEST's cell and 1; with no BEST 0, the goal word untouched.
+ * d_scratch: rplgpu_frontiers_scratch_words words, 16-byte aligned, the caller's; it holds nothing between calls.
+ * RPLGPU_ERR_INVALID_ARG, nothing queued and no output changed, for a spec the check refuses, G = 0 or above 65535,
+ * comp_cap out of range, a missing d_grid, d_result or d_scratch, a misaligned pointer (4 bytes; d_scratch 16), the
+ * stride rules (E26's for the grid and the field), d_rows = NULL with row_cap != 0, one of the goal pointers without
+ * the other, and an output (d_labels_out, d_rows, d_goal_out, d_n_goal_out, d_result, d_scratch) that overlaps an
+ * input or another output over the ranges used; RPLGPU_ERR_CAPACITY for G * ntx * nty above RPLGPU_NAV_MAX_TILES.
+ * Asynchronous; nothing is stored on the handle. */
+int32_t rplgpu_frontiers_dev(rplgpu_handle_t h, const rplgpu_frontiers_t *f, const int8_t *d_grid,
+                             uint64_t grid_stride, const uint32_t *d_potential, uint64_t potential_stride, uint32_t G,
+                             uint32_t comp_cap, uint32_t *d_labels_out, uint64_t label_stride, uint32_t *d_rows,
+                             uint64_t row_stride, uint32_t row_cap, uint32_t *d_goal_out, uint64_t goal_stride,
+                             uint32_t *d_n_goal_out, uint32_t *d_result, uint32_t *d_scratch);
+/* ONE grid, HOST buffers, arguments as rplgpu_frontiers_host.  Allocates its device buffers and scratch per call and
+ * returns when the results are in place: a door, not a hot path. */
+int32_t rplgpu_frontiers(rplgpu_handle_t h, const rplgpu_frontiers_t *f, const int8_t *grid, const uint32_t *potential,
+                         uint32_t comp_cap, uint32_t *labels_out, uint32_t *rows, uint32_t row_cap, uint32_t *goal_out,
+                         uint32_t *n_goal_out, uint32_t result[16]);
+
 #ifdef __cplusplus
 }
 #endif

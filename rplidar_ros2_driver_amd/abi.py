@@ -63,6 +63,11 @@ MPPI_MAX_SPREAD_SHIFT = 256   # RPLGPU_MPPI_MAX_SPREAD_SHIFT
 MPPI_PER_LANE = 8             # RPLGPU_MPPI_PER_LANE: candidates a lane of the sums launch folds
 MPPI_MAX_BLOCKS = 1 << 23     # RPLGPU_MPPI_MAX_BLOCKS: workgroups of one launch
 MPPI_NO_WEIGHT, MPPI_OFF_RANGE, MPPI_EMPTY_STEP = 1, 2, 4
+FRONTIER_WORDS = 16           # RPLGPU_FRONTIER_WORDS (E29): result words per grid
+FRONTIER_ROW_WORDS = 8        # RPLGPU_FRONTIER_ROW_WORDS
+FRONTIER_MAX_COMPS = 1 << 20  # RPLGPU_FRONTIER_MAX_COMPS: the greatest comp_cap
+FRONTIER_NO_LABEL = 0xFFFFFFFF  # RPLGPU_FRONTIER_NO_LABEL
+FRONTIER_NONE, FRONTIER_NO_KEPT, FRONTIER_BOUND, FRONTIER_LOOP = 1, 2, 4, 8
 REFINE_PLANES = 29            # RPLGPU_REFINE_PLANES
 REFINE_MAX_ITERS = 16         # RPLGPU_REFINE_MAX_ITERS
 REFINE_STEPPED = 0x01         # E25's step flags
@@ -272,6 +277,12 @@ ABI_SYMBOLS = [
     "rplgpu_mppi_spread_host",
     "rplgpu_mppi_spread_dev",
     "rplgpu_mppi_spread",
+    "rplgpu_default_frontiers",
+    "rplgpu_frontiers_check",
+    "rplgpu_frontiers_scratch_words",
+    "rplgpu_frontiers_host",
+    "rplgpu_frontiers_dev",
+    "rplgpu_frontiers",
     # include/rplgpu_comm.h
     "rplgpu_comm_unique_id",
     "rplgpu_comm_init",
@@ -819,6 +830,28 @@ class NavField(C.Structure):
         return int(load_library().rplgpu_nav_field_check(C.byref(self)))
 
 
+class Frontiers(C.Structure):
+    """Mirror of ``rplgpu_frontiers_t`` (E29: a map's frontiers found, grouped and the next goal picked)."""
+
+    _fields_ = [(k, C.c_uint32) for k in (
+        "width", "height", "lethal", "min_size", "dist_weight", "size_weight")]
+
+    @classmethod
+    def defaults(cls, **kw) -> "Frontiers":
+        """The library's own defaults (``rplgpu_default_frontiers``), then the overrides."""
+        f = cls()
+        load_library().rplgpu_default_frontiers(C.byref(f))
+        for k, v in kw.items():
+            if not hasattr(f, k):
+                raise AttributeError(k)
+            setattr(f, k, v)
+        return f
+
+    def check(self) -> int:
+        """``rplgpu_frontiers_check``: OK or ERR_INVALID_ARG."""
+        return int(load_library().rplgpu_frontiers_check(C.byref(self)))
+
+
 class Rollout(C.Structure):
     """Mirror of ``rplgpu_rollout_t`` (E27: candidate motions rolled out of a pose and scored)."""
 
@@ -1205,6 +1238,15 @@ def load_library() -> C.CDLL:
     lib.rplgpu_mppi_spread_host.argtypes = [vp, u32, vp, u32, u32, u32, u32, vp]
     lib.rplgpu_mppi_spread_dev.argtypes = [vp, vp, u64, u32, u32, vp, u64, u32, u32, u32, u32, u32, u32, vp, u64]
     lib.rplgpu_mppi_spread.argtypes = [vp, vp, u32, vp, u32, u32, u32, u32, vp]
+    lib.rplgpu_default_frontiers.argtypes = [C.POINTER(Frontiers)]
+    lib.rplgpu_default_frontiers.restype = None
+    lib.rplgpu_frontiers_check.argtypes = [C.POINTER(Frontiers)]
+    lib.rplgpu_frontiers_scratch_words.argtypes = [C.POINTER(Frontiers), u32, u32]
+    lib.rplgpu_frontiers_scratch_words.restype = u64
+    lib.rplgpu_frontiers_host.argtypes = [C.POINTER(Frontiers), vp, vp, u32, vp, vp, u32, vp, vp, vp]
+    lib.rplgpu_frontiers_dev.argtypes = [vp, C.POINTER(Frontiers), vp, u64, vp, u64, u32, u32, vp, u64, vp, u64, u32,
+                                         vp, u64, vp, vp, vp]
+    lib.rplgpu_frontiers.argtypes = [vp, C.POINTER(Frontiers), vp, vp, u32, vp, vp, u32, vp, vp, vp]
     for name in ABI_SYMBOLS:
         fn = getattr(lib, name)
         if fn.restype is C.c_int:  # default
@@ -1854,6 +1896,24 @@ class RplGpu:
             pot.ctypes.data, result.ctypes.data, starts.ctypes.data, len(starts), paths.ctypes.data, max_len,
             info.ctypes.data))
         return pot, result, paths, info
+
+    def frontiers_dev(self, spec: "Frontiers", d_grid: int, grid_stride: int, d_potential: int, potential_stride: int,
+                      G: int, comp_cap: int, d_labels_out: int, label_stride: int, d_rows: int, row_stride: int,
+                      row_cap: int, d_goal_out: int, goal_stride: int, d_n_goal_out: int, d_result: int,
+                      d_scratch: int):
+        """E29: the frontier cells of G grids (d_potential 0: every free cell counts as reached) grouped into
+        components, sixteen result words at d_result + 16 g; optional labels, rows of the kept components and BEST's
+        cell in E26's goal layout.  d_scratch: ``frontiers_scratch_words(spec, G, comp_cap)`` uint32 words."""
+        self._check(self._lib.rplgpu_frontiers_dev(
+            self._h, C.byref(spec), d_grid, grid_stride, d_potential, potential_stride, G, comp_cap, d_labels_out,
+            label_stride, d_rows, row_stride, row_cap, d_goal_out, goal_stride, d_n_goal_out, d_result, d_scratch))
+
+    def frontiers(self, spec: "Frontiers", grid, potential=None, comp_cap: int = 4096, row_cap: int = 0,
+                  labels: bool = True, row_fill: int = 0, goal_fill: int = 0) -> dict:
+        """E29, one grid, host buffers -> the dictionary of ``frontiers_host``."""
+        a = _frontier_args(spec, grid, potential, comp_cap, row_cap, labels, row_fill, goal_fill)
+        self._check(self._lib.rplgpu_frontiers(self._h, *a[0]))
+        return a[1]
 
     def rollout_dev(self, spec: "Rollout", d_start: int, start_per_group: int, d_delta: int, delta_stride: int,
                     delta_per_group: int, delta_per_step: int, d_footprint: int, F: int, d_grid: int,
@@ -3074,6 +3134,53 @@ def nav_path_host(spec: NavField, grid, potential, start: int, max_len: int, pat
     if rc < 0:
         raise RplGpuError(rc, "rplgpu_nav_path_host")
     return path, info
+
+
+def frontiers_check(spec: Frontiers) -> None:
+    """Host only: validates an E29 spec by the library's own rplgpu_frontiers_check; raises RplGpuError."""
+    rc = load_library().rplgpu_frontiers_check(C.byref(spec))
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_frontiers_check")
+
+
+def frontiers_scratch_words(spec: Frontiers, G: int, comp_cap: int) -> int:
+    """Host only: the uint32 words of scratch ``frontiers_dev`` takes; 0 when refused."""
+    return int(load_library().rplgpu_frontiers_scratch_words(C.byref(spec), G, comp_cap))
+
+
+def _frontier_args(spec, grid, potential, comp_cap, row_cap, labels, row_fill, goal_fill):
+    """The argument list (behind the handle) that rplgpu_frontiers_host and rplgpu_frontiers share, and the
+    dictionary of the arrays it points into."""
+    grid = np.ascontiguousarray(grid, np.int8)
+    if grid.shape != (spec.height, spec.width):
+        raise RplGpuError(ERR_INVALID_ARG, "frontiers: a (height, width) int8 grid")
+    if potential is not None:
+        potential = np.ascontiguousarray(potential, np.uint32)
+        if potential.shape != grid.shape:
+            raise RplGpuError(ERR_INVALID_ARG, "frontiers: a potential of the grid's shape")
+    out = {
+        "labels": np.zeros(grid.shape, np.uint32) if labels else None,
+        "rows": np.full((row_cap, 8), row_fill, np.uint32),
+        "goal": np.full(1, goal_fill, np.uint32),
+        "n_goal": np.zeros(1, np.uint32),
+        "result": np.zeros(16, np.uint32),
+        "grid": grid, "potential": potential,
+    }
+    args = (C.byref(spec), grid.ctypes.data, potential.ctypes.data if potential is not None else 0, comp_cap,
+            out["labels"].ctypes.data if labels else 0, out["rows"].ctypes.data if row_cap else 0, row_cap,
+            out["goal"].ctypes.data, out["n_goal"].ctypes.data, out["result"].ctypes.data)
+    return args, out
+
+
+def frontiers_host(spec: Frontiers, grid, potential=None, comp_cap: int = 4096, row_cap: int = 0,
+                   labels: bool = True, row_fill: int = 0, goal_fill: int = 0) -> dict:
+    """Host only: rplgpu_frontiers_host, the flood fill -> ``{"labels" (height, width) uint32 or None, "rows"
+    (row_cap, 8) uint32 (rows beyond result[14] keep ``row_fill``), "goal" (1,), "n_goal" (1,), "result" (16,)}``."""
+    a = _frontier_args(spec, grid, potential, comp_cap, row_cap, labels, row_fill, goal_fill)
+    rc = load_library().rplgpu_frontiers_host(*a[0])
+    if rc != OK:
+        raise RplGpuError(rc, "rplgpu_frontiers_host")
+    return a[1]
 
 
 def rollout_check(spec: Rollout) -> None:

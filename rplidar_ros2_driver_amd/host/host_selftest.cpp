@@ -400,6 +400,37 @@ int main(int argc, char **argv) {
     }
     std::printf("mppi: weights %u and %u, the blended step moves %g, spread around it %g and %g\n", mp_weights[0],
                 mp_weights[1], (double)mp_nominal[2], (double)mp_next[2], (double)mp_next[6]);
+    // E29 over that costmap with the field of E26 above (its goal standing in for the robot): the door against the
+    // library's own host twin, word for word, and the goal it picks is a frontier cell of the labels.
+    rplgpu_frontiers_t fro;
+    rplgpu_default_frontiers(&fro);
+    fro.width = cost_msg.info.width;
+    fro.height = cost_msg.info.height;
+    fro.min_size = 1;
+    rplgpu_host::ScanPath::FrontierResult fres;
+    std::vector<rplgpu_host::ScanPath::FrontierRow> frows;
+    std::vector<uint32_t> flabels;
+    if (!path.frontiers(cost_msg, fro, &potential, 64, 4, fres, &frows, &flabels)) {
+      std::fprintf(stderr, "frontiers failed: %s\n", path.last_error().c_str());
+      return 11;
+    }
+    {
+      std::vector<int8_t> bytes(cost_msg.data.begin(), cost_msg.data.end());
+      uint32_t twin[RPLGPU_FRONTIER_WORDS], twin_goal = 0, twin_n = 0;
+      std::vector<uint32_t> twin_labels(bytes.size()), twin_rows(32);
+      if (rplgpu_frontiers_host(&fro, bytes.data(), potential.data(), 64, twin_labels.data(), twin_rows.data(), 4,
+                                &twin_goal, &twin_n, twin) != RPLGPU_OK ||
+          twin[1] != fres.frontier_cells || twin[2] != fres.components || twin[3] != fres.kept ||
+          twin[5] != fres.best.label || twin[8] != fres.best.nearest_cell || (twin_n != 0) != fres.has_goal ||
+          (twin_n && twin_goal != fres.goal_cell) || twin_labels != flabels || frows.size() != twin[14] ||
+          (fres.has_goal && flabels[fres.goal_cell] != fres.best.label)) {
+        std::fprintf(stderr, "frontiers: wrong answer (%u cells, %u components, %u kept)\n", fres.frontier_cells,
+                     fres.components, fres.kept);
+        return 12;
+      }
+    }
+    std::printf("frontiers: %u cells in %u component(s), %u kept, the goal %s cell %u\n", fres.frontier_cells,
+                fres.components, fres.kept, fres.has_goal ? "is" : "would be", fres.goal_cell);
     // E14: the three rays of the E11 leg added twice into a count map.  Per call the row of the sensor gets
     // misses 3 3 2 2 1 1 (the whole ray beyond obstacle_max leaves its end cell 4 alone, the cut one counts its
     // end cell 5) and one hit in cell 2; after two calls the default rule (2 observations, 10 %) gives the E11 row.

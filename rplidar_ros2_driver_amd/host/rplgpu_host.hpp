@@ -27,6 +27,7 @@
 //         -> rplgpu_host::ScanPath::rollout(costmap_msg, rule, start, deltas, per_step, footprint, potential, ...)  (E27)
 //         -> rplgpu_host::ScanPath::mppi_update(rule, rollout_out, rollout_words, deltas, table, nominal, ...)  (E28)
 //         -> rplgpu_host::ScanPath::mppi_spread(nominal, noise, K, shift, keep_first, candidates)  (E28)
+//         -> rplgpu_host::ScanPath::frontiers(grid_msg, rule, potential, comp_cap, row_cap, result, rows, labels)  (E29)
 //   mat the localisation side's loop (a correlative scan matcher's search window over a likelihood field):
 //         -> rplgpu_host::ScanPath::match_scans(scans, ..., field_msg, window, result)  (E13)
 //         -> rplgpu_host::ScanPath::match_wide(scans, ..., field_msg, window, result)   (E24: up to 256 cells a side)
@@ -622,6 +623,69 @@ class ScanPath {
     result.greatest = res[5];
     result.tile_visits = res[6];
     result.rounds = res[7];
+    return true;
+  }
+
+  // ext E29 (include/rplgpu_msg.h): the frontier cells of a grid (free, reachable, next to unknown space) grouped into
+  // 8-connected components and the next goal picked — explore_lite's search.  lethal / min_size / dist_weight /
+  // size_weight of `rule` are used, its size comes from grid_msg.info.  potential: E26's field with the robot's own
+  // cell as the goal (nav_field's output), or null: every free cell then counts as reached.  rows: up to row_cap
+  // kept components in ascending label order; labels (optional): one word per cell.
+  struct FrontierRow {
+    uint32_t label = 0, cells = 0, nearest = 0, nearest_cell = 0;
+    uint64_t sum_x = 0, sum_y = 0;
+  };
+  struct FrontierResult {
+    uint32_t flags = 0, frontier_cells = 0, components = 0, kept = 0, dropped_cells = 0, greatest = 0;
+    bool has_goal = false;
+    uint32_t goal_cell = 0;
+    FrontierRow best;
+  };
+  template <class OccupancyGridT>
+  bool frontiers(const OccupancyGridT &grid_msg, const rplgpu_frontiers_t &rule, const std::vector<uint32_t> *potential,
+                 uint32_t comp_cap, uint32_t row_cap, FrontierResult &result, std::vector<FrontierRow> *rows = nullptr,
+                 std::vector<uint32_t> *labels = nullptr) {
+    if (!h_) return fail("rplgpu handle not configured");
+    last_error_.clear();
+    rplgpu_frontiers_t f = rule;
+    f.width = grid_msg.info.width;
+    f.height = grid_msg.info.height;
+    const size_t n_cells = static_cast<size_t>(f.width) * f.height;
+    if (n_cells == 0 || grid_msg.data.size() != n_cells) return fail("frontiers: data is not width x height");
+    if (potential && potential->size() != n_cells) return fail("frontiers: the potential is not width x height");
+    if (row_cap != 0 && !rows) return fail("frontiers: row_cap needs rows");
+    occ_prev_.assign(grid_msg.data.begin(), grid_msg.data.end());
+    if (labels) labels->assign(n_cells, RPLGPU_FRONTIER_NO_LABEL);
+    std::vector<uint32_t> flat(8u * static_cast<size_t>(row_cap), 0u);
+    uint32_t res[RPLGPU_FRONTIER_WORDS] = {0}, goal = 0, n_goal = 0;
+    if (rplgpu_frontiers(h_, &f, occ_prev_.data(), potential ? potential->data() : nullptr, comp_cap,
+                         labels ? labels->data() : nullptr, row_cap ? flat.data() : nullptr, row_cap, &goal, &n_goal,
+                         res) != RPLGPU_OK)
+      return note_error();
+    const auto row_of = [](const uint32_t *w) {
+      FrontierRow r;
+      r.label = w[0];
+      r.cells = w[1];
+      r.sum_x = (static_cast<uint64_t>(w[3]) << 32) | w[2];
+      r.sum_y = (static_cast<uint64_t>(w[5]) << 32) | w[4];
+      r.nearest = w[6];
+      r.nearest_cell = w[7];
+      return r;
+    };
+    if (rows) {
+      rows->clear();
+      for (uint32_t i = 0; i < res[14]; ++i) rows->push_back(row_of(&flat[8u * i]));
+    }
+    result.flags = res[0];
+    result.frontier_cells = res[1];
+    result.components = res[2];
+    result.kept = res[3];
+    result.dropped_cells = res[4];
+    result.greatest = res[13];
+    result.has_goal = n_goal != 0;
+    result.goal_cell = goal;
+    const uint32_t best[8] = {res[5], res[6], res[9], res[10], res[11], res[12], res[7], res[8]};
+    result.best = row_of(best);
     return true;
   }
 
