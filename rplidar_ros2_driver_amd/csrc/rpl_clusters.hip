@@ -54,6 +54,7 @@
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
 #include "rpl_moments.hpp"
+#include "rpl_unionfind.hpp"
 #include "rplgpu_msg.h"
 
 namespace rpl {
@@ -102,10 +103,6 @@ struct ClArgs {
   u64 map_stride;
   uint32_t *scratch;
 };
-
-__device__ __forceinline__ uint32_t cl_load(const uint32_t *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // word w of a group's map with the bits at and beyond NB masked
 __device__ __forceinline__ uint32_t cl_word(const uint32_t *map, uint32_t w, uint32_t nb) {
@@ -172,43 +169,9 @@ __global__ __launch_bounds__(kBlock) void k_cl_init(ClArgs a) {
   reinterpret_cast<u64 *>(grp + l.tabw)[r] = 0ull;
 }
 
-// The root of x.  Parents strictly decrease, so the walk ends within K steps; at the bound bit 5 is set and the walk
-// leaves where it stands.  Every value read is clamped below kc.  A node found two steps below its grandparent is hung
-// under it (atomicMin: a pointer only ever moves to a smaller node of the SAME tree — only roots are ever hooked to
-// another tree — so every node keeps reaching its tree's root and the later walks are short).
-__device__ __forceinline__ uint32_t cl_find(uint32_t *parent, uint32_t x, uint32_t K, uint32_t kc, uint32_t *hdr) {
-  for (uint32_t step = 0;; ++step) {  // bound: K steps (x strictly decreases)
-    const uint32_t p = min(cl_load(parent + x), kc - 1u);
-    if (p >= x) return x;  // (p == x: a root; p > x cannot be, and would end the walk as well)
-    const uint32_t gp = min(cl_load(parent + p), kc - 1u);
-    if (gp >= p) return p;
-    if (step >= K) {
-      atomicOr(hdr + H_FLAGS, 32u);
-      return x;
-    }
-    atomicMin(parent + x, gp);
-    x = gp;
-  }
-}
-
-__device__ __forceinline__ void cl_unite(uint32_t *parent, uint32_t a, uint32_t b, uint32_t K, uint32_t kc,
-                                         uint32_t *hdr) {
-  // bound: 2 K + 2 rounds — a round that does not end the loop replaces the larger of (a, b) by a smaller value and
-  // never raises the other
-  for (uint32_t round = 0;; ++round) {
-    a = cl_find(parent, a, K, kc, hdr);
-    b = cl_find(parent, b, K, kc, hdr);
-    if (a == b) return;
-    if (round >= 2u * K + 2u) {
-      atomicOr(hdr + H_FLAGS, 32u);
-      return;
-    }
-    const uint32_t hi = max(a, b), lo = min(a, b);
-    const uint32_t old = min(atomicCAS(parent + hi, hi, lo), kc - 1u);
-    if (old == hi) return;  // hi was still a root and now hangs under lo
-    a = old;                // somebody hooked hi under old < hi in between, and nothing was written: go on from there
-    b = lo;
-  }
+// the union-find over the ranks (rpl_unionfind.hpp): values clamped below kc, walks bounded by K, bit 5 at the bound
+__device__ __forceinline__ UfGlobal cl_uf(uint32_t K, uint32_t kc, uint32_t *hdr) {
+  return UfGlobal{kc, K, hdr + H_FLAGS, 32u};
 }
 
 __global__ __launch_bounds__(kBlock) void k_cl_link(ClArgs a) {
@@ -237,7 +200,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_link(ClArgs a) {
     }
     const uint32_t q = (k * a.ny + (uint32_t)y) * a.nx + (uint32_t)x;  // below NB
     if (q == b || !((cl_word(map, q >> 5, a.nb) >> (q & 31u)) & 1u)) continue;
-    cl_unite(parent, r, cl_rank(map, grp, l, q, a.nb), K, l.kc, grp);
+    uf_unite(parent, r, cl_rank(map, grp, l, q, a.nb), cl_uf(K, l.kc, grp));
   }
 }
 
@@ -252,7 +215,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_flatten(ClArgs a) {
   const uint32_t r = blockIdx.x * kClBlock + threadIdx.x;
   uint32_t is_root = 0u;
   if (r < K) {
-    const uint32_t root = cl_find(grp + l.parent, r, K, l.kc, grp);
+    const uint32_t root = uf_find(grp + l.parent, r, cl_uf(K, l.kc, grp));
     grp[l.root + r] = root;
     is_root = root == r ? 1u : 0u;
   }

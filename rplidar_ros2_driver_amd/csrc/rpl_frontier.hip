@@ -36,6 +36,7 @@
 #include "rpl_device.hpp"
 #include "rpl_launch.hpp"
 #include "rpl_frontier.hpp"
+#include "rpl_unionfind.hpp"
 #include "rplgpu_msg.h"
 
 namespace rpl {
@@ -78,75 +79,11 @@ __device__ __forceinline__ FrTileAt fr_tile_at(const FrArgs &a) {
   return FrTileAt{g, (t % a.l.tiles_x) * kFrTile, (t / a.l.tiles_x) * kFrTile};
 }
 
-__device__ __forceinline__ uint32_t fr_load(const uint32_t *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t fr_load_lds(const uint32_t *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// ---- the tile's own union-find, in LDS: nodes are the tile's cells (the first cell of a run stands for the run) ----
-__device__ __forceinline__ uint32_t fr_find_lds(const uint32_t *par, uint32_t x, uint32_t *loop) {
-  for (uint32_t step = 0;; ++step) {  // bound: kFrTileCells steps (x strictly decreases)
-    const uint32_t p = min(fr_load_lds(par + x), kFrTileCells - 1u);
-    if (p >= x) return x;
-    if (step >= kFrTileCells) {
-      *loop = 1u;
-      return x;
-    }
-    x = p;
-  }
-}
-__device__ __forceinline__ void fr_unite_lds(uint32_t *par, uint32_t a, uint32_t b, uint32_t *loop) {
-  // bound: 2 kFrTileCells + 2 rounds — a round that does not end the loop replaces the larger of (a, b) by a smaller
-  // value and never raises the other
-  for (uint32_t round = 0;; ++round) {
-    a = fr_find_lds(par, a, loop);
-    b = fr_find_lds(par, b, loop);
-    if (a == b) return;
-    if (round >= 2u * kFrTileCells + 2u) {
-      *loop = 1u;
-      return;
-    }
-    const uint32_t hi = max(a, b), lo = min(a, b);
-    const uint32_t old = min(atomicCAS(par + hi, hi, lo), kFrTileCells - 1u);
-    if (old == hi) return;
-    a = old;
-    b = lo;
-  }
-}
-
-// ---- the union-find across tiles, on the parent plane: E21's cl_find / cl_unite with cells for ranks ----
-__device__ __forceinline__ uint32_t fr_find(uint32_t *parent, uint32_t x, uint32_t cells, uint32_t *hdr) {
-  for (uint32_t step = 0;; ++step) {  // bound: cells steps (x strictly decreases)
-    const uint32_t p = min(fr_load(parent + x), cells - 1u);
-    if (p >= x) return x;
-    const uint32_t gp = min(fr_load(parent + p), cells - 1u);
-    if (gp >= p) return p;
-    if (step >= cells) {
-      atomicOr(hdr + FH_FLAGS, RPLGPU_FRONTIER_LOOP);
-      return x;
-    }
-    atomicMin(parent + x, gp);
-    x = gp;
-  }
-}
-__device__ __forceinline__ void fr_unite(uint32_t *parent, uint32_t a, uint32_t b, uint32_t cells, uint32_t *hdr) {
-  // bound: 2 cells + 2 rounds, as fr_unite_lds
-  for (uint32_t round = 0;; ++round) {
-    a = fr_find(parent, a, cells, hdr);
-    b = fr_find(parent, b, cells, hdr);
-    if (a == b) return;
-    if (round >= 2u * cells + 2u) {
-      atomicOr(hdr + FH_FLAGS, RPLGPU_FRONTIER_LOOP);
-      return;
-    }
-    const uint32_t hi = max(a, b), lo = min(a, b);
-    const uint32_t old = min(atomicCAS(parent + hi, hi, lo), cells - 1u);
-    if (old == hi) return;  // hi was still a root and now hangs under lo
-    a = old;                // somebody hooked hi under old < hi in between: go on from there
-    b = lo;
-  }
+// the two union-finds (rpl_unionfind.hpp).  The tile's own, in LDS: nodes are the tile's cells (the first cell of a
+// run stands for the run).  Across tiles, on the parent plane: nodes are the grid's cells, as E21's are its ranks.
+__device__ __forceinline__ UfLds fr_uf_lds(uint32_t *loop) { return UfLds{kFrTileCells, kFrTileCells, loop}; }
+__device__ __forceinline__ UfGlobal fr_uf(uint32_t cells, uint32_t *hdr) {
+  return UfGlobal{cells, cells, hdr + FH_FLAGS, RPLGPU_FRONTIER_LOOP};
 }
 
 // the bits [from, from + len) of a 64-bit word, len in 1 .. 64
@@ -235,7 +172,7 @@ __global__ __launch_bounds__(kFrTileBlock) void k_fr_tile(FrArgs a) {
     for (uint32_t k = 0; touch && k < 33u; ++k) {  // bound: 33 runs of a row touch one run
       const uint32_t q = (uint32_t)__builtin_ctzll(touch);
       const uint32_t s2 = fr_run_start(below, q), end2 = q + fr_run_len(below, q);
-      fr_unite_lds(s_par, row * kFrTile + s, (row + 1u) * kFrTile + s2, &loop);
+      uf_unite(s_par, row * kFrTile + s, (row + 1u) * kFrTile + s2, fr_uf_lds(&loop));
       touch = end2 >= 64u ? 0ull : touch & ~((1ull << end2) - 1ull);
     }
   }
@@ -246,7 +183,7 @@ __global__ __launch_bounds__(kFrTileBlock) void k_fr_tile(FrArgs a) {
     const fu64 mr = (fu64)s_mask[2u * ly] | ((fu64)s_mask[2u * ly + 1u] << 32);
     uint32_t label = kFrNone;
     if ((mr >> lx) & 1ull) {
-      const uint32_t root = fr_find_lds(s_par, ly * kFrTile + fr_run_start(mr, lx), &loop);
+      const uint32_t root = uf_find(s_par, ly * kFrTile + fr_run_start(mr, lx), fr_uf_lds(&loop));
       label = (at.y0 + (root >> 6)) * a.width + at.x0 + (root & 63u);  // a frontier cell: inside the grid
     }
     parent[(size_t)y * a.width + x] = label;
@@ -265,13 +202,13 @@ __global__ __launch_bounds__(kFrSeamBlock) void k_fr_seam(FrArgs a) {
   const uint32_t y = column ? at.y0 + threadIdx.x : at.y0 + kFrTile - 1u;
   if (x >= a.width || y >= a.height) return;
   const uint32_t c = y * a.width + x;
-  if (fr_load(parent + c) == kFrNone) return;
+  if (UfGlobal::load(parent + c) == kFrNone) return;
   for (int n = -1; n <= 1; ++n) {  // the last column: NE, E, SE; the last row: SW, S, SE
     const int nx = column ? (int)x + 1 : (int)x + n, ny = column ? (int)y + n : (int)y + 1;
     if (nx < 0 || ny < 0 || nx >= (int)a.width || ny >= (int)a.height) continue;
     const uint32_t q = (uint32_t)ny * a.width + (uint32_t)nx;  // below cells
-    if (fr_load(parent + q) == kFrNone) continue;
-    fr_unite(parent, c, q, cells, grp);
+    if (UfGlobal::load(parent + q) == kFrNone) continue;
+    uf_unite(parent, c, q, fr_uf(cells, grp));
   }
 }
 
@@ -285,8 +222,8 @@ __global__ __launch_bounds__(kBlock) void k_fr_flatten(FrArgs a, uint32_t *__res
   uint32_t is_root = 0u;
   if (c < cells) {
     uint32_t label = kFrNone;
-    if (fr_load(parent + c) != kFrNone) {
-      label = fr_find(parent, c, cells, grp);
+    if (UfGlobal::load(parent + c) != kFrNone) {
+      label = uf_find(parent, c, fr_uf(cells, grp));
       atomicMin(parent + c, label);
       is_root = label == c ? 1u : 0u;
     }

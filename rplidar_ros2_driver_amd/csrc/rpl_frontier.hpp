@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "rplgpu_msg.h"
+#include "rpl_rules.hpp"
 
 namespace rpl {
 
@@ -35,9 +36,7 @@ inline bool frontier_layout(uint32_t width, uint32_t height, uint32_t G, uint32_
   if (width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 || height > RPLGPU_MAX_OCC_DIM || G == 0 ||
       G > 65535u || comp_cap == 0 || comp_cap > RPLGPU_FRONTIER_MAX_COMPS)
     return false;
-  l->tiles_x = (width + RPLGPU_NAV_TILE - 1u) / RPLGPU_NAV_TILE;
-  l->tiles_y = (height + RPLGPU_NAV_TILE - 1u) / RPLGPU_NAV_TILE;
-  if ((uint64_t)G * l->tiles_x * l->tiles_y > RPLGPU_NAV_MAX_TILES) {
+  if (!nav_tiles(width, height, G, &l->tiles_x, &l->tiles_y)) {
     if (capacity) *capacity = true;
     return false;
   }

@@ -161,16 +161,56 @@ inline bool device_readable(rplgpu_ctx *c, std::initializer_list<PtrCheck> list)
   return true;
 }
 
+// ---- the table of a call's byte ranges --------------------------------------------------------------------------------
+struct Range {
+  const void *p;
+  uint64_t bytes;
+  bool out;
+};
+// No output may share a byte with an input or with another output.  A pair is passed over when neither is an output,
+// when either pointer is NULL or either length 0 (an optional argument that was not given), or when it is the pair
+// (skip_a, skip_b) of entries, skip_a < skip_b, which the caller has found to be ONE range read and written element
+// by element (an accepted in-place form).
+template <size_t N>
+inline bool ranges_clash(const Range (&ranges)[N], int skip_a = -1, int skip_b = -1) {
+  for (size_t i = 0; i < N; ++i) {
+    for (size_t j = i + 1; j < N; ++j) {
+      const Range &a = ranges[i], &b = ranges[j];
+      if (!(a.out || b.out) || !a.p || !b.p || !a.bytes || !b.bytes || ((int)i == skip_a && (int)j == skip_b)) continue;
+      if (rpl::ranges_overlap(a.p, a.bytes, b.p, b.bytes)) return true;
+    }
+  }
+  return false;
+}
+
+// a spec its check refused: c->err is "<fn>: invalid <type> (see include/rplgpu_msg.h)"
+inline int32_t refuse_spec(rplgpu_ctx *c, const char *fn, const char *type) {
+  c->err = std::string(fn) + ": invalid " + type + " (see include/rplgpu_msg.h)";
+  return RPLGPU_ERR_INVALID_ARG;
+}
+
+// a refusal with its reason: c->err is "<fn>: <what>"; false
+inline bool refuse(rplgpu_ctx *c, const char *fn, const char *what) {
+  c->err = std::string(fn) + ": " + what;
+  return false;
+}
+
+// the grid planes and the field planes of E26, E27 and E29 (d_potential NULL: the call takes none), `cells` a plane
+inline bool planes_ok(rplgpu_ctx *c, const char *fn, uint64_t cells, const void *d_grid, uint64_t grid_stride,
+                      const void *d_potential, uint64_t potential_stride) {
+  return (grid_stride >= cells && !(grid_stride & 3u) && !misaligned(d_grid, 3u) &&
+          (!d_potential || potential_stride >= cells) && !misaligned(d_potential, 3u)) ||
+         refuse(c, fn, "grid_stride must be >= width * height and a multiple of 4, potential_stride >= width * height, "
+                       "d_grid and d_potential 4-byte aligned");
+}
+
 // ---- the pose-list doors ----------------------------------------------------------------------------------------------
 // What the doors of the pose-list stages refuse alike, in parts, because a door tests its pointers between the counts
 // and the strides and the order of its tests is part of what a caller sees.  false: c->err is "<fn>: <what>".
 struct PoseListDoor {
   rplgpu_ctx *c;
   const char *fn;
-  bool refuse(const char *what) const {
-    c->err = std::string(fn) + ": " + what;
-    return false;
-  }
+  bool refuse(const char *what) const { return rpl::host::refuse(c, fn, what); }
   // (the tiles of a group by the groups: a grid's second dimension)
   bool groups(uint32_t G) const { return (G != 0 && G <= 65535u) || refuse("G must be in 1 .. 65535"); }
   bool poses(uint32_t P) const {
@@ -219,6 +259,16 @@ class DoorBuffer {
   template <class T = unsigned char>
   T *at(size_t off) const {
     return off == kAbsent ? nullptr : reinterpret_cast<T *>(d_ + off);
+  }
+  // (inside the body) a host block queued into a part, a part queued out to a host block, on the handle's stream; a
+  // NULL block, an absent part or no bytes: nothing
+  hipError_t put(size_t off, const void *src, size_t bytes) const {
+    if (!src || off == kAbsent || !bytes) return hipSuccess;
+    return hipMemcpyAsync(d_ + off, src, bytes, hipMemcpyHostToDevice, h_->stream);
+  }
+  hipError_t get(void *dst, size_t off, size_t bytes) const {
+    if (!dst || off == kAbsent || !bytes) return hipSuccess;
+    return hipMemcpyAsync(dst, d_ + off, bytes, hipMemcpyDeviceToHost, h_->stream);
   }
   // body: the uploads, the _dev call, the downloads and ONE synchronise; its return code is the door's
   template <class Body>

@@ -31,6 +31,7 @@
 
 #include "rpl_device.hpp"
 #include "rplgpu_msg.h"
+#include "rpl_rules.hpp"
 #include "rpl_nav.hpp"
 
 namespace rpl {
@@ -47,10 +48,7 @@ static_assert((unsigned long long)RPLGPU_NAV_MAX_CAP + 7ull * RPLGPU_NAV_MAX_COS
 constexpr uint32_t kBit4 = 1u << 11, kBit5 = 1u << 12, kBit6 = 1u << 13, kBit7 = 1u << 14;  // steps 4 .. 7 allowed
 
 __device__ __forceinline__ uint32_t nav_weight(const NavK &k, uint32_t byte) {
-  const int v = (int)(int8_t)byte;
-  if (v < 0) return k.unknown_cost;
-  if ((uint32_t)v >= k.lethal) return 0u;
-  return k.neutral + k.factor * (uint32_t)v;
+  return nav_byte_weight(k, (int)(int8_t)byte);
 }
 
 // the least of what the four straight (n4) and the permitted diagonal (n7) neighbours offer a cell of weight w
@@ -211,6 +209,18 @@ __global__ __launch_bounds__(kNavThreads) void k_nav_relax(NavK k, const uint8_t
   }
 }
 
+// The workgroup's sum of one value a thread, for k_nav_goals and k_nav_close (local to this unit: written for whole
+// waves of 64 and a word at *s_sum that one thread cleared in front of a barrier the workgroup has passed).  The
+// waves' sums meet in *s_sum by one LDS atomic a wave that has something to add; every thread passes the barrier
+// inside and reads the total behind it.
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *s_sum) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+  if (lane_id() == 0 && v) atomicAdd(s_sum, v);
+  __syncthreads();
+  return *s_sum;
+}
+
 // blockIdx.y: the grid.  The field UNREACHED and both planes clear unless resumed; the result words zero.
 __global__ __launch_bounds__(kNavThreads) void k_nav_init(uint32_t cells, uint32_t tiles, uint32_t *potential,
                                                           unsigned long long potential_stride, uint32_t *flags,
@@ -256,13 +266,10 @@ __global__ __launch_bounds__(kNavThreads) void k_nav_goals(uint32_t W, uint32_t 
     for (uint32_t ty = ty0; ty <= ty1; ++ty)
       for (uint32_t tx = tx0; tx <= tx1; ++tx) plane0[ty * tiles_x + tx] = 1u;
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) taken += __shfl_xor(taken, d, 64);
-  if (lane_id() == 0 && taken) atomicAdd(&s_taken, taken);
-  __syncthreads();
+  taken = block_sum(taken, &s_taken);
   if (threadIdx.x == 0) {
-    result[8u * g + 2u] = s_taken;
-    result[8u * g + 3u] = n - s_taken;
+    result[8u * g + 2u] = taken;
+    result[8u * g + 3u] = n - taken;
   }
 }
 
@@ -284,17 +291,16 @@ __global__ __launch_bounds__(kNavThreads) void k_nav_close(uint32_t tiles, uint3
       plane1[i] = 0u;
     }
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) count += __shfl_xor(count, d, 64);
-  if (lane_id() == 0 && count) atomicAdd(&s_count, count);
-  __syncthreads();
+  count = block_sum(count, &s_count);
   if (threadIdx.x == 0) {
-    result[8u * g + 0u] = s_count;
-    result[8u * g + 1u] = s_count ? RPLGPU_NAV_UNFINISHED : 0u;
+    result[8u * g + 0u] = count;
+    result[8u * g + 1u] = count ? RPLGPU_NAV_UNFINISHED : 0u;
   }
 }
 
-// blockIdx.y: the grid.  The reached cells and the greatest reached value into words 4 and 5.
+// blockIdx.y: the grid.  The reached cells and the greatest reached value into words 4 and 5.  The sum and the greatest
+// value go through ONE butterfly loop and ONE barrier, written out here: with block_sum and a block-max of its kind
+// beside it the kernel came out with 11 VGPRs for 8 (and 193 instructions for 190), so this call site keeps its copy.
 __global__ __launch_bounds__(kNavThreads) void k_nav_stats(uint32_t cells, const uint32_t *__restrict__ potential,
                                                            unsigned long long potential_stride, uint32_t *result) {
   __shared__ uint32_t s_n, s_max;
@@ -422,9 +428,9 @@ hipError_t launch_nav_goals(hipStream_t s, const NavK &k, uint32_t G, const uint
 hipError_t launch_nav_relax(hipStream_t s, const NavK &k, uint32_t G, const int8_t *grid,
                             unsigned long long grid_stride, uint32_t *potential, unsigned long long potential_stride,
                             uint32_t *flags, uint32_t round, uint32_t *result) {
-  const unsigned long long blocks = (unsigned long long)G * k.tiles_x * k.tiles_y;
-  if (blocks == 0 || blocks > RPLGPU_NAV_MAX_TILES) return hipErrorInvalidValue;  // (x 256 threads: below 2^32)
-  hipLaunchKernelGGL(k_nav_relax, dim3((uint32_t)blocks), dim3(kNavThreads), 0, s, k, (const uint8_t *)grid,
+  uint32_t tiles_x, tiles_y;
+  if (!nav_tiles(k.width, k.height, G, &tiles_x, &tiles_y)) return hipErrorInvalidValue;  // (x 256 threads: below 2^32)
+  hipLaunchKernelGGL(k_nav_relax, dim3(G * tiles_x * tiles_y), dim3(kNavThreads), 0, s, k, (const uint8_t *)grid,
                      grid_stride, potential, potential_stride, flags, round, result);
   return hipGetLastError();
 }

@@ -22,6 +22,25 @@ inline bool ranges_overlap(const void *a, uint64_t na, const void *b, uint64_t n
   return pa < pb + nb && pb < pa + na;
 }
 
+// the RPLGPU_NAV_TILE-cell tiles of a width x height grid, a workgroup each in E26's rounds and E29's labelling;
+// false: G grids of them are no launch (none, or above RPLGPU_NAV_MAX_TILES)
+inline bool nav_tiles(uint32_t width, uint32_t height, uint64_t G, uint32_t *tiles_x, uint32_t *tiles_y) {
+  *tiles_x = (width + RPLGPU_NAV_TILE - 1u) / RPLGPU_NAV_TILE;
+  *tiles_y = (height + RPLGPU_NAV_TILE - 1u) / RPLGPU_NAV_TILE;
+  const uint64_t all = G * *tiles_x * *tiles_y;  // (G below 2^32, a side at most RPLGPU_MAX_OCC_DIM: no carry)
+  return all != 0 && all <= RPLGPU_NAV_MAX_TILES;
+}
+
+// E26's weight of a costmap byte v (as int8), 0: impassable; on the device and on the host, as bin_map_words.  Spec:
+// the public rplgpu_nav_field_t or the kernels' copy of it, by reference (by value the fields cost k_nav_relax its
+// instruction count: DESIGN.md, the planner stages' shared pieces)
+template <class Spec>
+constexpr uint32_t nav_byte_weight(const Spec &s, int v) {
+  if (v < 0) return s.unknown_cost;
+  if ((uint32_t)v >= s.lethal) return 0u;
+  return s.neutral + s.factor * (uint32_t)v;
+}
+
 // the check of a match spec, E13's (rplgpu_scan_match_t) and E24's (rplgpu_wide_match_t, which adds its own
 // max_blocks test): the two structs begin with the same fields and differ in the shift they allow
 #define RPL_SAME_FIELD(f)                                                                                  \

@@ -2,7 +2,7 @@
 // (include/rplgpu_msg.h), in plain C++: the default, the check, the scratch size and the host twin — a flood fill over
 // the frontier cells in ascending cell index ("the definition a reader can run").  No handle, no stream, no HIP
 // header; built like rplgpu_nav_rules.cpp.  The doors that call these are in rplgpu_frontier_stages.hip;
-// tools/dev/frontier_rules_asan.cpp drives this file alone under the host sanitizers.
+// tools/dev/plan_rules_asan.cpp drives this file under the host sanitizers.
 #include <cstring>
 #include <vector>
 

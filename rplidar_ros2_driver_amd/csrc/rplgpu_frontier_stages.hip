@@ -19,29 +19,6 @@
 
 using namespace rpl::host;
 
-namespace {
-
-struct Range {
-  const void *p;
-  uint64_t bytes;
-  bool out;
-};
-
-// no output may share a byte with an input or with another output
-template <size_t N>
-bool ranges_clash(const Range (&ranges)[N]) {
-  for (size_t i = 0; i < N; ++i) {
-    for (size_t j = i + 1; j < N; ++j) {
-      const Range &a = ranges[i], &b = ranges[j];
-      if (!(a.out || b.out) || !a.p || !b.p || !a.bytes || !b.bytes) continue;
-      if (rpl::ranges_overlap(a.p, a.bytes, b.p, b.bytes)) return true;
-    }
-  }
-  return false;
-}
-
-}  // namespace
-
 extern "C" {
 
 int32_t rplgpu_frontiers_dev(rplgpu_handle_t h, const rplgpu_frontiers_t *f, const int8_t *d_grid,
@@ -52,11 +29,9 @@ int32_t rplgpu_frontiers_dev(rplgpu_handle_t h, const rplgpu_frontiers_t *f, con
   const char *fn = "rplgpu_frontiers_dev";
   const std::string at = std::string(fn) + ": ";
   if (!h || !f) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_frontiers_check(f) != RPLGPU_OK) {
-    h->err = at + "invalid rplgpu_frontiers_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!PoseListDoor{h, fn}.groups(G)) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_frontiers_check(f) != RPLGPU_OK) return refuse_spec(h, fn, "rplgpu_frontiers_t");
+  const PoseListDoor door{h, fn};
+  if (!door.groups(G)) return RPLGPU_ERR_INVALID_ARG;
   if (comp_cap == 0 || comp_cap > RPLGPU_FRONTIER_MAX_COMPS) {
     h->err = at + "comp_cap must be in 1 .. RPLGPU_FRONTIER_MAX_COMPS";
     return RPLGPU_ERR_INVALID_ARG;
@@ -66,18 +41,16 @@ int32_t rplgpu_frontiers_dev(rplgpu_handle_t h, const rplgpu_frontiers_t *f, con
                   "d_n_goal_out both or neither";
     return RPLGPU_ERR_INVALID_ARG;
   }
-  if (misaligned(d_grid, 3u) || misaligned(d_potential, 3u) || misaligned(d_labels_out, 3u) ||
-      misaligned(d_rows, 3u) || misaligned(d_goal_out, 3u) || misaligned(d_n_goal_out, 3u) ||
-      misaligned(d_result, 3u) || misaligned(d_scratch, 15u)) {
+  if (misaligned(d_labels_out, 3u) || misaligned(d_rows, 3u) || misaligned(d_goal_out, 3u) ||
+      misaligned(d_n_goal_out, 3u) || misaligned(d_result, 3u) || misaligned(d_scratch, 15u)) {
     h->err = at + "every pointer must be 4-byte aligned, d_scratch 16-byte";
     return RPLGPU_ERR_INVALID_ARG;
   }
   const uint64_t cells = (uint64_t)f->width * f->height;
-  if (grid_stride < cells || (grid_stride & 3u) || (d_potential && potential_stride < cells) ||
-      (d_labels_out && label_stride < cells) || (d_rows && row_stride < 8ull * row_cap) ||
+  if (!planes_ok(h, fn, cells, d_grid, grid_stride, d_potential, potential_stride)) return RPLGPU_ERR_INVALID_ARG;
+  if ((d_labels_out && label_stride < cells) || (d_rows && row_stride < 8ull * row_cap) ||
       (d_goal_out && goal_stride == 0)) {
-    h->err = at + "grid_stride must be >= width * height and a multiple of 4, potential_stride and label_stride >= "
-                  "width * height, row_stride >= 8 row_cap, goal_stride >= 1";
+    h->err = at + "label_stride >= width * height, row_stride >= 8 row_cap and goal_stride >= 1 are required";
     return RPLGPU_ERR_INVALID_ARG;
   }
   rpl::FrLayout l;
@@ -119,10 +92,8 @@ int32_t rplgpu_frontiers(rplgpu_handle_t h, const rplgpu_frontiers_t *f, const i
   const char *fn = "rplgpu_frontiers";
   if (!h || !f || !grid || !result || (row_cap != 0 && !rows) || (!goal_out) != (!n_goal_out))
     return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_frontiers_check(f) != RPLGPU_OK || rplgpu_frontiers_scratch_words(f, 1, comp_cap) == 0) {
-    h->err = std::string(fn) + ": invalid rplgpu_frontiers_t or comp_cap (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (rplgpu_frontiers_check(f) != RPLGPU_OK || rplgpu_frontiers_scratch_words(f, 1, comp_cap) == 0)
+    return refuse_spec(h, fn, "rplgpu_frontiers_t or comp_cap");
   RPL_HIP(h, hipSetDevice(h->device));
   const size_t cells = (size_t)f->width * f->height, stride = (cells + 3u) & ~(size_t)3u;
   const size_t row_bytes = 32u * (size_t)row_cap;
@@ -137,25 +108,21 @@ int32_t rplgpu_frontiers(rplgpu_handle_t h, const rplgpu_frontiers_t *f, const i
   uint32_t words[RPLGPU_FRONTIER_WORDS], goal[2] = {0u, 0u};
   std::vector<uint32_t> row_stage(8u * (size_t)row_cap);
   const int32_t rc = buf.run([&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_grid), grid, cells, hipMemcpyHostToDevice, h->stream));
-    if (potential)
-      RPL_HIP(h, hipMemcpyAsync(buf.at(o_pot), potential, 4u * cells, hipMemcpyHostToDevice, h->stream));
-    if (row_cap) RPL_HIP(h, hipMemcpyAsync(buf.at(o_rows), rows, row_bytes, hipMemcpyHostToDevice, h->stream));
-    if (goal_out) RPL_HIP(h, hipMemcpyAsync(buf.at(o_goal), goal_out, 4, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, buf.put(o_grid, grid, cells));
+    RPL_HIP(h, buf.put(o_pot, potential, 4u * cells));
+    RPL_HIP(h, buf.put(o_rows, rows, row_bytes));
+    RPL_HIP(h, buf.put(o_goal, goal_out, 4));
     const int32_t irc = rplgpu_frontiers_dev(h, f, buf.at<const int8_t>(o_grid), stride,
                                              buf.at<const uint32_t>(o_pot), cells, 1, comp_cap,
                                              buf.at<uint32_t>(o_lab), cells, buf.at<uint32_t>(o_rows),
                                              8ull * row_cap, row_cap, buf.at<uint32_t>(o_goal), 1,
                                              buf.at<uint32_t>(o_n), buf.at<uint32_t>(o_res), buf.at<uint32_t>(o_scr));
     if (irc) return irc;
-    if (labels_out)
-      RPL_HIP(h, hipMemcpyAsync(labels_out, buf.at(o_lab), 4u * cells, hipMemcpyDeviceToHost, h->stream));
-    if (row_cap) RPL_HIP(h, hipMemcpyAsync(row_stage.data(), buf.at(o_rows), row_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (goal_out) {
-      RPL_HIP(h, hipMemcpyAsync(&goal[0], buf.at(o_goal), 4, hipMemcpyDeviceToHost, h->stream));
-      RPL_HIP(h, hipMemcpyAsync(&goal[1], buf.at(o_n), 4, hipMemcpyDeviceToHost, h->stream));
-    }
-    RPL_HIP(h, hipMemcpyAsync(words, buf.at(o_res), sizeof(words), hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, buf.get(labels_out, o_lab, 4u * cells));
+    RPL_HIP(h, buf.get(row_stage.data(), o_rows, row_bytes));
+    RPL_HIP(h, buf.get(&goal[0], o_goal, 4));
+    RPL_HIP(h, buf.get(&goal[1], o_n, 4));
+    RPL_HIP(h, buf.get(words, o_res, sizeof(words)));
     RPL_HIP(h, hipStreamSynchronize(h->stream));
     return RPLGPU_OK;
   });

@@ -2,7 +2,7 @@
 // (include/rplgpu_msg.h), in plain C++: the default, the check, the scratch size, the softmax table and the two host
 // twins, one candidate after the other ("the definition a reader can run").  No handle, no stream, no HIP header; built
 // like rplgpu_rollout_rules.cpp (-ffp-contract=off: no product below fuses with a sum).  The doors that call these are
-// in rplgpu_mppi_stages.hip; tools/dev/mppi_rules_asan.cpp drives this file alone under the host sanitizers.
+// in rplgpu_mppi_stages.hip; tools/dev/plan_rules_asan.cpp drives this file under the host sanitizers.
 #include <algorithm>
 #include <cmath>
 #include <cstring>

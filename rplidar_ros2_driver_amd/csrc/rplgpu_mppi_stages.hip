@@ -21,24 +21,19 @@ using namespace rpl::host;
 
 namespace {
 
-struct Range {
-  const void *p;
-  uint64_t bytes;
-  bool out;
-};
+// K and the steps of an update, which the call and its door take alike
+bool update_counts_ok(rplgpu_ctx *h, const char *fn, uint32_t K, uint32_t T) {
+  return (K != 0 && K <= RPLGPU_MAX_POSES && (uint64_t)K * T <= (1ull << 24)) ||
+         refuse(h, fn, "K must be in 1 .. RPLGPU_MAX_POSES with K * steps <= 2^24");
+}
 
-// no output may share a byte with an input or with another output, but for the pair (skip_a, skip_b) of entries, which
-// the caller has found to be one range read and written element by element
-template <size_t N>
-bool ranges_clash(const Range (&ranges)[N], int skip_a, int skip_b) {
-  for (size_t i = 0; i < N; ++i) {
-    for (size_t j = i + 1; j < N; ++j) {
-      const Range &a = ranges[i], &b = ranges[j];
-      if (!(a.out || b.out) || !a.bytes || !b.bytes || ((int)i == skip_a && (int)j == skip_b)) continue;
-      if (rpl::ranges_overlap(a.p, a.bytes, b.p, b.bytes)) return true;
-    }
-  }
-  return false;
+// K, T, T_n and the shift of a spread, likewise
+bool spread_counts_ok(rplgpu_ctx *h, const char *fn, uint32_t K, uint32_t T, uint32_t T_n, uint32_t shift) {
+  return (K != 0 && K <= RPLGPU_MAX_POSES && T != 0 && T <= RPLGPU_ROLLOUT_MAX_STEPS && T_n != 0 &&
+          T_n <= RPLGPU_ROLLOUT_MAX_STEPS && (uint64_t)K * T <= (1ull << 24) &&
+          shift <= RPLGPU_MPPI_MAX_SPREAD_SHIFT) ||
+         refuse(h, fn, "K must be in 1 .. RPLGPU_MAX_POSES, T and T_n in 1 .. RPLGPU_ROLLOUT_MAX_STEPS with K * T <= "
+                       "2^24, shift at most RPLGPU_MPPI_MAX_SPREAD_SHIFT");
 }
 
 }  // namespace
@@ -52,18 +47,13 @@ int32_t rplgpu_mppi_update_dev(rplgpu_handle_t h, const rplgpu_mppi_t *m, const 
                                uint32_t *d_weights, uint64_t weight_stride, uint32_t *d_sums, uint64_t sums_stride,
                                float *d_nominal_out, uint64_t nominal_out_stride, uint32_t *d_result,
                                uint32_t *d_scratch) {
-  const std::string at = "rplgpu_mppi_update_dev: ";
+  const char *fn = "rplgpu_mppi_update_dev";
+  const std::string at = std::string(fn) + ": ";
   if (!h || !m) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_mppi_check(m) != RPLGPU_OK) {
-    h->err = at + "invalid rplgpu_mppi_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!PoseListDoor{h, "rplgpu_mppi_update_dev"}.groups(G)) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_mppi_check(m) != RPLGPU_OK) return refuse_spec(h, fn, "rplgpu_mppi_t");
+  const PoseListDoor door{h, fn};
   const uint32_t T = m->steps, T_e = m->delta_per_step ? T : 1u;
-  if (K == 0 || K > RPLGPU_MAX_POSES || (uint64_t)K * T > (1ull << 24)) {
-    h->err = at + "K must be in 1 .. RPLGPU_MAX_POSES with K * steps <= 2^24";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!door.groups(G) || !update_counts_ok(h, fn, K, T)) return RPLGPU_ERR_INVALID_ARG;
   if (!d_out || !d_rollout_result || !d_delta || !d_table || !d_weights || !d_sums || !d_nominal_out || !d_result ||
       !d_scratch || misaligned(d_out, 15u) || misaligned(d_delta, 15u) || misaligned(d_nominal, 15u) ||
       misaligned(d_sums, 15u) || misaligned(d_nominal_out, 15u) || misaligned(d_scratch, 15u) ||
@@ -129,14 +119,8 @@ int32_t rplgpu_mppi_update(rplgpu_handle_t h, const rplgpu_mppi_t *m, const uint
   const char *fn = "rplgpu_mppi_update";
   if (!h || !m || !out || !rollout_result || !delta || !table || !weights || !sums || !nominal_out || !result)
     return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_mppi_check(m) != RPLGPU_OK) {
-    h->err = std::string(fn) + ": invalid rplgpu_mppi_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (K == 0 || K > RPLGPU_MAX_POSES || (uint64_t)K * m->steps > (1ull << 24)) {
-    h->err = std::string(fn) + ": K must be in 1 .. RPLGPU_MAX_POSES with K * steps <= 2^24";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (rplgpu_mppi_check(m) != RPLGPU_OK) return refuse_spec(h, fn, "rplgpu_mppi_t");
+  if (!update_counts_ok(h, fn, K, m->steps)) return RPLGPU_ERR_INVALID_ARG;
   RPL_HIP(h, hipSetDevice(h->device));
   const uint32_t T_e = m->delta_per_step ? m->steps : 1u;
   const size_t n_delta = (size_t)K * T_e;
@@ -153,22 +137,21 @@ int32_t rplgpu_mppi_update(rplgpu_handle_t h, const rplgpu_mppi_t *m, const uint
   std::vector<float> nout(4u * (size_t)T_e);
   std::vector<uint32_t> w_stage(K), sums_stage(8u * (size_t)T_e);
   const int32_t rc = buf.run([&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_out), out, 32u * (size_t)K, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_rres), rollout_result, 32, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_delta), delta, 16u * n_delta, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_table), table, 2u * (size_t)m->table_len, hipMemcpyHostToDevice, h->stream));
-    if (nominal)
-      RPL_HIP(h, hipMemcpyAsync(buf.at(o_nom), nominal, 16u * (size_t)T_e, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, buf.put(o_out, out, 32u * (size_t)K));
+    RPL_HIP(h, buf.put(o_rres, rollout_result, 32));
+    RPL_HIP(h, buf.put(o_delta, delta, 16u * n_delta));
+    RPL_HIP(h, buf.put(o_table, table, 2u * (size_t)m->table_len));
+    RPL_HIP(h, buf.put(o_nom, nominal, 16u * (size_t)T_e));
     const int32_t irc = rplgpu_mppi_update_dev(
         h, m, buf.at<const uint32_t>(o_out), 8ull * K, buf.at<const uint32_t>(o_rres), buf.at<const float>(o_delta),
         4ull * n_delta, 0, buf.at<const uint16_t>(o_table), buf.at<const float>(o_nom), 4ull * T_e, 0, 1, K,
         buf.at<uint32_t>(o_w), K, buf.at<uint32_t>(o_sums), 8ull * T_e, buf.at<float>(o_nout), 4ull * T_e,
         buf.at<uint32_t>(o_res), buf.at<uint32_t>(o_scr));
     if (irc) return irc;
-    RPL_HIP(h, hipMemcpyAsync(w_stage.data(), buf.at(o_w), 4u * (size_t)K, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(sums_stage.data(), buf.at(o_sums), 32u * (size_t)T_e, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(nout.data(), buf.at(o_nout), 16u * (size_t)T_e, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(words, buf.at(o_res), 32, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, buf.get(w_stage.data(), o_w, 4u * (size_t)K));
+    RPL_HIP(h, buf.get(sums_stage.data(), o_sums, 32u * (size_t)T_e));
+    RPL_HIP(h, buf.get(nout.data(), o_nout, 16u * (size_t)T_e));
+    RPL_HIP(h, buf.get(words, o_res, 32));
     RPL_HIP(h, hipStreamSynchronize(h->stream));
     return RPLGPU_OK;
   });
@@ -184,15 +167,11 @@ int32_t rplgpu_mppi_spread_dev(rplgpu_handle_t h, const float *d_nominal, uint64
                                uint32_t nominal_per_group, uint32_t T_n, const float *d_noise, uint64_t noise_stride,
                                uint32_t noise_per_group, uint32_t G, uint32_t K, uint32_t T, uint32_t shift,
                                uint32_t keep_first, float *d_out, uint64_t out_stride) {
-  const std::string at = "rplgpu_mppi_spread_dev: ";
+  const char *fn = "rplgpu_mppi_spread_dev";
+  const std::string at = std::string(fn) + ": ";
   if (!h) return RPLGPU_ERR_INVALID_ARG;
-  if (!PoseListDoor{h, "rplgpu_mppi_spread_dev"}.groups(G)) return RPLGPU_ERR_INVALID_ARG;
-  if (K == 0 || K > RPLGPU_MAX_POSES || T == 0 || T > RPLGPU_ROLLOUT_MAX_STEPS || T_n == 0 ||
-      T_n > RPLGPU_ROLLOUT_MAX_STEPS || (uint64_t)K * T > (1ull << 24) || shift > RPLGPU_MPPI_MAX_SPREAD_SHIFT) {
-    h->err = at + "K must be in 1 .. RPLGPU_MAX_POSES, T and T_n in 1 .. RPLGPU_ROLLOUT_MAX_STEPS with K * T <= 2^24, "
-                  "shift at most RPLGPU_MPPI_MAX_SPREAD_SHIFT";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  const PoseListDoor door{h, fn};
+  if (!door.groups(G) || !spread_counts_ok(h, fn, K, T, T_n, shift)) return RPLGPU_ERR_INVALID_ARG;
   if (!d_nominal || !d_noise || !d_out || misaligned(d_nominal, 15u) || misaligned(d_noise, 15u) ||
       misaligned(d_out, 15u)) {
     h->err = at + "a pointer is missing or not 16-byte aligned";
@@ -230,23 +209,19 @@ int32_t rplgpu_mppi_spread(rplgpu_handle_t h, const float *nominal, uint32_t T_n
                            uint32_t T, uint32_t shift, uint32_t keep_first, float *out) {
   const char *fn = "rplgpu_mppi_spread";
   if (!h || !nominal || !noise || !out) return RPLGPU_ERR_INVALID_ARG;
-  if (K == 0 || K > RPLGPU_MAX_POSES || T == 0 || T > RPLGPU_ROLLOUT_MAX_STEPS || T_n == 0 ||
-      T_n > RPLGPU_ROLLOUT_MAX_STEPS || (uint64_t)K * T > (1ull << 24) || shift > RPLGPU_MPPI_MAX_SPREAD_SHIFT) {
-    h->err = std::string(fn) + ": K, T, T_n or shift out of range (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!spread_counts_ok(h, fn, K, T, T_n, shift)) return RPLGPU_ERR_INVALID_ARG;
   RPL_HIP(h, hipSetDevice(h->device));
   const size_t n = (size_t)K * T;
   DoorBuffer buf(h, fn);  // nominal | noise, spread in place
   const size_t o_nom = buf.part(16u * (size_t)T_n), o_noise = buf.part(16u * n);
   return buf.run([&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_nom), nominal, 16u * (size_t)T_n, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_noise), noise, 16u * n, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, buf.put(o_nom, nominal, 16u * (size_t)T_n));
+    RPL_HIP(h, buf.put(o_noise, noise, 16u * n));
     const int32_t irc = rplgpu_mppi_spread_dev(h, buf.at<const float>(o_nom), 4ull * T_n, 0, T_n,
                                                buf.at<const float>(o_noise), 4ull * n, 0, 1, K, T, shift, keep_first,
                                                buf.at<float>(o_noise), 4ull * n);
     if (irc) return irc;
-    RPL_HIP(h, hipMemcpyAsync(out, buf.at(o_noise), 16u * n, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, buf.get(out, o_noise, 16u * n));
     RPL_HIP(h, hipStreamSynchronize(h->stream));
     return RPLGPU_OK;
   });

@@ -2,7 +2,7 @@
 // (include/rplgpu_msg.h), in plain C++: the default, the check, the default rounds, the scratch size and the host
 // twins — a binary-heap Dijkstra from the goals ("the definition a reader can run") and the downhill walk.  No
 // handle, no stream, no HIP header; built like rplgpu_pose_rules.cpp.  The doors that call these are in
-// rplgpu_nav_stages.hip; tools/dev/nav_rules_asan.cpp drives this file alone under the host sanitizers.
+// rplgpu_nav_stages.hip; tools/dev/plan_rules_asan.cpp drives this file under the host sanitizers.
 #include <algorithm>
 #include <cstring>
 #include <functional>
@@ -12,27 +12,19 @@
 
 #include "rplgpu.h"
 #include "rplgpu_msg.h"
+#include "rpl_rules.hpp"
 
 namespace {
 
 const int kDx[8] = {1, -1, 0, 0, 1, -1, 1, -1};
 const int kDy[8] = {0, 0, 1, -1, 1, 1, -1, -1};
 
-uint32_t tiles_of(uint32_t cells) { return (cells + RPLGPU_NAV_TILE - 1u) / RPLGPU_NAV_TILE; }
-
-// the weight of a byte, 0: impassable
-uint32_t weight_of(const rplgpu_nav_field_t *f, int8_t v) {
-  if (v < 0) return f->unknown_cost;
-  if ((uint32_t)v >= f->lethal) return 0;
-  return f->neutral + f->factor * (uint32_t)v;
-}
-
 struct Grid {
   const rplgpu_nav_field_t *f;
   const int8_t *bytes;
   int w, h;
   bool inside(int x, int y) const { return x >= 0 && y >= 0 && x < w && y < h; }
-  uint32_t weight(int x, int y) const { return weight_of(f, bytes[(size_t)y * w + x]); }
+  uint32_t weight(int x, int y) const { return rpl::nav_byte_weight(*f, bytes[(size_t)y * w + x]); }
   // the step `dir` from (x, y): the neighbour inside the grid, (x, y) passable, no corner cut
   bool allowed(int x, int y, int dir) const {
     const int nx = x + kDx[dir], ny = y + kDy[dir];
@@ -47,7 +39,9 @@ extern "C" {
 
 uint32_t rplgpu_nav_field_default_rounds(uint32_t width, uint32_t height) {
   if (width == 0 || width > RPLGPU_MAX_OCC_DIM || height == 0 || height > RPLGPU_MAX_OCC_DIM) return 0;
-  return 2u * (tiles_of(width) + tiles_of(height)) + 2u;
+  uint32_t tiles_x, tiles_y;
+  (void)rpl::nav_tiles(width, height, 1, &tiles_x, &tiles_y);
+  return 2u * (tiles_x + tiles_y) + 2u;
 }
 
 void rplgpu_default_nav_field(rplgpu_nav_field_t *f) {
@@ -76,9 +70,9 @@ int32_t rplgpu_nav_field_check(const rplgpu_nav_field_t *f) {
 
 uint64_t rplgpu_nav_field_scratch_words(const rplgpu_nav_field_t *f, uint32_t G) {
   if (rplgpu_nav_field_check(f) != RPLGPU_OK || G == 0) return 0;
-  const uint64_t tiles = (uint64_t)tiles_of(f->width) * tiles_of(f->height);
-  if (G * tiles > RPLGPU_NAV_MAX_TILES) return 0;
-  return 2ull * tiles * G;
+  uint32_t tiles_x, tiles_y;
+  if (!rpl::nav_tiles(f->width, f->height, G, &tiles_x, &tiles_y)) return 0;
+  return 2ull * tiles_x * tiles_y * G;
 }
 
 int32_t rplgpu_nav_field_host(const rplgpu_nav_field_t *f, const int8_t *grid, const uint32_t *goals,

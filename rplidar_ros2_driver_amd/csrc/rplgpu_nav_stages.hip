@@ -21,28 +21,20 @@ using namespace rpl::host;
 namespace {
 
 rpl::NavK nav_k(const rplgpu_nav_field_t *f) {
-  return rpl::NavK{f->width,        f->height, f->lethal, f->neutral, f->factor,
-                   f->unknown_cost, f->cap,    (f->width + RPLGPU_NAV_TILE - 1u) / RPLGPU_NAV_TILE,
-                   (f->height + RPLGPU_NAV_TILE - 1u) / RPLGPU_NAV_TILE};
+  rpl::NavK k{f->width, f->height, f->lethal, f->neutral, f->factor, f->unknown_cost, f->cap, 0u, 0u};
+  (void)rpl::nav_tiles(f->width, f->height, 1, &k.tiles_x, &k.tiles_y);
+  return k;
 }
 
-// the spec, the grids and the fields, which both calls take alike
-int32_t planes_check(rplgpu_handle_t h, const char *fn, const rplgpu_nav_field_t *f, const int8_t *d_grid,
-                     uint64_t grid_stride, const uint32_t *d_potential, uint64_t potential_stride, uint32_t G) {
-  const std::string at = std::string(fn) + ": ";
+// the spec, the groups, the grids and the fields, which both calls take alike
+int32_t field_check(rplgpu_handle_t h, const char *fn, const rplgpu_nav_field_t *f, const int8_t *d_grid,
+                    uint64_t grid_stride, const uint32_t *d_potential, uint64_t potential_stride, uint32_t G) {
   if (!f || !d_grid || !d_potential) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_nav_field_check(f) != RPLGPU_OK) {
-    h->err = at + "invalid rplgpu_nav_field_t (see include/rplgpu_msg.h)";
+  if (rplgpu_nav_field_check(f) != RPLGPU_OK) return refuse_spec(h, fn, "rplgpu_nav_field_t");
+  const PoseListDoor door{h, fn};
+  if (!door.groups(G) ||
+      !planes_ok(h, fn, (uint64_t)f->width * f->height, d_grid, grid_stride, d_potential, potential_stride))
     return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!PoseListDoor{h, fn}.groups(G)) return RPLGPU_ERR_INVALID_ARG;
-  const uint64_t cells = (uint64_t)f->width * f->height;
-  if (grid_stride < cells || (grid_stride & 3u) || misaligned(d_grid, 3u) || potential_stride < cells ||
-      misaligned(d_potential, 3u)) {
-    h->err = at + "grid_stride must be >= width * height and a multiple of 4, potential_stride >= width * height, "
-                  "both pointers 4-byte aligned";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
   return RPLGPU_OK;
 }
 
@@ -56,7 +48,7 @@ int32_t rplgpu_nav_field_dev(rplgpu_handle_t h, const rplgpu_nav_field_t *f, con
                              uint32_t *d_scratch, uint32_t resume, uint32_t *d_result) {
   const char *fn = "rplgpu_nav_field_dev";
   if (!h) return RPLGPU_ERR_INVALID_ARG;
-  if (int32_t rc = planes_check(h, fn, f, d_grid, grid_stride, d_potential, potential_stride, G)) return rc;
+  if (int32_t rc = field_check(h, fn, f, d_grid, grid_stride, d_potential, potential_stride, G)) return rc;
   if (!d_goals || !d_n_goals || !d_scratch || !d_result || resume > 1u) {
     h->err = std::string(fn) + ": d_goals, d_n_goals, d_scratch and d_result must be given and resume be 0 or 1";
     return RPLGPU_ERR_INVALID_ARG;
@@ -92,7 +84,7 @@ int32_t rplgpu_nav_paths_dev(rplgpu_handle_t h, const rplgpu_nav_field_t *f, con
                              uint32_t *d_info) {
   const char *fn = "rplgpu_nav_paths_dev";
   if (!h) return RPLGPU_ERR_INVALID_ARG;
-  if (int32_t rc = planes_check(h, fn, f, d_grid, grid_stride, d_potential, potential_stride, G)) return rc;
+  if (int32_t rc = field_check(h, fn, f, d_grid, grid_stride, d_potential, potential_stride, G)) return rc;
   if (!d_starts || !d_paths || !d_info || S == 0 || S > RPLGPU_NAV_MAX_STARTS || max_len == 0) {
     h->err = std::string(fn) + ": d_starts, d_paths and d_info must be given, S be 1 .. RPLGPU_NAV_MAX_STARTS, max_len >= 1";
     return RPLGPU_ERR_INVALID_ARG;
@@ -115,10 +107,7 @@ int32_t rplgpu_nav_field(rplgpu_handle_t h, const rplgpu_nav_field_t *f, const i
                          uint32_t S, uint32_t *paths, uint32_t max_len, uint32_t *info) {
   const char *fn = "rplgpu_nav_field";
   if (!h || !f || !grid || !potential || !result || (n_goals != 0 && !goals)) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_nav_field_check(f) != RPLGPU_OK) {
-    h->err = std::string(fn) + ": invalid rplgpu_nav_field_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (rplgpu_nav_field_check(f) != RPLGPU_OK) return refuse_spec(h, fn, "rplgpu_nav_field_t");
   if (starts && (!paths || !info || S == 0 || S > RPLGPU_NAV_MAX_STARTS || max_len == 0)) {
     h->err = std::string(fn) + ": with starts, paths and info must be given, S be 1 .. RPLGPU_NAV_MAX_STARTS, max_len >= 1";
     return RPLGPU_ERR_INVALID_ARG;
@@ -135,9 +124,9 @@ int32_t rplgpu_nav_field(rplgpu_handle_t h, const rplgpu_nav_field_t *f, const i
   const size_t o_info = buf.part_if(starts, 16u * (size_t)S);
   uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int32_t rc = buf.run([&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_grid), grid, cells, hipMemcpyHostToDevice, h->stream));
-    if (n_goals) RPL_HIP(h, hipMemcpyAsync(buf.at(o_goals), goals, 4u * (size_t)n_goals, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_n), &n_goals, 4, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, buf.put(o_grid, grid, cells));
+    RPL_HIP(h, buf.put(o_goals, goals, 4u * (size_t)n_goals));
+    RPL_HIP(h, buf.put(o_n, &n_goals, 4));
     uint32_t visits = 0, rounds = 0;
     for (uint32_t call = 0; call < 64u; ++call) {
       const int32_t irc = rplgpu_nav_field_dev(h, f, buf.at<const int8_t>(o_grid), stride, 1,
@@ -145,7 +134,7 @@ int32_t rplgpu_nav_field(rplgpu_handle_t h, const rplgpu_nav_field_t *f, const i
                                                buf.at<const uint32_t>(o_n), buf.at<uint32_t>(o_pot), cells,
                                                buf.at<uint32_t>(o_scr), call ? 1u : 0u, buf.at<uint32_t>(o_res));
       if (irc) return irc;
-      RPL_HIP(h, hipMemcpyAsync(words, buf.at(o_res), 32, hipMemcpyDeviceToHost, h->stream));
+      RPL_HIP(h, buf.get(words, o_res, 32));
       RPL_HIP(h, hipStreamSynchronize(h->stream));
       visits += words[6];
       rounds += words[7];
@@ -153,17 +142,17 @@ int32_t rplgpu_nav_field(rplgpu_handle_t h, const rplgpu_nav_field_t *f, const i
     }
     words[6] = visits;
     words[7] = rounds;
-    RPL_HIP(h, hipMemcpyAsync(potential, buf.at(o_pot), 4u * cells, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, buf.get(potential, o_pot, 4u * cells));
     if (starts) {
-      RPL_HIP(h, hipMemcpyAsync(buf.at(o_starts), starts, 4u * (size_t)S, hipMemcpyHostToDevice, h->stream));
-      RPL_HIP(h, hipMemcpyAsync(buf.at(o_paths), paths, path_bytes, hipMemcpyHostToDevice, h->stream));
+      RPL_HIP(h, buf.put(o_starts, starts, 4u * (size_t)S));
+      RPL_HIP(h, buf.put(o_paths, paths, path_bytes));
       const int32_t prc = rplgpu_nav_paths_dev(h, f, buf.at<const int8_t>(o_grid), stride,
                                                buf.at<const uint32_t>(o_pot), cells, 1,
                                                buf.at<const uint32_t>(o_starts), S, buf.at<uint32_t>(o_paths), max_len,
                                                buf.at<uint32_t>(o_info));
       if (prc) return prc;
-      RPL_HIP(h, hipMemcpyAsync(paths, buf.at(o_paths), path_bytes, hipMemcpyDeviceToHost, h->stream));
-      RPL_HIP(h, hipMemcpyAsync(info, buf.at(o_info), 16u * (size_t)S, hipMemcpyDeviceToHost, h->stream));
+      RPL_HIP(h, buf.get(paths, o_paths, path_bytes));
+      RPL_HIP(h, buf.get(info, o_info, 16u * (size_t)S));
     }
     RPL_HIP(h, hipStreamSynchronize(h->stream));
     return RPLGPU_OK;

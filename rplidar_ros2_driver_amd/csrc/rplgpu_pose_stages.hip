@@ -618,11 +618,6 @@ int32_t rplgpu_cluster_poses_dev(rplgpu_handle_t h, const rplgpu_pose_clusters_t
   }
   // no output may share a byte with an input or with another output
   const uint64_t scratch_words = rplgpu_cluster_scratch_words(G, P, s->nx, s->ny, T);
-  struct Range {
-    const void *p;
-    uint64_t bytes;
-    bool out;
-  };
   const Range ranges[] = {
       {d_poses, 4ull * ((poses_per_group ? (uint64_t)(G - 1u) * pose_stride : 0ull) + 4ull * P), false},
       {d_weights, d_weights ? 4ull * ((uint64_t)(G - 1u) * weight_stride + P) : 0ull, false},
@@ -632,13 +627,9 @@ int32_t rplgpu_cluster_poses_dev(rplgpu_handle_t h, const rplgpu_pose_clusters_t
       {d_clusters, table ? 4ull * ((uint64_t)(G - 1u) * cluster_stride + 4ull * cluster_cap) : 0ull, true},
       {d_result, 4ull * RPLGPU_CLUSTER_WORDS * G, true},
       {d_scratch, 4ull * scratch_words, true}};
-  for (const Range &a : ranges) {
-    for (const Range &b : ranges) {
-      if (&a < &b && (a.out || b.out) && a.bytes && b.bytes && rpl::ranges_overlap(a.p, a.bytes, b.p, b.bytes)) {
-        h->err = "rplgpu_cluster_poses_dev: an output overlaps an input or another output";
-        return RPLGPU_ERR_INVALID_ARG;
-      }
-    }
+  if (ranges_clash(ranges)) {
+    h->err = "rplgpu_cluster_poses_dev: an output overlaps an input or another output";
+    return RPLGPU_ERR_INVALID_ARG;
   }
   if (!device_readable(h, {{d_poses, "d_poses", true}, {d_map, "d_map", true}, {d_bins, "d_bins", true},
                            {d_result, "d_result", true}, {d_scratch, "d_scratch", true},

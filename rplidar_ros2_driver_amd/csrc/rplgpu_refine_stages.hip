@@ -26,11 +26,6 @@ rpl::RefineK refine_k(const rplgpu_pose_refine_t *r) {
                       r->target,   r->damping,  r->max_step_cells, r->max_rot, r->min_points};
 }
 
-bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // what the sums take, in E15's order behind check_batch
 int32_t sums_args_check(rplgpu_handle_t h, const char *fn, const rplgpu_pose_refine_t *r, uint32_t group,
                         const float *d_poses, uint32_t P, uint64_t pose_stride, const int8_t *d_field,
@@ -86,7 +81,7 @@ int32_t step_args_check(rplgpu_handle_t h, const char *fn, const rplgpu_pose_ref
   const uint64_t in_bytes = 4u * ((uint64_t)(poses_per_group ? G - 1u : 0u) * pose_stride + 4ull * P);
   const uint64_t out_bytes = 4u * ((uint64_t)(G - 1u) * out_stride + 4ull * P);
   const bool in_place = d_poses_out == d_poses && out_stride == pose_stride && (poses_per_group || G == 1u);
-  if (!in_place && ranges_overlap(d_poses, in_bytes, d_poses_out, out_bytes)) {
+  if (!in_place && rpl::ranges_overlap(d_poses, in_bytes, d_poses_out, out_bytes)) {
     h->err = at + "d_poses_out overlaps d_poses (allowed only in place: equal pointers and strides, every group its own list)";
     return RPLGPU_ERR_INVALID_ARG;
   }

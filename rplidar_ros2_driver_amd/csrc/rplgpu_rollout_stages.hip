@@ -17,6 +17,18 @@
 
 using namespace rpl::host;
 
+namespace {
+
+// K, the steps, F and delta_per_step, which the call and its door take alike
+bool counts_ok(rplgpu_ctx *h, const char *fn, uint32_t K, uint32_t T, uint32_t F, uint32_t delta_per_step) {
+  return (K != 0 && K <= RPLGPU_MAX_POSES && (uint64_t)K * T <= (1ull << 24) && F != 0 &&
+          F <= RPLGPU_ROLLOUT_MAX_FOOTPRINT && delta_per_step <= 1u) ||
+         refuse(h, fn, "K must be in 1 .. RPLGPU_MAX_POSES with K * steps <= 2^24, F in 1 .. "
+                       "RPLGPU_ROLLOUT_MAX_FOOTPRINT, delta_per_step 0 or 1");
+}
+
+}  // namespace
+
 extern "C" {
 
 int32_t rplgpu_rollout_dev(rplgpu_handle_t h, const rplgpu_rollout_t *r, const float *d_start,
@@ -26,47 +38,32 @@ int32_t rplgpu_rollout_dev(rplgpu_handle_t h, const rplgpu_rollout_t *r, const f
                            uint64_t potential_stride, uint32_t grid_per_group, uint32_t G, uint32_t K,
                            uint32_t *d_out, uint64_t out_stride, float *d_end_poses, uint64_t end_stride,
                            uint32_t *d_result, uint32_t *d_scratch) {
-  const std::string at = "rplgpu_rollout_dev: ";
+  const char *fn = "rplgpu_rollout_dev";
   if (!h || !r) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_rollout_check(r) != RPLGPU_OK) {
-    h->err = at + "invalid rplgpu_rollout_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (!PoseListDoor{h, "rplgpu_rollout_dev"}.groups(G)) return RPLGPU_ERR_INVALID_ARG;
+  if (rplgpu_rollout_check(r) != RPLGPU_OK) return refuse_spec(h, fn, "rplgpu_rollout_t");
+  const PoseListDoor door{h, fn};
   const uint32_t T = r->steps;
-  if (K == 0 || K > RPLGPU_MAX_POSES || (uint64_t)K * T > (1ull << 24) || F == 0 ||
-      F > RPLGPU_ROLLOUT_MAX_FOOTPRINT || delta_per_step > 1u) {
-    h->err = at + "K must be in 1 .. RPLGPU_MAX_POSES with K * steps <= 2^24, F in 1 .. RPLGPU_ROLLOUT_MAX_FOOTPRINT, "
-                  "delta_per_step 0 or 1";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (!door.groups(G) || !counts_ok(h, fn, K, T, F, delta_per_step)) return RPLGPU_ERR_INVALID_ARG;
   if (!d_start || !d_delta || !d_footprint || !d_grid || !d_out || !d_result || !d_scratch ||
       misaligned(d_start, 15u) || misaligned(d_delta, 15u) || misaligned(d_out, 15u) || misaligned(d_end_poses, 15u) ||
-      misaligned(d_scratch, 15u) || misaligned(d_footprint, 7u) || misaligned(d_grid, 3u) ||
-      misaligned(d_potential, 3u) || misaligned(d_result, 3u)) {
-    h->err = at + "a required pointer is missing or a pointer is misaligned (16 bytes: d_start, d_delta, d_out, "
-                  "d_end_poses, d_scratch; 8: d_footprint; 4: the others)";
+      misaligned(d_scratch, 15u) || misaligned(d_footprint, 7u) || misaligned(d_result, 3u)) {
+    refuse(h, fn, "a required pointer is missing or a pointer is misaligned (16 bytes: d_start, d_delta, d_out, "
+                  "d_end_poses, d_scratch; 8: d_footprint; 4: d_result)");
     return RPLGPU_ERR_INVALID_ARG;
   }
   const uint64_t cells = (uint64_t)r->width * r->height, n_delta = (uint64_t)K * (delta_per_step ? T : 1u);
-  if (delta_stride < 4ull * n_delta || (delta_stride & 3u) || grid_stride < cells || (grid_stride & 3u) ||
-      (d_potential && potential_stride < cells) || out_stride < 8ull * K || (out_stride & 3u) ||
+  if (!planes_ok(h, fn, cells, d_grid, grid_stride, d_potential, potential_stride)) return RPLGPU_ERR_INVALID_ARG;
+  if (delta_stride < 4ull * n_delta || (delta_stride & 3u) || out_stride < 8ull * K || (out_stride & 3u) ||
       (d_end_poses && (end_stride < 4ull * K || (end_stride & 3u)))) {
-    h->err = at + "delta_stride >= 4 K (4 K steps per step), grid_stride >= width * height, out_stride >= 8 K, "
-                  "end_stride >= 4 K (all multiples of 4) and potential_stride >= width * height are required";
+    refuse(h, fn, "delta_stride >= 4 K (4 K steps per step), out_stride >= 8 K and end_stride >= 4 K (all multiples "
+                  "of 4) are required");
     return RPLGPU_ERR_INVALID_ARG;
   }
   const uint64_t scratch_words = rplgpu_rollout_scratch_words(G, K);
   if (scratch_words == 0) {
-    h->err = at + "G x tiles above RPLGPU_ROLLOUT_MAX_TILES";
+    refuse(h, fn, "G x tiles above RPLGPU_ROLLOUT_MAX_TILES");
     return RPLGPU_ERR_CAPACITY;
   }
-  // no output may share a byte with an input or with another output
-  struct Range {
-    const void *p;
-    uint64_t bytes;
-    bool out;
-  };
   const uint64_t last = G - 1u, maps = grid_per_group ? last : 0ull;
   const Range ranges[] = {
       {d_start, 16ull * (start_per_group ? G : 1u), false},
@@ -78,13 +75,9 @@ int32_t rplgpu_rollout_dev(rplgpu_handle_t h, const rplgpu_rollout_t *r, const f
       {d_end_poses, d_end_poses ? 4ull * (last * end_stride + 4ull * K) : 0ull, true},
       {d_result, 32ull * G, true},
       {d_scratch, 4ull * scratch_words, true}};
-  for (const Range &a : ranges) {
-    for (const Range &b : ranges) {
-      if (&a < &b && (a.out || b.out) && a.bytes && b.bytes && rpl::ranges_overlap(a.p, a.bytes, b.p, b.bytes)) {
-        h->err = at + "an output overlaps an input or another output";
-        return RPLGPU_ERR_INVALID_ARG;
-      }
-    }
+  if (ranges_clash(ranges)) {
+    refuse(h, fn, "an output overlaps an input or another output");
+    return RPLGPU_ERR_INVALID_ARG;
   }
   if (!device_readable(h, {{d_start, "d_start", true}, {d_delta, "d_delta", true}, {d_footprint, "d_footprint", true},
                            {d_grid, "d_grid", true}, {d_out, "d_out", true}, {d_result, "d_result", true},
@@ -106,16 +99,8 @@ int32_t rplgpu_rollout(rplgpu_handle_t h, const rplgpu_rollout_t *r, const float
                        const uint32_t *potential, uint32_t K, uint32_t *out, float *end_poses, uint32_t result[8]) {
   const char *fn = "rplgpu_rollout";
   if (!h || !r || !start || !delta || !footprint || !grid || !out || !result) return RPLGPU_ERR_INVALID_ARG;
-  if (rplgpu_rollout_check(r) != RPLGPU_OK) {
-    h->err = std::string(fn) + ": invalid rplgpu_rollout_t (see include/rplgpu_msg.h)";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
-  if (K == 0 || K > RPLGPU_MAX_POSES || (uint64_t)K * r->steps > (1ull << 24) || F == 0 ||
-      F > RPLGPU_ROLLOUT_MAX_FOOTPRINT || delta_per_step > 1u) {
-    h->err = std::string(fn) + ": K must be in 1 .. RPLGPU_MAX_POSES with K * steps <= 2^24, F in 1 .. "
-                               "RPLGPU_ROLLOUT_MAX_FOOTPRINT, delta_per_step 0 or 1";
-    return RPLGPU_ERR_INVALID_ARG;
-  }
+  if (rplgpu_rollout_check(r) != RPLGPU_OK) return refuse_spec(h, fn, "rplgpu_rollout_t");
+  if (!counts_ok(h, fn, K, r->steps, F, delta_per_step)) return RPLGPU_ERR_INVALID_ARG;
   RPL_HIP(h, hipSetDevice(h->device));
   const size_t cells = (size_t)r->width * r->height, stride = (cells + 3u) & ~(size_t)3u;
   const size_t n_delta = (size_t)K * (delta_per_step ? r->steps : 1u);
@@ -127,22 +112,20 @@ int32_t rplgpu_rollout(rplgpu_handle_t h, const rplgpu_rollout_t *r, const float
   const size_t o_res = buf.part(32), o_scr = buf.part(4u * (size_t)rplgpu_rollout_scratch_words(1, K));
   uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int32_t rc = buf.run([&]() -> int32_t {
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_start), start, 16, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_delta), delta, 16u * n_delta, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_fp), footprint, 8u * (size_t)F, hipMemcpyHostToDevice, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(buf.at(o_grid), grid, cells, hipMemcpyHostToDevice, h->stream));
-    if (potential)
-      RPL_HIP(h, hipMemcpyAsync(buf.at(o_pot), potential, 4u * cells, hipMemcpyHostToDevice, h->stream));
+    RPL_HIP(h, buf.put(o_start, start, 16));
+    RPL_HIP(h, buf.put(o_delta, delta, 16u * n_delta));
+    RPL_HIP(h, buf.put(o_fp, footprint, 8u * (size_t)F));
+    RPL_HIP(h, buf.put(o_grid, grid, cells));
+    RPL_HIP(h, buf.put(o_pot, potential, 4u * cells));
     const int32_t irc = rplgpu_rollout_dev(
         h, r, buf.at<const float>(o_start), 0, buf.at<const float>(o_delta), 4u * n_delta, 0, delta_per_step,
         buf.at<const float>(o_fp), F, buf.at<const int8_t>(o_grid), stride, buf.at<const uint32_t>(o_pot), cells, 0,
         1, K, buf.at<uint32_t>(o_out), 8ull * K, buf.at<float>(o_end), 4ull * K, buf.at<uint32_t>(o_res),
         buf.at<uint32_t>(o_scr));
     if (irc) return irc;
-    RPL_HIP(h, hipMemcpyAsync(out, buf.at(o_out), 32u * (size_t)K, hipMemcpyDeviceToHost, h->stream));
-    if (end_poses)
-      RPL_HIP(h, hipMemcpyAsync(end_poses, buf.at(o_end), 16u * (size_t)K, hipMemcpyDeviceToHost, h->stream));
-    RPL_HIP(h, hipMemcpyAsync(words, buf.at(o_res), 32, hipMemcpyDeviceToHost, h->stream));
+    RPL_HIP(h, buf.get(out, o_out, 32u * (size_t)K));
+    RPL_HIP(h, buf.get(end_poses, o_end, 16u * (size_t)K));
+    RPL_HIP(h, buf.get(words, o_res, 32));
     RPL_HIP(h, hipStreamSynchronize(h->stream));
     return RPLGPU_OK;
   });

@@ -33,12 +33,6 @@ uint64_t pooled_cells(const rplgpu_wide_match_t *m) {
   return (uint64_t)(m->width + RPLGPU_WIDE_MATCH_BLOCK - 1u) * (m->height + RPLGPU_WIDE_MATCH_BLOCK - 1u);
 }
 
-// the fields and their pooled fields must not overlap: F of each, a stride apart
-bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 int32_t pool_impl(rplgpu_handle_t h, const rplgpu_wide_match_t *m, const int8_t *d_field, uint64_t field_stride,
                   uint32_t F, int8_t *d_pooled, uint64_t pooled_stride) {
   if (!m || !d_field || !d_pooled) return RPLGPU_ERR_INVALID_ARG;
@@ -59,8 +53,8 @@ int32_t pool_impl(rplgpu_handle_t h, const rplgpu_wide_match_t *m, const int8_t 
     return RPLGPU_ERR_INVALID_ARG;
   }
   if (F == 0) return RPLGPU_OK;
-  if (ranges_overlap(d_field, (uint64_t)(F - 1u) * field_stride + (uint64_t)m->width * m->height, d_pooled,
-                     (uint64_t)(F - 1u) * pooled_stride + pooled_cells(m))) {
+  if (rpl::ranges_overlap(d_field, (uint64_t)(F - 1u) * field_stride + (uint64_t)m->width * m->height, d_pooled,
+                          (uint64_t)(F - 1u) * pooled_stride + pooled_cells(m))) {
     h->err = "rplgpu_pool_field_dev: d_pooled overlaps d_field";
     return RPLGPU_ERR_INVALID_ARG;
   }
